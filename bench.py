@@ -11,9 +11,18 @@ of Swarm-v0 envs (BASELINE configs[2]: 32 768 envs per GPU, 84x84x3 observation,
        SwarmEnv.step, TimeLimit, auto-reset, process_state]  + bootstrap forward + n-step returns
   + loss/backward over the T*E*10 samples + [RCCL all-reduce of the gradient] + clip + Adam.
 Everything is resident in HBM when the timed region starts; nothing crosses PCIe inside it.
-`value` = env-steps/s of that full update (policy forward AND training included).  The same JSON
-line also carries, measured in the same run: `rollout_only` (no training) and `env_only` (random
-Gaussian policy: the env/observation/returns kernels alone).
+`value` = env-steps/s of that full update (policy forward AND training included); `ms_per_step` = ms of one timed update.
+
+A plain run does only that: set up, warm up (--warmup updates), time --steps updates, write the outputs (--dump-outputs DIR)
+and print the line.  --full adds everything else, measured in the same run: `rollout_only` (no training), `env_only` (random
+Gaussian policy: the env/observation/returns kernels alone), the GEMM / env-step rooflines, the host-thread and communicator
+figures, the dense_form / interior_policy / shard legs, the Solow / TradeAR1 blocks and the CPU baseline (the --no-* flags
+leave parts of it out).
+
+--dump-outputs DIR: after the timed updates, what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB): the
+parameters after the update, its loss statistics, a fixed seeded sample of the rollout's actions / values / rewards / returns /
+advantages / bootstrap values and of the envs' state.  Seeds are fixed, so the same arguments give the same inputs every run.
+For N>1 rank 0 writes its own shard.
 
 Envs are independent, so N GPUs shard the env batch (global env ids key the generators; results do
 not depend on N); the only collective is one all-reduce of the 2.2M-float gradient per update.
@@ -56,6 +65,10 @@ MFMA_X3_PEAK_TFLOPS = MFMA_F16_PEAK_TFLOPS / F16_PRODUCTS_PER_FP32
 GEMM_TRAFFIC_FILE = "r05_gemm_traffic.json"   # PMC pass of the GEMM kernels (tools/run_prof.sh); refreshed per round
 GEMM_TRAFFIC_FILE_INTERIOR = "r05_gemm_traffic_interior.json"   # the same pass on the interior_policy state distribution
 SHARD_ENVS = 4096                             # 32 768 / 8: one GPU's share of BASELINE's target shape (strong scaling)
+DUMP_SEED = 20240                             # --dump-outputs: the seed of the row / env samples
+DUMP_ROLLOUT_BYTES = 32 << 20                 # --dump-outputs: budget of the sampled rollout arrays (24 B per agent-sample and step)
+DUMP_ENVS = 2048                              # --dump-outputs: envs whose state is written
+DUMP_MAX_BYTES = 64 * 10 ** 6
 
 
 def parse():
@@ -71,20 +84,28 @@ def parse():
     ap.add_argument("--fast-math", action="store_true", help="GRL_F_SWARM_FAST_MATH (not the parity default)")
     ap.add_argument("--single-stream", action="store_true",
                     help="GRL_NET_F_SINGLE_STREAM: every chunk on one stream (for rocprofv3 passes: clean per-kernel durations)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the rollout_only / env_only side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement and check (rooflines, host / communicator figures, rollout_only / env_only, "
+                         "legs, shard, flat configs, strong scaling, CPU baseline); a plain run times the update alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed update computed to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip rollout_only / env_only, the legs, the shard leg and the flat configs")
     ap.add_argument("--cpu-sample-envs", type=int, default=2048)
-    ap.add_argument("--no-strong", action="store_true", help="N>1: skip the strong-scaling point (32 768 envs in total)")
+    ap.add_argument("--no-strong", action="store_true", help="with --full, N>1: skip the strong-scaling point (32 768 envs in total)")
     ap.add_argument("--interior", action="store_true",
                     help="profiling aid: run the main measurement on the interior_policy state distribution (agents re-injected into the "
                          "interior of the box before every update, outside the clock)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the dense_form / interior_policy legs (two more 32 768-env jobs)")
-    ap.add_argument("--no-shard", action="store_true", help="skip the strong-scaling shard leg (the full update at 32 768 / 8 envs)")
-    ap.add_argument("--no-flat-configs", action="store_true", help="skip the Solow-4096 / TradeAR1-16 side blocks (configs 2 and 5)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the dense_form / interior_policy legs (two more 32 768-env jobs)")
+    ap.add_argument("--no-shard", action="store_true", help="with --full: skip the strong-scaling shard leg (the full update at 32 768 / 8 envs)")
+    ap.add_argument("--no-flat-configs", action="store_true", help="with --full: skip the Solow-4096 / TradeAR1-16 side blocks (configs 2 and 5)")
     ap.add_argument("--exchange", default="rccl", choices=["rccl", "host"],
                     help="gradient exchange for N>1: RCCL all-reduce inside the library (falls back together if any rank cannot "
                          "form the communicator), or the host-store path outright")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class RandomPolicyRollout(object):
@@ -246,6 +267,41 @@ def spread(per_s):
     return {"median": med * 1e3, "min": a[0] * 1e3, "max": a[-1] * 1e3, "n": n}
 
 
+def dump_outputs(out_dir, eng, roll, net, T):
+    """--dump-outputs: what the last timed update computed, as DIR/<name>.npy.  Conv policy: the parameters after the update, its
+    statistics (loss, policy_loss, critic_loss_mean, global_norm), and the rollout buffers (T, E*10 agent-samples) on a fixed seeded
+    sample of agent-sample rows; random policy: its rewards / returns / advantages (a seeded sample of envs beyond the budget).
+    Both: the state of a fixed sample of envs."""
+    E = eng.E
+    rng = np.random.RandomState(DUMP_SEED)
+    arrays = {}
+    if net is not None:
+        B = E * 10
+        rows = np.sort(rng.choice(B, min(B, max(1, DUMP_ROLLOUT_BYTES // (24 * T))), replace=False))
+        arrays["params"] = net.get_params()
+        if roll.train and roll.last_stats is not None:
+            arrays["update_stats"] = np.array([roll.last_stats[k] for k in ("loss", "policy_loss", "critic_loss_mean", "global_norm")],
+                                              np.float64)
+        arrays["rollout_actions"] = net.read_rollout("actions", (T, B, 2))[:, rows]
+        for name in ("values", "rewards", "y", "adv"):
+            arrays["rollout_" + name] = net.read_rollout(name, (T, B))[:, rows]
+        arrays["rollout_boot"] = net.read_rollout("boot", (B,))[rows]
+    else:
+        cols = np.sort(rng.choice(E, min(E, max(1, DUMP_ROLLOUT_BYTES // (12 * T))), replace=False))
+        for name, ptr in (("rewards", roll.rew), ("y", roll.y), ("adv", roll.adv)):
+            arrays["rollout_" + name] = eng.dev_download(ptr, (T, E), np.float32)[:, cols]
+    envs = np.sort(rng.choice(E, min(E, DUMP_ENVS), replace=False))
+    arrays["swarm_x"] = eng.get_state("SWARM_X")[envs]
+    arrays["swarm_xa"] = eng.get_state("SWARM_XA")[envs]
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def flat_config_block(kind, E, T, device_id, steps=10):
     """BASELINE configs[1] (Solow-v0, 4 096 envs) / the per-GPU share of configs[4] (TradeAR1 n=16, 65 536 envs / 8 GPUs = 8 192)
     with FlatPolicyVNetwork (GRU(32) + MLP): the T-step PAAC rollout as ONE persistent kernel (a workgroup keeps 64 / 32 / 16 envs for all
@@ -396,9 +452,10 @@ def workload_leg(args, ranks, E, T, env=None, interior=False, steps=3, traffic_f
     return out
 
 
-def measure_swarm(args, ranks, E, T, want_roofline, label):
+def measure_swarm(args, ranks, E, T, want_roofline, label, side=True, dump_dir=None):
     """One Swarm PAAC workload on this rank's shard of E envs: warmup, K timed updates (barrier + device sync on both sides,
-    max over ranks), then (rank 0, single-stream extra update) the per-GEMM HIP-event pass for the roofline."""
+    max over ranks), then (rank 0, dump_dir) the outputs of the last one.  With `side`: the host-thread and communicator figures and
+    the env-step probe; with `want_roofline`: the per-GEMM HIP-event pass (single-stream extra update) for the roofline."""
     from goldsrl import _ffi, sharding
     from goldsrl import distributed as D
     rank, world = ranks.rank, ranks.world
@@ -423,47 +480,47 @@ def measure_swarm(args, ranks, E, T, want_roofline, label):
     for _ in range(args.warmup):
         roll.run()
     barrier()
-    ht0 = net.host_times() if net is not None else None
+    ht0 = net.host_times() if (net is not None and side) else None
     before = None
     if getattr(args, "interior", False):
         irng = np.random.RandomState(4)
         before = lambda: inject_interior_agents(eng, irng)      # noqa: E731
     elapsed, per_update = timed_each(roll.run, eng.wait, args.steps, before)
-    ht1 = net.host_times() if net is not None else None
+    ht1 = net.host_times() if ht0 is not None else None
     ranks.barrier()
     elapsed = ranks.max(elapsed)
-    host = None
-    if ht0 is not None and ht1["updates"] > ht0["updates"]:
-        # what the host thread of THIS rank did per update: ms inside grl_net_rollout (asynchronous: all enqueue work) and inside
-        # grl_net_train_rollout up to its final stream synchronisation, and ms waiting in that synchronisation
-        k = float(ht1["updates"] - ht0["updates"])
-        mine = {"rank": rank, "rollout_enqueue_ms": (ht1["rollout_enqueue_ms"] - ht0["rollout_enqueue_ms"]) / k,
-                "train_enqueue_ms": (ht1["train_enqueue_ms"] - ht0["train_enqueue_ms"]) / k,
-                "train_wait_ms": (ht1["train_wait_ms"] - ht0["train_wait_ms"]) / k}
-        mine["host_enqueue_ms_per_update"] = mine["rollout_enqueue_ms"] + mine["train_enqueue_ms"]
-        host = [json.loads(x.decode()) for x in ranks.allgather_bytes(json.dumps(mine).encode())]
-    # env step kernel alone (roofline_env_step): in the conv rollout every chunk's step overlaps other chunks' kernels and has no
-    # clean duration, so it is timed here on whole-batch launches of a short random-policy rollout (HIP events on the handle's stream)
-    probe = RandomPolicyRollout(eng, 4) if args.policy == "conv" else roll
-    eng.profile_enable(True)
-    probe.run(); eng.wait()
-    env_launches, env_kernel_ms = eng.profile_read()
-    eng.profile_enable(False)
-    comm = None
-    if net is not None and world > 1:
-        # what RCCL itself reports (ncclCommCount) and the all-reduce time per rank (HIP events around the collective), gathered
-        # to rank 0; plus the cross-rank check that the replicas still hold identical parameters after the timed updates
-        info = net.comm_info()
-        mine = json.dumps({"rank": rank, "rccl_ranks": info["rccl_ranks"], "rccl_user_rank": info["rccl_user_rank"],
-                           "allreduce_calls": info["allreduce_calls"],
-                           "allreduce_ms": info["allreduce_ms_total"] / max(info["allreduce_calls"], 1)}).encode()
-        per_rank = [json.loads(x.decode()) for x in ranks.allgather_bytes(mine)]
-        comm = {"rccl_ranks": min(r["rccl_ranks"] for r in per_rank), "per_rank": per_rank,
-                "allreduce_ms": [r["allreduce_ms"] for r in per_rank],
-                "params_equal_across_ranks": bool(D.params_equal_across_ranks(net, ranks))}
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, eng, roll, net, T)      # before anything below runs the workload once more
     res = {"eng": eng, "roll": roll, "net": net, "exchange": exchange, "elapsed": elapsed, "E": E, "per_update": per_update,
-           "comm": comm, "host": host,
-           "env_launches": env_launches, "env_kernel_ms": env_kernel_ms, "gemm": None, "gemm_step_s": None, "gemm_tags": {}}
+           "comm": None, "host": None, "env_launches": None, "env_kernel_ms": None, "gemm": None, "gemm_step_s": None, "gemm_tags": {}}
+    if side:
+        if ht0 is not None and ht1["updates"] > ht0["updates"]:
+            # what the host thread of THIS rank did per update: ms inside grl_net_rollout (asynchronous: all enqueue work) and inside
+            # grl_net_train_rollout up to its final stream synchronisation, and ms waiting in that synchronisation
+            k = float(ht1["updates"] - ht0["updates"])
+            mine = {"rank": rank, "rollout_enqueue_ms": (ht1["rollout_enqueue_ms"] - ht0["rollout_enqueue_ms"]) / k,
+                    "train_enqueue_ms": (ht1["train_enqueue_ms"] - ht0["train_enqueue_ms"]) / k,
+                    "train_wait_ms": (ht1["train_wait_ms"] - ht0["train_wait_ms"]) / k}
+            mine["host_enqueue_ms_per_update"] = mine["rollout_enqueue_ms"] + mine["train_enqueue_ms"]
+            res["host"] = [json.loads(x.decode()) for x in ranks.allgather_bytes(json.dumps(mine).encode())]
+        # env step kernel alone (roofline_env_step): in the conv rollout every chunk's step overlaps other chunks' kernels and has no
+        # clean duration, so it is timed here on whole-batch launches of a short random-policy rollout (HIP events on the handle's stream)
+        probe = RandomPolicyRollout(eng, 4) if args.policy == "conv" else roll
+        eng.profile_enable(True)
+        probe.run(); eng.wait()
+        res["env_launches"], res["env_kernel_ms"] = eng.profile_read()
+        eng.profile_enable(False)
+        if net is not None and world > 1:
+            # what RCCL itself reports (ncclCommCount) and the all-reduce time per rank (HIP events around the collective), gathered
+            # to rank 0; plus the cross-rank check that the replicas still hold identical parameters after the timed updates
+            info = net.comm_info()
+            mine = json.dumps({"rank": rank, "rccl_ranks": info["rccl_ranks"], "rccl_user_rank": info["rccl_user_rank"],
+                               "allreduce_calls": info["allreduce_calls"],
+                               "allreduce_ms": info["allreduce_ms_total"] / max(info["allreduce_calls"], 1)}).encode()
+            per_rank = [json.loads(x.decode()) for x in ranks.allgather_bytes(mine)]
+            res["comm"] = {"rccl_ranks": min(r["rccl_ranks"] for r in per_rank), "per_rank": per_rank,
+                           "allreduce_ms": [r["allreduce_ms"] for r in per_rank],
+                           "params_equal_across_ranks": bool(D.params_equal_across_ranks(net, ranks))}
     # GEMM roofline: one more update of the same workload with a HIP event pair around every gemm_rowk / gemm_tn launch.
     # Per-launch events need the launches serialised, so this pass runs on one stream; the timed region above alternates
     # independent chunks between four streams, where kernels of different chunks overlap and have no clean duration.
@@ -515,13 +572,14 @@ def main():
         pin2 = affinity.pin_to_pci(_ffi.device_pci_address(local))
         pin2["sysfs_attempt"] = pin.get("reason")
         pin = pin2
-    m = measure_swarm(args, ranks, E, T, want_roofline=True, label="weak")
+    full = args.full
+    m = measure_swarm(args, ranks, E, T, want_roofline=full, label="weak", side=full, dump_dir=args.dump_outputs)
     m["pin"] = [json.loads(x.decode()) for x in ranks.allgather_bytes(json.dumps(pin).encode())]
     eng, roll, net, exchange, elapsed = m["eng"], m["roll"], m["net"], m["exchange"], m["elapsed"]
     env_launches, env_kernel_ms, gemm, gemm_step_s, gemm_tags = m["env_launches"], m["env_kernel_ms"], m["gemm"], m["gemm_step_s"], m["gemm_tags"]
 
     extras = {}
-    if not args.no_extras and args.policy == "conv" and world == 1:
+    if full and not args.no_extras and args.policy == "conv" and world == 1:
         if not args.no_train:      # same net, same rollout, without the gradient step
             roll.train = False
             roll.run(); eng.wait()
@@ -540,7 +598,7 @@ def main():
         net.close()
     eng.close()
 
-    if world > 1 and not args.no_strong and args.policy == "conv" and E % world == 0:
+    if full and world > 1 and not args.no_strong and args.policy == "conv" and E % world == 0:
         # strong scaling: BASELINE's target shape, 32 768 envs IN TOTAL, E / world per rank
         sargs = argparse.Namespace(**vars(args))
         sargs.warmup, sargs.steps = 2, max(3, min(args.steps, 10))
@@ -553,7 +611,7 @@ def main():
         if sm["net"] is not None:
             sm["net"].close()
         sm["eng"].close()
-    if world == 1 and not args.no_extras and not args.no_legs and args.policy == "conv" and not args.no_train and not args.single_stream:
+    if full and world == 1 and not args.no_extras and not args.no_legs and args.policy == "conv" and not args.no_train and not args.single_stream:
         # how much of `value` is the workload: the same update (a) without the zero-skipping forms, (b) with agents in the interior
         extras["dense_form"] = workload_leg(args, ranks, E, T, env={"GRL_PATCH_SKIP": "off", "GRL_TRUNK_SKIP": "off"})
         extras["dense_form"]["what"] = ("the same update with GRL_PATCH_SKIP=off GRL_TRUNK_SKIP=off: plain 5x5 dense1 patches, all 9 conv3 taps of "
@@ -564,7 +622,7 @@ def main():
                                              "mean_x + U(-1.2, 0), y = U(1.5, 4.3) -- where an agent's conv3 footprint is ~75 % of its 5x5 "
                                              "patch instead of ~25 % at the rim; `value` above stays on SURVEY 8(d)'s prescribed workload "
                                              "(random-init policy from the env's own reset states)")
-    if world == 1 and not args.no_extras and not args.no_shard and args.policy == "conv" and not args.no_train and not args.single_stream:
+    if full and world == 1 and not args.no_extras and not args.no_shard and args.policy == "conv" and not args.no_train and not args.single_stream:
         # the per-GPU share of the shape BASELINE's target is quoted on (32 768 Swarm envs over 8 GPUs, >= 6x of the 1-GPU rate): the
         # same full update at 4 096 envs.  On one GPU this prices everything of that point except the 8.84 MB all-reduce.
         sh = workload_leg(args, ranks, SHARD_ENVS, T, steps=7)
@@ -580,7 +638,7 @@ def main():
                                         "it leaves out the all-reduce of the 2.2 M-float gradient (8.84 MB per rank and update over "
                                         "xGMI) and the ranks' mutual wait -- RCCL with world size > 1 has not run on any box yet"}
         extras["shard_%d" % SHARD_ENVS] = sh
-    if world == 1 and not args.no_flat_configs and not args.no_extras and args.policy == "conv":
+    if full and world == 1 and not args.no_flat_configs and not args.no_extras and args.policy == "conv":
         device = int(os.environ.get("GRL_BENCH_FORCE_DEVICE", ranks.local_rank))
         extras["solow_4096"] = flat_config_block("solow", 4096, T, device)
         extras["trade16_gru_8192"] = flat_config_block("trade", 8192, T, device)
@@ -588,26 +646,28 @@ def main():
     if rank == 0:
         total_env_steps = world * E * T * args.steps
         value = total_env_steps / elapsed
-        k_avg_ms = env_kernel_ms / max(env_launches, 1)
-        env_achieved = E * SWARM_BYTES_PER_ENV_STEP / (k_avg_ms * 1e-3) / 1e9
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "swarm_step_traffic.json")
-        if os.path.exists(tpath):
-            with open(tpath) as f:
-                tj = json.load(f)
-            if tj.get("envs") == E and bool(tj.get("fast_math")) == bool(args.fast_math):
-                traffic = tj.get("hbm_bytes_per_launch")
-        env_roof = {"bound": "hbm", "kernel": "swarm_kernel<MODE_STEP>", "achieved": env_achieved, "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": env_achieved / HBM_PEAK_GBS, "traffic": traffic, "avg_kernel_ms": k_avg_ms,
-                    "launches": env_launches, "pair_interactions_per_s": E * SWARM_PAIRS_PER_ENV_STEP / (k_avg_ms * 1e-3),
-                    "note": "fp64-VALU/transcendental bound (~90 flop/B), not HBM bound: see DESIGN.md",
-                    # the bound that applies: the pair loop is 112 VALU instructions per pair in the gfx950 ISA (67 full-rate
-                    # fp64 fma/mul/add, 3 divisions = 6 div_scale + 3 rcp + 3 div_fmas + 3 div_fixup, 2 exp, 1 rsq, selects);
-                    # peak = 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz full-rate issue (rcp/rsq are quarter rate, so 100 % is not reachable)
-                    "valu_f64_issue": {"instr_per_pair": SWARM_VALU_INSTR_PER_PAIR,
-                                       "achieved": E * SWARM_PAIRS_PER_ENV_STEP * SWARM_VALU_INSTR_PER_PAIR / (k_avg_ms * 1e-3),
-                                       "peak": VALU_LANE_INSTR_PEAK, "unit": "lane-instructions/s",
-                                       "frac": E * SWARM_PAIRS_PER_ENV_STEP * SWARM_VALU_INSTR_PER_PAIR / (k_avg_ms * 1e-3) / VALU_LANE_INSTR_PEAK}}
+        env_roof = None
+        if env_launches is not None:      # --full: the env-step probe ran
+            k_avg_ms = env_kernel_ms / max(env_launches, 1)
+            env_achieved = E * SWARM_BYTES_PER_ENV_STEP / (k_avg_ms * 1e-3) / 1e9
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "swarm_step_traffic.json")
+            if os.path.exists(tpath):
+                with open(tpath) as f:
+                    tj = json.load(f)
+                if tj.get("envs") == E and bool(tj.get("fast_math")) == bool(args.fast_math):
+                    traffic = tj.get("hbm_bytes_per_launch")
+            env_roof = {"bound": "hbm", "kernel": "swarm_kernel<MODE_STEP>", "achieved": env_achieved, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": env_achieved / HBM_PEAK_GBS, "traffic": traffic, "avg_kernel_ms": k_avg_ms,
+                        "launches": env_launches, "pair_interactions_per_s": E * SWARM_PAIRS_PER_ENV_STEP / (k_avg_ms * 1e-3),
+                        "note": "fp64-VALU/transcendental bound (~90 flop/B), not HBM bound: see DESIGN.md",
+                        # the bound that applies: the pair loop is 112 VALU instructions per pair in the gfx950 ISA (67 full-rate
+                        # fp64 fma/mul/add, 3 divisions = 6 div_scale + 3 rcp + 3 div_fmas + 3 div_fixup, 2 exp, 1 rsq, selects);
+                        # peak = 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz full-rate issue (rcp/rsq are quarter rate, so 100 % is not reachable)
+                        "valu_f64_issue": {"instr_per_pair": SWARM_VALU_INSTR_PER_PAIR,
+                                           "achieved": E * SWARM_PAIRS_PER_ENV_STEP * SWARM_VALU_INSTR_PER_PAIR / (k_avg_ms * 1e-3),
+                                           "peak": VALU_LANE_INSTR_PEAK, "unit": "lane-instructions/s",
+                                           "frac": E * SWARM_PAIRS_PER_ENV_STEP * SWARM_VALU_INSTR_PER_PAIR / (k_avg_ms * 1e-3) / VALU_LANE_INSTR_PEAK}}
         stages = "action draw + norm clip + SwarmEnv.step + TimeLimit + auto-reset + process_state + n-step returns"
         if args.policy == "conv":
             stages = ("conv policy forward (fp32) + Gaussian sample + norm clip + SwarmEnv.step + TimeLimit + auto-reset + "
@@ -700,12 +760,12 @@ def main():
                     out["roofline"]["by_family"][fam]["executed_share_of_the_5x5_patch"] = \
                         gemm_tags[fam][2] / (gemm_tags[fam][0] * 2.0 * chunk_samples * 1600 * 512)
             out["roofline_env_step"] = env_roof
-        else:
+        elif env_roof is not None:
             out["roofline"] = env_roof
         out.update(extras)
         if last_stats:
             out["last_update_stats"] = last_stats
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_envs, T, mask=mask0)
             out["cpu_baseline"]["affinity"] = "the job's own mask (%s cpus), not the GPU rank's NUMA pin" % (len(mask0) if mask0 else "?")
         print(json.dumps(out))

@@ -104,7 +104,7 @@ def test_bench_gpus_2_without_a_launcher_reports_two_ranks():
     env = dict(os.environ, GRL_BENCH_FORCE_DEVICE="0")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--envs", "256", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=800)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -193,7 +193,7 @@ def test_bench_under_the_elastic_launcher_two_ranks_on_one_gpu():
         env.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--envs", "256", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-strong"], env=env, capture_output=True, text=True, timeout=800)
+                        "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--full"], env=env, capture_output=True, text=True, timeout=800)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 EXTRA=""
 for kv in "$@"; do case "$kv" in --*) EXTRA="$EXTRA $kv";; *) export "$kv";; esac; done
 mkdir -p gpurun_out
-ARGS="bench.py --envs 8192 --steps 1 --warmup 0 --no-cpu-baseline --no-extras --single-stream $EXTRA"
+ARGS="bench.py --full --envs 8192 --steps 1 --warmup 0 --no-cpu-baseline --no-extras --single-stream $EXTRA"
 D=gpurun_out/kpmc
 rm -rf $D
 timeout -k 10 200 rocprofv3 --kernel-trace --kernel-include-regex "$RX" --pmc FETCH_SIZE --output-format csv -d $D/mem -- python3 $ARGS > $D.mem.log 2>&1

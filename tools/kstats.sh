@@ -5,7 +5,7 @@ set -e
 TAG=${1:-x}; shift || true
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/ks_$TAG && mkdir -p gpurun_out
-EXTRA=""
+EXTRA="--full"      # the roofline pass is the third update of the pass
 for kv in "$@"; do case "$kv" in --*) EXTRA="$EXTRA $kv";; *) export "$kv";; esac; done
 UPD=3
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ks_$TAG -- python3 bench.py --envs 8192 --steps 2 --warmup 0 --no-cpu-baseline --no-extras --single-stream $EXTRA > gpurun_out/ks_$TAG.log 2>&1

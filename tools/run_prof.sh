@@ -15,7 +15,7 @@ if [ "$VAR" = "interior" ]; then SFX="_interior"; XARG="--interior"; fi
 P=gpurun_out/r${RND}${SFX}
 note() { echo "$(date +%T) $1" >> gpurun_out/r${RND}_prof.progress; }
 if [ "$PART" = "A" ]; then
-  ARGS="bench.py --envs 8192 --steps 2 --warmup 0 --no-cpu-baseline --no-extras --single-stream $XARG"
+  ARGS="bench.py --full --envs 8192 --steps 2 --warmup 0 --no-cpu-baseline --no-extras --single-stream $XARG"
   note "A$SFX stats";  rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_A_stats -- python3 $ARGS > ${P}_A_stats.log 2>&1
   note "A$SFX fetch";  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d ${P}_A_fetch -- python3 $ARGS > ${P}_A_fetch.log 2>&1
   note "A$SFX write";  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d ${P}_A_write -- python3 $ARGS > ${P}_A_write.log 2>&1
@@ -24,9 +24,9 @@ if [ "$PART" = "A" ]; then
   python3 tools/summarize_prof.py $RND A $VAR
   rm -rf ${P}_A_stats ${P}_A_fetch ${P}_A_write ${P}_A_sq      # raw traces stay on the box (gpurun_out is capped at 64 MiB)
 elif [ "$PART" = "B" ]; then
-  ARGS="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras $XARG"
+  ARGS="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras $XARG"
   note "B trace";  rocprofv3 --kernel-trace --output-format csv -d ${P}_B_trace -- python3 $ARGS > ${P}_B_trace.log 2>&1
-  ARGS1="bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras $XARG"
+  ARGS1="bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras $XARG"
   note "B sq";     rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY --output-format csv -d ${P}_B_sq -- python3 $ARGS1 > ${P}_B_sq.log 2>&1
   note "B fetch";  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d ${P}_B_fetch -- python3 $ARGS1 > ${P}_B_fetch.log 2>&1
   note "B write";  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d ${P}_B_write -- python3 $ARGS1 > ${P}_B_write.log 2>&1
@@ -34,7 +34,7 @@ elif [ "$PART" = "B" ]; then
   python3 tools/summarize_prof.py $RND B $VAR
   rm -rf ${P}_B_trace ${P}_B_sq ${P}_B_fetch ${P}_B_write
 else
-  ARGS="bench.py --policy random --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
+  ARGS="bench.py --full --policy random --steps 3 --warmup 1 --no-cpu-baseline --no-extras"
   note "C stats";  rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_C_stats -- python3 $ARGS > ${P}_C_stats.log 2>&1
   note "C fetch";  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d ${P}_C_fetch -- python3 $ARGS > ${P}_C_fetch.log 2>&1
   note "C write";  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d ${P}_C_write -- python3 $ARGS > ${P}_C_write.log 2>&1
