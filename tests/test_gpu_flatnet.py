@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import _flat_oracle as FO
 from oracle import nets as NN
 from oracle import oracle as O
 
@@ -41,10 +42,13 @@ def _samples(n, S0, D, T, A, seed=0):
     return states, hist, act, adv, y
 
 
-@pytest.mark.parametrize("S0,D,T,A", [(2, 2, 5, 1), (33, 33, 20, 16)])     # Solow defaults; TradeAR1-16 shapes (train_trade.py:38-40,119)
-def test_flat_forward_and_gradients_match_oracle(S0, D, T, A):
-    n = 150       # three wave-groups, last one partial
-    eng, net = _net({}, static_size=S0, temporal_size=D, rnn_length=T, num_actions=A, max_samples=256, scale=100.0)
+@pytest.mark.parametrize("S0,D,T,A,n", [
+    (2, 2, 5, 1, 150), (33, 33, 20, 16, 150),      # Solow defaults; TradeAR1-16 shapes (train_trade.py:38-40,119): three groups, last partial
+    (2, 2, 5, 1, 64 * 512 + 37),                   # 513 groups: flat_forward_kernel<false>; backward block 0 loops over groups 0 and 512 (partial)
+    (33, 33, 20, 16, 64 * 256 + 37),               # 257 groups: the forward instance without the GRU weights in LDS
+], ids=["2-2-5-1", "33-33-20-16", "2-2-5-1-32805", "33-33-20-16-16421"])      # the n = 150 cases keep their ids
+def test_flat_forward_and_gradients_match_oracle(S0, D, T, A, n):
+    eng, net = _net({}, static_size=S0, temporal_size=D, rnn_length=T, num_actions=A, max_samples=max(n, 256), scale=100.0)
     p = _params(net, S0, D, A)
     states, hist, act, adv, y = _samples(n, S0, D, T, A)
     out = net.predict(states, hist)
@@ -62,6 +66,17 @@ def test_flat_forward_and_gradients_match_oracle(S0, D, T, A):
     for name, _ in shapes:
         err = np.abs(got[name] - g[name]).max() / (np.abs(g[name]).max() + 1e-12)
         assert err < 2e-4, (name, err)
+    # the bound would see the last group (or group 256) left out, or group 0 counted twice
+    groups, f64 = (n + 63) // 64, [a.astype(np.float64) for a in (states, hist, act, adv, y)]
+    win = FO.dense_windows(f64[1])
+    part = lambda k: FO.group_contribution(p, f64[0], win, f64[2], f64[3], f64[4], k)      # noqa: E731
+    alts = {"group %d left out" % k: (-1.0, part(k)) for k in {groups - 1, min(256, groups - 1)}}
+    alts["group 0 twice"] = (1.0, part(0))
+    sens = FO.sensitivity(g, FO.altered(g, alts))
+    print("\n[flat oracle] explicit histories S0=%d n=%d: block error %.3g, tolerance 2e-4, altered %s"
+          % (S0, n, max(FO.block_errors(got, g).values()), {k: "%.3g (%s)" % v for k, v in sens.items()}))
+    for label, (e, k) in sens.items():
+        assert e > 2e-4, (label, e, k)
     np.testing.assert_allclose(st["global_norm"], np.sqrt(sum((v ** 2).sum() for v in g.values())), rtol=1e-4)
     first = net.get_grads()
     net.train(states, hist, act, adv, y, lr=0.0, apply_update=False)
@@ -269,7 +284,7 @@ def test_persistent_rollout_is_bit_identical_to_the_graph_of_launches(kind, E, c
 
 
 @pytest.mark.parametrize("kind,E,group", [("solow", 200, None), ("solow", 1100, 32), ("trade", 200, None), ("trade", 1100, 32),
-                                           ("solow", 300, 64), ("trade", 300, 64)])
+                                           ("solow", 300, 64), ("trade", 300, 64), ("solow", 4096, None), ("trade", 8192, None)])
 def test_a_rollout_that_keeps_its_activations_trains_exactly_as_one_that_recomputes_them(kind, E, group, monkeypatch):
     """grl_fnet_set_keep_activations: the persistent rollout fills the training workspace (step-major samples t * E + env, written by
     workgroups of 16 / 32 envs that share the 64-sample blocks of the layout) and the gradient step starts at the backward pass.
