@@ -122,25 +122,6 @@ __global__ void flat_transpose_kernel(const float *__restrict__ P, float *__rest
 }
 constexpr int kFlatTransposed = 11;
 
-// dst[i] = sum over the workgroups' slabs, in a fixed order: 64 parameters per block, thread (q, p) adds the slabs q, q + 16, ..
-// for parameter p (16 loads in flight per parameter instead of one thread walking all 256 slabs), the 16 partial sums then in order
-__global__ __launch_bounds__(1024) void flat_slab_reduce_kernel(const float *__restrict__ slab, int blocks, long n, float *__restrict__ dst) {
-    __shared__ float part[16][64];
-    const int p = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const long i = (long)blockIdx.x * 64 + p;
-    float s = 0.f;
-    if (i < n)
-        for (int b = q; b < blocks; b += 16) s += slab[(long)b * n + i];
-    part[q][p] = s;
-    __syncthreads();
-    if (q == 0 && i < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += part[k][p];
-        dst[i] = t;
-    }
-}
-
 // sum of squares in float64: kSumsqBlocks partial sums (a contiguous slice each, tree inside the block), added up in order by
 // flat_finalize_kernel
 constexpr int kSumsqBlocks = 32;

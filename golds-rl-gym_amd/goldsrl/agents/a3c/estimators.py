@@ -1,0 +1,66 @@
+"""fed_gym/agents/a3c/estimators.py for the Ticker gated trader: DiscreteAndContPolicyEstimator (:40-152) and ValueEstimator
+(:338-417) on the shared rnn_graph_lstm trunk (:18-28), as facades over ONE device net (goldsrl._ffi_gated.GatedNet: both
+estimators own the same parameters, as the reference's two graphs share the "shared" variable scope).  Only the Ticker sizes
+exist on the device: 2 assets x 3 choices, static input 7, temporal rows 4, hidden sizes 32 / 128."""
+import numpy as np
+
+
+def _check_sizes(static_size, temporal_size, static_hidden_size, num_assets=2):
+    if (num_assets, static_size, temporal_size, static_hidden_size) != (2, 7, 4, 128):
+        raise ValueError("the device net exists for the Ticker sizes only: num_assets=2, static_size=7, temporal_size=4, "
+                         "static_hidden_size=128 (got %r)" % ((num_assets, static_size, temporal_size, static_hidden_size),))
+
+
+def _batch(state, history, batch):
+    s = np.asarray(state, np.float32)
+    h = np.asarray(history, np.float32)
+    if not batch:
+        s, h = s[None], h[None]
+    return s, h
+
+
+class DiscreteAndContPolicyEstimator(object):
+    """predict() returns the reference's keys: mu, sigma, probs, each (n, num_assets, 3)."""
+    num_actions = 3
+    BUY_IDX = 1
+    SELL_IDX = 2
+
+    def __init__(self, num_assets, static_size, temporal_size, shared_layer=None, static_hidden_size=128, trainable=True,
+                 learning_rate=1e-4, seed=None, reuse=False, net=None):
+        _check_sizes(static_size, temporal_size, static_hidden_size, num_assets)
+        if net is None:
+            raise ValueError("pass net=GatedNet(ticker_engine, ...): the estimators are facades over one device net")
+        self.net, self.num_assets, self.static_size, self.temporal_size = net, num_assets, static_size, temporal_size
+        self.learning_rate = learning_rate
+
+    def _window(self, history):
+        h = np.asarray(history, np.float32)
+        R = self.net.R
+        out = np.zeros(h.shape[:-2] + (R, h.shape[-1]), np.float32)       # pad_sequences(padding='post', maxlen=R)
+        n = min(R, h.shape[-2])
+        out[..., :n, :] = h[..., -n:, :] if h.shape[-2] > R else h[..., :n, :]
+        return out
+
+    def predict(self, state, history, sess=None, batch=False):
+        s, h = _batch(state, self._window(history), batch)
+        out = self.net.predict(s, h)
+        return {"mu": out["mu"], "sigma": out["sigma"], "probs": out["probs"]}
+
+
+class ValueEstimator(object):
+    """predict() returns {'logits': (n,)}: scale times the value head, as the reference."""
+
+    def __init__(self, static_size, temporal_size, shared_layer=None, static_hidden_size=128, reuse=False, trainable=True,
+                 learning_rate=1e-4, num_actions=2, scale=1., net=None):
+        _check_sizes(static_size, temporal_size, static_hidden_size)
+        if net is None:
+            raise ValueError("pass net=GatedNet(ticker_engine, scale=...): the estimators are facades over one device net")
+        if abs(net.cfg.scale - scale) > 1e-12 * max(1.0, abs(scale)):
+            raise ValueError("scale %r differs from the net's %r" % (scale, net.cfg.scale))
+        self.net, self.static_size, self.temporal_size, self.scale = net, static_size, temporal_size, scale
+        self.learning_rate = learning_rate
+
+    def predict(self, state, history, sess=None, batch=False):
+        s, h = _batch(state, DiscreteAndContPolicyEstimator._window(self, history), batch)
+        return {"logits": self.net.predict(s, h)["values"]}
+

@@ -1,0 +1,86 @@
+"""`python -m goldsrl.scripts.train_ticker` -- the Ticker gated trader (TickerGatedTraderWorker, fed_gym/agents/a3c/worker.py:445-494)
+trained on the device: E envs x T steps per update, each env one A3C worker (include/goldsrl_gatednet.h).  The price table comes
+from a CSV (columns Open, Close, Volume) or a --table .npz (Open / Close / Volume or tbl_open / tbl_close / tbl_volume arrays)
+through the sampler of goldsrl.envs.data; scalars go to a TF-events file, the checkpoint to <out>/checkpoint.npz."""
+import argparse
+import logging
+import os
+import sys
+import time
+
+import numpy as np
+
+from goldsrl import _ffi, _ffi_gated
+from goldsrl.envs.data.sampler import OpenCloseSampler
+from goldsrl.utils_tfevents import EventFileWriter
+
+logging.basicConfig(stream=sys.stdout, level=logging.INFO)
+
+
+def get_arg_parser():
+    p = argparse.ArgumentParser(description=__doc__)
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--csv", help="price table CSV (Open, Close, Volume)")
+    src.add_argument("--table", help=".npz with the three columns")
+    p.add_argument("--envs", type=int, default=4096)
+    p.add_argument("--steps", type=int, default=20, help="env steps per update (T)")
+    p.add_argument("--updates", type=int, default=100)
+    p.add_argument("--rnn-length", type=int, default=5, help="the worker's max_seq_length (R), 1..20")
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--scale", type=float, default=1.0)
+    p.add_argument("--seed", type=int, default=3)
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--out", default="logs/ticker")
+    p.add_argument("--resume", help="checkpoint .npz to continue from")
+    p.add_argument("--checkpoint-every", type=int, default=50)
+    return p
+
+
+def load_table(args):
+    if args.csv:
+        return OpenCloseSampler(path=args.csv)
+    with np.load(args.table) as z:
+        keys = ("Open", "Close", "Volume") if "Open" in z.files else ("tbl_open", "tbl_close", "tbl_volume")
+        return OpenCloseSampler(table={"Open": z[keys[0]], "Close": z[keys[1]], "Volume": z[keys[2]]})
+
+
+def main(argv=None):
+    args = get_arg_parser().parse_args(argv)
+    sampler = load_table(args)
+    eng = _ffi.Engine(_ffi.ENV_TICKER, args.envs, device_id=args.device, seed=args.seed)
+    eng.ticker_set_table(sampler.data_matrix)
+    eng.reset()
+    eng.episodes_enable()
+    net = _ffi_gated.GatedNet(eng, rnn_length=args.rnn_length, scale=args.scale, max_samples=max(1, args.envs))
+    if args.resume:
+        net.load_checkpoint(args.resume)
+    else:
+        net.set_params(_ffi_gated.default_init_gated(args.seed))
+    os.makedirs(args.out, exist_ok=True)
+    writer = EventFileWriter(args.out)
+    ckpt = os.path.join(args.out, "checkpoint.npz")
+    for u in range(args.updates):
+        t0 = time.time()
+        net.rollout(args.steps)
+        stats = net.train_rollout(args.lr)
+        dt = time.time() - t0
+        step = net.get_optimizer_state()["global_step"]
+        for k, v in stats.items():
+            writer.add_scalar("train/" + k, v, step)
+        eps = eng.episodes_read()
+        if len(eps):
+            writer.add_scalar("episode/total_reward", float(np.mean(eps["total_reward"])), step)
+            writer.add_scalar("episode/length", float(np.mean(eps["length"])), step)
+        writer.add_scalar("perf/env_steps_per_s", args.envs * args.steps / dt, step)
+        writer.flush()
+        logging.info("update %d  global step %d  policy loss %.4g  value loss %.4g  entropy %.4g  %.0f env-steps/s", u + 1, step,
+                     stats["policy_loss"], stats["value_loss"], stats["entropy_mean"], args.envs * args.steps / dt)
+        if (u + 1) % args.checkpoint_every == 0 or u + 1 == args.updates:
+            net.save_checkpoint(ckpt)
+    writer.close()
+    net.close()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
