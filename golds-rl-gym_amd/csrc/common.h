@@ -28,6 +28,7 @@ struct SwarmState {
     double *reward64;
     double *act64;                                 // staging of grl_swarm_step_f64 (allocated on first use)
     uint8_t *lbins, *abins, *pos;
+    bool ref_div;                                  // GRL_SWARM_DIV=ref at grl_create: the exact step with three IEEE divisions per pair
 };
 
 struct SolowState {

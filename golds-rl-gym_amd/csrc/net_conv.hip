@@ -100,6 +100,7 @@ struct NetLane {
     unsigned *tamask, *tbmask, *tcmask, *tnmask;      // (tnmask: blocks of sraw anybody reads) + 100-bit mask of touched 2x2 conv1 pixel blocks, 49-bit mask of affected conv3 outputs
     int *trowlist, *tblklist, *tc3list, *trows_n, *twgcnt, *twgoff;      // their lists, live counts [conv2 rows, blocks, conv3 rows], scan scratch
     unsigned *tumask;          // union of the chunk's conv3 masks (2 words)
+    unsigned *obsrec;          // the chunk's observation index records (obs_index_kernel, net_shared.inc): kObsWords words per env, rebuilt per backward pass
     unsigned *tneed2;          // conv2 pixels inside the 3 x 3 windows of that union (3 words): what conv3 reads of a2sh
     float *tubias;             // dense1's per-env bias under that union (trunk_ubias_kernel)
     float *tug, *tuspix;       // gradient side: G = column sums of gd1sh (512), per-pixel closed-form sums (49 x 64)
@@ -150,6 +151,7 @@ struct grl_net : NetLane {
     // its conv2 row, a2 at all 81 pixels, [z3 | a3] of its conv3 row, the one-row list of those passes
     float *tbgimg, *tbgz, *tbgimg3, *tbgz3, *tybg;      // tybg[49][512]: a background pixel's contribution to dense1 (trunk_ybg_kernel)
     int *tbglist;
+    int obs_index;             // 1: conv1's backward helpers read the observation's index record (GRL_OBS_INDEX=off: the kernels that index inside)
     int trunk_skip;            // 1: conv2's forward / weight gradient / transposed convolution run over the rows the env's bins reach (GRL_TRUNK_SKIP=off: all rows)
     int patch_skip;            // 1: the dense1 patch GEMMs skip what the support masks say is zero (GRL_PATCH_SKIP=off: the plain 5x5 patch)
     int gemm_f32, range_fallback_on, range_fallbacks, range_bits_last, update_skipped_last;
@@ -903,6 +905,7 @@ static int alloc_lane_forward(grl_net *n) {
     if (rc == GRL_OK) rc = nalloc(n, &n->stmask, (c * 9 + 255) / 256 + 1);
     if (rc == GRL_OK) rc = nalloc(n, &n->szmask, 1024);
     if (rc == GRL_OK) rc = nalloc(n, &n->tamask, (c / 10) * 3 + 3);
+    if (rc == GRL_OK) rc = nalloc(n, &n->obsrec, (c / 10 + 1) * kObsWords);
     if (rc == GRL_OK) rc = nalloc(n, &n->tbmask, (c / 10) * 4 + 4);
     if (rc == GRL_OK) rc = nalloc(n, &n->tcmask, (c / 10) * 2 + 2);
     if (rc == GRL_OK) rc = nalloc(n, &n->tnmask, (c / 10) * 4 + 4);
@@ -1058,6 +1061,8 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
         if (const char *rr = getenv("GRL_NET_RANGE_RETURN")) n->range_return_k = strcmp(rr, "off") == 0 ? 0 : std::max(0, atoi(rr));
         const char *psk = getenv("GRL_PATCH_SKIP");
         n->patch_skip = (psk && strcmp(psk, "off") == 0) ? 0 : 1;
+        const char *oix = getenv("GRL_OBS_INDEX");
+        n->obs_index = (oix && strcmp(oix, "off") == 0) ? 0 : 1;
         const char *tsk = getenv("GRL_TRUNK_SKIP");
         n->trunk_skip = (tsk && strcmp(tsk, "off") == 0) ? 0 : 1;
         n->pfrac[0] = n->pfrac[1] = n->pfrac[2] = 1.0; n->sfrac = 1.0;
@@ -1340,6 +1345,31 @@ int grl_net_predict_obs(grl_net *n, int32_t n_envs, const uint8_t *lb, const uin
         rc = download_heads(n, n_envs * 10, mu_host, sigma_host, vs_host);
     }
     return rc;
+}
+
+int grl_net_debug_obs_index(grl_net *n, int32_t n_envs, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, uint32_t *host, size_t bytes) {
+    if (!n || !lb || !ab || !pos || !host || n_envs <= 0) return GRL_E_INVALID;
+    const size_t need = (size_t)n_envs * kObsWords * 4;
+    if (bytes != need) return nfail(n, GRL_E_SIZE, "grl_net_debug_obs_index: need " + std::to_string(need) + " bytes");
+    hipSetDevice(n->h->cfg.device_id);
+    int rc = ensure_tmp_obs(n, n_envs);
+    if (rc) return rc;
+    hipStream_t st = n->h->stream;
+    unsigned *tmp = nullptr;
+    NET_HIP(n, hipMalloc((void **)&tmp, need));
+    hipError_t e = hipMemsetAsync(tmp, 0, need, st);      // the words the kernel leaves alone (padding, list tails) read as zero
+    if (e == hipSuccess) e = hipMemcpyAsync(n->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(n->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(n->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        rc = obs_index(n, n->tmp_lb, n->tmp_ab, n->tmp_pos, n_envs, tmp, st, 3);
+        if (rc == GRL_OK) e = hipStreamSynchronize(st);
+        if (rc == GRL_OK && e == hipSuccess) e = hipMemcpy(host, tmp, need, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(tmp);
+    if (rc) return rc;
+    if (e != hipSuccess) return nfail(n, GRL_E_HIP, std::string("grl_net_debug_obs_index: ") + hipGetErrorString(e));
+    return GRL_OK;
 }
 
 int grl_net_range_info(grl_net *n, int32_t *gemm_f32, int32_t *fallbacks, int32_t *update_skipped) {

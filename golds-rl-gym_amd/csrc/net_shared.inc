@@ -830,6 +830,272 @@ __global__ __launch_bounds__(256) void trunk_ubias_kernel(const float *__restric
         if (!((p < 32 ? u0 >> p : u1 >> (p - 32)) & 1u)) s += y[p];
     ubias[j] = s;
 }
+// ---- the observation's index record (obs_index_kernel): what conv1's backward helpers used to derive from lbins / abins / pos inside
+// their full-grid kernels, once per env behind workgroup barriers -- the distinct bins of the two count channels with their counts, bucketed
+// by tap class, and the agents' candidate-pixel tables -- built once per backward chunk pass by a small kernel the other lanes' GEMMs hide.
+// One WAVE owns an env (four envs per workgroup, no workgroup barrier).  The record is lane scratch; an env's record is kObsWords 32-bit
+// words (1 152 B = 9 x 128 B):
+//   [0]                 header: listed bins of channel 0 | all listed bins << 8 | nslots << 16
+//   [kObsOff ..)        33 bytes: bucket offsets into the list; bucket = channel * 16 + q, q = (h % 4) * 4 + w % 4
+//   [kObsList .. +90)   the distinct (channel, bin) pairs, packed h | w << 8 | channel << 16 | count << 20, ordered by (channel, q, lowest
+//                       point id): the order conv1_wgrad_shared_kernel adds in
+//   [kObsPix .. +40)    agent_ds_kernel's 40 (agent, cover) candidates: pixel | tap << 16, or -1
+//   [kObsCslot ..)      40 bytes: the candidate's distinct-pixel slot (255: none)
+//   [kObsSlotpix ..)    40 x uint16: pixel of a slot
+//   [kObsPm .. +13)     400-bit mask of the conv1 pixels whose 8 x 8 window holds a bin (pixel = oy * 20 + ox)
+//   [kObsList2 .. +90)  the same packed entries in (h, channel, w) order: the (ky, c, kx) order the forward adds a window's taps in
+//                       (written out a second time rather than as a permutation: the forward then reads one list, not two)
+// Equal keys meet in a 128-slot hash table in the wave's own LDS (open addressing; at most 90 keys): count and lowest point id per key
+// with LDS atomics, instead of every lane comparing itself with 90 others (that form took 36 us per 8 192 envs, this one 11).  The
+// order inside a bucket comes from one bit per listed point id in the bucket's three mask words.
+constexpr int kObsWords = 288, kObsOff = 4, kObsList = 16, kObsPix = 112, kObsCslot = 152, kObsSlotpix = 162, kObsPm = 182, kObsList2 = 196;
+struct ObsWaveLds {
+    unsigned key[128], low[128], cnt[128];      // hash table: key (0xFFFFFFFF: free), lowest id, number of points
+    unsigned bm[32][3];                         // per bucket: listed point ids 0..31, 32..63, 64..89
+    unsigned off[36];
+    unsigned pm[16];
+};
+// a wave's own LDS words, written by some of its lanes and read by others: the hardware runs a wave's LDS accesses in order
+__device__ __forceinline__ void obs_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ void obs_hash_clear(ObsWaveLds &L, int lane) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { L.key[lane + 64 * i] = 0xFFFFFFFFu; L.low[lane + 64 * i] = 0xFFFFFFFFu; L.cnt[lane + 64 * i] = 0u; }
+}
+// the slot of `key` (any value but 0xFFFFFFFF); counts the point and keeps the lowest id.  Lanes of one wave may call it together.
+__device__ __forceinline__ int obs_hash_add(ObsWaveLds &L, unsigned key, unsigned id) {
+    unsigned s = (key * 2654435761u) >> 25;
+    for (int t = 0; t < 128; ++t) {      // (bounded: the table cannot fill)
+        const unsigned old = atomicCAS(&L.key[s], 0xFFFFFFFFu, key);
+        if (old == 0xFFFFFFFFu || old == key) break;
+        s = (s + 1) & 127u;
+    }
+    atomicAdd(&L.cnt[s], 1u);
+    atomicMin(&L.low[s], id);
+    return (int)s;
+}
+// PARTS: 1 = what the forward reads (pm, the second order), 2 = what the backward reads (the first order, the agents' tables), 3 = all
+template <int PARTS>
+__global__ __launch_bounds__(256) void obs_index_kernel(const uint8_t *__restrict__ lbins, const uint8_t *__restrict__ abins,
+                                                        const uint8_t *__restrict__ pos, int nenv, int G, unsigned *__restrict__ rec) {
+    __shared__ ObsWaveLds lds[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, env = blockIdx.x * 4 + wv;
+    if (env >= nenv) return;      // wave-uniform, and no workgroup barrier below
+    ObsWaveLds &L = lds[wv];
+    unsigned *r = rec + (size_t)env * kObsWords;
+    // point `lane` (a locust) and point 64 + lane (locusts 64..79, agents 80..89: lanes 0..25)
+    const int id1 = 64 + lane, c1 = id1 >= 80 ? 1 : 0;
+    int h0, w0, h1 = 255, w1 = 0, ph = 0, pw = 0;
+    {
+        const uint8_t *b = lbins + ((size_t)env * 80 + lane) * 2;
+        h0 = b[0]; w0 = b[1];
+        if (lane < 26) {
+            const uint8_t *b1 = c1 ? abins + ((size_t)env * 10 + (id1 - 80)) * 2 : lbins + ((size_t)env * 80 + id1) * 2;
+            h1 = b1[0]; w1 = b1[1];
+        }
+        if (lane < 40) { ph = pos[((size_t)env * 10 + (lane >> 2)) * 2]; pw = pos[((size_t)env * 10 + (lane >> 2)) * 2 + 1]; }
+    }
+    const bool v0 = h0 != 255, v1 = h1 != 255;
+    obs_hash_clear(L, lane);
+    (&L.bm[0][0])[lane] = 0u;
+    if (lane < 32) (&L.bm[0][0])[64 + lane] = 0u;
+    if (lane >= 48) L.pm[lane - 48] = 0u;
+    obs_wave_sync();
+    // the lowest point id in a (channel, bin) lists it, with the bin's count
+    const int s0 = v0 ? obs_hash_add(L, (unsigned)(h0 * G + w0), (unsigned)lane) : 0;
+    const int s1 = v1 ? obs_hash_add(L, (unsigned)((c1 << 16) | (h1 * G + w1)), (unsigned)id1) : 0;
+    obs_wave_sync();
+    const bool f0 = v0 && L.low[s0] == (unsigned)lane, f1 = v1 && L.low[s1] == (unsigned)id1;
+    const int n0 = __popcll(__ballot(f0)) + __popcll(__ballot(f1 && !c1)), nall = __popcll(__ballot(f0)) + __popcll(__ballot(f1));
+    // touched pixels: the four conv1 outputs whose window holds a listed bin
+#pragma unroll
+    for (int c = 0; c < (PARTS & 1 ? 4 : 0); ++c) {
+        const int oya = (h0 >> 2) - (c >> 1), oxa = (w0 >> 2) - (c & 1), oyb = (h1 >> 2) - (c >> 1), oxb = (w1 >> 2) - (c & 1);
+        if (f0 && oya >= 0 && oya < 20 && oxa >= 0 && oxa < 20) atomicOr(&L.pm[(oya * 20 + oxa) >> 5], 1u << ((oya * 20 + oxa) & 31));
+        if (f1 && oyb >= 0 && oyb < 20 && oxb >= 0 && oxb < 20) atomicOr(&L.pm[(oyb * 20 + oxb) >> 5], 1u << ((oyb * 20 + oxb) & 31));
+    }
+    const int k0 = (int)L.cnt[s0], k1 = (int)L.cnt[s1];
+    if (PARTS & 2) {
+        // first order: bucket (channel, q), inside a bucket by point id
+        const int bk0 = (h0 & 3) * 4 + (w0 & 3), bk1 = c1 * 16 + (h1 & 3) * 4 + (w1 & 3);
+        if (f0) atomicOr(&L.bm[bk0][lane >> 5], 1u << (lane & 31));
+        if (f1) atomicOr(&L.bm[bk1][2], 1u << lane);
+        obs_wave_sync();
+        int bc = lane < 32 ? __popc(L.bm[lane][0]) + __popc(L.bm[lane][1]) + __popc(L.bm[lane][2]) : 0, incl = bc;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d);
+            if (lane >= d) incl += o;
+        }
+        if (lane < 33) {      // exclusive prefix: the bucket's offset; lane 32: the total
+            L.off[lane] = (unsigned)(incl - bc);
+            reinterpret_cast<uint8_t *>(r + kObsOff)[lane] = (uint8_t)(incl - bc);
+        }
+        obs_wave_sync();
+        if (f0) {
+            const int at = (int)L.off[bk0] + (lane >= 32 ? __popc(L.bm[bk0][0]) : 0) + __popc(L.bm[bk0][lane >> 5] & ((1u << (lane & 31)) - 1u));
+            r[kObsList + at] = (unsigned)(h0 | (w0 << 8) | (k0 << 20));
+        }
+        if (f1) {
+            const int at = (int)L.off[bk1] + __popc(L.bm[bk1][0]) + __popc(L.bm[bk1][1]) + __popc(L.bm[bk1][2] & ((1u << lane) - 1u));
+            r[kObsList + at] = (unsigned)(h1 | (w1 << 8) | (c1 << 16) | (k1 << 20));
+        }
+    }
+    const unsigned nlist = (unsigned)(n0 | (nall << 8));
+    if (PARTS & 1) {
+        obs_wave_sync();
+        if (lane < 13) r[kObsPm + lane] = L.pm[lane];
+        {   // second order: an entry's place is the number of listed entries with a smaller (h, channel, w); the keys are distinct
+            const int q0 = f0 ? (h0 << 9) | w0 : 0x7FFFFFFF, q1 = f1 ? (h1 << 9) | (c1 << 8) | w1 : 0x7FFFFFFF;
+            int r0 = 0, r1 = 0;
+            for (int j = 0; j < 64; ++j) {
+                const int kj = __builtin_amdgcn_readlane(q0, j);
+                r0 += kj < q0 ? 1 : 0; r1 += kj < q1 ? 1 : 0;
+            }
+            for (int j = 0; j < 26; ++j) {
+                const int kj = __builtin_amdgcn_readlane(q1, j);
+                r0 += kj < q0 ? 1 : 0; r1 += kj < q1 ? 1 : 0;
+            }
+            if (f0) r[kObsList2 + r0] = (unsigned)(h0 | (w0 << 8) | (k0 << 20));
+            if (f1) r[kObsList2 + r1] = (unsigned)(h1 | (w1 << 8) | (c1 << 16) | (k1 << 20));
+        }
+    }
+    if (!(PARTS & 2)) {      // the forward's record: header without the agents' slots
+        if (lane == 0) r[0] = nlist;
+        return;
+    }
+    // the 40 (agent, cover) candidate pixels and their distinct-pixel table, in candidate order (as agent_ds_kernel builds them):
+    // a pixel's slot is the rank of its first candidate among the first candidates
+    int px = -1;
+    {
+        int oy1, ox1, tap1;
+        if (lane < 40 && conv1_cover(ph, pw, lane & 3, oy1, ox1, tap1)) px = (oy1 * 20 + ox1) | (tap1 << 16);
+        if (lane < 40) r[kObsPix + lane] = (unsigned)px;
+    }
+    obs_wave_sync();      // every lane has read the bins' table
+    obs_hash_clear(L, lane);
+    obs_wave_sync();
+    const int sp = px >= 0 ? obs_hash_add(L, (unsigned)(px & 0xFFFF), (unsigned)lane) : 0;
+    obs_wave_sync();
+    const int firstlane = px >= 0 ? (int)L.low[sp] : lane;
+    const bool first = px >= 0 && firstlane == lane;
+    const unsigned long long fb = __ballot(first);
+    const int rank = __popcll(fb & ((1ull << lane) - 1ull));
+    const int slot = __shfl(rank, firstlane);
+    if (lane < 40) reinterpret_cast<uint8_t *>(r + kObsCslot)[lane] = (uint8_t)(px >= 0 ? slot : 255);
+    if (first) reinterpret_cast<unsigned short *>(r + kObsSlotpix)[rank] = (unsigned short)(px & 0xFFFF);
+    if (lane == 0) r[0] = nlist | ((unsigned)__popcll(fb) << 16);
+}
+static int obs_index(grl_net *net, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, int nenv, unsigned *rec, hipStream_t st, int parts) {
+    const dim3 g((nenv + 3) / 4), b(256);
+    const int G = net->h->cfg.grid_size;
+    if (parts == 1) hipLaunchKernelGGL(obs_index_kernel<1>, g, b, 0, st, lb, ab, pos, nenv, G, rec);
+    else if (parts == 2) hipLaunchKernelGGL(obs_index_kernel<2>, g, b, 0, st, lb, ab, pos, nenv, G, rec);
+    else hipLaunchKernelGGL(obs_index_kernel<3>, g, b, 0, st, lb, ab, pos, nenv, G, rec);
+    NET_HIP(net, hipGetLastError());
+    return GRL_OK;
+}
+// conv1_sparse_shared_kernel (net_conv.hip) from the index record: the touched-pixel mask comes out of the record, and a half wave builds its
+// pixel's tap list from the env's (h, channel, w)-sorted entries -- a window test per entry, a ballot, and the list is in (ky, c, kx) order --
+// instead of scanning 32 count words of two 84 x 84 byte grids.  The grids (14 KB of LDS), their atomics and the take-back pass are gone,
+// and three workgroup barriers per env are left of five.  Same terms in the same order: bit-identical sraw.
+__global__ __launch_bounds__(256) void conv1_sparse_indexed_kernel(const unsigned *__restrict__ rec, const float *__restrict__ w1,
+                                                                   const float *__restrict__ b1, float *__restrict__ sraw,
+                                                                   const unsigned *__restrict__ nmask, int nenv) {
+    __shared__ unsigned need[4], pm[13];            // blocks anybody reads (nmask == nullptr: all); touched pixels
+    __shared__ float vtab[2][96];                   // count / 80, count / 10 as the reference forms them (float64 division rounded to float32)
+    __shared__ unsigned short plist[400];
+    __shared__ unsigned short evl[8][128];          // per half wave: the non-zero taps of its pixel, in order
+    __shared__ unsigned lst[96];                    // the env's entries in (h, channel, w) order
+    __shared__ int ntouched, nlist;
+    __shared__ __attribute__((aligned(16))) float wl[64 * 2 * 32];      // the two count channels' kernels [tap][c][co]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 64 * 2 * 8; i += 256) {
+        const int t = i >> 4, c = (i >> 3) & 1, j = i & 7;
+        reinterpret_cast<float4 *>(wl)[i] = *reinterpret_cast<const float4 *>(w1 + (t * 3 + c) * 32 + j * 4);
+    }
+    if (tid >= 64 && tid < 64 + 81) vtab[0][tid - 64] = (float)((double)(tid - 64) / 80.0);
+    if (tid >= 160 && tid < 160 + 11) vtab[1][tid - 160] = (float)((double)(tid - 160) / 10.0);
+    // this lane's word of the first env's record; inside the loop: of the next one
+    unsigned nword = 0u, nneed = 0xFFFFFFFFu;
+    auto fetch = [&](int e) {
+        if (e < nenv) {
+            const unsigned *r = rec + (size_t)e * kObsWords;
+            if (tid < 90) nword = r[kObsList2 + tid];      // (words past the env's count are never used)
+            else if (tid >= 96 && tid < 109) nword = r[kObsPm + tid - 96];
+            else if (tid == 128) nword = (r[0] >> 8) & 255u;
+            if (tid < 4 && nmask) nneed = nmask[(size_t)e * 4 + tid];
+        }
+    };
+    fetch(blockIdx.x);
+    for (int env = blockIdx.x; env < nenv; env += gridDim.x) {
+        __syncthreads();      // the previous env's walk is over (evl, plist, pm, need, lst)
+        if (tid < 90) lst[tid] = nword;
+        else if (tid >= 96 && tid < 109) pm[tid - 96] = nword;
+        else if (tid == 128) nlist = (int)nword;
+        if (tid < 4) need[tid] = nmask ? nneed : 0xFFFFFFFFu;
+        fetch(env + gridDim.x);
+        __syncthreads();
+        for (int p = tid; p < 400; p += 256)
+            if ((pm[p >> 5] >> (p & 31)) & 1u) {
+                int before = __popc(pm[p >> 5] & ((1u << (p & 31)) - 1u));
+                for (int w = 0; w < (p >> 5); ++w) before += __popc(pm[w]);
+                plist[before] = (unsigned short)p;
+            }
+        if (tid == 0) {
+            int n = 0;
+            for (int w = 0; w < 13; ++w) n += __popc(pm[w]);
+            ntouched = n;
+        }
+        // the untouched pixels somebody reads: b1
+        float4 *out = reinterpret_cast<float4 *>(sraw + (size_t)env * 12800);
+        for (int item = tid; item < 3200; item += 256) {
+            const int pix = item >> 3, oy = pix / 20, ox = pix - oy * 20, blk = (oy >> 1) * 10 + (ox >> 1);
+            if (!((need[blk >> 5] >> (blk & 31)) & 1u) || ((pm[pix >> 5] >> (pix & 31)) & 1u)) continue;
+            out[item] = *reinterpret_cast<const float4 *>(b1 + (item & 7) * 4);
+        }
+        __syncthreads();
+        // A touched pixel gets half a wave, one output channel per lane.  Lane l tests entries l, 32 + l, 64 + l against the pixel's window; the
+        // entries inside keep their order, so their places are the set bits below them in the half wave's ballot.
+        const int co = tid & 31, hw = tid >> 5, nt = ntouched, n = nlist, sh = (tid & 32);
+        unsigned short *ev = evl[hw];
+        for (int t = hw; t < ((nt + 7) & ~7); t += 8) {      // whole waves run every round (the ballots)
+            const bool live = t < nt;
+            const int pix = live ? plist[t] : 0, oy = pix / 20, ox = pix - oy * 20;
+            int total = 0;
+            for (int i0 = 0; i0 < n; i0 += 32) {
+                const int i = i0 + co;
+                const unsigned e = i < n ? lst[i] : 0u;
+                const int ky = (int)(e & 255u) - 4 * oy, kx = (int)((e >> 8) & 255u) - 4 * ox, c = (int)((e >> 16) & 1u);
+                const bool in = live && i < n && (unsigned)ky < 8u && (unsigned)kx < 8u;
+                const unsigned m = (unsigned)(__ballot(in) >> sh);
+                if (in) ev[total + __popc(m & ((1u << co) - 1u))] = (unsigned short)((((ky * 8 + kx) * 2 + c) << 7) | (e >> 20));      // tap-and-channel row of wl, count
+                total += __popc(m);
+            }
+            obs_wave_sync();      // the half wave's list is read by all its lanes
+            float acc = b1[co];
+            for (int e = 0; e < total; ++e) {
+                const int code = ev[e];
+                acc += vtab[(code >> 7) & 1][code & 127] * wl[(code >> 7) * 32 + co];
+            }
+            if (live) sraw[(size_t)env * 12800 + pix * 32 + co] = acc;
+            obs_wave_sync();      // ... before the next pixel's list overwrites it
+        }
+    }
+}
+static int conv1_sparse_indexed_grid() {
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)conv1_sparse_indexed_kernel, 256, 0) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+        hipGetDeviceProperties(&prop, dev) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        return 1024;
+    }
+    return per_cu * prop.multiProcessorCount;
+}
 static int trunk_index(grl_net *net, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, int nenv) {
     hipStream_t st = net->h->stream;
     const int nwg = (nenv + TRUNK_ENVS - 1) / TRUNK_ENVS;
@@ -917,6 +1183,15 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
     if (side) NET_HIP(net, hipEventRecord(net->ev_side2[net->cur_lane], st));      // the trunk's masks are there: the item sort reads cmask
     // list form: sraw is written where somebody reads it -- the 2 x 2 pixel blocks under the affected conv2 outputs' windows
     static const int hgc1 = conv1_sparse_grid();      // one resident wave of workgroups (they stride over the envs)
+    if (net->obs_index) {
+        // The record's first consumer is the first kernel of the env-level trunk, so the record is written on the lane itself: the index
+        // side stream only starts behind the trunk (below) and would make conv1 wait for an event round trip.  (Every pixel of sraw is the
+        // sum of its own window, whatever workgroup computes it: this kernel's grid is its own.)
+        static const int hgc1i = conv1_sparse_indexed_grid();
+        if (int rc = obs_index(net, lb, ab, pos, nenv, net->obsrec, st, 1)) return rc;
+        hipLaunchKernelGGL(conv1_sparse_indexed_kernel, dim3(nenv < hgc1i ? nenv : hgc1i), dim3(256), 0, st, (const unsigned *)net->obsrec, P + ConvOffsets::c1w,
+                           P + ConvOffsets::c1b, net->sraw, trunk ? (const unsigned *)net->tnmask : (const unsigned *)nullptr, nenv);
+    } else
     hipLaunchKernelGGL(conv1_sparse_shared_kernel, dim3(nenv < hgc1 ? nenv : hgc1), dim3(256), 0, st, lb, ab, P + ConvOffsets::c1w, P + ConvOffsets::c1b,
                        net->h->cfg.grid_size, net->sraw, trunk ? (const unsigned *)net->tnmask : (const unsigned *)nullptr, nenv);
     if (trunk) {      // the affected rows; the rest is the background row (trunk_background), filled
@@ -1283,10 +1558,16 @@ __global__ __launch_bounds__(256) void gather_t2_kernel(const float *__restrict_
 // computed and never read here -- only the 40 candidate pixels are; the distinct-pixel table is built by the 40 candidate lanes with
 // one ballot instead of a 40-step chain on thread 0 behind a 400-entry map; a lane owns four channels (16-byte loads of tt / sraw /
 // w1 and of the dS rows, which are fetched as soon as the pixel table is known and added after the fold).
-__global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__ sraw, const uint8_t *__restrict__ pos,
-                                                       const float *__restrict__ tt, int npad, float *__restrict__ gt,
-                                                       const float *__restrict__ w1, int nenv, float *__restrict__ slab1h,
-                                                       float *__restrict__ slab1b) {
+// IDX (agent_ds_indexed_kernel): the candidate and distinct-pixel tables come out of the env's index record (obs_index_kernel) instead of
+// a 40-step shuffle chain behind a barrier, and the fold keeps ONE barrier in front of it instead of one per agent: it runs on one wave,
+// whose LDS accesses the hardware executes in order, and within one agent the four covers touch four different taps and pixels (cover
+// (dy, dx) is pixel (h/4 - dy, w/4 - dx) and tap (h%4 + 4 dy, w%4 + 4 dx)), so no two lanes of a step meet in acc1h or corr.
+// Same values, same order of additions; 44 -> 42 us per 8 192-env chunk: the barriers were not what the kernel waits for.
+template <bool IDX>
+__device__ __forceinline__ void agent_ds_body(const float *__restrict__ sraw, const uint8_t *__restrict__ pos,
+                                              const float *__restrict__ tt, int npad, float *__restrict__ gt,
+                                              const float *__restrict__ w1, int nenv, float *__restrict__ slab1h,
+                                              float *__restrict__ slab1b, const unsigned *__restrict__ rec) {
     __shared__ __attribute__((aligned(16))) float acc1h[64 * 32];
     __shared__ __attribute__((aligned(16))) float tl[10 * 128];        // masked T2 values: [agent][c][ci] for the agent's own mask ...
     __shared__ __attribute__((aligned(16))) float tsh[10 * 128];       // ... and for the shared mask
@@ -1302,7 +1583,14 @@ __global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__
         __syncthreads();
         const float *senv = sraw + (size_t)env * 12800;
         float *genv = gt + (size_t)env * 12800;
-        if (tid < 64) {      // the 40 (agent, candidate) conv1 pixels and their distinct-pixel table, in candidate order
+        const unsigned *r = IDX ? rec + (size_t)env * kObsWords : nullptr;
+        if (IDX) {      // wave 0 keeps its fold's tables in LDS (it alone reads them there); everybody else reads the record
+            if (tid < 40) {
+                pix[tid] = (int)r[kObsPix + tid];
+                const int cs = reinterpret_cast<const uint8_t *>(r + kObsCslot)[tid];
+                cslotid[tid] = cs == 255 ? -1 : cs;
+            }
+        } else if (tid < 64) {      // the 40 (agent, candidate) conv1 pixels and their distinct-pixel table, in candidate order
             int px = -1;
             if (tid < 40) {
                 const int a = tid >> 2, c = tid & 3;
@@ -1325,14 +1613,18 @@ __global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__
             if (first) slotpix[rank] = p0;
             if (tid == 0) nslots = __popcll(fb);
         }
-        __syncthreads();
+        if (!IDX) __syncthreads();
         // the dS rows of the distinct pixels (<= 40 x 8 lanes: two passes), in flight over the item pass and the fold
-        const int ns8 = nslots * 8;
+        const int ns8 = (IDX ? (int)((r[0] >> 16) & 255u) : nslots) * 8;
+        int spx[2] = {0, 0};
         float4 gv[2] = {zero4, zero4};
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = tid + 256 * r;
-            if (i < ns8) gv[r] = *reinterpret_cast<const float4 *>(genv + slotpix[i >> 3] * 32 + c4);
+        for (int r2 = 0; r2 < 2; ++r2) {
+            const int i = tid + 256 * r2;
+            if (i < ns8) {
+                spx[r2] = IDX ? (int)reinterpret_cast<const unsigned short *>(r + kObsSlotpix)[i >> 3] : slotpix[i >> 3];      // (IDX: kept for the write-back)
+                gv[r2] = *reinterpret_cast<const float4 *>(genv + spx[r2] * 32 + c4);
+            }
         }
         // (agent a, candidate c, four channels) items: 320 lanes, two passes with their loads in flight together
         float4 tv[2], sv[2], wv[2];
@@ -1340,7 +1632,7 @@ __global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int it = tid + 256 * r, ac = it >> 3;      // ac = a * 4 + c
-            const int px = it < 320 ? pix[ac] : -1;
+            const int px = it < 320 ? (IDX ? (int)rec[(size_t)env * kObsWords + kObsPix + ac] : pix[ac]) : -1;
             on[r] = px >= 0;
             tv[r] = sv[r] = wv[r] = zero4;
             if (on[r]) {
@@ -1363,7 +1655,8 @@ __global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__
         }
         for (int i = tid; i < ns8; i += 256) reinterpret_cast<float4 *>(corr)[i] = zero4;
         for (int a = 0; a < 10; ++a) {      // fold in agent order (two agents may share a pixel or a tap)
-            __syncthreads();
+            if (!IDX || a == 0) __syncthreads();
+            else obs_wave_sync();      // keeps the compiler from moving an agent's LDS reads above the previous agent's writes
             if (tid < 32) {
                 const int ac = a * 4 + (tid >> 3), px = pix[ac];
                 if (px >= 0) {
@@ -1383,7 +1676,7 @@ __global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__
             const int i = tid + 256 * r;
             if (i < ns8) {
                 const float4 c = reinterpret_cast<const float4 *>(corr)[i];
-                *reinterpret_cast<float4 *>(genv + slotpix[i >> 3] * 32 + c4) = make_float4(gv[r].x + c.x, gv[r].y + c.y, gv[r].z + c.z, gv[r].w + c.w);
+                *reinterpret_cast<float4 *>(genv + (IDX ? spx[r] : slotpix[i >> 3]) * 32 + c4) = make_float4(gv[r].x + c.x, gv[r].y + c.y, gv[r].z + c.z, gv[r].w + c.w);
                 csc.x += c.x; csc.y += c.y; csc.z += c.z; csc.w += c.w;
             }
         }
@@ -1398,6 +1691,18 @@ __global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__
         for (int g = 0; g < 32; ++g) s += tsh[(g * 8 + (tid >> 2)) * 4 + (tid & 3)];
         slab1b[(size_t)blockIdx.x * 32 + tid] = s;
     }
+}
+__global__ __launch_bounds__(256) void agent_ds_kernel(const float *__restrict__ sraw, const uint8_t *__restrict__ pos,
+                                                       const float *__restrict__ tt, int npad, float *__restrict__ gt,
+                                                       const float *__restrict__ w1, int nenv, float *__restrict__ slab1h,
+                                                       float *__restrict__ slab1b) {
+    agent_ds_body<false>(sraw, pos, tt, npad, gt, w1, nenv, slab1h, slab1b, nullptr);
+}
+__global__ __launch_bounds__(256) void agent_ds_indexed_kernel(const float *__restrict__ sraw, const unsigned *__restrict__ rec,
+                                                               const float *__restrict__ tt, int npad, float *__restrict__ gt,
+                                                               const float *__restrict__ w1, int nenv, float *__restrict__ slab1h,
+                                                               float *__restrict__ slab1b) {
+    agent_ds_body<true>(sraw, nullptr, tt, npad, gt, w1, nenv, slab1h, slab1b, rec);
 }
 
 // (onehot_reduce_kernel: its body is a job of reduce_batch_kernel since round 4, net_reduce.inc)

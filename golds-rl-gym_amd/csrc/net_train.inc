@@ -528,6 +528,95 @@ __global__ __launch_bounds__(256, 6) void conv1_wgrad_shared_kernel(const uint8_
     }
 }
 
+// The same sums from the env's index record (obs_index_kernel, net_shared.inc): the bucket (channel, q) of this thread is a range of the
+// record's list -- the 16 lanes of a q read one address -- so the per-env set-up above (three barriers, the duplicate scan, the ballots,
+// 10.7 KB of LDS) is gone and nothing in the kernel waits for another wave.  The next env's bucket ranges and the first kWgBins entries of
+// each bucket are requested before the current env is walked.  Order of additions per accumulator as above (bins by lowest point id,
+// envs in stride order, workgroups in index order): launched on the same grid, it writes the same slabs bit for bit.
+// 117 -> 77 us per 8 192-env chunk (single stream); what is left is the chain list entry -> dS rows -> adds of the ~5 envs of a workgroup.
+struct WgradBuckets {
+    unsigned range;      // lo | hi << 8 of channel 0's bucket, << 16 of channel 1's
+    unsigned e[2][kWgBins];
+};
+__device__ __forceinline__ WgradBuckets wgrad_fetch(const unsigned *__restrict__ rec, int env, int nenv, int q) {
+    WgradBuckets b;
+    const unsigned *r = rec + (size_t)(env < nenv ? env : nenv - 1) * kObsWords;
+    const uint8_t *off = reinterpret_cast<const uint8_t *>(r + kObsOff);
+    b.range = 0u;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const unsigned lo = off[c * 16 + q], hi = env < nenv ? off[c * 16 + q + 1] : lo;
+        b.range |= (lo | (hi << 8)) << (16 * c);
+#pragma unroll
+        for (int u = 0; u < kWgBins; ++u) b.e[c][u] = lo + u < hi ? r[kObsList + lo + u] : 0u;
+    }
+    return b;
+}
+__global__ __launch_bounds__(256, 6) void conv1_wgrad_indexed_kernel(const unsigned *__restrict__ rec, const float *__restrict__ ds, int nenv,
+                                                                  double *__restrict__ slab64) {
+    const int tid = threadIdx.x;
+    const int q = tid >> 4, cp = tid & 15;      // this thread's tap class and output channels 2 cp, 2 cp + 1
+    double acc[4][2][2];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) (&acc[0][0][0])[i] = 0.0;
+    WgradBuckets nx = wgrad_fetch(rec, blockIdx.x, nenv, q);
+    for (int env = blockIdx.x; env < nenv; env += gridDim.x) {
+        const WgradBuckets cur = nx;
+        nx = wgrad_fetch(rec, env + gridDim.x, nenv, q);
+        const unsigned *list = rec + (size_t)env * kObsWords + kObsList;
+        const float *dsenv = ds + (size_t)env * 12800 + 2 * cp;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int lo = (cur.range >> (16 * c)) & 255, nb = (int)((cur.range >> (16 * c + 8)) & 255) - lo;
+            const double inv = c == 0 ? 80.0 : 10.0;
+            unsigned en[kWgBins];
+#pragma unroll
+            for (int u = 0; u < kWgBins; ++u) en[u] = cur.e[c][u];
+            for (int z0 = 0; z0 < nb; z0 += kWgBins) {      // kWgBins bins x four covers of 8-byte loads in flight, then added in list order
+                float2 v[kWgBins][4];
+                bool okc[kWgBins][4];
+                float val[kWgBins];
+                int ec[kWgBins];
+#pragma unroll
+                for (int u = 0; u < kWgBins; ++u) {      // ... and the next group's entries requested beside them
+                    ec[u] = (int)en[u];
+                    en[u] = z0 + kWgBins + u < nb ? list[lo + z0 + kWgBins + u] : 0u;
+                }
+#pragma unroll
+                for (int u = 0; u < kWgBins; ++u) {
+                    const int z = z0 + u;
+                    const int e = ec[u];
+                    const int hh = e & 255, ww = (e >> 8) & 255, kk = e >> 20;
+                    val[u] = (float)((double)kk / inv);
+#pragma unroll
+                    for (int cov = 0; cov < 4; ++cov) {
+                        const int oy = hh / 4 - (cov >> 1), ox = ww / 4 - (cov & 1);
+                        okc[u][cov] = z < nb && oy >= 0 && oy < 20 && ox >= 0 && ox < 20;
+                        v[u][cov] = *reinterpret_cast<const float2 *>(dsenv + (okc[u][cov] ? oy * 20 + ox : 0) * 32);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kWgBins; ++u)
+#pragma unroll
+                    for (int cov = 0; cov < 4; ++cov)
+                        if (okc[u][cov]) {
+                            acc[cov][c][0] += (double)(val[u] * v[u][cov].x);
+                            acc[cov][c][1] += (double)(val[u] * v[u][cov].y);
+                        }
+            }
+        }
+    }
+    // slab layout [tap = ky*8 + kx][c][co] with ky = h%4 + 4 dy, kx = w%4 + 4 dx
+#pragma unroll
+    for (int cov = 0; cov < 4; ++cov) {
+        const int ky = (q >> 2) + 4 * (cov >> 1), kx = (q & 3) + 4 * (cov & 1);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) slab64[(size_t)blockIdx.x * 4096 + ((ky * 8 + kx) * 2 + c) * 32 + 2 * cp + j] = acc[cov][c][j];
+    }
+}
+
 // (slab64_reduce_shared_kernel: its body is a job of reduce_batch_kernel since round 4, net_reduce.inc)
 
 __global__ void slab64_reduce_kernel(const double *__restrict__ slab, int chunks, int n, float *__restrict__ dst) {
@@ -812,6 +901,9 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     const bool have_heads = slot >= 0 && pmu && psg && pval;
     int rc = forward_chunk(net, lb, ab, pos, nenv, tb.cmu, tb.csigma, tb.cvs, slot >= 0, have_heads);
     if (rc) return rc;
+    // the observation's index record for conv1's backward helpers at the end of this pass: a small kernel, enqueued here so that it runs
+    // behind the GEMMs in between (lane scratch like the trunk lists: rebuilt per pass, not kept with the rollout)
+    if (net->shared_trunk && net->obs_index && (rc = obs_index(net, lb, ab, pos, nenv, net->obsrec, st, 2))) return rc;
     const float *hmu = have_heads ? pmu : tb.cmu, *hsg = have_heads ? psg : tb.csigma, *hvs = have_heads ? pval : tb.cvs;
     const HeadOff &ho = net->ho;
     const int HS = heads_slab(ho.A), NW = 1024 * ho.A + 2 * ho.A;      // NW: [muw|mub|sgw|sgb], contiguous in the flat vector
@@ -1146,8 +1238,13 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
             rq_push(net, RD_C2W, j);
         }
         float *slab1h = net->slab1h, *slab1b_ds = net->slab1b + (size_t)2 * 2048 * 64;
-        hipLaunchKernelGGL(agent_ds_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, pos, net->tt2, npad, net->gt, P + ConvOffsets::c1w,
-                           nenv, slab1h, slab1b_ds);
+        // (both forms on the parent kernels' grids: the workgroup an env falls to decides the order of the sums)
+        if (net->obs_index)
+            hipLaunchKernelGGL(agent_ds_indexed_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, (const unsigned *)net->obsrec, net->tt2, npad, net->gt,
+                               P + ConvOffsets::c1w, nenv, slab1h, slab1b_ds);
+        else
+            hipLaunchKernelGGL(agent_ds_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, pos, net->tt2, npad, net->gt, P + ConvOffsets::c1w,
+                               nenv, slab1h, slab1b_ds);
         {
             RJob j{};
             j.kind = RJ_ONEHOT; j.blocks = 2048 / 16; j.i0 = dblocks; j.p0 = slab1h; j.d0 = Gr + ConvOffsets::c1w;
@@ -1161,9 +1258,17 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
         // dependent steps, so its time falls with the workgroups in flight -- 768: 175 us per 8 192-env chunk, 1 024: 143, 1 280: 121-125, 1 536:
         // 116 (round 4; the 32 KB LDS accumulators that had made 1 280 slower than 1 024 in round 3 are registers since then)
         static const int hgw = resident_grid((const void *)conv1_wgrad_shared_kernel, 1536);
+        // conv1_wgrad_indexed_kernel runs on THIS grid too, taken from the other kernel's occupancy on purpose: the workgroup an env falls to
+        // decides the order of the slab sums, and GRL_OBS_INDEX=off / on are held bit for bit against each other (tests/test_gpu_obs_index.py).
+        // Both kernels are bound to six waves per SIMD, so the grid is one resident wave of workgroups for either.  Without that test the
+        // barrier-free kernel could take fewer, wider workgroups (fewer 32 KB slabs to write and reduce): not measured.
         const int wblocks = nenv < hgw ? nenv : hgw;
-        hipLaunchKernelGGL(conv1_wgrad_shared_kernel, dim3(wblocks), dim3(256), 0, st, lb, ab, (const float *)net->gt, nenv,
-                           net->h->cfg.grid_size, net->slab64);
+        if (net->obs_index)
+            hipLaunchKernelGGL(conv1_wgrad_indexed_kernel, dim3(wblocks), dim3(256), 0, st, (const unsigned *)net->obsrec, (const float *)net->gt, nenv,
+                               net->slab64);
+        else
+            hipLaunchKernelGGL(conv1_wgrad_shared_kernel, dim3(wblocks), dim3(256), 0, st, lb, ab, (const float *)net->gt, nenv,
+                               net->h->cfg.grid_size, net->slab64);
         RJob j{};
         j.kind = RJ_SLAB64; j.blocks = 4096 / 16; j.i0 = wblocks; j.p0 = net->slab64; j.d0 = Gr + ConvOffsets::c1w;
         rq_push(net, RD_C1W_CNT, j);

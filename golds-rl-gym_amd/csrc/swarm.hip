@@ -12,6 +12,8 @@
 // actions 80 read; x 1280 + xa 160 + bins 200 + reward/done/elapsed ~17 written.
 #include "common.h"
 #include "rng.h"
+#include <stdlib.h>
+#include <string.h>
 
 namespace grl {
 
@@ -79,37 +81,75 @@ __device__ __forceinline__ void x_update_f32v(double &x, double &y, float vx, fl
     if (y <= 0) y = 0;
 }
 
-template <bool FAST>
+// How pair_term evaluates the exact path's three quotients.  MATH_EXACT and MATH_REFDIV give the same bits (see pair_term);
+// MATH_REFDIV keeps the compiler's three IEEE divisions so that tests can hold the two against each other (GRL_SWARM_DIV=ref).
+enum { MATH_EXACT = 0, MATH_FAST = 1, MATH_REFDIV = 2 };
+
+template <int MATH>
 __device__ __forceinline__ void pair_term(double sx, double sy, double xj, double yj, double &t0, double &t1) {
     double dx = sx - xj, dy = sy - yj;
     double d = sqrt(dx * dx + dy * dy);
-    if (FAST) {
+    if (MATH == MATH_FAST) {
         double t = exp(d * -0.1);
         double t2 = t * t, t4 = t2 * t2, t5 = t4 * t, t10 = t5 * t5;
         double w = (FATT * t - t10) / (d + 0.000001);
         t0 = w * dx;
         t1 = w * dy;
-    } else {
+    } else if (MATH == MATH_REFDIV) {
         // s(r) = F*exp(-r/L) - exp(-r)   (multiagent.py:65-68); term = s*dx/(r+1e-6) (:103-104)
         double s = FATT * exp(-d / LATT) - exp(-d);
         double den = d + 0.000001;
         t0 = s * dx / den;
         t1 = s * dy / den;
+    } else {
+        // The same three correctly rounded quotients as MATH_REFDIV, from one reciprocal instead of three divisions.  An IEEE
+        // fp64 division expands to div_scale x2, rcp, two Newton steps on the reciprocal, quotient, one residual correction
+        // (div_fmas) and div_fixup.  Below is that sequence without the scaling and the fix-up, and with the reciprocal of den
+        // shared by both numerators.  Scaling and fix-up only act when an operand or the quotient is zero, subnormal, infinite,
+        // NaN or within ~2^100 of the exponent limits; here they are identities:
+        //   den = d + 1e-6 lies in [1e-6, d_max + 1e-6]; |s| <= 1 and |dx|, |dy| <= d bound a numerator s*dx by d_max.
+        //   A nonzero numerator is a normal number far from the limits as long as d stays below a few hundred: s = F exp(-d/10) -
+        //   exp(-d) is ~0.5 exp(-d/10) there (2e-44 at d = 1e3; near its root at d ~ 0.77 it is a difference of two doubles of
+        //   (0, 1), at least ~1e-17 unless exactly zero), and a nonzero dx is at least an ulp of a coordinate (~1e-19).  The claim
+        //   is made for d <= ~5e3, where |s| >= 1e-218: beyond d ~ 7e3 s itself goes subnormal and the unscaled sequence may differ
+        //   from `/` in the last bit.  Nothing bounds a locust's x in x_update, but an episode is at most max_episode_steps long
+        //   (gym's TimeLimit; 128 for Swarm-v0), the reset puts all points into the unit box and a step moves a point by
+        //   dt |v| with |v| <= 1 + 90: two points are never 5e3 apart.  (max_episode_steps = 0 lifts the cap: the long-range force is
+        //   attractive, so the swarm stays together in practice, but past d ~ 7e3 a quotient may then differ from `/` in its last bit.)
+        //   A zero numerator (dx = 0 or s = 0) gives a zero quotient, but +0 where the division gives -0 (fma(-den, -0, -0) =
+        //   +0).  That sign reaches no result: a zero term only decides the sign of a sum whose other terms are all zero, and
+        //   locust_velocity adds that sum to WIND or GRAV; -d / 10 only feeds exp().
+        // -d / 10: q = n * rn(1/10), one residual correction with the exact divisor (Markstein); rn(0.1) is the correctly
+        // rounded reciprocal of 10, for which the corrected quotient is correctly rounded for every n away from the limits.
+        // Held to `/` on 10^7 random operands plus the edge values by tests/test_swarm_div_exact.py, and on the device by
+        // tests/test_gpu_swarm_div.py.  The fmas are explicit: the file is compiled with -ffp-contract=off.
+        double n10 = -d;
+        double q10 = n10 * 0.1;
+        q10 = __builtin_fma(__builtin_fma(-LATT, q10, n10), 0.1, q10);
+        double s = FATT * exp(q10) - exp(-d);
+        double den = d + 0.000001;
+        double y = __builtin_amdgcn_rcp(den);
+        y = __builtin_fma(y, __builtin_fma(-den, y, 1.0), y);
+        y = __builtin_fma(y, __builtin_fma(-den, y, 1.0), y);
+        double n0 = s * dx, n1 = s * dy;
+        double q0 = n0 * y, q1 = n1 * y;
+        t0 = __builtin_fma(__builtin_fma(-den, q0, n0), y, q0);
+        t1 = __builtin_fma(__builtin_fma(-den, q1, n1), y, q1);
     }
 }
 
 // v_calculate for one target locust (multiagent.py:100-113).  Sums follow numpy's pairwise
 // order for n=80 and n=10: 8 strided accumulators, a fixed tree, then the tail.
-template <bool FAST>
+template <int MATH>
 __device__ __forceinline__ void locust_velocity(const double2 *src, double xj, double yj, double &vx, double &vy) {
     double a0[8], a1[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) pair_term<FAST>(src[k].x, src[k].y, xj, yj, a0[k], a1[k]);
+    for (int k = 0; k < 8; ++k) pair_term<MATH>(src[k].x, src[k].y, xj, yj, a0[k], a1[k]);
     for (int i = 8; i < N_LOCUSTS; i += 8) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             double t0, t1;
-            pair_term<FAST>(src[i + k].x, src[i + k].y, xj, yj, t0, t1);
+            pair_term<MATH>(src[i + k].x, src[i + k].y, xj, yj, t0, t1);
             a0[k] += t0;
             a1[k] += t1;
         }
@@ -117,13 +157,13 @@ __device__ __forceinline__ void locust_velocity(const double2 *src, double xj, d
     double ll0 = ((a0[0] + a0[1]) + (a0[2] + a0[3])) + ((a0[4] + a0[5]) + (a0[6] + a0[7]));
     double ll1 = ((a1[0] + a1[1]) + (a1[2] + a1[3])) + ((a1[4] + a1[5]) + (a1[6] + a1[7]));
 #pragma unroll
-    for (int k = 0; k < 8; ++k) pair_term<FAST>(src[N_LOCUSTS + k].x, src[N_LOCUSTS + k].y, xj, yj, a0[k], a1[k]);
+    for (int k = 0; k < 8; ++k) pair_term<MATH>(src[N_LOCUSTS + k].x, src[N_LOCUSTS + k].y, xj, yj, a0[k], a1[k]);
     double al0 = ((a0[0] + a0[1]) + (a0[2] + a0[3])) + ((a0[4] + a0[5]) + (a0[6] + a0[7]));
     double al1 = ((a1[0] + a1[1]) + (a1[2] + a1[3])) + ((a1[4] + a1[5]) + (a1[6] + a1[7]));
 #pragma unroll
     for (int k = 8; k < N_AGENTS; ++k) {
         double t0, t1;
-        pair_term<FAST>(src[N_LOCUSTS + k].x, src[N_LOCUSTS + k].y, xj, yj, t0, t1);
+        pair_term<MATH>(src[N_LOCUSTS + k].x, src[N_LOCUSTS + k].y, xj, yj, t0, t1);
         al0 += t0;
         al1 += t1;
     }
@@ -135,7 +175,7 @@ __device__ __forceinline__ void locust_velocity(const double2 *src, double xj, d
 // Agent lanes (tid < 40) carry (actx, acty) = action BEFORE wind and (anx, any) raw noise; act32: the action came from a
 // float32 row and its wind / dt arithmetic is float32 (x_update_f32v).
 // On return L.p holds the new positions of all 90 points, L.rew[el] the reward; ends on a barrier.
-template <bool FAST>
+template <int MATH>
 __device__ __forceinline__ void block_step(SwarmLds &L, int tid, int el, int j, double &xj, double &yj, double actx,
                                            double acty, double anx, double any, double pnx, double pny, bool act32 = false,
                                            bool wind = true) {
@@ -150,7 +190,7 @@ __device__ __forceinline__ void block_step(SwarmLds &L, int tid, int el, int j, 
     L.p[el][j] = make_double2(xj, yj);
     __syncthreads();
     double vx, vy;
-    locust_velocity<FAST>(L.p[el], xj, yj, vx, vy);
+    locust_velocity<MATH>(L.p[el], xj, yj, vx, vy);
     L.en[el][j] = vx * vx + vy * vy;
     x_update(xj, yj, vx, vy, pnx, pny);
     __syncthreads();
@@ -188,13 +228,9 @@ __device__ __forceinline__ int count_edges_le(double v, double lo, double hi, do
 
 enum { MODE_STEP = 0, MODE_OBSERVE = 1, MODE_RESET = 2 };
 
-template <int MODE, bool FAST>
-// The step's pair loop is a long chain of dependent fp64 operations (two exp polynomials, three divisions per pair): five waves per SIMD
-// instead of the four its 124 registers allowed hide more of it -- 0.976 -> 0.875 ms per 32 768-env step with 96 registers and 24 bytes of
-// scratch per lane (round 4).  Six waves (80 registers, 104 bytes of scratch) measured 0.859 ms but tripled the kernel's HBM-side bytes
-// (each lane writes and reads its spill slots once: 488 MB per launch against 151 MB algorithmic); 7 / 8 waves: 0.875 / 0.863 ms.
-// The second launch bound is waves per SIMD.
-__global__ __launch_bounds__(SWARM_TPB, MODE == 0 ? 5 : 1) void swarm_kernel(SwarmParams P) {
+// The body of swarm_kernel / swarm_kernel_refdiv; MATH selects pair_term's arithmetic.
+template <int MODE, int MATH>
+__device__ __forceinline__ void swarm_body(const SwarmParams &P) {
     __shared__ SwarmLds L;
     __shared__ int env_of[SWARM_EPB];
     const int tid = threadIdx.x;
@@ -251,7 +287,7 @@ __global__ __launch_bounds__(SWARM_TPB, MODE == 0 ? 5 : 1) void swarm_kernel(Swa
             double2 n = reinterpret_cast<const double2 *>(P.anoise)[(size_t)aenv * N_AGENTS + a];
             anx = n.x; any = n.y;
         }
-        block_step<FAST>(L, tid, el, j, xj, yj, actx, acty, anx, any, pnx, pny, P.actions64 == nullptr, P.no_wind == 0);
+        block_step<MATH>(L, tid, el, j, xj, yj, actx, acty, anx, any, pnx, pny, P.actions64 == nullptr, P.no_wind == 0);
         if (active) reinterpret_cast<double2 *>(P.x)[(size_t)env * N_LOCUSTS + j] = make_double2(xj, yj);
         if (aactive) reinterpret_cast<double2 *>(P.xa)[(size_t)aenv * N_AGENTS + a] = L.p[ea][N_LOCUSTS + a];
         if (active && j == 0) {
@@ -354,7 +390,7 @@ __global__ __launch_bounds__(SWARM_TPB, MODE == 0 ? 5 : 1) void swarm_kernel(Swa
                     pn10x = pnx; pn10y = pny; an10x = anx; an10y = any;
                     break;
                 }
-                block_step<FAST>(L, tid, el, j, xj, yj, actx, acty, anx, any, pnx, pny);
+                block_step<MATH>(L, tid, el, j, xj, yj, actx, acty, anx, any, pnx, pny);
             }
         }
         if (active) {
@@ -416,6 +452,23 @@ __global__ __launch_bounds__(SWARM_TPB, MODE == 0 ? 5 : 1) void swarm_kernel(Swa
     }
 }
 
+template <int MODE, bool FAST>
+// The step's pair loop is a long chain of dependent fp64 operations (two exp polynomials, three quotients per pair): five waves per SIMD
+// instead of the four its 124 registers allowed hide more of it -- 0.976 -> 0.875 ms per 32 768-env step with 96 registers and 24 bytes of
+// scratch per lane (round 4).  Six waves (80 registers, 104 bytes of scratch) measured 0.859 ms but tripled the kernel's HBM-side bytes
+// (each lane writes and reads its spill slots once: 488 MB per launch against 151 MB algorithmic); 7 / 8 waves: 0.875 / 0.863 ms.
+// With the quotients from one reciprocal (pair_term<MATH_EXACT>): 276 -> 217 us per 8 192-env chunk, 96 registers, 20 bytes of scratch.
+// The second launch bound is waves per SIMD.
+__global__ __launch_bounds__(SWARM_TPB, MODE == 0 ? 5 : 1) void swarm_kernel(SwarmParams P) {
+    swarm_body<MODE, FAST ? MATH_FAST : MATH_EXACT>(P);
+}
+
+// GRL_SWARM_DIV=ref: the exact path with the compiler's three IEEE divisions per pair, for tests/test_gpu_swarm_div.py
+template <int MODE>
+__global__ __launch_bounds__(SWARM_TPB, MODE == 0 ? 5 : 1) void swarm_kernel_refdiv(SwarmParams P) {
+    swarm_body<MODE, MATH_REFDIV>(P);
+}
+
 // get_local_states (paac/emulator_runner.py:98-111) as a dense f32 tensor; compat/debug only.
 __global__ void swarm_materialize_kernel(const uint8_t *lbins, const uint8_t *abins, const uint8_t *pos, int first, int G,
                                          float *out) {
@@ -471,6 +524,7 @@ static int dmalloc(grl_handle *h, T **p, size_t n) {
 int swarm_alloc(grl_handle *h) {
     size_t E = h->E;
     int rc;
+    { const char *dv = getenv("GRL_SWARM_DIV"); h->sw.ref_div = dv && strcmp(dv, "ref") == 0; }      // A/B and tests: pair_term's MATH_REFDIV
     if ((rc = dmalloc(h, &h->sw.x, E * N_LOCUSTS * 2))) return rc;
     if ((rc = dmalloc(h, &h->sw.xa, E * N_AGENTS * 2))) return rc;
     if ((rc = dmalloc(h, &h->sw.pnoise, E * N_LOCUSTS * 2))) return rc;
@@ -490,6 +544,17 @@ int swarm_alloc(grl_handle *h) {
 
 static inline int nblocks(int n) { return (n + SWARM_EPB - 1) / SWARM_EPB; }
 
+// the step / reset kernel in the handle's arithmetic: fast math, the exact path, or the exact path with the reference divisions
+template <int MODE>
+static void launch_swarm(grl_handle *h, int blocks, const SwarmParams &P) {
+    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH)
+        hipLaunchKernelGGL((swarm_kernel<MODE, true>), dim3(blocks), dim3(SWARM_TPB), 0, h->stream, P);
+    else if (h->sw.ref_div)
+        hipLaunchKernelGGL((swarm_kernel_refdiv<MODE>), dim3(blocks), dim3(SWARM_TPB), 0, h->stream, P);
+    else
+        hipLaunchKernelGGL((swarm_kernel<MODE, false>), dim3(blocks), dim3(SWARM_TPB), 0, h->stream, P);
+}
+
 int swarm_launch_step(grl_handle *h, const float *actions_dev, const double *actions64_dev, int no_wind) {
     SwarmParams P = make_params(h);
     P.actions = actions_dev;
@@ -497,10 +562,7 @@ int swarm_launch_step(grl_handle *h, const float *actions_dev, const double *act
     P.no_wind = no_wind;
     GRL_HIP(h, hipMemsetAsync(h->done_count, 0, sizeof(int32_t), h->stream));
     prof_begin(h);
-    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH)
-        hipLaunchKernelGGL((swarm_kernel<MODE_STEP, true>), dim3(nblocks(h->E)), dim3(SWARM_TPB), 0, h->stream, P);
-    else
-        hipLaunchKernelGGL((swarm_kernel<MODE_STEP, false>), dim3(nblocks(h->E)), dim3(SWARM_TPB), 0, h->stream, P);
+    launch_swarm<MODE_STEP>(h, nblocks(h->E), P);
     prof_end(h);
     GRL_HIP(h, hipGetLastError());
     // auto-reset of the envs that just finished (paac/emulator_runner.py:128-132): the terminal
@@ -521,10 +583,7 @@ int swarm_launch_step_range(grl_handle *h, const float *actions_dev, int env_bas
     P.done_list = h->done_list + env_base;
     P.done_count = h->done_count + slot;
     if (!counter_zeroed) GRL_HIP(h, hipMemsetAsync(P.done_count, 0, sizeof(int32_t), h->stream));      // (the conv rollout's sampling kernel does it)
-    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH)
-        hipLaunchKernelGGL((swarm_kernel<MODE_STEP, true>), dim3(nblocks(count)), dim3(SWARM_TPB), 0, h->stream, P);
-    else
-        hipLaunchKernelGGL((swarm_kernel<MODE_STEP, false>), dim3(nblocks(count)), dim3(SWARM_TPB), 0, h->stream, P);
+    launch_swarm<MODE_STEP>(h, nblocks(count), P);
     GRL_HIP(h, hipGetLastError());
     return swarm_launch_reset(h, P.done_list, P.done_count, count);
 }
@@ -533,10 +592,7 @@ int swarm_launch_reset(grl_handle *h, const int32_t *list_dev, const int32_t *co
     SwarmParams P = make_params(h);
     P.reset_list = list_dev;
     P.reset_count = count_dev;
-    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH)
-        hipLaunchKernelGGL((swarm_kernel<MODE_RESET, true>), dim3(nblocks(max_count)), dim3(SWARM_TPB), 0, h->stream, P);
-    else
-        hipLaunchKernelGGL((swarm_kernel<MODE_RESET, false>), dim3(nblocks(max_count)), dim3(SWARM_TPB), 0, h->stream, P);
+    launch_swarm<MODE_RESET>(h, nblocks(max_count), P);
     GRL_HIP(h, hipGetLastError());
     return GRL_OK;
 }
@@ -574,10 +630,7 @@ int swarm_reset_injected(grl_handle *h, const double *x0, const double *xa0, con
             P.flags &= ~(GRL_F_RESET_FROM_SNAPSHOT);
             P.reset_list = h->done_list; P.reset_count = h->done_count;
             P.inj_x0 = d_x0; P.inj_xa0 = d_xa0; P.inj_ra = d_ra; P.inj_an = d_an; P.inj_pn = d_pn;
-            if (h->cfg.flags & GRL_F_SWARM_FAST_MATH)
-                hipLaunchKernelGGL((swarm_kernel<MODE_RESET, true>), dim3(nblocks(h->E)), dim3(SWARM_TPB), 0, h->stream, P);
-            else
-                hipLaunchKernelGGL((swarm_kernel<MODE_RESET, false>), dim3(nblocks(h->E)), dim3(SWARM_TPB), 0, h->stream, P);
+            launch_swarm<MODE_RESET>(h, nblocks(h->E), P);
             if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }

@@ -43,6 +43,7 @@ NET_SIGNATURES = {
     "grl_net_comm_broadcast_params": (C.c_int, [_P, _I]),
     "grl_net_comm_destroy": (C.c_int, [_P]),
     "grl_net_comm_info": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "grl_net_debug_obs_index": (C.c_int, [_P, _I, _P, _P, _P, _P, _SZ]),
     "grl_net_range_info": (C.c_int, [_P, _P, _P, _P]),
     "grl_net_host_times": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "grl_net_set_gemm_f32": (C.c_int, [_P, C.c_int32]),
@@ -188,6 +189,15 @@ class ConvNet(object):
         self._check(self.lib.grl_net_predict_obs(self.n, ne, _ffi._ptr(lb), _ffi._ptr(ab), _ffi._ptr(ps), _ffi._ptr(mu),
                                                  _ffi._ptr(sg), _ffi._ptr(vs)))
         return {"mu": mu, "sigma": sg, "vs": vs}
+
+    def debug_obs_index(self, locust_bins, agent_bins, positions):
+        """The device's observation index records (obs_index_kernel) of host observations: (n_envs, 288) uint32."""
+        lb = np.ascontiguousarray(locust_bins, np.uint8); ab = np.ascontiguousarray(agent_bins, np.uint8)
+        ps = np.ascontiguousarray(positions, np.uint8)
+        rec = np.empty((lb.shape[0], 288), np.uint32)
+        self._check(self.lib.grl_net_debug_obs_index(self.n, lb.shape[0], _ffi._ptr(lb), _ffi._ptr(ab), _ffi._ptr(ps), _ffi._ptr(rec),
+                                                     rec.nbytes))
+        return rec
 
     def train_obs(self, locust_bins, agent_bins, positions, actions, advantages, critic_target, lr, apply_update=True):
         lb = np.ascontiguousarray(locust_bins, np.uint8); ab = np.ascontiguousarray(agent_bins, np.uint8)

@@ -123,6 +123,12 @@ int grl_net_read_rollout(grl_net *net, const char *which, void *host, size_t byt
  * per-agent "a2"/"a3" are not materialised by the forward pass; they are expanded on demand by this call. */
 int grl_net_read_activation(grl_net *net, const char *which, float *host, size_t bytes);
 
+/* Debug / test access: the observation index record conv1's backward helpers read (obs_index_kernel, csrc/net_shared.inc, where the
+ * layout is written down), built on the device for n_envs host observations (the arrays grl_net_predict_obs takes).
+ * host: n_envs x 288 uint32; words the kernel does not write read as zero. */
+int grl_net_debug_obs_index(grl_net *net, int32_t n_envs, const uint8_t *locust_bins, const uint8_t *agent_bins,
+                            const uint8_t *positions, uint32_t *host, size_t bytes);
+
 /* ---- multi-GPU: one process per GPU, one RCCL all-reduce (sum, fp32) of the flat gradient per
  * rollout over xGMI (no counterpart in the reference, which is single-device: actor_learner.py:70-75).
  * Rank 0 calls grl_comm_unique_id and ships the bytes to the other ranks by any means (goldsrl/distributed.py uses its own
