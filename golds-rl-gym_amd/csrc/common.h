@@ -128,7 +128,8 @@ int swarm_reset_injected(grl_handle *h, const double *x0, const double *xa0, con
 int swarm_materialize(grl_handle *h, int first, int count, float *out_dev);
 // flat_envs.hip
 int solow_alloc(grl_handle *h);
-int solow_launch_step(grl_handle *h, const float *actions_dev);
+// term_obs_dev (E,2) or null: the processed observation of every env whose episode this step ended (other rows untouched)
+int solow_launch_step(grl_handle *h, const float *actions_dev, float *term_obs_dev = nullptr);
 int solow_launch_reset(grl_handle *h, const int32_t *list_dev, const int32_t *count_dev, int max_count, bool advance_episode);
 int solow_launch_observe(grl_handle *h);
 int trade_alloc(grl_handle *h);

@@ -28,6 +28,7 @@ struct SolowParams {
     float *reward;
     uint8_t *done;
     float *obs_raw, *obs, *history;
+    float *term_obs;      // (E,2) or null: the processed observation an episode ended in, before the auto-reset overwrites it
     int32_t *done_list, *done_count, *err_flag;
     const int32_t *reset_list, *reset_count;
     int E, P, Q, T, rnn, max_steps;
@@ -106,6 +107,7 @@ __device__ __forceinline__ SolowStepOut solow_step_env(const SolowParams &S, int
     S.done[env] = o.done ? 1 : 0;
     int nh;
     if (o.done) {   // auto-reset: terminal reward stays, observation is the reset one (quirk Q6)
+        if (S.term_obs) reinterpret_cast<float2 *>(S.term_obs)[env] = make_float2(kn / 100.0f, zn);
         zn = solow_reset_env(S, env);
         kn = S.kss;
         nh = 1;

@@ -87,9 +87,10 @@ static bool solow_needs_tape(const grl_handle *h) {
     return !(h->cfg.flags & GRL_F_RESET_FROM_SNAPSHOT);
 }
 
-int solow_launch_step(grl_handle *h, const float *actions_dev) {
+int solow_launch_step(grl_handle *h, const float *actions_dev, float *term_obs_dev) {
     SolowParams S = solow_params(h);
     S.actions = actions_dev;
+    S.term_obs = term_obs_dev;
     GRL_HIP(h, hipMemsetAsync(h->done_count, 0, sizeof(int32_t), h->stream));
     hipLaunchKernelGGL(solow_step_kernel, dim3((h->E + 255) / 256), dim3(256), 0, h->stream, S);
     GRL_HIP(h, hipGetLastError());

@@ -441,65 +441,7 @@ __global__ __launch_bounds__(256, 1) void gated_backward_kernel(GArgs a) {
     }
 }
 
-// sums of squares in float64 of the two gradients: kGSumsqBlocks partial sums each, added in order by gated_finalize_kernel
-constexpr int kGSumsqBlocks = 32;
-__global__ __launch_bounds__(256) void gated_sumsq_kernel(const float *__restrict__ g, long n, double *__restrict__ out) {
-    __shared__ double red[256];
-    const float *gg = g + (size_t)blockIdx.y * n;
-    const long per = (n + kGSumsqBlocks - 1) / kGSumsqBlocks, lo = (long)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-    double s = 0.0;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) s += (double)gg[i] * (double)gg[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.y * kGSumsqBlocks + blockIdx.x] = red[0];
-}
-
-// stats: policy loss, value loss, entropy mean, policy norm, value norm, lr; then the two clip factors (tf.clip_by_global_norm)
-__global__ void gated_finalize_kernel(const double *__restrict__ stats64, const double *__restrict__ sumsq, float clip_norm, float lr,
-                                      float *__restrict__ stats) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double sp = 0.0, sv = 0.0;
-    for (int b = 0; b < kGSumsqBlocks; ++b) { sp += sumsq[b]; sv += sumsq[kGSumsqBlocks + b]; }
-    const float np_ = (float)sqrt(sp), nv = (float)sqrt(sv);
-    stats[0] = (float)stats64[0];
-    stats[1] = (float)stats64[1];
-    stats[2] = stats64[3] > 0.0 ? (float)(stats64[2] / (2.0 * stats64[3])) : 0.f;
-    stats[3] = np_; stats[4] = nv; stats[5] = lr;
-    stats[6] = clip_norm > 0.f ? clip_norm / fmaxf(np_, clip_norm) : 1.0f;
-    stats[7] = clip_norm > 0.f ? clip_norm / fmaxf(nv, clip_norm) : 1.0f;
-}
-
-// both RMSProp steps (TF 1.x, momentum 0): ms <- rho ms + (1-rho) g^2 ; step = lr g / sqrt(ms + eps).  The policy gradient covers
-// [0, v1w), the value gradient [0, c1w) and [v1w, total): the trunk takes both steps, each from the same pre-update parameters.
-__global__ void gated_rmsprop_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ msp, float *__restrict__ msv, long n,
-                                     long c1w, long v1w, const float *__restrict__ stats, float rho, float eps) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float lr = stats[5];
-    float w = p[i];
-    if (i < v1w) {
-        const float gi = g[i] * stats[6];
-        const float m = rho * msp[i] + (1.0f - rho) * gi * gi;
-        msp[i] = m;
-        w = w - lr * gi / sqrtf(m + eps);
-    }
-    if (i < c1w || i >= v1w) {
-        const float gi = g[n + i] * stats[7];
-        const float m = rho * msv[i] + (1.0f - rho) * gi * gi;
-        msv[i] = m;
-        w = w - lr * gi / sqrtf(m + eps);
-    }
-    p[i] = w;
-}
-
-__global__ void gated_fill_kernel(float *__restrict__ p, long n, float v) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
+#include "net_a3c_update.inc"
 
 // ---------------------------------------------------------------------------------------------- rollout
 // window of env e: rows [0, min(k+1, R)) hold the episode's last temporal rows (current last), zero rows after; k = kstep[e]
@@ -565,7 +507,7 @@ struct grl_gnet {
     std::string err;
     grl::GOff off;
     float *params, *grads, *msp, *msv, *stats;    // grads: [policy P | value P]
-    double *stats64;                              // 4 loss sums, then 2 x kGSumsqBlocks partial sums
+    double *stats64;                              // 4 loss sums, then 2 x kA3cSumsqBlocks partial sums
     int64_t global_step;
     uint64_t act_counter;
     // host-sample staging
@@ -646,12 +588,12 @@ static int train_device(grl_gnet *net, int n, const float *states, const float *
     a.slab = net->slab; a.scratch = net->scratch; a.stats64 = net->stats64;
     hipLaunchKernelGGL(gated_backward_kernel, dim3(blocks), dim3(256), GATED_LDS, st, a);
     hipLaunchKernelGGL(flat_slab_reduce_kernel, dim3((unsigned)((2 * P + 63) / 64)), dim3(1024), 0, st, net->slab, blocks, 2 * P, net->grads);
-    hipLaunchKernelGGL(gated_sumsq_kernel, dim3(kGSumsqBlocks, 2), dim3(256), 0, st, net->grads, P, net->stats64 + 4);
+    hipLaunchKernelGGL(a3c_sumsq_kernel, dim3(kA3cSumsqBlocks, 2), dim3(256), 0, st, net->grads, P, net->stats64 + 4);
     // tf.train.exponential_decay(lr0, global_step, decay_steps, rate, staircase=False), global_step before the update
     const float lr = (float)((double)lr0 * pow((double)net->cfg.lr_decay_rate, (double)net->global_step / (double)net->cfg.lr_decay_steps));
-    hipLaunchKernelGGL(gated_finalize_kernel, dim3(1), dim3(64), 0, st, net->stats64, net->stats64 + 4, net->cfg.clip_norm, lr, net->stats);
+    hipLaunchKernelGGL(a3c_finalize_kernel, dim3(1), dim3(64), 0, st, net->stats64, net->stats64 + 4, 2.0, net->cfg.clip_norm, lr, net->stats);
     if (apply) {
-        hipLaunchKernelGGL(gated_rmsprop_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, net->params, net->grads, net->msp, net->msv, P,
+        hipLaunchKernelGGL(a3c_rmsprop_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, net->params, net->grads, net->msp, net->msv, P,
                            net->off.c1w, net->off.v1w, net->stats, net->cfg.rms_decay, net->cfg.rms_epsilon);
         net->global_step += 2;      // both train ops increment it (estimators.py:137-140, 403-406)
     }
@@ -719,10 +661,10 @@ int grl_gnet_create(grl_handle *h, const grl_gnet_config *cfg, grl_gnet **out) {
     Al(&n->win, E * R * GD); Al(&n->ro_boot, E); Al(&n->ro_act, E * 4); Al(&n->boot_states, E * GS0); Al(&n->boot_win, E * R * GD);
     if (rc == GRL_OK) rc = galloc(n, &n->d_choices, ms * 2, n->allocs);
     if (rc == GRL_OK) rc = galloc(n, &n->kstep, E, n->allocs);
-    if (rc == GRL_OK) rc = galloc(n, &n->stats64, 4 + 2 * kGSumsqBlocks, n->allocs);
+    if (rc == GRL_OK) rc = galloc(n, &n->stats64, 4 + 2 * kA3cSumsqBlocks, n->allocs);
     if (rc == GRL_OK) {      // RMSProp ms starts at ones (TF 1.x)
-        hipLaunchKernelGGL(gated_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msp, (long)P, 1.0f);
-        hipLaunchKernelGGL(gated_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msv, (long)P, 1.0f);
+        hipLaunchKernelGGL(a3c_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msp, (long)P, 1.0f);
+        hipLaunchKernelGGL(a3c_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msv, (long)P, 1.0f);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gated_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATED_LDS);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gated_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATED_LDS);

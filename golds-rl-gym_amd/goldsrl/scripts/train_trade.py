@@ -1,0 +1,75 @@
+"""`python -m goldsrl.scripts.train_trade` -- scripts/train_trade.py of the reference on the device: the TradeWorker
+(fed_gym/agents/a3c/worker.py:418-442) on `TradeAR1-v0` (2 assets, 1 024-step episodes), E envs x t_max steps per update, each env
+one A3C worker (include/goldsrl_gaussnet.h).  The reference's settings: t_max 64, max_seq_length 20, value scale 1,
+always_bootstrap off, learning rate 1e-4.  The reference's TradeWorker cannot run as written; the device form takes the evident
+reading (per-action mu and sigma, the raw draw stored and trained on, tanh to the env).  Scalars go to a
+TF-events file, the checkpoint to <model_dir>/checkpoint.npz."""
+import argparse
+import logging
+import os
+import sys
+import time
+
+import numpy as np
+
+from goldsrl import _ffi, _ffi_gauss
+from goldsrl.utils_tfevents import EventFileWriter
+
+logging.basicConfig(stream=sys.stdout, level=logging.INFO)
+
+MAX_SEQ_LENGTH = 20         # scripts/train_trade.py:119
+SCALE = 1.0
+
+
+def get_arg_parser():
+    p = argparse.ArgumentParser(description=__doc__)
+    p.add_argument("--model_dir", "--out", dest="model_dir", default="/tmp/a3c", help="directory of the events file and the checkpoint")
+    p.add_argument("--t_max", type=int, default=64, help="number of steps before performing an update")
+    p.add_argument("--envs", "--parallelism", dest="envs", type=int, default=4096, help="number of envs, each one A3C worker")
+    p.add_argument("--updates", type=int, default=100)
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--seed", type=int, default=3)
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--resume", help="checkpoint .npz to continue from")
+    p.add_argument("--checkpoint-every", type=int, default=50)
+    return p
+
+
+def main(argv=None):
+    args = get_arg_parser().parse_args(argv)
+    eng = _ffi.Engine(_ffi.ENV_TRADE, args.envs, device_id=args.device, seed=args.seed, n_assets=2, max_episode_steps=1024)
+    eng.reset()
+    eng.episodes_enable()
+    net = _ffi_gauss.GaussNet(eng, rnn_length=MAX_SEQ_LENGTH, scale=SCALE, always_bootstrap=0, max_samples=max(1, args.envs))
+    if args.resume:
+        net.load_checkpoint(args.resume)
+    else:
+        net.set_params(_ffi_gauss.default_init_gauss(args.seed, **_ffi_gauss.TRADE_SIZES))
+    os.makedirs(args.model_dir, exist_ok=True)
+    writer = EventFileWriter(args.model_dir)
+    ckpt = os.path.join(args.model_dir, "checkpoint.npz")
+    for u in range(args.updates):
+        t0 = time.time()
+        net.rollout(args.t_max)
+        stats = net.train_rollout(args.lr)
+        dt = time.time() - t0
+        step = net.get_optimizer_state()["global_step"]
+        for k, v in stats.items():
+            writer.add_scalar("train/" + k, v, step)
+        eps = eng.episodes_read()
+        if len(eps):
+            writer.add_scalar("episode/total_reward", float(np.mean(eps["total_reward"])), step)
+            writer.add_scalar("episode/length", float(np.mean(eps["length"])), step)
+        writer.add_scalar("perf/env_steps_per_s", args.envs * args.t_max / dt, step)
+        writer.flush()
+        logging.info("update %d  global step %d  policy loss %.4g  value loss %.4g  entropy %.4g  %.0f env-steps/s", u + 1, step,
+                     stats["policy_loss"], stats["value_loss"], stats["entropy_mean"], args.envs * args.t_max / dt)
+        if (u + 1) % args.checkpoint_every == 0 or u + 1 == args.updates:
+            net.save_checkpoint(ckpt)
+    writer.close()
+    net.close()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
