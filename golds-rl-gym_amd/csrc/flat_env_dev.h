@@ -1,6 +1,7 @@
-// Device-side pieces of the Solow-v0 / TradeAR1-v0 step shared by the stand-alone step kernels (flat_envs.hip) and the persistent
-// flat PAAC rollout (net_flat.hip: one workgroup keeps 64 envs for all T steps): parameter blocks, the per-env Solow step with the
-// worker's auto-reset, the shock-tape draw, the TradeAR1 observation transform.  Reference: fed_gym/envs/fed_env.py:161-334,
+// Device-side pieces of the Solow-v0 / TradeAR1-v0 step shared by the stand-alone step kernels (flat_envs.hip), the persistent
+// flat PAAC rollout (net_flat.hip: one workgroup keeps 64 envs for all T steps) and the Gaussian agent's greedy evaluation
+// (net_gauss_eval.inc): parameter blocks, the per-env Solow and TradeAR1 steps with the worker's auto-reset, the shock-tape draw,
+// the TradeAR1 observation transform.  Reference: fed_gym/envs/fed_env.py:161-334,
 // fed_gym/agents/paac/emulator_runner.py:48-65.
 #pragma once
 #include "common.h"
@@ -179,6 +180,90 @@ static inline TradeParams trade_params(grl_handle *h) {
     R.err_flag = h->err_flag; R.E = h->E; R.n = h->cfg.n_assets; R.max_steps = h->cfg.max_episode_steps;
     R.std_e = h->tr.std_e; R.start = h->tr.start; R.flags = h->cfg.flags; R.env_off = (uint32_t)h->cfg.env_id_offset; R.seed = h->cfg.seed;
     return R;
+}
+
+// TradeAR1Env._step + the worker's auto-reset for ONE env (fed_env.py:300-330, emulator_runner.py:48-65); actions: the env's n
+// actions.  Updates the env's account in global memory, writes reward / done / observation, returns what a fused caller keeps in
+// registers.
+struct TradeStepOut { float reward; bool done; };
+__device__ __forceinline__ TradeStepOut trade_step_env(const TradeParams &R, int env, const float *actions) {
+    TradeStepOut o_;
+    const int n = R.n, S = 1 + 2 * n;
+    const size_t E = R.E;
+    // TradeAR1Env._step (fed_env.py:300-321)
+    double cash = R.cash[env];
+    const double assets_old = R.assets[env];
+    double cost = 0.0, value = 0.0;
+    bool bad = false;
+    for (int a = 0; a < n; ++a) {
+        const float actf = actions[a];
+        bad |= !(actf >= -1.0f && actf <= 1.0f);                     // action_space.contains (fed_env.py:301)
+        const double act = (double)actf;
+        const double p = R.p[a * E + env];
+        double q = R.q[a * E + env];
+        const double q_add = act > 0.0 ? (act / (double)n) * cash / p : act * q;
+        q += q_add;
+        cost += q_add * p;
+        value += q * p;
+        R.q[a * E + env] = q;
+    }
+    if (bad) atomicAdd(R.err_flag, 1);
+    cash = cash + (-cost);
+    const double assets = cash + value;
+    const bool own_done = assets < 1.0;                              // MIN_CASH (fed_env.py:272,313)
+    o_.reward = (float)(log(assets + 1e-4) - log(assets_old + 1e-4));
+    R.reward[env] = o_.reward;
+    const int el = R.elapsed[env] + 1;
+    const bool done = own_done || (R.max_steps > 0 && el >= R.max_steps);
+    R.done[env] = done ? 1 : 0;
+    const uint32_t st = R.nstep[env];
+    R.nstep[env] = st + 1;
+    float *oraw = R.obs_raw + (size_t)env * S, *o = R.obs + (size_t)env * S;
+    if (done) {   // auto-reset (emulator_runner.py:50-52) -> TradeAR1Env._reset (fed_env.py:323-330)
+        cash = R.start;
+        R.assets[env] = R.start;
+        R.elapsed[env] = 0;
+        R.nhist[env] = 1;            // histories[i] = [reset state]  (emulator_runner.py:52)
+        R.episode[env] = R.episode[env] + 1;
+        for (int a = 0; a < n; ++a) {
+            R.q[a * E + env] = 0.0; R.p[a * E + env] = 1.0;
+            oraw[1 + a] = 0.f; oraw[1 + n + a] = 1.f;
+            o[1 + a] = trade_proc(1, 0.0); o[1 + n + a] = trade_proc(1, 1.0);
+        }
+    } else {
+        R.assets[env] = assets;
+        R.elapsed[env] = el;
+        {
+            const int nh = R.nhist[env] + 1;
+            R.nhist[env] = nh > R.rnn + 1 ? R.rnn + 1 : nh;     // list trimmed to rnn+1 (emulator_runner.py:61)
+        }
+        const int pairs = (n + 1) / 2;
+        for (int a = 0; a < n; a += 2) {
+            double z[2];
+            if (R.flags & GRL_F_INJECT_NOISE) {
+                z[0] = R.normals[a * E + env];
+                z[1] = a + 1 < n ? R.normals[(a + 1) * E + env] : 0.0;
+            } else {
+                normal_pair(rng_block(R.seed, (uint32_t)env + R.env_off, 0u, RS_TRADE_PRICE, st * pairs + (a >> 1)), z[0], z[1]);
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int ak = a + k;
+                if (ak >= n) break;
+                // _price_transition: p**rho_p * exp(std_e * N(0,1))  (fed_env.py:296-298)
+                const double p = pow(R.p[ak * E + env], 0.9) * exp(R.std_e * z[k]);
+                R.p[ak * E + env] = p;
+                const double q = R.q[ak * E + env];
+                oraw[1 + ak] = (float)q; oraw[1 + n + ak] = (float)p;
+                o[1 + ak] = trade_proc(1, q); o[1 + n + ak] = trade_proc(1, p);
+            }
+        }
+    }
+    R.cash[env] = cash;
+    oraw[0] = (float)cash;
+    o[0] = trade_proc(0, cash);
+    o_.done = done;
+    return o_;
 }
 
 

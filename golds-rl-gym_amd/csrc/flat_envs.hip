@@ -128,81 +128,7 @@ int solow_launch_observe(grl_handle *h) {
 __global__ __launch_bounds__(256) void trade_step_kernel(TradeParams R) {
     const int env = blockIdx.x * blockDim.x + threadIdx.x;
     bool done = false;
-    if (env < R.E) {
-        const int n = R.n, S = 1 + 2 * n;
-        const size_t E = R.E;
-        // TradeAR1Env._step (fed_env.py:300-321)
-        double cash = R.cash[env];
-        const double assets_old = R.assets[env];
-        double cost = 0.0, value = 0.0;
-        bool bad = false;
-        for (int a = 0; a < n; ++a) {
-            const float actf = R.actions[(size_t)env * n + a];
-            bad |= !(actf >= -1.0f && actf <= 1.0f);                     // action_space.contains (fed_env.py:301)
-            const double act = (double)actf;
-            const double p = R.p[a * E + env];
-            double q = R.q[a * E + env];
-            const double q_add = act > 0.0 ? (act / (double)n) * cash / p : act * q;
-            q += q_add;
-            cost += q_add * p;
-            value += q * p;
-            R.q[a * E + env] = q;
-        }
-        if (bad) atomicAdd(R.err_flag, 1);
-        cash = cash + (-cost);
-        const double assets = cash + value;
-        const bool own_done = assets < 1.0;                              // MIN_CASH (fed_env.py:272,313)
-        R.reward[env] = (float)(log(assets + 1e-4) - log(assets_old + 1e-4));
-        const int el = R.elapsed[env] + 1;
-        done = own_done || (R.max_steps > 0 && el >= R.max_steps);
-        R.done[env] = done ? 1 : 0;
-        const uint32_t st = R.nstep[env];
-        R.nstep[env] = st + 1;
-        float *oraw = R.obs_raw + (size_t)env * S, *o = R.obs + (size_t)env * S;
-        if (done) {   // auto-reset (emulator_runner.py:50-52) -> TradeAR1Env._reset (fed_env.py:323-330)
-            cash = R.start;
-            R.assets[env] = R.start;
-            R.elapsed[env] = 0;
-            R.nhist[env] = 1;            // histories[i] = [reset state]  (emulator_runner.py:52)
-            R.episode[env] = R.episode[env] + 1;
-            for (int a = 0; a < n; ++a) {
-                R.q[a * E + env] = 0.0; R.p[a * E + env] = 1.0;
-                oraw[1 + a] = 0.f; oraw[1 + n + a] = 1.f;
-                o[1 + a] = trade_proc(1, 0.0); o[1 + n + a] = trade_proc(1, 1.0);
-            }
-        } else {
-            R.assets[env] = assets;
-            R.elapsed[env] = el;
-            {
-                const int nh = R.nhist[env] + 1;
-                R.nhist[env] = nh > R.rnn + 1 ? R.rnn + 1 : nh;     // list trimmed to rnn+1 (emulator_runner.py:61)
-            }
-            const int pairs = (n + 1) / 2;
-            for (int a = 0; a < n; a += 2) {
-                double z[2];
-                if (R.flags & GRL_F_INJECT_NOISE) {
-                    z[0] = R.normals[a * E + env];
-                    z[1] = a + 1 < n ? R.normals[(a + 1) * E + env] : 0.0;
-                } else {
-                    normal_pair(rng_block(R.seed, (uint32_t)env + R.env_off, 0u, RS_TRADE_PRICE, st * pairs + (a >> 1)), z[0], z[1]);
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int ak = a + k;
-                    if (ak >= n) break;
-                    // _price_transition: p**rho_p * exp(std_e * N(0,1))  (fed_env.py:296-298)
-                    const double p = pow(R.p[ak * E + env], 0.9) * exp(R.std_e * z[k]);
-                    R.p[ak * E + env] = p;
-                    const double q = R.q[ak * E + env];
-                    oraw[1 + ak] = (float)q; oraw[1 + n + ak] = (float)p;
-                    o[1 + ak] = trade_proc(1, q); o[1 + n + ak] = trade_proc(1, p);
-                }
-            }
-        }
-        R.cash[env] = cash;
-        oraw[0] = (float)cash;
-        o[0] = trade_proc(0, cash);
-    }
+    if (env < R.E) done = trade_step_env(R, env, R.actions + (size_t)env * R.n).done;
     compact_done(done, env, R.done_list, R.done_count);
 }
 

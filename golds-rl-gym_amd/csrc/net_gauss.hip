@@ -14,6 +14,7 @@
 //             Weight gradients of the groups a workgroup loops over are summed into its private slab [policy P | value P]; the slabs
 //             are reduced in a fixed order (bitwise reproducible runs, no float atomics on gradients)
 //   update    two float64 sums of squares, clip factors, both RMSProp steps -- on the device
+//   eval      whole greedy episodes in one launch (net_gauss_eval.inc): a workgroup keeps its 64 envs, mu tower only
 #include <stdlib.h>
 #include <string.h>
 
@@ -25,6 +26,7 @@
 #include "common.h"
 #include "rng.h"
 #include "rollout_dev.h"
+#include "flat_env_dev.h"
 
 namespace grl {
 
@@ -71,6 +73,7 @@ struct AArgs {
     float *act;                         // (n,A) the env's action
     float *raw_out;                     // (n,A)
     int tanh_action;                    // TradeAR1: tanh(raw); Solow: the stable sigmoid
+    int greedy;                         // raw = mu, nothing is drawn (run_n_steps(stochastic=False), worker.py:180-230)
     uint64_t seed;
     uint32_t env_off, counter;
     // backward
@@ -172,7 +175,7 @@ __device__ __forceinline__ void gauss_trunk(const AArgs &a, float *lds, int sbas
     float *X = lds + AL_X * LS, *HX = lds + AL_HX * LS, *HS = lds + AL_HS * LS, *G = lds + AL_G * LS, *Cc = lds + AL_C * LS,
           *ST = lds + AL_ST * LS, *S1 = lds + AL_S1 * LS;
     const int tid = gauss_tid<LOOP>(), lane = tid & 63, wave = gauss_wave<LOOP>(tid);
-    const int s = sbase + lane, ss = s < a.n ? s : 0, R = a.R;
+    const int s = sbase + lane, ss = s < a.n ? s : a.n - 1, R = a.R;      // lanes past n read their own group's last sample
     const float *P = a.P, *w = a.win + (size_t)ss * R * D;
     const int len = gauss_length(w, R, D);
     for (int i = wave; i < AH; i += 4) HS[i * LS + lane] = 0.f;
@@ -242,6 +245,14 @@ __device__ __forceinline__ void gauss_tower_fwd(const AArgs &a, float *lds, int 
 __device__ __forceinline__ float gauss_mu(float z) { return 5.0f * tanhf(z); }                   // lb = -5, ub = 5 (estimators.py:283)
 __device__ __forceinline__ float gauss_sigma(float z) { return sigmoidf_(z) + 1e-3f; }          // estimators.py:288-290
 
+// what the env is stepped with: SolowWorker.transform_raw_action (worker.py:414-415) as a stable float32 sigmoid, TradeWorker
+// (:436-442) tanh per action
+__device__ __forceinline__ float gauss_env_action(float raw, int tanh_action) {
+    if (tanh_action) return tanhf(raw);
+    const float z = expf(-fabsf(raw));
+    return raw >= 0.f ? 1.0f / (1.0f + z) : z / (1.0f + z);
+}
+
 // one launch per forward pass (predict, a rollout step, the bootstraps); with a.act: the draw and the env action as well
 template <int D>
 __global__ __launch_bounds__(256) void gauss_forward_kernel(AArgs a) {
@@ -271,19 +282,13 @@ __global__ __launch_bounds__(256) void gauss_forward_kernel(AArgs a) {
         if (wave == 0 && a.vals) a.vals[s] = a.scale * O[lane];
     }
     if (a.act && valid && wave < A) {
-        // SolowWorker.get_random_action (worker.py:410-412) + transform_raw_action (:414-415); TradeWorker (:436-442) per action
-        double nz, nz1;
-        normal_pair(rng_block(a.seed, (uint32_t)s + a.env_off, a.counter, RS_GAUSS_ACTION, (uint32_t)wave), nz, nz1);
-        const float raw = (float)((double)MU[wave * LS + lane] + (double)SG[wave * LS + lane] * nz);
+        // SolowWorker.get_random_action (worker.py:410-412), TradeWorker (:436-442) per action; greedy: a zero in place of the normal
+        double nz = 0.0, nz1;
+        if (!a.greedy) normal_pair(rng_block(a.seed, (uint32_t)s + a.env_off, a.counter, RS_GAUSS_ACTION, (uint32_t)wave), nz, nz1);
+        const float m = MU[wave * LS + lane];
+        const float raw = a.greedy ? m : (float)((double)m + (double)SG[wave * LS + lane] * nz);
         a.raw_out[(size_t)s * A + wave] = raw;
-        float ea;
-        if (a.tanh_action) {
-            ea = tanhf(raw);
-        } else {
-            const float z = expf(-fabsf(raw));
-            ea = raw >= 0.f ? 1.0f / (1.0f + z) : z / (1.0f + z);
-        }
-        a.act[(size_t)s * A + wave] = ea;
+        a.act[(size_t)s * A + wave] = gauss_env_action(raw, a.tanh_action);
     }
 }
 
@@ -471,6 +476,17 @@ __device__ __forceinline__ void gauss_window_push(float *w, int R, int D, int k,
     }
 }
 
+// the window rule behind an env step (k = the env's step in its episode before it, o = the observation after it): a new row,
+// or a restart at the reset observation where the episode ended.  Returns the new k.
+__device__ __forceinline__ int gauss_window_step(float *w, int R, int D, int k, bool done, const float *o) {
+    if (done) {
+        gauss_window_restart(w, R, D, o);
+        return 0;
+    }
+    gauss_window_push(w, R, D, k + 1, o);
+    return k + 1;
+}
+
 // before a rollout: envs the handle (re)set since (elapsed 0), or all of them the first time, start a new window
 __global__ void gauss_sync_kernel(const int32_t *__restrict__ elapsed, const float *__restrict__ obs, float *__restrict__ win,
                                   int32_t *__restrict__ kstep, int E, int R, int D, int all) {
@@ -507,20 +523,14 @@ __global__ void gauss_post_kernel(const float *__restrict__ reward, const uint8_
     mask[e] = d ? 0.0f : 1.0f;
     float *w = win + (size_t)e * R * D;
     const float *o = obs + (size_t)e * D;
-    const int k = kstep[e] + 1;
-    if (d) {
-        if (term_obs) {
-            const float *to = term_obs + (size_t)e * D;
-            gauss_window_push(w, R, D, k, to);
-            for (int i = 0; i < D; ++i) term_st[(size_t)e * D + i] = to[i];
-            for (int i = 0; i < R * D; ++i) term_wn[(size_t)e * R * D + i] = w[i];
-        }
-        gauss_window_restart(w, R, D, o);
-        kstep[e] = 0;
-        return;
+    const int k = kstep[e];
+    if (d && term_obs) {
+        const float *to = term_obs + (size_t)e * D;
+        gauss_window_push(w, R, D, k + 1, to);
+        for (int i = 0; i < D; ++i) term_st[(size_t)e * D + i] = to[i];
+        for (int i = 0; i < R * D; ++i) term_wn[(size_t)e * R * D + i] = w[i];
     }
-    kstep[e] = k;
-    gauss_window_push(w, R, D, k, o);
+    kstep[e] = gauss_window_step(w, R, D, k, d, o);
 }
 
 // The worker's GAE (worker.py:241-294) per env column, cut at episode ends: delta_t = r_t + g V_next - V_t with V_next = V_{t+1}, or
@@ -547,6 +557,8 @@ __global__ void gauss_returns_kernel(const float *__restrict__ r, const float *_
     }
 }
 
+#include "net_gauss_eval.inc"
+
 }  // namespace grl
 
 struct grl_anet {
@@ -559,6 +571,7 @@ struct grl_anet {
     double *stats64;                              // 4 loss sums, then 2 x kA3cSumsqBlocks partial sums
     int64_t global_step;
     uint64_t act_counter;
+    int greedy;                                   // grl_anet_set_greedy
     // host-sample staging
     float *d_states, *d_win, *d_raw, *d_adv, *d_tgt, *d_wt, *d_mu, *d_sigma, *d_vals;
     // training workspace (grown on demand)
@@ -573,7 +586,14 @@ struct grl_anet {
     float *ro_act;                                // (T,E,A) the action each env was stepped with
     float *ro_term_st, *ro_term_wn, *ro_term_val; // ro_term_st / ro_term_wn: always_bootstrap only
     float *ro_boot, *boot_states, *boot_win, *term_obs;
-    std::vector<void *> allocs, ro_allocs, ws_allocs;
+    // grl_anet_eval: per-env results, the step's actions, the trace of the first ev_trace steps
+    double *ev_total;
+    int32_t *ev_len;
+    uint8_t *ev_fin;
+    float *ev_act, *ev_states, *ev_mu, *ev_actions, *ev_rew, *ev_done;
+    int32_t ev_reset_count;                       // E, the source of the reset list's count (outlives the async copy)
+    int ev_trace, ev_trace_cap, ev_played;        // ev_played: -1 until grl_anet_read_eval has looked, -2 before any evaluation
+    std::vector<void *> allocs, ro_allocs, ws_allocs, ev_allocs;
 };
 
 namespace grl {
@@ -679,6 +699,21 @@ static int ensure_rollout(grl_anet *net, int T) {
     return rc;
 }
 
+// the trace buffers of grl_anet_eval for `steps` steps (they only grow)
+static int ensure_eval_trace(grl_anet *net, int steps) {
+    if (steps <= net->ev_trace_cap) return GRL_OK;
+    ANET_HIP(net, hipStreamSynchronize(net->h->stream));
+    for (void *p : net->ev_allocs) hipFree(p);
+    net->ev_allocs.clear();
+    net->ev_trace_cap = -1;
+    const size_t SE = (size_t)steps * net->h->E, D = net->D, A = net->A;
+    int rc = GRL_OK;
+    auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = aalloc(net, p, cnt, net->ev_allocs); };
+    Al(&net->ev_states, SE * D); Al(&net->ev_mu, SE * A); Al(&net->ev_actions, SE * A); Al(&net->ev_rew, SE); Al(&net->ev_done, SE);
+    if (rc == GRL_OK) net->ev_trace_cap = steps;
+    return rc;
+}
+
 }  // namespace grl
 
 using namespace grl;
@@ -712,7 +747,8 @@ int grl_anet_create(grl_handle *h, const grl_anet_config *cfg, grl_anet **out) {
     n->h = h; n->cfg = *cfg;
     n->D = solow ? 2 : 5; n->A = solow ? 1 : 2;
     n->off = gauss_offsets(n->D, n->A);
-    n->global_step = 0; n->act_counter = 0; n->ws_blocks = 0; n->win_init = 0; n->T = 0;
+    n->global_step = 0; n->act_counter = 0; n->greedy = 0; n->ws_blocks = 0; n->win_init = 0; n->T = 0;
+    n->ev_trace = 0; n->ev_trace_cap = -1; n->ev_played = -2;
     const size_t ms = cfg->max_samples, P = n->off.total, R = cfg->rnn_length, E = h->E, D = n->D, A = n->A;
     int rc = GRL_OK;
     auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = aalloc(n, p, cnt, n->allocs); };
@@ -720,15 +756,19 @@ int grl_anet_create(grl_handle *h, const grl_anet_config *cfg, grl_anet **out) {
     Al(&n->d_states, ms * D); Al(&n->d_win, ms * R * D); Al(&n->d_raw, ms * A); Al(&n->d_adv, ms); Al(&n->d_tgt, ms); Al(&n->d_wt, ms);
     Al(&n->d_mu, ms * A); Al(&n->d_sigma, ms * A); Al(&n->d_vals, ms);
     Al(&n->win, E * R * D); Al(&n->ro_boot, E); Al(&n->boot_states, E * D); Al(&n->boot_win, E * R * D);
-    Al(&n->term_obs, E * D);
+    Al(&n->term_obs, E * D); Al(&n->ev_act, E * A);
     if (rc == GRL_OK) rc = aalloc(n, &n->kstep, E, n->allocs);
+    if (rc == GRL_OK) rc = aalloc(n, &n->ev_total, E, n->allocs);
+    if (rc == GRL_OK) rc = aalloc(n, &n->ev_len, E, n->allocs);
+    if (rc == GRL_OK) rc = aalloc(n, &n->ev_fin, E, n->allocs);
     if (rc == GRL_OK) rc = aalloc(n, &n->stats64, 4 + 2 * kA3cSumsqBlocks, n->allocs);
     if (rc == GRL_OK) {      // RMSProp ms starts at ones (TF 1.x)
         hipLaunchKernelGGL(a3c_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msp, (long)P, 1.0f);
         hipLaunchKernelGGL(a3c_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msv, (long)P, 1.0f);
         hipError_t e = hipGetLastError();
-        const void *kernels[2] = {solow ? (const void *)gauss_forward_kernel<2> : (const void *)gauss_forward_kernel<5>,
-                                  solow ? (const void *)gauss_backward_kernel<2> : (const void *)gauss_backward_kernel<5>};
+        const void *kernels[3] = {solow ? (const void *)gauss_forward_kernel<2> : (const void *)gauss_forward_kernel<5>,
+                                  solow ? (const void *)gauss_backward_kernel<2> : (const void *)gauss_backward_kernel<5>,
+                                  solow ? (const void *)gauss_eval_kernel<2, SolowParams> : (const void *)gauss_eval_kernel<5, TradeParams>};
         for (const void *k : kernels)
             if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GAUSS_LDS);
         if (e != hipSuccess) rc = afail(n, GRL_E_HIP, std::string("grl_anet_create: ") + hipGetErrorString(e));
@@ -749,6 +789,7 @@ int grl_anet_destroy(grl_anet *n) {
     for (void *p : n->allocs) hipFree(p);
     for (void *p : n->ro_allocs) hipFree(p);
     for (void *p : n->ws_allocs) hipFree(p);
+    for (void *p : n->ev_allocs) hipFree(p);
     delete n;
     return GRL_OK;
 }
@@ -858,6 +899,7 @@ int grl_anet_rollout(grl_anet *net, int32_t T) {
         a.mu = net->ro_mu + o * A; a.sigma = net->ro_sigma + o * A; a.vals = net->ro_val + o;
         a.act = net->ro_act + o * A; a.raw_out = net->ro_raw + o * A; a.tanh_action = solow ? 0 : 1;
         a.seed = h->cfg.seed; a.env_off = (uint32_t)h->cfg.env_id_offset; a.counter = (uint32_t)(net->act_counter + (uint64_t)t);
+        a.greedy = net->greedy;
         if ((rc = launch_fwd(net, a))) return rc;
         rc = solow ? solow_launch_step(h, net->ro_act + o * A, ab ? net->term_obs : nullptr) : trade_launch_step(h, net->ro_act + o * A);
         if (rc) return afail(net, rc, h->err);
@@ -866,7 +908,7 @@ int grl_anet_rollout(grl_anet *net, int32_t T) {
                            net->win, net->kstep, E, R, D, net->ro_rew + o, net->ro_done + o, net->ro_mask + o, ab ? net->ro_term_st + o * D : (float *)nullptr,
                            ab ? net->ro_term_wn + o * R * D : (float *)nullptr);
     }
-    net->act_counter += (uint64_t)T;
+    if (!net->greedy) net->act_counter += (uint64_t)T;      // a greedy rollout draws nothing
     // bootstrap: V of the window after the last step; with always_bootstrap also V behind every finished episode (workgroups whose
     // 64 samples ended none leave at once); then the worker's GAE (worker.py:241-294)
     hipLaunchKernelGGL(gauss_record_kernel, dim3(eb), dim3(256), 0, st, obs, net->win, net->kstep, E, R, D, net->boot_states, net->boot_win,
@@ -883,6 +925,75 @@ int grl_anet_rollout(grl_anet *net, int32_t T) {
                        net->cfg.gamma, net->cfg.gae_lambda, net->cfg.scale, ab, net->ro_tgt, net->ro_adv);
     ANET_HIP(net, hipGetLastError());
     return GRL_OK;
+}
+
+int grl_anet_set_greedy(grl_anet *net, int32_t on) {
+    if (!net) return GRL_E_INVALID;
+    net->greedy = on ? 1 : 0;
+    return GRL_OK;
+}
+
+int grl_anet_eval(grl_anet *net, int32_t max_steps, int32_t trace_steps) {
+    if (!net) return GRL_E_INVALID;
+    if (max_steps < 1 || trace_steps < 0) return afail(net, GRL_E_INVALID, "grl_anet_eval: max_steps >= 1, trace_steps >= 0");
+    grl_handle *h = net->h;
+    hipSetDevice(h->cfg.device_id);
+    if (trace_steps > max_steps) trace_steps = max_steps;
+    int rc = ensure_eval_trace(net, trace_steps);
+    if (rc) return rc;
+    hipStream_t st = h->stream;
+    const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
+    const int E = h->E;
+    AEvalArgs v{};
+    v.a = aargs(net, E, anet_obs(net), net->win);
+    v.win = net->win; v.act = net->ev_act; v.tanh_action = solow ? 0 : 1; v.max_steps = max_steps; v.trace_steps = trace_steps;
+    v.total = net->ev_total; v.length = net->ev_len; v.finished = net->ev_fin;
+    v.tr_states = net->ev_states; v.tr_mu = net->ev_mu; v.tr_act = net->ev_actions; v.tr_rew = net->ev_rew; v.tr_done = net->ev_done;
+    if (solow) {
+        SolowParams S = solow_params(h);
+        hipLaunchKernelGGL((gauss_eval_kernel<2, SolowParams>), dim3((E + 63) / 64), dim3(256), GAUSS_LDS, st, v, S);
+    } else {
+        TradeParams S = trade_params(h);
+        hipLaunchKernelGGL((gauss_eval_kernel<5, TradeParams>), dim3((E + 63) / 64), dim3(256), GAUSS_LDS, st, v, S);
+    }
+    ANET_HIP(net, hipGetLastError());
+    net->ev_trace = trace_steps;
+    net->ev_played = -1;
+    net->win_init = 0;      // the windows were the evaluation's: the next rollout starts every env's anew
+    // the handle's full reset (for Solow with the tape draw), as grl_reset(h, NULL, 0) enqueues it
+    if ((rc = launch_iota(h, h->done_list, E))) return afail(net, rc, h->err);
+    net->ev_reset_count = E;
+    ANET_HIP(net, hipMemcpyAsync(h->done_count, &net->ev_reset_count, 4, hipMemcpyHostToDevice, st));
+    rc = solow ? solow_launch_reset(h, h->done_list, h->done_count, E, true) : trade_launch_reset(h, h->done_list, h->done_count, E);
+    if (rc) return afail(net, rc, h->err);
+    return GRL_OK;
+}
+
+int grl_anet_read_eval(grl_anet *net, const char *which, void *host, size_t bytes) {
+    if (!net || !which || !host) return afail(net, GRL_E_INVALID, "grl_anet_read_eval: bad argument");
+    if (net->ev_played == -2) return afail(net, GRL_E_STATE, "grl_anet_read_eval: no evaluation yet");
+    hipSetDevice(net->h->cfg.device_id);
+    ANET_HIP(net, hipStreamSynchronize(net->h->stream));
+    const size_t E = net->h->E, D = net->D, A = net->A;
+    if (net->ev_played < 0) {      // steps the call played = the longest episode
+        std::vector<int32_t> len(E);
+        ANET_HIP(net, hipMemcpy(len.data(), net->ev_len, E * 4, hipMemcpyDeviceToHost));
+        int32_t mx = 0;
+        for (int32_t l : len) mx = l > mx ? l : mx;
+        net->ev_played = mx;
+    }
+    const size_t SE = (size_t)(net->ev_trace < net->ev_played ? net->ev_trace : net->ev_played) * E;
+    struct { const char *name; const void *p; size_t n; } tab[] = {
+        {"total_reward", net->ev_total, E * 8}, {"length", net->ev_len, E * 4}, {"finished", net->ev_fin, E},
+        {"states", net->ev_states, SE * D * 4}, {"mu", net->ev_mu, SE * A * 4}, {"actions", net->ev_actions, SE * A * 4},
+        {"rewards", net->ev_rew, SE * 4}, {"dones", net->ev_done, SE * 4}};
+    for (auto &e : tab)
+        if (!strcmp(which, e.name)) {
+            if (bytes != e.n) return afail(net, GRL_E_SIZE, std::string("grl_anet_read_eval: wrong size for ") + which);
+            if (bytes) ANET_HIP(net, hipMemcpy(host, e.p, bytes, hipMemcpyDeviceToHost));
+            return GRL_OK;
+        }
+    return afail(net, GRL_E_INVALID, std::string("grl_anet_read_eval: unknown buffer ") + which);
 }
 
 int grl_anet_train_rollout(grl_anet *net, float lr0, float *stats_host) {

@@ -37,6 +37,13 @@ ANET_SIGNATURES = {
     "grl_anet_train_rollout": (C.c_int, [_P, _F, _P]),
     "grl_anet_read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
 }
+# include/goldsrl_gausseval.h: a dict of its own, as the header is a file of its own (ANET_SIGNATURES is pinned to goldsrl_gaussnet.h's
+# 17 training functions by tests/test_oracle_gauss.py; these three are pinned by tests/test_gauss_eval_header.py)
+ANET_EVAL_SIGNATURES = {
+    "grl_anet_set_greedy": (C.c_int, [_P, _I]),
+    "grl_anet_eval": (C.c_int, [_P, _I, _I]),
+    "grl_anet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+}
 
 
 def gauss_param_shapes(static_size=2, temporal_size=2, num_actions=1, H=32, S=128):
@@ -77,7 +84,7 @@ class GaussNet(object):
     always_bootstrap defaults to what the engine's env takes (Solow 1, TradeAR1 0)."""
 
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=ANET_SIGNATURES)
+        self.lib = _ffi.load_library(extra_signatures=dict(ANET_SIGNATURES, **ANET_EVAL_SIGNATURES))
         self.eng = engine
         cfg = GrlAnetConfig()
         self.lib.grl_anet_config_default(C.byref(cfg))
@@ -199,3 +206,28 @@ class GaussNet(object):
         a = np.empty(shapes[which], np.float32)
         self._check(self.lib.grl_anet_read_rollout(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
         return a
+
+    def set_greedy(self, on):
+        """on: rollout draws nothing, raw = mu (run_n_steps(stochastic=False), a3c/worker.py:180-230); the action counter stands still."""
+        self._check(self.lib.grl_anet_set_greedy(self.n, 1 if on else 0))
+
+    EVAL_TRACE = ("states", "mu", "actions", "rewards", "dones")
+
+    def eval(self, max_steps, trace_steps=0, trace_fields=EVAL_TRACE):
+        """Greedy episodes of every env from the engine's current state (reset it first), one kernel launch; the engine is reset
+        afterwards.  Returns total_reward (E) float64, length (E) int32, finished (E) uint8 and, with trace_steps > 0, states
+        (S,E,S0), mu, actions (S,E,A), rewards, dones (S,E) of the first S = min(trace_steps, steps played) steps, each defined up to
+        its env's own end (trace_fields: the ones to read back)."""
+        self._check(self.lib.grl_anet_eval(self.n, int(max_steps), int(trace_steps)))
+        E = self.eng.E
+        out = {"total_reward": np.empty(E, np.float64), "length": np.empty(E, np.int32), "finished": np.empty(E, np.uint8)}
+        for k in ("total_reward", "length", "finished"):
+            self._check(self.lib.grl_anet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
+        if trace_steps > 0:
+            S = min(int(trace_steps), int(max_steps), int(out["length"].max()))
+            tails = {"states": (self.S0,), "mu": (self.A,), "actions": (self.A,), "rewards": (), "dones": ()}
+            for k in trace_fields:
+                tail = tails[k]
+                out[k] = np.empty((S, E) + tail, np.float32)
+                self._check(self.lib.grl_anet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
+        return out

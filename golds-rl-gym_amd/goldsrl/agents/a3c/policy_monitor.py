@@ -1,0 +1,111 @@
+"""PolicyMonitor (reference fed_gym/agents/a3c/policy_monitor.py:11-118) on the device: the greedy evaluation of the A3C Gaussian
+agent, every episode of `n_envs` seeded eval envs in one kernel launch (grl_anet_eval, include/goldsrl_gaussnet.h).
+
+The reference plays ONE episode of the eval env per evaluation, one `sess.run` per step, with the action sigmoid(mu[0]).  Here the
+monitor owns an eval engine of `n_envs` envs whose streams are keyed by the global env id, so env 0 is exactly that single episode
+and envs 1.. are further seeded episodes of the same registration; `eval_once` returns env 0's `(total_reward, episode_length,
+rewards)` as the reference does and keeps every env's totals for the caller.  The action is the worker's own transform of mu:
+the stable sigmoid for Solow, tanh for TradeAR1 (the reference's monitor applies its sigmoid to every env kind).
+What has no counterpart: the gym `Monitor` video wrapper, the TF session and summaries (the caller writes the scalars), the Saver."""
+import json
+import time
+
+import numpy as np
+
+ENVS = ("Solow-%d-%d-finite-eval-v0", "TradeAR1-v0")
+
+
+def make_eval_engine(env, n_envs, device_id=0, max_episode_steps=1024):
+    """The engine of an eval registration with n_envs envs.  env: `Solow-p-q-finite-eval-v0` (seed 1692, reseeded at every reset,
+    so every evaluation plays the same episodes) or `TradeAR1-v0` (fed_gym/__init__.py:3-33, both capped at 1 024 steps)."""
+    from ... import _ffi
+    if env.startswith("Solow-") and env.endswith("-finite-eval-v0"):
+        p, q = (int(v) for v in env.split("-")[1:3])
+        return _ffi.Engine(_ffi.ENV_SOLOW, n_envs, device_id=device_id, seed=1692, flags=_ffi.F_RESEED_EACH_RESET, solow_p=p, solow_q=q,
+                           max_episode_steps=max_episode_steps)
+    if env == "TradeAR1-v0":
+        return _ffi.Engine(_ffi.ENV_TRADE, n_envs, device_id=device_id, seed=1692, n_assets=2, max_episode_steps=max_episode_steps)
+    raise ValueError("no device evaluation for env %r (one of %s)" % (env, ", ".join(ENVS)))
+
+
+class PolicyMonitor(object):
+    """policy_monitor.py:11-118.  env: the eval registration's id.  global_policy_net, state_processor, summary_writer, saver are
+    kept as the reference keeps them (the device does the processing; summary_writer, when given, gets the eval/* scalars through
+    add_scalar).  net: an evaluation net to use instead of building one (its `eng` is the eval engine)."""
+
+    def __init__(self, env, global_policy_net=None, state_processor=None, summary_writer=None, saver=None, num_actions=None,
+                 input_size=None, temporal_size=None, n_envs=1, max_seq_length=5, scale=1.0, device_id=0, max_episode_steps=1024,
+                 net=None):
+        self.env = env
+        self.global_policy_net = global_policy_net
+        self.state_processor = state_processor
+        self.summary_writer = summary_writer
+        self.saver = saver
+        self.max_episode_steps = int(max_episode_steps)
+        self._own = net is None
+        if net is None:
+            from ... import _ffi_gauss
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            eng = make_eval_engine(env, n_envs, device_id, self.max_episode_steps)
+            net = _ffi_gauss.GaussNet(eng, rnn_length=max_seq_length, scale=scale, max_samples=1)       # the "policy_eval" copy
+            want = (net.A, net.S0, net.D)
+            for name, got, exp in zip(("num_actions", "input_size", "temporal_size"), (num_actions, input_size, temporal_size), want):
+                if got is not None and got != exp:
+                    raise ValueError("%s = %r, the device net of %s has %r" % (name, got, env, exp))
+        self.net = net
+        self.n_envs = int(net.eng.E)
+        self.total_rewards, self.episode_lengths = None, None       # every env's, of the last evaluation
+        self.log = {"total_reward": [], "episode_length": [], "mean_total_reward": [], "std_total_reward": [], "n_envs": self.n_envs}
+
+    def eval_once(self, params, max_sequence_length=None):
+        """Copy the parameters (copy_params_op), reset the eval envs, play every env's greedy episode.  Returns env 0's
+        (total_reward, episode_length, rewards)."""
+        if max_sequence_length is not None and max_sequence_length != self.net.R:
+            raise ValueError("max_sequence_length %r: the evaluation net was built with %r" % (max_sequence_length, self.net.R))
+        self.net.set_params(params)
+        self.net.eng.reset()
+        r = self.net.eval(self.max_episode_steps, trace_steps=self.max_episode_steps, trace_fields=("rewards",))
+        self.total_rewards = np.asarray(r["total_reward"], np.float64)
+        self.episode_lengths = np.asarray(r["length"])
+        total_reward, episode_length = float(self.total_rewards[0]), int(self.episode_lengths[0])
+        rewards = [float(v) for v in np.asarray(r["rewards"])[:episode_length, 0]]
+        self.log["total_reward"].append(total_reward)
+        self.log["episode_length"].append(episode_length)
+        self.log["mean_total_reward"].append(float(self.total_rewards.mean()))
+        self.log["std_total_reward"].append(float(self.total_rewards.std()))
+        return total_reward, episode_length, rewards
+
+    def write_scalars(self, global_step):
+        """eval/total_reward and eval/episode_length of env 0 (policy_monitor.py:79-83), eval/mean_total_reward over the envs"""
+        w = self.summary_writer
+        if w is None or not self.log["total_reward"]:
+            return
+        w.add_scalar("eval/total_reward", self.log["total_reward"][-1], global_step)
+        w.add_scalar("eval/episode_length", self.log["episode_length"][-1], global_step)
+        w.add_scalar("eval/mean_total_reward", self.log["mean_total_reward"][-1], global_step)
+        w.flush()
+
+    def write_log(self, total_reward_log_file):
+        """The reference's two keys from env 0 (policy_monitor.py:110-118), plus mean_total_reward, std_total_reward and n_envs."""
+        with open(total_reward_log_file, "w") as f:
+            json.dump(self.log, f)
+
+    def continuous_eval(self, eval_every, get_params, coord, max_seq_length=None, total_reward_log_file=None, get_global_step=None):
+        """Evaluate every eval_every seconds until coord.should_stop() (policy_monitor.py:98-118).  get_params() returns the
+        learner's current flat parameters."""
+        while not coord.should_stop():
+            self.eval_once(get_params(), max_sequence_length=max_seq_length)
+            if get_global_step is not None:
+                self.write_scalars(get_global_step())
+            if total_reward_log_file:
+                self.write_log(total_reward_log_file)
+            if eval_every > 0:
+                time.sleep(eval_every)
+
+    def close(self):
+        if self._own and self.net is not None:
+            eng = self.net.eng
+            self.net.close()
+            eng.close()
+        self.net = None

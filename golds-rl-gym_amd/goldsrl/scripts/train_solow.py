@@ -3,7 +3,9 @@
 A3C worker (include/goldsrl_gaussnet.h).  The reference's settings: t_max 64, max_seq_length 5, value scale 100, always_bootstrap
 on, learning rate 1e-4.  Scalars go to a TF-events file, the checkpoint to <model_dir>/checkpoint.npz.  Every --eval-every updates
 the greedy evaluation of a3c/policy_monitor.py:42-96 plays one episode of the seeded `Solow-1-1-finite-eval-v0` with the action
-sigmoid(mu) and appends to Solow-1-1.json ({total_reward: [...], episode_length: [...]}, policy_monitor.py:110-118)."""
+sigmoid(mu) and appends to Solow-1-1.json ({total_reward: [...], episode_length: [...]}, policy_monitor.py:110-118).  With
+--eval-envs N the evaluation runs on the device instead (goldsrl/agents/a3c/policy_monitor.py): N seeded eval episodes in one
+kernel launch, env 0 the same episode as before; the JSON gains mean_total_reward, std_total_reward and n_envs."""
 import argparse
 import json
 import logging
@@ -15,6 +17,7 @@ import numpy as np
 
 from goldsrl import _ffi, _ffi_gauss
 from goldsrl.agents.a3c.estimators import GaussianPolicyEstimator
+from goldsrl.agents.a3c.policy_monitor import PolicyMonitor
 from goldsrl.agents.state_processors import SolowStateProcessor
 from goldsrl.envs import fed_env
 from goldsrl.utils_tfevents import EventFileWriter
@@ -34,6 +37,8 @@ def get_arg_parser():
     p.add_argument("--updates", type=int, default=100)
     p.add_argument("--eval-every", "--eval_every", dest="eval_every", type=int, default=5,
                    help="evaluate the greedy policy every N updates (0: never)")
+    p.add_argument("--eval-envs", "--eval_envs", dest="eval_envs", type=int, default=0,
+                   help="evaluate N seeded eval episodes on the device, one kernel launch per evaluation (0: one episode driven from the host)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -93,7 +98,13 @@ def main(argv=None):
     os.makedirs(args.model_dir, exist_ok=True)
     writer = EventFileWriter(args.model_dir)
     ckpt = os.path.join(args.model_dir, "checkpoint.npz")
-    monitor = GreedyMonitor(args.device, os.path.join(args.model_dir, "Solow-%d-%d.json" % (P_ORDER, Q_ORDER))) if args.eval_every > 0 else None
+    log_file = os.path.join(args.model_dir, "Solow-%d-%d.json" % (P_ORDER, Q_ORDER))
+    monitor = None
+    if args.eval_every > 0 and args.eval_envs > 0:
+        monitor = PolicyMonitor("Solow-%d-%d-finite-eval-v0" % (P_ORDER, Q_ORDER), summary_writer=writer, n_envs=args.eval_envs,
+                                max_seq_length=MAX_SEQ_LENGTH, scale=SCALE, device_id=args.device)
+    elif args.eval_every > 0:
+        monitor = GreedyMonitor(args.device, log_file)
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.t_max)
@@ -108,9 +119,13 @@ def main(argv=None):
             writer.add_scalar("episode/length", float(np.mean(eps["length"])), step)
         writer.add_scalar("perf/env_steps_per_s", args.envs * args.t_max / dt, step)
         if monitor is not None and ((u + 1) % args.eval_every == 0 or u + 1 == args.updates):
-            total_reward, episode_length = monitor.eval_once(net.get_params())
-            writer.add_scalar("eval/total_reward", total_reward, step)
-            writer.add_scalar("eval/episode_length", episode_length, step)
+            total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
+            if args.eval_envs > 0:
+                monitor.write_scalars(step)
+                monitor.write_log(log_file)
+            else:
+                writer.add_scalar("eval/total_reward", total_reward, step)
+                writer.add_scalar("eval/episode_length", episode_length, step)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d", step, total_reward, episode_length)
         writer.flush()
         logging.info("update %d  global step %d  policy loss %.4g  value loss %.4g  entropy %.4g  %.0f env-steps/s", u + 1, step,

@@ -3,7 +3,9 @@
 one A3C worker (include/goldsrl_gaussnet.h).  The reference's settings: t_max 64, max_seq_length 20, value scale 1,
 always_bootstrap off, learning rate 1e-4.  The reference's TradeWorker cannot run as written; the device form takes the evident
 reading (per-action mu and sigma, the raw draw stored and trained on, tanh to the env).  Scalars go to a
-TF-events file, the checkpoint to <model_dir>/checkpoint.npz."""
+TF-events file, the checkpoint to <model_dir>/checkpoint.npz.  With --eval-every N and --eval-envs M the PolicyMonitor of
+scripts/train_trade.py:94-124 runs on the device (goldsrl/agents/a3c/policy_monitor.py): every N updates M greedy episodes of
+`TradeAR1-v0` in one kernel launch, action tanh(mu); totals go to TradeAR1.json and the eval/* scalars."""
 import argparse
 import logging
 import os
@@ -13,6 +15,7 @@ import time
 import numpy as np
 
 from goldsrl import _ffi, _ffi_gauss
+from goldsrl.agents.a3c.policy_monitor import PolicyMonitor
 from goldsrl.utils_tfevents import EventFileWriter
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO)
@@ -27,6 +30,9 @@ def get_arg_parser():
     p.add_argument("--t_max", type=int, default=64, help="number of steps before performing an update")
     p.add_argument("--envs", "--parallelism", dest="envs", type=int, default=4096, help="number of envs, each one A3C worker")
     p.add_argument("--updates", type=int, default=100)
+    p.add_argument("--eval-every", "--eval_every", dest="eval_every", type=int, default=0,
+                   help="evaluate the greedy policy every N updates (0: never)")
+    p.add_argument("--eval-envs", "--eval_envs", dest="eval_envs", type=int, default=64, help="eval episodes per evaluation")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -48,6 +54,11 @@ def main(argv=None):
     os.makedirs(args.model_dir, exist_ok=True)
     writer = EventFileWriter(args.model_dir)
     ckpt = os.path.join(args.model_dir, "checkpoint.npz")
+    log_file = os.path.join(args.model_dir, "TradeAR1.json")
+    monitor = None
+    if args.eval_every > 0 and args.eval_envs > 0:
+        monitor = PolicyMonitor("TradeAR1-v0", summary_writer=writer, n_envs=args.eval_envs, max_seq_length=MAX_SEQ_LENGTH, scale=SCALE,
+                                device_id=args.device)
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.t_max)
@@ -61,12 +72,20 @@ def main(argv=None):
             writer.add_scalar("episode/total_reward", float(np.mean(eps["total_reward"])), step)
             writer.add_scalar("episode/length", float(np.mean(eps["length"])), step)
         writer.add_scalar("perf/env_steps_per_s", args.envs * args.t_max / dt, step)
+        if monitor is not None and ((u + 1) % args.eval_every == 0 or u + 1 == args.updates):
+            total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
+            monitor.write_scalars(step)
+            monitor.write_log(log_file)
+            logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
+                         episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
         writer.flush()
         logging.info("update %d  global step %d  policy loss %.4g  value loss %.4g  entropy %.4g  %.0f env-steps/s", u + 1, step,
                      stats["policy_loss"], stats["value_loss"], stats["entropy_mean"], args.envs * args.t_max / dt)
         if (u + 1) % args.checkpoint_every == 0 or u + 1 == args.updates:
             net.save_checkpoint(ckpt)
     writer.close()
+    if monitor is not None:
+        monitor.close()
     net.close()
     eng.close()
 

@@ -38,6 +38,14 @@
  * Update: policy and value gradients, each clipped to clip_norm on its own, each to its own RMSProp (ms <- rho ms + (1-rho) g^2,
  * w <- w - lr g / sqrt(ms + eps), ms starts at 1): params <- (params - step_p) - step_v.
  * lr = lr0 * decay_rate^(global_step / decay_steps) with the global step before the update; the global step advances by 2.
+ * Greedy acting (run_n_steps(stochastic=False) / get_greedy_action, worker.py:180-230): grl_anet_set_greedy(net, 1) makes
+ * grl_anet_rollout draw nothing -- raw = mu exactly, the env gets the same sigmoid / tanh of it, the action counter stands still.
+ * Greedy evaluation (PolicyMonitor.eval_once, fed_gym/agents/a3c/policy_monitor.py:42-96): grl_anet_eval plays whole greedy
+ * episodes of every env in ONE kernel launch: a workgroup keeps 64 envs for the episode and runs per step the trunk, the mu tower
+ * (the sigma and value towers are not evaluated), the action, the env step and the window rule -- the device functions the
+ * per-step path runs, so it reproduces a greedy grl_anet_rollout bit for bit up to each env's first done.  The evaluation feeds no
+ * episode records (grl_episodes_*): its totals and lengths are read with grl_anet_read_eval.  These three functions are declared
+ * in goldsrl_gausseval.h, which this header includes.
  * Conventions as in goldsrl.h.
  */
 #ifndef GOLDSRL_GAUSSNET_H
@@ -113,4 +121,7 @@ int grl_anet_read_rollout(grl_anet *net, const char *which, void *host, size_t b
 #ifdef __cplusplus
 }
 #endif
+
+#include "goldsrl_gausseval.h" /* greedy acting and the one-launch greedy evaluation of the same net */
+
 #endif /* GOLDSRL_GAUSSNET_H */
