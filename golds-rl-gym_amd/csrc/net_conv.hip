@@ -204,9 +204,17 @@ struct grl_net : NetLane {
     // forward pass.  Exact: parameters do not change between the two (paac.py:302-387).  keep_version tracks that;
     // GRL_NET_F_RECOMPUTE_FORWARD or too little free memory selects recomputation.
     int keep_level;            // 0: nothing resident, 1: conv3/dense activations, 2: + the per-env trunk tensors the gradient step reads
+                               // 3: + the chunk's index lists (GRL_IDX_LIST)
     float *keep;
     size_t keep_slots;
     long param_version, keep_version;
+    // How the level is chosen (ensure_rollout_bufs, net_train.inc), read when the net is created: GRL_NET_KEEP_LEVEL=1..3 is the
+    // highest level tried (default 3); GRL_NET_KEEP_FREE_MB caps the free memory the choice sees (a comparison only: nothing is
+    // allocated for it), so that the descent 3 -> 2 -> 1 -> 0 can be walked at any size.  grl_net_keep_info reports the outcome.
+    int keep_max_level;
+    bool keep_free_capped;
+    size_t keep_free_cap, keep_headroom, keep_free_seen;
+    int resident_last;         // the last train_rollout* pass read the rollout's resident activations
     float last_inv_total;      // 1 / samples of the last gradient pass (grl_net_apply_grads)
     // lanes
     NetLane lanes[GRL_MAX_LANES];
@@ -717,8 +725,9 @@ static size_t keep_floats_per_slot(const grl_net *net, int level) {
 }
 
 // the activations the gradient step reads point into slot `slot` of the rollout-resident buffer, or at the chunk
-// workspace for slot < 0
-static void bind_activations(grl_net *net, long slot) {
+// workspace for slot < 0.  Returns the bytes of the slot the walk covered (0 for the workspace): ensure_rollout_bufs holds it
+// to keep_floats_per_slot, which sizes the same slot a second time.
+static size_t bind_activations(grl_net *net, long slot) {
     net->a3 = net->ws_a3; net->d1 = net->ws_d1; net->d2 = net->ws_d2; net->p1 = net->ws_p1; net->v1 = net->ws_v1; net->v2 = net->ws_v2;
     net->a3sh = net->ws_a3sh; net->d3 = net->ws_d3; net->m3 = net->ws_m3;
     net->mb_d2 = net->ws_mb; net->mb_v1 = net->ws_mb + (size_t)net->chunk * 4;
@@ -729,9 +738,10 @@ static void bind_activations(grl_net *net, long slot) {
         GRL_IDX_LIST(X)
 #undef X
     }
-    if (slot < 0 || !net->keep) return;
+    if (slot < 0 || !net->keep) return 0;
     const size_t c = net->chunk;
-    float *b = net->keep + (size_t)slot * keep_floats_per_slot(net, net->keep_level);
+    float *const b0 = net->keep + (size_t)slot * keep_floats_per_slot(net, net->keep_level);
+    float *b = b0;
     if (net->shared_trunk) {
         net->a3sh = b; b += (c / 10) * 3136;
         net->d3 = b; b += c * 1600;
@@ -752,13 +762,16 @@ static void bind_activations(grl_net *net, long slot) {
         net->m2s = reinterpret_cast<unsigned long long *>(b); b += c * 18;      // 9 words per sample
         net->ulist = reinterpret_cast<signed char *>(b); b += ((c * 9 + 3) / 4 + 3) / 4 * 4;
     }
+    size_t walked = (size_t)(b - b0) * sizeof(float);
     if (net->shared_trunk && net->keep_level >= 3) {
-        const size_t used = (size_t)(b - (net->keep + (size_t)slot * keep_floats_per_slot(net, net->keep_level)));
+        const size_t used = (size_t)(b - b0);
         char *q = reinterpret_cast<char *>(b + (((used + 31) & ~(size_t)31) - used));
 #define X(m, bytes) net->m = reinterpret_cast<decltype(net->m)>(q); q += ((size_t)(bytes) + 127) & ~(size_t)127;
         GRL_IDX_LIST(X)
 #undef X
+        walked = (size_t)(q - reinterpret_cast<char *>(b0));
     }
+    return walked;
 }
 
 // reuse_tail: a3..v2 of this chunk are already resident (bind_activations); only the cheap per-env trunk, the
@@ -1031,6 +1044,15 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
         return fail(h, GRL_E_INVALID, "grl_net_create: max_chunk_samples must be a multiple of 10 in 10..131072");
     if (cfg->num_actions < 1 || cfg->num_actions > GRL_MAX_ACTIONS)
         return fail(h, GRL_E_INVALID, "grl_net_create: num_actions must be in 1..4");
+    bool free_capped = false;
+    unsigned long long free_mb = 0;
+    if (const char *e = getenv("GRL_NET_KEEP_FREE_MB")) {      // decimal digits only, below 2^44: anything else is refused, not read as 0
+        char *end = nullptr;
+        free_mb = strtoull(e, &end, 10);
+        if (*e < '0' || *e > '9' || *end != 0 || free_mb >= (1ull << 44))
+            return fail(h, GRL_E_INVALID, "grl_net_create: GRL_NET_KEEP_FREE_MB must be a number of MB (decimal digits)");
+        free_capped = true;
+    }
     hipSetDevice(h->cfg.device_id);
     grl_net *n = new grl_net();
     n->h = h; n->cfg = *cfg; n->chunk = cfg->max_chunk_samples; n->adam_t = 0;
@@ -1041,6 +1063,10 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
     n->keep_level = 0;
     n->ar_ev0 = n->ar_ev1 = nullptr; n->ar_pending = 0; n->ar_calls = 0; n->ht_rollouts = n->ht_updates = 0; n->ht_rollout_ms = n->ht_train_enq_ms = n->ht_train_wait_ms = 0.0; n->ht_train_t0 = 0.0; n->ar_ms_total = 0.0; n->ar_ms_last = 0.f;
     n->keep = nullptr; n->keep_slots = 0; n->param_version = 0; n->keep_version = -1;
+    n->keep_max_level = 3; n->keep_free_capped = false; n->keep_free_cap = 0; n->keep_headroom = 0; n->keep_free_seen = 0;
+    n->resident_last = 0;
+    if (const char *e = getenv("GRL_NET_KEEP_LEVEL")) n->keep_max_level = atoi(e);      // A/B: 2 = re-index in the gradient step
+    n->keep_free_capped = free_capped; n->keep_free_cap = (size_t)free_mb << 20;
     n->shared_trunk = (cfg->reserved & GRL_NET_F_PER_AGENT_TRUNK) ? 0 : 1;     // the plain per-agent evaluation is the A/B reference
     n->cur_lane = 0; n->last_lane = 0;
     for (int k = 0; k < GRL_MAX_LANES; ++k) { n->lane_stream[k] = nullptr; n->ev_join[k] = nullptr; n->side_stream[k] = nullptr; n->ev_side0[k] = n->ev_side1[k] = n->ev_side2[k] = nullptr; }

@@ -1481,17 +1481,33 @@ static int ensure_rollout_bufs(grl_net *net, int T) {
     if (net->keep) { (void)hipFree(net->keep); net->keep = nullptr; net->keep_slots = 0; }
     net->keep_version = -1;
     net->keep_level = 0;
+    net->keep_headroom = 0; net->keep_free_seen = 0;
     if (!(net->cfg.reserved & GRL_NET_F_RECOMPUTE_FORWARD)) {
         const size_t ce = net->chunk / 10, nchunks = ((size_t)E + ce - 1) / ce, slots = (size_t)T * nchunks;
         size_t free_b = 0, total_b = 0;
         NET_HIP(net, hipMemGetInfo(&free_b, &total_b));
+        if (net->keep_free_capped) free_b = std::min(free_b, net->keep_free_cap);      // GRL_NET_KEEP_FREE_MB: the descent below at any size
         const size_t headroom = ((size_t)12 << 30) + (size_t)net->chunk * 160000;   // training buffers: ~105 KB per chunk sample
-        static const int max_level = getenv("GRL_NET_KEEP_LEVEL") ? atoi(getenv("GRL_NET_KEEP_LEVEL")) : 3;      // A/B: 2 = re-index in the gradient step
+        net->keep_headroom = headroom; net->keep_free_seen = free_b;
+        const int max_level = net->keep_max_level;      // GRL_NET_KEEP_LEVEL, read by grl_net_create
         const bool lists = net->trunk_skip && net->expand2_gemm;      // level 3 binds the trunk's row lists: they exist in the default (list) form only
         for (int level = net->shared_trunk ? std::min(lists ? 3 : 2, std::max(max_level, 1)) : 1; level >= 1 && !net->keep; --level) {
             const size_t bytes = slots * keep_floats_per_slot(net, level) * sizeof(float);
             if (free_b > bytes + headroom && hipMalloc((void **)&net->keep, bytes) == hipSuccess) { net->keep_slots = slots; net->keep_level = level; }
             else { net->keep = nullptr; (void)hipGetLastError(); }
+        }
+        if (net->keep) {
+            // before anything is written there: the pointer walk over the last slot ends where the slot does (the two are written
+            // down twice; a slot that ends anywhere else overlaps its neighbour).  The net is left bound to the workspace: what it
+            // was bound to may have been a slot of the buffer freed above, and every user binds before it reads.
+            const size_t walked = bind_activations(net, (long)slots - 1);
+            bind_activations(net, -1);
+            if (walked != keep_floats_per_slot(net, net->keep_level) * sizeof(float)) {
+                (void)hipFree(net->keep);
+                net->keep = nullptr; net->keep_slots = 0; net->keep_level = 0;
+                net->T = 0;      // no rollout stored: the next call comes through here again
+                return nfail(net, GRL_E_INVALID, "ensure_rollout_bufs: bind_activations and keep_floats_per_slot disagree about a resident slot");
+            }
         }
     }
     return GRL_OK;
@@ -1594,6 +1610,7 @@ static int train_rollout_impl(grl_net *net, float lr, float *stats_host, int fin
         return rc;
     }
     const bool resident = net->keep && net->keep_version >= 0 && net->keep_version == net->param_version;
+    net->resident_last = resident ? 1 : 0;      // grl_net_keep_info
     long ci = 0;
     for (int t = 0; t < T; ++t)
         for (int e0 = 0; e0 < E; e0 += ce, ++ci) {
@@ -1721,6 +1738,19 @@ int grl_net_host_times(grl_net *net, int64_t *rollouts_out, int64_t *updates_out
     if (rollout_enqueue_ms_out) *rollout_enqueue_ms_out = net->ht_rollout_ms;
     if (train_enqueue_ms_out) *train_enqueue_ms_out = net->ht_train_enq_ms;
     if (train_wait_ms_out) *train_wait_ms_out = net->ht_train_wait_ms;
+    return GRL_OK;
+}
+
+int grl_net_keep_info(grl_net *net, int32_t *level_out, int64_t *slots_out, int64_t *slot_bytes_out, int64_t *headroom_bytes_out,
+                      int64_t *free_bytes_out, int32_t *resident_out) {
+    if (!net) return GRL_E_INVALID;
+    if (level_out) *level_out = net->keep ? net->keep_level : 0;
+    if (slots_out) *slots_out = net->keep ? (int64_t)net->keep_slots : 0;
+    if (slot_bytes_out)
+        for (int level = 1; level <= 3; ++level) slot_bytes_out[level - 1] = (int64_t)(keep_floats_per_slot(net, level) * sizeof(float));
+    if (headroom_bytes_out) *headroom_bytes_out = (int64_t)net->keep_headroom;
+    if (free_bytes_out) *free_bytes_out = (int64_t)net->keep_free_seen;
+    if (resident_out) *resident_out = net->resident_last;
     return GRL_OK;
 }
 

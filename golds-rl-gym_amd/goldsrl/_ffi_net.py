@@ -46,6 +46,7 @@ NET_SIGNATURES = {
     "grl_net_debug_obs_index": (C.c_int, [_P, _I, _P, _P, _P, _P, _SZ]),
     "grl_net_range_info": (C.c_int, [_P, _P, _P, _P]),
     "grl_net_host_times": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "grl_net_keep_info": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "grl_net_set_gemm_f32": (C.c_int, [_P, C.c_int32]),
     "grl_net_range_return_info": (C.c_int, [_P, _P, _P, _P, _P]),
     "grl_net_set_range_return": (C.c_int, [_P, C.c_int32]),
@@ -278,6 +279,16 @@ class ConvNet(object):
         self._check(self.lib.grl_net_host_times(self.n, C.byref(ro), C.byref(up), C.byref(a), C.byref(b), C.byref(c)))
         return {"rollouts": int(ro.value), "updates": int(up.value), "rollout_enqueue_ms": a.value, "train_enqueue_ms": b.value,
                 "train_wait_ms": c.value}
+
+    def keep_info(self):
+        """Which form of the gradient step over a rollout this net runs (grl_net_keep_info): 'level' 0..3 and 'slots' of the resident
+        buffer (0, 0 before the first rollout), 'slot_bytes' {1, 2, 3: bytes per slot at that level}, 'headroom_bytes' and
+        'free_bytes' the choice was made with, 'resident' = the last train_rollout* call read the rollout's resident activations."""
+        lv, res, slots, hr, fr = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        sb = (C.c_int64 * 3)()
+        self._check(self.lib.grl_net_keep_info(self.n, C.byref(lv), C.byref(slots), sb, C.byref(hr), C.byref(fr), C.byref(res)))
+        return {"level": lv.value, "slots": int(slots.value), "slot_bytes": {1: int(sb[0]), 2: int(sb[1]), 3: int(sb[2])},
+                "headroom_bytes": int(hr.value), "free_bytes": int(fr.value), "resident": bool(res.value)}
 
     def range_info(self):
         """Arithmetic form of the GEMMs: 'gemm_f32' once a range violation (or set_gemm_f32) moved the net to the fp32 form,

@@ -175,6 +175,25 @@ int grl_net_comm_info(grl_net *net, int32_t *count_out, int32_t *user_rank_out, 
 int grl_net_host_times(grl_net *net, int64_t *rollouts_out, int64_t *updates_out, double *rollout_enqueue_ms_out,
                        double *train_enqueue_ms_out, double *train_wait_ms_out);
 
+/* Which form of the gradient step over a rollout this net runs.  grl_net_rollout keeps the forward pass's activations of every
+ * (step, chunk) in one slot of a resident buffer when it fits into the device's free memory beside a headroom for the training
+ * workspace; how much of a chunk is kept is the level, tried from the top down:
+ *   3  conv3 / dense activations, the per-env trunk tensors and the chunk's index lists: the gradient step rebuilds nothing
+ *      (the default form of the trunk only: not with GRL_TRUNK_SKIP=off or GRL_NET_EXPAND2=lds in the environment)
+ *   2  without the lists: the gradient step runs the index kernels again
+ *   1  conv3 / dense activations only: the env-level trunk is evaluated again (the only level of GRL_NET_F_PER_AGENT_TRUNK)
+ *   0  nothing resident: GRL_NET_F_RECOMPUTE_FORWARD, or nothing fits
+ * Environment, read by grl_net_create: GRL_NET_KEEP_LEVEL=1..3 is the highest level tried (default 3); GRL_NET_KEEP_FREE_MB=n
+ * lets the choice see min(free memory, n MB) -- a comparison only, nothing is allocated for it; a value that is not a
+ * decimal number fails grl_net_create with GRL_E_INVALID.
+ * *level_out / *slots_out: what the last (re)allocation of the rollout buffers chose (0 / 0 before the first rollout);
+ * slot_bytes_out[3]: bytes per slot this net would take at levels 1, 2, 3; *headroom_bytes_out / *free_bytes_out: the headroom and
+ * the free memory of that choice (0 with GRL_NET_F_RECOMPUTE_FORWARD); *resident_out = 1 when the LAST grl_net_train_rollout*
+ * call read resident activations -- 0 when it recomputed them: level 0, parameters changed since the rollout (an upload, or an
+ * update already applied on it), or a rollout of more steps x chunks than there are slots.  Any out pointer may be NULL. */
+int grl_net_keep_info(grl_net *net, int32_t *level_out, int64_t *slots_out, int64_t *slot_bytes_out, int64_t *headroom_bytes_out,
+                      int64_t *free_bytes_out, int32_t *resident_out);
+
 /* Per-kernel timing of the GEMM kernels for bench.py's roofline (HIP events around every launch
  * of gemm_rowk / gemm_tn while enabled): returns launches, summed ms and summed FLOPs. */
 int grl_net_profile_enable(grl_net *net, int32_t on);

@@ -131,14 +131,9 @@ def test_forward_and_gradients_match_the_oracle_above_one_row_tile(E, regime):
     eng.close()
 
 
-@pytest.mark.parametrize("regime", ["rim", "interior"])
-def test_rollout_gradient_matches_the_oracle_at_64_envs(regime):
-    """grl_net_rollout(T = 3) + grl_net_train_rollout_grads at 64 envs (1 920 samples, chunks of 500: four per step, the
-    rollout-resident activations in use) against the oracle's pieces: the stored observations, raw actions, returns and
-    advantages of the rollout fed to the float64 loss / gradient of the same parameters (paac.py:360-387: time-major
-    flatten, adv / scale, mean over T * B).  interior (round 5): the agents start inside the observation box, near the swarm -- where
-    a policy takes them within 100 updates (profiles/r04_training_geometry.json) -- so every step of the rollout runs 3 x 3 slot
-    rectangles, 5 x 5 supports and a full union mask through the resident-activation path."""
+def _rollout_form(regime, flags, keep_level, monkeypatch):
+    """One 3-step rollout at 64 envs from fixed seeds and its gradient, in one form of the gradient step: what the rollout stored,
+    (statistics, gradient), keep_info after the step."""
     from goldsrl import _ffi, _ffi_net
     E, T = 64, 3
     B = E * 10
@@ -153,18 +148,45 @@ def test_rollout_gradient_matches_the_oracle_at_64_envs(regime):
         eng.set_state("SWARM_XA", xa)
         eng.observe()
         eng.wait()
-    flat, p = _biased_params(9)
-    net = _ffi_net.ConvNet(eng, max_chunk_samples=500)
-    net.set_params(flat)
+    monkeypatch.delenv("GRL_NET_KEEP_FREE_MB", raising=False)
+    if keep_level is None:
+        monkeypatch.delenv("GRL_NET_KEEP_LEVEL", raising=False)
+    else:
+        monkeypatch.setenv("GRL_NET_KEEP_LEVEL", str(keep_level))      # read when the net is created
+    net = _ffi_net.ConvNet(eng, max_chunk_samples=500, reserved=flags)
+    net.set_params(_biased_params(9)[0])
     net.rollout(T, 0)
     eng.wait()
-    lb = net.read_rollout("locust_bins", (T, E, 80, 2), np.uint8)
-    ab = net.read_rollout("agent_bins", (T, E, 10, 2), np.uint8)
-    ps = net.read_rollout("positions", (T, E, 10, 2), np.uint8)
+    ro = {"lb": net.read_rollout("locust_bins", (T, E, 80, 2), np.uint8), "ab": net.read_rollout("agent_bins", (T, E, 10, 2), np.uint8),
+          "ps": net.read_rollout("positions", (T, E, 10, 2), np.uint8), "acts": net.read_rollout("actions", (T, B, 2)),
+          "vals": net.read_rollout("values", (T, B)), "rews": net.read_rollout("rewards", (T, B)), "yy": net.read_rollout("y", (T, B)),
+          "adv": net.read_rollout("adv", (T, B)), "boot": net.read_rollout("boot", (B,))}
+    st = net.train_rollout_grads()
+    grads, info = net.get_grads(), net.keep_info()
+    net.close()
+    eng.close()
+    return ro, st, grads, info
+
+
+@pytest.mark.parametrize("regime", ["rim", "interior"])
+def test_rollout_gradient_matches_the_oracle_at_64_envs(regime, monkeypatch):
+    """grl_net_rollout(T = 3) + grl_net_train_rollout_grads at 64 envs (1 920 samples, chunks of 500 and 140: two per step, the
+    rollout-resident activations in use) against the oracle's pieces: the stored observations, raw actions, returns and
+    advantages of the rollout fed to the float64 loss / gradient of the same parameters (paac.py:360-387: time-major
+    flatten, adv / scale, mean over T * B).  interior (round 5): the agents start inside the observation box, near the swarm -- where
+    a policy takes them within 100 updates (profiles/r04_training_geometry.json) -- so every step of the rollout runs 3 x 3 slot
+    rectangles, 5 x 5 supports and a full union mask through the resident-activation path.
+    Every form of the gradient step goes against the SAME oracle evaluation: the default net (which must have run at level 3 on
+    resident activations), GRL_NET_KEEP_LEVEL = 2 and 1, and GRL_NET_F_RECOMPUTE_FORWARD, each on a fresh engine and net from the
+    same seeds -- their stored rollouts are asserted identical first, so one set of oracle inputs serves all four."""
+    E, T = 64, 3
+    _, p = _biased_params(9)
+    ro, st, grads, info = _rollout_form(regime, 0, None, monkeypatch)
+    assert info["level"] == 3 and info["resident"] and info["slots"] == T * 2, info      # 500 + 140 samples per step
+    lb, ab, ps = ro["lb"], ro["ab"], ro["ps"]
     inside = ((ps.astype(int) >= 8) & (ps.astype(int) <= 75)).all(axis=3).mean()
     assert inside > 0.95 if regime == "interior" else inside < 0.9, (regime, inside)      # the premise of the case
-    acts = net.read_rollout("actions", (T, B, 2)); vals = net.read_rollout("values", (T, B)); rews = net.read_rollout("rewards", (T, B))
-    yy = net.read_rollout("y", (T, B)); adv = net.read_rollout("adv", (T, B)); boot = net.read_rollout("boot", (B,))
+    acts, vals, rews, yy, adv, boot = ro["acts"], ro["vals"], ro["rews"], ro["yy"], ro["adv"], ro["boot"]
     states = np.concatenate([_states(lb[t], ab[t], ps[t]) for t in range(T)])
     mu, sigma, vs = NN.conv_forward(p, states, 1000.0)
     np.testing.assert_allclose(vals.reshape(-1), vs, rtol=2e-5, atol=2e-5 * 1000.0)
@@ -173,11 +195,21 @@ def test_rollout_gradient_matches_the_oracle_at_64_envs(regime):
     np.testing.assert_allclose(adv, oadv / 1000.0, rtol=1e-5, atol=1e-6)
     loss, pl, cl, g, _ = NN.conv_loss_and_grads(p, states, acts.reshape(-1, 2).astype(np.float64), adv.reshape(-1).astype(np.float64),
                                                 yy.reshape(-1).astype(np.float64), 0.02, 1000.0)
-    st = net.train_rollout_grads()
     np.testing.assert_allclose(st["loss"], loss, rtol=1e-4)
-    _check_grads(net.get_grads(), g, p, states, acts.reshape(-1, 2), adv.reshape(-1), yy.reshape(-1), tag="rollout-" + regime)
-    net.close()
-    eng.close()
+    _check_grads(grads, g, p, states, acts.reshape(-1, 2), adv.reshape(-1), yy.reshape(-1), tag="rollout-" + regime)
+    checked = [grads]      # gradients that went through _check_grads: one that equals any of them bit for bit has passed it too
+    for flags, keep_level, want in ((0, 2, (2, True)), (0, 1, (1, True)), (2, None, (0, False))):
+        ro_f, st_f, grads_f, info_f = _rollout_form(regime, flags, keep_level, monkeypatch)
+        tag = "rollout-%s-%s" % (regime, "recompute" if flags else "level%d" % keep_level)
+        assert (info_f["level"], info_f["resident"]) == want, (tag, info_f)
+        for k in ro:
+            assert np.array_equal(ro_f[k], ro[k]), (tag, k)
+        np.testing.assert_allclose(st_f["loss"], loss, rtol=1e-4)
+        if any(np.array_equal(grads_f, c) for c in checked):
+            print("%s: the gradient equals one already held to the oracle, bit for bit" % tag)
+            continue
+        _check_grads(grads_f, g, p, states, acts.reshape(-1, 2), adv.reshape(-1), yy.reshape(-1), tag=tag)
+        checked.append(grads_f)
 
 
 def test_workspace_left_by_other_geometry_is_never_read():
