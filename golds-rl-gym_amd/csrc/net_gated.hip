@@ -12,6 +12,7 @@
 //             forms both losses' data and weight gradients and sums the weight gradients of the groups it loops over into a
 //             private slab [policy P | value P]; the slabs are reduced in a fixed order (bitwise reproducible runs)
 //   update    two float64 sums of squares, clip factors, both RMSProp steps -- on the device
+//   eval      whole greedy episodes in one launch (net_gated_eval.inc): a workgroup keeps its 64 envs, class + normal towers only
 #include <stdlib.h>
 #include <string.h>
 
@@ -23,6 +24,7 @@
 #include "common.h"
 #include "rng.h"
 #include "rollout_dev.h"
+#include "ticker_dev.h"
 
 namespace grl {
 
@@ -71,6 +73,7 @@ struct GArgs {
     float *raw_out;                     // (n,2)
     uint64_t seed;
     uint32_t env_off, counter;
+    int greedy;                         // the choice is the argmax, raw = mu[choice], nothing is drawn (grl_gnet_set_greedy)
     // backward
     const int32_t *choices;
     const float *raw, *adv, *tgt, *wt;  // wt may be null (all 1)
@@ -225,6 +228,19 @@ __device__ __forceinline__ void softmax3(float l0, float l1, float l2, float &p0
     p0 = e0 / z; p1 = e1 / z; p2 = e2 / z;
 }
 
+// The greedy action of one asset: the first index of the largest of the three float32 probabilities (np.argmax of
+// get_greedy_action, worker.py:370-372: a tie goes to the lower index), raw = mu[choice], fraction = the worker's float64 sigmoid
+// (transform_raw_action, worker.py:491-494) rounded to float32.
+__device__ __forceinline__ void gated_greedy_pick(float p0, float p1, float p2, float m0, float m1, float m2, int &choice, float &raw,
+                                                  float &fraction) {
+    int ch = p1 > p0 ? 1 : 0;
+    const float best = ch ? p1 : p0;
+    if (p2 > best) ch = 2;
+    choice = ch;
+    raw = ch == 0 ? m0 : (ch == 1 ? m1 : m2);
+    fraction = (float)(1.0 / (1.0 + exp(-(double)raw)));
+}
+
 // one launch per forward pass (predict, a rollout step, the bootstrap); with a.act: the draw and the env action as well
 __global__ __launch_bounds__(256) void gated_forward_kernel(GArgs a) {
     extern __shared__ float lds[];
@@ -254,7 +270,17 @@ __global__ __launch_bounds__(256) void gated_forward_kernel(GArgs a) {
         }
         if (wave == 0 && a.vals) a.vals[s] = a.scale * O[lane];
     }
-    if (a.act && valid && wave < 2) {
+    if (a.act && valid && wave < 2 && a.greedy) {
+        const int as = wave;
+        int ch;
+        float raw, frac;
+        gated_greedy_pick(PR[(3 * as) * LS + lane], PR[(3 * as + 1) * LS + lane], PR[(3 * as + 2) * LS + lane], MU[(3 * as) * LS + lane],
+                          MU[(3 * as + 1) * LS + lane], MU[(3 * as + 2) * LS + lane], ch, raw, frac);
+        a.choice_out[(size_t)s * 2 + as] = ch;
+        a.raw_out[(size_t)s * 2 + as] = raw;
+        a.act[(size_t)s * 4 + as] = (float)ch;
+        a.act[(size_t)s * 4 + 2 + as] = frac;
+    } else if (a.act && valid && wave < 2) {
         // get_random_discrete_action (worker.py:223-227) + get_random_action (:460-464) + transform_raw_action (:491-494)
         const int as = wave;
         double u, u1, nz, nz1;
@@ -450,6 +476,19 @@ __device__ __forceinline__ void gated_window_restart(float *win, int R, const fl
     for (int i = GD; i < R * GD; ++i) win[i] = 0.f;
 }
 
+// after the env step: the window restarts on done (o is the reset observation) or takes the new row; returns the env's new k
+__device__ __forceinline__ int gated_window_step(float *w, int R, int k, bool done, const float *o) {
+    if (done) { gated_window_restart(w, R, o); return 0; }
+    k += 1;
+    if (k < R) {
+        for (int i = 0; i < GD; ++i) w[k * GD + i] = o[3 + i];
+    } else {
+        for (int i = 0; i < (R - 1) * GD; ++i) w[i] = w[i + GD];
+        for (int i = 0; i < GD; ++i) w[(R - 1) * GD + i] = o[3 + i];
+    }
+    return k;
+}
+
 // before a rollout: envs the handle (re)set since (elapsed 0), or all of them the first time, start a new window
 __global__ void gated_sync_kernel(const int32_t *__restrict__ elapsed, const float *__restrict__ obs, float *__restrict__ win,
                                   int32_t *__restrict__ kstep, int E, int R, int all) {
@@ -481,23 +520,15 @@ __global__ void gated_post_kernel(const float *__restrict__ reward, const uint8_
     rew[e] = reward[e];
     dn[e] = d ? 1.0f : 0.0f;
     mask[e] = d ? 0.0f : 1.0f;
-    float *w = win + (size_t)e * R * GD;
-    const float *o = obs + (size_t)e * GS0;
-    if (d) { gated_window_restart(w, R, o); kstep[e] = 0; return; }
-    const int k = kstep[e] + 1;
-    kstep[e] = k;
-    if (k < R) {
-        for (int i = 0; i < GD; ++i) w[k * GD + i] = o[3 + i];
-    } else {
-        for (int i = 0; i < (R - 1) * GD; ++i) w[i] = w[i + GD];
-        for (int i = 0; i < GD; ++i) w[(R - 1) * GD + i] = o[3 + i];
-    }
+    kstep[e] = gated_window_step(win + (size_t)e * R * GD, R, kstep[e], d, obs + (size_t)e * GS0);
 }
 
 __global__ void gated_boot_mask_kernel(float *__restrict__ boot, const float *__restrict__ mask, int E) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < E) boot[e] = boot[e] * mask[e];      // 0 behind a finished episode (worker.py:232-237)
 }
+
+#include "net_gated_eval.inc"
 
 }  // namespace grl
 
@@ -510,6 +541,7 @@ struct grl_gnet {
     double *stats64;                              // 4 loss sums, then 2 x kA3cSumsqBlocks partial sums
     int64_t global_step;
     uint64_t act_counter;
+    int greedy;                                   // grl_gnet_set_greedy
     // host-sample staging
     float *d_states, *d_win, *d_raw, *d_adv, *d_tgt, *d_wt, *d_probs, *d_mu, *d_sigma, *d_vals;
     int32_t *d_choices;
@@ -522,9 +554,17 @@ struct grl_gnet {
     int win_init;
     int T;
     float *ro_states, *ro_win, *ro_raw, *ro_probs, *ro_mu, *ro_sigma, *ro_val, *ro_rew, *ro_done, *ro_mask, *ro_wt, *ro_adv, *ro_tgt;
-    float *ro_boot, *ro_act, *boot_states, *boot_win;
+    float *ro_boot, *ro_act, *boot_states, *boot_win;      // ro_act (T,E,4): the action each env was stepped with
     int32_t *ro_choices;
-    std::vector<void *> allocs, ro_allocs, ws_allocs;
+    // grl_gnet_eval: per-env results and the trace of the first ev_trace steps
+    double *ev_total;
+    int32_t *ev_len;
+    uint8_t *ev_fin;
+    float *ev_states, *ev_probs, *ev_mu, *ev_actions, *ev_rew, *ev_done;
+    int32_t *ev_choices;
+    int32_t ev_reset_count;                       // E, the source of the reset list's count (outlives the async copy)
+    int ev_trace, ev_trace_cap, ev_played;        // ev_played: -1 until grl_gnet_read_eval has looked, -2 before any evaluation
+    std::vector<void *> allocs, ro_allocs, ws_allocs, ev_allocs;
 };
 
 namespace grl {
@@ -618,9 +658,26 @@ static int ensure_rollout(grl_gnet *net, int T) {
     auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = galloc(net, p, cnt, net->ro_allocs); };
     Al(&net->ro_states, TE * GS0); Al(&net->ro_win, TE * R * GD); Al(&net->ro_raw, TE * 2); Al(&net->ro_probs, TE * 6);
     Al(&net->ro_mu, TE * 6); Al(&net->ro_sigma, TE * 6); Al(&net->ro_val, TE); Al(&net->ro_rew, TE); Al(&net->ro_done, TE);
-    Al(&net->ro_mask, TE); Al(&net->ro_wt, TE); Al(&net->ro_adv, TE); Al(&net->ro_tgt, TE);
+    Al(&net->ro_mask, TE); Al(&net->ro_wt, TE); Al(&net->ro_adv, TE); Al(&net->ro_tgt, TE); Al(&net->ro_act, TE * 4);
     if (rc == GRL_OK) rc = galloc(net, &net->ro_choices, TE * 2, net->ro_allocs);
     if (rc == GRL_OK) net->T = T;
+    return rc;
+}
+
+// the trace buffers of grl_gnet_eval for `steps` steps (they only grow)
+static int ensure_eval_trace(grl_gnet *net, int steps) {
+    if (steps <= net->ev_trace_cap) return GRL_OK;
+    GNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    for (void *p : net->ev_allocs) hipFree(p);
+    net->ev_allocs.clear();
+    net->ev_trace_cap = -1;
+    const size_t SE = (size_t)steps * net->h->E;
+    int rc = GRL_OK;
+    auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = galloc(net, p, cnt, net->ev_allocs); };
+    Al(&net->ev_states, SE * GS0); Al(&net->ev_probs, SE * 6); Al(&net->ev_mu, SE * 6); Al(&net->ev_actions, SE * 4); Al(&net->ev_rew, SE);
+    Al(&net->ev_done, SE);
+    if (rc == GRL_OK) rc = galloc(net, &net->ev_choices, SE * 2, net->ev_allocs);
+    if (rc == GRL_OK) net->ev_trace_cap = steps;
     return rc;
 }
 
@@ -651,23 +708,28 @@ int grl_gnet_create(grl_handle *h, const grl_gnet_config *cfg, grl_gnet **out) {
     hipSetDevice(h->cfg.device_id);
     grl_gnet *n = new grl_gnet();
     n->h = h; n->cfg = *cfg; n->off = gated_offsets();
-    n->global_step = 0; n->act_counter = 0; n->ws_blocks = 0; n->win_init = 0; n->T = 0;
+    n->global_step = 0; n->act_counter = 0; n->greedy = 0; n->ws_blocks = 0; n->win_init = 0; n->T = 0;
+    n->ev_trace = 0; n->ev_trace_cap = -1; n->ev_played = -2;
     const size_t ms = cfg->max_samples, P = n->off.total, R = cfg->rnn_length, E = h->E;
     int rc = GRL_OK;
     auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = galloc(n, p, cnt, n->allocs); };
     Al(&n->params, P); Al(&n->grads, 2 * P); Al(&n->msp, P); Al(&n->msv, P); Al(&n->stats, 8);
     Al(&n->d_states, ms * GS0); Al(&n->d_win, ms * R * GD); Al(&n->d_raw, ms * 2); Al(&n->d_adv, ms); Al(&n->d_tgt, ms); Al(&n->d_wt, ms);
     Al(&n->d_probs, ms * 6); Al(&n->d_mu, ms * 6); Al(&n->d_sigma, ms * 6); Al(&n->d_vals, ms);
-    Al(&n->win, E * R * GD); Al(&n->ro_boot, E); Al(&n->ro_act, E * 4); Al(&n->boot_states, E * GS0); Al(&n->boot_win, E * R * GD);
+    Al(&n->win, E * R * GD); Al(&n->ro_boot, E); Al(&n->boot_states, E * GS0); Al(&n->boot_win, E * R * GD);
     if (rc == GRL_OK) rc = galloc(n, &n->d_choices, ms * 2, n->allocs);
     if (rc == GRL_OK) rc = galloc(n, &n->kstep, E, n->allocs);
     if (rc == GRL_OK) rc = galloc(n, &n->stats64, 4 + 2 * kA3cSumsqBlocks, n->allocs);
+    if (rc == GRL_OK) rc = galloc(n, &n->ev_total, E, n->allocs);
+    if (rc == GRL_OK) rc = galloc(n, &n->ev_len, E, n->allocs);
+    if (rc == GRL_OK) rc = galloc(n, &n->ev_fin, E, n->allocs);
     if (rc == GRL_OK) {      // RMSProp ms starts at ones (TF 1.x)
         hipLaunchKernelGGL(a3c_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msp, (long)P, 1.0f);
         hipLaunchKernelGGL(a3c_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, n->msv, (long)P, 1.0f);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gated_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATED_LDS);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gated_backward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATED_LDS);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)gated_eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GATED_LDS);
         if (e != hipSuccess) rc = gfail(n, GRL_E_HIP, std::string("grl_gnet_create: ") + hipGetErrorString(e));
     }
     if (rc != GRL_OK) {
@@ -686,6 +748,7 @@ int grl_gnet_destroy(grl_gnet *n) {
     for (void *p : n->allocs) hipFree(p);
     for (void *p : n->ro_allocs) hipFree(p);
     for (void *p : n->ws_allocs) hipFree(p);
+    for (void *p : n->ev_allocs) hipFree(p);
     delete n;
     return GRL_OK;
 }
@@ -795,15 +858,16 @@ int grl_gnet_rollout(grl_gnet *net, int32_t T) {
                            net->ro_win + o * R * GD, net->ro_wt + o);
         GArgs a = gargs(net, E, net->ro_states + o * GS0, net->ro_win + o * R * GD);
         a.probs = net->ro_probs + o * 6; a.mu = net->ro_mu + o * 6; a.sigma = net->ro_sigma + o * 6; a.vals = net->ro_val + o;
-        a.act = net->ro_act; a.choice_out = net->ro_choices + o * 2; a.raw_out = net->ro_raw + o * 2;
+        a.act = net->ro_act + o * 4; a.choice_out = net->ro_choices + o * 2; a.raw_out = net->ro_raw + o * 2;
         a.seed = h->cfg.seed; a.env_off = (uint32_t)h->cfg.env_id_offset; a.counter = (uint32_t)(net->act_counter + (uint64_t)t);
+        a.greedy = net->greedy;
         if ((rc = launch_fwd(net, a))) return rc;
-        if ((rc = ticker_launch_step(h, net->ro_act))) return gfail(net, rc, h->err);
+        if ((rc = ticker_launch_step(h, net->ro_act + o * 4))) return gfail(net, rc, h->err);
         if ((rc = episodes_launch_account(h))) return gfail(net, rc, h->err);
         hipLaunchKernelGGL(gated_post_kernel, dim3(eb), dim3(256), 0, st, h->reward, h->done, h->tk.obs, net->win, net->kstep, E, R,
                            net->ro_rew + o, net->ro_done + o, net->ro_mask + o);
     }
-    net->act_counter += (uint64_t)T;
+    if (!net->greedy) net->act_counter += (uint64_t)T;      // a greedy rollout draws nothing
     // bootstrap: V of the window after the last step, 0 behind a finished episode; then the worker's GAE (worker.py:241-294)
     hipLaunchKernelGGL(gated_record_kernel, dim3(eb), dim3(256), 0, st, h->tk.obs, net->win, net->kstep, E, R, net->boot_states, net->boot_win,
                        (float *)nullptr);
@@ -816,6 +880,72 @@ int grl_gnet_rollout(grl_gnet *net, int32_t T) {
         return gfail(net, rc, h->err);
     GNET_HIP(net, hipGetLastError());
     return GRL_OK;
+}
+
+int grl_gnet_set_greedy(grl_gnet *net, int32_t on) {
+    if (!net) return GRL_E_INVALID;
+    net->greedy = on ? 1 : 0;
+    return GRL_OK;
+}
+
+int grl_gnet_eval(grl_gnet *net, int32_t max_steps, int32_t trace_steps) {
+    if (!net) return GRL_E_INVALID;
+    if (max_steps < 1 || trace_steps < 0) return gfail(net, GRL_E_INVALID, "grl_gnet_eval: max_steps >= 1, trace_steps >= 0");
+    grl_handle *h = net->h;
+    hipSetDevice(h->cfg.device_id);
+    if (!h->tk.table) return gfail(net, GRL_E_STATE, "Ticker handle has no price table yet: call grl_ticker_set_table first");
+    if (h->cfg.max_episode_steps < 1)
+        return gfail(net, GRL_E_STATE, "grl_gnet_eval: the handle has no max_episode_steps, an episode could run past its 1024-row price window");
+    if (trace_steps > max_steps) trace_steps = max_steps;
+    int rc = ensure_eval_trace(net, trace_steps);
+    if (rc) return rc;
+    hipStream_t st = h->stream;
+    const int E = h->E;
+    GEvalArgs v{};
+    v.a = gargs(net, E, h->tk.obs, net->win);
+    v.win = net->win; v.max_steps = max_steps; v.trace_steps = trace_steps;
+    v.total = net->ev_total; v.length = net->ev_len; v.finished = net->ev_fin;
+    v.tr_states = net->ev_states; v.tr_probs = net->ev_probs; v.tr_mu = net->ev_mu; v.tr_choices = net->ev_choices;
+    v.tr_act = net->ev_actions; v.tr_rew = net->ev_rew; v.tr_done = net->ev_done;
+    hipLaunchKernelGGL(gated_eval_kernel, dim3((E + 63) / 64), dim3(256), GATED_LDS, st, v, ticker_params(h));
+    GNET_HIP(net, hipGetLastError());
+    net->ev_trace = trace_steps;
+    net->ev_played = -1;
+    net->win_init = 0;      // the windows were the evaluation's: the next rollout starts every env's anew
+    // the handle's full reset, as grl_reset(h, NULL, 0) enqueues it
+    if ((rc = launch_iota(h, h->done_list, E))) return gfail(net, rc, h->err);
+    net->ev_reset_count = E;
+    GNET_HIP(net, hipMemcpyAsync(h->done_count, &net->ev_reset_count, 4, hipMemcpyHostToDevice, st));
+    if ((rc = ticker_launch_reset(h, h->done_list, h->done_count, E))) return gfail(net, rc, h->err);
+    return GRL_OK;
+}
+
+int grl_gnet_read_eval(grl_gnet *net, const char *which, void *host, size_t bytes) {
+    if (!net || !which || !host) return gfail(net, GRL_E_INVALID, "grl_gnet_read_eval: bad argument");
+    if (net->ev_played == -2) return gfail(net, GRL_E_STATE, "grl_gnet_read_eval: no evaluation yet");
+    hipSetDevice(net->h->cfg.device_id);
+    GNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    const size_t E = net->h->E;
+    if (net->ev_played < 0) {      // steps the call played = the longest episode
+        std::vector<int32_t> len(E);
+        GNET_HIP(net, hipMemcpy(len.data(), net->ev_len, E * 4, hipMemcpyDeviceToHost));
+        int32_t mx = 0;
+        for (int32_t l : len) mx = l > mx ? l : mx;
+        net->ev_played = mx;
+    }
+    const size_t SE = (size_t)(net->ev_trace < net->ev_played ? net->ev_trace : net->ev_played) * E;
+    struct { const char *name; const void *p; size_t n; } tab[] = {
+        {"total_reward", net->ev_total, E * 8}, {"length", net->ev_len, E * 4}, {"finished", net->ev_fin, E},
+        {"states", net->ev_states, SE * GS0 * 4}, {"probs", net->ev_probs, SE * 24}, {"mu", net->ev_mu, SE * 24},
+        {"choices", net->ev_choices, SE * 8}, {"actions", net->ev_actions, SE * 16}, {"rewards", net->ev_rew, SE * 4},
+        {"dones", net->ev_done, SE * 4}};
+    for (auto &e : tab)
+        if (!strcmp(which, e.name)) {
+            if (bytes != e.n) return gfail(net, GRL_E_SIZE, std::string("grl_gnet_read_eval: wrong size for ") + which);
+            if (bytes) GNET_HIP(net, hipMemcpy(host, e.p, bytes, hipMemcpyDeviceToHost));
+            return GRL_OK;
+        }
+    return gfail(net, GRL_E_INVALID, std::string("grl_gnet_read_eval: unknown buffer ") + which);
 }
 
 int grl_gnet_train_rollout(grl_gnet *net, float lr0, float *stats_host) {
@@ -837,7 +967,7 @@ int grl_gnet_read_rollout(grl_gnet *net, const char *which, void *host, size_t b
         {"states", net->ro_states, TE * GS0}, {"windows", net->ro_win, TE * R * GD}, {"choices", net->ro_choices, TE * 2},
         {"raw", net->ro_raw, TE * 2}, {"probs", net->ro_probs, TE * 6}, {"mu", net->ro_mu, TE * 6}, {"sigma", net->ro_sigma, TE * 6},
         {"values", net->ro_val, TE}, {"rewards", net->ro_rew, TE}, {"dones", net->ro_done, TE}, {"weights", net->ro_wt, TE},
-        {"adv", net->ro_adv, TE}, {"targets", net->ro_tgt, TE}, {"boot", net->ro_boot, (size_t)net->h->E}};
+        {"adv", net->ro_adv, TE}, {"targets", net->ro_tgt, TE}, {"actions", net->ro_act, TE * 4}, {"boot", net->ro_boot, (size_t)net->h->E}};
     for (auto &e : tab)
         if (!strcmp(which, e.name)) { src = e.p; cnt = e.n; }
     if (!src) return gfail(net, GRL_E_INVALID, std::string("grl_gnet_read_rollout: unknown buffer ") + which);

@@ -36,6 +36,13 @@ GNET_SIGNATURES = {
     "grl_gnet_train_rollout": (C.c_int, [_P, _F, _P]),
     "grl_gnet_read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
 }
+# include/goldsrl_gatedeval.h: a dict of its own, as the header is a file of its own (GNET_SIGNATURES is pinned to goldsrl_gatednet.h's
+# 17 training functions by tests/test_oracle_gated.py; these three are pinned by tests/test_gated_eval_header.py)
+GNET_EVAL_SIGNATURES = {
+    "grl_gnet_set_greedy": (C.c_int, [_P, _I]),
+    "grl_gnet_eval": (C.c_int, [_P, _I, _I]),
+    "grl_gnet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+}
 
 
 def gated_param_shapes(static_size=STATIC_SIZE, temporal_size=TEMPORAL_SIZE, H=32, S=128):
@@ -72,7 +79,7 @@ class GatedNet(object):
     """The gated trader on a Ticker Engine: predict / train on host samples, device-resident rollout + update."""
 
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=GNET_SIGNATURES)
+        self.lib = _ffi.load_library(extra_signatures=dict(GNET_SIGNATURES, **GNET_EVAL_SIGNATURES))
         self.eng = engine
         cfg = GrlGnetConfig()
         self.lib.grl_gnet_config_default(C.byref(cfg))
@@ -188,7 +195,34 @@ class GatedNet(object):
         T, E, R = self.T, self.eng.E, self.R
         shapes = {"states": (T, E, STATIC_SIZE), "windows": (T, E, R, TEMPORAL_SIZE), "choices": (T, E, N_ASSETS), "raw": (T, E, N_ASSETS),
                   "probs": (T, E, N_ASSETS, N_CHOICES), "mu": (T, E, N_ASSETS, N_CHOICES), "sigma": (T, E, N_ASSETS, N_CHOICES),
-                  "values": (T, E), "rewards": (T, E), "dones": (T, E), "weights": (T, E), "adv": (T, E), "targets": (T, E), "boot": (E,)}
+                  "values": (T, E), "rewards": (T, E), "dones": (T, E), "weights": (T, E), "adv": (T, E), "targets": (T, E),
+                  "actions": (T, E, 2 * N_ASSETS), "boot": (E,)}
         a = np.empty(shapes[which], np.int32 if which == "choices" else np.float32)
         self._check(self.lib.grl_gnet_read_rollout(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
         return a
+
+    def set_greedy(self, on):
+        """on: rollout draws nothing -- per asset the choice is the first argmax of the float32 probs, raw = mu[choice]; the action
+        counter stands still."""
+        self._check(self.lib.grl_gnet_set_greedy(self.n, 1 if on else 0))
+
+    EVAL_TRACE = ("states", "probs", "mu", "choices", "actions", "rewards", "dones")
+
+    def eval(self, max_steps, trace_steps=0, trace_fields=EVAL_TRACE):
+        """Greedy episodes of every env from the engine's current state (reset it first), one kernel launch; the engine is reset
+        afterwards.  Returns total_reward (E) float64, length (E) int32, finished (E) uint8 and, with trace_steps > 0, states (S,E,7),
+        probs, mu (S,E,2,3), choices (S,E,2) int32, actions (S,E,4), rewards, dones (S,E) of the first S = min(trace_steps, steps
+        played) steps, each defined up to its env's own end (trace_fields: the ones to read back)."""
+        self._check(self.lib.grl_gnet_eval(self.n, int(max_steps), int(trace_steps)))
+        E = self.eng.E
+        out = {"total_reward": np.empty(E, np.float64), "length": np.empty(E, np.int32), "finished": np.empty(E, np.uint8)}
+        for k in ("total_reward", "length", "finished"):
+            self._check(self.lib.grl_gnet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
+        if trace_steps > 0:
+            S = min(int(trace_steps), int(max_steps), int(out["length"].max()))
+            tails = {"states": (STATIC_SIZE,), "probs": (N_ASSETS, N_CHOICES), "mu": (N_ASSETS, N_CHOICES), "choices": (N_ASSETS,),
+                     "actions": (2 * N_ASSETS,), "rewards": (), "dones": ()}
+            for k in trace_fields:
+                out[k] = np.empty((S, E) + tails[k], np.int32 if k == "choices" else np.float32)
+                self._check(self.lib.grl_gnet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
+        return out

@@ -6,7 +6,16 @@ monitor owns an eval engine of `n_envs` envs whose streams are keyed by the glob
 and envs 1.. are further seeded episodes of the same registration; `eval_once` returns env 0's `(total_reward, episode_length,
 rewards)` as the reference does and keeps every env's totals for the caller.  The action is the worker's own transform of mu:
 the stable sigmoid for Solow, tanh for TradeAR1 (the reference's monitor applies its sigmoid to every env kind).
-What has no counterpart: the gym `Monitor` video wrapper, the TF session and summaries (the caller writes the scalars), the Saver."""
+What has no counterpart: the gym `Monitor` video wrapper, the TF session and summaries (the caller writes the scalars), the Saver.
+
+GatedPolicyMonitor is the same monitor for the Ticker gated trader (grl_gnet_eval, include/goldsrl_gatedeval.h).  The reference has
+nothing to compare it with: no PolicyMonitor is written for TickerGatedTraderWorker, its get_action_from_policy ignores `stochastic`
+(worker.py:466-476), so the net cannot act without drawing, and there is no eval registration of the Ticker env, no held-out price
+table and no episode that repeats from one evaluation to the next.  All three are stated here instead.  The greedy rule, per asset:
+choice = the first index of the largest of the three float32 probabilities (np.argmax, as GridSolowWorker.get_greedy_action picks,
+worker.py:370-372), raw = mu[choice], fraction = the worker's float64 sigmoid of raw rounded to float32 (worker.py:229-230).  The
+eval registration: seed 1692 and a reseed at every reset, as the Solow eval registration has it, so env e trades the same 1 024-row
+price window at every evaluation; the table may be another one than the training table."""
 import json
 import time
 
@@ -28,31 +37,24 @@ def make_eval_engine(env, n_envs, device_id=0, max_episode_steps=1024):
     raise ValueError("no device evaluation for env %r (one of %s)" % (env, ", ".join(ENVS)))
 
 
-class PolicyMonitor(object):
-    """policy_monitor.py:11-118.  env: the eval registration's id.  global_policy_net, state_processor, summary_writer, saver are
-    kept as the reference keeps them (the device does the processing; summary_writer, when given, gets the eval/* scalars through
-    add_scalar).  net: an evaluation net to use instead of building one (its `eng` is the eval engine)."""
+def make_ticker_eval_engine(table, n_envs, device_id=0, max_episode_steps=1023):
+    """The engine of the Ticker eval registration with n_envs envs on `table` (the sampler's (rows,4) data matrix, or a sampler):
+    seed 1692, reseeded at every reset, so env e's price window is the same at every evaluation.  1 023 steps is the longest episode
+    a 1 024-row window holds."""
+    from ... import _ffi
+    eng = _ffi.Engine(_ffi.ENV_TICKER, n_envs, device_id=device_id, seed=1692, flags=_ffi.F_RESEED_EACH_RESET,
+                      max_episode_steps=max_episode_steps)
+    eng.ticker_set_table(getattr(table, "data_matrix", table))
+    return eng
 
-    def __init__(self, env, global_policy_net=None, state_processor=None, summary_writer=None, saver=None, num_actions=None,
-                 input_size=None, temporal_size=None, n_envs=1, max_seq_length=5, scale=1.0, device_id=0, max_episode_steps=1024,
-                 net=None):
-        self.env = env
-        self.global_policy_net = global_policy_net
-        self.state_processor = state_processor
+
+class _DeviceMonitor(object):
+    """What the device monitors share: the evaluation net on its eval engine, the log, the scalars, the loop."""
+
+    def _adopt(self, net, own, summary_writer, max_episode_steps):
         self.summary_writer = summary_writer
-        self.saver = saver
         self.max_episode_steps = int(max_episode_steps)
-        self._own = net is None
-        if net is None:
-            from ... import _ffi_gauss
-            if n_envs < 1:
-                raise ValueError("n_envs must be at least 1")
-            eng = make_eval_engine(env, n_envs, device_id, self.max_episode_steps)
-            net = _ffi_gauss.GaussNet(eng, rnn_length=max_seq_length, scale=scale, max_samples=1)       # the "policy_eval" copy
-            want = (net.A, net.S0, net.D)
-            for name, got, exp in zip(("num_actions", "input_size", "temporal_size"), (num_actions, input_size, temporal_size), want):
-                if got is not None and got != exp:
-                    raise ValueError("%s = %r, the device net of %s has %r" % (name, got, env, exp))
+        self._own = own
         self.net = net
         self.n_envs = int(net.eng.E)
         self.total_rewards, self.episode_lengths = None, None       # every env's, of the last evaluation
@@ -109,3 +111,48 @@ class PolicyMonitor(object):
             self.net.close()
             eng.close()
         self.net = None
+
+
+class PolicyMonitor(_DeviceMonitor):
+    """policy_monitor.py:11-118.  env: the eval registration's id.  global_policy_net, state_processor, summary_writer, saver are
+    kept as the reference keeps them (the device does the processing; summary_writer, when given, gets the eval/* scalars through
+    add_scalar).  net: an evaluation net to use instead of building one (its `eng` is the eval engine)."""
+
+    def __init__(self, env, global_policy_net=None, state_processor=None, summary_writer=None, saver=None, num_actions=None,
+                 input_size=None, temporal_size=None, n_envs=1, max_seq_length=5, scale=1.0, device_id=0, max_episode_steps=1024,
+                 net=None):
+        self.env = env
+        self.global_policy_net = global_policy_net
+        self.state_processor = state_processor
+        self.saver = saver
+        own = net is None
+        if net is None:
+            from ... import _ffi_gauss
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            eng = make_eval_engine(env, n_envs, device_id, int(max_episode_steps))
+            net = _ffi_gauss.GaussNet(eng, rnn_length=max_seq_length, scale=scale, max_samples=1)       # the "policy_eval" copy
+            want = (net.A, net.S0, net.D)
+            for name, got, exp in zip(("num_actions", "input_size", "temporal_size"), (num_actions, input_size, temporal_size), want):
+                if got is not None and got != exp:
+                    raise ValueError("%s = %r, the device net of %s has %r" % (name, got, env, exp))
+        self._adopt(net, own, summary_writer, max_episode_steps)
+
+
+class GatedPolicyMonitor(_DeviceMonitor):
+    """The PolicyMonitor of the Ticker gated trader.  table: the eval price table (the sampler's data matrix or a sampler), the
+    training one or a held-out one.  summary_writer, when given, gets the eval/* scalars through add_scalar.  net: an evaluation
+    net to use instead of building one (its `eng` is the eval engine)."""
+
+    def __init__(self, table=None, summary_writer=None, n_envs=1, max_seq_length=5, scale=1.0, device_id=0, max_episode_steps=1023,
+                 net=None):
+        own = net is None
+        if net is None:
+            from ... import _ffi_gated
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            if table is None:
+                raise ValueError("the Ticker eval engine needs a price table")
+            eng = make_ticker_eval_engine(table, n_envs, device_id, int(max_episode_steps))
+            net = _ffi_gated.GatedNet(eng, rnn_length=max_seq_length, scale=scale, max_samples=1)
+        self._adopt(net, own, summary_writer, max_episode_steps)

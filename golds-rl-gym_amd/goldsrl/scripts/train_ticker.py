@@ -1,7 +1,10 @@
 """`python -m goldsrl.scripts.train_ticker` -- the Ticker gated trader (TickerGatedTraderWorker, fed_gym/agents/a3c/worker.py:445-494)
 trained on the device: E envs x T steps per update, each env one A3C worker (include/goldsrl_gatednet.h).  The price table comes
 from a CSV (columns Open, Close, Volume) or a --table .npz (Open / Close / Volume or tbl_open / tbl_close / tbl_volume arrays)
-through the sampler of goldsrl.envs.data; scalars go to a TF-events file, the checkpoint to <out>/checkpoint.npz."""
+through the sampler of goldsrl.envs.data; scalars go to a TF-events file, the checkpoint to <out>/checkpoint.npz.  With --eval-envs M
+the GatedPolicyMonitor (goldsrl/agents/a3c/policy_monitor.py) plays, every --eval-every updates and after the last one, M greedy
+episodes in one kernel launch on --eval-csv / --eval-table (a held-out price table; default: the training table): per asset the
+most probable choice with mu of that choice.  Totals go to <out>/Ticker.json and the eval/* scalars."""
 import argparse
 import logging
 import os
@@ -11,6 +14,7 @@ import time
 import numpy as np
 
 from goldsrl import _ffi, _ffi_gated
+from goldsrl.agents.a3c.policy_monitor import GatedPolicyMonitor
 from goldsrl.envs.data.sampler import OpenCloseSampler
 from goldsrl.utils_tfevents import EventFileWriter
 
@@ -33,13 +37,20 @@ def get_arg_parser():
     p.add_argument("--out", default="logs/ticker")
     p.add_argument("--resume", help="checkpoint .npz to continue from")
     p.add_argument("--checkpoint-every", type=int, default=50)
+    p.add_argument("--eval-envs", "--eval_envs", dest="eval_envs", type=int, default=0,
+                   help="greedy eval episodes per evaluation (0: no evaluation)")
+    p.add_argument("--eval-every", "--eval_every", dest="eval_every", type=int, default=10, help="evaluate every N updates")
+    ev = p.add_mutually_exclusive_group()
+    ev.add_argument("--eval-csv", "--eval_csv", dest="eval_csv", help="held-out price table CSV for the evaluation")
+    ev.add_argument("--eval-table", "--eval_table", dest="eval_table", help="held-out price table .npz for the evaluation")
     return p
 
 
-def load_table(args):
-    if args.csv:
-        return OpenCloseSampler(path=args.csv)
-    with np.load(args.table) as z:
+def load_table(args, csv=None, table=None):
+    csv, table = (args.csv, args.table) if csv is None and table is None else (csv, table)
+    if csv:
+        return OpenCloseSampler(path=csv)
+    with np.load(table) as z:
         keys = ("Open", "Close", "Volume") if "Open" in z.files else ("tbl_open", "tbl_close", "tbl_volume")
         return OpenCloseSampler(table={"Open": z[keys[0]], "Close": z[keys[1]], "Volume": z[keys[2]]})
 
@@ -59,6 +70,14 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     writer = EventFileWriter(args.out)
     ckpt = os.path.join(args.out, "checkpoint.npz")
+    log_file = os.path.join(args.out, "Ticker.json")
+    monitor = None
+    if args.eval_envs > 0:
+        if args.eval_every < 1:
+            raise SystemExit("--eval-every must be at least 1")
+        held_out = load_table(args, args.eval_csv, args.eval_table) if args.eval_csv or args.eval_table else sampler
+        monitor = GatedPolicyMonitor(held_out, summary_writer=writer, n_envs=args.eval_envs, max_seq_length=args.rnn_length,
+                                     scale=args.scale, device_id=args.device)
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.steps)
@@ -72,12 +91,20 @@ def main(argv=None):
             writer.add_scalar("episode/total_reward", float(np.mean(eps["total_reward"])), step)
             writer.add_scalar("episode/length", float(np.mean(eps["length"])), step)
         writer.add_scalar("perf/env_steps_per_s", args.envs * args.steps / dt, step)
+        if monitor is not None and ((u + 1) % args.eval_every == 0 or u + 1 == args.updates):
+            total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
+            monitor.write_scalars(step)
+            monitor.write_log(log_file)
+            logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
+                         episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
         writer.flush()
         logging.info("update %d  global step %d  policy loss %.4g  value loss %.4g  entropy %.4g  %.0f env-steps/s", u + 1, step,
                      stats["policy_loss"], stats["value_loss"], stats["entropy_mean"], args.envs * args.steps / dt)
         if (u + 1) % args.checkpoint_every == 0 or u + 1 == args.updates:
             net.save_checkpoint(ckpt)
     writer.close()
+    if monitor is not None:
+        monitor.close()
     net.close()
     eng.close()
 

@@ -27,7 +27,8 @@
  * Update: policy and value gradients (sums over the weighted samples times grad_mult), each clipped to clip_norm on its own, each
  * to its own RMSProp (ms <- rho ms + (1-rho) g^2, w <- w - lr g / sqrt(ms + eps), ms starts at 1): params <- (params - step_p) - step_v.
  * lr = lr0 * decay_rate^(global_step / decay_steps) with the global step before the update; the global step advances by 2.
- * Conventions as in goldsrl.h.
+ * Conventions as in goldsrl.h.  Greedy acting (grl_gnet_set_greedy) and the one-launch greedy evaluation (grl_gnet_eval) are declared
+ * in goldsrl_gatedeval.h, which this header includes.
  */
 #ifndef GOLDSRL_GATEDNET_H
 #define GOLDSRL_GATEDNET_H
@@ -91,10 +92,14 @@ int grl_gnet_rollout(grl_gnet *net, int32_t T);
 /* the update on the last rollout: grad_mult = 1/E (each env is one A3C worker; the gradient is averaged over them) */
 int grl_gnet_train_rollout(grl_gnet *net, float lr0, float *stats_host);
 /* "states" (T,E,7) "windows" (T,E,R,4) "choices" (T,E,2) int32 "raw" (T,E,2) "probs" "mu" "sigma" (T,E,2,3) "values" "rewards"
- * "dones" "weights" "adv" "targets" (T,E) "boot" (E) (0 behind a finished episode) */
+ * "dones" "weights" "adv" "targets" (T,E) "actions" (T,E,4) (what the env was stepped with: both choices, both fractions)
+ * "boot" (E) (0 behind a finished episode) */
 int grl_gnet_read_rollout(grl_gnet *net, const char *which, void *host, size_t bytes);
 
 #ifdef __cplusplus
 }
 #endif
+
+#include "goldsrl_gatedeval.h" /* greedy acting and the one-launch greedy evaluation of the same net */
+
 #endif /* GOLDSRL_GATEDNET_H */
