@@ -97,6 +97,7 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 #include "net_flat_fast.inc"
 #include "net_flat_bwd_fast.inc"
 #include "net_flat_rollout.inc"
+#include "net_flat_eval.inc"
 
 // PT: the weight matrices the data gradients multiply with, transposed (block b = matrix b; the GRU kernels: their recurrent rows)
 __global__ void flat_transpose_kernel(const float *__restrict__ P, float *__restrict__ PT, FOff o, int D, int A) {
@@ -165,23 +166,16 @@ __global__ void flat_adam_kernel(float *__restrict__ p, const float *__restrict_
 
 // a = mu + sigma*N(0,1) (paac.py:36), SolowRunner.transform_actions_for_env = sigmoid (emulator_runner.py:77-79)
 __global__ void flat_sample_kernel(const float *__restrict__ mu, const float *__restrict__ sigma, int n, int A, uint64_t seed,
-                                   uint32_t env_off, const uint32_t *__restrict__ counter_base, uint32_t step, int env_kind,
+                                   uint32_t env_off, const uint32_t *__restrict__ counter_base, uint32_t step, int env_kind, int greedy,
                                    float *__restrict__ raw, float *__restrict__ envact) {
     // the draw counter is read from device memory so that a captured rollout graph can be replayed (base is set per rollout)
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * A) return;
     const uint32_t counter = *counter_base + step;
     int e = i / A, k = i - e * A;
-    double e0, e1;
-    normal_pair(rng_block(seed, (uint32_t)e + env_off, counter, RS_FLAT_ACTION, k >> 1), e0, e1);
-    float r = (float)((double)mu[i] + (double)sigma[i] * ((k & 1) ? e1 : e0));
+    const float r = flat_raw_action(greedy, mu[i], sigma[i], seed, (uint32_t)e + env_off, counter, k);
     raw[i] = r;
-    if (env_kind == GRL_ENV_SOLOW) {
-        float z = expf(-fabsf(r));
-        envact[i] = r >= 0.f ? 1.0f / (1.0f + z) : z / (1.0f + z);
-    } else {
-        envact[i] = tanhf(r);
-    }
+    envact[i] = flat_env_action(env_kind, r);
 }
 
 __global__ void flat_mask_kernel(const uint8_t *__restrict__ done, int n, float *__restrict__ mask) {
@@ -212,6 +206,17 @@ struct grl_fnet {
     hipGraphExec_t ro_graph;       // the T-step rollout captured once and replayed (launch-bound at 4 096 envs)
     int ro_graph_T;
     bool ro_graph_ep;              // the captured rollout contains the R6 accounting launches
+    int ro_graph_greedy;           // the greedy flag the captured sample launches carry
+    int greedy;                    // grl_fnet_set_greedy: the rollout acts with raw = mu, draws nothing, the action counter stands still
+    // grl_fnet_eval: per-env results and the trace of the first ev_trace steps (buffers for ev_trace_cap steps; they only grow)
+    double *ev_total;
+    int32_t *ev_len, *ev_nhist;
+    uint8_t *ev_fin;
+    float *ev_states, *ev_mu, *ev_sigma, *ev_raw, *ev_act, *ev_val, *ev_rew, *ev_done;
+    int ev_trace, ev_trace_cap, ev_played;      // ev_played: -1 until grl_fnet_read_eval has looked, -2 before any evaluation
+    int32_t ev_reset_count;
+    char ev_attr_set[3];           // flat_eval_kernel<16 / 32 / 64> has its dynamic-LDS limit raised on this net's device
+    std::vector<void *> ev_allocs;
     int fast_forward;              // 1: synthesized-window forwards use net_flat_fast.inc (GRL_FLAT_FORWARD=layers: the layer-by-layer form)
     int ro_persistent;             // 1: the T-step actor loop is ONE persistent kernel (net_flat_rollout.inc); 0: the hipGraph of launches
     char ro_attr_set[2][3];        // the rollout kernel instance (KEEP x G = 16, 32, 64) has its dynamic-LDS limit raised on this net's device
@@ -399,7 +404,7 @@ static int enqueue_rollout(grl_fnet *net, int T) {
         rc = launch_forward(net, E, obs, nullptr, net->mu, net->sigma, net->ro_val + (size_t)t * E, false, nh);
         if (rc) return rc;
         hipLaunchKernelGGL(flat_sample_kernel, dim3((E * A + 255) / 256), dim3(256), 0, st, net->mu, net->sigma, E, A, h->cfg.seed,
-                           (uint32_t)h->cfg.env_id_offset, (const uint32_t *)net->d_counter, (uint32_t)t, h->cfg.env_kind,
+                           (uint32_t)h->cfg.env_id_offset, (const uint32_t *)net->d_counter, (uint32_t)t, h->cfg.env_kind, net->greedy,
                            net->ro_act + (size_t)t * E * A, net->ro_envact);
         rc = solow ? solow_launch_step(h, net->ro_envact) : trade_launch_step(h, net->ro_envact);
         if (rc) return ffail(net, rc, h->err);
@@ -488,7 +493,7 @@ static int launch_persistent_rollout(grl_fnet *net, int T) {
     R.ep_total = h->ep_total; R.ep_len = h->ep_len; R.ep_steps = h->ep_steps; R.ep_rec = h->ep_rec; R.ep_count = h->ep_count;
     R.ep_cap = h->ep_capacity;
     hipStream_t st = h->stream;
-    R.ts = net->d_ts; R.ts_n = net->d_ts_n;
+    R.ts = net->d_ts; R.ts_n = net->d_ts_n; R.greedy = net->greedy;
     if (net->d_ts_n) FNET_HIP(net, hipMemsetAsync(net->d_ts_n, 0, sizeof(int), st));
     FNET_HIP(net, hipMemsetAsync(h->done_count, 0, sizeof(int32_t), st));      // the last step's done list is built inside the kernel
     FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ro_args), &R, sizeof(RolloutArgs), (size_t)net->arg_slot * sizeof(RolloutArgs),
@@ -500,6 +505,77 @@ static int launch_persistent_rollout(grl_fnet *net, int T) {
     hipLaunchKernelGGL(kern_fn, grid, dim3(FNT), lds_bytes, st, net->arg_slot);
     FNET_HIP(net, hipGetLastError());
     net->ws_resident = keep ? 1 : 0;
+    return GRL_OK;
+}
+
+// the result and trace buffers of grl_fnet_eval for `steps` traced steps
+static int ensure_eval_buffers(grl_fnet *net, int steps) {
+    const size_t E = net->h->E;
+    int rc = GRL_OK;
+    if (!net->ev_total) {
+        if ((rc = falloc(net, &net->ev_total, E))) return rc;
+        if ((rc = falloc(net, &net->ev_len, E))) return rc;
+        if ((rc = falloc(net, &net->ev_fin, E))) return rc;
+    }
+    if (steps <= net->ev_trace_cap) return GRL_OK;
+    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    for (void *p : net->ev_allocs) hipFree(p);
+    net->ev_allocs.clear();
+    net->ev_trace_cap = -1;
+    const size_t SE = (size_t)steps * E, S0 = net->cfg.static_size, A = net->cfg.num_actions;
+    hipStream_t st = net->h->stream;
+    auto Al = [&](auto **p, size_t cnt) {
+        if (rc != GRL_OK) return;
+        cnt = cnt ? cnt : 1;
+        hipError_t e = hipMalloc((void **)p, cnt * sizeof(**p));
+        if (e == hipSuccess) { net->ev_allocs.push_back(*p); e = hipMemsetAsync(*p, 0, cnt * sizeof(**p), st); }
+        if (e != hipSuccess) rc = ffail(net, GRL_E_HIP, std::string("eval trace buffers: ") + hipGetErrorString(e));
+    };
+    Al(&net->ev_states, SE * S0); Al(&net->ev_nhist, SE); Al(&net->ev_mu, SE * A); Al(&net->ev_sigma, SE * A); Al(&net->ev_raw, SE * A);
+    Al(&net->ev_act, SE * A); Al(&net->ev_val, SE); Al(&net->ev_rew, SE); Al(&net->ev_done, SE);
+    if (rc == GRL_OK) net->ev_trace_cap = steps;
+    return rc;
+}
+
+// whole episodes of every env as ONE kernel (net_flat_eval.inc)
+static int launch_eval(grl_fnet *net, int max_steps, int trace_steps, int greedy) {
+    grl_handle *h = net->h;
+    if (net->arg_slot < 0) return ffail(net, GRL_E_STATE, "grl_fnet_eval: no constant-memory argument slot is free for this net");
+    const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
+    RolloutArgs R{};
+    R.f = base_args(net, h->E, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+    R.f.ts = nullptr; R.f.ts_n = nullptr;
+    R.steps = 0; R.env_kind = h->cfg.env_kind; R.slot = net->arg_slot;
+    int live_off = 0;
+    const size_t lds_bytes = (size_t)eval_lds_floats(net->cfg.static_size, solow ? 0 : h->cfg.n_assets, &R, &live_off) * sizeof(float);
+    if (lds_bytes > 160 * 1024) return ffail(net, GRL_E_SIZE, "grl_fnet_eval: the evaluation's LDS rows do not fit a CU");
+    int G = net->ro_group;      // the rule of launch_persistent_rollout
+    if (!G) G = h->E <= 16 * 256 ? 16 : (h->E <= 32 * 256 ? 32 : 64);
+    R.gs = G;
+    typedef void (*EvKernel)(int, int);
+    static const EvKernel kernels[3] = {flat_eval_kernel<16>, flat_eval_kernel<32>, flat_eval_kernel<64>};
+    const int gi = G == 16 ? 0 : (G == 32 ? 1 : 2);
+    if (!net->ev_attr_set[gi]) {
+        FNET_HIP(net, hipFuncSetAttribute((const void *)kernels[gi], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        net->ev_attr_set[gi] = 1;
+    }
+    if (solow) { R.so = solow_params(h); R.obs0 = h->so.obs; }
+    else { R.tr = trade_params(h); R.obs0 = h->tr.obs; }
+    R.counter_base = net->d_counter; R.seed = h->cfg.seed; R.env_off = (uint32_t)h->cfg.env_id_offset;
+    R.greedy = greedy ? 1 : 0;
+    R.ev.max_steps = max_steps; R.ev.trace_steps = trace_steps;
+    R.ev.total = net->ev_total; R.ev.length = net->ev_len; R.ev.finished = net->ev_fin;
+    R.ev.states = net->ev_states; R.ev.nhist = net->ev_nhist; R.ev.mu = net->ev_mu; R.ev.sigma = net->ev_sigma; R.ev.raw = net->ev_raw;
+    R.ev.act = net->ev_act; R.ev.val = net->ev_val; R.ev.rew = net->ev_rew; R.ev.done = net->ev_done;
+    hipStream_t st = h->stream;
+    FNET_HIP(net, hipMemsetD32Async((hipDeviceptr_t)net->d_counter, (int)(uint32_t)net->act_counter, 1, st));
+    FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ro_args), &R, sizeof(RolloutArgs), (size_t)net->arg_slot * sizeof(RolloutArgs),
+                                         hipMemcpyHostToDevice, st));
+    FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &R.f, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
+                                         hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kernels[gi], dim3((h->E + G - 1) / G), dim3(FNT), lds_bytes, st, net->arg_slot, live_off);
+    FNET_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -544,7 +620,8 @@ int grl_fnet_create(grl_handle *h, const grl_fnet_config *cfg, grl_fnet **out) {
     Al(&n->mu, ms * A); Al(&n->sigma, ms * A); Al(&n->vs, ms);
     if (rc == GRL_OK) rc = falloc(n, &n->stats64, 4 + kSumsqBlocks);      // loss sums (2 used of 4), then the squares' partial sums
     if (rc == GRL_OK) rc = falloc(n, &n->d_counter, 4);
-    n->ro_graph = nullptr; n->ro_graph_T = 0; n->ro_graph_ep = false;
+    n->ro_graph = nullptr; n->ro_graph_T = 0; n->ro_graph_ep = false; n->ro_graph_greedy = 0; n->greedy = 0;
+    n->ev_total = nullptr; n->ev_trace = 0; n->ev_trace_cap = -1; n->ev_played = -2; memset(n->ev_attr_set, 0, sizeof(n->ev_attr_set));
     {   // GRL_FLAT_ROLLOUT=graph keeps the launch-per-stage rollout (captured into a hipGraph) for A/B and for the equality tests
         const char *e = getenv("GRL_FLAT_ROLLOUT");
         n->ro_persistent = (e && strcmp(e, "graph") == 0) ? 0 : 1;
@@ -594,6 +671,7 @@ int grl_fnet_destroy(grl_fnet *n) {
     if (n->ar_ev0) { hipEventDestroy(n->ar_ev0); hipEventDestroy(n->ar_ev1); }
     flat_slot_release(n->arg_slot);
     for (void *p : n->allocs) hipFree(p);
+    for (void *p : n->ev_allocs) hipFree(p);
     delete n;
     return GRL_OK;
 }
@@ -740,7 +818,7 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     hipStream_t st = h->stream;
     // draw counter of step t = act_counter + t, read by the sample kernel from device memory
     FNET_HIP(net, hipMemsetD32Async((hipDeviceptr_t)net->d_counter, (int)(uint32_t)net->act_counter, 1, st));
-    net->act_counter += (unsigned long)T;
+    if (!net->greedy) net->act_counter += (unsigned long)T;
     // one workgroup per 64 envs and one workgroup per CU (its LDS): beyond two rounds of workgroups (E > 32 768) the graph of
     // launches takes over.  Measured at the end of round 5, persistent / graph, ms per 20-step rollout: TradeAR1-16 32 768 envs
     // 3.86 / 4.40, 65 536: 7.64 / 7.84; Solow 32 768: 2.01 / 1.93, 65 536: 3.94 / 3.39 (GRL_FLAT_PERSIST_GROUPS moves the limit)
@@ -751,7 +829,7 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
         if (rc != GRL_E_SIZE) return rc;
         net->ro_persistent = 0;      // does not fit the LDS of a CU (very long rollouts): the graph path from here on
     }
-    if (net->ro_graph && net->ro_graph_T == T && net->ro_graph_ep == (h->ep_total != nullptr)) {
+    if (net->ro_graph && net->ro_graph_T == T && net->ro_graph_ep == (h->ep_total != nullptr) && net->ro_graph_greedy == net->greedy) {
         FNET_HIP(net, hipGraphLaunch(net->ro_graph, st));
     } else {
         if (net->ro_graph) { (void)hipGraphExecDestroy(net->ro_graph); net->ro_graph = nullptr; }
@@ -765,6 +843,7 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
             if (rc == GRL_OK && e == hipSuccess && graph && hipGraphInstantiate(&net->ro_graph, graph, nullptr, nullptr, 0) == hipSuccess) {
                 net->ro_graph_T = T;
                 net->ro_graph_ep = h->ep_total != nullptr;
+                net->ro_graph_greedy = net->greedy;
             } else {
                 net->ro_graph = nullptr;
                 (void)hipGetLastError();
@@ -780,6 +859,65 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     FNET_HIP(net, hipGetLastError());
     h->step_in_flight = true;
     return GRL_OK;
+}
+
+int grl_fnet_set_greedy(grl_fnet *net, int32_t on) {
+    if (!net) return GRL_E_INVALID;
+    net->greedy = on ? 1 : 0;
+    return GRL_OK;
+}
+
+int grl_fnet_eval(grl_fnet *net, int32_t max_steps, int32_t trace_steps, int32_t greedy) {
+    if (!net) return GRL_E_INVALID;
+    if (max_steps < 1 || trace_steps < 0) return ffail(net, GRL_E_INVALID, "grl_fnet_eval: max_steps >= 1, trace_steps >= 0");
+    grl_handle *h = net->h;
+    hipSetDevice(h->cfg.device_id);
+    int rc = check_env(net);
+    if (rc) return rc;
+    if (trace_steps > max_steps) trace_steps = max_steps;
+    if ((rc = ensure_eval_buffers(net, trace_steps))) return rc;
+    if ((rc = launch_eval(net, max_steps, trace_steps, greedy))) return rc;
+    if (!greedy) net->act_counter += (unsigned long)max_steps;      // later rollouts never reuse the evaluation's noise
+    net->ev_trace = trace_steps;
+    net->ev_played = -1;
+    // the handle's full reset (for Solow with the tape draw), as grl_reset(h, NULL, 0) enqueues it
+    const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
+    const int E = h->E;
+    hipStream_t st = h->stream;
+    if ((rc = launch_iota(h, h->done_list, E))) return ffail(net, rc, h->err);
+    net->ev_reset_count = E;
+    FNET_HIP(net, hipMemcpyAsync(h->done_count, &net->ev_reset_count, 4, hipMemcpyHostToDevice, st));
+    rc = solow ? solow_launch_reset(h, h->done_list, h->done_count, E, true) : trade_launch_reset(h, h->done_list, h->done_count, E);
+    if (rc) return ffail(net, rc, h->err);
+    return GRL_OK;
+}
+
+int grl_fnet_read_eval(grl_fnet *net, const char *which, void *host, size_t bytes) {
+    if (!net || !which || !host) return ffail(net, GRL_E_INVALID, "grl_fnet_read_eval: bad argument");
+    if (net->ev_played == -2) return ffail(net, GRL_E_STATE, "grl_fnet_read_eval: no evaluation yet");
+    hipSetDevice(net->h->cfg.device_id);
+    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    const size_t E = net->h->E, S0 = net->cfg.static_size, A = net->cfg.num_actions;
+    if (net->ev_played < 0) {      // steps the call played = the longest episode
+        std::vector<int32_t> len(E);
+        FNET_HIP(net, hipMemcpy(len.data(), net->ev_len, E * 4, hipMemcpyDeviceToHost));
+        int32_t mx = 0;
+        for (int32_t l : len) mx = l > mx ? l : mx;
+        net->ev_played = mx;
+    }
+    const size_t SE = (size_t)(net->ev_trace < net->ev_played ? net->ev_trace : net->ev_played) * E;
+    struct { const char *name; const void *p; size_t n; } tab[] = {
+        {"total_reward", net->ev_total, E * 8}, {"length", net->ev_len, E * 4}, {"finished", net->ev_fin, E},
+        {"states", net->ev_states, SE * S0 * 4}, {"nhist", net->ev_nhist, SE * 4}, {"mu", net->ev_mu, SE * A * 4},
+        {"sigma", net->ev_sigma, SE * A * 4}, {"raw", net->ev_raw, SE * A * 4}, {"actions", net->ev_act, SE * A * 4},
+        {"values", net->ev_val, SE * 4}, {"rewards", net->ev_rew, SE * 4}, {"dones", net->ev_done, SE * 4}};
+    for (auto &e : tab)
+        if (!strcmp(which, e.name)) {
+            if (bytes != e.n) return ffail(net, GRL_E_SIZE, std::string("grl_fnet_read_eval: wrong size for ") + which);
+            if (bytes) FNET_HIP(net, hipMemcpy(host, e.p, bytes, hipMemcpyDeviceToHost));
+            return GRL_OK;
+        }
+    return ffail(net, GRL_E_INVALID, std::string("grl_fnet_read_eval: unknown buffer ") + which);
 }
 
 // Debug / profiling: attach a timestamp buffer to the persistent rollout and read the stage clock of workgroup 0 after the next

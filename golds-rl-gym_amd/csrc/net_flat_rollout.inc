@@ -14,6 +14,16 @@
 // returns_column, episodes_account_env; the TradeAR1 step below repeats trade_step_kernel expression by expression), so the rollout
 // buffers are bit-identical to the graph path's (GRL_FLAT_ROLLOUT=graph keeps that path for A/B; tests compare the two).
 
+// what flat_eval_kernel (net_flat_eval.inc) leaves behind: per-env results and the optional trace of the first trace_steps steps
+struct EvalOut {
+    int max_steps, trace_steps;
+    double *total;              // (E)
+    int32_t *length;            // (E)
+    uint8_t *finished;          // (E)
+    float *states, *mu, *sigma, *raw, *act, *val, *rew, *done;      // (trace_steps, E, ..)
+    int32_t *nhist;
+};
+
 struct RolloutArgs {
     FlatArgs f;                 // P, o, n = E, S0, D, T = rnn, A, scale, bound; global outputs unused
     int slot;                   // the same block in g_flat_args (what the forward reads)
@@ -39,6 +49,8 @@ struct RolloutArgs {
     int row_rvm, row_int, off_f64;
     long long *ts;              // stage timestamps of workgroup 0 (grl_fnet_rollout_stage_times), or nullptr
     int *ts_n;
+    int greedy;                 // wave-uniform: raw = mu, nothing is drawn (grl_fnet_set_greedy, grl_fnet_eval(.., greedy))
+    EvalOut ev;                 // flat_eval_kernel only (net_flat_eval.inc)
 };
 
 __host__ __device__ inline int rollout_lds_floats(int S0, int steps, int n_assets, RolloutArgs *map) {
@@ -183,19 +195,24 @@ __device__ __noinline__ void ro_returns(int slot, float *lds, int lane, int env)
                    R.ro_y + env, R.ro_adv + env, (size_t)R.f.n);
 }
 
-// all waves: states[t] = shared_states, histories[t] = shared_histories (paac.py:132-133), and the window's true_length of the
-// lane's env (a3c/estimators.py:11-15) for the forward that follows
-__device__ __noinline__ int ro_record(int slot, float *lds, int t, int sbase) {
-    RO_ARGS(slot);
-    const RoLds L = ro_lds(R, lds);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int E = R.f.n, S0 = R.f.S0, D = R.f.D, Rn = R.f.T;
+// the window's true_length of the lane's env (a3c/estimators.py:11-15) for the forward that follows
+__device__ __forceinline__ int ro_window_len(const RolloutArgs &R, const RoLds &L, int lane) {
+    const int D = R.f.D, Rn = R.f.T;
     int nh = L.NH[lane];
     nh = nh < 1 ? 1 : nh;
     const int nrows = nh < Rn ? nh : Rn;      // min(max(n,1), rnn) copies of the current state (quirk Q11)
     float m = 0.f;
     for (int i = 0; i < D; ++i) m = fmaxf(m, fabsf(L.ST[i * LS + lane]));
-    const int len = m > 0.f ? nrows : 0;
+    return m > 0.f ? nrows : 0;
+}
+
+// all waves: states[t] = shared_states, histories[t] = shared_histories (paac.py:132-133), and the window's true_length
+__device__ __noinline__ int ro_record(int slot, float *lds, int t, int sbase) {
+    RO_ARGS(slot);
+    const RoLds L = ro_lds(R, lds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int E = R.f.n, S0 = R.f.S0, Rn = R.f.T;
+    const int len = ro_window_len(R, L, lane);
     if (t < R.steps) {
         for (int idx = tid; idx < R.gs * S0; idx += FNT) {
             const int sl = idx / S0, i = idx - sl * S0;
@@ -213,7 +230,23 @@ __device__ __noinline__ int ro_record(int slot, float *lds, int t, int sbase) {
     return len;
 }
 
-// all waves: values[t]; a = mu + sigma * N(0,1) (paac.py:36); transform_actions_for_env: sigmoid (Solow) / tanh (TradeAR1)
+// a = mu + sigma * N(0,1) (paac.py:36) in double, from the stream of (env, step counter, action pair); greedy: a = mu by selection
+__device__ __forceinline__ float flat_raw_action(int greedy, float mu, float sigma, uint64_t seed, uint32_t env_id, uint32_t counter, int k) {
+    if (greedy) return mu;
+    double e0, e1;
+    normal_pair(rng_block(seed, env_id, counter, RS_FLAT_ACTION, k >> 1), e0, e1);
+    return (float)((double)mu + (double)sigma * ((k & 1) ? e1 : e0));
+}
+// transform_actions_for_env: the stable sigmoid (SolowRunner, emulator_runner.py:77-79) / tanh (TradeAR1, a3c/worker.py:440-442)
+__device__ __forceinline__ float flat_env_action(int env_kind, float r) {
+    if (env_kind == GRL_ENV_SOLOW) {
+        const float z = expf(-fabsf(r));
+        return r >= 0.f ? 1.0f / (1.0f + z) : z / (1.0f + z);
+    }
+    return tanhf(r);
+}
+
+// all waves: values[t]; the raw action and the env's
 __device__ __noinline__ void ro_sample(int slot, float *lds, int t, int sbase, uint32_t counter) {
     RO_ARGS(slot);
     const RoLds L = ro_lds(R, lds);
@@ -226,43 +259,49 @@ __device__ __noinline__ void ro_sample(int slot, float *lds, int t, int sbase, u
         if (valid) R.ro_val[(size_t)t * E + env] = v;
     }
     for (int k = wave; k < A; k += FNW) {
-        double e0, e1;
-        normal_pair(rng_block(R.seed, (uint32_t)env + R.env_off, counter, RS_FLAT_ACTION, k >> 1), e0, e1);
-        const float r = (float)((double)L.MUL[k * LS + lane] + (double)L.SGL[k * LS + lane] * ((k & 1) ? e1 : e0));
+        const float r = flat_raw_action(R.greedy, L.MUL[k * LS + lane], L.SGL[k * LS + lane], R.seed, (uint32_t)env + R.env_off, counter, k);
         if (valid) R.ro_act[((size_t)t * E + env) * A + k] = r;
-        float ea;
-        if (R.env_kind == GRL_ENV_SOLOW) {
-            const float z = expf(-fabsf(r));
-            ea = r >= 0.f ? 1.0f / (1.0f + z) : z / (1.0f + z);
-        } else {
-            ea = tanhf(r);
-        }
-        L.ACT[k * LS + lane] = ea;
+        L.ACT[k * LS + lane] = flat_env_action(R.env_kind, r);
     }
 }
 
-// wave 0: R6, rewards / masks of step t from the step's result
+// wave 0: R6, rewards / masks of step t from the step's result.  EVAL (flat_eval_kernel): no rollout rows and no episode records --
+// the done flag of a lane that played this step (it stays set: the lane is masked from then on) and the step's trace
+template <bool EVAL>
 __device__ __forceinline__ void ro_bookkeeping(const RolloutArgs &R, float *lds, int t, int lane, int env, bool valid, bool solow, StepOut so) {
     const RoLds L = ro_lds(R, lds);
     const int E = R.f.n;
     const float reward = so.reward;
     const int dn = so.done;
     const bool done = dn != 0;
-    L.DN[lane] = dn;
-    if (R.ep_total) episodes_account_env(valid, env, reward, done, R.ep_total, R.ep_len, R.ep_steps, R.ep_rec, R.ep_count, R.ep_cap);
-    L.RW[t * LS + lane] = reward;
-    const float mk = 1.0f - (float)dn;      // episodes_over_masks (paac.py:140)
-    L.MK[t * LS + lane] = mk;
-    if (valid) { R.ro_rew[(size_t)t * E + env] = reward; R.ro_mask[(size_t)t * E + env] = mk; }
-    if (t == R.steps - 1) compact_done(done, env, solow ? R.so.done_list : R.tr.done_list, solow ? R.so.done_count : R.tr.done_count);
+    if constexpr (EVAL) {
+        if (valid) {
+            L.DN[lane] = dn;
+            if (t < R.ev.trace_steps) { R.ev.rew[(size_t)t * E + env] = reward; R.ev.done[(size_t)t * E + env] = (float)dn; }
+        }
+    } else {
+        L.DN[lane] = dn;
+        if (R.ep_total) episodes_account_env(valid, env, reward, done, R.ep_total, R.ep_len, R.ep_steps, R.ep_rec, R.ep_count, R.ep_cap);
+        L.RW[t * LS + lane] = reward;
+        const float mk = 1.0f - (float)dn;      // episodes_over_masks (paac.py:140)
+        L.MK[t * LS + lane] = mk;
+        if (valid) { R.ro_rew[(size_t)t * E + env] = reward; R.ro_mask[(size_t)t * E + env] = mk; }
+        if (t == R.steps - 1) compact_done(done, env, solow ? R.so.done_list : R.tr.done_list, solow ? R.so.done_count : R.tr.done_count);
+    }
 }
 
-// wave 0: the Solow step of the group's envs
+// wave 0: the Solow step of the group's envs (alive: the lane's env still plays; the rollout's always do)
+template <bool EVAL>
+__device__ __forceinline__ StepOut ro_solow_env_step_body(const RolloutArgs &R, float *lds, int t, int sbase, bool alive) {
+    const int lane = threadIdx.x & 63, env = ro_env(R, sbase, lane);
+    const bool valid = env < R.f.n && alive;
+    const StepOut so = ro_solow_step(R, lds, lane, env, valid);
+    ro_bookkeeping<EVAL>(R, lds, t, lane, env, valid, true, so);
+    return so;
+}
 __device__ __noinline__ void ro_solow_env_step(int slot, float *lds, int t, int sbase) {
     RO_ARGS(slot);
-    const int lane = threadIdx.x & 63, env = ro_env(R, sbase, lane);
-    const bool valid = env < R.f.n;
-    ro_bookkeeping(R, lds, t, lane, env, valid, true, ro_solow_step(R, lds, lane, env, valid));
+    ro_solow_env_step_body<false>(R, lds, t, sbase, true);
 }
 
 // all waves: the rest of TradeAR1Env._step behind the trades, as ONE stage of two halves around a barrier.  Wave 0 settles the
@@ -272,20 +311,22 @@ __device__ __noinline__ void ro_solow_env_step(int slot, float *lds, int t, int 
 // the price waves idled for the account's 3 us and the account's wave for the prices' 9.)  The generator counter of the step is
 // read by the price waves before the barrier and advanced by wave 0 after it.
 static_assert(MAXA <= 16, "one pair of assets per wave 8..15");
-__device__ __noinline__ void ro_trade_step(int slot, float *lds, int t, int sbase) {
-    RO_ARGS(slot);
+template <bool EVAL>
+__device__ __forceinline__ StepOut ro_trade_step_body(const RolloutArgs &R, float *lds, int t, int sbase, bool alive) {
     const RoLds L = ro_lds(R, lds);
     const TradeParams &Tr = R.tr;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), env = ro_env(R, sbase, lane);
-    const bool valid = env < R.f.n;
+    const bool valid = env < R.f.n && alive;
     const int n_as = Tr.n, E = Tr.E, pairs = (n_as + 1) / 2;
     const int j = wave - 8, as0 = 2 * j;
     const bool price_wave = j >= 0 && j < pairs && valid;
     int nst_next = 0;
+    StepOut so{0.f, 0};
     double pn[2] = {0.0, 0.0};
     float oq[2] = {0.f, 0.f}, op[2] = {0.f, 0.f};
     if (wave == 0) {
-        ro_bookkeeping(R, lds, t, lane, env, valid, false, ro_trade_account(R, lds, lane, env, valid, nst_next));
+        so = ro_trade_account(R, lds, lane, env, valid, nst_next);
+        ro_bookkeeping<EVAL>(R, lds, t, lane, env, valid, false, so);
     } else if (price_wave) {
         double z[2];
         if (Tr.flags & GRL_F_INJECT_NOISE) {
@@ -320,6 +361,11 @@ __device__ __noinline__ void ro_trade_step(int slot, float *lds, int t, int sbas
             }
         }
     }
+    return so;
+}
+__device__ __noinline__ void ro_trade_step(int slot, float *lds, int t, int sbase) {
+    RO_ARGS(slot);
+    ro_trade_step_body<false>(R, lds, t, sbase, true);
 }
 
 // all waves: the group's observation and per-env scalars into LDS

@@ -46,6 +46,13 @@ FNET_SIGNATURES = {
     "grl_comm_unique_id": (C.c_int, [_P, _SZ]),
 }
 
+# include/goldsrl_flateval.h: greedy acting and the one-launch evaluation (tests/test_flat_eval_header.py holds the two together)
+FNET_EVAL_SIGNATURES = {
+    "grl_fnet_set_greedy": (C.c_int, [_P, _I]),
+    "grl_fnet_eval": (C.c_int, [_P, _I, _I, _I]),
+    "grl_fnet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+}
+
 
 def flat_param_shapes(static_size=2, temporal_size=2, num_actions=1, H=32, S=32):
     """tf.trainable_variables() order of FlatPolicyVNetwork (policy_v_network.py:207-244, a3c/estimators.py:18-28)."""
@@ -78,7 +85,7 @@ def default_init_flat(seed=3, **kw):
 
 class FlatNet(object):
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=FNET_SIGNATURES)
+        self.lib = _ffi.load_library(extra_signatures=dict(FNET_SIGNATURES, **FNET_EVAL_SIGNATURES))
         self.eng = engine
         cfg = GrlFnetConfig()
         self.lib.grl_fnet_config_default(C.byref(cfg))
@@ -184,6 +191,32 @@ class FlatNet(object):
         """The rollouts that follow fill the training workspace; train_rollout on them starts at the backward pass (bit-identical
         gradients, the rollout pays the stores).  Off by default."""
         self._check(self.lib.grl_fnet_set_keep_activations(self.n, 1 if on else 0))
+
+    def set_greedy(self, on):
+        """on: rollout draws nothing, raw = mu ("actions" reads back equal to mu); the action counter stands still."""
+        self._check(self.lib.grl_fnet_set_greedy(self.n, 1 if on else 0))
+
+    EVAL_TRACE = ("states", "nhist", "mu", "sigma", "raw", "actions", "values", "rewards", "dones")
+
+    def eval(self, max_steps, trace_steps=0, greedy=False, trace_fields=EVAL_TRACE):
+        """Episodes of every env from the engine's current state (reset it first), one kernel launch; the engine is reset afterwards.
+        greedy=False draws the rollout's action noise at counters action_counter + t and advances the counter by max_steps.
+        Returns total_reward (E) float64, length (E) int32, finished (E) uint8 and, with trace_steps > 0, states (S,E,S0), nhist
+        (S,E) int32, mu, sigma, raw, actions (S,E,A), values, rewards, dones (S,E) of the first S = min(trace_steps, steps played)
+        steps, each defined up to its env's own end (trace_fields: the ones to read back)."""
+        self._check(self.lib.grl_fnet_eval(self.n, int(max_steps), int(trace_steps), 1 if greedy else 0))
+        E, A, S0 = self.eng.E, self.cfg.num_actions, self.cfg.static_size
+        out = {"total_reward": np.empty(E, np.float64), "length": np.empty(E, np.int32), "finished": np.empty(E, np.uint8)}
+        for k in ("total_reward", "length", "finished"):
+            self._check(self.lib.grl_fnet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
+        if trace_steps > 0:
+            S = min(int(trace_steps), int(max_steps), int(out["length"].max()))
+            tails = {"states": (S0,), "nhist": (), "mu": (A,), "sigma": (A,), "raw": (A,), "actions": (A,), "values": (), "rewards": (),
+                     "dones": ()}
+            for k in trace_fields:
+                out[k] = np.empty((S, E) + tails[k], np.int32 if k == "nhist" else np.float32)
+                self._check(self.lib.grl_fnet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
+        return out
 
     def train_rollout(self, lr):
         stats = np.zeros(4, np.float32)

@@ -60,14 +60,19 @@ class _DeviceMonitor(object):
         self.total_rewards, self.episode_lengths = None, None       # every env's, of the last evaluation
         self.log = {"total_reward": [], "episode_length": [], "mean_total_reward": [], "std_total_reward": [], "n_envs": self.n_envs}
 
-    def eval_once(self, params, max_sequence_length=None):
-        """Copy the parameters (copy_params_op), reset the eval envs, play every env's greedy episode.  Returns env 0's
-        (total_reward, episode_length, rewards)."""
-        if max_sequence_length is not None and max_sequence_length != self.net.R:
-            raise ValueError("max_sequence_length %r: the evaluation net was built with %r" % (max_sequence_length, self.net.R))
+    def _before_episodes(self):
+        """Between copying the parameters and resetting the eval envs (the flat PAAC monitor rewinds its action noise here)."""
+
+    def eval_once(self, params, max_sequence_length=None, **eval_kw):
+        """Copy the parameters (copy_params_op), reset the eval envs, play every env's episode (eval_kw: further arguments of the
+        net's eval, e.g. greedy=).  Returns env 0's (total_reward, episode_length, rewards)."""
+        rnn = getattr(self.net, "R", None) or self.net.cfg.rnn_length
+        if max_sequence_length is not None and max_sequence_length != rnn:
+            raise ValueError("max_sequence_length %r: the evaluation net was built with %r" % (max_sequence_length, rnn))
         self.net.set_params(params)
+        self._before_episodes()
         self.net.eng.reset()
-        r = self.net.eval(self.max_episode_steps, trace_steps=self.max_episode_steps, trace_fields=("rewards",))
+        r = self.net.eval(self.max_episode_steps, trace_steps=self.max_episode_steps, trace_fields=("rewards",), **eval_kw)
         self.total_rewards = np.asarray(r["total_reward"], np.float64)
         self.episode_lengths = np.asarray(r["length"])
         total_reward, episode_length = float(self.total_rewards[0]), int(self.episode_lengths[0])

@@ -47,7 +47,33 @@ class PAACLearner(ActorLearner):
         net = self.network.net
         if self.resume:
             self.load_checkpoint(self.resume)
-        return self._loop(net, ranks, lambda: net.rollout(self.max_local_steps), max_updates)
+        return self._loop(net, ranks, lambda: net.rollout(self.max_local_steps), max_updates, self._device_eval_hook(ranks, p, q, device_id))
+
+    def _device_eval_hook(self, ranks, p, q, device_id):
+        """paac.py:63-77: the reference starts a SolowPolicyMonitor on Solow-p-q-finite-eval-v0 beside the training loop.  Here the
+        episodes of `eval_envs` seeded envs of that registration are one kernel launch between two updates (rank 0 only): after every
+        eval_updates-th update, or (eval_updates = 0) when eval_every seconds have passed.  eval_envs = 0: no monitor, no hook."""
+        eval_envs = int(getattr(self, "eval_envs", 0) or 0)
+        if eval_envs <= 0 or ranks.rank != 0:
+            return None
+        from .policy_monitor import DeviceSolowPolicyMonitor, ScalarWriter
+        self.policy_monitor = DeviceSolowPolicyMonitor(
+            "Solow-%d-%d-finite-eval-v0" % (p, q), global_policy_net=self.network, state_processor=self.state_processor,
+            summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), learner=self, n_envs=eval_envs, rnn_length=self.rnn_length, device_id=device_id,
+            max_episode_steps=int(getattr(self, "max_episode_steps", 1024)))
+        every_updates = int(getattr(self, "eval_updates", 0) or 0)
+        every_seconds = float(getattr(self, "eval_every", 0.0) or 0.0)
+        state = {"last_eval": time.time()}
+
+        def between_updates(counter):
+            if every_updates > 0:
+                due = counter % every_updates == 0
+            else:
+                due = every_seconds > 0 and time.time() - state["last_eval"] >= every_seconds
+            if due:
+                self.policy_monitor.eval_once()
+                state["last_eval"] = time.time()
+        return between_updates
 
     def _ranks(self):
         """One process per GPU (RANK / WORLD_SIZE / LOCAL_RANK from the launcher): this rank owns `emulator_counts` envs with
@@ -112,6 +138,15 @@ class PAACLearner(ActorLearner):
         del self.total_rewards[:-1000]      # the log line reads the last ten only
         del self.episode_log[:-100000]
         self._ep_steps_seen += T
+
+
+    def cleanup(self):
+        """Closes the device monitor's eval engine and net (train with eval_envs > 0 built them)."""
+        mon = getattr(self, "policy_monitor", None)
+        if mon is not None:
+            mon.close()
+            self.policy_monitor = None
+        super(PAACLearner, self).cleanup()
 
 
 class GridPAACLearner(PAACLearner):

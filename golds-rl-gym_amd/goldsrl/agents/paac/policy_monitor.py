@@ -14,6 +14,7 @@ import time
 
 import numpy as np
 
+from ..a3c.policy_monitor import _DeviceMonitor
 from .emulator_runner import SolowRunner, SwarmRunner
 from .policy_v_network import ConvSingleAgentPolicyNetwork, FlatPolicyVNetwork
 
@@ -151,6 +152,45 @@ class SolowPolicyMonitor(PolicyMonitor):
         total_reward, episode_length = float(np.sum(rewards)), len(rewards)
         self._summaries(global_step, total_reward, episode_length, rewards)
         return total_reward, episode_length, rewards
+
+
+class DeviceSolowPolicyMonitor(_DeviceMonitor):
+    """SolowPolicyMonitor with the whole episode on the device: every episode of `n_envs` seeded envs of the eval registration
+    `Solow-p-q-finite-eval-v0` (seed 1692, reseeded at every reset) in one kernel launch (grl_fnet_eval,
+    include/goldsrl_flateval.h).  The streams are keyed by the global env id, so env 0 is the single episode the reference plays
+    and envs 1.. are further seeded episodes of the same registration; `eval_once` returns env 0's (total_reward, episode_length,
+    rewards) and keeps every env's totals and lengths.  Actions are drawn, a = mu + sigma * N(0,1), as the reference's monitor
+    draws them (policy_monitor.py:45-49) -- from the device's action stream at counter 0, so every evaluation plays the same
+    episodes with the same noise; greedy=True acts with mu.  The window is the rollout's (the current state repeated, the window
+    the policy is trained under), not the true last-rnn states SolowPolicyMonitor feeds."""
+
+    def __init__(self, env, global_policy_net, state_processor=None, summary_writer=None, saver=None, network_conf=None, learner=None,
+                 n_envs=1, rnn_length=5, device_id=0, max_episode_steps=1024):
+        from ... import _ffi
+        if not (env.startswith("Solow-") and env.endswith("-finite-eval-v0")):
+            raise ValueError("no device evaluation for env %r (Solow-p-q-finite-eval-v0)" % (env,))
+        if n_envs < 1:
+            raise ValueError("n_envs must be at least 1")
+        p, q = (int(v) for v in env.split("-")[1:3])
+        self.env = env
+        self.global_policy_net = global_policy_net
+        self.state_processor = state_processor
+        self.saver = saver
+        self.learner = learner
+        eng = _ffi.Engine(_ffi.ENV_SOLOW, int(n_envs), device_id=device_id, seed=1692, flags=_ffi.F_RESEED_EACH_RESET, solow_p=p, solow_q=q,
+                          rnn_length=int(rnn_length), max_episode_steps=int(max_episode_steps))
+        conf = network_conf if network_conf is not None else global_policy_net.conf
+        self.policy_net = FlatPolicyVNetwork(conf).bind(eng, rnn_length=int(rnn_length), max_samples=int(n_envs))      # the "policy_eval" copy
+        self._adopt(self.policy_net.net, True, summary_writer, max_episode_steps)
+
+    def _before_episodes(self):
+        self.net.set_action_counter(0)      # every evaluation draws the same noise
+
+    def eval_once(self, greedy=False, sess=None, max_sequence_length=None):
+        global_step = int(self.learner.global_step) if self.learner is not None else 0
+        out = _DeviceMonitor.eval_once(self, self.global_policy_net.get_flat_params(), max_sequence_length, greedy=greedy)
+        self.write_scalars(global_step)
+        return out
 
 
 class SwarmPolicyMonitor(PolicyMonitor):

@@ -36,6 +36,13 @@ def get_network_and_environment_creator(args, random_seed=3):
 def get_arg_parser():
     p = _conv_parser()
     p.set_defaults(scale=100.)              # train_paac_solow.py:122 (the conv script uses 1000)
+    p.add_argument('--eval-envs', default=0, type=int, dest="eval_envs",
+                   help="envs of Solow-1-1-finite-eval-v0 evaluated on the device between updates (paac.py:63-77), one launch per "
+                        "evaluation; 0: no evaluation")
+    p.add_argument('--eval-updates', default=0, type=int, dest="eval_updates",
+                   help="evaluate after every K-th update; 0: when --eval-every seconds have passed")
+    p.add_argument('--max_episode_steps', default=None, type=int, dest="max_episode_steps",
+                   help="TimeLimit of the training and eval envs (the registered ids have 1024)")
     return p
 
 
@@ -43,7 +50,10 @@ def main(args):
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = PAACLearner(network_creator, env_creator, args, SolowRunner, SolowStateProcessor())
     logging.info('Starting training')
-    learner.train()
+    try:
+        learner.train()
+    finally:
+        learner.cleanup()      # the device monitor's eval engine and net, when --eval-envs built them
     logging.info('Finished training')
 
 

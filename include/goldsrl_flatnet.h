@@ -108,4 +108,7 @@ int grl_fnet_comm_info(grl_fnet *net, int32_t *count_out, int32_t *user_rank_out
 #ifdef __cplusplus
 }
 #endif
+
+#include "goldsrl_flateval.h" /* greedy acting and the one-launch evaluation of the same net */
+
 #endif /* GOLDSRL_FLATNET_H */
