@@ -19,7 +19,7 @@
 
 #include <rccl/rccl.h>
 
-#include "../../include/goldsrl_flatnet.h"
+#include "../../include/goldsrl_flatnet.h"      // brings goldsrl_flateval.h and goldsrl_flatwindow.h
 #include "common.h"
 #include "rng.h"
 #include "flat_env_dev.h"
@@ -89,6 +89,8 @@ struct FlatArgs {
     double *stats64;
     long long *ts;                  // stage clock of workgroup 0 (debug, grl_fnet_rollout_stage_times) or nullptr
     int *ts_n;
+    int wstride, wring;             // wstride > 0: the TRUE window (net_flat_window.inc) -- nhist[s] rows wstride * S0 floats apart that end at
+                                    // states[s]; wring > 0 (evaluation): the time slices form a ring of wring
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -98,6 +100,7 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 #include "net_flat_bwd_fast.inc"
 #include "net_flat_rollout.inc"
 #include "net_flat_eval.inc"
+#include "net_flat_window.inc"
 
 // PT: the weight matrices the data gradients multiply with, transposed (block b = matrix b; the GRU kernels: their recurrent rows)
 __global__ void flat_transpose_kernel(const float *__restrict__ P, float *__restrict__ PT, FOff o, int D, int A) {
@@ -226,6 +229,19 @@ struct grl_fnet {
     int arg_slot;                  // this net's slot of g_flat_args (net_flat_fast.inc), -1: none free (graph path)
     long long *d_ts;               // stage timestamps of workgroup 0 of the persistent rollout (debug: grl_fnet_rollout_stage_times)
     int *d_ts_n;
+    // grl_fnet_set_true_window (net_flat_window.inc): the rollout's states live in a slab with rnn - 1 leading time slices (and one
+    // behind, the bootstrap observation), ro_states = ro_slab + (rnn - 1) * E * S0, and the windows are strided views of it
+    int true_window;
+    float *ro_slab;
+    int slab_T;                    // rollout steps the slab has room for
+    int32_t *w_len, *w_elapsed, *w_episode;      // (E): the rows the next forward sees; TimeLimit counter / episode the net saw last
+    const float *w_src;            // where the rnn - 1 slices behind the next rollout's first step lie (ro_slab itself once carried)
+    int w_restart_all, w_have;     // every window restarts at the next call; w_len / w_elapsed / w_episode describe a finished rollout
+    int w_valid;                   // the slab still holds the last rollout (nothing was carried forward since)
+    float *ev_ring;                // evaluation: (rnn, E, S0) ring of the last states
+    char ro_win_attr_set[3], ev_win_attr_set[3];
+    int ro_graph_tw;               // the captured rollout is the true-window one, on
+    float *ro_graph_slab;          // this slab
     int last_n;                    // samples of the last gradient pass (grl_fnet_apply_grads normalises the loss sums with it)
     void *comm;                    // ncclComm_t (RCCL): one all-reduce of the flat gradient per rollout, or nullptr
     int comm_world, comm_rank;
@@ -258,20 +274,27 @@ static int falloc(grl_fnet *n, T **p, size_t count) {
 }
 
 static FlatArgs base_args(grl_fnet *net, int n, const float *states, const float *hist, float *mu, float *sigma, float *vs, bool save,
-                          const int32_t *nhist = nullptr) {
+                          const int32_t *nhist = nullptr, int wstride = 0) {
     FlatArgs a{};
     a.P = net->params; a.o = net->off; a.n = n; a.S0 = net->cfg.static_size; a.D = net->cfg.temporal_size; a.T = net->cfg.rnn_length;
     a.A = net->cfg.num_actions; a.scale = net->cfg.scale; a.bound = net->cfg.mu_bound; a.states = states; a.hist = hist;
     a.mu = mu; a.sigma = sigma; a.vs = vs; a.ws = save ? net->ws : nullptr; a.nhist = nhist;
-    a.ts = net->d_ts; a.ts_n = net->d_ts_n;
+    a.ts = net->d_ts; a.ts_n = net->d_ts_n; a.wstride = wstride;
     return a;
 }
 
 static int launch_forward(grl_fnet *net, int n, const float *states, const float *hist, float *mu, float *sigma, float *vs, bool save,
-                          const int32_t *nhist = nullptr) {
-    FlatArgs a = base_args(net, n, states, hist, mu, sigma, vs, save, nhist);
+                          const int32_t *nhist = nullptr, int wstride = 0) {
+    FlatArgs a = base_args(net, n, states, hist, mu, sigma, vs, save, nhist, wstride);
     const int groups = (n + 63) / 64;
-    if (nhist && net->cfg.static_size == net->cfg.temporal_size && net->fast_forward) {
+    if (wstride && !save) {
+        // true windows, predictions only: the fast forward for distinct rows (net_flat_window.inc)
+        if (net->cfg.temporal_size <= 4) hipLaunchKernelGGL(flat_forward_win_kernel<1>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
+        else hipLaunchKernelGGL(flat_forward_win_kernel<9>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
+        FNET_HIP(net, hipGetLastError());
+        return GRL_OK;
+    }
+    if (nhist && !wstride && net->cfg.static_size == net->cfg.temporal_size && net->fast_forward) {
         // synthesized window (the PAAC worker's: the current state repeated): the 2T + 5 stage form of net_flat_fast.inc
         if (save) hipLaunchKernelGGL(flat_forward_fast_kernel<true>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
         else hipLaunchKernelGGL(flat_forward_fast_kernel<false>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
@@ -292,22 +315,23 @@ static int launch_forward(grl_fnet *net, int n, const float *states, const float
 // resident: the workspace already holds this forward (the rollout that produced the samples kept its activations, and the
 // parameters have not moved since): the pass starts at the backward
 static int train_grads_device(grl_fnet *net, int n, const float *states, const float *hist, const float *actions, const float *adv,
-                              const float *y, const int32_t *nhist = nullptr, bool resident = false) {
+                              const float *y, const int32_t *nhist = nullptr, bool resident = false, int wstride = 0) {
     hipStream_t st = net->h->stream;
     if (n > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "train: n exceeds max_samples of the net");
     int rc = GRL_OK;
     if (!resident) {
         net->ws_resident = 0;
-        rc = launch_forward(net, n, states, hist, net->mu, net->sigma, net->vs, true, nhist);
+        rc = launch_forward(net, n, states, hist, net->mu, net->sigma, net->vs, true, nhist, wstride);
     }
     if (rc) return rc;
     int groups = (n + 63) / 64;
-    const bool fast = nhist && net->cfg.static_size == net->cfg.temporal_size && net->fast_forward && net->arg_slot >= 0;
+    // true windows (wstride): the general forward and backward over the strided views; a fast backward for distinct rows does not exist
+    const bool fast = nhist && !wstride && net->cfg.static_size == net->cfg.temporal_size && net->fast_forward && net->arg_slot >= 0;
     int blocks = groups < net->slab_blocks ? groups : net->slab_blocks;
     if (fast && blocks > 256) blocks = 256;      // the 16-wave form: one workgroup per CU (100 KB of LDS)
     if (!fast) FNET_HIP(net, hipMemsetAsync(net->slab, 0, (size_t)blocks * net->off.total * 4, st));      // the fast backward clears its own
     FNET_HIP(net, hipMemsetAsync(net->stats64, 0, 4 * sizeof(double), st));
-    FlatArgs a = base_args(net, n, states, hist, net->mu, net->sigma, net->vs, true, nhist);
+    FlatArgs a = base_args(net, n, states, hist, net->mu, net->sigma, net->vs, true, nhist, wstride);
     a.actions = actions; a.adv = adv; a.y = y; a.inv_n = 1.0f / (float)n; a.slab = net->slab; a.stats64 = net->stats64;
     if (fast && net->arg_slot >= 0) {
         a.PT = net->paramsT;
@@ -376,12 +400,63 @@ static int train_apply_device(grl_fnet *net, float lr, int apply_update, float g
 
 // gradient pass [+ all-reduce over ranks if a communicator is attached and the parameters are to be updated] + clip + Adam
 static int train_device(grl_fnet *net, int n, const float *states, const float *hist, const float *actions, const float *adv, const float *y,
-                        float lr, int apply_update, float *stats_host, const int32_t *nhist = nullptr, bool resident = false) {
-    int rc = train_grads_device(net, n, states, hist, actions, adv, y, nhist, resident);
+                        float lr, int apply_update, float *stats_host, const int32_t *nhist = nullptr, bool resident = false, int wstride = 0) {
+    int rc = train_grads_device(net, n, states, hist, actions, adv, y, nhist, resident, wstride);
     if (rc) return rc;
     float grad_scale = 1.0f;
     if (apply_update && (rc = fcomm_allreduce_grads(net, &grad_scale))) return rc;
     return train_apply_device(net, lr, apply_update, grad_scale, stats_host);
+}
+
+// ---- true window (net_flat_window.inc): the state the net keeps between calls
+// the slab for rollouts of T steps; ro_states points behind its rnn - 1 leading slices
+static int window_ensure_slab(grl_fnet *net, int T) {
+    const size_t slice = (size_t)net->h->E * net->cfg.static_size, lead = (size_t)net->cfg.rnn_length - 1;
+    int rc = GRL_OK;
+    if (!net->w_len) {
+        if ((rc = falloc(net, &net->w_len, net->h->E))) return rc;
+        if ((rc = falloc(net, &net->w_elapsed, net->h->E))) return rc;
+        if ((rc = falloc(net, &net->w_episode, net->h->E))) return rc;
+        net->w_restart_all = 1;
+    }
+    if (!net->ro_slab || net->slab_T < T) {
+        // an older slab stays allocated until the net is destroyed: w_src may still point into it
+        if ((rc = falloc(net, &net->ro_slab, (lead + (size_t)T + 1) * slice))) return rc;
+        net->slab_T = T;
+    }
+    net->ro_states = net->ro_slab + lead * slice;
+    return GRL_OK;
+}
+
+// before a forward on the handle's current observation: the rows behind it move to the front of the slab (once), and windows
+// restart for every env the host reset or stepped since the net last looked (or for all of them)
+static int window_enter(grl_fnet *net) {
+    grl_handle *h = net->h;
+    const int E = h->E, lead = net->cfg.rnn_length - 1;
+    const long slice = (long)E * net->cfg.static_size;
+    hipStream_t st = h->stream;
+    const int all = (net->w_restart_all || !net->w_have) ? 1 : 0;
+    if (!all && lead > 0 && net->w_src && net->w_src != net->ro_slab)
+        hipLaunchKernelGGL(flat_window_carry_kernel, dim3((unsigned)((slice + 255) / 256)), dim3(256), 0, st, net->w_src, net->ro_slab, lead, slice);
+    net->w_src = net->ro_slab;
+    net->w_valid = 0;
+    hipLaunchKernelGGL(flat_window_detect_kernel, dim3((E + 255) / 256), dim3(256), 0, st, net->w_len, (const int32_t *)h->elapsed,
+                       (const int32_t *)h->episode, (const int32_t *)net->w_elapsed, (const int32_t *)net->w_episode, E, all);
+    FNET_HIP(net, hipGetLastError());
+    net->w_restart_all = 0;
+    return GRL_OK;
+}
+
+// behind a rollout of T steps: what the net has seen of every env, and where the next rollout's leading rows lie
+static int window_leave(grl_fnet *net, int T) {
+    grl_handle *h = net->h;
+    const long slice = (long)h->E * net->cfg.static_size;
+    FNET_HIP(net, hipMemcpyAsync(net->w_elapsed, h->elapsed, (size_t)h->E * 4, hipMemcpyDeviceToDevice, h->stream));
+    FNET_HIP(net, hipMemcpyAsync(net->w_episode, h->episode, (size_t)h->E * 4, hipMemcpyDeviceToDevice, h->stream));
+    net->w_src = net->ro_states + ((long)T - (net->cfg.rnn_length - 1)) * slice;
+    net->w_have = 1;
+    net->w_valid = 1;
+    return GRL_OK;
 }
 
 // the T-step actor loop as stream operations (captured into a graph by grl_fnet_rollout)
@@ -399,10 +474,17 @@ static int enqueue_rollout(grl_fnet *net, int T) {
         // the window is kept as (state, #rows) for both envs -- the worker's history is min(n, rnn) copies of the current state
         // (quirk Q11); Solow's dense (E, rnn, 2) form is recorded too (grl_fnet_read_rollout "histories")
         const int32_t *nh = solow ? h->so.nhist : h->tr.nhist;
+        if (net->true_window) {
+            // the window: the rows of the slab that end at states[t] (w_len of them per env)
+            FNET_HIP(net, hipMemcpyAsync(net->ro_nhist + (size_t)t * E, net->w_len, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
+            rc = launch_forward(net, E, net->ro_states + (size_t)t * E * S0, nullptr, net->mu, net->sigma, net->ro_val + (size_t)t * E, false, net->w_len, E);
+            if (rc) return rc;
+        } else {
         if (solow) FNET_HIP(net, hipMemcpyAsync(net->ro_hist + (size_t)t * E * R * 2, h->so.history, (size_t)E * R * 8, hipMemcpyDeviceToDevice, st));
         FNET_HIP(net, hipMemcpyAsync(net->ro_nhist + (size_t)t * E, nh, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
         rc = launch_forward(net, E, obs, nullptr, net->mu, net->sigma, net->ro_val + (size_t)t * E, false, nh);
         if (rc) return rc;
+        }
         hipLaunchKernelGGL(flat_sample_kernel, dim3((E * A + 255) / 256), dim3(256), 0, st, net->mu, net->sigma, E, A, h->cfg.seed,
                            (uint32_t)h->cfg.env_id_offset, (const uint32_t *)net->d_counter, (uint32_t)t, h->cfg.env_kind, net->greedy,
                            net->ro_act + (size_t)t * E * A, net->ro_envact);
@@ -411,8 +493,15 @@ static int enqueue_rollout(grl_fnet *net, int T) {
         if ((rc = episodes_launch_account(h))) return ffail(net, rc, h->err);      // R6 (paac.py:142-157), when enabled on the handle
         FNET_HIP(net, hipMemcpyAsync(net->ro_rew + (size_t)t * E, h->reward, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(flat_mask_kernel, dim3((E + 255) / 256), dim3(256), 0, st, h->done, E, net->ro_mask + (size_t)t * E);
+        if (net->true_window)
+            hipLaunchKernelGGL(flat_window_step_kernel, dim3((E + 255) / 256), dim3(256), 0, st, net->w_len, (const uint8_t *)h->done, E, R);
     }
-    rc = launch_forward(net, E, obs, nullptr, net->mu, net->sigma, net->ro_boot, false, solow ? h->so.nhist : h->tr.nhist);
+    if (net->true_window) {      // the bootstrap observation is slice T of the slab: the window behind the last step
+        FNET_HIP(net, hipMemcpyAsync(net->ro_states + (size_t)T * E * S0, obs, (size_t)E * S0 * 4, hipMemcpyDeviceToDevice, st));
+        rc = launch_forward(net, E, net->ro_states + (size_t)T * E * S0, nullptr, net->mu, net->sigma, net->ro_boot, false, net->w_len, E);
+    } else {
+        rc = launch_forward(net, E, obs, nullptr, net->mu, net->sigma, net->ro_boot, false, solow ? h->so.nhist : h->tr.nhist);
+    }
     if (rc) return rc;
     // rewards clipped to [-2, 2] (paac.py:145), masked n-step return (paac.py:167-172), adv / scale (paac.py:177)
     // gae_lambda < 1: the A3C worker's GAE on the raw rewards (a3c/worker.py:232-294)
@@ -446,11 +535,17 @@ static int launch_persistent_rollout(grl_fnet *net, int T) {
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     RolloutArgs R{};
     R.f = base_args(net, h->E, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-    const bool keep = net->keep_activations != 0;
+    const bool tw = net->true_window != 0;
+    const bool keep = net->keep_activations != 0 && !tw;      // true window: accepted and ignored, the gradient step recomputes
     if (keep) R.f.ws = net->ws;
     R.steps = T; R.env_kind = h->cfg.env_kind; R.slot = net->arg_slot;
     const int n_assets = solow ? 0 : h->cfg.n_assets;
-    const size_t lds_bytes = (size_t)rollout_lds_floats(net->cfg.static_size, T, n_assets, &R) * sizeof(float);
+    size_t lds_bytes = (size_t)rollout_lds_floats(net->cfg.static_size, T, n_assets, &R) * sizeof(float);
+    if (tw) {      // one more row of ints behind everything: the window's rows per env; the forward reads the windows from the slab
+        R.off_wl = (int)(lds_bytes / sizeof(float));
+        lds_bytes += 64 * sizeof(float);
+        R.wlen = net->w_len; R.f.states = net->ro_states; R.f.wstride = h->E;
+    }
     if (lds_bytes > 160 * 1024) return GRL_E_SIZE;
     // envs per workgroup: a workgroup has a CU to itself (LDS), and a group's chain of stages is as long for 16 envs as for 64 with
     // fewer tiles per stage -- so the smallest group that still gives every CU at most one workgroup (GRL_FLAT_GROUP = 64 / 32 / 16
@@ -464,12 +559,13 @@ static int launch_persistent_rollout(grl_fnet *net, int T) {
     typedef void (*RoKernel)(int);
     static const RoKernel kernels[2][3] = {{flat_rollout_kernel<16, false>, flat_rollout_kernel<32, false>, flat_rollout_kernel<64, false>},
                                            {flat_rollout_kernel<16, true>, flat_rollout_kernel<32, true>, flat_rollout_kernel<64, true>}};
+    static const RoKernel win_kernels[3] = {flat_rollout_win_kernel<16>, flat_rollout_win_kernel<32>, flat_rollout_win_kernel<64>};
     const int gi = G == 16 ? 0 : (G == 32 ? 1 : 2);
-    const RoKernel kern_fn = kernels[keep ? 1 : 0][gi];
+    const RoKernel kern_fn = tw ? win_kernels[gi] : kernels[keep ? 1 : 0][gi];
     const void *kern = (const void *)kern_fn;
     // the attribute belongs to the kernel (per device), not to the net: every net raises it to the CU's whole LDS, so that no net's
     // smaller rollout lowers it under another net's larger one
-    char &attr_set = net->ro_attr_set[keep ? 1 : 0][gi];
+    char &attr_set = tw ? net->ro_win_attr_set[gi] : net->ro_attr_set[keep ? 1 : 0][gi];
     if (!attr_set) {
         if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
             (void)hipGetLastError();
@@ -547,17 +643,30 @@ static int launch_eval(grl_fnet *net, int max_steps, int trace_steps, int greedy
     R.f.ts = nullptr; R.f.ts_n = nullptr;
     R.steps = 0; R.env_kind = h->cfg.env_kind; R.slot = net->arg_slot;
     int live_off = 0;
-    const size_t lds_bytes = (size_t)eval_lds_floats(net->cfg.static_size, solow ? 0 : h->cfg.n_assets, &R, &live_off) * sizeof(float);
+    const bool tw = net->true_window != 0;
+    size_t lds_bytes = (size_t)eval_lds_floats(net->cfg.static_size, solow ? 0 : h->cfg.n_assets, &R, &live_off) * sizeof(float);
+    if (tw) {      // the window's rows per env behind the live word; the last rnn states of every env in a ring of time slices
+        R.off_wl = (int)(lds_bytes / sizeof(float));
+        lds_bytes += 64 * sizeof(float);
+        if (!net->ev_ring) {
+            int rc = falloc(net, &net->ev_ring, (size_t)net->cfg.rnn_length * h->E * net->cfg.static_size);
+            if (rc) return rc;
+        }
+        R.f.states = net->ev_ring; R.f.wstride = h->E; R.f.wring = net->cfg.rnn_length;
+    }
     if (lds_bytes > 160 * 1024) return ffail(net, GRL_E_SIZE, "grl_fnet_eval: the evaluation's LDS rows do not fit a CU");
     int G = net->ro_group;      // the rule of launch_persistent_rollout
     if (!G) G = h->E <= 16 * 256 ? 16 : (h->E <= 32 * 256 ? 32 : 64);
     R.gs = G;
     typedef void (*EvKernel)(int, int);
-    static const EvKernel kernels[3] = {flat_eval_kernel<16>, flat_eval_kernel<32>, flat_eval_kernel<64>};
+    static const EvKernel quirk_kernels[3] = {flat_eval_kernel<16>, flat_eval_kernel<32>, flat_eval_kernel<64>};
+    static const EvKernel win_kernels[3] = {flat_eval_win_kernel<16>, flat_eval_win_kernel<32>, flat_eval_win_kernel<64>};
+    const EvKernel *kernels = tw ? win_kernels : quirk_kernels;
     const int gi = G == 16 ? 0 : (G == 32 ? 1 : 2);
-    if (!net->ev_attr_set[gi]) {
+    char &ev_attr = tw ? net->ev_win_attr_set[gi] : net->ev_attr_set[gi];
+    if (!ev_attr) {
         FNET_HIP(net, hipFuncSetAttribute((const void *)kernels[gi], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        net->ev_attr_set[gi] = 1;
+        ev_attr = 1;
     }
     if (solow) { R.so = solow_params(h); R.obs0 = h->so.obs; }
     else { R.tr = trade_params(h); R.obs0 = h->tr.obs; }
@@ -634,6 +743,9 @@ int grl_fnet_create(grl_handle *h, const grl_fnet_config *cfg, grl_fnet **out) {
         const char *f = getenv("GRL_FLAT_FORWARD");
         n->fast_forward = (f && strcmp(f, "layers") == 0) ? 0 : 1;
     }
+    n->true_window = 0; n->ro_slab = nullptr; n->slab_T = 0; n->w_len = n->w_elapsed = n->w_episode = nullptr; n->w_src = nullptr;
+    n->w_restart_all = 1; n->w_have = 0; n->w_valid = 0; n->ev_ring = nullptr; n->ro_graph_tw = 0;
+    memset(n->ro_win_attr_set, 0, sizeof(n->ro_win_attr_set)); memset(n->ev_win_attr_set, 0, sizeof(n->ev_win_attr_set));
     n->last_n = 0; n->comm = nullptr; n->comm_world = 1; n->comm_rank = 0;
     n->ar_ev0 = n->ar_ev1 = nullptr; n->ar_pending = 0; n->ar_calls = 0; n->ar_ms_total = 0.0; n->ar_ms_last = 0.f;
     hipError_t e = hipSuccess;
@@ -647,6 +759,10 @@ int grl_fnet_create(grl_handle *h, const grl_fnet_config *cfg, grl_fnet **out) {
         e = hipFuncSetAttribute((const void *)flat_forward_fast_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_lds_bytes(MAXS0));
     if (rc == GRL_OK && e == hipSuccess)
         e = hipFuncSetAttribute((const void *)flat_forward_fast_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_lds_bytes(MAXS0));
+    if (rc == GRL_OK && e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)flat_forward_win_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_lds_bytes(MAXS0));
+    if (rc == GRL_OK && e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)flat_forward_win_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_lds_bytes(MAXS0));
     if (rc == GRL_OK && e == hipSuccess)
         e = hipFuncSetAttribute((const void *)flat_backward_fast_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB2_LDS_BYTES);
     if (rc == GRL_OK && e != hipSuccess) rc = ffail(n, GRL_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
@@ -774,6 +890,16 @@ int grl_fnet_predict_env(grl_fnet *net, float *mu, float *sigma, float *vs) {
     int rc = check_env(net);
     if (rc) return rc;
     grl_handle *h = net->h;
+    if (net->true_window) {
+        // the window the next rollout's first step would see: the rows behind it are carried forward now (the slab no longer
+        // holds the last rollout: grl_fnet_train_rollout and grl_fnet_read_windows need a new one)
+        const float *obs = h->cfg.env_kind == GRL_ENV_SOLOW ? h->so.obs : h->tr.obs;
+        if ((rc = window_ensure_slab(net, net->T > 0 ? net->T : 1))) return rc;
+        if ((rc = window_enter(net))) return rc;
+        FNET_HIP(net, hipMemcpyAsync(net->ro_states, obs, (size_t)h->E * net->cfg.static_size * 4, hipMemcpyDeviceToDevice, h->stream));
+        if ((rc = launch_forward(net, h->E, net->ro_states, nullptr, net->mu, net->sigma, net->vs, false, net->w_len, h->E))) return rc;
+        return fdownload(net, h->E, mu, sigma, vs);
+    }
     if (h->cfg.env_kind == GRL_ENV_SOLOW) rc = launch_forward(net, h->E, h->so.obs, nullptr, net->mu, net->sigma, net->vs, false, h->so.nhist);
     else rc = launch_forward(net, h->E, h->tr.obs, nullptr, net->mu, net->sigma, net->vs, false, h->tr.nhist);
     if (rc) return rc;
@@ -804,14 +930,20 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     const int E = h->E, R = net->cfg.rnn_length, S0 = net->cfg.static_size, A = net->cfg.num_actions;
     if ((long)T * E > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "grl_fnet_rollout: T*num_envs exceeds max_samples");
-    if (!net->ro_states || net->T < T) {
+    const bool tw = net->true_window != 0;
+    if (!net->ro_act || net->T < T) {
         auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = falloc(net, p, cnt); };
-        Al(&net->ro_states, (size_t)T * E * S0); Al(&net->ro_act, (size_t)T * E * A);
+        if (!tw) Al(&net->ro_states, (size_t)T * E * S0);      // true window: the states live in the slab
+        Al(&net->ro_act, (size_t)T * E * A);
         Al(&net->ro_envact, (size_t)E * A); Al(&net->ro_val, (size_t)T * E); Al(&net->ro_rew, (size_t)T * E); Al(&net->ro_mask, (size_t)T * E);
         Al(&net->ro_y, (size_t)T * E); Al(&net->ro_adv, (size_t)T * E); Al(&net->ro_boot, E);
         if (solow) Al(&net->ro_hist, (size_t)T * E * R * 2);
         if (rc == GRL_OK) rc = falloc(net, &net->ro_nhist, (size_t)T * E);
         if (rc) return rc;
+    }
+    if (tw) {
+        if ((rc = window_ensure_slab(net, T))) return rc;
+        if ((rc = window_enter(net))) return rc;
     }
     net->T = T;
     net->ws_resident = 0;      // set again by a persistent rollout that keeps its activations
@@ -825,11 +957,13 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     static const int persist_max_groups = getenv("GRL_FLAT_PERSIST_GROUPS") ? atoi(getenv("GRL_FLAT_PERSIST_GROUPS")) : 512;
     if (net->ro_persistent && (E + 63) / 64 <= persist_max_groups) {
         rc = launch_persistent_rollout(net, T);
-        if (rc == GRL_OK) { h->step_in_flight = true; return GRL_OK; }
+        if (rc == GRL_OK) { h->step_in_flight = true; return tw ? window_leave(net, T) : GRL_OK; }
         if (rc != GRL_E_SIZE) return rc;
         net->ro_persistent = 0;      // does not fit the LDS of a CU (very long rollouts): the graph path from here on
     }
-    if (net->ro_graph && net->ro_graph_T == T && net->ro_graph_ep == (h->ep_total != nullptr) && net->ro_graph_greedy == net->greedy) {
+    // (the graph holds the buffers' addresses: a true-window graph is only replayed while the slab is the one it was captured on)
+    if (net->ro_graph && net->ro_graph_T == T && net->ro_graph_ep == (h->ep_total != nullptr) && net->ro_graph_greedy == net->greedy &&
+        net->ro_graph_tw == (tw ? 1 : 0) && (!tw || net->ro_graph_slab == net->ro_slab)) {
         FNET_HIP(net, hipGraphLaunch(net->ro_graph, st));
     } else {
         if (net->ro_graph) { (void)hipGraphExecDestroy(net->ro_graph); net->ro_graph = nullptr; }
@@ -844,6 +978,8 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
                 net->ro_graph_T = T;
                 net->ro_graph_ep = h->ep_total != nullptr;
                 net->ro_graph_greedy = net->greedy;
+                net->ro_graph_tw = tw ? 1 : 0;
+                net->ro_graph_slab = net->ro_slab;
             } else {
                 net->ro_graph = nullptr;
                 (void)hipGetLastError();
@@ -858,6 +994,36 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     }
     FNET_HIP(net, hipGetLastError());
     h->step_in_flight = true;
+    return tw ? window_leave(net, T) : GRL_OK;
+}
+
+int grl_fnet_set_true_window(grl_fnet *net, int32_t on) {
+    if (!net) return GRL_E_INVALID;
+    if (net->cfg.static_size != net->cfg.temporal_size)
+        return ffail(net, GRL_E_INVALID, "grl_fnet_set_true_window: the window's rows are the states, so static_size must equal temporal_size");
+    net->true_window = on ? 1 : 0;
+    net->ws_resident = 0;      // kept activations are dropped
+    net->w_restart_all = 1; net->w_have = 0; net->w_valid = 0;      // every window restarts at the next call
+    return GRL_OK;
+}
+
+int grl_fnet_read_windows(grl_fnet *net, int32_t first, int32_t count, float *host, size_t bytes) {
+    if (!net || (!host && count > 0)) return ffail(net, GRL_E_INVALID, "grl_fnet_read_windows: bad argument");
+    if (!net->true_window || !net->ro_act || net->T <= 0 || !net->w_valid)
+        return ffail(net, GRL_E_STATE, "grl_fnet_read_windows: no true-window rollout to read (none yet, or its rows were carried forward)");
+    const long TE = (long)net->T * net->h->E;
+    const int R = net->cfg.rnn_length, D = net->cfg.temporal_size;
+    if (first < 0 || count < 0 || (long)first + count > TE) return ffail(net, GRL_E_SIZE, "grl_fnet_read_windows: samples out of range");
+    if (bytes != (size_t)count * R * D * 4) return ffail(net, GRL_E_SIZE, "grl_fnet_read_windows: wrong size");
+    if (count == 0) return GRL_OK;
+    hipSetDevice(net->h->cfg.device_id);
+    hipStream_t st = net->h->stream;
+    const long total = (long)count * R * D;
+    hipLaunchKernelGGL(flat_window_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float *)net->ro_states,
+                       (const int32_t *)net->ro_nhist, net->h->E, first, count, R, D, net->d_hist);
+    FNET_HIP(net, hipGetLastError());
+    FNET_HIP(net, hipStreamSynchronize(st));
+    FNET_HIP(net, hipMemcpy(host, net->d_hist, bytes, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 
@@ -880,6 +1046,7 @@ int grl_fnet_eval(grl_fnet *net, int32_t max_steps, int32_t trace_steps, int32_t
     if (!greedy) net->act_counter += (unsigned long)max_steps;      // later rollouts never reuse the evaluation's noise
     net->ev_trace = trace_steps;
     net->ev_played = -1;
+    net->w_restart_all = 1;      // the handle is reset below: every window restarts
     // the handle's full reset (for Solow with the tape draw), as grl_reset(h, NULL, 0) enqueues it
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     const int E = h->E;
@@ -944,6 +1111,10 @@ int grl_fnet_train_rollout(grl_fnet *net, float lr, float *stats_host) {
     if (!net || !net->ro_states || net->T <= 0) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout: no rollout to train on");
     hipSetDevice(net->h->cfg.device_id);
     const int n = net->T * net->h->E;
+    if (net->true_window) {
+        if (!net->w_valid) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout: the last rollout's windows were carried forward");
+        return train_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, lr, 1, stats_host, net->ro_nhist, false, net->h->E);
+    }
     return train_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, lr, 1, stats_host, net->ro_nhist,
                         net->ws_resident != 0);
 }
@@ -954,7 +1125,10 @@ int grl_fnet_train_rollout_grads(grl_fnet *net, float *stats_host) {
     if (!net || !net->ro_states || net->T <= 0) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout_grads: no rollout to train on");
     hipSetDevice(net->h->cfg.device_id);
     const int n = net->T * net->h->E;
-    int rc = train_grads_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, net->ro_nhist, net->ws_resident != 0);
+    if (net->true_window && !net->w_valid) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout_grads: the last rollout's windows were carried forward");
+    int rc = net->true_window
+                 ? train_grads_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, net->ro_nhist, false, net->h->E)
+                 : train_grads_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, net->ro_nhist, net->ws_resident != 0);
     if (rc) return rc;
     return train_apply_device(net, 0.f, 0, 1.0f, stats_host);
 }
@@ -1039,6 +1213,11 @@ int grl_fnet_read_rollout(grl_fnet *net, const char *which, void *host, size_t b
     else if (w == "adv") src = net->ro_adv;
     else if (w == "boot") { src = net->ro_boot; need = (size_t)net->h->E * 4; }
     else if (w == "states") { src = net->ro_states; need = TE * net->cfg.static_size * 4; }
+    else if (w == "histories" && net->true_window) {      // the true windows, dense: grl_fnet_read_windows over every sample
+        need = TE * net->cfg.rnn_length * net->cfg.temporal_size * 4;
+        if (need != bytes) return ffail(net, GRL_E_SIZE, "grl_fnet_read_rollout: 'histories' needs " + std::to_string(need) + " bytes");
+        return grl_fnet_read_windows(net, 0, (int32_t)TE, (float *)host, bytes);
+    }
     else if (w == "histories") { src = net->ro_hist; need = TE * net->cfg.rnn_length * 8; }
     else if (w == "nhist") { src = net->ro_nhist; need = TE * 4; }
     else return ffail(net, GRL_E_INVALID, "grl_fnet_read_rollout: unknown buffer '" + w + "'");

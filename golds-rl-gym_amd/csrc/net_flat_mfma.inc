@@ -49,6 +49,22 @@ __device__ __forceinline__ void flat_lengths(const FlatArgs &a, int ss, bool val
     }
 }
 
+// the third source beside "dense" and "synthesized": the true window as a strided view of the rollout's state slab (net_flat_window.inc).
+// a.nhist[ss] rows, a.wstride * S0 floats apart, the last one a.states[ss] itself; true_length over the rows as for a dense window
+__device__ __forceinline__ void flat_lengths_win(const FlatArgs &a, int ss, bool valid, const float *&hrow, int &hstep, int &nrows, int &len) {
+    int nh = a.nhist[ss];
+    nh = nh < 1 ? 1 : nh;
+    nrows = nh < a.T ? nh : a.T;
+    hrow = a.states + ((long)ss - (long)(nrows - 1) * a.wstride) * a.S0;
+    hstep = a.wstride * a.S0;
+    len = 0;
+    for (int t = 0; t < nrows; ++t) {
+        float m = 0.f;
+        for (int i = 0; i < a.D; ++i) m = fmaxf(m, fabsf(hrow[(long)t * hstep + i]));
+        len += (valid && m > 0.f) ? 1 : 0;
+    }
+}
+
 // WLDS: the GRU's two kernels ([x,h] -> gates 64, candidate 32: (D+32) x 96 floats, 25 KB at D = 33) are copied to LDS behind the
 // activation rows once per workgroup; the 2 x T MFMA loops of the recurrence then read them with ds_read instead of one
 // global load per MFMA.  The forward is latency bound (SQ counters at 8 192 TradeAR1 envs: 59 % of the wave cycles parked at
@@ -88,8 +104,11 @@ __device__ __forceinline__ void flat_forward_core(const FlatArgs &a, float *lds,
     float *ws = a.ws;
     const float *hrow = nullptr;
     int hstep = 0, nrows = loc.nrows, len = loc.len;
-    const bool synth = loc.staged || a.nhist != nullptr;
-    if (!loc.staged) flat_lengths(a, ss, true, hrow, hstep, nrows, len);
+    const bool synth = loc.staged || (a.nhist != nullptr && a.wstride == 0);
+    if (!loc.staged) {
+        if (a.wstride) flat_lengths_win(a, ss, true, hrow, hstep, nrows, len);
+        else flat_lengths(a, ss, true, hrow, hstep, nrows, len);
+    }
     float *WG = lds + wlds_row0 * LS, *WC = WG + (D + FH) * 2 * FH;
     if (WLDS && !loc.weights_ready) {
         for (int i = tid; i < (D + FH) * 2 * FH; i += 256) WG[i] = P[a.o.gw + i];
@@ -300,7 +319,8 @@ __global__ __launch_bounds__(256, 2) void flat_backward_kernel(FlatArgs a) {
         // ---- GRU, back through time with the sequence-length mask
         const float *hrow;
         int hstep, nrows, len;
-        flat_lengths(a, ss, valid, hrow, hstep, nrows, len);
+        if (a.wstride) flat_lengths_win(a, ss, valid, hrow, hstep, nrows, len);
+        else flat_lengths(a, ss, valid, hrow, hstep, nrows, len);
         for (int t = T - 1; t >= 0; --t) {
             const bool act = t < len;
             __syncthreads();

@@ -51,6 +51,8 @@ struct RolloutArgs {
     int *ts_n;
     int greedy;                 // wave-uniform: raw = mu, nothing is drawn (grl_fnet_set_greedy, grl_fnet_eval(.., greedy))
     EvalOut ev;                 // flat_eval_kernel only (net_flat_eval.inc)
+    int off_wl;                 // true window only (net_flat_window.inc): float offset of the per-env window rows in LDS, and
+    int32_t *wlen;              // (E) the rows the next forward of every env sees, kept between calls
 };
 
 __host__ __device__ inline int rollout_lds_floats(int S0, int steps, int n_assets, RolloutArgs *map) {

@@ -53,6 +53,12 @@ FNET_EVAL_SIGNATURES = {
     "grl_fnet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
 }
 
+# include/goldsrl_flatwindow.h: the true history window (tests/test_flat_window_header.py holds the two together)
+FNET_WINDOW_SIGNATURES = {
+    "grl_fnet_set_true_window": (C.c_int, [_P, _I]),
+    "grl_fnet_read_windows": (C.c_int, [_P, _I, _I, _P, _SZ]),
+}
+
 
 def flat_param_shapes(static_size=2, temporal_size=2, num_actions=1, H=32, S=32):
     """tf.trainable_variables() order of FlatPolicyVNetwork (policy_v_network.py:207-244, a3c/estimators.py:18-28)."""
@@ -85,7 +91,7 @@ def default_init_flat(seed=3, **kw):
 
 class FlatNet(object):
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=dict(FNET_SIGNATURES, **FNET_EVAL_SIGNATURES))
+        self.lib = _ffi.load_library(extra_signatures=dict(FNET_SIGNATURES, **FNET_EVAL_SIGNATURES, **FNET_WINDOW_SIGNATURES))
         self.eng = engine
         cfg = GrlFnetConfig()
         self.lib.grl_fnet_config_default(C.byref(cfg))
@@ -184,8 +190,11 @@ class FlatNet(object):
         self._check(self.lib.grl_fnet_train(self.n, arrs[0].shape[0], *[_ffi._ptr(a) for a in arrs], lr, 1 if apply_update else 0, _ffi._ptr(stats)))
         return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
 
+    _last_T = 0
+
     def rollout(self, T):
         self._check(self.lib.grl_fnet_rollout(self.n, T))
+        self._last_T = int(T)
 
     def set_keep_activations(self, on):
         """The rollouts that follow fill the training workspace; train_rollout on them starts at the backward pass (bit-identical
@@ -195,6 +204,19 @@ class FlatNet(object):
     def set_greedy(self, on):
         """on: rollout draws nothing, raw = mu ("actions" reads back equal to mu); the action counter stands still."""
         self._check(self.lib.grl_fnet_set_greedy(self.n, 1 if on else 0))
+
+    def set_true_window(self, on):
+        """on: rollout, predict_env, eval and train_rollout run the net under the true window -- the last min(k + 1, rnn) states of
+        the env's episode -- instead of the worker's copies of the current state (quirk Q11).  Restarts every window."""
+        self._check(self.lib.grl_fnet_set_true_window(self.n, 1 if on else 0))
+
+    def read_windows(self, first=0, count=None):
+        """Dense (count, rnn, D) true windows of samples [first, first + count) of the last rollout's flattened (T * E) batch."""
+        if count is None:
+            count = self._last_T * self.eng.E - first
+        a = np.empty((count, self.cfg.rnn_length, self.cfg.temporal_size), np.float32)
+        self._check(self.lib.grl_fnet_read_windows(self.n, int(first), int(count), _ffi._ptr(a), a.nbytes))
+        return a
 
     EVAL_TRACE = ("states", "nhist", "mu", "sigma", "raw", "actions", "values", "rewards", "dones")
 

@@ -43,7 +43,7 @@ class PAACLearner(ActorLearner):
                                   seed=int(getattr(self, "seed", 1692)), env_id_offset=ranks.rank * self.emulator_counts)
         self.engine.reset()
         self.network.bind(self.engine, rnn_length=self.rnn_length, gamma=self.gamma,
-                          max_samples=self.emulator_counts * self.max_local_steps)
+                          max_samples=self.emulator_counts * self.max_local_steps, true_window=bool(getattr(self, "true_history", False)))
         net = self.network.net
         if self.resume:
             self.load_checkpoint(self.resume)
@@ -60,7 +60,7 @@ class PAACLearner(ActorLearner):
         self.policy_monitor = DeviceSolowPolicyMonitor(
             "Solow-%d-%d-finite-eval-v0" % (p, q), global_policy_net=self.network, state_processor=self.state_processor,
             summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), learner=self, n_envs=eval_envs, rnn_length=self.rnn_length, device_id=device_id,
-            max_episode_steps=int(getattr(self, "max_episode_steps", 1024)))
+            max_episode_steps=int(getattr(self, "max_episode_steps", 1024)), true_window=bool(getattr(self, "true_history", False)))
         every_updates = int(getattr(self, "eval_updates", 0) or 0)
         every_seconds = float(getattr(self, "eval_every", 0.0) or 0.0)
         state = {"last_eval": time.time()}

@@ -162,10 +162,12 @@ class DeviceSolowPolicyMonitor(_DeviceMonitor):
     rewards) and keeps every env's totals and lengths.  Actions are drawn, a = mu + sigma * N(0,1), as the reference's monitor
     draws them (policy_monitor.py:45-49) -- from the device's action stream at counter 0, so every evaluation plays the same
     episodes with the same noise; greedy=True acts with mu.  The window is the rollout's (the current state repeated, the window
-    the policy is trained under), not the true last-rnn states SolowPolicyMonitor feeds."""
+    the policy is trained under by default), not the true last-rnn states SolowPolicyMonitor feeds -- unless
+    true_window=True: then the evaluation feeds those true last-rnn states of the episode, as SolowPolicyMonitor does (for a
+    policy trained with FlatPolicyVNetwork.bind(true_window=True) / --true-history)."""
 
     def __init__(self, env, global_policy_net, state_processor=None, summary_writer=None, saver=None, network_conf=None, learner=None,
-                 n_envs=1, rnn_length=5, device_id=0, max_episode_steps=1024):
+                 n_envs=1, rnn_length=5, device_id=0, max_episode_steps=1024, true_window=False):
         from ... import _ffi
         if not (env.startswith("Solow-") and env.endswith("-finite-eval-v0")):
             raise ValueError("no device evaluation for env %r (Solow-p-q-finite-eval-v0)" % (env,))
@@ -180,7 +182,8 @@ class DeviceSolowPolicyMonitor(_DeviceMonitor):
         eng = _ffi.Engine(_ffi.ENV_SOLOW, int(n_envs), device_id=device_id, seed=1692, flags=_ffi.F_RESEED_EACH_RESET, solow_p=p, solow_q=q,
                           rnn_length=int(rnn_length), max_episode_steps=int(max_episode_steps))
         conf = network_conf if network_conf is not None else global_policy_net.conf
-        self.policy_net = FlatPolicyVNetwork(conf).bind(eng, rnn_length=int(rnn_length), max_samples=int(n_envs))      # the "policy_eval" copy
+        self.policy_net = FlatPolicyVNetwork(conf).bind(eng, rnn_length=int(rnn_length), max_samples=int(n_envs),
+                                                          true_window=bool(true_window))      # the "policy_eval" copy
         self._adopt(self.policy_net.net, True, summary_writer, max_episode_steps)
 
     def _before_episodes(self):

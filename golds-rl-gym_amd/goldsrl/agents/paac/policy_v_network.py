@@ -65,7 +65,9 @@ class FlatPolicyVNetwork(object):
             raise Exception('Norm type not recognized')
         self.net = None
 
-    def bind(self, engine, rnn_length=5, gamma=0.99, seed=3, max_samples=None):
+    def bind(self, engine, rnn_length=5, gamma=0.99, seed=3, max_samples=None, true_window=False):
+        """true_window: rollout, evaluation and gradient step run the GRU over the true last-rnn_length states of the env's episode
+        (what SolowPolicyMonitor.eval_once feeds) instead of the worker's copies of the current state (quirk Q11)."""
         clip = self.clip_norm if self.clip_norm_type == 'global' else 0.0
         self.net = _ffi_flat.FlatNet(engine, static_size=self.static_size, temporal_size=self.temporal_size, rnn_length=rnn_length,
                                      num_actions=self.num_actions, scale=self.scale, clip_norm=clip, gamma=gamma,
@@ -73,6 +75,8 @@ class FlatPolicyVNetwork(object):
                                      gae_lambda=float(self.conf.get('gae_lambda', 1.0)))     # <1: the A3C worker's GAE targets
         self.net.set_params(_ffi_flat.default_init_flat(seed, static_size=self.static_size, temporal_size=self.temporal_size,
                                                         num_actions=self.num_actions))
+        if true_window:
+            self.net.set_true_window(True)
         return self
 
     def predict(self, states, histories, session=None):

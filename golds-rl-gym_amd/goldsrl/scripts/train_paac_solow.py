@@ -41,6 +41,9 @@ def get_arg_parser():
                         "evaluation; 0: no evaluation")
     p.add_argument('--eval-updates', default=0, type=int, dest="eval_updates",
                    help="evaluate after every K-th update; 0: when --eval-every seconds have passed")
+    p.add_argument('--true-history', action='store_true', dest="true_history",
+                   help="train and evaluate the GRU over the true last --rnn_length states of each env's episode (what the reference's "
+                        "monitor feeds) instead of the worker's copies of the current state (quirk Q11)")
     p.add_argument('--max_episode_steps', default=None, type=int, dest="max_episode_steps",
                    help="TimeLimit of the training and eval envs (the registered ids have 1024)")
     return p

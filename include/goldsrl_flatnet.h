@@ -110,5 +110,6 @@ int grl_fnet_comm_info(grl_fnet *net, int32_t *count_out, int32_t *user_rank_out
 #endif
 
 #include "goldsrl_flateval.h" /* greedy acting and the one-launch evaluation of the same net */
+#include "goldsrl_flatwindow.h" /* the same net under the true history window */
 
 #endif /* GOLDSRL_FLATNET_H */
