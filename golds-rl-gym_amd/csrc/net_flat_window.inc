@@ -1,7 +1,7 @@
 // Included by net_flat.hip (inside namespace grl, after net_flat_eval.inc): the flat PAAC policy under the TRUE history window
 // (grl_fnet_set_true_window, include/goldsrl_flatwindow.h).
 //
-// Window rule (SolowPolicyMonitor.eval_once, fed_gym/agents/paac/policy_monitor.py:84-108; gauss_window_step in net_gauss.hip): the
+// Window rule (SolowPolicyMonitor.eval_once, fed_gym/agents/paac/policy_monitor.py:84-108; a3c_window_step in net_a3c_core.inc): the
 // last L = min(k + 1, rnn) processed states of the env's current episode, oldest first, the current state last, zero rows behind;
 // k = steps since the episode's reset.  The worker's window (quirk Q11, emulator_runner.py:48-63) is L copies of the current state.
 //

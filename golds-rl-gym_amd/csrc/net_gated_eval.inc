@@ -9,7 +9,7 @@
 // grid-wide barrier and no residency requirement.
 //
 // Nothing here restates arithmetic: the forward is gated_trunk / gated_tower_fwd / softmax3, the action gated_greedy_pick, the env
-// step ticker_step_env (ticker_dev.h), the window gated_window_restart / gated_window_step -- the functions the per-step rollout
+// step ticker_step_env (ticker_dev.h), the window a3c_window_restart / a3c_window_step -- the functions the per-step rollout
 // path runs, so the two agree bit for bit.  The per-step forward is a function of its own (gated_eval_forward, not inlined), for
 // the schedule of its GEMM loops; the kernel's 520 B of scratch per lane are that call's argument block (DESIGN section 3).
 //
@@ -29,14 +29,14 @@ struct GEvalArgs {
 };
 
 // probs (6) and mu (6) where the forward kernel keeps them; sigma's 6 rows stay unused
-constexpr int GL_EV_PR = GL_HEAD, GL_EV_MU = GL_HEAD + 6, GL_EV_CH = GL_HEAD + 18, GL_EV_FR = GL_HEAD + 20, GL_EV_LIVE = GL_HEAD + 22;
-static_assert(GL_EV_LIVE < GL_HEAD + GX, "the eval rows overflow the dL/dx rows");
+constexpr int L_EV_PR = L_HEAD, L_EV_MU = L_HEAD + 6, L_EV_CH = L_HEAD + 18, L_EV_FR = L_HEAD + 20, L_EV_LIVE = L_HEAD + 22;
+static_assert(L_EV_LIVE < L_HEAD + NX, "the eval rows overflow the dL/dx rows");
 
 // One step's forward for the group at sbase: probs and mu into their LDS rows.  Not inlined: inside the kernel's loop over steps the
 // compiler schedules the GEMM k-loops for the fewest registers (one weight load in flight); as a function of its own they get the
 // forward kernel's schedule (DESIGN section 3).
 __device__ __noinline__ void gated_eval_forward(const GArgs &a, float *lds, int sbase) {
-    float *O = lds + GL_O * LS, *PR = lds + GL_EV_PR * LS, *MU = lds + GL_EV_MU * LS;
+    float *O = lds + L_O * LS, *PR = lds + L_EV_PR * LS, *MU = lds + L_EV_MU * LS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     gated_trunk(a, lds, sbase, nullptr);
     gated_tower_fwd(a, lds, 0);
@@ -53,9 +53,9 @@ __device__ __noinline__ void gated_eval_forward(const GArgs &a, float *lds, int 
 
 __global__ __launch_bounds__(256, 1) void gated_eval_kernel(GEvalArgs v, TickerParams K) {
     extern __shared__ float lds[];
-    float *PR = lds + GL_EV_PR * LS, *MU = lds + GL_EV_MU * LS, *FR = lds + GL_EV_FR * LS;
-    int *CH = reinterpret_cast<int *>(lds + GL_EV_CH * LS);
-    int *live = reinterpret_cast<int *>(lds + GL_EV_LIVE * LS);
+    float *PR = lds + L_EV_PR * LS, *MU = lds + L_EV_MU * LS, *FR = lds + L_EV_FR * LS;
+    int *CH = reinterpret_cast<int *>(lds + L_EV_CH * LS);
+    int *live = reinterpret_cast<int *>(lds + L_EV_LIVE * LS);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sbase = blockIdx.x * 64, s = sbase + lane, n = v.a.n, R = v.a.R;
     const bool mine = wave == 0 && s < n;            // this lane steps env s
@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256, 1) void gated_eval_kernel(GEvalArgs v, TickerP
     bool active = mine;
     double total = 0.0;
     int len = 0, k = 0;
-    if (mine) gated_window_restart(w, R, obs);       // every env's window starts at its current observation
+    constexpr GD_t D{};      // the row width as a constant inside the window rules: this kernel's code as tuned
+    if (mine) a3c_window_restart(w, R, D, obs + GTOFF);      // every env's window starts at its current observation
     __syncthreads();
 #pragma unroll 1
     for (int step = 0; step < v.max_steps; ++step) {
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256, 1) void gated_eval_kernel(GEvalArgs v, TickerP
                 const TickerStepOut o = ticker_step_env(K, s, act);
                 total += (double)o.reward;
                 ++len;
-                k = gated_window_step(w, R, k, o.done, obs);
+                k = a3c_window_step(w, R, D, k, o.done, obs + GTOFF);
                 if (tr) {
                     v.tr_rew[row] = o.reward;
                     v.tr_done[row] = o.done ? 1.0f : 0.0f;

@@ -6,8 +6,8 @@
 // optional trace; then a barrier and the next step.  An env that is done masks its lane; the workgroup leaves when none of its envs
 // is still playing, or after max_steps.  Workgroups share nothing, so there is no grid-wide barrier and no residency requirement.
 //
-// Nothing here restates arithmetic: the forward is gauss_trunk / gauss_tower_fwd / gauss_mu, the action gauss_env_action, the env
-// step solow_step_env / trade_step_env (flat_env_dev.h), the window gauss_window_restart / gauss_window_step -- the functions the
+// Nothing here restates arithmetic: the forward is a3c_trunk / gauss_tower_fwd / gauss_mu, the action gauss_env_action, the env
+// step solow_step_env / trade_step_env (flat_env_dev.h), the window a3c_window_restart / a3c_window_step -- the functions the
 // per-step rollout path runs, so the two agree bit for bit.  The trunk and the tower are the forward kernel's instantiations
 // (LOOP = false: tile loops unrolled): with the backward's (LOOP = true) a GRU step took 12.2 us against 8.0, and TradeAR1's 20 of
 // them put the evaluation above the per-step rollout (DESIGN section 3).  0 B of scratch either way.
@@ -36,16 +36,16 @@ __device__ __forceinline__ void gauss_eval_env_step(const TradeParams &S, int en
     reward = o.reward; done = o.done;
 }
 
-constexpr int AL_EV_MU = AL_HEAD, AL_EV_ACT = AL_HEAD + AMAXA, AL_EV_LIVE = AL_HEAD + 2 * AMAXA;
-static_assert(AL_EV_LIVE < AL_HEAD + AX, "the eval rows overflow the dL/dx rows");
+constexpr int L_EV_MU = L_HEAD, L_EV_ACT = L_HEAD + AMAXA, L_EV_LIVE = L_HEAD + 2 * AMAXA;
+static_assert(L_EV_LIVE < L_HEAD + NX, "the eval rows overflow the dL/dx rows");
 
 template <int D, typename ENV>
 __global__ __launch_bounds__(256, 1) void gauss_eval_kernel(AEvalArgs v, ENV S) {
     constexpr int A = D == 2 ? 1 : 2;      // Solow: 1 action, TradeAR1 with 2 assets: 2
     extern __shared__ float lds[];
-    float *O = lds + AL_O * LS, *MU = lds + AL_EV_MU * LS, *ACT = lds + AL_EV_ACT * LS;
-    int *live = reinterpret_cast<int *>(lds + AL_EV_LIVE * LS);
-    const int tid = gauss_tid(), lane = tid & 63, wave = gauss_wave(tid);
+    float *O = lds + L_O * LS, *MU = lds + L_EV_MU * LS, *ACT = lds + L_EV_ACT * LS;
+    int *live = reinterpret_cast<int *>(lds + L_EV_LIVE * LS);
+    const int tid = a3c_tid(), lane = tid & 63, wave = a3c_wave(tid);
     const int sbase = blockIdx.x * 64, s = sbase + lane, n = v.a.n, R = v.a.R;
     const bool mine = wave == 0 && s < n;            // this lane steps env s
     const int ss = s < n ? s : n - 1;                // lanes past n stay inside their own group's rows
@@ -55,11 +55,11 @@ __global__ __launch_bounds__(256, 1) void gauss_eval_kernel(AEvalArgs v, ENV S) 
     bool active = mine;
     double total = 0.0;
     int len = 0, k = 0;
-    if (mine) gauss_window_restart(w, R, D, obs);      // history = [state] (policy_monitor.py:63-65)
+    if (mine) a3c_window_restart(w, R, D, obs);      // history = [state] (policy_monitor.py:63-65)
     __syncthreads();
 #pragma unroll 1
     for (int step = 0; step < v.max_steps; ++step) {
-        gauss_trunk<D, false>(v.a, lds, sbase, nullptr);
+        a3c_trunk<D, D, false>(v.a, lds, sbase, nullptr);
         gauss_tower_fwd<D, false>(v.a, lds, 0);
         if (wave < A) {
             const float m = gauss_mu(O[wave * LS + lane]);
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256, 1) void gauss_eval_kernel(AEvalArgs v, ENV S) 
                 gauss_eval_env_step(S, s, ea, reward, done);
                 total += (double)reward;              // total_reward += reward (policy_monitor.py:80)
                 ++len;
-                k = gauss_window_step(w, R, D, k, done, obs);
+                k = a3c_window_step(w, R, D, k, done, obs);
                 if (tr) {
                     v.tr_rew[row] = reward;
                     v.tr_done[row] = done ? 1.0f : 0.0f;
