@@ -7,7 +7,6 @@
 // ~12k instead of 2.46M multiply-adds -- by one workgroup per env that stages the 84x84 count
 // grids in LDS, builds the pre-activation shared by the env's 10 agents once, and adds each
 // agent's one-hot tap.  conv2/conv3/dense layers are fp32-MFMA implicit GEMMs (net_gemm.h).
-#include <rccl/rccl.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -19,6 +18,7 @@
 #include "../../include/goldsrl_net.h"
 #include "common.h"
 #include "net_gemm.h"
+#include "net_paac_host.h"
 #include "net_reduce.inc"
 #include "rng.h"
 
@@ -131,14 +131,10 @@ struct NetLane {
     bool train_ready;
 };
 
-struct grl_net : NetLane {
-    grl_handle *h;
+struct grl_net : NetLane, grl::PaacCommNet {      // stats: [8..9] loss scale S and 1/S, [10] bits of the head-gradient bound, [12] the range latch
     grl_net_config cfg;
-    std::string err;
     int chunk;                 // samples per pass
-    float *params, *adam_m, *adam_v;
     float *paramsT;            // W^T of every GEMM layer at the same flat offsets ([N][K]: the forward's Bt operand)
-    long adam_t;
     float *w3t, *w2t;          // rearranged conv weights for the data gradients
     float *w3f;                // w3f[(tap,co)][ci] = W3[tap][ci][co] (slot product GEMM of conv3's forward)
     float *wpvT;               // [pol1_w | v1_w] transposed side by side: (1024, 256), the B operand of the one GEMM that computes both from d2
@@ -170,7 +166,6 @@ struct grl_net : NetLane {
     size_t slab_floats, slab_used, slabb_floats, slabb_used;      // bump allocation of a chunk's partial-sum regions (net_train.inc)
     std::vector<grl::RJob> rq;      // the chunk's queued reductions (net_reduce.inc)
     std::vector<int> rq_dst;
-    float *stats;              // device: [0..4] loss parts / norm / clip factor, [8..9] loss scale S and 1/S, [10] bits of the head-gradient bound
     // rollout storage (allocated by grl_net_rollout)
     int T, B;
     uint8_t *ro_lb, *ro_ab, *ro_pos, *ro_done;      // ro_done (T,E): episode_over after each step (R6 / tests; the grid return ignores it, Q5)
@@ -178,8 +173,6 @@ struct grl_net : NetLane {
     float *mu, *sigma, *vs;    // (B,2) (B,2) (B) of the last predict
     uint8_t *tmp_lb, *tmp_ab, *tmp_pos;
     int tmp_envs;
-    unsigned long act_counter;
-    std::vector<void *> allocs;
     bool prof_on;
     std::vector<hipEvent_t> prof_ev;
     std::vector<unsigned char> prof_tag;     // GRL_PROF_TAG_* of every bracketed launch
@@ -188,17 +181,10 @@ struct grl_net : NetLane {
     size_t prof_used;
     double prof_flops;
     int last_n;                // samples in the last chunk (for read_activation)
-    void *comm;                // ncclComm_t (RCCL) for the per-rollout gradient all-reduce, or nullptr
-    int comm_world, comm_rank;
-    hipEvent_t ar_ev0, ar_ev1; // bracket the all-reduce on the handle's stream (grl_net_comm_info)
-    int ar_pending;
-    long ar_calls;
     // host clocks of the actor loop (grl_net_host_times)
     long ht_rollouts, ht_updates;
     double ht_rollout_ms, ht_train_enq_ms, ht_train_wait_ms;
     double ht_train_t0;      // steady-clock ms at the entry of the gradient step in flight (0: none)
-    double ar_ms_total;
-    float ar_ms_last;
     // Rollout-resident activations: the rollout's forward pass writes its activations of every (step, chunk) into one
     // T*B-sample buffer (what 288 GB of HBM is for) and the gradient step reads them back instead of recomputing the
     // forward pass.  Exact: parameters do not change between the two (paac.py:302-387).  keep_version tracks that;
@@ -231,27 +217,6 @@ struct grl_net : NetLane {
 
 namespace grl {
 
-static int nfail(grl_net *n, int code, const std::string &msg) {
-    if (n) n->err = msg;
-    return code;
-}
-#define NET_HIP(n, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t _e = (call);                                                                            \
-        if (_e != hipSuccess) return nfail(n, GRL_E_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-template <typename T>
-static int nalloc(grl_net *n, T **p, size_t count) {
-    NET_HIP(n, hipMalloc((void **)p, count * sizeof(T)));
-    n->allocs.push_back(*p);
-    NET_HIP(n, hipMemsetAsync(*p, 0, count * sizeof(T), n->h->stream));
-    // allocations happen on whichever lane is current (a non-blocking stream) while other streams may be the first to touch the
-    // buffer (w2t / w3t are written on the main stream): finish the fill before anyone can see the pointer
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
-    return GRL_OK;
-}
-
 // ---- lanes: swap the per-stream workspace (and the stream kernels are enqueued on) between chunk enqueues
 static void use_lane(grl_net *net, int k) {
     if (k == net->cur_lane) return;
@@ -265,8 +230,8 @@ static int lanes_active(const grl_net *net) { return net->prof_on ? 1 : net->nla
 static int lanes_fork(grl_net *net) {
     if (lanes_active(net) < 2) return GRL_OK;
     use_lane(net, 0);
-    NET_HIP(net, hipEventRecord(net->ev_fork, net->lane_stream[0]));
-    for (int k = 1; k < net->nlanes; ++k) NET_HIP(net, hipStreamWaitEvent(net->lane_stream[k], net->ev_fork, 0));
+    PAAC_HIP(net, hipEventRecord(net->ev_fork, net->lane_stream[0]));
+    for (int k = 1; k < net->nlanes; ++k) PAAC_HIP(net, hipStreamWaitEvent(net->lane_stream[k], net->ev_fork, 0));
     return GRL_OK;
 }
 // the main stream sees everything enqueued on lane 1; lane 0 becomes current again
@@ -274,8 +239,8 @@ static int lanes_join(grl_net *net) {
     use_lane(net, 0);
     if (lanes_active(net) < 2) return GRL_OK;
     for (int k = 1; k < net->nlanes; ++k) {
-        NET_HIP(net, hipEventRecord(net->ev_join[k], net->lane_stream[k]));
-        NET_HIP(net, hipStreamWaitEvent(net->lane_stream[0], net->ev_join[k], 0));
+        PAAC_HIP(net, hipEventRecord(net->ev_join[k], net->lane_stream[k]));
+        PAAC_HIP(net, hipStreamWaitEvent(net->lane_stream[0], net->ev_join[k], 0));
     }
     return GRL_OK;
 }
@@ -844,7 +809,7 @@ static int forward_chunk(grl_net *net, const uint8_t *lb, const uint8_t *ab, con
     if (!skip_heads)      // (the gradient step over a resident rollout has the heads' outputs of every step already)
     GRL_HEADS_DISPATCH(net->ho.A, hipLaunchKernelGGL(heads_forward_kernel<kA>, dim3((n + 4 * kHeadRows - 1) / (4 * kHeadRows)), dim3(256), 0, st, net->p1, net->v2, P, net->ho, n,
                                                       net->cfg.scale, mu, sigma, vs));
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -871,7 +836,7 @@ static int forward_all(grl_net *net, const uint8_t *lb, const uint8_t *ab, const
 static int alloc_lane_forward(grl_net *n) {
     const size_t c = n->chunk;
     int rc = GRL_OK;
-    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = nalloc(n, p, cnt); };
+    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };
     A(&n->grads, n->ho.total);
     // a2: the per-agent conv2 tensor of the dense form; in shared-trunk mode the workspace of conv3's gather form (net_patch.inc:
     // canonical cell blocks of ctiles * 256 rows, then the items' descriptors, tap masks, tile masks and sort counters)
@@ -879,70 +844,70 @@ static int alloc_lane_forward(grl_net *n) {
     A(&n->a2, std::max(c * 5184, gather_ws)); A(&n->d1, c * 512); A(&n->d2, c * 256); A(&n->p1, c * 512); A(&n->v1, c * 512); A(&n->v2, c * 256);
     if (!n->shared_trunk) { A(&n->a1, c * 12800); A(&n->a3, c * 3136); }       // per-agent tensors the shared evaluation never forms
     A(&n->sraw, (c / 10) * 12800); A(&n->z2sh, (c / 10) * 5184);
-    A(&n->a2sh, (c / 10) * 5184); A(&n->d2s, c * 9 * 64); if (rc == GRL_OK) rc = nalloc(n, &n->m2s, c * 9); A(&n->z3sh, (c / 10) * 3136);
-    if (rc == GRL_OK) rc = nalloc(n, &n->ulist, c * 9);
-    A(&n->a3sh, (c / 10) * 3136); A(&n->d3, c * 1600); if (rc == GRL_OK) rc = nalloc(n, &n->m3, c * 25); A(&n->ysh, (c / 10) * 512);
+    A(&n->a2sh, (c / 10) * 5184); A(&n->d2s, c * 9 * 64); if (rc == GRL_OK) rc = paac_alloc(n, &n->m2s, c * 9); A(&n->z3sh, (c / 10) * 3136);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->ulist, c * 9);
+    A(&n->a3sh, (c / 10) * 3136); A(&n->d3, c * 1600); if (rc == GRL_OK) rc = paac_alloc(n, &n->m3, c * 25); A(&n->ysh, (c / 10) * 512);
     n->ws_a3 = n->a3; n->ws_d1 = n->d1; n->ws_d2 = n->d2; n->ws_p1 = n->p1; n->ws_v1 = n->v1; n->ws_v2 = n->v2;
     n->ws_a3sh = n->a3sh; n->ws_d3 = n->d3; n->ws_m3 = n->m3;
-    if (rc == GRL_OK) rc = nalloc(n, &n->ws_mb, c * 12);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->ws_mb, c * 12);
     n->mb_d2 = n->ws_mb; n->mb_v1 = n->ws_mb + c * 4;
     n->ws_sraw = n->sraw; n->ws_a2sh = n->a2sh; n->ws_d2s = n->d2s; n->ws_m2s = n->m2s; n->ws_ulist = n->ulist;
-    if (rc == GRL_OK) rc = nalloc(n, &n->perm, (size_t)n->ptiles * 256);
-    if (rc == GRL_OK) rc = nalloc(n, &n->goffp, 32);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sbeg, n->pslices);
-    if (rc == GRL_OK) rc = nalloc(n, &n->send, n->pslices);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sgrp, n->pslices);
-    if (rc == GRL_OK) rc = nalloc(n, &n->blkcnt, ((c + 255) / 256) * PATCH_KEYS);
-    if (rc == GRL_OK) rc = nalloc(n, &n->blkoff, ((c + 255) / 256) * PATCH_KEYS);
-    if (rc == GRL_OK) rc = nalloc(n, &n->binbase, PATCH_KEYS);
-    if (rc == GRL_OK) rc = nalloc(n, &n->pkey, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->prank, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->smask, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tmask, (size_t)n->ptiles * 2 + 2);
-    if (rc == GRL_OK) rc = nalloc(n, &n->zmask, (size_t)n->pslices);
-    if (rc == GRL_OK) rc = nalloc(n, &n->wmask, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->slot_of, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tilegroup, (size_t)n->ptiles);
-    if (rc == GRL_OK) rc = nalloc(n, &n->org, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sbase, c + 1);
-    if (rc == GRL_OK) rc = nalloc(n, &n->rowagent, c * 9);
-    if (rc == GRL_OK) rc = nalloc(n, &n->rowdesc, c * 9);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sblk, 1024);
-    if (rc == GRL_OK) rc = nalloc(n, &n->skey, c * 9);
-    if (rc == GRL_OK) rc = nalloc(n, &n->srank, c * 9);
-    if (rc == GRL_OK) rc = nalloc(n, &n->stap, c * 9);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sblkcnt, ((c * 9 + 1023) / 1024 + 1) * 25);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sblkoff, ((c * 9 + 1023) / 1024 + 1) * 25);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sbinbase, 32);
-    if (rc == GRL_OK) rc = nalloc(n, &n->sperm, c * 9 + 256);
-    if (rc == GRL_OK) rc = nalloc(n, &n->stmask, (c * 9 + 255) / 256 + 1);
-    if (rc == GRL_OK) rc = nalloc(n, &n->szmask, 1024);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tamask, (c / 10) * 3 + 3);
-    if (rc == GRL_OK) rc = nalloc(n, &n->obsrec, (c / 10 + 1) * kObsWords);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tbmask, (c / 10) * 4 + 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tcmask, (c / 10) * 2 + 2);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tnmask, (c / 10) * 4 + 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->trowlist, (c / 10) * 81 + 256);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tblklist, (c / 10) * 100 + 256);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tc3list, (c / 10) * 49 + 256);
-    if (rc == GRL_OK) rc = nalloc(n, &n->trows_n, 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->twgcnt, ((c / 10 + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3);
-    if (rc == GRL_OK) rc = nalloc(n, &n->twgoff, ((c / 10 + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tumask, 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tneed2, 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tubias, 512);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tug, 512);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tuspix, 49 * 64);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tslab, 2 * 2048 * 64);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tsums, 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->perm, (size_t)n->ptiles * 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->goffp, 32);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sbeg, n->pslices);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->send, n->pslices);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sgrp, n->pslices);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->blkcnt, ((c + 255) / 256) * PATCH_KEYS);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->blkoff, ((c + 255) / 256) * PATCH_KEYS);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->binbase, PATCH_KEYS);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->pkey, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->prank, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->smask, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tmask, (size_t)n->ptiles * 2 + 2);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->zmask, (size_t)n->pslices);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->wmask, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->slot_of, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tilegroup, (size_t)n->ptiles);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->org, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sbase, c + 1);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->rowagent, c * 9);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->rowdesc, c * 9);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sblk, 1024);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->skey, c * 9);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->srank, c * 9);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->stap, c * 9);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sblkcnt, ((c * 9 + 1023) / 1024 + 1) * 25);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sblkoff, ((c * 9 + 1023) / 1024 + 1) * 25);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sbinbase, 32);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->sperm, c * 9 + 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->stmask, (c * 9 + 255) / 256 + 1);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->szmask, 1024);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tamask, (c / 10) * 3 + 3);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->obsrec, (c / 10 + 1) * kObsWords);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tbmask, (c / 10) * 4 + 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tcmask, (c / 10) * 2 + 2);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tnmask, (c / 10) * 4 + 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->trowlist, (c / 10) * 81 + 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tblklist, (c / 10) * 100 + 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tc3list, (c / 10) * 49 + 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->trows_n, 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->twgcnt, ((c / 10 + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->twgoff, ((c / 10 + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tumask, 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tneed2, 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tubias, 512);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tug, 512);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tuspix, 49 * 64);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tslab, 2 * 2048 * 64);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tsums, 256);
     A(&n->carow, c * 128);
-    if (rc == GRL_OK) rc = nalloc(n, &n->cperm, (size_t)n->ctiles * 256);
-    if (rc == GRL_OK) rc = nalloc(n, &n->cblkcnt, ((c + 255) / 256) * 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->cblkoff, ((c + 255) / 256) * 4);
-    if (rc == GRL_OK) rc = nalloc(n, &n->cgoff, 8);
-    if (rc == GRL_OK) rc = nalloc(n, &n->cslot, c * 9);
-    if (rc == GRL_OK) rc = nalloc(n, &n->cinv, c);
-    if (rc == GRL_OK) rc = nalloc(n, &n->ctilegroup, (size_t)n->ctiles);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->cperm, (size_t)n->ctiles * 256);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->cblkcnt, ((c + 255) / 256) * 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->cblkoff, ((c + 255) / 256) * 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->cgoff, 8);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->cslot, c * 9);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->cinv, c);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->ctilegroup, (size_t)n->ctiles);
     if (rc == GRL_OK) {
         grl_net *net = n;
         int k = 0;
@@ -957,13 +922,13 @@ static int alloc_lane_forward(grl_net *n) {
 static int ensure_tmp_obs(grl_net *net, int n_envs) {
     if (net->tmp_envs >= n_envs) return GRL_OK;
     int rc;
-    if ((rc = nalloc(net, &net->tmp_lb, (size_t)n_envs * 160))) return rc;
-    if ((rc = nalloc(net, &net->tmp_ab, (size_t)n_envs * 20))) return rc;
-    if ((rc = nalloc(net, &net->tmp_pos, (size_t)n_envs * 20))) return rc;
+    if ((rc = paac_alloc(net, &net->tmp_lb, (size_t)n_envs * 160))) return rc;
+    if ((rc = paac_alloc(net, &net->tmp_ab, (size_t)n_envs * 20))) return rc;
+    if ((rc = paac_alloc(net, &net->tmp_pos, (size_t)n_envs * 20))) return rc;
     float *m, *s, *v;
-    if ((rc = nalloc(net, &m, (size_t)n_envs * 10 * net->ho.A))) return rc;
-    if ((rc = nalloc(net, &s, (size_t)n_envs * 10 * net->ho.A))) return rc;
-    if ((rc = nalloc(net, &v, (size_t)n_envs * 10))) return rc;
+    if ((rc = paac_alloc(net, &m, (size_t)n_envs * 10 * net->ho.A))) return rc;
+    if ((rc = paac_alloc(net, &s, (size_t)n_envs * 10 * net->ho.A))) return rc;
+    if ((rc = paac_alloc(net, &v, (size_t)n_envs * 10))) return rc;
     net->mu = m; net->sigma = s; net->vs = v;
     net->tmp_envs = n_envs;
     return GRL_OK;
@@ -1055,13 +1020,13 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
     }
     hipSetDevice(h->cfg.device_id);
     grl_net *n = new grl_net();
-    n->h = h; n->cfg = *cfg; n->chunk = cfg->max_chunk_samples; n->adam_t = 0;
-    n->ho = head_offsets(cfg->num_actions);
-    n->T = 0; n->B = 0; n->tmp_envs = 0; n->act_counter = 0; n->prof_on = false; n->prof_used = 0; n->prof_flops = 0; n->last_n = 0; n->prof_tag_cur = 0;
+    n->h = h; n->cfg = *cfg; n->chunk = cfg->max_chunk_samples; n->alloc_waits = true;
+    n->ho = head_offsets(cfg->num_actions); n->num_params = n->ho.total;
+    n->T = 0; n->B = 0; n->tmp_envs = 0; n->prof_on = false; n->prof_used = 0; n->prof_flops = 0; n->last_n = 0; n->prof_tag_cur = 0;
     n->ro_lb = nullptr; n->slab_floats = 0; n->slab_used = 0; n->slabb_floats = 0; n->slabb_used = 0; n->w3t = n->w2t = nullptr;
     n->mu = n->sigma = n->vs = nullptr;
     n->keep_level = 0;
-    n->ar_ev0 = n->ar_ev1 = nullptr; n->ar_pending = 0; n->ar_calls = 0; n->ht_rollouts = n->ht_updates = 0; n->ht_rollout_ms = n->ht_train_enq_ms = n->ht_train_wait_ms = 0.0; n->ht_train_t0 = 0.0; n->ar_ms_total = 0.0; n->ar_ms_last = 0.f;
+    n->ht_rollouts = n->ht_updates = 0; n->ht_rollout_ms = n->ht_train_enq_ms = n->ht_train_wait_ms = 0.0; n->ht_train_t0 = 0.0;
     n->keep = nullptr; n->keep_slots = 0; n->param_version = 0; n->keep_version = -1;
     n->keep_max_level = 3; n->keep_free_capped = false; n->keep_free_cap = 0; n->keep_headroom = 0; n->keep_free_seen = 0;
     n->resident_last = 0;
@@ -1118,11 +1083,11 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
     n->pslices = (int)((c + n->pslice_rows - 1) / n->pslice_rows) + 9;
     n->npad = (int)((c + 255) / 256 * 256);
     int rc = GRL_OK;
-    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = nalloc(n, p, cnt); };
+    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };
     A(&n->params, n->ho.total); A(&n->paramsT, n->ho.total); A(&n->adam_m, n->ho.total); A(&n->adam_v, n->ho.total);
     A(&n->w3f, 576 * 64); A(&n->stats, 16); A(&n->wpvT, (size_t)1024 * 256); A(&n->w2corr, 4 * 576 * 128);
     A(&n->tbgimg, 12800); A(&n->tbgz, 128); A(&n->tbgimg3, 5184); A(&n->tbgz3, 128); A(&n->tybg, 49 * 512);
-    if (rc == GRL_OK) rc = nalloc(n, &n->tbglist, 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->tbglist, 4);
     int nlanes = (cfg->reserved & GRL_NET_F_SINGLE_STREAM) ? 1 : 4;      // measured at 32 768 envs: 1.41 / 1.22 / 1.16 / 1.13 / 1.14 s per update with 1 / 2 / 3 / 4 / 8
     if (const char *env = getenv("GRL_NET_LANES")) { int v = atoi(env); if (v >= 1 && v <= GRL_MAX_LANES) nlanes = v; }      // tuning knob
     for (int k = 0; k < nlanes && rc == GRL_OK; ++k) {       // lane k's forward workspace (allocated into *n, then parked)
@@ -1136,7 +1101,7 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
         for (int k = 1; k < nlanes && ok; ++k)
             ok = hipStreamCreateWithFlags(&n->lane_stream[k], hipStreamNonBlocking) == hipSuccess &&
                  hipEventCreateWithFlags(&n->ev_join[k], hipEventDisableTiming) == hipSuccess;
-        if (!ok) rc = nfail(n, GRL_E_HIP, "creating the lane streams/events failed");
+        if (!ok) rc = paac_fail(n, GRL_E_HIP, "creating the lane streams/events failed");
     }
     if (rc == GRL_OK) n->nlanes = nlanes;
     // The index side stream of lane 0 (used by a rollout with ONE chunk per step: grl_net_rollout; not in the single-stream profiling
@@ -1160,7 +1125,7 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
     }
     if (rc == GRL_OK && hipFuncSetAttribute((const void *)expand_conv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)EXP2_LDS_BYTES) != hipSuccess)
-        rc = nfail(n, GRL_E_HIP, "hipFuncSetAttribute(expand_conv2_kernel)");
+        rc = paac_fail(n, GRL_E_HIP, "hipFuncSetAttribute(expand_conv2_kernel)");
     if (rc == GRL_OK) rc = ensure_tmp_obs(n, h->E);
     if (rc == GRL_OK) rc = range_flag_init(n);
     if (rc != GRL_OK) {
@@ -1177,10 +1142,7 @@ int grl_net_destroy(grl_net *n) {
     if (!n) return GRL_OK;
     const bool alive = grl_handle_alive(n->h);      // the handle may have been destroyed first (finaliser order of a host binding)
     grl_sync_for_destroy(n->h);
-    if (n->comm) {
-        ncclCommDestroy((ncclComm_t)n->comm);
-        (void)hipGetLastError();   // RCCL teardown may leave a stale HIP error on this thread
-    }
+    paac_comm_release(n);
     if (alive) use_lane(n, 0);      // restores the handle's stream
     for (int k = 1; k < GRL_MAX_LANES; ++k) {
         if (n->lane_stream[k]) { hipStreamSynchronize(n->lane_stream[k]); hipStreamDestroy(n->lane_stream[k]); }
@@ -1193,57 +1155,36 @@ int grl_net_destroy(grl_net *n) {
         if (n->ev_side2[k]) hipEventDestroy(n->ev_side2[k]);
     }
     if (n->ev_fork) hipEventDestroy(n->ev_fork);
-    if (n->ar_ev0) { hipEventDestroy(n->ar_ev0); hipEventDestroy(n->ar_ev1); }
-    for (void *p : n->allocs) hipFree(p);
+    paac_free(n);
     if (n->keep) hipFree(n->keep);
     for (hipEvent_t ev : n->prof_ev) hipEventDestroy(ev);
     delete n;
     return GRL_OK;
 }
 
-const char *grl_net_last_error(const grl_net *n) { return n ? n->err.c_str() : ""; }
-int64_t grl_net_num_params(const grl_net *n) { return n ? n->ho.total : 0; }
+const char *grl_net_last_error(const grl_net *n) { return paac_last_error(n); }
+int64_t grl_net_num_params(const grl_net *n) { return paac_num_params(n); }
 
-int grl_net_set_params(grl_net *n, const float *host, int64_t cnt) {
-    if (!n || !host) return GRL_E_INVALID;
-    if (cnt != n->ho.total) return nfail(n, GRL_E_SIZE, "grl_net_set_params: expected " + std::to_string((long)n->ho.total) + " floats");
-    hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
-    NET_HIP(n, hipMemcpy(n->params, host, cnt * 4, hipMemcpyHostToDevice));
+// after the parameters moved: the kept activations and the transposes are the old ones'
+static int params_moved(grl_net *n) {
     n->param_version += 1;
     refresh_transposes(n);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     return GRL_OK;
 }
 
-static int get_flat(grl_net *n, const float *src, float *host, int64_t cnt) {
-    if (!n || !host) return GRL_E_INVALID;
-    if (cnt != n->ho.total) return nfail(n, GRL_E_SIZE, "expected " + std::to_string((long)n->ho.total) + " floats");
-    hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
-    NET_HIP(n, hipMemcpy(host, src, cnt * 4, hipMemcpyDeviceToHost));
-    return GRL_OK;
+int grl_net_set_params(grl_net *n, const float *host, int64_t cnt) {
+    int rc = paac_copy_flat(n, "grl_net_set_params", n ? n->params : nullptr, (float *)host, cnt, true);
+    return rc ? rc : params_moved(n);
 }
-int grl_net_get_params(grl_net *n, float *host, int64_t cnt) { return get_flat(n, n ? n->params : nullptr, host, cnt); }
-int grl_net_get_grads(grl_net *n, float *host, int64_t cnt) { return get_flat(n, n ? n->grads : nullptr, host, cnt); }
+int grl_net_get_params(grl_net *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->params : nullptr, host, cnt, false); }
+int grl_net_get_grads(grl_net *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->grads : nullptr, host, cnt, false); }
 
 int grl_net_get_optimizer_state(grl_net *n, float *m_host, float *v_host, int64_t cnt, int64_t *step_out) {
-    if (!n || !m_host || !v_host || !step_out) return GRL_E_INVALID;
-    int rc = get_flat(n, n->adam_m, m_host, cnt);
-    if (rc == GRL_OK) rc = get_flat(n, n->adam_v, v_host, cnt);
-    *step_out = n->adam_t;
-    return rc;
+    return paac_get_optimizer_state(n, m_host, v_host, cnt, step_out);
 }
-
 int grl_net_set_optimizer_state(grl_net *n, const float *m_host, const float *v_host, int64_t cnt, int64_t step) {
-    if (!n || !m_host || !v_host || step < 0) return GRL_E_INVALID;
-    if (cnt != n->ho.total) return nfail(n, GRL_E_SIZE, "grl_net_set_optimizer_state: expected " + std::to_string((long)n->ho.total) + " floats");
-    hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
-    NET_HIP(n, hipMemcpy(n->adam_m, m_host, cnt * 4, hipMemcpyHostToDevice));
-    NET_HIP(n, hipMemcpy(n->adam_v, v_host, cnt * 4, hipMemcpyHostToDevice));
-    n->adam_t = (long)step;
-    return GRL_OK;
+    return paac_set_optimizer_state(n, "grl_net_set_optimizer_state", m_host, v_host, cnt, step);
 }
 
 // After a synchronisation point: did any GEMM output of the work just finished leave the fp16 range (net_gemm.h: g_gemm_range_flag)?
@@ -1254,15 +1195,15 @@ constexpr int kMaxDevices = 64;
 static int *g_range_flag_dev[kMaxDevices] = {};
 static int range_flag_init(grl_net *n) {
     const int dev = n->h->cfg.device_id;
-    if (dev < 0 || dev >= kMaxDevices) return nfail(n, GRL_E_INVALID, "device ordinal beyond 63");
+    if (dev < 0 || dev >= kMaxDevices) return paac_fail(n, GRL_E_INVALID, "device ordinal beyond 63");
     if (g_range_flag_dev[dev]) return GRL_OK;
-    NET_HIP(n, hipSetDevice(dev));
+    PAAC_HIP(n, hipSetDevice(dev));
     int *p = nullptr;
-    NET_HIP(n, hipMalloc((void **)&p, 2 * sizeof(int)));      // [0] the range flag, [1] the fp32 form's largest |output| (float bits)
-    NET_HIP(n, hipMemset(p, 0, 2 * sizeof(int)));
-    NET_HIP(n, hipMemcpyToSymbol(HIP_SYMBOL(grl::g_gemm_range_flag), &p, sizeof(p)));      // this device's instance of the symbol
+    PAAC_HIP(n, hipMalloc((void **)&p, 2 * sizeof(int)));      // [0] the range flag, [1] the fp32 form's largest |output| (float bits)
+    PAAC_HIP(n, hipMemset(p, 0, 2 * sizeof(int)));
+    PAAC_HIP(n, hipMemcpyToSymbol(HIP_SYMBOL(grl::g_gemm_range_flag), &p, sizeof(p)));      // this device's instance of the symbol
     unsigned *pa = reinterpret_cast<unsigned *>(p + 1);
-    NET_HIP(n, hipMemcpyToSymbol(HIP_SYMBOL(grl::g_gemm_absmax), &pa, sizeof(pa)));
+    PAAC_HIP(n, hipMemcpyToSymbol(HIP_SYMBOL(grl::g_gemm_absmax), &pa, sizeof(pa)));
     (void)hipGetLastError();      // the symbol lookup may probe other ordinals and leave a stale error on this thread
     g_range_flag_dev[dev] = p;
     return GRL_OK;
@@ -1273,12 +1214,12 @@ static unsigned *range_absmax_ptr(grl_net *n) { return reinterpret_cast<unsigned
 // rollout ended (rollout_range_mark_kernel), i.e. the rollout's own actions / values come from invalid operands
 static int range_check(grl_net *n, const char *where) {
     int flag = 0;
-    NET_HIP(n, hipMemcpy(&flag, range_flag_ptr(n), sizeof(int), hipMemcpyDeviceToHost));
+    PAAC_HIP(n, hipMemcpy(&flag, range_flag_ptr(n), sizeof(int), hipMemcpyDeviceToHost));
     n->range_bits_last = flag;
     if (!flag) return GRL_OK;
-    NET_HIP(n, hipMemset(range_flag_ptr(n), 0, sizeof(int)));
-    NET_HIP(n, hipDeviceSynchronize());
-    return nfail(n, GRL_E_RANGE, std::string(where) + ": an activation or gradient exceeded 65504, the range of the fp16 matrix-pipe GEMMs "
+    PAAC_HIP(n, hipMemset(range_flag_ptr(n), 0, sizeof(int)));
+    PAAC_HIP(n, hipDeviceSynchronize());
+    return paac_fail(n, GRL_E_RANGE, std::string(where) + ": an activation or gradient exceeded 65504, the range of the fp16 matrix-pipe GEMMs "
                                                       "(include/goldsrl_net.h, Arithmetic); the results of this call are not valid");
 }
 
@@ -1305,8 +1246,8 @@ static bool range_fall_back(grl_net *n) {
 static int range_maybe_return(grl_net *n) {
     if (!n->gemm_f32 || !n->f32_by_fallback || n->range_return_k <= 0) return GRL_OK;
     unsigned bits = 0;
-    NET_HIP(n, hipMemcpy(&bits, range_absmax_ptr(n), sizeof(bits), hipMemcpyDeviceToHost));
-    NET_HIP(n, hipMemset(range_absmax_ptr(n), 0, sizeof(unsigned)));
+    PAAC_HIP(n, hipMemcpy(&bits, range_absmax_ptr(n), sizeof(bits), hipMemcpyDeviceToHost));
+    PAAC_HIP(n, hipMemset(range_absmax_ptr(n), 0, sizeof(unsigned)));
     float amax;
     memcpy(&amax, &bits, sizeof(amax));
     n->absmax_last = amax;
@@ -1319,24 +1260,24 @@ static int range_maybe_return(grl_net *n) {
     n->range_returns += 1;
     int rc = trunk_background(n);
     if (rc) return rc;
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     int flag = 0;
-    NET_HIP(n, hipMemcpy(&flag, range_flag_ptr(n), sizeof(int), hipMemcpyDeviceToHost));
+    PAAC_HIP(n, hipMemcpy(&flag, range_flag_ptr(n), sizeof(int), hipMemcpyDeviceToHost));
     if (flag) {
-        NET_HIP(n, hipMemset(range_flag_ptr(n), 0, sizeof(int)));
+        PAAC_HIP(n, hipMemset(range_flag_ptr(n), 0, sizeof(int)));
         n->range_returns -= 1;
         (void)range_fall_back(n);
-        NET_HIP(n, hipStreamSynchronize(n->h->stream));
+        PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     }
     return GRL_OK;
 }
 
 static int download_heads(grl_net *n, int B, float *mu_host, float *sigma_host, float *vs_host) {
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     if (int rc = range_check(n, "grl_net_predict")) return rc;
-    if (mu_host) NET_HIP(n, hipMemcpy(mu_host, n->mu, (size_t)B * n->ho.A * 4, hipMemcpyDeviceToHost));
-    if (sigma_host) NET_HIP(n, hipMemcpy(sigma_host, n->sigma, (size_t)B * n->ho.A * 4, hipMemcpyDeviceToHost));
-    if (vs_host) NET_HIP(n, hipMemcpy(vs_host, n->vs, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (mu_host) PAAC_HIP(n, hipMemcpy(mu_host, n->mu, (size_t)B * n->ho.A * 4, hipMemcpyDeviceToHost));
+    if (sigma_host) PAAC_HIP(n, hipMemcpy(sigma_host, n->sigma, (size_t)B * n->ho.A * 4, hipMemcpyDeviceToHost));
+    if (vs_host) PAAC_HIP(n, hipMemcpy(vs_host, n->vs, (size_t)B * 4, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 
@@ -1360,9 +1301,9 @@ int grl_net_predict_obs(grl_net *n, int32_t n_envs, const uint8_t *lb, const uin
     hipSetDevice(n->h->cfg.device_id);
     int rc = ensure_tmp_obs(n, n_envs);
     if (rc) return rc;
-    NET_HIP(n, hipMemcpyAsync(n->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, n->h->stream));
-    NET_HIP(n, hipMemcpyAsync(n->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, n->h->stream));
-    NET_HIP(n, hipMemcpyAsync(n->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, n->h->stream));
+    PAAC_HIP(n, hipMemcpyAsync(n->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, n->h->stream));
+    PAAC_HIP(n, hipMemcpyAsync(n->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, n->h->stream));
+    PAAC_HIP(n, hipMemcpyAsync(n->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, n->h->stream));
     rc = forward_all(n, n->tmp_lb, n->tmp_ab, n->tmp_pos, n_envs, n->mu, n->sigma, n->vs);
     if (rc) return rc;
     rc = download_heads(n, n_envs * 10, mu_host, sigma_host, vs_host);
@@ -1376,13 +1317,13 @@ int grl_net_predict_obs(grl_net *n, int32_t n_envs, const uint8_t *lb, const uin
 int grl_net_debug_obs_index(grl_net *n, int32_t n_envs, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, uint32_t *host, size_t bytes) {
     if (!n || !lb || !ab || !pos || !host || n_envs <= 0) return GRL_E_INVALID;
     const size_t need = (size_t)n_envs * kObsWords * 4;
-    if (bytes != need) return nfail(n, GRL_E_SIZE, "grl_net_debug_obs_index: need " + std::to_string(need) + " bytes");
+    if (bytes != need) return paac_fail(n, GRL_E_SIZE, "grl_net_debug_obs_index: need " + std::to_string(need) + " bytes");
     hipSetDevice(n->h->cfg.device_id);
     int rc = ensure_tmp_obs(n, n_envs);
     if (rc) return rc;
     hipStream_t st = n->h->stream;
     unsigned *tmp = nullptr;
-    NET_HIP(n, hipMalloc((void **)&tmp, need));
+    PAAC_HIP(n, hipMalloc((void **)&tmp, need));
     hipError_t e = hipMemsetAsync(tmp, 0, need, st);      // the words the kernel leaves alone (padding, list tails) read as zero
     if (e == hipSuccess) e = hipMemcpyAsync(n->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(n->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, st);
@@ -1394,7 +1335,7 @@ int grl_net_debug_obs_index(grl_net *n, int32_t n_envs, const uint8_t *lb, const
     }
     (void)hipFree(tmp);
     if (rc) return rc;
-    if (e != hipSuccess) return nfail(n, GRL_E_HIP, std::string("grl_net_debug_obs_index: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return paac_fail(n, GRL_E_HIP, std::string("grl_net_debug_obs_index: ") + hipGetErrorString(e));
     return GRL_OK;
 }
 
@@ -1409,7 +1350,7 @@ int grl_net_range_info(grl_net *n, int32_t *gemm_f32, int32_t *fallbacks, int32_
 int grl_net_set_gemm_f32(grl_net *n, int32_t on) {
     if (!n) return GRL_E_INVALID;
     hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     n->gemm_f32 = on ? 1 : 0;
     n->f32_by_fallback = 0;      // the caller's choice stands until the caller (or a range violation) changes it
     n->f32_clean_passes = 0;
@@ -1446,16 +1387,16 @@ static int read_activation_impl(grl_net *n, const char *which, float *host, size
     const float *src = nullptr;
     size_t per = 0;
     if (w == "a1") {
-        if (n->shared_trunk) return nfail(n, GRL_E_INVALID, "grl_net_read_activation: 'a1' is not materialised in shared-trunk mode (read 'a1sh')");
+        if (n->shared_trunk) return paac_fail(n, GRL_E_INVALID, "grl_net_read_activation: 'a1' is not materialised in shared-trunk mode (read 'a1sh')");
         src = n->a1; per = 12800;
     }
     else if (w == "a1sh" || w == "sraw") {     // per ENV: (n/10, 20, 20, 32)
         size_t need_e = (size_t)(n->last_n / 10) * 12800 * 4;
-        if (bytes != need_e) return nfail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need_e) + " bytes");
+        if (bytes != need_e) return paac_fail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need_e) + " bytes");
         if (n->trunk_skip && n->expand2_gemm)      // list form: the blocks nobody reads were not written; they hold b1 (debug/test access)
             hipLaunchKernelGGL(materialize_sraw_kernel, dim3(n->last_n / 10), dim3(256), 0, n->h->stream, n->tnmask, n->params + ConvOffsets::c1b, n->sraw);
-        NET_HIP(n, hipStreamSynchronize(n->h->stream));
-        NET_HIP(n, hipMemcpy(host, n->sraw, bytes, hipMemcpyDeviceToHost));
+        PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
+        PAAC_HIP(n, hipMemcpy(host, n->sraw, bytes, hipMemcpyDeviceToHost));
         if (w == "a1sh") {     // relu(sraw): not materialised on the device
             float *hp = static_cast<float *>(host);
             for (size_t i = 0; i < need_e / 4; ++i) hp[i] = hp[i] > 0.f ? hp[i] : 0.f;
@@ -1464,32 +1405,32 @@ static int read_activation_impl(grl_net *n, const char *which, float *host, size
     }
     else if (w == "a2" && n->shared_trunk) {     // not materialised in shared-trunk mode: expand it on demand (debug/test access)
         size_t need_a = (size_t)n->last_n * 5184 * 4;
-        if (bytes != need_a) return nfail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need_a) + " bytes");
-        if (n->last_n <= 0) return nfail(n, GRL_E_STATE, "grl_net_read_activation: no forward pass yet");
+        if (bytes != need_a) return paac_fail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need_a) + " bytes");
+        if (n->last_n <= 0) return paac_fail(n, GRL_E_STATE, "grl_net_read_activation: no forward pass yet");
         float *tmp = nullptr;
-        NET_HIP(n, hipMalloc((void **)&tmp, need_a));
+        PAAC_HIP(n, hipMalloc((void **)&tmp, need_a));
         if (n->trunk_skip && n->expand2_gemm)      // list form: the pixels no consumer reads were not filled; they hold the background row (debug/test access)
             hipLaunchKernelGGL(trunk_fill_kernel, dim3((n->last_n / 10 * 81 * 16 + 255) / 256), dim3(256), 0, n->h->stream, (const unsigned *)n->tamask, 3, 81,
                                (const float *)(n->tbgz + 64), n->last_n / 10 * 81, n->a2sh, (const float *)nullptr, (float *)nullptr, 0, (const unsigned *)nullptr);
         hipLaunchKernelGGL(materialize_a2_kernel, dim3(n->last_n), dim3(256), 0, n->h->stream, n->a2sh, n->d2s, n->m2s, n->ulist, n->sbase, tmp);
         hipError_t e1 = hipStreamSynchronize(n->h->stream), e2 = hipMemcpy(host, tmp, bytes, hipMemcpyDeviceToHost);
         (void)hipFree(tmp);
-        if (e1 != hipSuccess || e2 != hipSuccess) return nfail(n, GRL_E_HIP, "grl_net_read_activation: expanding a2 failed");
+        if (e1 != hipSuccess || e2 != hipSuccess) return paac_fail(n, GRL_E_HIP, "grl_net_read_activation: expanding a2 failed");
         return GRL_OK;
     }
     else if (w == "a2") { src = n->a2; per = 5184; }
     else if (w == "a3" && n->shared_trunk) {     // likewise: a3sh with the agent's 5x5 patch replaced by its own values
         size_t need_a = (size_t)n->last_n * 3136 * 4;
-        if (bytes != need_a) return nfail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need_a) + " bytes");
-        if (n->last_n <= 0) return nfail(n, GRL_E_STATE, "grl_net_read_activation: no forward pass yet");
+        if (bytes != need_a) return paac_fail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need_a) + " bytes");
+        if (n->last_n <= 0) return paac_fail(n, GRL_E_STATE, "grl_net_read_activation: no forward pass yet");
         float *tmp = nullptr;
-        NET_HIP(n, hipMalloc((void **)&tmp, need_a));
+        PAAC_HIP(n, hipMalloc((void **)&tmp, need_a));
         if (n->trunk_skip && n->expand2_gemm)
             hipLaunchKernelGGL(materialize_a3sh_kernel, dim3(n->last_n / 10), dim3(256), 0, n->h->stream, (const unsigned *)n->tumask, (const float *)(n->tbgz3 + 64), n->a3sh);
         hipLaunchKernelGGL(materialize_a3_kernel, dim3(n->last_n), dim3(256), 0, n->h->stream, n->a3sh, n->d3, n->m3, n->org, n->patch_skip ? n->smask : nullptr, tmp);
         hipError_t e1 = hipStreamSynchronize(n->h->stream), e2 = hipMemcpy(host, tmp, bytes, hipMemcpyDeviceToHost);
         (void)hipFree(tmp);
-        if (e1 != hipSuccess || e2 != hipSuccess) return nfail(n, GRL_E_HIP, "grl_net_read_activation: expanding a3 failed");
+        if (e1 != hipSuccess || e2 != hipSuccess) return paac_fail(n, GRL_E_HIP, "grl_net_read_activation: expanding a3 failed");
         return GRL_OK;
     }
     else if (w == "a3") { src = n->a3; per = 3136; }
@@ -1505,23 +1446,23 @@ static int read_activation_impl(grl_net *n, const char *which, float *host, size
     else if (w == "gd2") { src = n->gd2; per = 256; }
     else if (w == "gv1") { src = n->gv1; per = 512; }
     else if (w == "gd1") { src = n->gd1; per = 512; }
-    else return nfail(n, GRL_E_INVALID, "grl_net_read_activation: unknown tensor '" + w + "'");
+    else return paac_fail(n, GRL_E_INVALID, "grl_net_read_activation: unknown tensor '" + w + "'");
     size_t need = (size_t)n->last_n * per * 4;
-    if (bytes != need) return nfail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need) + " bytes");
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
-    NET_HIP(n, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+    if (bytes != need) return paac_fail(n, GRL_E_SIZE, "grl_net_read_activation: need " + std::to_string(need) + " bytes");
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 
 int grl_net_profile_enable(grl_net *n, int32_t on) {
     if (!n) return GRL_E_INVALID;
     hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     if (on && n->prof_ev.empty()) {
         n->prof_ev.resize(131072);   // 65 536 bracketed launches (~13 full updates at 32 768 envs)
         n->prof_tag.assign(65536, 0);
         n->prof_launch_flops.assign(65536, 0.0);
-        for (auto &ev : n->prof_ev) NET_HIP(n, hipEventCreate(&ev));
+        for (auto &ev : n->prof_ev) PAAC_HIP(n, hipEventCreate(&ev));
     }
     n->prof_on = on != 0; n->prof_used = 0; n->prof_flops = 0;
     return GRL_OK;
@@ -1530,11 +1471,11 @@ int grl_net_profile_enable(grl_net *n, int32_t on) {
 int grl_net_profile_read(grl_net *n, int32_t *launches_out, float *total_ms_out, double *flops_out) {
     if (!n || !launches_out || !total_ms_out || !flops_out) return GRL_E_INVALID;
     hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     float total = 0.f;
     for (size_t i = 0; i + 1 < n->prof_used; i += 2) {
         float ms = 0.f;
-        NET_HIP(n, hipEventElapsedTime(&ms, n->prof_ev[i], n->prof_ev[i + 1]));
+        PAAC_HIP(n, hipEventElapsedTime(&ms, n->prof_ev[i], n->prof_ev[i + 1]));
         total += ms;
     }
     *launches_out = (int32_t)(n->prof_used / 2); *total_ms_out = total; *flops_out = n->prof_flops;
@@ -1544,11 +1485,11 @@ int grl_net_profile_read(grl_net *n, int32_t *launches_out, float *total_ms_out,
 int grl_net_profile_read_tags(grl_net *n, int32_t ntags, int32_t *launches, float *ms, double *flops) {
     if (!n || !launches || !ms || !flops || ntags < PT_COUNT) return GRL_E_INVALID;
     hipSetDevice(n->h->cfg.device_id);
-    NET_HIP(n, hipStreamSynchronize(n->h->stream));
+    PAAC_HIP(n, hipStreamSynchronize(n->h->stream));
     for (int t = 0; t < ntags; ++t) { launches[t] = 0; ms[t] = 0.f; flops[t] = 0.0; }
     for (size_t i = 0; i + 1 < n->prof_used; i += 2) {
         float d = 0.f;
-        NET_HIP(n, hipEventElapsedTime(&d, n->prof_ev[i], n->prof_ev[i + 1]));
+        PAAC_HIP(n, hipEventElapsedTime(&d, n->prof_ev[i], n->prof_ev[i + 1]));
         const int t = n->prof_tag[i / 2] < PT_COUNT ? n->prof_tag[i / 2] : 0;
         launches[t] += 1; ms[t] += d; flops[t] += n->prof_launch_flops[i / 2];
     }

@@ -15,6 +15,7 @@
 
 #include "../../include/goldsrl_fieldnet.h"
 #include "common.h"
+#include "net_paac_host.h"
 
 namespace grl {
 
@@ -315,20 +316,6 @@ __global__ void field_conv_dgrad_kernel(const float *__restrict__ dz, const floa
     dx[i] = s;
 }
 
-// sum of squares in a fixed order: 256 strided partial sums per workgroup, then one workgroup over the partials
-__global__ __launch_bounds__(256) void field_sumsq_kernel(const float *__restrict__ g, long n, double *__restrict__ part) {
-    __shared__ double red[256];
-    double s = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += (double)g[i] * (double)g[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
-}
-
 __global__ void field_finalize_kernel(const double *__restrict__ part, int nparts, const double *__restrict__ stats64, float inv_n, float clip_norm,
                                       float *__restrict__ stats) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -340,28 +327,14 @@ __global__ void field_finalize_kernel(const double *__restrict__ part, int npart
     stats[4] = clip_norm > 0.f ? clip_norm / fmaxf(norm, clip_norm) : 1.0f;      // tf.clip_by_global_norm (actor_learner.py:52-57)
 }
 
-__global__ void field_adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long n,
-                                  const float *__restrict__ stats, float lr_t) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i] * stats[4];
-    const float mi = 0.9f * m[i] + 0.1f * gi;
-    const float vi = 0.999f * v[i] + 0.001f * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + 1e-8f);
-}
-
 }  // namespace grl
 
-struct grl_fieldnet {
-    grl_handle *h;
+struct grl_fieldnet : grl::PaacNet {
     grl_fieldnet_config cfg;
-    std::string err;
     grl::FieldOff off;
     int L, F, A, P2, HWA, D0;
     int lh[grl::FIELD_MAX_LAYERS + 1], lw[grl::FIELD_MAX_LAYERS + 1], lc[grl::FIELD_MAX_LAYERS + 1];      // input geometry of layer l (l = L: the flattened map)
-    float *params, *grads, *adam_m, *adam_v;
-    long adam_t;
+    float *grads;
     float *x[grl::FIELD_MAX_LAYERS + 1];          // x[0] = states, x[l+1] = pooled output of layer l
     uint8_t *idx[grl::FIELD_MAX_LAYERS];
     float *dxl[grl::FIELD_MAX_LAYERS + 1];        // gradient of x[l] (l >= 1)
@@ -369,31 +342,12 @@ struct grl_fieldnet {
     float *cslab;
     float *d1, *d2, *p1, *p2, *v1, *v2, *mu, *sigma, *vs;
     float *dd1, *dd2, *dp1, *dp2, *dv1, *dv2, *dzh;
-    float *d_act, *d_adv, *d_y, *stats;
+    float *d_act, *d_adv, *d_y;
     int32_t *d_pos;
     double *stats64;
-    std::vector<void *> allocs;
 };
 
 namespace grl {
-
-static int xfail(grl_fieldnet *n, int code, const std::string &msg) {
-    if (n) n->err = msg;
-    return code;
-}
-#define FLD_HIP(n, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t _e = (call);                                                                            \
-        if (_e != hipSuccess) return xfail(n, GRL_E_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-template <typename T>
-static int xalloc(grl_fieldnet *n, T **p, size_t count) {
-    FLD_HIP(n, hipMalloc((void **)p, count * sizeof(T)));
-    n->allocs.push_back(*p);
-    FLD_HIP(n, hipMemsetAsync(*p, 0, count * sizeof(T), n->h->stream));
-    return GRL_OK;
-}
 
 static inline unsigned nb(long total) { return (unsigned)((total + 255) / 256); }
 
@@ -425,7 +379,7 @@ static int field_forward(grl_fieldnet *net, int n) {
     dense(net->v1, o.v2w, o.v2b, 2 * FIELD_FC, FIELD_FC, net->v2);
     FIELD_DISPATCH(net->A, hipLaunchKernelGGL(field_heads_fwd_kernel<kA>, dim3((n + 3) / 4), dim3(256), 0, st, net->p2, net->v2, net->d_pos, P, o, n,
                                               net->P2, net->HWA, net->cfg.width, net->cfg.scale, net->mu, net->sigma, net->vs));
-    FLD_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -433,10 +387,10 @@ static int field_upload(grl_fieldnet *net, int n, const float *states, const int
     const grl_fieldnet_config &c = net->cfg;
     for (int i = 0; i < n; ++i)
         if (positions[2 * i] < 0 || positions[2 * i] >= c.height || positions[2 * i + 1] < 0 || positions[2 * i + 1] >= c.width)
-            return xfail(net, GRL_E_INVALID, "agent position outside the " + std::to_string(c.height) + "x" + std::to_string(c.width) + " field (tf.gather_nd would raise)");
+            return paac_fail(net, GRL_E_INVALID, "agent position outside the " + std::to_string(c.height) + "x" + std::to_string(c.width) + " field (tf.gather_nd would raise)");
     hipStream_t st = net->h->stream;
-    FLD_HIP(net, hipMemcpyAsync(net->x[0], states, (size_t)n * c.height * c.width * c.channels * 4, hipMemcpyHostToDevice, st));
-    FLD_HIP(net, hipMemcpyAsync(net->d_pos, positions, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->x[0], states, (size_t)n * c.height * c.width * c.channels * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_pos, positions, (size_t)n * 8, hipMemcpyHostToDevice, st));
     return GRL_OK;
 }
 
@@ -468,7 +422,7 @@ int grl_fieldnet_create(grl_handle *h, const grl_fieldnet_config *cfg, grl_field
                                       "channels 1..8, filters 1..32, num_actions 1..4)");
     hipSetDevice(h->cfg.device_id);
     grl_fieldnet *n = new grl_fieldnet();
-    n->h = h; n->cfg = *cfg; n->adam_t = 0;
+    n->h = h; n->cfg = *cfg;
     n->L = L; n->F = cfg->filters; n->A = cfg->num_actions;
     n->HWA = cfg->height * cfg->width * cfg->num_actions; n->P2 = 2 * n->HWA;
     n->lh[0] = cfg->height; n->lw[0] = cfg->width; n->lc[0] = cfg->channels;
@@ -483,16 +437,16 @@ int grl_fieldnet_create(grl_handle *h, const grl_fieldnet_config *cfg, grl_field
     o.muw = take((long)n->P2 * n->HWA); o.mub = take(n->HWA); o.sgw = take((long)n->P2 * n->HWA); o.sgb = take(n->HWA);
     o.v1w = take(FIELD_FC * 2 * FIELD_FC); o.v1b = take(2 * FIELD_FC); o.v2w = take(2 * FIELD_FC * FIELD_FC); o.v2b = take(FIELD_FC);
     o.v3w = take(FIELD_FC); o.v3b = take(1);
-    o.total = p;
+    o.total = p; n->num_params = p;
     const size_t ms = cfg->max_samples;
     int rc = GRL_OK;
-    auto Al = [&](float **q, size_t cnt) { if (rc == GRL_OK) rc = xalloc(n, q, cnt); };
+    auto Al = [&](float **q, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, q, cnt); };
     Al(&n->params, o.total); Al(&n->grads, o.total); Al(&n->adam_m, o.total); Al(&n->adam_v, o.total);
     size_t maxconv = 0, maxslab = 0;
     for (int l = 0; l <= L; ++l) {
         const size_t e = ms * n->lh[l] * n->lw[l] * n->lc[l];
         Al(&n->x[l], e);
-        if (l >= 1) { Al(&n->dxl[l], e); if (rc == GRL_OK) rc = xalloc(n, &n->idx[l - 1], e); }
+        if (l >= 1) { Al(&n->dxl[l], e); if (rc == GRL_OK) rc = paac_alloc(n, &n->idx[l - 1], e); }
         if (l < L) {
             const size_t conv = ms * n->lh[l] * n->lw[l] * n->F, T = 9 * (size_t)n->lc[l] * n->F + n->F;
             if (conv > maxconv) maxconv = conv;
@@ -505,9 +459,9 @@ int grl_fieldnet_create(grl_handle *h, const grl_fieldnet_config *cfg, grl_field
     Al(&n->mu, ms * n->A); Al(&n->sigma, ms * n->A); Al(&n->vs, ms);
     Al(&n->dd1, ms * 64); Al(&n->dd2, ms * 32); Al(&n->dp1, ms * 64); Al(&n->dp2, ms * n->P2); Al(&n->dv1, ms * 64); Al(&n->dv2, ms * 32);
     Al(&n->dzh, ms * (2 * n->A + 3)); Al(&n->d_act, ms * n->A); Al(&n->d_adv, ms); Al(&n->d_y, ms); Al(&n->stats, 8);
-    if (rc == GRL_OK) rc = xalloc(n, &n->d_pos, ms * 2);
-    if (rc == GRL_OK) rc = xalloc(n, &n->stats64, 8 + 1024);
-    if (rc == GRL_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = xfail(n, GRL_E_HIP, "hipStreamSynchronize");
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->d_pos, ms * 2);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->stats64, 8 + 1024);
+    if (rc == GRL_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = paac_fail(n, GRL_E_HIP, "hipStreamSynchronize");
     if (rc != GRL_OK) {
         fail(h, rc, "grl_fieldnet_create: " + n->err);
         grl_fieldnet_destroy(n);
@@ -520,59 +474,50 @@ int grl_fieldnet_create(grl_handle *h, const grl_fieldnet_config *cfg, grl_field
 int grl_fieldnet_destroy(grl_fieldnet *n) {
     if (!n) return GRL_OK;
     grl_sync_for_destroy(n->h);      // the handle may have been destroyed first (finaliser order of a host binding)
-    for (void *p : n->allocs) hipFree(p);
+    paac_free(n);
     delete n;
     return GRL_OK;
 }
 
-const char *grl_fieldnet_last_error(const grl_fieldnet *n) { return n ? n->err.c_str() : ""; }
-int64_t grl_fieldnet_num_params(const grl_fieldnet *n) { return n ? n->off.total : 0; }
+const char *grl_fieldnet_last_error(const grl_fieldnet *n) { return paac_last_error(n); }
+int64_t grl_fieldnet_num_params(const grl_fieldnet *n) { return paac_num_params(n); }
 
-static int field_copy_flat(grl_fieldnet *n, float *dev, float *host, int64_t cnt, bool to_dev) {
-    if (!n || !host) return GRL_E_INVALID;
-    if (cnt != n->off.total) return xfail(n, GRL_E_SIZE, "expected " + std::to_string(n->off.total) + " floats");
-    hipSetDevice(n->h->cfg.device_id);
-    FLD_HIP(n, hipStreamSynchronize(n->h->stream));
-    if (to_dev) FLD_HIP(n, hipMemcpy(dev, host, cnt * 4, hipMemcpyHostToDevice));
-    else FLD_HIP(n, hipMemcpy(host, dev, cnt * 4, hipMemcpyDeviceToHost));
-    return GRL_OK;
-}
-int grl_fieldnet_set_params(grl_fieldnet *n, const float *host, int64_t cnt) { return field_copy_flat(n, n ? n->params : nullptr, (float *)host, cnt, true); }
-int grl_fieldnet_get_params(grl_fieldnet *n, float *host, int64_t cnt) { return field_copy_flat(n, n ? n->params : nullptr, host, cnt, false); }
-int grl_fieldnet_get_grads(grl_fieldnet *n, float *host, int64_t cnt) { return field_copy_flat(n, n ? n->grads : nullptr, host, cnt, false); }
+int grl_fieldnet_set_params(grl_fieldnet *n, const float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->params : nullptr, (float *)host, cnt, true); }
+int grl_fieldnet_get_params(grl_fieldnet *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->params : nullptr, host, cnt, false); }
+int grl_fieldnet_get_grads(grl_fieldnet *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->grads : nullptr, host, cnt, false); }
 
 int grl_fieldnet_predict(grl_fieldnet *net, int32_t n, const float *states, const int32_t *positions, float *mu, float *sigma, float *vs) {
-    if (!net || n <= 0 || !states || !positions) return xfail(net, GRL_E_INVALID, "grl_fieldnet_predict: bad argument");
-    if (n > net->cfg.max_samples) return xfail(net, GRL_E_SIZE, "grl_fieldnet_predict: n exceeds max_samples");
+    if (!net || n <= 0 || !states || !positions) return paac_fail(net, GRL_E_INVALID, "grl_fieldnet_predict: bad argument");
+    if (n > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "grl_fieldnet_predict: n exceeds max_samples");
     hipSetDevice(net->h->cfg.device_id);
     int rc = field_upload(net, n, states, positions);
     if (rc == GRL_OK) rc = field_forward(net, n);
     if (rc) return rc;
-    FLD_HIP(net, hipStreamSynchronize(net->h->stream));
-    if (mu) FLD_HIP(net, hipMemcpy(mu, net->mu, (size_t)n * net->A * 4, hipMemcpyDeviceToHost));
-    if (sigma) FLD_HIP(net, hipMemcpy(sigma, net->sigma, (size_t)n * net->A * 4, hipMemcpyDeviceToHost));
-    if (vs) FLD_HIP(net, hipMemcpy(vs, net->vs, (size_t)n * 4, hipMemcpyDeviceToHost));
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
+    if (mu) PAAC_HIP(net, hipMemcpy(mu, net->mu, (size_t)n * net->A * 4, hipMemcpyDeviceToHost));
+    if (sigma) PAAC_HIP(net, hipMemcpy(sigma, net->sigma, (size_t)n * net->A * 4, hipMemcpyDeviceToHost));
+    if (vs) PAAC_HIP(net, hipMemcpy(vs, net->vs, (size_t)n * 4, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 
 int grl_fieldnet_train(grl_fieldnet *net, int32_t n, const float *states, const int32_t *positions, const float *actions, const float *advantages,
                     const float *critic_target, float lr, int32_t apply_update, float *stats_host) {
-    if (!net || n <= 0 || !states || !positions || !actions || !advantages || !critic_target) return xfail(net, GRL_E_INVALID, "grl_fieldnet_train: bad argument");
-    if (n > net->cfg.max_samples) return xfail(net, GRL_E_SIZE, "grl_fieldnet_train: n exceeds max_samples");
+    if (!net || n <= 0 || !states || !positions || !actions || !advantages || !critic_target) return paac_fail(net, GRL_E_INVALID, "grl_fieldnet_train: bad argument");
+    if (n > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "grl_fieldnet_train: n exceeds max_samples");
     hipSetDevice(net->h->cfg.device_id);
     hipStream_t st = net->h->stream;
     int rc = field_upload(net, n, states, positions);
     if (rc) return rc;
-    FLD_HIP(net, hipMemcpyAsync(net->d_act, actions, (size_t)n * net->A * 4, hipMemcpyHostToDevice, st));
-    FLD_HIP(net, hipMemcpyAsync(net->d_adv, advantages, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    FLD_HIP(net, hipMemcpyAsync(net->d_y, critic_target, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_act, actions, (size_t)n * net->A * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_adv, advantages, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_y, critic_target, (size_t)n * 4, hipMemcpyHostToDevice, st));
     if ((rc = field_forward(net, n))) return rc;
     const float *P = net->params;
     float *G = net->grads;
     const FieldOff &o = net->off;
     const int P2 = net->P2, HWA = net->HWA, W = net->cfg.width;
     // the gathered heads touch A columns per sample: the rest of their gradient is zero
-    FLD_HIP(net, hipMemsetAsync(G + o.muw, 0, (size_t)(o.v1w - o.muw) * 4, st));
+    PAAC_HIP(net, hipMemsetAsync(G + o.muw, 0, (size_t)(o.v1w - o.muw) * 4, st));
     FIELD_DISPATCH(net->A, hipLaunchKernelGGL(field_heads_bwd_kernel<kA>, dim3((n + 3) / 4), dim3(256), 0, st, net->p2, net->v2, net->d_pos, net->mu,
                                               net->sigma, net->vs, net->d_act, net->d_adv, net->d_y, P, o, n, P2, HWA, W, net->cfg.scale,
                                               net->cfg.entropy_beta, 1.0f / (float)n, net->dzh, net->dp2, net->dv2));
@@ -611,22 +556,17 @@ int grl_fieldnet_train(grl_fieldnet *net, int32_t n, const float *states, const 
         }
     }
     const int nparts = 1024;
-    hipLaunchKernelGGL(field_sumsq_kernel, dim3(nparts), dim3(256), 0, st, G, o.total, net->stats64 + 8);
+    hipLaunchKernelGGL(paac_sumsq_kernel<>, dim3(nparts), dim3(256), 0, st, G, o.total, net->stats64 + 8);
     hipLaunchKernelGGL(field_finalize_kernel, dim3(1), dim3(64), 0, st, net->stats64 + 8, nparts, net->stats64, 1.0f / (float)n, net->cfg.clip_norm,
                        net->stats);
     if (apply_update) {
         net->adam_t += 1;
-        const float lr_t = (float)((double)lr * sqrt(1.0 - pow(0.999, (double)net->adam_t)) / (1.0 - pow(0.9, (double)net->adam_t)));
-        hipLaunchKernelGGL(field_adam_kernel, dim3(nb(o.total)), dim3(256), 0, st, net->params, G, net->adam_m, net->adam_v, o.total, net->stats, lr_t);
+        hipLaunchKernelGGL(paac_adam_kernel<>, dim3(nb(o.total)), dim3(256), 0, st, net->params, G, net->adam_m, net->adam_v, o.total, net->stats,
+                           adam_lr_t(lr, net->adam_t));
     }
-    FLD_HIP(net, hipGetLastError());
-    FLD_HIP(net, hipStreamSynchronize(st));
-    if (stats_host) {
-        float s[5];
-        FLD_HIP(net, hipMemcpy(s, net->stats, sizeof(s), hipMemcpyDeviceToHost));
-        stats_host[0] = s[2]; stats_host[1] = s[0]; stats_host[2] = s[1]; stats_host[3] = s[3];
-    }
-    return GRL_OK;
+    PAAC_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipStreamSynchronize(st));
+    return paac_read_stats(net, stats_host);
 }
 
 }  // extern "C"

@@ -17,10 +17,9 @@
 #include <string>
 #include <vector>
 
-#include <rccl/rccl.h>
-
 #include "../../include/goldsrl_flatnet.h"      // brings goldsrl_flateval.h and goldsrl_flatwindow.h
 #include "common.h"
+#include "net_paac_host.h"
 #include "rng.h"
 #include "flat_env_dev.h"
 #include "rollout_dev.h"
@@ -156,17 +155,6 @@ __global__ void flat_finalize_kernel(const double *__restrict__ sumsq, const dou
     stats[4] = grad_scale * (clip_norm > 0.f ? clip_norm / fmaxf(norm, clip_norm) : 1.0f);      // tf.clip_by_global_norm
 }
 
-__global__ void flat_adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long n,
-                                 const float *__restrict__ stats, float lr_t) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float gi = g[i] * stats[4];
-    float mi = 0.9f * m[i] + 0.1f * gi;
-    float vi = 0.999f * v[i] + 0.001f * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + 1e-8f);
-}
-
 // a = mu + sigma*N(0,1) (paac.py:36), SolowRunner.transform_actions_for_env = sigmoid (emulator_runner.py:77-79)
 __global__ void flat_sample_kernel(const float *__restrict__ mu, const float *__restrict__ sigma, int n, int A, uint64_t seed,
                                    uint32_t env_off, const uint32_t *__restrict__ counter_base, uint32_t step, int env_kind, int greedy,
@@ -188,15 +176,12 @@ __global__ void flat_mask_kernel(const uint8_t *__restrict__ done, int n, float 
 
 }  // namespace grl
 
-struct grl_fnet {
-    grl_handle *h;
+struct grl_fnet : grl::PaacCommNet {
     grl_fnet_config cfg;
-    std::string err;
     grl::FOff off;
     grl::WsOff wso;
-    float *params, *paramsT, *grads, *adam_m, *adam_v;      // paramsT: net_flat_bwd_fast.inc (fb_dx)
-    long adam_t;
-    float *ws, *slab, *stats;
+    float *paramsT, *grads;      // paramsT: net_flat_bwd_fast.inc (fb_dx)
+    float *ws, *slab;
     double *stats64;
     float *d_states, *d_hist, *d_act, *d_adv, *d_y, *mu, *sigma, *vs;
     int slab_blocks;
@@ -204,7 +189,6 @@ struct grl_fnet {
     int T;
     float *ro_states, *ro_hist, *ro_act, *ro_envact, *ro_val, *ro_rew, *ro_mask, *ro_y, *ro_adv, *ro_boot;
     int32_t *ro_nhist;
-    unsigned long act_counter;
     uint32_t *d_counter;           // act_counter at the start of the rollout in flight
     hipGraphExec_t ro_graph;       // the T-step rollout captured once and replayed (launch-bound at 4 096 envs)
     int ro_graph_T;
@@ -243,35 +227,9 @@ struct grl_fnet {
     int ro_graph_tw;               // the captured rollout is the true-window one, on
     float *ro_graph_slab;          // this slab
     int last_n;                    // samples of the last gradient pass (grl_fnet_apply_grads normalises the loss sums with it)
-    void *comm;                    // ncclComm_t (RCCL): one all-reduce of the flat gradient per rollout, or nullptr
-    int comm_world, comm_rank;
-    hipEvent_t ar_ev0, ar_ev1;     // bracket the all-reduce on the handle's stream (grl_fnet_comm_info)
-    int ar_pending;
-    long ar_calls;
-    double ar_ms_total;
-    float ar_ms_last;
-    std::vector<void *> allocs;
 };
 
 namespace grl {
-
-static int ffail(grl_fnet *n, int code, const std::string &msg) {
-    if (n) n->err = msg;
-    return code;
-}
-#define FNET_HIP(n, call)                                                                                  \
-    do {                                                                                                   \
-        hipError_t _e = (call);                                                                            \
-        if (_e != hipSuccess) return ffail(n, GRL_E_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-template <typename T>
-static int falloc(grl_fnet *n, T **p, size_t count) {
-    FNET_HIP(n, hipMalloc((void **)p, count * sizeof(T)));
-    n->allocs.push_back(*p);
-    FNET_HIP(n, hipMemsetAsync(*p, 0, count * sizeof(T), n->h->stream));
-    return GRL_OK;
-}
 
 static FlatArgs base_args(grl_fnet *net, int n, const float *states, const float *hist, float *mu, float *sigma, float *vs, bool save,
                           const int32_t *nhist = nullptr, int wstride = 0) {
@@ -291,14 +249,14 @@ static int launch_forward(grl_fnet *net, int n, const float *states, const float
         // true windows, predictions only: the fast forward for distinct rows (net_flat_window.inc)
         if (net->cfg.temporal_size <= 4) hipLaunchKernelGGL(flat_forward_win_kernel<1>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
         else hipLaunchKernelGGL(flat_forward_win_kernel<9>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
-        FNET_HIP(net, hipGetLastError());
+        PAAC_HIP(net, hipGetLastError());
         return GRL_OK;
     }
     if (nhist && !wstride && net->cfg.static_size == net->cfg.temporal_size && net->fast_forward) {
         // synthesized window (the PAAC worker's: the current state repeated): the 2T + 5 stage form of net_flat_fast.inc
         if (save) hipLaunchKernelGGL(flat_forward_fast_kernel<true>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
         else hipLaunchKernelGGL(flat_forward_fast_kernel<false>, dim3(groups), dim3(FNT), ff_lds_bytes(net->cfg.static_size), net->h->stream, a);
-        FNET_HIP(net, hipGetLastError());
+        PAAC_HIP(net, hipGetLastError());
         return GRL_OK;
     }
     const size_t wbytes = (size_t)(net->cfg.temporal_size + FH) * 3 * FH * sizeof(float);
@@ -307,7 +265,7 @@ static int launch_forward(grl_fnet *net, int n, const float *states, const float
         hipLaunchKernelGGL(flat_forward_kernel<true>, dim3(groups), dim3(256), FLAT_LDS_BYTES + wbytes, net->h->stream, a, (int)FLAT_LDS_ROWS);
     else
         hipLaunchKernelGGL(flat_forward_kernel<false>, dim3(groups), dim3(256), FLAT_LDS_BYTES, net->h->stream, a, (int)FLAT_LDS_ROWS);
-    FNET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -317,7 +275,7 @@ static int launch_forward(grl_fnet *net, int n, const float *states, const float
 static int train_grads_device(grl_fnet *net, int n, const float *states, const float *hist, const float *actions, const float *adv,
                               const float *y, const int32_t *nhist = nullptr, bool resident = false, int wstride = 0) {
     hipStream_t st = net->h->stream;
-    if (n > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "train: n exceeds max_samples of the net");
+    if (n > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "train: n exceeds max_samples of the net");
     int rc = GRL_OK;
     if (!resident) {
         net->ws_resident = 0;
@@ -329,8 +287,8 @@ static int train_grads_device(grl_fnet *net, int n, const float *states, const f
     const bool fast = nhist && !wstride && net->cfg.static_size == net->cfg.temporal_size && net->fast_forward && net->arg_slot >= 0;
     int blocks = groups < net->slab_blocks ? groups : net->slab_blocks;
     if (fast && blocks > 256) blocks = 256;      // the 16-wave form: one workgroup per CU (100 KB of LDS)
-    if (!fast) FNET_HIP(net, hipMemsetAsync(net->slab, 0, (size_t)blocks * net->off.total * 4, st));      // the fast backward clears its own
-    FNET_HIP(net, hipMemsetAsync(net->stats64, 0, 4 * sizeof(double), st));
+    if (!fast) PAAC_HIP(net, hipMemsetAsync(net->slab, 0, (size_t)blocks * net->off.total * 4, st));      // the fast backward clears its own
+    PAAC_HIP(net, hipMemsetAsync(net->stats64, 0, 4 * sizeof(double), st));
     FlatArgs a = base_args(net, n, states, hist, net->mu, net->sigma, net->vs, true, nhist, wstride);
     a.actions = actions; a.adv = adv; a.y = y; a.inv_n = 1.0f / (float)n; a.slab = net->slab; a.stats64 = net->stats64;
     if (fast && net->arg_slot >= 0) {
@@ -338,7 +296,7 @@ static int train_grads_device(grl_fnet *net, int n, const float *states, const f
         hipLaunchKernelGGL(flat_transpose_kernel, dim3(kFlatTransposed), dim3(256), 0, st, net->params, net->paramsT, net->off,
                            net->cfg.temporal_size, net->cfg.num_actions);
         // the stages of the fast backward are calls that read their arguments from the net's __constant__ slot (net_flat_fast.inc)
-        FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &a, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
+        PAAC_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &a, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
                                              hipMemcpyHostToDevice, st));
         (void)hipGetLastError();
         hipLaunchKernelGGL(flat_backward_fast_kernel, dim3(blocks), dim3(FNT), FB2_LDS_BYTES, st, net->arg_slot, n, net->cfg.rnn_length, a.ts, a.ts_n);
@@ -347,25 +305,8 @@ static int train_grads_device(grl_fnet *net, int n, const float *states, const f
     }
     hipLaunchKernelGGL(flat_slab_reduce_kernel, dim3((unsigned)((net->off.total + 63) / 64)), dim3(1024), 0, st, net->slab, blocks,
                        net->off.total, net->grads);
-    FNET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     net->last_n = n;
-    return GRL_OK;
-}
-
-// One all-reduce (sum, fp32) of the flat gradient per rollout over RCCL/xGMI, the rule of net_train.inc: every rank's
-// gradient is the mean over ITS T*E_local samples, the loss is a mean over the whole batch (policy_v_network.py:246-251), so the
-// sum is scaled by 1/world (folded into the clip factor); clip after the reduction, Adam replicated.
-static int fcomm_allreduce_grads(grl_fnet *net, float *grad_scale_out) {
-    *grad_scale_out = 1.0f;
-    if (!net->comm) return GRL_OK;
-    if (!net->ar_ev0) { FNET_HIP(net, hipEventCreate(&net->ar_ev0)); FNET_HIP(net, hipEventCreate(&net->ar_ev1)); }
-    FNET_HIP(net, hipEventRecord(net->ar_ev0, net->h->stream));
-    ncclResult_t r = ncclAllReduce(net->grads, net->grads, (size_t)net->off.total, ncclFloat, ncclSum, (ncclComm_t)net->comm, net->h->stream);
-    (void)hipGetLastError();   // RCCL probes may leave a stale HIP error on this thread
-    if (r != ncclSuccess) return ffail(net, GRL_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-    FNET_HIP(net, hipEventRecord(net->ar_ev1, net->h->stream));
-    net->ar_pending = 1;
-    *grad_scale_out = 1.0f / (float)net->comm_world;
     return GRL_OK;
 }
 
@@ -379,23 +320,13 @@ static int train_apply_device(grl_fnet *net, float lr, int apply_update, float g
     if (apply_update) {
         net->ws_resident = 0;      // the parameters move
         net->adam_t += 1;
-        float lr_t = (float)((double)lr * sqrt(1.0 - pow(0.999, (double)net->adam_t)) / (1.0 - pow(0.9, (double)net->adam_t)));
-        hipLaunchKernelGGL(flat_adam_kernel, dim3((unsigned)((net->off.total + 255) / 256)), dim3(256), 0, st, net->params, net->grads,
-                           net->adam_m, net->adam_v, net->off.total, net->stats, lr_t);
+        hipLaunchKernelGGL(paac_adam_kernel<>, dim3((unsigned)((net->off.total + 255) / 256)), dim3(256), 0, st, net->params, net->grads,
+                           net->adam_m, net->adam_v, net->off.total, net->stats, adam_lr_t(lr, net->adam_t));
     }
-    FNET_HIP(net, hipGetLastError());
-    FNET_HIP(net, hipStreamSynchronize(st));
-    if (net->ar_pending) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, net->ar_ev0, net->ar_ev1) == hipSuccess) { net->ar_ms_last = ms; net->ar_ms_total += ms; net->ar_calls += 1; }
-        net->ar_pending = 0;
-    }
-    if (stats_host) {
-        float s[5];
-        FNET_HIP(net, hipMemcpy(s, net->stats, sizeof(s), hipMemcpyDeviceToHost));
-        stats_host[0] = s[2]; stats_host[1] = s[0]; stats_host[2] = s[1]; stats_host[3] = s[3];
-    }
-    return GRL_OK;
+    PAAC_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipStreamSynchronize(st));
+    paac_allreduce_account(net);
+    return paac_read_stats(net, stats_host);
 }
 
 // gradient pass [+ all-reduce over ranks if a communicator is attached and the parameters are to be updated] + clip + Adam
@@ -404,7 +335,7 @@ static int train_device(grl_fnet *net, int n, const float *states, const float *
     int rc = train_grads_device(net, n, states, hist, actions, adv, y, nhist, resident, wstride);
     if (rc) return rc;
     float grad_scale = 1.0f;
-    if (apply_update && (rc = fcomm_allreduce_grads(net, &grad_scale))) return rc;
+    if (apply_update && (rc = paac_allreduce_grads(net, net->grads, nullptr, &grad_scale))) return rc;
     return train_apply_device(net, lr, apply_update, grad_scale, stats_host);
 }
 
@@ -414,14 +345,14 @@ static int window_ensure_slab(grl_fnet *net, int T) {
     const size_t slice = (size_t)net->h->E * net->cfg.static_size, lead = (size_t)net->cfg.rnn_length - 1;
     int rc = GRL_OK;
     if (!net->w_len) {
-        if ((rc = falloc(net, &net->w_len, net->h->E))) return rc;
-        if ((rc = falloc(net, &net->w_elapsed, net->h->E))) return rc;
-        if ((rc = falloc(net, &net->w_episode, net->h->E))) return rc;
+        if ((rc = paac_alloc(net, &net->w_len, net->h->E))) return rc;
+        if ((rc = paac_alloc(net, &net->w_elapsed, net->h->E))) return rc;
+        if ((rc = paac_alloc(net, &net->w_episode, net->h->E))) return rc;
         net->w_restart_all = 1;
     }
     if (!net->ro_slab || net->slab_T < T) {
         // an older slab stays allocated until the net is destroyed: w_src may still point into it
-        if ((rc = falloc(net, &net->ro_slab, (lead + (size_t)T + 1) * slice))) return rc;
+        if ((rc = paac_alloc(net, &net->ro_slab, (lead + (size_t)T + 1) * slice))) return rc;
         net->slab_T = T;
     }
     net->ro_states = net->ro_slab + lead * slice;
@@ -442,7 +373,7 @@ static int window_enter(grl_fnet *net) {
     net->w_valid = 0;
     hipLaunchKernelGGL(flat_window_detect_kernel, dim3((E + 255) / 256), dim3(256), 0, st, net->w_len, (const int32_t *)h->elapsed,
                        (const int32_t *)h->episode, (const int32_t *)net->w_elapsed, (const int32_t *)net->w_episode, E, all);
-    FNET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     net->w_restart_all = 0;
     return GRL_OK;
 }
@@ -451,8 +382,8 @@ static int window_enter(grl_fnet *net) {
 static int window_leave(grl_fnet *net, int T) {
     grl_handle *h = net->h;
     const long slice = (long)h->E * net->cfg.static_size;
-    FNET_HIP(net, hipMemcpyAsync(net->w_elapsed, h->elapsed, (size_t)h->E * 4, hipMemcpyDeviceToDevice, h->stream));
-    FNET_HIP(net, hipMemcpyAsync(net->w_episode, h->episode, (size_t)h->E * 4, hipMemcpyDeviceToDevice, h->stream));
+    PAAC_HIP(net, hipMemcpyAsync(net->w_elapsed, h->elapsed, (size_t)h->E * 4, hipMemcpyDeviceToDevice, h->stream));
+    PAAC_HIP(net, hipMemcpyAsync(net->w_episode, h->episode, (size_t)h->E * 4, hipMemcpyDeviceToDevice, h->stream));
     net->w_src = net->ro_states + ((long)T - (net->cfg.rnn_length - 1)) * slice;
     net->w_have = 1;
     net->w_valid = 1;
@@ -470,18 +401,18 @@ static int enqueue_rollout(grl_fnet *net, int T) {
     for (int t = 0; t < T; ++t) {
         // states[t] = shared_states, histories[t] = shared_histories (paac.py:132-133).  For TradeAR1 the window is
         // kept as (state, #rows): the worker's history is min(n, rnn) copies of the current state (quirk Q11)
-        FNET_HIP(net, hipMemcpyAsync(net->ro_states + (size_t)t * E * S0, obs, (size_t)E * S0 * 4, hipMemcpyDeviceToDevice, st));
+        PAAC_HIP(net, hipMemcpyAsync(net->ro_states + (size_t)t * E * S0, obs, (size_t)E * S0 * 4, hipMemcpyDeviceToDevice, st));
         // the window is kept as (state, #rows) for both envs -- the worker's history is min(n, rnn) copies of the current state
         // (quirk Q11); Solow's dense (E, rnn, 2) form is recorded too (grl_fnet_read_rollout "histories")
         const int32_t *nh = solow ? h->so.nhist : h->tr.nhist;
         if (net->true_window) {
             // the window: the rows of the slab that end at states[t] (w_len of them per env)
-            FNET_HIP(net, hipMemcpyAsync(net->ro_nhist + (size_t)t * E, net->w_len, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
+            PAAC_HIP(net, hipMemcpyAsync(net->ro_nhist + (size_t)t * E, net->w_len, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
             rc = launch_forward(net, E, net->ro_states + (size_t)t * E * S0, nullptr, net->mu, net->sigma, net->ro_val + (size_t)t * E, false, net->w_len, E);
             if (rc) return rc;
         } else {
-        if (solow) FNET_HIP(net, hipMemcpyAsync(net->ro_hist + (size_t)t * E * R * 2, h->so.history, (size_t)E * R * 8, hipMemcpyDeviceToDevice, st));
-        FNET_HIP(net, hipMemcpyAsync(net->ro_nhist + (size_t)t * E, nh, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
+        if (solow) PAAC_HIP(net, hipMemcpyAsync(net->ro_hist + (size_t)t * E * R * 2, h->so.history, (size_t)E * R * 8, hipMemcpyDeviceToDevice, st));
+        PAAC_HIP(net, hipMemcpyAsync(net->ro_nhist + (size_t)t * E, nh, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
         rc = launch_forward(net, E, obs, nullptr, net->mu, net->sigma, net->ro_val + (size_t)t * E, false, nh);
         if (rc) return rc;
         }
@@ -489,15 +420,15 @@ static int enqueue_rollout(grl_fnet *net, int T) {
                            (uint32_t)h->cfg.env_id_offset, (const uint32_t *)net->d_counter, (uint32_t)t, h->cfg.env_kind, net->greedy,
                            net->ro_act + (size_t)t * E * A, net->ro_envact);
         rc = solow ? solow_launch_step(h, net->ro_envact) : trade_launch_step(h, net->ro_envact);
-        if (rc) return ffail(net, rc, h->err);
-        if ((rc = episodes_launch_account(h))) return ffail(net, rc, h->err);      // R6 (paac.py:142-157), when enabled on the handle
-        FNET_HIP(net, hipMemcpyAsync(net->ro_rew + (size_t)t * E, h->reward, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
+        if (rc) return paac_fail(net, rc, h->err);
+        if ((rc = episodes_launch_account(h))) return paac_fail(net, rc, h->err);      // R6 (paac.py:142-157), when enabled on the handle
+        PAAC_HIP(net, hipMemcpyAsync(net->ro_rew + (size_t)t * E, h->reward, (size_t)E * 4, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(flat_mask_kernel, dim3((E + 255) / 256), dim3(256), 0, st, h->done, E, net->ro_mask + (size_t)t * E);
         if (net->true_window)
             hipLaunchKernelGGL(flat_window_step_kernel, dim3((E + 255) / 256), dim3(256), 0, st, net->w_len, (const uint8_t *)h->done, E, R);
     }
     if (net->true_window) {      // the bootstrap observation is slice T of the slab: the window behind the last step
-        FNET_HIP(net, hipMemcpyAsync(net->ro_states + (size_t)T * E * S0, obs, (size_t)E * S0 * 4, hipMemcpyDeviceToDevice, st));
+        PAAC_HIP(net, hipMemcpyAsync(net->ro_states + (size_t)T * E * S0, obs, (size_t)E * S0 * 4, hipMemcpyDeviceToDevice, st));
         rc = launch_forward(net, E, net->ro_states + (size_t)T * E * S0, nullptr, net->mu, net->sigma, net->ro_boot, false, net->w_len, E);
     } else {
         rc = launch_forward(net, E, obs, nullptr, net->mu, net->sigma, net->ro_boot, false, solow ? h->so.nhist : h->tr.nhist);
@@ -508,7 +439,7 @@ static int enqueue_rollout(grl_fnet *net, int T) {
     const bool gae = net->cfg.gae_lambda < 1.0f;
     if ((rc = launch_returns(h, net->ro_rew, net->ro_val, net->ro_mask, net->ro_boot, T, E, net->cfg.gamma, gae ? net->cfg.gae_lambda : 1.0f,
                              net->cfg.scale, gae ? 0.f : -2.f, gae ? 0.f : 2.f, net->ro_y, net->ro_adv)))
-        return ffail(net, rc, h->err);
+        return paac_fail(net, rc, h->err);
     return GRL_OK;
 }
 
@@ -590,16 +521,16 @@ static int launch_persistent_rollout(grl_fnet *net, int T) {
     R.ep_cap = h->ep_capacity;
     hipStream_t st = h->stream;
     R.ts = net->d_ts; R.ts_n = net->d_ts_n; R.greedy = net->greedy;
-    if (net->d_ts_n) FNET_HIP(net, hipMemsetAsync(net->d_ts_n, 0, sizeof(int), st));
-    FNET_HIP(net, hipMemsetAsync(h->done_count, 0, sizeof(int32_t), st));      // the last step's done list is built inside the kernel
-    FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ro_args), &R, sizeof(RolloutArgs), (size_t)net->arg_slot * sizeof(RolloutArgs),
+    if (net->d_ts_n) PAAC_HIP(net, hipMemsetAsync(net->d_ts_n, 0, sizeof(int), st));
+    PAAC_HIP(net, hipMemsetAsync(h->done_count, 0, sizeof(int32_t), st));      // the last step's done list is built inside the kernel
+    PAAC_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ro_args), &R, sizeof(RolloutArgs), (size_t)net->arg_slot * sizeof(RolloutArgs),
                                          hipMemcpyHostToDevice, st));      // pageable source: staged before the call returns
-    FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &R.f, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
+    PAAC_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &R.f, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
                                          hipMemcpyHostToDevice, st));
     (void)hipGetLastError();      // the symbol lookup may probe other ordinals and leave a stale error on this thread
     const dim3 grid((h->E + G - 1) / G);
     hipLaunchKernelGGL(kern_fn, grid, dim3(FNT), lds_bytes, st, net->arg_slot);
-    FNET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     net->ws_resident = keep ? 1 : 0;
     return GRL_OK;
 }
@@ -609,12 +540,12 @@ static int ensure_eval_buffers(grl_fnet *net, int steps) {
     const size_t E = net->h->E;
     int rc = GRL_OK;
     if (!net->ev_total) {
-        if ((rc = falloc(net, &net->ev_total, E))) return rc;
-        if ((rc = falloc(net, &net->ev_len, E))) return rc;
-        if ((rc = falloc(net, &net->ev_fin, E))) return rc;
+        if ((rc = paac_alloc(net, &net->ev_total, E))) return rc;
+        if ((rc = paac_alloc(net, &net->ev_len, E))) return rc;
+        if ((rc = paac_alloc(net, &net->ev_fin, E))) return rc;
     }
     if (steps <= net->ev_trace_cap) return GRL_OK;
-    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
     for (void *p : net->ev_allocs) hipFree(p);
     net->ev_allocs.clear();
     net->ev_trace_cap = -1;
@@ -625,7 +556,7 @@ static int ensure_eval_buffers(grl_fnet *net, int steps) {
         cnt = cnt ? cnt : 1;
         hipError_t e = hipMalloc((void **)p, cnt * sizeof(**p));
         if (e == hipSuccess) { net->ev_allocs.push_back(*p); e = hipMemsetAsync(*p, 0, cnt * sizeof(**p), st); }
-        if (e != hipSuccess) rc = ffail(net, GRL_E_HIP, std::string("eval trace buffers: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = paac_fail(net, GRL_E_HIP, std::string("eval trace buffers: ") + hipGetErrorString(e));
     };
     Al(&net->ev_states, SE * S0); Al(&net->ev_nhist, SE); Al(&net->ev_mu, SE * A); Al(&net->ev_sigma, SE * A); Al(&net->ev_raw, SE * A);
     Al(&net->ev_act, SE * A); Al(&net->ev_val, SE); Al(&net->ev_rew, SE); Al(&net->ev_done, SE);
@@ -636,7 +567,7 @@ static int ensure_eval_buffers(grl_fnet *net, int steps) {
 // whole episodes of every env as ONE kernel (net_flat_eval.inc)
 static int launch_eval(grl_fnet *net, int max_steps, int trace_steps, int greedy) {
     grl_handle *h = net->h;
-    if (net->arg_slot < 0) return ffail(net, GRL_E_STATE, "grl_fnet_eval: no constant-memory argument slot is free for this net");
+    if (net->arg_slot < 0) return paac_fail(net, GRL_E_STATE, "grl_fnet_eval: no constant-memory argument slot is free for this net");
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     RolloutArgs R{};
     R.f = base_args(net, h->E, nullptr, nullptr, nullptr, nullptr, nullptr, false);
@@ -649,12 +580,12 @@ static int launch_eval(grl_fnet *net, int max_steps, int trace_steps, int greedy
         R.off_wl = (int)(lds_bytes / sizeof(float));
         lds_bytes += 64 * sizeof(float);
         if (!net->ev_ring) {
-            int rc = falloc(net, &net->ev_ring, (size_t)net->cfg.rnn_length * h->E * net->cfg.static_size);
+            int rc = paac_alloc(net, &net->ev_ring, (size_t)net->cfg.rnn_length * h->E * net->cfg.static_size);
             if (rc) return rc;
         }
         R.f.states = net->ev_ring; R.f.wstride = h->E; R.f.wring = net->cfg.rnn_length;
     }
-    if (lds_bytes > 160 * 1024) return ffail(net, GRL_E_SIZE, "grl_fnet_eval: the evaluation's LDS rows do not fit a CU");
+    if (lds_bytes > 160 * 1024) return paac_fail(net, GRL_E_SIZE, "grl_fnet_eval: the evaluation's LDS rows do not fit a CU");
     int G = net->ro_group;      // the rule of launch_persistent_rollout
     if (!G) G = h->E <= 16 * 256 ? 16 : (h->E <= 32 * 256 ? 32 : 64);
     R.gs = G;
@@ -665,7 +596,7 @@ static int launch_eval(grl_fnet *net, int max_steps, int trace_steps, int greedy
     const int gi = G == 16 ? 0 : (G == 32 ? 1 : 2);
     char &ev_attr = tw ? net->ev_win_attr_set[gi] : net->ev_attr_set[gi];
     if (!ev_attr) {
-        FNET_HIP(net, hipFuncSetAttribute((const void *)kernels[gi], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        PAAC_HIP(net, hipFuncSetAttribute((const void *)kernels[gi], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ev_attr = 1;
     }
     if (solow) { R.so = solow_params(h); R.obs0 = h->so.obs; }
@@ -677,14 +608,14 @@ static int launch_eval(grl_fnet *net, int max_steps, int trace_steps, int greedy
     R.ev.states = net->ev_states; R.ev.nhist = net->ev_nhist; R.ev.mu = net->ev_mu; R.ev.sigma = net->ev_sigma; R.ev.raw = net->ev_raw;
     R.ev.act = net->ev_act; R.ev.val = net->ev_val; R.ev.rew = net->ev_rew; R.ev.done = net->ev_done;
     hipStream_t st = h->stream;
-    FNET_HIP(net, hipMemsetD32Async((hipDeviceptr_t)net->d_counter, (int)(uint32_t)net->act_counter, 1, st));
-    FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ro_args), &R, sizeof(RolloutArgs), (size_t)net->arg_slot * sizeof(RolloutArgs),
+    PAAC_HIP(net, hipMemsetD32Async((hipDeviceptr_t)net->d_counter, (int)(uint32_t)net->act_counter, 1, st));
+    PAAC_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ro_args), &R, sizeof(RolloutArgs), (size_t)net->arg_slot * sizeof(RolloutArgs),
                                          hipMemcpyHostToDevice, st));
-    FNET_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &R.f, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
+    PAAC_HIP(net, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_flat_args), &R.f, sizeof(FlatArgs), (size_t)net->arg_slot * sizeof(FlatArgs),
                                          hipMemcpyHostToDevice, st));
     (void)hipGetLastError();
     hipLaunchKernelGGL(kernels[gi], dim3((h->E + G - 1) / G), dim3(FNT), lds_bytes, st, net->arg_slot, live_off);
-    FNET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -716,19 +647,19 @@ int grl_fnet_create(grl_handle *h, const grl_fnet_config *cfg, grl_fnet **out) {
     hipSetDevice(h->cfg.device_id);
     grl_fnet *n = new grl_fnet();
     n->h = h; n->cfg = *cfg;
-    n->off = make_offsets(cfg->temporal_size, cfg->static_size, cfg->num_actions);
+    n->off = make_offsets(cfg->temporal_size, cfg->static_size, cfg->num_actions); n->num_params = n->off.total;
     n->wso = ws_offsets(cfg->rnn_length, cfg->num_actions);
     n->slab_blocks = 512;      // two workgroups per CU (LDS 75 KB each)
     size_t ms = cfg->max_samples;
     const int A = cfg->num_actions, S0 = cfg->static_size, D = cfg->temporal_size, T = cfg->rnn_length;
     int rc = GRL_OK;
-    auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = falloc(n, p, cnt); };
+    auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };
     Al(&n->params, n->off.total); Al(&n->paramsT, n->off.total); Al(&n->grads, n->off.total); Al(&n->adam_m, n->off.total); Al(&n->adam_v, n->off.total);
     Al(&n->ws, (ms + 63) / 64 * 64 * n->wso.total); Al(&n->slab, (size_t)n->slab_blocks * n->off.total); Al(&n->stats, 8);
     Al(&n->d_states, ms * S0); Al(&n->d_hist, ms * T * D); Al(&n->d_act, ms * A); Al(&n->d_adv, ms); Al(&n->d_y, ms);
     Al(&n->mu, ms * A); Al(&n->sigma, ms * A); Al(&n->vs, ms);
-    if (rc == GRL_OK) rc = falloc(n, &n->stats64, 4 + kSumsqBlocks);      // loss sums (2 used of 4), then the squares' partial sums
-    if (rc == GRL_OK) rc = falloc(n, &n->d_counter, 4);
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->stats64, 4 + kSumsqBlocks);      // loss sums (2 used of 4), then the squares' partial sums
+    if (rc == GRL_OK) rc = paac_alloc(n, &n->d_counter, 4);
     n->ro_graph = nullptr; n->ro_graph_T = 0; n->ro_graph_ep = false; n->ro_graph_greedy = 0; n->greedy = 0;
     n->ev_total = nullptr; n->ev_trace = 0; n->ev_trace_cap = -1; n->ev_played = -2; memset(n->ev_attr_set, 0, sizeof(n->ev_attr_set));
     {   // GRL_FLAT_ROLLOUT=graph keeps the launch-per-stage rollout (captured into a hipGraph) for A/B and for the equality tests
@@ -746,8 +677,7 @@ int grl_fnet_create(grl_handle *h, const grl_fnet_config *cfg, grl_fnet **out) {
     n->true_window = 0; n->ro_slab = nullptr; n->slab_T = 0; n->w_len = n->w_elapsed = n->w_episode = nullptr; n->w_src = nullptr;
     n->w_restart_all = 1; n->w_have = 0; n->w_valid = 0; n->ev_ring = nullptr; n->ro_graph_tw = 0;
     memset(n->ro_win_attr_set, 0, sizeof(n->ro_win_attr_set)); memset(n->ev_win_attr_set, 0, sizeof(n->ev_win_attr_set));
-    n->last_n = 0; n->comm = nullptr; n->comm_world = 1; n->comm_rank = 0;
-    n->ar_ev0 = n->ar_ev1 = nullptr; n->ar_pending = 0; n->ar_calls = 0; n->ar_ms_total = 0.0; n->ar_ms_last = 0.f;
+    n->last_n = 0;
     hipError_t e = hipSuccess;
     if (rc == GRL_OK) e = hipFuncSetAttribute((const void *)flat_forward_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLAT_LDS_BYTES);
     if (rc == GRL_OK && e == hipSuccess)
@@ -765,7 +695,7 @@ int grl_fnet_create(grl_handle *h, const grl_fnet_config *cfg, grl_fnet **out) {
         e = hipFuncSetAttribute((const void *)flat_forward_win_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ff_lds_bytes(MAXS0));
     if (rc == GRL_OK && e == hipSuccess)
         e = hipFuncSetAttribute((const void *)flat_backward_fast_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FB2_LDS_BYTES);
-    if (rc == GRL_OK && e != hipSuccess) rc = ffail(n, GRL_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
+    if (rc == GRL_OK && e != hipSuccess) rc = paac_fail(n, GRL_E_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
     if (rc != GRL_OK) {
         fail(h, rc, "grl_fnet_create: " + n->err);
         grl_fnet_destroy(n);
@@ -780,33 +710,20 @@ int grl_fnet_destroy(grl_fnet *n) {
     if (!n) return GRL_OK;
     grl_sync_for_destroy(n->h);      // the handle may have been destroyed first (finaliser order of a host binding)
     if (n->ro_graph) (void)hipGraphExecDestroy(n->ro_graph);
-    if (n->comm) {
-        ncclCommDestroy((ncclComm_t)n->comm);
-        (void)hipGetLastError();   // RCCL teardown may leave a stale HIP error on this thread
-    }
-    if (n->ar_ev0) { hipEventDestroy(n->ar_ev0); hipEventDestroy(n->ar_ev1); }
+    paac_comm_release(n);
     flat_slot_release(n->arg_slot);
-    for (void *p : n->allocs) hipFree(p);
+    paac_free(n);
     for (void *p : n->ev_allocs) hipFree(p);
     delete n;
     return GRL_OK;
 }
 
-const char *grl_fnet_last_error(const grl_fnet *n) { return n ? n->err.c_str() : ""; }
-int64_t grl_fnet_num_params(const grl_fnet *n) { return n ? n->off.total : 0; }
+const char *grl_fnet_last_error(const grl_fnet *n) { return paac_last_error(n); }
+int64_t grl_fnet_num_params(const grl_fnet *n) { return paac_num_params(n); }
 
-static int fcopy_flat(grl_fnet *n, float *dev, float *host, int64_t cnt, bool to_dev) {
-    if (!n || !host) return GRL_E_INVALID;
-    if (cnt != n->off.total) return ffail(n, GRL_E_SIZE, "expected " + std::to_string(n->off.total) + " floats");
-    hipSetDevice(n->h->cfg.device_id);
-    FNET_HIP(n, hipStreamSynchronize(n->h->stream));
-    if (to_dev) FNET_HIP(n, hipMemcpy(dev, host, cnt * 4, hipMemcpyHostToDevice));
-    else FNET_HIP(n, hipMemcpy(host, dev, cnt * 4, hipMemcpyDeviceToHost));
-    return GRL_OK;
-}
 int grl_fnet_set_params(grl_fnet *n, const float *host, int64_t cnt) {
     if (n) n->ws_resident = 0;
-    return fcopy_flat(n, n ? n->params : nullptr, (float *)host, cnt, true);
+    return paac_copy_flat(n, nullptr, n ? n->params : nullptr, (float *)host, cnt, true);
 }
 
 int grl_fnet_set_keep_activations(grl_fnet *net, int32_t on) {
@@ -814,54 +731,36 @@ int grl_fnet_set_keep_activations(grl_fnet *net, int32_t on) {
     net->keep_activations = on ? 1 : 0;
     return GRL_OK;
 }
-int grl_fnet_get_params(grl_fnet *n, float *host, int64_t cnt) { return fcopy_flat(n, n ? n->params : nullptr, host, cnt, false); }
-int grl_fnet_get_grads(grl_fnet *n, float *host, int64_t cnt) { return fcopy_flat(n, n ? n->grads : nullptr, host, cnt, false); }
+int grl_fnet_get_params(grl_fnet *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->params : nullptr, host, cnt, false); }
+int grl_fnet_get_grads(grl_fnet *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->grads : nullptr, host, cnt, false); }
 
 int grl_fnet_get_optimizer_state(grl_fnet *n, float *m_host, float *v_host, int64_t cnt, int64_t *step_out) {
-    if (!n || !m_host || !v_host || !step_out) return GRL_E_INVALID;
-    int rc = fcopy_flat(n, n->adam_m, m_host, cnt, false);
-    if (rc == GRL_OK) rc = fcopy_flat(n, n->adam_v, v_host, cnt, false);
-    *step_out = n->adam_t;
-    return rc;
+    return paac_get_optimizer_state(n, m_host, v_host, cnt, step_out);
 }
-
 int grl_fnet_set_optimizer_state(grl_fnet *n, const float *m_host, const float *v_host, int64_t cnt, int64_t step) {
-    if (!n || !m_host || !v_host || step < 0) return GRL_E_INVALID;
-    int rc = fcopy_flat(n, n->adam_m, (float *)m_host, cnt, true);
-    if (rc == GRL_OK) rc = fcopy_flat(n, n->adam_v, (float *)v_host, cnt, true);
-    if (rc == GRL_OK) n->adam_t = (long)step;
-    return rc;
+    return paac_set_optimizer_state(n, nullptr, m_host, v_host, cnt, step);
 }
 
-int grl_fnet_get_action_counter(grl_fnet *net, uint64_t *out) {
-    if (!net || !out) return GRL_E_INVALID;
-    *out = (uint64_t)net->act_counter;
-    return GRL_OK;
-}
-
-int grl_fnet_set_action_counter(grl_fnet *net, uint64_t value) {
-    if (!net) return GRL_E_INVALID;
-    net->act_counter = (unsigned long)value;
-    return GRL_OK;
-}
+int grl_fnet_get_action_counter(grl_fnet *net, uint64_t *out) { return paac_get_action_counter(net, out); }
+int grl_fnet_set_action_counter(grl_fnet *net, uint64_t value) { return paac_set_action_counter(net, value); }
 
 static int fdownload(grl_fnet *net, int n, float *mu, float *sigma, float *vs) {
     const int A = net->cfg.num_actions;
-    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
-    if (mu) FNET_HIP(net, hipMemcpy(mu, net->mu, (size_t)n * A * 4, hipMemcpyDeviceToHost));
-    if (sigma) FNET_HIP(net, hipMemcpy(sigma, net->sigma, (size_t)n * A * 4, hipMemcpyDeviceToHost));
-    if (vs) FNET_HIP(net, hipMemcpy(vs, net->vs, (size_t)n * 4, hipMemcpyDeviceToHost));
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
+    if (mu) PAAC_HIP(net, hipMemcpy(mu, net->mu, (size_t)n * A * 4, hipMemcpyDeviceToHost));
+    if (sigma) PAAC_HIP(net, hipMemcpy(sigma, net->sigma, (size_t)n * A * 4, hipMemcpyDeviceToHost));
+    if (vs) PAAC_HIP(net, hipMemcpy(vs, net->vs, (size_t)n * 4, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 
 int grl_fnet_predict(grl_fnet *net, int32_t n, const float *states, const float *history, float *mu, float *sigma, float *vs) {
-    if (!net || n <= 0 || !states || !history) return ffail(net, GRL_E_INVALID, "grl_fnet_predict: bad argument");
-    if (n > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "grl_fnet_predict: n exceeds max_samples");
+    if (!net || n <= 0 || !states || !history) return paac_fail(net, GRL_E_INVALID, "grl_fnet_predict: bad argument");
+    if (n > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "grl_fnet_predict: n exceeds max_samples");
     hipSetDevice(net->h->cfg.device_id);
     const grl_fnet_config &c = net->cfg;
     hipStream_t st = net->h->stream;
-    FNET_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * c.static_size * 4, hipMemcpyHostToDevice, st));
-    FNET_HIP(net, hipMemcpyAsync(net->d_hist, history, (size_t)n * c.rnn_length * c.temporal_size * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * c.static_size * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_hist, history, (size_t)n * c.rnn_length * c.temporal_size * 4, hipMemcpyHostToDevice, st));
     int rc = launch_forward(net, n, net->d_states, net->d_hist, net->mu, net->sigma, net->vs, false);
     if (rc) return rc;
     return fdownload(net, n, mu, sigma, vs);
@@ -871,16 +770,16 @@ static int check_env(grl_fnet *net) {
     grl_handle *h = net->h;
     if (h->cfg.env_kind == GRL_ENV_SOLOW) {
         if (net->cfg.static_size != 2 || net->cfg.temporal_size != 2 || net->cfg.rnn_length != h->cfg.rnn_length || net->cfg.num_actions != 1)
-            return ffail(net, GRL_E_INVALID, "a Solow handle needs a net with static=temporal=2, num_actions=1 and the handle's rnn_length");
+            return paac_fail(net, GRL_E_INVALID, "a Solow handle needs a net with static=temporal=2, num_actions=1 and the handle's rnn_length");
     } else if (h->cfg.env_kind == GRL_ENV_TRADE) {
         const int S = 1 + 2 * h->cfg.n_assets;      // INPUT_SIZE = TEMPORAL_SIZE = 1+2n, NUM_ACTIONS = n (train_trade.py:38-40)
         if (net->cfg.static_size != S || net->cfg.temporal_size != S || net->cfg.num_actions != h->cfg.n_assets ||
             net->cfg.rnn_length != h->cfg.rnn_length)
-            return ffail(net, GRL_E_INVALID, "a TradeAR1 handle needs a net with static=temporal=1+2n, num_actions=n and the handle's rnn_length");
+            return paac_fail(net, GRL_E_INVALID, "a TradeAR1 handle needs a net with static=temporal=1+2n, num_actions=n and the handle's rnn_length");
     } else {
-        return ffail(net, GRL_E_INVALID, "this call needs a Solow or TradeAR1 handle");
+        return paac_fail(net, GRL_E_INVALID, "this call needs a Solow or TradeAR1 handle");
     }
-    if (h->E > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "num_envs exceeds max_samples of the net");
+    if (h->E > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "num_envs exceeds max_samples of the net");
     return GRL_OK;
 }
 
@@ -896,7 +795,7 @@ int grl_fnet_predict_env(grl_fnet *net, float *mu, float *sigma, float *vs) {
         const float *obs = h->cfg.env_kind == GRL_ENV_SOLOW ? h->so.obs : h->tr.obs;
         if ((rc = window_ensure_slab(net, net->T > 0 ? net->T : 1))) return rc;
         if ((rc = window_enter(net))) return rc;
-        FNET_HIP(net, hipMemcpyAsync(net->ro_states, obs, (size_t)h->E * net->cfg.static_size * 4, hipMemcpyDeviceToDevice, h->stream));
+        PAAC_HIP(net, hipMemcpyAsync(net->ro_states, obs, (size_t)h->E * net->cfg.static_size * 4, hipMemcpyDeviceToDevice, h->stream));
         if ((rc = launch_forward(net, h->E, net->ro_states, nullptr, net->mu, net->sigma, net->vs, false, net->w_len, h->E))) return rc;
         return fdownload(net, h->E, mu, sigma, vs);
     }
@@ -908,37 +807,37 @@ int grl_fnet_predict_env(grl_fnet *net, float *mu, float *sigma, float *vs) {
 
 int grl_fnet_train(grl_fnet *net, int32_t n, const float *states, const float *history, const float *actions, const float *advantages,
                    const float *critic_target, float lr, int32_t apply_update, float *stats_host) {
-    if (!net || n <= 0 || !states || !history || !actions || !advantages || !critic_target) return ffail(net, GRL_E_INVALID, "grl_fnet_train: bad argument");
-    if (n > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "grl_fnet_train: n exceeds max_samples");
+    if (!net || n <= 0 || !states || !history || !actions || !advantages || !critic_target) return paac_fail(net, GRL_E_INVALID, "grl_fnet_train: bad argument");
+    if (n > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "grl_fnet_train: n exceeds max_samples");
     hipSetDevice(net->h->cfg.device_id);
     const grl_fnet_config &c = net->cfg;
     hipStream_t st = net->h->stream;
-    FNET_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * c.static_size * 4, hipMemcpyHostToDevice, st));
-    FNET_HIP(net, hipMemcpyAsync(net->d_hist, history, (size_t)n * c.rnn_length * c.temporal_size * 4, hipMemcpyHostToDevice, st));
-    FNET_HIP(net, hipMemcpyAsync(net->d_act, actions, (size_t)n * c.num_actions * 4, hipMemcpyHostToDevice, st));
-    FNET_HIP(net, hipMemcpyAsync(net->d_adv, advantages, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    FNET_HIP(net, hipMemcpyAsync(net->d_y, critic_target, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * c.static_size * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_hist, history, (size_t)n * c.rnn_length * c.temporal_size * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_act, actions, (size_t)n * c.num_actions * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_adv, advantages, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(net->d_y, critic_target, (size_t)n * 4, hipMemcpyHostToDevice, st));
     return train_device(net, n, net->d_states, net->d_hist, net->d_act, net->d_adv, net->d_y, lr, apply_update, stats_host);
 }
 
 int grl_fnet_rollout(grl_fnet *net, int32_t T) {
-    if (!net || T <= 0 || T > 1024) return ffail(net, GRL_E_INVALID, "grl_fnet_rollout: bad argument");
+    if (!net || T <= 0 || T > 1024) return paac_fail(net, GRL_E_INVALID, "grl_fnet_rollout: bad argument");
     hipSetDevice(net->h->cfg.device_id);
     int rc = check_env(net);
     if (rc) return rc;
     grl_handle *h = net->h;
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     const int E = h->E, R = net->cfg.rnn_length, S0 = net->cfg.static_size, A = net->cfg.num_actions;
-    if ((long)T * E > net->cfg.max_samples) return ffail(net, GRL_E_SIZE, "grl_fnet_rollout: T*num_envs exceeds max_samples");
+    if ((long)T * E > net->cfg.max_samples) return paac_fail(net, GRL_E_SIZE, "grl_fnet_rollout: T*num_envs exceeds max_samples");
     const bool tw = net->true_window != 0;
     if (!net->ro_act || net->T < T) {
-        auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = falloc(net, p, cnt); };
+        auto Al = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(net, p, cnt); };
         if (!tw) Al(&net->ro_states, (size_t)T * E * S0);      // true window: the states live in the slab
         Al(&net->ro_act, (size_t)T * E * A);
         Al(&net->ro_envact, (size_t)E * A); Al(&net->ro_val, (size_t)T * E); Al(&net->ro_rew, (size_t)T * E); Al(&net->ro_mask, (size_t)T * E);
         Al(&net->ro_y, (size_t)T * E); Al(&net->ro_adv, (size_t)T * E); Al(&net->ro_boot, E);
         if (solow) Al(&net->ro_hist, (size_t)T * E * R * 2);
-        if (rc == GRL_OK) rc = falloc(net, &net->ro_nhist, (size_t)T * E);
+        if (rc == GRL_OK) rc = paac_alloc(net, &net->ro_nhist, (size_t)T * E);
         if (rc) return rc;
     }
     if (tw) {
@@ -949,7 +848,7 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     net->ws_resident = 0;      // set again by a persistent rollout that keeps its activations
     hipStream_t st = h->stream;
     // draw counter of step t = act_counter + t, read by the sample kernel from device memory
-    FNET_HIP(net, hipMemsetD32Async((hipDeviceptr_t)net->d_counter, (int)(uint32_t)net->act_counter, 1, st));
+    PAAC_HIP(net, hipMemsetD32Async((hipDeviceptr_t)net->d_counter, (int)(uint32_t)net->act_counter, 1, st));
     if (!net->greedy) net->act_counter += (unsigned long)T;
     // one workgroup per 64 envs and one workgroup per CU (its LDS): beyond two rounds of workgroups (E > 32 768) the graph of
     // launches takes over.  Measured at the end of round 5, persistent / graph, ms per 20-step rollout: TradeAR1-16 32 768 envs
@@ -964,7 +863,7 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
     // (the graph holds the buffers' addresses: a true-window graph is only replayed while the slab is the one it was captured on)
     if (net->ro_graph && net->ro_graph_T == T && net->ro_graph_ep == (h->ep_total != nullptr) && net->ro_graph_greedy == net->greedy &&
         net->ro_graph_tw == (tw ? 1 : 0) && (!tw || net->ro_graph_slab == net->ro_slab)) {
-        FNET_HIP(net, hipGraphLaunch(net->ro_graph, st));
+        PAAC_HIP(net, hipGraphLaunch(net->ro_graph, st));
     } else {
         if (net->ro_graph) { (void)hipGraphExecDestroy(net->ro_graph); net->ro_graph = nullptr; }
         // ~9 tiny operations per step: capture them once into a graph; every argument is a device pointer or a constant
@@ -986,13 +885,13 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
             }
             if (graph) (void)hipGraphDestroy(graph);
             if (rc) return rc;
-            if (net->ro_graph) FNET_HIP(net, hipGraphLaunch(net->ro_graph, st));
+            if (net->ro_graph) PAAC_HIP(net, hipGraphLaunch(net->ro_graph, st));
             else if ((rc = enqueue_rollout(net, T))) return rc;      // capture unavailable: plain launches
         } else if (rc) {
             return rc;
         }
     }
-    FNET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     h->step_in_flight = true;
     return tw ? window_leave(net, T) : GRL_OK;
 }
@@ -1000,7 +899,7 @@ int grl_fnet_rollout(grl_fnet *net, int32_t T) {
 int grl_fnet_set_true_window(grl_fnet *net, int32_t on) {
     if (!net) return GRL_E_INVALID;
     if (net->cfg.static_size != net->cfg.temporal_size)
-        return ffail(net, GRL_E_INVALID, "grl_fnet_set_true_window: the window's rows are the states, so static_size must equal temporal_size");
+        return paac_fail(net, GRL_E_INVALID, "grl_fnet_set_true_window: the window's rows are the states, so static_size must equal temporal_size");
     net->true_window = on ? 1 : 0;
     net->ws_resident = 0;      // kept activations are dropped
     net->w_restart_all = 1; net->w_have = 0; net->w_valid = 0;      // every window restarts at the next call
@@ -1008,22 +907,22 @@ int grl_fnet_set_true_window(grl_fnet *net, int32_t on) {
 }
 
 int grl_fnet_read_windows(grl_fnet *net, int32_t first, int32_t count, float *host, size_t bytes) {
-    if (!net || (!host && count > 0)) return ffail(net, GRL_E_INVALID, "grl_fnet_read_windows: bad argument");
+    if (!net || (!host && count > 0)) return paac_fail(net, GRL_E_INVALID, "grl_fnet_read_windows: bad argument");
     if (!net->true_window || !net->ro_act || net->T <= 0 || !net->w_valid)
-        return ffail(net, GRL_E_STATE, "grl_fnet_read_windows: no true-window rollout to read (none yet, or its rows were carried forward)");
+        return paac_fail(net, GRL_E_STATE, "grl_fnet_read_windows: no true-window rollout to read (none yet, or its rows were carried forward)");
     const long TE = (long)net->T * net->h->E;
     const int R = net->cfg.rnn_length, D = net->cfg.temporal_size;
-    if (first < 0 || count < 0 || (long)first + count > TE) return ffail(net, GRL_E_SIZE, "grl_fnet_read_windows: samples out of range");
-    if (bytes != (size_t)count * R * D * 4) return ffail(net, GRL_E_SIZE, "grl_fnet_read_windows: wrong size");
+    if (first < 0 || count < 0 || (long)first + count > TE) return paac_fail(net, GRL_E_SIZE, "grl_fnet_read_windows: samples out of range");
+    if (bytes != (size_t)count * R * D * 4) return paac_fail(net, GRL_E_SIZE, "grl_fnet_read_windows: wrong size");
     if (count == 0) return GRL_OK;
     hipSetDevice(net->h->cfg.device_id);
     hipStream_t st = net->h->stream;
     const long total = (long)count * R * D;
     hipLaunchKernelGGL(flat_window_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float *)net->ro_states,
                        (const int32_t *)net->ro_nhist, net->h->E, first, count, R, D, net->d_hist);
-    FNET_HIP(net, hipGetLastError());
-    FNET_HIP(net, hipStreamSynchronize(st));
-    FNET_HIP(net, hipMemcpy(host, net->d_hist, bytes, hipMemcpyDeviceToHost));
+    PAAC_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipStreamSynchronize(st));
+    PAAC_HIP(net, hipMemcpy(host, net->d_hist, bytes, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 
@@ -1035,7 +934,7 @@ int grl_fnet_set_greedy(grl_fnet *net, int32_t on) {
 
 int grl_fnet_eval(grl_fnet *net, int32_t max_steps, int32_t trace_steps, int32_t greedy) {
     if (!net) return GRL_E_INVALID;
-    if (max_steps < 1 || trace_steps < 0) return ffail(net, GRL_E_INVALID, "grl_fnet_eval: max_steps >= 1, trace_steps >= 0");
+    if (max_steps < 1 || trace_steps < 0) return paac_fail(net, GRL_E_INVALID, "grl_fnet_eval: max_steps >= 1, trace_steps >= 0");
     grl_handle *h = net->h;
     hipSetDevice(h->cfg.device_id);
     int rc = check_env(net);
@@ -1051,23 +950,23 @@ int grl_fnet_eval(grl_fnet *net, int32_t max_steps, int32_t trace_steps, int32_t
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     const int E = h->E;
     hipStream_t st = h->stream;
-    if ((rc = launch_iota(h, h->done_list, E))) return ffail(net, rc, h->err);
+    if ((rc = launch_iota(h, h->done_list, E))) return paac_fail(net, rc, h->err);
     net->ev_reset_count = E;
-    FNET_HIP(net, hipMemcpyAsync(h->done_count, &net->ev_reset_count, 4, hipMemcpyHostToDevice, st));
+    PAAC_HIP(net, hipMemcpyAsync(h->done_count, &net->ev_reset_count, 4, hipMemcpyHostToDevice, st));
     rc = solow ? solow_launch_reset(h, h->done_list, h->done_count, E, true) : trade_launch_reset(h, h->done_list, h->done_count, E);
-    if (rc) return ffail(net, rc, h->err);
+    if (rc) return paac_fail(net, rc, h->err);
     return GRL_OK;
 }
 
 int grl_fnet_read_eval(grl_fnet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return ffail(net, GRL_E_INVALID, "grl_fnet_read_eval: bad argument");
-    if (net->ev_played == -2) return ffail(net, GRL_E_STATE, "grl_fnet_read_eval: no evaluation yet");
+    if (!net || !which || !host) return paac_fail(net, GRL_E_INVALID, "grl_fnet_read_eval: bad argument");
+    if (net->ev_played == -2) return paac_fail(net, GRL_E_STATE, "grl_fnet_read_eval: no evaluation yet");
     hipSetDevice(net->h->cfg.device_id);
-    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
     const size_t E = net->h->E, S0 = net->cfg.static_size, A = net->cfg.num_actions;
     if (net->ev_played < 0) {      // steps the call played = the longest episode
         std::vector<int32_t> len(E);
-        FNET_HIP(net, hipMemcpy(len.data(), net->ev_len, E * 4, hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipMemcpy(len.data(), net->ev_len, E * 4, hipMemcpyDeviceToHost));
         int32_t mx = 0;
         for (int32_t l : len) mx = l > mx ? l : mx;
         net->ev_played = mx;
@@ -1080,11 +979,11 @@ int grl_fnet_read_eval(grl_fnet *net, const char *which, void *host, size_t byte
         {"values", net->ev_val, SE * 4}, {"rewards", net->ev_rew, SE * 4}, {"dones", net->ev_done, SE * 4}};
     for (auto &e : tab)
         if (!strcmp(which, e.name)) {
-            if (bytes != e.n) return ffail(net, GRL_E_SIZE, std::string("grl_fnet_read_eval: wrong size for ") + which);
-            if (bytes) FNET_HIP(net, hipMemcpy(host, e.p, bytes, hipMemcpyDeviceToHost));
+            if (bytes != e.n) return paac_fail(net, GRL_E_SIZE, std::string("grl_fnet_read_eval: wrong size for ") + which);
+            if (bytes) PAAC_HIP(net, hipMemcpy(host, e.p, bytes, hipMemcpyDeviceToHost));
             return GRL_OK;
         }
-    return ffail(net, GRL_E_INVALID, std::string("grl_fnet_read_eval: unknown buffer ") + which);
+    return paac_fail(net, GRL_E_INVALID, std::string("grl_fnet_read_eval: unknown buffer ") + which);
 }
 
 // Debug / profiling: attach a timestamp buffer to the persistent rollout and read the stage clock of workgroup 0 after the next
@@ -1093,26 +992,26 @@ int grl_fnet_rollout_stage_times(grl_fnet *net, int64_t *out, int32_t max, int32
     if (!net || !n_out) return GRL_E_INVALID;
     hipSetDevice(net->h->cfg.device_id);
     if (!net->d_ts) {
-        int rc = falloc(net, &net->d_ts, 4096);
-        if (rc == GRL_OK) rc = falloc(net, &net->d_ts_n, 4);
+        int rc = paac_alloc(net, &net->d_ts, 4096);
+        if (rc == GRL_OK) rc = paac_alloc(net, &net->d_ts_n, 4);
         *n_out = 0;
         return rc;
     }
-    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
     int n = 0;
-    FNET_HIP(net, hipMemcpy(&n, net->d_ts_n, sizeof(int), hipMemcpyDeviceToHost));
+    PAAC_HIP(net, hipMemcpy(&n, net->d_ts_n, sizeof(int), hipMemcpyDeviceToHost));
     if (n > max) n = max;
-    if (out && n > 0) FNET_HIP(net, hipMemcpy(out, net->d_ts, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out && n > 0) PAAC_HIP(net, hipMemcpy(out, net->d_ts, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost));
     *n_out = n;
     return GRL_OK;
 }
 
 int grl_fnet_train_rollout(grl_fnet *net, float lr, float *stats_host) {
-    if (!net || !net->ro_states || net->T <= 0) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout: no rollout to train on");
+    if (!net || !net->ro_states || net->T <= 0) return paac_fail(net, GRL_E_STATE, "grl_fnet_train_rollout: no rollout to train on");
     hipSetDevice(net->h->cfg.device_id);
     const int n = net->T * net->h->E;
     if (net->true_window) {
-        if (!net->w_valid) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout: the last rollout's windows were carried forward");
+        if (!net->w_valid) return paac_fail(net, GRL_E_STATE, "grl_fnet_train_rollout: the last rollout's windows were carried forward");
         return train_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, lr, 1, stats_host, net->ro_nhist, false, net->h->E);
     }
     return train_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, lr, 1, stats_host, net->ro_nhist,
@@ -1122,10 +1021,10 @@ int grl_fnet_train_rollout(grl_fnet *net, float lr, float *stats_host) {
 // the gradient step in two halves for callers that exchange gradients themselves (host all-reduce through gloo when no RCCL
 // communicator can be formed): _grads leaves the LOCAL mean gradient in the net, nothing is updated
 int grl_fnet_train_rollout_grads(grl_fnet *net, float *stats_host) {
-    if (!net || !net->ro_states || net->T <= 0) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout_grads: no rollout to train on");
+    if (!net || !net->ro_states || net->T <= 0) return paac_fail(net, GRL_E_STATE, "grl_fnet_train_rollout_grads: no rollout to train on");
     hipSetDevice(net->h->cfg.device_id);
     const int n = net->T * net->h->E;
-    if (net->true_window && !net->w_valid) return ffail(net, GRL_E_STATE, "grl_fnet_train_rollout_grads: the last rollout's windows were carried forward");
+    if (net->true_window && !net->w_valid) return paac_fail(net, GRL_E_STATE, "grl_fnet_train_rollout_grads: the last rollout's windows were carried forward");
     int rc = net->true_window
                  ? train_grads_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, net->ro_nhist, false, net->h->E)
                  : train_grads_device(net, n, net->ro_states, nullptr, net->ro_act, net->ro_adv, net->ro_y, net->ro_nhist, net->ws_resident != 0);
@@ -1133,73 +1032,33 @@ int grl_fnet_train_rollout_grads(grl_fnet *net, float *stats_host) {
     return train_apply_device(net, 0.f, 0, 1.0f, stats_host);
 }
 
-int grl_fnet_set_grads(grl_fnet *n, const float *host, int64_t cnt) { return fcopy_flat(n, n ? n->grads : nullptr, (float *)host, cnt, true); }
+int grl_fnet_set_grads(grl_fnet *n, const float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->grads : nullptr, (float *)host, cnt, true); }
 
 int grl_fnet_apply_grads(grl_fnet *net, float lr, float grad_scale, float *stats_host) {
-    if (!net || net->last_n <= 0) return ffail(net, GRL_E_STATE, "grl_fnet_apply_grads: no gradient pass has run yet");
+    if (!net || net->last_n <= 0) return paac_fail(net, GRL_E_STATE, "grl_fnet_apply_grads: no gradient pass has run yet");
     hipSetDevice(net->h->cfg.device_id);
     return train_apply_device(net, lr, 1, grad_scale, stats_host);
 }
 
 int grl_fnet_comm_init(grl_fnet *net, const void *unique_id, size_t bytes, int32_t rank, int32_t world_size) {
-    if (!net || !unique_id || bytes != sizeof(ncclUniqueId) || world_size < 1 || rank < 0 || rank >= world_size)
-        return ffail(net, GRL_E_INVALID, "grl_fnet_comm_init: bad argument");
-    if (net->comm) return ffail(net, GRL_E_STATE, "grl_fnet_comm_init: communicator already attached");
-    hipSetDevice(net->h->cfg.device_id);
-    ncclUniqueId id;
-    memcpy(&id, unique_id, sizeof(id));
-    ncclComm_t comm;
-    ncclResult_t r = ncclCommInitRank(&comm, world_size, id, rank);
-    (void)hipGetLastError();
-    if (r != ncclSuccess) return ffail(net, GRL_E_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-    net->comm = (void *)comm; net->comm_world = world_size; net->comm_rank = rank;
-    return GRL_OK;
+    return paac_comm_init(net, "grl_fnet_comm_init", unique_id, bytes, rank, world_size);
 }
 
 int grl_fnet_comm_info(grl_fnet *net, int32_t *count_out, int32_t *user_rank_out, int64_t *allreduce_calls_out,
                        double *allreduce_ms_total_out, float *allreduce_ms_last_out) {
-    if (!net) return GRL_E_INVALID;
-    int count = 0, urank = -1;
-    if (net->comm) {
-        ncclResult_t r = ncclCommCount((ncclComm_t)net->comm, &count);
-        if (r == ncclSuccess) r = ncclCommUserRank((ncclComm_t)net->comm, &urank);
-        (void)hipGetLastError();
-        if (r != ncclSuccess) return ffail(net, GRL_E_COMM, std::string("ncclCommCount: ") + ncclGetErrorString(r));
-    }
-    if (count_out) *count_out = count;
-    if (user_rank_out) *user_rank_out = urank;
-    if (allreduce_calls_out) *allreduce_calls_out = net->ar_calls;
-    if (allreduce_ms_total_out) *allreduce_ms_total_out = net->ar_ms_total;
-    if (allreduce_ms_last_out) *allreduce_ms_last_out = net->ar_ms_last;
-    return GRL_OK;
+    return paac_comm_info(net, count_out, user_rank_out, allreduce_calls_out, allreduce_ms_total_out, allreduce_ms_last_out);
 }
 
 int grl_fnet_comm_broadcast_params(grl_fnet *net, int32_t root) {
-    if (!net || !net->comm) return ffail(net, GRL_E_STATE, "grl_fnet_comm_broadcast_params: no communicator");
-    hipSetDevice(net->h->cfg.device_id);
-    net->ws_resident = 0;      // the parameters may move (every rank but the root)
-    ncclResult_t r = ncclBroadcast(net->params, net->params, (size_t)net->off.total, ncclFloat, root, (ncclComm_t)net->comm, net->h->stream);
-    (void)hipGetLastError();
-    if (r != ncclSuccess) return ffail(net, GRL_E_COMM, std::string("ncclBroadcast: ") + ncclGetErrorString(r));
-    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
-    return GRL_OK;
+    if (net && net->comm) net->ws_resident = 0;      // the parameters may move (every rank but the root)
+    return paac_comm_broadcast_params(net, "grl_fnet_comm_broadcast_params", root);
 }
 
-int grl_fnet_comm_destroy(grl_fnet *net) {
-    if (!net) return GRL_E_INVALID;
-    if (net->comm) {
-        hipSetDevice(net->h->cfg.device_id);
-        hipStreamSynchronize(net->h->stream);
-        ncclCommDestroy((ncclComm_t)net->comm);
-        (void)hipGetLastError();
-        net->comm = nullptr; net->comm_world = 1; net->comm_rank = 0;
-    }
-    return GRL_OK;
-}
+int grl_fnet_comm_destroy(grl_fnet *net) { return paac_comm_destroy(net); }
 
 int grl_fnet_read_rollout(grl_fnet *net, const char *which, void *host, size_t bytes) {
     if (!net || !which || !host) return GRL_E_INVALID;
-    if (!net->ro_states) return ffail(net, GRL_E_STATE, "grl_fnet_read_rollout: no rollout yet");
+    if (!net->ro_states) return paac_fail(net, GRL_E_STATE, "grl_fnet_read_rollout: no rollout yet");
     hipSetDevice(net->h->cfg.device_id);
     std::string w(which);
     const size_t TE = (size_t)net->T * net->h->E;
@@ -1215,16 +1074,16 @@ int grl_fnet_read_rollout(grl_fnet *net, const char *which, void *host, size_t b
     else if (w == "states") { src = net->ro_states; need = TE * net->cfg.static_size * 4; }
     else if (w == "histories" && net->true_window) {      // the true windows, dense: grl_fnet_read_windows over every sample
         need = TE * net->cfg.rnn_length * net->cfg.temporal_size * 4;
-        if (need != bytes) return ffail(net, GRL_E_SIZE, "grl_fnet_read_rollout: 'histories' needs " + std::to_string(need) + " bytes");
+        if (need != bytes) return paac_fail(net, GRL_E_SIZE, "grl_fnet_read_rollout: 'histories' needs " + std::to_string(need) + " bytes");
         return grl_fnet_read_windows(net, 0, (int32_t)TE, (float *)host, bytes);
     }
     else if (w == "histories") { src = net->ro_hist; need = TE * net->cfg.rnn_length * 8; }
     else if (w == "nhist") { src = net->ro_nhist; need = TE * 4; }
-    else return ffail(net, GRL_E_INVALID, "grl_fnet_read_rollout: unknown buffer '" + w + "'");
-    if (!src) return ffail(net, GRL_E_INVALID, "grl_fnet_read_rollout: '" + w + "' does not exist for this env kind");
-    if (need != bytes) return ffail(net, GRL_E_SIZE, "grl_fnet_read_rollout: '" + w + "' needs " + std::to_string(need) + " bytes");
-    FNET_HIP(net, hipStreamSynchronize(net->h->stream));
-    FNET_HIP(net, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+    else return paac_fail(net, GRL_E_INVALID, "grl_fnet_read_rollout: unknown buffer '" + w + "'");
+    if (!src) return paac_fail(net, GRL_E_INVALID, "grl_fnet_read_rollout: '" + w + "' does not exist for this env kind");
+    if (need != bytes) return paac_fail(net, GRL_E_SIZE, "grl_fnet_read_rollout: '" + w + "' needs " + std::to_string(need) + " bytes");
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
+    PAAC_HIP(net, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 

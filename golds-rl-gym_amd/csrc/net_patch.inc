@@ -332,7 +332,7 @@ static int patch_sort(grl_net *net, int n) {
     hipLaunchKernelGGL(patch_masks_kernel, dim3(net->ptiles * 2), dim3(128), 0, st, net->perm, net->tilegroup, net->smask, net->tmask);
     hipLaunchKernelGGL(patch_slice_masks_kernel, dim3((net->pslices + 127) / 128), dim3(128), 0, st, net->sbeg, net->send, net->pslices, net->tmask, net->zmask);
     hipLaunchKernelGGL(patch_wmask_kernel, dim3((n + 255) / 256), dim3(256), 0, st, net->slot_of, net->org, net->goffp, n, net->pslice_rows, net->zmask, net->wmask);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return patch_prof(net);
 }
 // GEMM profiling pass only: the executed share of the dense1 patch GEMMs of the chunk whose lists are bound (freshly sorted or resident)
@@ -345,10 +345,10 @@ static int patch_prof(grl_net *net) {
         // gradient per slice
         std::vector<unsigned> tm((size_t)net->ptiles * 2);
         std::vector<int> sb(net->pslices), se(net->pslices);
-        NET_HIP(net, hipStreamSynchronize(st));
-        NET_HIP(net, hipMemcpy(tm.data(), net->tmask, tm.size() * 4, hipMemcpyDeviceToHost));
-        NET_HIP(net, hipMemcpy(sb.data(), net->sbeg, sb.size() * 4, hipMemcpyDeviceToHost));
-        NET_HIP(net, hipMemcpy(se.data(), net->send, se.size() * 4, hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipStreamSynchronize(st));
+        PAAC_HIP(net, hipMemcpy(tm.data(), net->tmask, tm.size() * 4, hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipMemcpy(sb.data(), net->sbeg, sb.size() * 4, hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipMemcpy(se.data(), net->send, se.size() * 4, hipMemcpyDeviceToHost));
         double a0 = 0, t0 = 0, a1 = 0, t1 = 0, a2 = 0, t2 = 0;
         for (size_t t = 0; t < tm.size(); ++t)
             if (tm[t]) { a0 += __builtin_popcount(tm[t]); t0 += 25; }
@@ -596,7 +596,7 @@ static int pitem_index(grl_net *net, int n, const uint8_t *pos) {
     const bool trunk3f = net->trunk_skip && net->expand2_gemm;
     const unsigned *wm = net->patch_skip ? net->wmask : nullptr, *smk = net->patch_skip ? net->smask : nullptr;
     const int nb = (n + 255) / 256;
-    if ((nb + PITEM_SB - 1) / PITEM_SB > 256) return nfail(net, GRL_E_INVALID, "pitem_index: chunk too large for the item scan");
+    if ((nb + PITEM_SB - 1) / PITEM_SB > 256) return paac_fail(net, GRL_E_INVALID, "pitem_index: chunk too large for the item scan");
     hipLaunchKernelGGL(pitem_count_kernel, dim3(nb), dim3(256), 0, st, wm, smk, n, (const signed char *)net->org, pos, (const int *)net->cslot, b.icnt);
     hipLaunchKernelGGL(pitem_scan_kernel, dim3(1), dim3(1024), 0, st, (const int *)b.icnt, nb, b.ioff, b.irows);
     hipLaunchKernelGGL(pitem_place_kernel, dim3(nb), dim3(256), 0, st, wm, smk, n, (const signed char *)net->org, pos, (const int *)net->cslot,
@@ -605,7 +605,7 @@ static int pitem_index(grl_net *net, int n, const uint8_t *pos) {
     // (256-row tiles: 153 -> 122 us per chunk on the bench workload, 470 -> 392 us with every agent in the interior)
     const int tiles = (n * 25 + 127) / 128;
     hipLaunchKernelGGL(pitem_masks_kernel, dim3(tiles), dim3(128), 0, st, b.desc, (const unsigned short *)b.tapm, (const int *)b.irows, b.tmask9);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -646,11 +646,11 @@ static int forward_conv3_dense1_shared(grl_net *net, int nenv, const uint8_t *po
         double live_pairs = (double)maxrows * 9;      // FLOP count of the profiling pass: rows x live taps of their tile
         if (net->prof_on) {
             int nlive = 0;
-            NET_HIP(net, hipStreamSynchronize(st));
-            NET_HIP(net, hipMemcpy(&nlive, irows, sizeof(int), hipMemcpyDeviceToHost));
+            PAAC_HIP(net, hipStreamSynchronize(st));
+            PAAC_HIP(net, hipMemcpy(&nlive, irows, sizeof(int), hipMemcpyDeviceToHost));
             const int nt = (nlive + 127) / 128;
             std::vector<unsigned short> tm(nt > 0 ? nt : 1);
-            if (nt > 0) NET_HIP(net, hipMemcpy(tm.data(), tmask9, (size_t)nt * 2, hipMemcpyDeviceToHost));
+            if (nt > 0) PAAC_HIP(net, hipMemcpy(tm.data(), tmask9, (size_t)nt * 2, hipMemcpyDeviceToHost));
             live_pairs = 0;
             for (int t = 0; t < nt; ++t) live_pairs += 128.0 * __builtin_popcount(tm[t] & 0x1FFu);
         }
@@ -701,7 +701,7 @@ static int forward_conv3_dense1_shared(grl_net *net, int nenv, const uint8_t *po
         GemmTimer t(net, 2.0 * n * 1600 * 512 * net->pfrac[0]);
         launch_rowk<128, 128, kW128M, kW128N, PatchRows, EpiPatchFwd, true, false, 2>(net, dim3(512 / 128, net->ptiles * 2), st, g, PT + ConvOffsets::d1w, 3136, 512, e);
     }
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 

@@ -252,7 +252,7 @@ static int slot_index(grl_net *net, const uint8_t *pos, int n) {
     hipLaunchKernelGGL(slot_count_kernel, dim3(nb), dim3(256), 0, st, pos, n, net->sbase, net->sblk);
     hipLaunchKernelGGL(slot_scan_kernel, dim3(1), dim3(1024), 0, st, net->sblk, nb, net->sblk + 512, n, net->sbase);
     hipLaunchKernelGGL(slot_place_kernel, dim3(nb), dim3(256), 0, st, net->sblk + 512, n, net->sbase, net->rowagent);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -267,7 +267,7 @@ static int slot_sort(grl_net *net, int n) {
     hipLaunchKernelGGL(slot_sorted_place_kernel, dim3(nb), dim3(SLOT_SORT_BLOCK), 0, st, net->skey, net->srank, live, net->sblkoff, net->sbinbase,
                        net->sperm);
     hipLaunchKernelGGL(slot_tile_masks_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, net->sperm, net->stap, live, net->stmask);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return slot_prof(net, n);
 }
 // GEMM profiling pass only: the executed share of the slot GEMMs of the chunk whose lists are bound (freshly sorted or resident)
@@ -277,12 +277,12 @@ static int slot_prof(grl_net *net, int n) {
     net->sfrac = 1.0;
     if (net->prof_on && net->patch_skip) {      // GEMM profiling pass: the share of the 9 taps the slot GEMMs of this chunk execute (per 256-row tile)
         int nlive = 0;
-        NET_HIP(net, hipStreamSynchronize(st));
-        NET_HIP(net, hipMemcpy(&nlive, live, sizeof(int), hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipStreamSynchronize(st));
+        PAAC_HIP(net, hipMemcpy(&nlive, live, sizeof(int), hipMemcpyDeviceToHost));
         const int nt = (nlive + 255) / 256;
         if (nt > 0) {
             std::vector<unsigned> tm(nt);
-            NET_HIP(net, hipMemcpy(tm.data(), net->stmask, (size_t)nt * 4, hipMemcpyDeviceToHost));
+            PAAC_HIP(net, hipMemcpy(tm.data(), net->stmask, (size_t)nt * 4, hipMemcpyDeviceToHost));
             double a = 0;
             for (int t = 0; t < nt; ++t) a += __builtin_popcount(tm[t] & 0x1FFu);
             net->sfrac = a / (9.0 * nt);
@@ -995,7 +995,7 @@ static int obs_index(grl_net *net, const uint8_t *lb, const uint8_t *ab, const u
     if (parts == 1) hipLaunchKernelGGL(obs_index_kernel<1>, g, b, 0, st, lb, ab, pos, nenv, G, rec);
     else if (parts == 2) hipLaunchKernelGGL(obs_index_kernel<2>, g, b, 0, st, lb, ab, pos, nenv, G, rec);
     else hipLaunchKernelGGL(obs_index_kernel<3>, g, b, 0, st, lb, ab, pos, nenv, G, rec);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 // conv1_sparse_shared_kernel (net_conv.hip) from the index record: the touched-pixel mask comes out of the record, and a half wave builds its
@@ -1106,7 +1106,7 @@ static int trunk_index(grl_net *net, const uint8_t *lb, const uint8_t *ab, const
     // dense1's per-env bias under the union mask: b + the background's contribution of the pixels outside it
     hipLaunchKernelGGL(trunk_ubias_kernel, dim3(2), dim3(256), 0, st, net->params + ConvOffsets::d1b, (const float *)net->tybg, (const unsigned *)net->tumask,
                        net->tubias, net->tneed2);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 // live entries of a trunk list -- read back only while profiling (serialised pass), for the FLOP count; otherwise the upper bound
@@ -1139,7 +1139,7 @@ static int trunk_background(grl_net *net) {
         launch_rowk<256, 64, kW256M, kW256N, GatherConv3Rows, EpiBiasDualRows>(net, dim3(1, 1), st, g, PT + ConvOffsets::c3w, 576, 64, e);
     }
     hipLaunchKernelGGL(trunk_ybg_kernel, dim3(98), dim3(256), 0, st, (const float *)(net->tbgz3 + 64), P + ConvOffsets::d1w, net->tybg);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -1177,10 +1177,10 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
     // sits on another hardware queue than the lane (grl_net_create), while the lane computes the env-level trunk (round 5).  Same kernels, same buffers: the side stream starts behind everything already enqueued on the lane
     // (the previous pass's consumers of those buffers) and the main stream waits for it before the first consumer (conv2_prep's data part).
     const bool side = net->idx_side && net->side_now && net->cur_lane == 0 && net->expand2_gemm && !net->prof_on && net->side_stream[0];
-    if (side) NET_HIP(net, hipEventRecord(net->ev_side0[net->cur_lane], st));      // what is enqueued on the lane so far: the earlier passes' consumers of the lists
+    if (side) PAAC_HIP(net, hipEventRecord(net->ev_side0[net->cur_lane], st));      // what is enqueued on the lane so far: the earlier passes' consumers of the lists
     if (trunk)
         if (int rc = trunk_index(net, lb, ab, pos, nenv)) return rc;
-    if (side) NET_HIP(net, hipEventRecord(net->ev_side2[net->cur_lane], st));      // the trunk's masks are there: the item sort reads cmask
+    if (side) PAAC_HIP(net, hipEventRecord(net->ev_side2[net->cur_lane], st));      // the trunk's masks are there: the item sort reads cmask
     // list form: sraw is written where somebody reads it -- the 2 x 2 pixel blocks under the affected conv2 outputs' windows
     static const int hgc1 = conv1_sparse_grid();      // one resident wave of workgroups (they stride over the envs)
     if (net->obs_index) {
@@ -1221,7 +1221,7 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
     }
     if (side) {      // (enqueued behind the trunk's kernels: the queues are served in the order their work arrives)
         hipStream_t ss = net->side_stream[net->cur_lane];
-        NET_HIP(net, hipStreamWaitEvent(ss, net->ev_side0[net->cur_lane], 0));
+        PAAC_HIP(net, hipStreamWaitEvent(ss, net->ev_side0[net->cur_lane], 0));
         net->h->stream = ss;      // slot_index / patch_sort enqueue on the handle's current stream
         int rc = slot_index(net, pos, n);
         if (rc == GRL_OK) {
@@ -1234,7 +1234,7 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
             hipLaunchKernelGGL(corr_place_kernel, dim3(nb), dim3(256), 0, ss, pos, n, net->cblkoff, net->cgoff, net->cperm, net->cinv);
             rc = patch_sort(net, n);
             if (rc == GRL_OK && tail && pitem_gather_on(net)) {      // the conv3 gather's item sort rides along (needs the trunk's cmask: ev_side2)
-                NET_HIP(net, hipStreamWaitEvent(ss, net->ev_side2[net->cur_lane], 0));
+                PAAC_HIP(net, hipStreamWaitEvent(ss, net->ev_side2[net->cur_lane], 0));
                 rc = pitem_index(net, n, pos);
                 net->pitem_on_side = rc == GRL_OK;
             }
@@ -1243,8 +1243,8 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
         if (rc) return rc;
     }
     if (side) {      // the main stream goes on when the side stream's lists are there
-        NET_HIP(net, hipEventRecord(net->ev_side1[net->cur_lane], net->side_stream[net->cur_lane]));
-        NET_HIP(net, hipStreamWaitEvent(st, net->ev_side1[net->cur_lane], 0));
+        PAAC_HIP(net, hipEventRecord(net->ev_side1[net->cur_lane], net->side_stream[net->cur_lane]));
+        PAAC_HIP(net, hipStreamWaitEvent(st, net->ev_side1[net->cur_lane], 0));
     } else if (int rc = slot_index(net, pos, n)) return rc;
     if (net->expand2_gemm) {
         const int nb = (n + 255) / 256;
@@ -1265,7 +1265,7 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
         hipLaunchKernelGGL(expand_conv2_kernel, dim3(nenv < 256 ? nenv : 256), dim3(1024), EXP2_LDS_BYTES, st, net->sraw, net->z2sh, pos,
                            P + ConvOffsets::c1w, P + ConvOffsets::c2w, nenv, net->a2sh, net->d2s, net->m2s, net->ulist, net->sbase);
     }
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return side ? GRL_OK : patch_sort(net, n);
 }
 

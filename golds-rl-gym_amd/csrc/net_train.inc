@@ -47,7 +47,7 @@ static int rq_flush(grl_net *net) {
     }
     net->rq.clear(); net->rq_dst.clear();
     net->slab_used = 0; net->slabb_used = 0;
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 // a few independent jobs NOW, as one launch (their results feed kernels of the same chunk)
@@ -628,19 +628,6 @@ __global__ void slab64_reduce_kernel(const double *__restrict__ slab, int chunks
 }
 
 // ------------------------------------------------------------------------------------------ optimiser
-__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float *__restrict__ g, long n, double *__restrict__ partial) {
-    __shared__ double red[256];
-    double s = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += (double)g[i] * (double)g[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
 // stats[0..1] = loss parts (mean), stats[2] = loss, stats[3] = global_norm, stats[4] = clip factor
 __global__ void finalize_stats_kernel(const double *__restrict__ partial, int nparts, const double *__restrict__ stats64,
                                       float inv_total, float clip_norm, float grad_scale, float *__restrict__ stats) {
@@ -709,13 +696,13 @@ static int ensure_train_bufs(grl_net *net) {
     if (net->train_ready) return GRL_OK;
     size_t c = net->chunk;
     int rc = GRL_OK;
-    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = nalloc(net, p, cnt); };
+    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(net, p, cnt); };
     if (!net->shared_trunk) { A(&net->ga1, c * 12800); A(&net->ga2, c * 5184); A(&net->ga3, c * 3136); }
     A(&net->gd1, c * 512); A(&net->gd2, c * 256); A(&net->gp1, c * 512 * 2); net->gv1 = net->gp1 + c * 512; A(&net->gv2, c * 256);
     if (!net->w3t) { A(&net->w3t, 576 * 64); A(&net->w2t, 4 * 256 * 32); }      // shared by the lanes (read-only during a pass)
     A(&net->dz2, (c / 10) * 5184); A(&net->gt, (c / 10) * 12800);
     A(&net->gsl, c * 9 * 64); A(&net->dza, c * 9 * 64); A(&net->dz3sh, (c / 10) * 3136); A(&net->tmpw3, 576 * 64);
-    if (rc == GRL_OK) rc = nalloc(net, &net->t2desc, (size_t)4 * net->npad);
+    if (rc == GRL_OK) rc = paac_alloc(net, &net->t2desc, (size_t)4 * net->npad);
     A(&net->dl2, (size_t)4 * net->npad * 32); A(&net->tt2, (size_t)4 * net->npad * 32);
     A(&net->tmpw2, 4 * 256 * 32);
     A(&net->gd1sh, (c / 10) * 512); A(&net->gsh3, (c / 10) * 3136); A(&net->g3p, c * 1600); A(&net->dz3p, c * 1600);
@@ -738,7 +725,7 @@ static int ensure_train_bufs(grl_net *net) {
     }
     A(&net->slab1b, (size_t)3 * 2048 * 64);      // agent_dz3, agent_dz2, agent_ds: a region each
     A(&net->cfold, (size_t)kFoldParts * 32);
-    if (rc == GRL_OK) rc = nalloc(net, &net->slab64, kSlab64Doubles + 4096);
+    if (rc == GRL_OK) rc = paac_alloc(net, &net->slab64, kSlab64Doubles + 4096);
     A(&net->ro_mu, c * (3 * (size_t)net->ho.A + net->ho.dz + 3));      // cmu csigma cvs dzh cact cadv cy
     if (rc == GRL_OK) net->train_ready = true;
     return rc;
@@ -753,12 +740,12 @@ static int tn_launch(grl_net *net, int rd, AG ag, int I, const float *dY, int J,
     if (min_chunks > chunks) chunks = min_chunks;       // short per-workgroup K loops where only part of the rows is live (compact slots)
     if (chunks > 1024) chunks = 1024;
     if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-    if (chunks < 1) return nfail(net, GRL_E_INVALID, "tn_launch: slab too small");
+    if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "tn_launch: slab too small");
     int mc = ((M + chunks - 1) / chunks + 31) / 32 * 32;
     chunks = (M + mc - 1) / mc;
     const long n = (long)I * J;
     float *slab = slab_take(net, (size_t)chunks * n);
-    if (!slab) return nfail(net, GRL_E_INVALID, "tn_launch: slab too small");
+    if (!slab) return paac_fail(net, GRL_E_INVALID, "tn_launch: slab too small");
     {
         GemmTimer t(net, 2.0 * (flop_rows > 0.0 ? flop_rows : (double)M) * (double)I * J);
         launch_tn<BM, BN, WGM, WGN, AG>(net, dim3(I / BM, J / BN, chunks), net->h->stream, ag, dY, J, mc, slab);
@@ -766,7 +753,7 @@ static int tn_launch(grl_net *net, int rd, AG ag, int I, const float *dY, int J,
     RJob j{};
     j.kind = RJ_SLAB; j.blocks = (int)((n + 255) / 256); j.i0 = chunks; j.i1 = accumulate; j.n = n; j.p0 = slab; j.d0 = gdst;
     rq_push(net, rd, j);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -793,11 +780,11 @@ static int slot_wgrad_launch(grl_net *net, int n, float *gw3, double flop_rows, 
     if (min_chunks > chunks) chunks = min_chunks;
     if (chunks > 1024) chunks = 1024;
     if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-    if (chunks < 1) return nfail(net, GRL_E_INVALID, "slot_wgrad_launch: slab too small");
+    if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "slot_wgrad_launch: slab too small");
     const int mc = ((M + chunks - 1) / chunks + 31) / 32 * 32;
     chunks = (M + mc - 1) / mc;
     float *slab = slab_take(net, (size_t)chunks * I * J);
-    if (!slab) return nfail(net, GRL_E_INVALID, "slot_wgrad_launch: slab too small");
+    if (!slab) return paac_fail(net, GRL_E_INVALID, "slot_wgrad_launch: slab too small");
     hipStream_t st = net->h->stream;
     const bool skip = net->patch_skip != 0;
     if (skip) hipLaunchKernelGGL(slot_range_masks_kernel, dim3(chunks), dim3(256), 0, st, net->sperm, net->stap, net->sbase + n, mc, net->szmask);
@@ -814,23 +801,23 @@ static int slot_wgrad_launch(grl_net *net, int n, float *gw3, double flop_rows, 
     RJob j{};
     j.kind = RJ_TAPS_C3; j.blocks = I * J / 32; j.i0 = chunks; j.p0 = slab; j.p1 = skip ? net->szmask : nullptr; j.d0 = gw3;
     rq_push(net, RD_C3W, j);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
 static int colsum_launch(grl_net *net, int rd, const float *dY, int M, int J, float *gdst) {
-    if (J < 32 || J > 1024 || (J & (J - 1))) return nfail(net, GRL_E_INVALID, "colsum_launch: J must be a power of two in 32..1024");
+    if (J < 32 || J > 1024 || (J & (J - 1))) return paac_fail(net, GRL_E_INVALID, "colsum_launch: J must be a power of two in 32..1024");
     int chunks = (M + 31) / 32;
     if (chunks > 2048) chunks = 2048;
     int mc = (M + chunks - 1) / chunks;
     chunks = (M + mc - 1) / mc;
     float *slab = slab_take(net, (size_t)chunks * J);
-    if (!slab) return nfail(net, GRL_E_INVALID, "colsum_launch: slab too small");
+    if (!slab) return paac_fail(net, GRL_E_INVALID, "colsum_launch: slab too small");
     hipLaunchKernelGGL(colsum_kernel, dim3(1, chunks), dim3(256), 0, net->h->stream, dY, M, J, mc, slab);
     RJob j{};
     j.kind = RJ_NARROW; j.blocks = (J + kNarrowCols - 1) / kNarrowCols; j.i0 = chunks; j.i1 = 1; j.n = J; j.p0 = slab; j.d0 = gdst;
     rq_push(net, rd, j);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -882,7 +869,7 @@ static int backward_chunk(grl_net *net, const TrainBufs &tb, const uint8_t *lb, 
                           const float *pmu = nullptr, const float *psg = nullptr, const float *pval = nullptr) {
     if (!net->rq.empty() || net->slab_used || net->slabb_used) {      // cannot happen: every exit below leaves them empty
         rq_reset(net);
-        return nfail(net, GRL_E_INVALID, "backward_chunk: reductions of an earlier chunk were still queued");
+        return paac_fail(net, GRL_E_INVALID, "backward_chunk: reductions of an earlier chunk were still queued");
     }
     const int rc = backward_chunk_body(net, tb, lb, ab, pos, nenv, actions, adv, y, inv_total, slot, pmu, psg, pval);
     if (rc != GRL_OK) rq_reset(net);
@@ -912,7 +899,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     if (chunks > 1024) chunks = 1024;
     const int HS2 = HS + 768;      // + the bias rows of pol1 (512) and v2 (256): column sums of gp1 / gv2, taken while they are written
     float *hslab = slab_take(net, (size_t)chunks * HS2);
-    if (!hslab) return nfail(net, GRL_E_INVALID, "backward_chunk: slab too small for the heads");
+    if (!hslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small for the heads");
     GRL_HEADS_DISPATCH(ho.A, hipLaunchKernelGGL(heads_backward_kernel<kA>, dim3(chunks), dim3(256), 0, st, net->p1, net->v2,
                                                 hmu, hsg, hvs, actions, adv, y, P, ho, n, net->cfg.scale, net->cfg.entropy_beta, inv_total,
                                                 (const float *)(net->stats + kLossScaleAt), net->gp1, net->gv2, tb.dzh, tb.stats64, hslab));
@@ -926,7 +913,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     net->prof_tag_cur = net->shared_trunk ? PT_DENSE_DGRAD : PT_PER_AGENT;
     const size_t csum_floats = ((size_t)n / 128 + 2) * kW128M * 512;
     float *cs1 = slabb_take(net, csum_floats), *cs2 = slabb_take(net, csum_floats), *cs3 = slabb_take(net, csum_floats);
-    if (!cs1 || !cs2 || !cs3) return nfail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
+    if (!cs1 || !cs2 || !cs3) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
     // (round 5: the one-accumulator form on this instance and on dense2 / v2's forwards -- 122 -> 92 registers, no faster alone -- moved the
     // four-stream update by nothing: 300.2 / 301.2 / 299.7 / 301.9 against 302.9 / 300.4 / 300.7 / 300.2 ms)
     rowk_launch<128, 128, kW128M, kW128N>(net, DenseRows{net->gv2, n, 256, 256}, P + ho.v2w, 256, 512,
@@ -957,7 +944,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
             const int cmc = (nenv + cch - 1) / cch;
             cch = (nenv + cmc - 1) / cmc;
             float *gslab = slab_take(net, (size_t)cch * 512);
-            if (!gslab) return nfail(net, GRL_E_INVALID, "backward_chunk: slab too small");
+            if (!gslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small");
             hipLaunchKernelGGL(colsum_kernel, dim3(1, cch), dim3(256), 0, st, (const float *)net->gd1sh, nenv, 512, cmc, gslab);
             hipLaunchKernelGGL(slab_reduce_narrow_kernel, dim3((512 + kNarrowCols - 1) / kNarrowCols), dim3(256), 0, st, gslab, cch, 512, net->tug, 0);
             rowk_launch<256, 64, kW256M, kW256N>(net, DenseRowsNU{{net->gd1sh, nenv, 512, 512}, net->tumask}, P + ConvOffsets::d1w, 512, 3136,
@@ -1014,7 +1001,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
         net->prof_tag_cur = PT_ENV_DGRAD;
         if (trunk3) {      // at the affected conv2 rows only: the others enter the conv2-level gradients as a sum (trunk_closed3_kernel)
             float *cs4 = slabb_take(net, ((size_t)nenv * 81 / 128 + 2) * 4 * 64);
-            if (!cs4) return nfail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
+            if (!cs4) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
             rowk_launch<128, 64, 4, 1, false, 1, true>(net, GatherT3Rows{net->dz3sh, net->trowlist, net->trows_n, nenv * 81}, net->w3t, 576, 64,
                                        EpiGradRowsSum{net->dz2, 64, net->a2sh, cs4, net->trowlist, net->trows_n},
                                        2.0 * trunk_live(net, 0, (double)nenv * 81) * 576 * 64);
@@ -1059,7 +1046,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
         // dS = relu'(S) . T2(DZ2): the mask comes from the stored pre-activation, the column sums (conv1's bias gradient up to
         // the per-agent corrections agent_ds_kernel adds) from the epilogue
         float *cs5 = slabb_take(net, ((size_t)nenv * 100 / 128 + 2) * kW128M * 128);
-        if (!cs5) return nfail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
+        if (!cs5) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
         if (trunk) {      // at the touched 2x2 pixel blocks only: nobody reads dS anywhere else (net_shared.inc, trunk_mark_kernel)
             rowk_launch<128, 128, 2, 2, false>(net, GatherT2Rows{net->dz2, net->tblklist, net->trows_n + 1, nenv * 100}, net->w2t, 256, 128,
                                         EpiGradStride2Rows{net->gt, net->sraw, cs5, P + ConvOffsets::c1b, net->tblklist, net->trows_n + 1},
@@ -1088,7 +1075,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     rowk_launch<128, 128, 2, 2, false>(net, GatherT2{net->ga2, n * 100}, net->w2t, 256, 128, EpiGradStride2<true>{net->ga1, net->a1, nullptr},
                                 2.0 * n * 100 * 256 * 128);
     }
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     // ---- weight gradients
     net->prof_tag_cur = net->shared_trunk ? PT_DENSE_WGRAD : PT_PER_AGENT;
     if ((rc = tn_launch<128, 128, 2, 2>(net, RD_V2W, DenseRows{net->v1, n, 512, 512}, 512, net->gv2, 256, Gr + net->ho.v2w, 1, 0.0, 0, net->tn_wgs_dense))) return rc;
@@ -1102,11 +1089,11 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
             constexpr int I = 3136, J = 512, tiles = (I / 64) * (J / 128);
             int chunks = (net->tn_wgs + tiles - 1) / tiles;
             if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-            if (chunks < 1) return nfail(net, GRL_E_INVALID, "dense1 per-env weight gradient: slab too small");
+            if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "dense1 per-env weight gradient: slab too small");
             const int mc = ((nenv + chunks - 1) / chunks + 31) / 32 * 32;
             chunks = (nenv + mc - 1) / mc;
             float *slab = slab_take(net, (size_t)chunks * I * J);
-            if (!slab) return nfail(net, GRL_E_INVALID, "dense1 per-env weight gradient: slab too small");
+            if (!slab) return paac_fail(net, GRL_E_INVALID, "dense1 per-env weight gradient: slab too small");
             {
                 GemmTimer t(net, 2.0 * nenv * 64.0 * trunk_union_pixels(net) * J);
                 launch_tn<64, 128, 2, 2, DenseRowsIU>(net, dim3(I / 64, J / 128, chunks), st, DenseRowsIU{{net->a3sh, nenv, 3136, 3136}, net->tumask},
@@ -1119,7 +1106,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
         } else if ((rc = tn_launch<64, 128, 2, 2>(net, RD_D1W, DenseRows{net->a3sh, nenv, 3136, 3136}, 3136, net->gd1sh, 512, Gr + ConvOffsets::d1w))) return rc;
         {
             float *pslab = slab_take(net, (size_t)net->pslices * 1600 * 512);
-            if (!pslab) return nfail(net, GRL_E_INVALID, "backward_chunk: slab too small for the patch slices");
+            if (!pslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small for the patch slices");
             PatchRows g{net->d3, net->perm, net->tilegroup, net->ptiles * 256, 1600, 1600, 0, net->sbeg, net->send, net->patch_skip ? net->tmask : nullptr,
                         net->patch_skip ? net->zmask : nullptr};
             {
@@ -1153,9 +1140,9 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
             constexpr int I = 576, J = 64, tiles = (I / 64) * (J / 64);
             int chunks = (net->tn_wgs + tiles - 1) / tiles;
             if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-            if (chunks < 1) return nfail(net, GRL_E_INVALID, "conv3 weight gradient: slab too small");
+            if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "conv3 weight gradient: slab too small");
             float *slab = slab_take(net, (size_t)chunks * I * J);
-            if (!slab) return nfail(net, GRL_E_INVALID, "conv3 weight gradient: slab too small");
+            if (!slab) return paac_fail(net, GRL_E_INVALID, "conv3 weight gradient: slab too small");
             GatherConv3Rows ag{net->a2sh, net->tc3list, net->trows_n + 2, net->tbgimg3, nenv * 49, chunks};
             {
                 GemmTimer t(net, 2.0 * trunk_live(net, 2, (double)nenv * 49) * I * J);
@@ -1180,9 +1167,9 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
             constexpr int I = 512, J = 64, tiles = (I / 128) * (J / 64);
             int chunks = (net->tn_wgs + tiles - 1) / tiles;
             if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-            if (chunks < 1) return nfail(net, GRL_E_INVALID, "conv2 weight gradient: slab too small");
+            if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "conv2 weight gradient: slab too small");
             float *slab = slab_take(net, (size_t)chunks * I * J);
-            if (!slab) return nfail(net, GRL_E_INVALID, "conv2 weight gradient: slab too small");
+            if (!slab) return paac_fail(net, GRL_E_INVALID, "conv2 weight gradient: slab too small");
             GatherConv2ReluRows ag{net->sraw, net->trowlist, net->trows_n, net->tbgimg, nenv * 81, chunks};
             {
                 GemmTimer t(net, 2.0 * trunk_live(net, 0, (double)nenv * 81) * I * J);
@@ -1228,7 +1215,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
                 launch_rowk<128, 32, 4, 1, T2SlotGather, EpiStore>(net, dim3(1, 4 * npad / 128), st, g, net->w2t, 256, 32, EpiStore{net->tt2, 32});
             }
             float *cslab = slab_take(net, (size_t)4 * cpc * 8192);
-            if (!cslab) return nfail(net, GRL_E_INVALID, "class corrections: slab too small");
+            if (!cslab) return paac_fail(net, GRL_E_INVALID, "class corrections: slab too small");
             {
                 GemmTimer t(net, 4 * 2.0 * n * 256 * 32);
                 launch_tn<64, 32, 4, 1, T2SlotGather>(net, dim3(256 / 64, 1, 4 * cpc), st, g, net->dl2, 32, mc, cslab);      // one tap per I tile: its validity is per row
@@ -1281,7 +1268,7 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     }
     if (!net->shared_trunk)
         hipLaunchKernelGGL(slab64_reduce_kernel, dim3(6144 / 256), dim3(256), 0, st, net->slab64, blocks, 6144, Gr + ConvOffsets::c1w);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     // the chunk's queued folds into the lane's gradient accumulator: one launch per phase (net_reduce.inc)
     return rq_flush(net);
 }
@@ -1303,13 +1290,13 @@ static int train_begin(grl_net *net, TrainBufs *tb) {
         tb[k].cadv = tb[k].cact + c * A; tb[k].cy = tb[k].cadv + c;
         tb[k].stats64 = net->slab64 + kSlab64Doubles;      // chunk-independent scalars live at the tail of slab64's allocation
         tb[k].partial = tb[k].stats64 + 8;
-        NET_HIP(net, hipMemsetAsync(net->grads, 0, net->ho.total * 4, main_st));
-        NET_HIP(net, hipMemsetAsync(tb[k].stats64, 0, 8 * sizeof(double), main_st));
+        PAAC_HIP(net, hipMemsetAsync(net->grads, 0, net->ho.total * 4, main_st));
+        PAAC_HIP(net, hipMemsetAsync(tb[k].stats64, 0, 8 * sizeof(double), main_st));
     }
     hipLaunchKernelGGL(transpose_conv_weights_kernel, dim3((576 * 64 + 255) / 256), dim3(256), 0, main_st,
                        net->params + ConvOffsets::c2w, net->params + ConvOffsets::c3w, net->w2t, net->w3t);
-    NET_HIP(net, hipMemsetAsync(net->stats + kLossBoundAt, 0, sizeof(float), main_st));
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipMemsetAsync(net->stats + kLossBoundAt, 0, sizeof(float), main_st));
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -1319,7 +1306,7 @@ static int train_bound_rows(grl_net *net, const float *mu, const float *sigma, c
     GRL_HEADS_DISPATCH(net->ho.A, hipLaunchKernelGGL(head_bound_kernel<kA>, dim3((unsigned)std::min<long>((n + 255) / 256, 2048)), dim3(256), 0, net->lane_stream[0], mu,
                                                      sigma, vs, actions, adv, y, n, net->cfg.scale, net->cfg.entropy_beta,
                                                      reinterpret_cast<unsigned *>(net->stats + kLossBoundAt)));
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -1327,7 +1314,7 @@ static int train_bound_rows(grl_net *net, const float *mu, const float *sigma, c
 static int train_scale_and_fork(grl_net *net, float inv_total) {
     hipLaunchKernelGGL(loss_scale_kernel, dim3(1), dim3(64), 0, net->lane_stream[0], reinterpret_cast<const unsigned *>(net->stats + kLossBoundAt),
                        inv_total, net->loss_scale_on, net->stats + kLossScaleAt);
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return lanes_fork(net);
 }
 
@@ -1337,33 +1324,6 @@ __global__ void lane_fold_kernel(float *__restrict__ g0, const float *__restrict
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) g0[i] += g1[i];
     if (i < 8) s0[i] += s1[i];
-}
-
-// One all-reduce (sum, fp32) of the flat gradient per rollout over RCCL/xGMI (SURVEY 8e).  Every rank's
-// gradient is the mean over ITS T*B_local samples; the reference's loss is a mean over the whole batch
-// (policy_v_network.py:54,62), so the summed gradient is scaled by 1/world afterwards (folded into the
-// clip factor); clip-by-global-norm is applied after the reduction, Adam runs replicated.
-// The GEMMs' range flag travels with it (max over ranks): a rank whose pass overflowed makes EVERY replica skip the update and fail
-// the call, instead of erroring alone and leaving its peers blocked in the next collective.  The pair is bracketed by HIP events
-// on the handle's stream (grl_net_comm_info reports the time).
-static int comm_allreduce_grads(grl_net *net, float *grad_scale_out) {
-    *grad_scale_out = 1.0f;
-    if (!net->comm) return GRL_OK;
-    hipStream_t st = net->h->stream;
-    if (!net->ar_ev0) { NET_HIP(net, hipEventCreate(&net->ar_ev0)); NET_HIP(net, hipEventCreate(&net->ar_ev1)); }
-    NET_HIP(net, hipEventRecord(net->ar_ev0, st));
-    ncclResult_t r = ncclGroupStart();
-    // [flag, largest |output| of the fp32 form as float bits]: both words by max (non-negative floats order like their bits)
-    if (r == ncclSuccess) r = ncclAllReduce(range_flag_ptr(net), range_flag_ptr(net), 2, ncclUint32, ncclMax, (ncclComm_t)net->comm, st);
-    if (r == ncclSuccess) r = ncclAllReduce(net->grads, net->grads, (size_t)net->ho.total, ncclFloat, ncclSum, (ncclComm_t)net->comm, st);
-    ncclResult_t r2 = ncclGroupEnd();
-    if (r == ncclSuccess) r = r2;
-    (void)hipGetLastError();   // RCCL probes (peer access, other ordinals) may leave a stale HIP error on this thread
-    if (r != ncclSuccess) return nfail(net, GRL_E_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(r));
-    NET_HIP(net, hipEventRecord(net->ar_ev1, st));
-    net->ar_pending = 1;
-    *grad_scale_out = 1.0f / (float)net->comm_world;
-    return GRL_OK;
 }
 
 // joins the lanes, folds their gradient accumulators and loss sums into lane 0's (fixed order) and removes the loss scale
@@ -1376,7 +1336,7 @@ static int train_fold(grl_net *net, const TrainBufs *tbs) {
                            net->lanes[k].grads, (long)net->ho.total, tbs[0].stats64, tbs[k].stats64);
     hipLaunchKernelGGL(unscale_grads_kernel, dim3((unsigned)((net->ho.total + 255) / 256)), dim3(256), 0, net->h->stream, net->grads,
                        (long)net->ho.total, (const float *)(net->stats + kLossScaleAt));
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 
@@ -1385,15 +1345,14 @@ static int train_apply(grl_net *net, float inv_total, float lr, int apply_update
     hipStream_t st = net->h->stream;
     double *stats64 = net->slab64 + kSlab64Doubles, *partial = stats64 + 8;      // lane 0 (current after train_fold)
     const int nparts = 1024;
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nparts), dim3(256), 0, st, net->grads, (long)net->ho.total, partial);
+    hipLaunchKernelGGL(paac_sumsq_kernel<>, dim3(nparts), dim3(256), 0, st, net->grads, (long)net->ho.total, partial);
     hipLaunchKernelGGL(finalize_stats_kernel, dim3(1), dim3(64), 0, st, partial, nparts, stats64, inv_total, net->cfg.clip_norm,
                        grad_scale, net->stats);
     int *latch = reinterpret_cast<int *>(net->stats + kRangeLatchAt);
     if (apply_update) {
         net->adam_t += 1;
         net->param_version += 1;
-        const double b1 = 0.9, b2 = 0.999;
-        float lr_t = (float)((double)lr * sqrt(1.0 - pow(b2, (double)net->adam_t)) / (1.0 - pow(b1, (double)net->adam_t)));
+        const float lr_t = adam_lr_t(lr, net->adam_t);
         hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((net->ho.total + 255) / 256)), dim3(256), 0, st, net->params, net->grads,
                            net->adam_m, net->adam_v, (long)net->ho.total, net->stats, lr_t, 0.9f, 0.999f, 1e-8f,
                            (const int *)range_flag_ptr(net));
@@ -1401,9 +1360,9 @@ static int train_apply(grl_net *net, float inv_total, float lr, int apply_update
         hipLaunchKernelGGL(range_latch_kernel, dim3(1), dim3(1), 0, st, range_flag_ptr(net), latch);
         refresh_transposes(net);
     }
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     const double t_sync0 = host_now_ms();
-    NET_HIP(net, hipStreamSynchronize(st));
+    PAAC_HIP(net, hipStreamSynchronize(st));
     if (net->ht_train_t0 > 0.0) {      // grl_net_host_times: the gradient step's enqueue work ends where its first blocking call begins
         const double t_sync1 = host_now_ms();
         net->ht_train_enq_ms += t_sync0 - net->ht_train_t0;
@@ -1411,43 +1370,34 @@ static int train_apply(grl_net *net, float inv_total, float lr, int apply_update
         net->ht_updates += 1;
         net->ht_train_t0 = 0.0;
     }
-    if (net->ar_pending) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, net->ar_ev0, net->ar_ev1) == hipSuccess) { net->ar_ms_last = ms; net->ar_ms_total += ms; net->ar_calls += 1; }
-        net->ar_pending = 0;
-    }
+    paac_allreduce_account(net);
     if (apply_update) {
         int lflag = 0;
-        NET_HIP(net, hipMemcpy(&lflag, latch, sizeof(int), hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipMemcpy(&lflag, latch, sizeof(int), hipMemcpyDeviceToHost));
         if (lflag) {      // rollout + backward of this update: adam_kernel skipped the update on the device, parameters and moments are intact
             net->range_bits_last = lflag;
             net->adam_t -= 1;      // (param_version stays advanced: the retry recomputes its forward passes in the form it runs in)
             // (the background pass ran on the unchanged parameters: whatever it raised is that of the rows already in use)
-            NET_HIP(net, hipMemset(range_flag_ptr(net), 0, sizeof(int)));
-            return nfail(net, GRL_E_RANGE, "gradient pass: an activation or gradient exceeded 65504, the range of the fp16 matrix-pipe GEMMs "
+            PAAC_HIP(net, hipMemset(range_flag_ptr(net), 0, sizeof(int)));
+            return paac_fail(net, GRL_E_RANGE, "gradient pass: an activation or gradient exceeded 65504, the range of the fp16 matrix-pipe GEMMs "
                                            "(include/goldsrl_net.h, Arithmetic); the results of this call are not valid");
         }
         // only the background pass on the UPDATED parameters left the range: the update stands (it was computed and applied from valid
         // operands); the net moves to the fp32 form for what follows, which recomputes the background rows.  Every rank holds the same
         // parameters, so every rank takes this branch together.  With the fallback off the flag stays up and the next call fails.
         int bflag = 0;
-        NET_HIP(net, hipMemcpy(&bflag, range_flag_ptr(net), sizeof(int), hipMemcpyDeviceToHost));
+        PAAC_HIP(net, hipMemcpy(&bflag, range_flag_ptr(net), sizeof(int), hipMemcpyDeviceToHost));
         net->range_bits_last = 0;
         if (bflag && net->range_fallback_on) {
-            NET_HIP(net, hipMemset(range_flag_ptr(net), 0, sizeof(int)));
+            PAAC_HIP(net, hipMemset(range_flag_ptr(net), 0, sizeof(int)));
             if (!range_fall_back(net)) (void)trunk_background(net);
-            NET_HIP(net, hipStreamSynchronize(st));
+            PAAC_HIP(net, hipStreamSynchronize(st));
         }
         else if (int rrc = range_maybe_return(net)) return rrc;      // an update on the fp32 form ended cleanly: one step on the way back
     } else if (int rrc = range_check(net, "gradient pass")) {
         return rrc;
     }
-    if (stats_host) {
-        float s[5];
-        NET_HIP(net, hipMemcpy(s, net->stats, sizeof(s), hipMemcpyDeviceToHost));
-        stats_host[0] = s[2]; stats_host[1] = s[0]; stats_host[2] = s[1]; stats_host[3] = s[3];
-    }
-    return GRL_OK;
+    return paac_read_stats(net, stats_host);
 }
 
 static int train_finish(grl_net *net, const TrainBufs *tbs, float inv_total, float lr, int apply_update, float *stats_host) {
@@ -1455,7 +1405,10 @@ static int train_finish(grl_net *net, const TrainBufs *tbs, float inv_total, flo
     if (rc) return rc;
     net->last_inv_total = inv_total;
     float grad_scale = 1.0f;
-    if ((rc = comm_allreduce_grads(net, &grad_scale))) return rc;
+    // the GEMMs' range words [flag, largest |output| of the fp32 form as float bits: non-negative floats order like their bits] travel
+    // with the gradient (max over ranks): a rank whose pass overflowed makes EVERY replica skip the update and fail the call, instead
+    // of erroring alone and leaving its peers blocked in the next collective
+    if ((rc = paac_allreduce_grads(net, net->grads, range_flag_ptr(net), &grad_scale))) return rc;
     return train_apply(net, inv_total, lr, apply_update, grad_scale, stats_host);
 }
 
@@ -1463,19 +1416,19 @@ static int ensure_rollout_bufs(grl_net *net, int T) {
     const int E = net->h->E, B = E * 10;
     if (net->ro_lb && net->T >= T) return GRL_OK;
     int rc;
-    if ((rc = nalloc(net, &net->ro_lb, (size_t)T * E * 160))) return rc;
-    if ((rc = nalloc(net, &net->ro_ab, (size_t)T * E * 20))) return rc;
-    if ((rc = nalloc(net, &net->ro_pos, (size_t)T * E * 20))) return rc;
-    if ((rc = nalloc(net, &net->ro_act, (size_t)T * B * 2))) return rc;
-    if ((rc = nalloc(net, &net->ro_envact, (size_t)B * 2))) return rc;
-    if ((rc = nalloc(net, &net->ro_val, (size_t)T * B))) return rc;
-    if ((rc = nalloc(net, &net->ro_rew, (size_t)T * B))) return rc;
-    if ((rc = nalloc(net, &net->ro_y, (size_t)T * B))) return rc;
-    if ((rc = nalloc(net, &net->ro_adv, (size_t)T * B))) return rc;
-    if ((rc = nalloc(net, &net->ro_boot, (size_t)B))) return rc;
-    if ((rc = nalloc(net, &net->ro_done, (size_t)T * E))) return rc;
-    if ((rc = nalloc(net, &net->ro_pmu, (size_t)T * B * 2))) return rc;      // the policy the actions were drawn from: the gradient
-    if ((rc = nalloc(net, &net->ro_psg, (size_t)T * B * 2))) return rc;      // step bounds its head gradients with it (loss scale)
+    if ((rc = paac_alloc(net, &net->ro_lb, (size_t)T * E * 160))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_ab, (size_t)T * E * 20))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_pos, (size_t)T * E * 20))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_act, (size_t)T * B * 2))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_envact, (size_t)B * 2))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_val, (size_t)T * B))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_rew, (size_t)T * B))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_y, (size_t)T * B))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_adv, (size_t)T * B))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_boot, (size_t)B))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_done, (size_t)T * E))) return rc;
+    if ((rc = paac_alloc(net, &net->ro_pmu, (size_t)T * B * 2))) return rc;      // the policy the actions were drawn from: the gradient
+    if ((rc = paac_alloc(net, &net->ro_psg, (size_t)T * B * 2))) return rc;      // step bounds its head gradients with it (loss scale)
     net->T = T; net->B = B;
     // rollout-resident activations when they fit (with headroom for the training workspace and RCCL)
     if (net->keep) { (void)hipFree(net->keep); net->keep = nullptr; net->keep_slots = 0; }
@@ -1485,7 +1438,7 @@ static int ensure_rollout_bufs(grl_net *net, int T) {
     if (!(net->cfg.reserved & GRL_NET_F_RECOMPUTE_FORWARD)) {
         const size_t ce = net->chunk / 10, nchunks = ((size_t)E + ce - 1) / ce, slots = (size_t)T * nchunks;
         size_t free_b = 0, total_b = 0;
-        NET_HIP(net, hipMemGetInfo(&free_b, &total_b));
+        PAAC_HIP(net, hipMemGetInfo(&free_b, &total_b));
         if (net->keep_free_capped) free_b = std::min(free_b, net->keep_free_cap);      // GRL_NET_KEEP_FREE_MB: the descent below at any size
         const size_t headroom = ((size_t)12 << 30) + (size_t)net->chunk * 160000;   // training buffers: ~105 KB per chunk sample
         net->keep_headroom = headroom; net->keep_free_seen = free_b;
@@ -1506,7 +1459,7 @@ static int ensure_rollout_bufs(grl_net *net, int T) {
                 (void)hipFree(net->keep);
                 net->keep = nullptr; net->keep_slots = 0; net->keep_level = 0;
                 net->T = 0;      // no rollout stored: the next call comes through here again
-                return nfail(net, GRL_E_INVALID, "ensure_rollout_bufs: bind_activations and keep_floats_per_slot disagree about a resident slot");
+                return paac_fail(net, GRL_E_INVALID, "ensure_rollout_bufs: bind_activations and keep_floats_per_slot disagree about a resident slot");
             }
         }
     }
@@ -1520,17 +1473,17 @@ using namespace grl;
 extern "C" {
 
 int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
-    if (!net || T <= 0 || T > 1024 || (reward_layout != 0 && reward_layout != 1)) return nfail(net, GRL_E_INVALID, "grl_net_rollout: bad argument");
+    if (!net || T <= 0 || T > 1024 || (reward_layout != 0 && reward_layout != 1)) return paac_fail(net, GRL_E_INVALID, "grl_net_rollout: bad argument");
     const double ht0 = host_now_ms();
     grl_handle *h = net->h;
-    if (net->ho.A != 2) return nfail(net, GRL_E_INVALID, "grl_net_rollout: SwarmEnv.step takes (10, 2) actions; this net was built with num_actions != 2");
+    if (net->ho.A != 2) return paac_fail(net, GRL_E_INVALID, "grl_net_rollout: SwarmEnv.step takes (10, 2) actions; this net was built with num_actions != 2");
     hipSetDevice(h->cfg.device_id);
     int rc = ensure_rollout_bufs(net, T);
     if (rc) return rc;
     const int E = h->E, B = E * 10, ce = net->chunk / 10, nchunks = (E + ce - 1) / ce;
     net->T = T;
     net->keep_version = net->keep && (size_t)T * nchunks <= net->keep_slots ? net->param_version : -1;
-    if (reward_layout == 1) NET_HIP(net, hipMemsetAsync(net->ro_rew, 0, (size_t)T * B * 4, h->stream));
+    if (reward_layout == 1) PAAC_HIP(net, hipMemsetAsync(net->ro_rew, 0, (size_t)T * B * 4, h->stream));
     // Envs are independent, so a chunk of envs is its own T-step pipeline: forward -> a = mu + sigma*N(0,1) -> norm clip -> env step /
     // auto-reset / observe -> bookkeeping -> next forward.  Chunk c always runs on lane c % nl (a HIP stream keeps its order), so
     // the lanes never wait for each other inside the rollout: the fp64 VALU-bound env step and the memory-bound helper kernels of
@@ -1572,7 +1525,7 @@ int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
             if ((rc = swarm_launch_step_range(h, net->ro_envact, e0, ne, net->cur_lane, true)) ||
                 (rc = episodes_launch_account(h, e0, ne))) {      // R6 (paac.py:331-349), when enabled on the handle
                 (void)lanes_join(net);
-                return nfail(net, rc, h->err);
+                return paac_fail(net, rc, h->err);
             }
             hipLaunchKernelGGL(reward_layout_kernel, dim3((ne * 10 + 255) / 256), dim3(256), 0, st, h->reward, e0, ne, reward_layout,
                                net->ro_rew + (size_t)t * B, (const uint8_t *)h->done, net->ro_done + (size_t)t * E);
@@ -1581,9 +1534,9 @@ int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
     // n-step returns over all columns (paac.py:360-372)
     if ((rc = launch_returns(h, net->ro_rew, net->ro_val, nullptr, net->ro_boot, T, B, net->cfg.gamma, 1.0f, net->cfg.scale, 0.f, 0.f,
                              net->ro_y, net->ro_adv)))
-        return nfail(net, rc, h->err);
+        return paac_fail(net, rc, h->err);
     hipLaunchKernelGGL(rollout_range_mark_kernel, dim3(1), dim3(1), 0, h->stream, range_flag_ptr(net));
-    NET_HIP(net, hipGetLastError());
+    PAAC_HIP(net, hipGetLastError());
     h->step_in_flight = true;
     net->ht_rollout_ms += host_now_ms() - ht0;
     net->ht_rollouts += 1;
@@ -1593,7 +1546,7 @@ int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
 // gradient of the last rollout into lane 0's accumulator (every chunk, all lanes, folded); finish: 0 = stop there (local
 // statistics only), 1 = all-reduce + clip + Adam
 static int train_rollout_impl(grl_net *net, float lr, float *stats_host, int finish) {
-    if (!net || !net->ro_lb || net->T <= 0) return nfail(net, GRL_E_STATE, "grl_net_train_rollout: no rollout to train on");
+    if (!net || !net->ro_lb || net->T <= 0) return paac_fail(net, GRL_E_STATE, "grl_net_train_rollout: no rollout to train on");
     grl_handle *h = net->h;
     hipSetDevice(h->cfg.device_id);
     net->ht_train_t0 = host_now_ms();
@@ -1654,16 +1607,11 @@ int grl_net_train_rollout(grl_net *net, float lr, float *stats_host) { return tr
 int grl_net_train_rollout_grads(grl_net *net, float *stats_host) { return train_rollout_checked(net, 0.f, stats_host, 0); }
 
 int grl_net_set_grads(grl_net *net, const float *host, int64_t cnt) {
-    if (!net || !host) return GRL_E_INVALID;
-    if (cnt != net->ho.total) return nfail(net, GRL_E_SIZE, "grl_net_set_grads: expected " + std::to_string((long)net->ho.total) + " floats");
-    hipSetDevice(net->h->cfg.device_id);
-    NET_HIP(net, hipStreamSynchronize(net->h->stream));
-    NET_HIP(net, hipMemcpy(net->grads, host, cnt * 4, hipMemcpyHostToDevice));
-    return GRL_OK;
+    return paac_copy_flat(net, "grl_net_set_grads", net ? net->grads : nullptr, (float *)host, cnt, true);
 }
 
 int grl_net_apply_grads(grl_net *net, float lr, float grad_scale, float *stats_host) {
-    if (!net || !net->train_ready) return nfail(net, GRL_E_STATE, "grl_net_apply_grads: no gradient step has run yet");
+    if (!net || !net->train_ready) return paac_fail(net, GRL_E_STATE, "grl_net_apply_grads: no gradient step has run yet");
     hipSetDevice(net->h->cfg.device_id);
     return train_apply(net, net->last_inv_total, lr, 1, grad_scale, stats_host);
 }
@@ -1671,15 +1619,15 @@ int grl_net_apply_grads(grl_net *net, float lr, float grad_scale, float *stats_h
 static int train_obs_impl(grl_net *net, int32_t n_envs, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, const float *actions,
                           const float *advantages, const float *critic_target, float lr, int32_t apply_update, float *stats_host) {
     if (!net || n_envs <= 0 || !lb || !ab || !pos || !actions || !advantages || !critic_target)
-        return nfail(net, GRL_E_INVALID, "grl_net_train_obs: bad argument");
+        return paac_fail(net, GRL_E_INVALID, "grl_net_train_obs: bad argument");
     grl_handle *h = net->h;
     hipSetDevice(h->cfg.device_id);
     int rc = ensure_tmp_obs(net, n_envs);
     if (rc) return rc;
     hipStream_t st0 = net->lane_stream[0];
-    NET_HIP(net, hipMemcpyAsync(net->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, st0));
-    NET_HIP(net, hipMemcpyAsync(net->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, st0));
-    NET_HIP(net, hipMemcpyAsync(net->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, st0));
+    PAAC_HIP(net, hipMemcpyAsync(net->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, st0));
+    PAAC_HIP(net, hipMemcpyAsync(net->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, st0));
+    PAAC_HIP(net, hipMemcpyAsync(net->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, st0));
     TrainBufs tb[GRL_MAX_LANES];
     if ((rc = train_begin(net, tb))) { (void)lanes_join(net); return rc; }
     const int ce = net->chunk / 10, nl = lanes_active(net);
@@ -1692,13 +1640,13 @@ static int train_obs_impl(grl_net *net, int32_t n_envs, const uint8_t *lb, const
         hipError_t ce = hipMemcpyAsync(t.cact, actions + s0 * net->ho.A, (size_t)ne * 10 * net->ho.A * 4, hipMemcpyHostToDevice, st0);
         if (ce == hipSuccess) ce = hipMemcpyAsync(t.cadv, advantages + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st0);
         if (ce == hipSuccess) ce = hipMemcpyAsync(t.cy, critic_target + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st0);
-        if (ce != hipSuccess) return nfail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(ce));
+        if (ce != hipSuccess) return paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(ce));
         bind_activations(net, -1);
         if ((rc = forward_chunk(net, net->tmp_lb + (size_t)e0 * 160, net->tmp_ab + (size_t)e0 * 20, net->tmp_pos + (size_t)e0 * 20, ne, t.cmu,
                                 t.csigma, t.cvs)) ||
             (rc = train_bound_rows(net, t.cmu, t.csigma, t.cvs, t.cact, t.cadv, t.cy, (long)ne * 10)))
             return rc;
-        NET_HIP(net, hipStreamSynchronize(st0));      // host staging buffers are reused by the next chunk
+        PAAC_HIP(net, hipStreamSynchronize(st0));      // host staging buffers are reused by the next chunk
     }
     if ((rc = train_scale_and_fork(net, inv_total))) { (void)lanes_join(net); return rc; }
     for (int e0 = 0; e0 < n_envs; e0 += ce) {
@@ -1713,9 +1661,9 @@ static int train_obs_impl(grl_net *net, int32_t n_envs, const uint8_t *lb, const
         if (ce == hipSuccess) ce = hipMemcpyAsync(t.cy, critic_target + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st);
         rc = ce == hipSuccess ? backward_chunk(net, t, net->tmp_lb + (size_t)e0 * 160, net->tmp_ab + (size_t)e0 * 20,
                                                net->tmp_pos + (size_t)e0 * 20, ne, t.cact, t.cadv, t.cy, inv_total)
-                              : nfail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(ce));
+                              : paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(ce));
         if (rc == GRL_OK && (ce = hipStreamSynchronize(st)) != hipSuccess)      // host staging buffers are reused by the next chunk
-            rc = nfail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipStreamSynchronize: ") + hipGetErrorString(ce));
+            rc = paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipStreamSynchronize: ") + hipGetErrorString(ce));
         if (rc) { (void)lanes_join(net); return rc; }
     }
     return train_finish(net, tb, inv_total, lr, apply_update, stats_host);
@@ -1754,17 +1702,8 @@ int grl_net_keep_info(grl_net *net, int32_t *level_out, int64_t *slots_out, int6
     return GRL_OK;
 }
 
-int grl_net_get_action_counter(grl_net *net, uint64_t *out) {
-    if (!net || !out) return GRL_E_INVALID;
-    *out = (uint64_t)net->act_counter;
-    return GRL_OK;
-}
-
-int grl_net_set_action_counter(grl_net *net, uint64_t value) {
-    if (!net) return GRL_E_INVALID;
-    net->act_counter = (unsigned long)value;
-    return GRL_OK;
-}
+int grl_net_get_action_counter(grl_net *net, uint64_t *out) { return paac_get_action_counter(net, out); }
+int grl_net_set_action_counter(grl_net *net, uint64_t value) { return paac_set_action_counter(net, value); }
 
 int grl_comm_unique_id(void *out, size_t bytes) {
     if (!out || bytes != sizeof(ncclUniqueId)) return GRL_E_INVALID;
@@ -1779,65 +1718,24 @@ int grl_comm_unique_id(void *out, size_t bytes) {
 size_t grl_comm_unique_id_bytes(void) { return sizeof(ncclUniqueId); }
 
 int grl_net_comm_init(grl_net *net, const void *unique_id, size_t bytes, int32_t rank, int32_t world_size) {
-    if (!net || !unique_id || bytes != sizeof(ncclUniqueId) || world_size < 1 || rank < 0 || rank >= world_size)
-        return nfail(net, GRL_E_INVALID, "grl_net_comm_init: bad argument");
-    if (net->comm) return nfail(net, GRL_E_STATE, "grl_net_comm_init: communicator already attached");
-    hipSetDevice(net->h->cfg.device_id);
-    ncclUniqueId id;
-    memcpy(&id, unique_id, sizeof(id));
-    ncclComm_t comm;
-    ncclResult_t r = ncclCommInitRank(&comm, world_size, id, rank);
-    (void)hipGetLastError();
-    if (r != ncclSuccess) return nfail(net, GRL_E_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-    net->comm = (void *)comm; net->comm_world = world_size; net->comm_rank = rank;
-    return GRL_OK;
+    return paac_comm_init(net, "grl_net_comm_init", unique_id, bytes, rank, world_size);
 }
 
 int grl_net_comm_info(grl_net *net, int32_t *count_out, int32_t *user_rank_out, int64_t *allreduce_calls_out,
                       double *allreduce_ms_total_out, float *allreduce_ms_last_out) {
-    if (!net) return GRL_E_INVALID;
-    int count = 0, urank = -1;
-    if (net->comm) {
-        ncclResult_t r = ncclCommCount((ncclComm_t)net->comm, &count);
-        if (r == ncclSuccess) r = ncclCommUserRank((ncclComm_t)net->comm, &urank);
-        (void)hipGetLastError();
-        if (r != ncclSuccess) return nfail(net, GRL_E_COMM, std::string("ncclCommCount: ") + ncclGetErrorString(r));
-    }
-    if (count_out) *count_out = count;
-    if (user_rank_out) *user_rank_out = urank;
-    if (allreduce_calls_out) *allreduce_calls_out = net->ar_calls;
-    if (allreduce_ms_total_out) *allreduce_ms_total_out = net->ar_ms_total;
-    if (allreduce_ms_last_out) *allreduce_ms_last_out = net->ar_ms_last;
-    return GRL_OK;
+    return paac_comm_info(net, count_out, user_rank_out, allreduce_calls_out, allreduce_ms_total_out, allreduce_ms_last_out);
 }
 
 int grl_net_comm_broadcast_params(grl_net *net, int32_t root) {
-    if (!net || !net->comm) return nfail(net, GRL_E_STATE, "grl_net_comm_broadcast_params: no communicator");
-    hipSetDevice(net->h->cfg.device_id);
-    ncclResult_t r = ncclBroadcast(net->params, net->params, (size_t)net->ho.total, ncclFloat, root, (ncclComm_t)net->comm, net->h->stream);
-    (void)hipGetLastError();
-    if (r != ncclSuccess) return nfail(net, GRL_E_COMM, std::string("ncclBroadcast: ") + ncclGetErrorString(r));
-    net->param_version += 1;
-    refresh_transposes(net);
-    NET_HIP(net, hipStreamSynchronize(net->h->stream));
-    return GRL_OK;
+    int rc = paac_comm_broadcast_params(net, "grl_net_comm_broadcast_params", root);
+    return rc ? rc : params_moved(net);
 }
 
-int grl_net_comm_destroy(grl_net *net) {
-    if (!net) return GRL_E_INVALID;
-    if (net->comm) {
-        hipSetDevice(net->h->cfg.device_id);
-        hipStreamSynchronize(net->h->stream);
-        ncclCommDestroy((ncclComm_t)net->comm);
-        (void)hipGetLastError();
-        net->comm = nullptr;
-    }
-    return GRL_OK;
-}
+int grl_net_comm_destroy(grl_net *net) { return paac_comm_destroy(net); }
 
 int grl_net_read_rollout(grl_net *net, const char *which, void *host, size_t bytes) {
     if (!net || !which || !host) return GRL_E_INVALID;
-    if (!net->ro_lb) return nfail(net, GRL_E_STATE, "grl_net_read_rollout: no rollout yet");
+    if (!net->ro_lb) return paac_fail(net, GRL_E_STATE, "grl_net_read_rollout: no rollout yet");
     hipSetDevice(net->h->cfg.device_id);
     std::string w(which);
     const size_t T = net->T, B = net->B, E = net->h->E;
@@ -1853,10 +1751,10 @@ int grl_net_read_rollout(grl_net *net, const char *which, void *host, size_t byt
     else if (w == "agent_bins") { src = net->ro_ab; need = T * E * 20; }
     else if (w == "positions") { src = net->ro_pos; need = T * E * 20; }
     else if (w == "dones") { src = net->ro_done; need = T * E; }
-    else return nfail(net, GRL_E_INVALID, "grl_net_read_rollout: unknown buffer '" + w + "'");
-    if (need != bytes) return nfail(net, GRL_E_SIZE, "grl_net_read_rollout: '" + w + "' needs " + std::to_string(need) + " bytes");
-    NET_HIP(net, hipStreamSynchronize(net->h->stream));
-    NET_HIP(net, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+    else return paac_fail(net, GRL_E_INVALID, "grl_net_read_rollout: unknown buffer '" + w + "'");
+    if (need != bytes) return paac_fail(net, GRL_E_SIZE, "grl_net_read_rollout: '" + w + "' needs " + std::to_string(need) + " bytes");
+    PAAC_HIP(net, hipStreamSynchronize(net->h->stream));
+    PAAC_HIP(net, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
     return GRL_OK;
 }
 

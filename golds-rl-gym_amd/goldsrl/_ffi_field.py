@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _ffi_paac
 
 _P, _I, _F = C.c_void_p, C.c_int32, C.c_float
 
@@ -46,68 +46,14 @@ def field_param_shapes(height=32, width=32, channels=3, filters=5, conv_layers=2
 
 def glorot_uniform_flat(seed=3, **geometry):
     """tf.layers defaults: glorot-uniform kernels, zero biases -> flat float32 vector."""
-    rng = np.random.RandomState(seed)
-    parts = []
-    for name, shape in field_param_shapes(**geometry):
-        if name.endswith("_w"):
-            if len(shape) == 2:
-                fan_in, fan_out = shape
-            else:
-                rf = int(np.prod(shape[:-2]))
-                fan_in, fan_out = rf * shape[-2], rf * shape[-1]
-            lim = np.sqrt(6.0 / (fan_in + fan_out))
-            parts.append(rng.uniform(-lim, lim, size=shape).astype(np.float32).reshape(-1))
-        else:
-            parts.append(np.zeros(int(np.prod(shape)), np.float32))
-    return np.concatenate(parts)
+    return _ffi_paac.glorot_uniform_flat(field_param_shapes(**geometry), seed)
 
 
-class FieldNet(object):
+class FieldNet(_ffi_paac.PaacNet):
+    PREFIX = "grl_fieldnet_"
+
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=FIELD_SIGNATURES)
-        self.eng = engine
-        cfg = GrlFieldnetConfig()
-        self.lib.grl_fieldnet_config_default(C.byref(cfg))
-        for k, v in kw.items():
-            if not hasattr(cfg, k):
-                raise TypeError("unknown grl_fieldnet_config field %r" % k)
-            setattr(cfg, k, v)
-        self.cfg = cfg
-        n = C.c_void_p()
-        rc = self.lib.grl_fieldnet_create(engine.h, C.byref(cfg), C.byref(n))
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, self.lib.grl_last_error(engine.h).decode())
-        self.n = n
-        self.num_params = int(self.lib.grl_fieldnet_num_params(n))
-
-    def _check(self, rc):
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, self.lib.grl_fieldnet_last_error(self.n).decode())
-
-    def close(self):
-        if getattr(self, "n", None):
-            self.lib.grl_fieldnet_destroy(self.n)
-            self.n = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, flat):
-        a = np.ascontiguousarray(flat, np.float32)
-        self._check(self.lib.grl_fieldnet_set_params(self.n, _ffi._ptr(a), a.size))
-
-    def get_params(self):
-        a = np.empty(self.num_params, np.float32)
-        self._check(self.lib.grl_fieldnet_get_params(self.n, _ffi._ptr(a), a.size))
-        return a
-
-    def get_grads(self):
-        a = np.empty(self.num_params, np.float32)
-        self._check(self.lib.grl_fieldnet_get_grads(self.n, _ffi._ptr(a), a.size))
-        return a
+        self._create(engine, FIELD_SIGNATURES, GrlFieldnetConfig(), kw)
 
     def _inputs(self, states, positions):
         c = self.cfg
@@ -131,7 +77,4 @@ class FieldNet(object):
         adv, y = np.ascontiguousarray(advantages, np.float32), np.ascontiguousarray(critic_target, np.float32)
         if a.shape != (n, int(self.cfg.num_actions)) or adv.shape != (n,) or y.shape != (n,):
             raise ValueError("train: actions (n,A), advantages (n,), critic_target (n,) expected")
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_fieldnet_train(self.n, n, _ffi._ptr(s), _ffi._ptr(p), _ffi._ptr(a), _ffi._ptr(adv), _ffi._ptr(y), lr,
-                                                1 if apply_update else 0, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
+        return self._stats4("train", n, _ffi._ptr(s), _ffi._ptr(p), _ffi._ptr(a), _ffi._ptr(adv), _ffi._ptr(y), lr, 1 if apply_update else 0)

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _ffi_paac
 
 _P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 
@@ -89,85 +89,11 @@ def default_init_flat(seed=3, **kw):
     return np.concatenate(parts).astype(np.float32)
 
 
-class FlatNet(object):
+class FlatNet(_ffi_paac.PaacTrainerNet):
+    PREFIX = "grl_fnet_"
+
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=dict(FNET_SIGNATURES, **FNET_EVAL_SIGNATURES, **FNET_WINDOW_SIGNATURES))
-        self.eng = engine
-        cfg = GrlFnetConfig()
-        self.lib.grl_fnet_config_default(C.byref(cfg))
-        for k, v in kw.items():
-            if not hasattr(cfg, k):
-                raise TypeError("unknown grl_fnet_config field %r" % k)
-            setattr(cfg, k, v)
-        self.cfg = cfg
-        n = C.c_void_p()
-        rc = self.lib.grl_fnet_create(engine.h, C.byref(cfg), C.byref(n))
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, self.lib.grl_last_error(engine.h).decode())
-        self.n = n
-        self.num_params = int(self.lib.grl_fnet_num_params(n))
-
-    def _check(self, rc):
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, self.lib.grl_fnet_last_error(self.n).decode())
-
-    def close(self):
-        if getattr(self, "n", None):
-            self.lib.grl_fnet_destroy(self.n)
-            self.n = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, flat):
-        a = np.ascontiguousarray(flat, np.float32)
-        self._check(self.lib.grl_fnet_set_params(self.n, _ffi._ptr(a), a.size))
-
-    def get_params(self):
-        a = np.empty(self.num_params, np.float32)
-        self._check(self.lib.grl_fnet_get_params(self.n, _ffi._ptr(a), a.size))
-        return a
-
-    def get_grads(self):
-        a = np.empty(self.num_params, np.float32)
-        self._check(self.lib.grl_fnet_get_grads(self.n, _ffi._ptr(a), a.size))
-        return a
-
-    def get_optimizer_state(self):
-        """Adam moments and the number of updates applied: with the parameters, the estimator's whole training state."""
-        m, v = np.empty(self.num_params, np.float32), np.empty(self.num_params, np.float32)
-        step = C.c_int64(0)
-        self._check(self.lib.grl_fnet_get_optimizer_state(self.n, _ffi._ptr(m), _ffi._ptr(v), m.size, C.byref(step)))
-        return {"adam_m": m, "adam_v": v, "adam_step": int(step.value)}
-
-    def set_optimizer_state(self, adam_m, adam_v, adam_step):
-        m, v = np.ascontiguousarray(adam_m, np.float32), np.ascontiguousarray(adam_v, np.float32)
-        self._check(self.lib.grl_fnet_set_optimizer_state(self.n, _ffi._ptr(m), _ffi._ptr(v), m.size, int(adam_step)))
-
-    def get_action_counter(self):
-        v = C.c_uint64(0)
-        self._check(self.lib.grl_fnet_get_action_counter(self.n, C.byref(v)))
-        return int(v.value)
-
-    def set_action_counter(self, value):
-        self._check(self.lib.grl_fnet_set_action_counter(self.n, int(value)))
-
-    def save_checkpoint(self, path, **extra):
-        """Flat-weights checkpoint (.npz): parameters in tf.trainable_variables() order, Adam state, caller's scalars."""
-        st = self.get_optimizer_state()
-        np.savez(path, params=self.get_params(), adam_m=st["adam_m"], adam_v=st["adam_v"], adam_step=st["adam_step"], action_counter=self.get_action_counter(),
-                 **{k: np.asarray(v) for k, v in extra.items()})
-
-    def load_checkpoint(self, path):
-        with np.load(path) as z:
-            self.set_params(z["params"])
-            self.set_optimizer_state(z["adam_m"], z["adam_v"], int(z["adam_step"]))
-            if "action_counter" in z.files:      # the action-noise stream continues where the saved run stopped
-                self.set_action_counter(int(z["action_counter"]))
-            return {k: z[k] for k in z.files if k not in ("params", "adam_m", "adam_v", "adam_step", "action_counter")}
+        self._create(engine, dict(FNET_SIGNATURES, **FNET_EVAL_SIGNATURES, **FNET_WINDOW_SIGNATURES), GrlFnetConfig(), kw)
 
     def _outs(self, n):
         A = self.cfg.num_actions
@@ -186,9 +112,7 @@ class FlatNet(object):
 
     def train(self, states, histories, actions, advantages, critic_target, lr, apply_update=True):
         arrs = [np.ascontiguousarray(a, np.float32) for a in (states, histories, actions, advantages, critic_target)]
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_fnet_train(self.n, arrs[0].shape[0], *[_ffi._ptr(a) for a in arrs], lr, 1 if apply_update else 0, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
+        return self._stats4("train", arrs[0].shape[0], *([_ffi._ptr(a) for a in arrs] + [lr, 1 if apply_update else 0]))
 
     _last_T = 0
 
@@ -240,59 +164,12 @@ class FlatNet(object):
                 self._check(self.lib.grl_fnet_read_eval(self.n, k.encode(), _ffi._ptr(out[k]), out[k].nbytes))
         return out
 
-    def train_rollout(self, lr):
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_fnet_train_rollout(self.n, lr, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
-
-    def train_rollout_grads(self):
-        """Loss + backward over the last rollout only: the local mean gradient stays in the net (get_grads)."""
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_fnet_train_rollout_grads(self.n, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
-
-    def set_grads(self, flat):
-        a = np.ascontiguousarray(flat, np.float32)
-        self._check(self.lib.grl_fnet_set_grads(self.n, _ffi._ptr(a), a.size))
-
-    def apply_grads(self, lr, grad_scale=1.0):
-        """clip_by_global_norm(grad_scale * grads) + Adam(lr) on the gradient currently in the net."""
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_fnet_apply_grads(self.n, lr, grad_scale, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
-
-    # ---- multi-GPU: one RCCL all-reduce of the flat gradient per rollout (include/goldsrl_flatnet.h)
-    def comm_unique_id(self):
-        n = int(self.lib.grl_comm_unique_id_bytes())
-        buf = np.zeros(n, np.uint8)
-        rc = self.lib.grl_comm_unique_id(_ffi._ptr(buf), n)
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, "grl_comm_unique_id")
-        return buf
-
-    def comm_init(self, unique_id, rank, world_size):
-        buf = np.ascontiguousarray(unique_id, np.uint8)
-        self._check(self.lib.grl_fnet_comm_init(self.n, _ffi._ptr(buf), buf.size, rank, world_size))
-
-    def comm_broadcast_params(self, root=0):
-        self._check(self.lib.grl_fnet_comm_broadcast_params(self.n, root))
-
     def rollout_stage_times(self):
         """Constant-clock ticks (10 ns) of workgroup 0 at every barrier of the last persistent rollout (first call: attaches)."""
         buf = np.zeros(4096, np.int64)
         n = C.c_int32()
         self._check(self.lib.grl_fnet_rollout_stage_times(self.n, _ffi._ptr(buf), 4096, C.byref(n)))
         return buf[:n.value].copy()
-
-    def comm_info(self):
-        """What RCCL reports for the attached communicator (ranks = ncclCommCount, 0 without one) and the all-reduce timing."""
-        cnt, ur, calls, tot, last = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double(), C.c_float()
-        self._check(self.lib.grl_fnet_comm_info(self.n, C.byref(cnt), C.byref(ur), C.byref(calls), C.byref(tot), C.byref(last)))
-        return {"rccl_ranks": cnt.value, "rccl_user_rank": ur.value, "allreduce_calls": calls.value,
-                "allreduce_ms_total": tot.value, "allreduce_ms_last": last.value}
-
-    def comm_destroy(self):
-        self._check(self.lib.grl_fnet_comm_destroy(self.n))
 
     def read_rollout(self, which, shape):
         a = np.empty(shape, np.float32)

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _ffi_paac
 
 _P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 
@@ -75,105 +75,16 @@ CONV_PARAM_SHAPES = conv_param_shapes(2)      # train_paac_conv.py: SwarmEnviron
 
 def glorot_uniform_flat(seed=3, num_actions=2):
     """tf.layers defaults: glorot-uniform kernels, zero biases -> flat float32 vector."""
-    rng = np.random.RandomState(seed)
-    parts = []
-    for name, shape in conv_param_shapes(num_actions):
-        if name.endswith("_w"):
-            if len(shape) == 2:
-                fan_in, fan_out = shape
-            else:
-                rf = int(np.prod(shape[:-2]))
-                fan_in, fan_out = rf * shape[-2], rf * shape[-1]
-            lim = np.sqrt(6.0 / (fan_in + fan_out))
-            parts.append(rng.uniform(-lim, lim, size=shape).reshape(-1))
-        else:
-            parts.append(np.zeros(int(np.prod(shape))))
-    return np.concatenate(parts).astype(np.float32)
+    return _ffi_paac.glorot_uniform_flat(conv_param_shapes(num_actions), seed)
 
 
-class ConvNet(object):
+class ConvNet(_ffi_paac.PaacTrainerNet):
     """ConvSingleAgentPolicyNetwork on the device of a Swarm Engine."""
 
+    PREFIX = "grl_net_"
+
     def __init__(self, engine, **kw):
-        self.lib = _ffi.load_library(extra_signatures=NET_SIGNATURES)
-        self.eng = engine
-        cfg = GrlNetConfig()
-        rc = self.lib.grl_net_config_default(NET_CONV_SINGLE_AGENT, C.byref(cfg))
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, "grl_net_config_default")
-        for k, v in kw.items():
-            if not hasattr(cfg, k):
-                raise TypeError("unknown grl_net_config field %r" % k)
-            setattr(cfg, k, v)
-        self.cfg = cfg
-        n = C.c_void_p()
-        rc = self.lib.grl_net_create(engine.h, C.byref(cfg), C.byref(n))
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, self.lib.grl_last_error(engine.h).decode())
-        self.n = n
-        self.num_params = int(self.lib.grl_net_num_params(n))
-
-    def _check(self, rc):
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, self.lib.grl_net_last_error(self.n).decode())
-
-    def close(self):
-        if getattr(self, "n", None):
-            self.lib.grl_net_destroy(self.n)
-            self.n = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, flat):
-        a = np.ascontiguousarray(flat, dtype=np.float32)
-        self._check(self.lib.grl_net_set_params(self.n, _ffi._ptr(a), a.size))
-
-    def get_params(self):
-        a = np.empty(self.num_params, np.float32)
-        self._check(self.lib.grl_net_get_params(self.n, _ffi._ptr(a), a.size))
-        return a
-
-    def get_grads(self):
-        a = np.empty(self.num_params, np.float32)
-        self._check(self.lib.grl_net_get_grads(self.n, _ffi._ptr(a), a.size))
-        return a
-
-    def get_optimizer_state(self):
-        """Adam moments and the number of updates applied: with the parameters, the estimator's whole training state."""
-        m, v = np.empty(self.num_params, np.float32), np.empty(self.num_params, np.float32)
-        step = C.c_int64(0)
-        self._check(self.lib.grl_net_get_optimizer_state(self.n, _ffi._ptr(m), _ffi._ptr(v), m.size, C.byref(step)))
-        return {"adam_m": m, "adam_v": v, "adam_step": int(step.value)}
-
-    def set_optimizer_state(self, adam_m, adam_v, adam_step):
-        m, v = np.ascontiguousarray(adam_m, np.float32), np.ascontiguousarray(adam_v, np.float32)
-        self._check(self.lib.grl_net_set_optimizer_state(self.n, _ffi._ptr(m), _ffi._ptr(v), m.size, int(adam_step)))
-
-    def get_action_counter(self):
-        v = C.c_uint64(0)
-        self._check(self.lib.grl_net_get_action_counter(self.n, C.byref(v)))
-        return int(v.value)
-
-    def set_action_counter(self, value):
-        self._check(self.lib.grl_net_set_action_counter(self.n, int(value)))
-
-    def save_checkpoint(self, path, **extra):
-        """Flat-weights checkpoint (.npz): parameters in tf.trainable_variables() order, Adam state, caller's scalars."""
-        st = self.get_optimizer_state()
-        np.savez(path, params=self.get_params(), adam_m=st["adam_m"], adam_v=st["adam_v"], adam_step=st["adam_step"], action_counter=self.get_action_counter(),
-                 **{k: np.asarray(v) for k, v in extra.items()})
-
-    def load_checkpoint(self, path):
-        with np.load(path) as z:
-            self.set_params(z["params"])
-            self.set_optimizer_state(z["adam_m"], z["adam_v"], int(z["adam_step"]))
-            if "action_counter" in z.files:      # the action-noise stream continues where the saved run stopped
-                self.set_action_counter(int(z["action_counter"]))
-            return {k: z[k] for k in z.files if k not in ("params", "adam_m", "adam_v", "adam_step", "action_counter")}
+        self._create(engine, NET_SIGNATURES, GrlNetConfig(), kw, NET_CONV_SINGLE_AGENT)
 
     def predict(self):
         B, A = self.eng.E * 10, int(self.cfg.num_actions)
@@ -207,34 +118,11 @@ class ConvNet(object):
         y = np.ascontiguousarray(critic_target, np.float32)
         if a.shape != (lb.shape[0] * 10, int(self.cfg.num_actions)):
             raise ValueError("train_obs: actions must be (%d, %d), got %s" % (lb.shape[0] * 10, self.cfg.num_actions, a.shape))
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_net_train_obs(self.n, lb.shape[0], _ffi._ptr(lb), _ffi._ptr(ab), _ffi._ptr(ps), _ffi._ptr(a),
-                                               _ffi._ptr(adv), _ffi._ptr(y), lr, 1 if apply_update else 0, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
+        return self._stats4("train_obs", lb.shape[0], _ffi._ptr(lb), _ffi._ptr(ab), _ffi._ptr(ps), _ffi._ptr(a), _ffi._ptr(adv), _ffi._ptr(y), lr,
+                            1 if apply_update else 0)
 
     def rollout(self, T, reward_layout=0):
         self._check(self.lib.grl_net_rollout(self.n, T, reward_layout))
-
-    def train_rollout(self, lr):
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_net_train_rollout(self.n, lr, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
-
-    def train_rollout_grads(self):
-        """Loss + backward over the last rollout only: the local mean gradient stays in the net (get_grads)."""
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_net_train_rollout_grads(self.n, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
-
-    def set_grads(self, flat):
-        a = np.ascontiguousarray(flat, dtype=np.float32)
-        self._check(self.lib.grl_net_set_grads(self.n, _ffi._ptr(a), a.size))
-
-    def apply_grads(self, lr, grad_scale=1.0):
-        """clip_by_global_norm(grad_scale * grads) + Adam(lr) on the gradient currently in the net."""
-        stats = np.zeros(4, np.float32)
-        self._check(self.lib.grl_net_apply_grads(self.n, lr, grad_scale, _ffi._ptr(stats)))
-        return dict(zip(("loss", "policy_loss", "critic_loss_mean", "global_norm"), stats.tolist()))
 
     def read_rollout(self, which, shape, dtype=np.float32):
         a = np.empty(shape, dtype)
@@ -245,32 +133,6 @@ class ConvNet(object):
         a = np.empty(shape, np.float32)
         self._check(self.lib.grl_net_read_activation(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
         return a
-
-    # -- multi-GPU (RCCL): rank 0 makes the id, everybody attaches
-    def comm_unique_id(self):
-        n = int(self.lib.grl_comm_unique_id_bytes())
-        buf = np.zeros(n, np.uint8)
-        rc = self.lib.grl_comm_unique_id(_ffi._ptr(buf), n)
-        if rc != _ffi.OK:
-            raise _ffi.GrlError(rc, "grl_comm_unique_id")
-        return buf
-
-    def comm_init(self, unique_id, rank, world_size):
-        buf = np.ascontiguousarray(unique_id, np.uint8)
-        self._check(self.lib.grl_net_comm_init(self.n, _ffi._ptr(buf), buf.size, rank, world_size))
-
-    def comm_broadcast_params(self, root=0):
-        self._check(self.lib.grl_net_comm_broadcast_params(self.n, root))
-
-    def comm_info(self):
-        """What RCCL reports for the attached communicator (ranks = ncclCommCount, 0 without one) and the all-reduce timing."""
-        cnt, ur, calls, tot, last = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double(), C.c_float()
-        self._check(self.lib.grl_net_comm_info(self.n, C.byref(cnt), C.byref(ur), C.byref(calls), C.byref(tot), C.byref(last)))
-        return {"rccl_ranks": cnt.value, "rccl_user_rank": ur.value, "allreduce_calls": calls.value,
-                "allreduce_ms_total": tot.value, "allreduce_ms_last": last.value}
-
-    def comm_destroy(self):
-        self._check(self.lib.grl_net_comm_destroy(self.n))
 
     def host_times(self):
         """Wall-clock ms this thread spent enqueueing rollouts / gradient steps and waiting for the device (grl_net_host_times)."""
