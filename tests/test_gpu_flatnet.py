@@ -217,7 +217,8 @@ def test_trade_rollout_with_the_a3c_workers_gae():
 
 def _flat_job(kind, E, T, cap, mode, monkeypatch, group=None):
     """One engine + FlatNet + three rollouts (with R6 accounting on); mode 'graph' keeps the launch-per-stage rollout; group: the
-    persistent kernel's envs per workgroup (GRL_FLAT_GROUP; None = chosen by the env count)."""
+    persistent kernel's envs per workgroup (GRL_FLAT_GROUP; None = chosen by the env count).  Also returns the stage clock's stamp
+    count behind every rollout: the persistent kernel clears it at every launch, the graph's forward launches add to it."""
     from goldsrl import _ffi
     from goldsrl import rollout as R
     if mode == "graph":
@@ -238,8 +239,11 @@ def _flat_job(kind, E, T, cap, mode, monkeypatch, group=None):
     out = []
     A = roll.net.cfg.num_actions
     S0 = roll.net.cfg.static_size
+    roll.net.rollout_stage_times()      # attaches the stage clock
+    stamps = []
     for _ in range(3):
         roll.run(); eng.wait()
+        stamps.append(len(roll.net.rollout_stage_times()))
         d = {k: roll.net.read_rollout(k, (T, E)) for k in ("values", "rewards", "masks", "y", "adv")}
         d["actions"] = roll.net.read_rollout("actions", (T, E, A))
         d["states"] = roll.net.read_rollout("states", (T, E, S0))
@@ -260,7 +264,7 @@ def _flat_job(kind, E, T, cap, mode, monkeypatch, group=None):
         out.append(d)
     pred = roll.net.predict_env()
     roll.net.close(); eng.close()
-    return out, pred
+    return out, pred, stamps
 
 
 @pytest.mark.parametrize("kind,E,cap", [("solow", 200, 7), ("solow", 4096, 1024), ("trade", 200, 9), ("trade", 1000, 1024)])
@@ -270,9 +274,12 @@ def test_persistent_rollout_is_bit_identical_to_the_graph_of_launches(kind, E, c
     state, the handle's outputs, the done list and the R6 records, over three consecutive rollouts with TimeLimit resets (and Solow
     tape refills) inside them; E = 200 and E = 1000 leave the last group partial at every group size."""
     T = 20
-    b, pb = _flat_job(kind, E, T, cap, "graph", monkeypatch)
+    b, pb, sb = _flat_job(kind, E, T, cap, "graph", monkeypatch)
+    assert 0 < sb[0] < 4096 and sb[1] == 2 * sb[0] and sb[2] == 3 * sb[0]      # the graph's launches: their stamps add up
     for group in (64, 32, 16, None):
-        a, pa = _flat_job(kind, E, T, cap, "persistent", monkeypatch, group)
+        a, pa, sa = _flat_job(kind, E, T, cap, "persistent", monkeypatch, group)
+        # the persistent kernel ran, all three times: the same count from zero every time, and not the graph's
+        assert 0 < sa[0] < 4096 and sa[0] == sa[1] == sa[2] and sa[0] != sb[0], (kind, group, sa, sb)
         for u, (da, db) in enumerate(zip(a, b)):
             assert sorted(da) == sorted(db)
             for k in da:
