@@ -1,5 +1,5 @@
-// Included inside namespace grl by net_gated.hip (the Ticker gated trader) and net_gauss.hip (the Gaussian Solow / TradeAR1 agent):
-// the device code the two A3C nets share -- the LDS row layout, the GRU trunk forward and backward, the in-place dx, the window rules
+// Included inside namespace grl by net_gated.hip (the Ticker gated trader), net_gauss.hip (the Gaussian Solow / TradeAR1 agent) and
+// net_discrete.hip (the discrete savings-grid Solow agent): the device code the A3C nets share -- the LDS row layout, the GRU trunk forward and backward, the in-place dx, the window rules
 // with their per-env kernels and the update.  static / inline: every including translation unit has its own copy.  The including
 // file defines first
 //   A3C_DPAD      rows kept for the temporal row x_t (its widest D; the layout, and with it the compiled code, depends on it)
@@ -362,4 +362,30 @@ static __global__ void a3c_post_kernel(const float *__restrict__ reward, const u
         for (int i = 0; i < R * D; ++i) term_wn[(size_t)e * R * D + i] = w[i];
     }
     kstep[e] = a3c_window_step(w, R, D, k, d, obs + (size_t)e * S0 + toff);
+}
+
+// The worker's GAE (worker.py:241-294) per env column, cut at episode ends: delta_t = r_t + g V_next - V_t with V_next = V_{t+1}, or
+// behind a finished episode term[t] (always_bootstrap) / done_penalty = 0; A_t = delta_t + g lam m_t A_{t+1}; target = A_t + V_t,
+// adv = A_t / scale.  float64 running sums like returns_column (rollout_dev.h).  boot[e] becomes the value behind the last step.
+// A template so that only the nets that launch it (the Gaussian and the discrete agent) carry it.
+template <typename F>
+static __global__ void a3c_returns_kernel(const F *__restrict__ r, const F *__restrict__ v, const F *__restrict__ dn,
+                                          const F *__restrict__ term, F *__restrict__ boot, int T, int E, float gamma, float lam, float scale,
+                                          int always_bootstrap, F *__restrict__ y, F *__restrict__ adv) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double g = (double)gamma, gl = g * (double)lam;
+    double run = 0.0, vnext = (double)boot[e];
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t i = (size_t)t * E + e;
+        const bool d = dn[i] != 0.f;
+        if (d) vnext = always_bootstrap ? (double)term[i] : 0.0;
+        if (d && t == T - 1) boot[e] = (F)vnext;
+        const double vt = (double)v[i];
+        const double delta = (double)r[i] + g * vnext - vt;
+        run = delta + (d ? 0.0 : gl * run);
+        y[i] = (F)(run + vt);
+        adv[i] = (F)(run / (double)scale);
+        vnext = vt;
+    }
 }

@@ -1,5 +1,5 @@
-// The host scaffold the two A3C nets share (net_gated.hip, net_gauss.hip): the state grl_gnet and grl_anet derive from and one copy
-// of what they do alike -- allocation lists, parameter / optimizer copies, the training workspace, the update behind the backward
+// The host scaffold the A3C nets share (net_gated.hip, net_gauss.hip, net_discrete.hip): the state grl_gnet, grl_anet and grl_dnet
+// derive from and one copy of what they do alike -- allocation lists, parameter / optimizer copies, the training workspace, the update behind the backward
 // kernel, the evaluation's closing reset and the named read-backs.  Included behind net_a3c_core.inc (it launches its kernels);
 // static: every including translation unit has its own copy.  Functions take the C function's name where their message carries it.
 #pragma once
@@ -180,6 +180,56 @@ static int a3c_train_finish(NET *net, int blocks, long first_tower, double heads
         A3C_HIP(net, hipMemcpy(s, net->stats, sizeof(s), hipMemcpyDeviceToHost));
         for (int i = 0; i < 6; ++i) stats_host[i] = s[i];
     }
+    return GRL_OK;
+}
+
+// The rollout of the nets whose temporal row is the whole processed observation (the Gaussian and the discrete agent; D = S0 =
+// net->D, obs = the handle's processed observation): T steps of record, forward + action, env step, episode accounting and window
+// rule; then V of the window after the last step, with always_bootstrap also V behind every finished episode (workgroups whose 64
+// samples ended none leave at once), and the worker's GAE (worker.py:241-294).  The net brings what differs:
+//   args(n, states, windows)   its forward's argument block (fields vals and gate are set here)
+//   acting(a, o, t)            the heads' outputs and the action of step t into the rollout buffers at sample offset o = t * E
+//   fwd(a)                     the forward launch
+//   env_step(o)                the env's step on the actions recorded at o
+// and the buffers ro_states .. ro_boot, boot_states, boot_win, term_obs by these names.
+template <typename NET, typename ARGS, typename ACTING, typename FWD, typename STEP>
+static int a3c_rollout_run(NET *net, int T, const float *obs, ARGS args, ACTING acting, FWD fwd, STEP env_step) {
+    grl_handle *h = net->h;
+    hipStream_t st = h->stream;
+    const int E = h->E, R = net->cfg.rnn_length, D = net->D, eb = (E + 255) / 256, ab = net->cfg.always_bootstrap;
+    const size_t TE = (size_t)T * E;
+    int rc;
+    if (ab) A3C_HIP(net, hipMemsetAsync(net->ro_term_val, 0, TE * 4, st));      // steps that end no episode read 0
+    hipLaunchKernelGGL((a3c_sync_kernel<int, int, int>), dim3(eb), dim3(256), 0, st, h->elapsed, obs, net->win, net->kstep, E, R, D, D, 0, net->win_init ? 0 : 1);
+    net->win_init = 1;
+    for (int t = 0; t < T; ++t) {
+        const size_t o = (size_t)t * E;
+        hipLaunchKernelGGL((a3c_record_kernel<int, int>), dim3(eb), dim3(256), 0, st, obs, net->win, net->kstep, E, R, D, D, net->ro_states + o * D,
+                           net->ro_win + o * R * D, net->ro_wt + o);
+        auto a = args(E, net->ro_states + o * D, net->ro_win + o * R * D);
+        a.vals = net->ro_val + o;
+        acting(a, o, t);
+        if ((rc = fwd(a))) return rc;
+        if ((rc = env_step(o))) return a3c_fail(net, rc, h->err);
+        if ((rc = episodes_launch_account(h))) return a3c_fail(net, rc, h->err);
+        hipLaunchKernelGGL((a3c_post_kernel<int, int, int>), dim3(eb), dim3(256), 0, st, h->reward, h->done, obs, ab ? net->term_obs : (const float *)nullptr,
+                           net->win, net->kstep, E, R, D, D, 0, net->ro_rew + o, net->ro_done + o, net->ro_mask + o,
+                           ab ? net->ro_term_st + o * D : (float *)nullptr, ab ? net->ro_term_wn + o * R * D : (float *)nullptr);
+    }
+    if (!net->greedy) net->act_counter += (uint64_t)T;      // a greedy rollout draws nothing
+    hipLaunchKernelGGL((a3c_record_kernel<int, int>), dim3(eb), dim3(256), 0, st, obs, net->win, net->kstep, E, R, D, D, net->boot_states, net->boot_win,
+                       (float *)nullptr);
+    auto b = args(E, net->boot_states, net->boot_win);
+    b.vals = net->ro_boot;
+    if ((rc = fwd(b))) return rc;
+    if (ab) {
+        auto c = args((int)TE, net->ro_term_st, net->ro_term_wn);
+        c.gate = net->ro_done; c.vals = net->ro_term_val;
+        if ((rc = fwd(c))) return rc;
+    }
+    hipLaunchKernelGGL(a3c_returns_kernel<float>, dim3(eb), dim3(256), 0, st, net->ro_rew, net->ro_val, net->ro_done, net->ro_term_val, net->ro_boot, T, E,
+                       net->cfg.gamma, net->cfg.gae_lambda, net->cfg.scale, ab, net->ro_tgt, net->ro_adv);
+    A3C_HIP(net, hipGetLastError());
     return GRL_OK;
 }
 

@@ -258,30 +258,6 @@ __global__ __launch_bounds__(256, 1) void gauss_backward_kernel(AArgs a) {
     }
 }
 
-// The worker's GAE (worker.py:241-294) per env column, cut at episode ends: delta_t = r_t + g V_next - V_t with V_next = V_{t+1}, or
-// behind a finished episode term[t] (always_bootstrap) / done_penalty = 0; A_t = delta_t + g lam m_t A_{t+1}; target = A_t + V_t,
-// adv = A_t / scale.  float64 running sums like returns_column (rollout_dev.h).  boot[e] becomes the value behind the last step.
-__global__ void gauss_returns_kernel(const float *__restrict__ r, const float *__restrict__ v, const float *__restrict__ dn,
-                                     const float *__restrict__ term, float *__restrict__ boot, int T, int E, float gamma, float lam, float scale,
-                                     int always_bootstrap, float *__restrict__ y, float *__restrict__ adv) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double g = (double)gamma, gl = g * (double)lam;
-    double run = 0.0, vnext = (double)boot[e];
-    for (int t = T - 1; t >= 0; --t) {
-        const size_t i = (size_t)t * E + e;
-        const bool d = dn[i] != 0.f;
-        if (d) vnext = always_bootstrap ? (double)term[i] : 0.0;
-        if (d && t == T - 1) boot[e] = (float)vnext;
-        const double vt = (double)v[i];
-        const double delta = (double)r[i] + g * vnext - vt;
-        run = delta + (d ? 0.0 : gl * run);
-        y[i] = (float)(run + vt);
-        adv[i] = (float)(run / (double)scale);
-        vnext = vt;
-    }
-}
-
 #include "net_gauss_eval.inc"
 
 }  // namespace grl
@@ -478,48 +454,21 @@ int grl_anet_rollout(grl_anet *net, int32_t T) {
     hipSetDevice(h->cfg.device_id);
     int rc = ensure_rollout(net, T);
     if (rc) return rc;
-    hipStream_t st = h->stream;
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
-    const int E = h->E, R = net->cfg.rnn_length, D = net->D, A = net->A, eb = (E + 255) / 256, ab = net->cfg.always_bootstrap;
-    const float *obs = anet_obs(net);
-    const size_t TE = (size_t)T * E;
-    if (ab) A3C_HIP(net, hipMemsetAsync(net->ro_term_val, 0, TE * 4, st));      // steps that end no episode read 0
-    hipLaunchKernelGGL((a3c_sync_kernel<int, int, int>), dim3(eb), dim3(256), 0, st, h->elapsed, obs, net->win, net->kstep, E, R, D, D, 0, net->win_init ? 0 : 1);
-    net->win_init = 1;
-    for (int t = 0; t < T; ++t) {
-        const size_t o = (size_t)t * E;
-        hipLaunchKernelGGL((a3c_record_kernel<int, int>), dim3(eb), dim3(256), 0, st, obs, net->win, net->kstep, E, R, D, D, net->ro_states + o * D,
-                           net->ro_win + o * R * D, net->ro_wt + o);
-        AArgs a = aargs(net, E, net->ro_states + o * D, net->ro_win + o * R * D);
-        a.mu = net->ro_mu + o * A; a.sigma = net->ro_sigma + o * A; a.vals = net->ro_val + o;
-        a.act = net->ro_act + o * A; a.raw_out = net->ro_raw + o * A; a.tanh_action = solow ? 0 : 1;
-        a.seed = h->cfg.seed; a.env_off = (uint32_t)h->cfg.env_id_offset; a.counter = (uint32_t)(net->act_counter + (uint64_t)t);
-        a.greedy = net->greedy;
-        if ((rc = launch_fwd(net, a))) return rc;
-        rc = solow ? solow_launch_step(h, net->ro_act + o * A, ab ? net->term_obs : nullptr) : trade_launch_step(h, net->ro_act + o * A);
-        if (rc) return a3c_fail(net, rc, h->err);
-        if ((rc = episodes_launch_account(h))) return a3c_fail(net, rc, h->err);
-        hipLaunchKernelGGL((a3c_post_kernel<int, int, int>), dim3(eb), dim3(256), 0, st, h->reward, h->done, obs, ab ? net->term_obs : (const float *)nullptr,
-                           net->win, net->kstep, E, R, D, D, 0, net->ro_rew + o, net->ro_done + o, net->ro_mask + o,
-                           ab ? net->ro_term_st + o * D : (float *)nullptr, ab ? net->ro_term_wn + o * R * D : (float *)nullptr);
-    }
-    if (!net->greedy) net->act_counter += (uint64_t)T;      // a greedy rollout draws nothing
-    // bootstrap: V of the window after the last step; with always_bootstrap also V behind every finished episode (workgroups whose
-    // 64 samples ended none leave at once); then the worker's GAE (worker.py:241-294)
-    hipLaunchKernelGGL((a3c_record_kernel<int, int>), dim3(eb), dim3(256), 0, st, obs, net->win, net->kstep, E, R, D, D, net->boot_states, net->boot_win,
-                       (float *)nullptr);
-    AArgs b = aargs(net, E, net->boot_states, net->boot_win);
-    b.vals = net->ro_boot;
-    if ((rc = launch_fwd(net, b))) return rc;
-    if (ab) {
-        AArgs c = aargs(net, (int)TE, net->ro_term_st, net->ro_term_wn);
-        c.gate = net->ro_done; c.vals = net->ro_term_val;
-        if ((rc = launch_fwd(net, c))) return rc;
-    }
-    hipLaunchKernelGGL(gauss_returns_kernel, dim3(eb), dim3(256), 0, st, net->ro_rew, net->ro_val, net->ro_done, net->ro_term_val, net->ro_boot, T, E,
-                       net->cfg.gamma, net->cfg.gae_lambda, net->cfg.scale, ab, net->ro_tgt, net->ro_adv);
-    A3C_HIP(net, hipGetLastError());
-    return GRL_OK;
+    const size_t A = net->A;
+    const int ab = net->cfg.always_bootstrap;
+    return a3c_rollout_run(
+        net, T, anet_obs(net), [&](int n, const float *states, const float *win) { return aargs(net, n, states, win); },
+        [&](AArgs &a, size_t o, int t) {
+            a.mu = net->ro_mu + o * A; a.sigma = net->ro_sigma + o * A;
+            a.act = net->ro_act + o * A; a.raw_out = net->ro_raw + o * A; a.tanh_action = solow ? 0 : 1;
+            a.seed = h->cfg.seed; a.env_off = (uint32_t)h->cfg.env_id_offset; a.counter = (uint32_t)(net->act_counter + (uint64_t)t);
+            a.greedy = net->greedy;
+        },
+        [&](const AArgs &a) { return launch_fwd(net, a); },
+        [&](size_t o) {
+            return solow ? solow_launch_step(h, net->ro_act + o * A, ab ? net->term_obs : nullptr) : trade_launch_step(h, net->ro_act + o * A);
+        });
 }
 
 int grl_anet_eval(grl_anet *net, int32_t max_steps, int32_t trace_steps) {

@@ -1,5 +1,5 @@
-// Included inside namespace grl by net_flat_mfma.inc (FlatPolicyVNetwork), net_gated.hip (the Ticker gated trader) and
-// net_gauss.hip (the A3C Gaussian agent): the
+// Included inside namespace grl by net_flat_mfma.inc (FlatPolicyVNetwork), net_gated.hip (the Ticker gated trader),
+// net_gauss.hip (the A3C Gaussian agent) and net_discrete.hip (the A3C savings-grid agent): the
 // fp32 MFMA building blocks of the [feature][sample] LDS layout (row stride LS, 64 samples per group) and the fixed-order
 // reduction of per-workgroup gradient slabs.  The includer defines LS and sigmoidf_.
 

@@ -1,11 +1,12 @@
-"""fed_gym/agents/a3c/estimators.py on the device: DiscreteAndContPolicyEstimator (:40-152), GaussianPolicyEstimator (:241-334) and
-ValueEstimator (:338-417) on the shared rnn_graph_lstm trunk (:18-28), as facades over ONE device net (both estimators own the same
+"""fed_gym/agents/a3c/estimators.py on the device: DiscreteAndContPolicyEstimator (:40-152), DiscretePolicyEstimator (:155-238),
+GaussianPolicyEstimator (:241-334) and ValueEstimator (:338-417) on the shared rnn_graph_lstm trunk (:18-28), as facades over ONE device net (both estimators own the same
 parameters, as the reference's two graphs share the "shared" variable scope).  The gated trader (goldsrl._ffi_gated.GatedNet)
 exists for the Ticker sizes only: 2 assets x 3 choices, static input 7, temporal rows 4; the Gaussian agent
-(goldsrl._ffi_gauss.GaussNet) for the Solow sizes (2, 2, 1 action) and the 2-asset TradeAR1 sizes (5, 5, 2 actions); hidden
-sizes 32 / 128."""
+(goldsrl._ffi_gauss.GaussNet) for the Solow sizes (2, 2, 1 action) and the 2-asset TradeAR1 sizes (5, 5, 2 actions); the discrete
+savings-grid agent (goldsrl._ffi_discrete.DiscreteNet) for the Solow sizes with one output of 2..64 choices; hidden sizes 32 / 128."""
 import numpy as np
 
+from ..._ffi_discrete import DiscreteNet
 from ..._ffi_gauss import GaussNet
 
 
@@ -56,6 +57,31 @@ def _is_gauss(net):
     return isinstance(net, GaussNet)
 
 
+def _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size, num_outputs=None, num_choices=None):
+    got = (static_size, temporal_size, static_hidden_size)
+    want = (net.S0, net.D, 128)
+    if got != want or (num_outputs is not None and num_outputs != 1) or (num_choices is not None and num_choices != net.K):
+        raise ValueError("the net was built for static_size=%d, temporal_size=%d, static_hidden_size=%d, num_outputs=1, num_choices=%d "
+                         "(got %r, num_outputs=%r, num_choices=%r)" % (want + (net.K, got, num_outputs, num_choices)))
+
+
+class DiscretePolicyEstimator(object):
+    """predict() returns the reference's key: probs, (n, num_outputs = 1, num_choices).  lb and ub are accepted as the reference's
+    constructor accepts them; it does not use them either (the grid is the worker's, the net's grid_lb / grid_ub here)."""
+
+    def __init__(self, num_outputs, num_choices, static_size, temporal_size, shared_layer=None, static_hidden_size=128, reuse=False,
+                 trainable=True, learning_rate=1e-4, seed=None, lb=-5., ub=5., net=None):
+        if not isinstance(net, DiscreteNet):
+            raise ValueError("pass net=DiscreteNet(solow_engine, num_choices=...): the estimators are facades over one device net")
+        _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size, num_outputs, num_choices)
+        self.net, self.num_outputs, self.num_choices = net, num_outputs, num_choices
+        self.static_size, self.temporal_size, self.learning_rate = static_size, temporal_size, learning_rate
+
+    def predict(self, state, history, sess=None, batch=False):
+        s, h = _batch(state, _window(history, self.net.R), batch)
+        return {"probs": self.net.predict(s, h)["probs"][:, None, :]}
+
+
 def _check_gauss_sizes(net, static_size, temporal_size, static_hidden_size, num_actions=None):
     got = (static_size, temporal_size, static_hidden_size)
     want = (net.sizes["static_size"], net.sizes["temporal_size"], 128)
@@ -90,6 +116,8 @@ class ValueEstimator(object):
                  learning_rate=1e-4, num_actions=2, scale=1., net=None):
         if _is_gauss(net):
             _check_gauss_sizes(net, static_size, temporal_size, static_hidden_size)
+        elif isinstance(net, DiscreteNet):
+            _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size)
         else:
             _check_sizes(static_size, temporal_size, static_hidden_size)
         if net is None:

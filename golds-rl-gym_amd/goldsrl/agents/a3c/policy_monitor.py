@@ -15,7 +15,12 @@ table and no episode that repeats from one evaluation to the next.  All three ar
 choice = the first index of the largest of the three float32 probabilities (np.argmax, as GridSolowWorker.get_greedy_action picks,
 worker.py:370-372), raw = mu[choice], fraction = the worker's float64 sigmoid of raw rounded to float32 (worker.py:229-230).  The
 eval registration: seed 1692 and a reseed at every reset, as the Solow eval registration has it, so env e trades the same 1 024-row
-price window at every evaluation; the table may be another one than the training table."""
+price window at every evaluation; the table may be another one than the training table.
+
+GridPolicyMonitor is the monitor of the discrete savings-grid agent (grl_dnet_eval, include/goldsrl_discreteeval.h) on the Solow
+eval registration.  The reference's PolicyMonitor cannot evaluate that agent -- it reads preds["mu"] -- and GridSolowWorker's own
+greedy path cannot run (get_greedy_action hands the grid value to transform_raw_action, which indexes it, worker.py:370-376).  The
+rule is the evident intention: choice = the first index of the largest float32 probability, action = grid[choice]."""
 import json
 import time
 
@@ -160,4 +165,25 @@ class GatedPolicyMonitor(_DeviceMonitor):
                 raise ValueError("the Ticker eval engine needs a price table")
             eng = make_ticker_eval_engine(table, n_envs, device_id, int(max_episode_steps))
             net = _ffi_gated.GatedNet(eng, rnn_length=max_seq_length, scale=scale, max_samples=1)
+        self._adopt(net, own, summary_writer, max_episode_steps)
+
+
+class GridPolicyMonitor(_DeviceMonitor):
+    """The PolicyMonitor of the discrete savings-grid agent.  env: the Solow eval registration's id.  n_grid, lb, ub: the
+    worker's grid (GridSolowWorker's n_grid, lb, ub).  summary_writer, when given, gets the eval/* scalars through add_scalar.
+    net: an evaluation net to use instead of building one (its `eng` is the eval engine)."""
+
+    def __init__(self, env="Solow-1-1-finite-eval-v0", summary_writer=None, n_envs=1, n_grid=51, lb=0.01, ub=0.99, max_seq_length=5,
+                 scale=1.0, device_id=0, max_episode_steps=1024, net=None):
+        self.env = env
+        own = net is None
+        if net is None:
+            from ... import _ffi_discrete
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            if not env.startswith("Solow-"):
+                raise ValueError("the savings-grid agent exists for the Solow env only (got %r)" % (env,))
+            eng = make_eval_engine(env, n_envs, device_id, int(max_episode_steps))
+            net = _ffi_discrete.DiscreteNet(eng, rnn_length=max_seq_length, scale=scale, num_choices=n_grid, grid_lb=lb, grid_ub=ub,
+                                            max_samples=1)
         self._adopt(net, own, summary_writer, max_episode_steps)

@@ -1,0 +1,435 @@
+"""GPU: the A3C discrete savings-grid agent (csrc/net_discrete.hip through include/goldsrl_discretenet.h) against the float64
+restatement tests/_grid_oracle.py -- predict, the host-sample update, the single-env rollout against the reference worker's update,
+the rollout's replay (sampler, grid, windows, GAE), consistency (host vs rollout path, bitwise reproducibility, checkpoints), greedy
+acting, the estimator facade and the training script."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _grid_oracle as D
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+# Bounds of |device - oracle|.  The arithmetic is the Gaussian net's (exact-fp32 MFMA GEMMs, fixed summation orders), so the bounds
+# are its bounds (tests/test_gpu_gaussnet.py): gradient blocks 1e-6 (policy) / 3e-7 (value) of the block's largest oracle entry plus the
+# gradient's largest entry, forward rtol 5e-5 / atol 5e-6.  The softmax and log head is new; measured on the MI355X against the
+# float64 oracle, every case holds at those bounds, so they are unchanged:
+#   host samples (n = 130, R = 5, mixed weights with zeros, _samples(K, 130, 5, 11)), worst block:
+#     K = 3   1.41e-7 (policy, static2_b)  / 5.80e-8 (value, value2_b)
+#     K = 51  1.38e-7 (policy, temporal_b) / 1.48e-7 (value, value2_w)
+#     K = 64  1.12e-7 (policy, temporal_b) / 4.59e-8 (value, temporal_b)
+#   forward (predict at n = 1 .. 200, R = 1 / 5 / 20, scale 3), worst |device - oracle| / (5e-6 + 5e-5 |oracle|):
+#     K = 3   0.0055 (probs) 0.066 (values);  K = 51  0.0034 / 0.034;  K = 64  0.0028 / 0.040
+GRAD_REL_BOUND = {"policy": 1e-6, "value": 3e-7}
+FWD_RTOL, FWD_ATOL = 5e-5, 5e-6
+
+
+def _engine(E, seed=7, **kw):
+    from goldsrl import _ffi
+    eng = _ffi.Engine(_ffi.ENV_SOLOW, E, seed=seed, **kw)
+    eng.reset()
+    return eng
+
+
+def _net(eng, **kw):
+    from goldsrl import _ffi_discrete
+    kw.setdefault("max_samples", 256)
+    return _ffi_discrete.DiscreteNet(eng, **kw)
+
+
+def _params(K, seed=5):
+    p = D.init(seed, K)
+    rng = np.random.RandomState(seed)
+    for k in p:
+        if k.endswith("_b"):
+            p[k] = p[k] + 0.05 * rng.normal(size=p[k].shape)
+    p["probs3_w"] = p["probs3_w"] * 4.0          # logits a few units apart: probabilities from 1e-4 to 0.5, not a near-uniform row
+    return D.flatten(p).astype(np.float32)
+
+
+def _samples(K, n, R, seed=0):
+    """windows of every true length 0..R, mixed weights with zeros, advantages of both signs"""
+    rng = np.random.RandomState(seed)
+    states = rng.normal(size=(n, 2)).astype(np.float32)
+    win = rng.normal(size=(n, R, 2)).astype(np.float32)
+    lens = (np.arange(n) + seed) % (R + 1)
+    for i in range(n):
+        win[i, lens[i]:] = 0.0
+    ch = rng.randint(0, K, size=n).astype(np.int32)
+    adv = rng.normal(size=n).astype(np.float32)
+    tgt = rng.normal(size=n).astype(np.float32)
+    w = np.where(rng.uniform(size=n) > 0.25, rng.uniform(0.5, 1.5, size=n), 0.0).astype(np.float32)
+    return states, win, ch, adv, tgt, w
+
+
+def _as64(K, flat):
+    return D.unflatten(np.asarray(flat, np.float32).astype(np.float64), K)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = _engine(64)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("R", [1, 5, 20])
+@pytest.mark.parametrize("K", [3, 51, 64])
+def test_predict_matches_oracle(eng, K, R):
+    net = _net(eng, rnn_length=R, scale=3.0, num_choices=K)
+    assert net.num_params == D.num_params(K) == 90561 + 129 * K
+    flat = _params(K)
+    net.set_params(flat)
+    p = _as64(K, flat)
+    worst = {}
+    for n in (1, 63, 64, 65, 200):
+        s, w = _samples(K, n, R, seed=n)[:2]
+        got = net.predict(s, w)
+        ref = D.forward(p, s.astype(np.float64), w.astype(np.float64), 3.0)
+        for k, r in zip(("probs", "values"), ref):
+            assert got[k].shape == r.shape and got[k].dtype == np.float32
+            worst[k] = max(worst.get(k, 0.0), float((np.abs(got[k] - r) / (FWD_ATOL + FWD_RTOL * np.abs(r))).max()))
+        assert np.abs(got["probs"].astype(np.float64).sum(1) - 1.0).max() < 1e-6
+    print("predict K=%d R=%d: worst error / bound %s" % (K, R, {k: "%.3g" % v for k, v in worst.items()}))
+    assert all(v <= 1.0 for v in worst.values()), worst
+    net.close()
+
+
+def _block_err(K, got, ref):
+    """max over blocks of |got - ref|_inf / (the block's largest oracle entry + the gradient's largest), and the worst block's name"""
+    gmax = np.abs(ref).max()
+    worst, name = 0.0, None
+    for b, (lo, hi) in D.block_ranges(K).items():
+        e = np.abs(got[lo:hi] - ref[lo:hi]).max() / (np.abs(ref[lo:hi]).max() + gmax)
+        if e > worst:
+            worst, name = e, b
+    return worst, name
+
+
+@pytest.mark.parametrize("K", [3, 51, 64])
+def test_host_train_gradients_clip_and_rmsprop(eng, K):
+    n, R = 130, 5
+    P = D.num_params(K)
+    net = _net(eng, rnn_length=R, clip_norm=0.5, num_choices=K)
+    flat = _params(K)
+    net.set_params(flat)
+    net.set_optimizer_state(np.ones(P, np.float32), np.ones(P, np.float32), 200000)
+    s, w, ch, adv, tgt, wt = _samples(K, n, R, seed=11)
+    assert (wt == 0).any() and (wt > 0).any() and (adv < 0).any() and (adv > 0).any()
+    mult = 0.3
+    stats = net.train(s, w, ch, adv, tgt, wt, grad_mult=mult, lr=1e-3, apply_update=False)
+    gp, gv = net.get_grads("policy"), net.get_grads("value")
+    args64 = [a.astype(np.float64) for a in (s, w)]
+    (pl, vl, ent), rp, rv = D.grads(_as64(K, flat), *args64, ch, adv, tgt, wt, mult)
+    rp, rv = D.flatten(rp), D.flatten(rv)
+    ep, bp = _block_err(K, gp, rp)
+    ev, bv = _block_err(K, gv, rv)
+    print("K=%d worst block error: policy %.3g (%s), value %.3g (%s)" % (K, ep, bp, ev, bv))
+    assert ep < GRAD_REL_BOUND["policy"] and ev < GRAD_REL_BOUND["value"], (ep, bp, ev, bv)
+    assert not gp[~D.policy_mask(K)].any() and not gv[~D.value_mask(K)].any()
+    np.testing.assert_allclose([stats["policy_loss"], stats["value_loss"], stats["entropy_mean"]], [pl, vl, ent], rtol=1e-4)
+    np.testing.assert_allclose([stats["policy_norm"], stats["value_norm"]], [np.linalg.norm(rp), np.linalg.norm(rv)], rtol=1e-4)
+    # the bound is tight enough to see one 64-sample group go missing
+    keep = np.ones(n, bool); keep[64:128] = False
+    _, mp, mv = D.grads(_as64(K, flat), *[a[keep] for a in args64], ch[keep], adv[keep], tgt[keep], wt[keep], mult)
+    assert _block_err(K, D.flatten(mp), rp)[0] > GRAD_REL_BOUND["policy"] and _block_err(K, D.flatten(mv), rv)[0] > GRAD_REL_BOUND["value"]
+    # clip (0.5 on each gradient) + both RMSProp steps + the lr decay, on the device's own gradient
+    stats = net.train(s, w, ch, adv, tgt, wt, grad_mult=mult, lr=1e-3, apply_update=True)
+    st = net.get_optimizer_state()
+    assert st["global_step"] == 200002
+    lr = D.lr_at(1e-3, 200000)
+    assert abs(stats["lr"] - lr) <= 1e-7 * lr
+    w_ref, msp, msv, step, _, _, _ = D.apply_update(flat.astype(np.float64), gp.astype(np.float64), gv.astype(np.float64), np.ones(P), np.ones(P),
+                                                     200000, 1e-3, K, clip=0.5)
+    np.testing.assert_allclose(net.get_params(), w_ref, rtol=1e-6, atol=1e-9)
+    np.testing.assert_allclose(st["ms_policy"], msp, rtol=1e-6, atol=1e-12)
+    np.testing.assert_allclose(st["ms_value"], msv, rtol=1e-6, atol=1e-12)
+    # a choice outside the grid is refused, not clamped
+    from goldsrl import _ffi
+    bad = ch.copy(); bad[5] = K
+    with pytest.raises(_ffi.GrlError) as ei:
+        net.train(s, w, bad, adv, tgt, wt)
+    assert ei.value.code == _ffi.E_INVALID
+    net.close()
+
+
+REC = ("states", "windows", "probs", "choices", "actions", "values", "rewards", "dones", "weights", "adv", "targets", "boot", "term_values",
+       "term_states", "term_windows")
+
+
+def _read(net):
+    return {k: net.read_rollout(k) for k in REC}
+
+
+@pytest.mark.parametrize("cap", [1024, 9])
+def test_single_env_rollout_is_the_reference_worker_update(cap):
+    """E = 1: the rollout is GridSolowWorker's run_n_steps + update through the oracle.  With the 9-step cap an episode ends inside
+    the rollout: it then holds two worker rollouts, the first bootstrapped from the terminal observation (always_bootstrap), and one
+    update sums their gradients."""
+    R, T, K, scale = 5, 16, 51, 1.0
+    P = D.num_params(K)
+    e1 = _engine(1, seed=3, max_episode_steps=cap)
+    net = _net(e1, rnn_length=R, scale=scale, num_choices=K)
+    assert net.cfg.always_bootstrap == 1
+    flat = _params(K, 9)
+    net.set_params(flat)
+    net.rollout(T)
+    rec = _read(net)
+    stats = net.train_rollout(lr=1e-3)
+    after = net.get_params()
+    st = net.get_optimizer_state()
+    net.close(); e1.close()
+    d = rec["dones"][:, 0] > 0
+    assert np.flatnonzero(d).tolist() == ([] if cap == 1024 else [cap - 1])
+    assert not rec["term_values"][~d].any() and (cap == 1024 or rec["term_values"][d].all())
+    win, wts, twin = D.replay_windows(rec["states"], rec["dones"], R, rec["term_states"])
+    np.testing.assert_array_equal(rec["windows"], win)
+    np.testing.assert_array_equal(rec["weights"], wts)
+    np.testing.assert_array_equal(rec["term_windows"][d], twin[d])
+    p = _as64(K, flat)
+    gp, gv = np.zeros(P), np.zeros(P)
+    segs = ((0, T),) if cap == 1024 else ((0, cap), (cap, T))
+    for lo, hi in segs:
+        keep = np.zeros(T, bool); keep[lo + R - 1:hi] = True
+        assert np.array_equal(rec["weights"][lo:hi, 0] > 0, keep[lo:hi])
+        boot = float(rec["term_values"][hi - 1, 0]) if hi < T else float(rec["boot"][0])
+        s64, w64 = rec["states"][keep, 0].astype(np.float64), rec["windows"][keep, 0].astype(np.float64)
+        V = D.forward(p, s64, w64, scale)[1]
+        feed = D.update_feed(s64, w64, rec["choices"][keep, 0], rec["rewards"][keep, 0], V, boot, 0.99, 0.96, scale)
+        _, a, b = D.grads(p, feed["states"], feed["history"], feed["actions"], feed["advantages"], feed["targets"], None, 1.0, scale)
+        gp += D.flatten(a); gv += D.flatten(b)
+    w_ref, msp, msv, step, lr, normp, normv = D.apply_update(flat.astype(np.float64), gp, gv, np.ones(P), np.ones(P), 0, 1e-3, K)
+    assert st["global_step"] == 2
+    np.testing.assert_allclose([stats["policy_norm"], stats["value_norm"]], [normp, normv], rtol=2e-3)
+    np.testing.assert_allclose(after, w_ref, rtol=1e-5, atol=2e-8)
+    np.testing.assert_allclose(st["ms_policy"], msp, rtol=1e-5, atol=1e-9)
+    np.testing.assert_allclose(st["ms_value"], msv, rtol=1e-5, atol=1e-9)
+
+
+@pytest.mark.parametrize("E", [65, 130])
+def test_rollout_replay(E):
+    T, R, K, cap, scale = 8, 3, 51, 5, 2.0
+    eng = _engine(E, seed=21, max_episode_steps=cap, env_id_offset=1000)
+    net = _net(eng, rnn_length=R, scale=scale, num_choices=K, max_samples=T * E)
+    flat = _params(K, 4)
+    net.set_params(flat)
+    net.set_action_counter(1000)
+    net.rollout(T)
+    r = _read(net)
+    assert net.get_action_counter() == 1000 + T
+    assert r["choices"].dtype == np.int32 and r["dones"][cap - 1].all() and not r["dones"][:cap - 1].any()
+    grid = D.grid(K)
+    # the sampler on the device's OWN float32 probabilities and the oracle's u: exact.  (On the oracle's probabilities a u within
+    # 1e-7 of a cumulative sum would make a correct kernel fail.)
+    for t in range(T):
+        u = D.draws(eng.cfg.seed, np.arange(E) + 1000, 1000 + t)
+        want = np.array([D.choose(r["probs"][t, e], u[e]) for e in range(E)])
+        assert np.array_equal(r["choices"][t], want), t
+    assert np.array_equal(r["actions"], grid[r["choices"]].astype(np.float32))
+    assert len(np.unique(r["choices"])) > K // 2
+    # probs and values against the oracle on the recorded inputs, and bit-equal to predict on them
+    p = _as64(K, flat)
+    S, W = r["states"].reshape(-1, 2), r["windows"].reshape(-1, R, 2)
+    probs, values = D.forward(p, S.astype(np.float64), W.astype(np.float64), scale)
+    np.testing.assert_allclose(r["probs"].reshape(-1, K), probs, rtol=FWD_RTOL, atol=FWD_ATOL)
+    np.testing.assert_allclose(r["values"].reshape(-1), values, rtol=FWD_RTOL, atol=FWD_ATOL)
+    got = net.predict(S, W)
+    np.testing.assert_array_equal(got["probs"], r["probs"].reshape(-1, K))
+    np.testing.assert_array_equal(got["values"], r["values"].reshape(-1))
+    # windows, weights, terminal windows, terminal values
+    win, wts, twin = D.replay_windows(r["states"], r["dones"], R, r["term_states"])
+    dd = r["dones"] > 0
+    np.testing.assert_array_equal(r["windows"], win)
+    np.testing.assert_array_equal(r["weights"], wts)
+    np.testing.assert_array_equal(r["term_windows"][dd], twin[dd])
+    tv = net.predict(r["term_states"][dd], r["term_windows"][dd])["values"]
+    np.testing.assert_array_equal(tv, r["term_values"][dd])
+    assert not r["term_values"][~dd].any()
+    # GAE and targets: the worker's, cut at episode ends
+    adv, tgt = D.gae_segments(r["rewards"], r["values"], r["boot"], r["dones"], r["term_values"], True, 0.99, 0.96, scale)
+    np.testing.assert_allclose(r["adv"], adv, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(r["targets"], tgt, rtol=1e-5, atol=1e-6 * scale)
+    net.close(); eng.close()
+
+
+def test_train_rollout_equals_host_train_reproducible_and_checkpoint(tmp_path):
+    E, T, R, K = 130, 6, 3, 51
+    P = D.num_params(K)
+    kw = dict(max_episode_steps=4)                      # episodes end inside the rollout
+    eng = _engine(E, seed=5, **kw)
+    net = _net(eng, rnn_length=R, num_choices=K, max_samples=T * E)
+    flat = _params(K, 6)
+    net.set_params(flat)
+    net.rollout(T)
+    r = {k: net.read_rollout(k) for k in ("states", "windows", "choices", "adv", "targets", "weights")}
+    s1 = net.train_rollout(lr=1e-3)
+    g_ro = net.get_grads("policy"), net.get_grads("value")
+    p_ro = net.get_params()
+    net.set_params(flat)
+    net.set_optimizer_state(np.ones(P, np.float32), np.ones(P, np.float32), 0)
+    s2 = net.train(r["states"].reshape(-1, 2), r["windows"].reshape(-1, R, 2), r["choices"].reshape(-1), r["adv"].reshape(-1),
+                   r["targets"].reshape(-1), r["weights"].reshape(-1), grad_mult=1.0 / E, lr=1e-3)
+    assert np.array_equal(net.get_grads("policy"), g_ro[0]) and np.array_equal(net.get_grads("value"), g_ro[1])
+    assert np.array_equal(net.get_params(), p_ro) and g_ro[0].any() and g_ro[1].any()
+    assert s1["policy_norm"] == s2["policy_norm"] and s1["value_norm"] == s2["value_norm"]
+    net.close(); eng.close()
+
+    def run(n_upd):
+        e = _engine(E, seed=5, **kw)
+        nt = _net(e, rnn_length=R, num_choices=K)
+        nt.set_params(flat)
+        for _ in range(n_upd):
+            nt.rollout(T)
+            nt.train_rollout(lr=1e-3)
+        res = (nt.get_params(), nt.get_optimizer_state(), nt.get_action_counter(), nt.get_grads("policy"), nt.get_grads("value"))
+        nt.close(); e.close()
+        return res
+    a, b = run(3), run(3)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1]["ms_policy"], b[1]["ms_policy"]) and a[1]["global_step"] == 6
+    assert np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4]) and a[2] == 3 * T
+    # checkpoint after update 1, restored into a fresh net on an engine that carries on from the same env state: same bits as an
+    # uninterrupted run whose net is also re-created (windows restarted) after update 1
+    ck = str(tmp_path / "grid.npz")
+    e = _engine(E, seed=5, **kw)
+    nt = _net(e, rnn_length=R, num_choices=K)
+    nt.set_params(flat)
+    nt.rollout(T); nt.train_rollout(lr=1e-3)
+    nt.save_checkpoint(ck)
+    nt.close()
+    nt2 = _net(e, rnn_length=R, num_choices=K)
+    nt2.load_checkpoint(ck)
+    ck_state = np.load(ck)
+    assert int(ck_state["global_step"]) == 2 and int(ck_state["action_counter"]) == T
+    for _ in range(2):
+        nt2.rollout(T); nt2.train_rollout(lr=1e-3)
+    got = nt2.get_params(), nt2.get_optimizer_state()
+    nt2.close(); e.close()
+    e = _engine(E, seed=5, **kw)
+    nt = _net(e, rnn_length=R, num_choices=K)
+    nt.set_params(flat)
+    nt.rollout(T); nt.train_rollout(lr=1e-3)
+    keep = (nt.get_params(), nt.get_optimizer_state(), nt.get_action_counter())
+    nt.close()
+    nt3 = _net(e, rnn_length=R, num_choices=K)
+    nt3.set_params(keep[0]); nt3.set_optimizer_state(keep[1]["ms_policy"], keep[1]["ms_value"], keep[1]["global_step"])
+    nt3.set_action_counter(keep[2])
+    for _ in range(2):
+        nt3.rollout(T); nt3.train_rollout(lr=1e-3)
+    want = nt3.get_params(), nt3.get_optimizer_state()
+    nt3.close(); e.close()
+    assert got[1]["global_step"] == 6
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1]["ms_value"], want[1]["ms_value"])
+
+
+def test_greedy_rollout():
+    E, T, R, K = 70, 6, 3, 51
+    eng = _engine(E, seed=9, max_episode_steps=4)
+    net = _net(eng, rnn_length=R, num_choices=K)
+    net.set_action_counter(1000)
+    net.set_greedy(True)
+    # zero parameters: a uniform row, the first index, the grid's lower end
+    net.rollout(T)
+    assert net.get_action_counter() == 1000
+    assert (net.read_rollout("probs") == np.float32(1.0) / np.float32(K)).all()
+    assert not net.read_rollout("choices").any() and (net.read_rollout("actions") == np.float32(0.01)).all()
+    # random parameters: the arg-max of the device's own probabilities, first index on ties
+    flat = _params(K, 3)
+    net.set_params(flat)
+    net.rollout(T)
+    r = {k: net.read_rollout(k) for k in ("probs", "choices", "actions")}
+    want = np.array([[D.greedy(r["probs"][t, e]) for e in range(E)] for t in range(T)])
+    assert np.array_equal(r["choices"], want) and len(np.unique(want)) >= 2
+    assert np.array_equal(r["actions"], D.grid(K)[want].astype(np.float32))
+    # a constructed exact tie: columns 7 and 3 of probs3 are the same column with the same, largest, bias
+    p = _as64(K, flat)
+    p["probs3_w"][:, 7] = p["probs3_w"][:, 3]
+    p["probs3_b"][[3, 7]] = 30.0
+    net.set_params(D.flatten(p).astype(np.float32))
+    net.rollout(T)
+    pr, ch = net.read_rollout("probs"), net.read_rollout("choices")
+    assert np.array_equal(pr[..., 3], pr[..., 7]) and (pr[..., 3] > 0.3).all()
+    assert (ch == 3).all() and (net.read_rollout("actions") == np.float32(D.grid(K)[3])).all()
+    assert net.get_action_counter() == 1000
+    # greedy off again: the stochastic rollout of a net that saw the switch equals one that never did
+    net.close(); eng.close()
+    outs = []
+    for switch in (True, False):
+        e = _engine(E, seed=9, max_episode_steps=4)
+        nt = _net(e, rnn_length=R, num_choices=K)
+        nt.set_params(flat)
+        if switch:
+            nt.set_greedy(True); nt.set_greedy(False)
+        nt.rollout(T)
+        outs.append({k: nt.read_rollout(k) for k in ("probs", "choices", "actions", "adv", "targets")})
+        assert nt.get_action_counter() == T
+        nt.close(); e.close()
+    for k in outs[0]:
+        np.testing.assert_array_equal(outs[0][k], outs[1][k], err_msg=k)
+    assert not np.array_equal(outs[0]["choices"], np.argmax(outs[0]["probs"], -1))
+
+
+def test_estimator_facade_and_refusals(eng):
+    from goldsrl import _ffi, _ffi_discrete, _ffi_gauss
+    from goldsrl.agents.a3c import estimators as est
+    K = 3
+    net = _net(eng, rnn_length=5, scale=2.0, num_choices=K)
+    flat = _params(K, 12)
+    net.set_params(flat)
+    pol = est.DiscretePolicyEstimator(1, K, static_size=2, temporal_size=2, net=net)
+    val = est.ValueEstimator(static_size=2, temporal_size=2, net=net, scale=2.0)
+    for bad in (dict(num_outputs=2, num_choices=K), dict(num_outputs=1, num_choices=K + 1)):
+        with pytest.raises(ValueError):
+            est.DiscretePolicyEstimator(static_size=2, temporal_size=2, net=net, **bad)
+    with pytest.raises(ValueError):
+        est.DiscretePolicyEstimator(1, K, static_size=5, temporal_size=5, net=net)
+    with pytest.raises(ValueError):
+        est.DiscretePolicyEstimator(1, K, static_size=2, temporal_size=2, net=None)
+    with pytest.raises(ValueError):
+        est.ValueEstimator(static_size=2, temporal_size=2, net=net, scale=1.0)
+    s, w = _samples(K, 5, 5, seed=2)[:2]
+    hist = w[:, :3].copy(); hist[hist == 0] = 0.5         # three full rows: padded post to R = 5 inside predict
+    p1 = pol.predict(s, hist, batch=True)
+    assert set(p1) == {"probs"} and p1["probs"].shape == (5, 1, K)
+    v1 = val.predict(s, hist, batch=True)
+    ref = D.forward(_as64(K, flat), s.astype(np.float64), np.concatenate([hist, np.zeros((5, 2, 2), np.float32)], 1).astype(np.float64), 2.0)
+    np.testing.assert_allclose(p1["probs"][:, 0], ref[0], rtol=FWD_RTOL, atol=FWD_ATOL)
+    np.testing.assert_allclose(v1["logits"], ref[1], rtol=FWD_RTOL, atol=FWD_ATOL)
+    assert pol.predict(s[0], hist[0])["probs"].shape == (1, 1, K)
+    net.close()
+    # only Solow handles, always_bootstrap 1, 2..64 choices
+    for kw in (dict(always_bootstrap=0), dict(num_choices=1), dict(num_choices=65), dict(grid_lb=0.5, grid_ub=0.5)):
+        with pytest.raises(_ffi.GrlError) as ei:
+            _ffi_discrete.DiscreteNet(eng, **kw)
+        assert ei.value.code == _ffi.E_INVALID
+    e3 = _ffi.Engine(_ffi.ENV_TRADE, 4, n_assets=2)
+    with pytest.raises(_ffi.GrlError) as ei:
+        _ffi_discrete.DiscreteNet(e3)
+    assert ei.value.code == _ffi.E_INVALID
+    e3.close()
+
+
+def test_train_solow_grid_script(tmp_path):
+    out = tmp_path / "run"
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "golds-rl-gym_amd"), os.environ.get("PYTHONPATH", "")]))
+
+    def run(extra):
+        cmd = [sys.executable, "-m", "goldsrl.scripts.train_solow_grid", "--envs", "64", "--t-max", "8", "--updates", "3", "--n-grid", "11",
+               "--eval-envs", "8", "--eval-every", "2", "--model_dir", str(out)] + extra
+        res = subprocess.run(cmd, cwd=ROOT, env=env, timeout=300, capture_output=True, text=True)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+        with np.load(out / "checkpoint.npz") as z:
+            return {k: z[k] for k in z.files}
+    z = run([])
+    files = os.listdir(out)
+    assert any(f.startswith("events.out.tfevents") for f in files) and "Solow-1-1-grid.json" in files
+    assert int(z["global_step"]) == 6 and z["params"].size == D.num_params(11) and int(z["action_counter"]) == 24
+    import json
+    log = json.load(open(out / "Solow-1-1-grid.json"))
+    assert log["n_envs"] == 8 and log["episode_length"] == [1024, 1024] and all(np.isfinite(v) for v in log["mean_total_reward"])
+    z2 = run(["--resume", str(out / "checkpoint.npz")])
+    assert int(z2["global_step"]) == 12 and int(z2["action_counter"]) == 48 and not np.array_equal(z["params"], z2["params"])
