@@ -61,6 +61,17 @@ struct TickerState {
     int rows;
 };
 
+// buffers of grl_solow_sweep (solow_sweep.hip): allocated on first use, grown when a later sweep is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct SolowSweepState {
+    float *rates, *mn, *mx, *trace_r, *trace_k;   // (cap_rates) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace)
+    double *total, *sum_sq;                       // (cap_pairs)
+    int32_t *length, *err;                        // (cap_pairs) (1)
+    uint8_t *finished;                            // (cap_pairs)
+    size_t cap_rates, cap_pairs, cap_trace;
+    int n_rates, max_steps, trace_env;            // of the last sweep; n_rates == 0: none yet
+};
+
 }  // namespace grl
 
 struct grl_handle {
@@ -82,6 +93,7 @@ struct grl_handle {
     grl::SolowState so;
     grl::TradeState tr;
     grl::TickerState tk;
+    grl::SolowSweepState swp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;
     // R6 episode bookkeeping (grl_episodes_*): nullptr until enabled

@@ -123,6 +123,37 @@ __device__ __forceinline__ SolowStepOut solow_step_env(const SolowParams &S, int
     return o;
 }
 
+// The arithmetic of solow_step_env on values held in registers, for a caller that keeps an env's whole state there and plays
+// several savings rates over one shock path (solow_sweep.hip).  Same operations in the same order as lines of solow_step_env
+// above, so the two give the same bits (tests/test_gpu_solow_sweep.py holds them together).
+//
+// The shock history is kept right-aligned in eight registers: zr[8 - P + i] = z[i], so zr[7] is z[-1] and the shift needs no
+// runtime index; rz / re are rho_z / rho_e aligned the same way by the host.  Slots below 8 - P are never read: the sums skip
+// them with a uniform branch instead of adding 0 * z terms.
+struct SolowShockCoef { float rz[8], re[8]; int P, Q; };
+
+__device__ __forceinline__ float solow_shock_next(const SolowShockCoef &C, float (&zr)[8], float (&er)[8], float e_t) {
+    float ar = 0.f, ma = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) if (j >= 8 - C.P) ar += C.rz[j] * zr[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) if (j >= 8 - C.Q) ma += C.re[j] * er[j];
+    const float zn = (ar + ma) + e_t;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) { zr[j] = zr[j + 1]; er[j] = er[j + 1]; }
+    zr[7] = zn;
+    er[7] = e_t;
+    return zn;
+}
+
+// one rate's share of the step: ez = expf(z[-1]) is the same for every rate of the env.  Advances k, returns the reward.
+__device__ __forceinline__ float solow_capital_step(float ez, float delta, float rate, float &k) {
+    const float s = fmaxf(1e-3f, rate);
+    const float y = ez * powf(k, 0.33f);
+    k = (1.0f - delta) * k + s * y;
+    return logf((1.0f - s) * y + 1e-4f);
+}
+
 // es = N(0, sigma)^T: pair `pr` of the tape of `env` (fed_env.py:248); episode[env] was already advanced by the reset
 __device__ __forceinline__ void solow_tape_pair(const SolowParams &S, int env, int episode_after_reset, int pr) {
     uint32_t ep = (S.flags & GRL_F_RESEED_EACH_RESET) ? 0u : (uint32_t)(episode_after_reset - 1);

@@ -98,6 +98,39 @@ class _DeviceMonitor(object):
         w.add_scalar("eval/mean_total_reward", self.log["mean_total_reward"][-1], global_step)
         w.flush()
 
+    def _baseline_rates(self):
+        """The rates baseline() plays when given none: the reference's 20 (scripts/constant_solow.py:19)."""
+        from ...baselines import REFERENCE_RATES
+        return REFERENCE_RATES
+
+    def baseline(self, rates=None):
+        """The constant-savings baseline (goldsrl/baselines.py) on the monitor's own eval engine, so it plays exactly the seeded
+        episodes the policy is evaluated on: one kernel launch for every (env, rate) pair.  Keeps baseline_rate and
+        baseline_total_reward -- the best rate by the mean over the envs of the episode's total reward, the unit of
+        eval/mean_total_reward -- and the whole statistics in baseline_stats; leaves the engine reset.  Returns the two."""
+        from ... import _ffi
+        from ...baselines import ConstantSavingsBaseline
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_SOLOW:
+            raise ValueError("the constant-savings baseline exists for the Solow env only")
+        b = ConstantSavingsBaseline(rates=self._baseline_rates() if rates is None else rates, max_episode_steps=self.max_episode_steps,
+                                    engine=eng)
+        self.baseline_stats = b.run()
+        rate, total = b.best_total()
+        self.baseline_rate, self.baseline_total_reward = float(rate), float(total)
+        eng.reset()
+        return self.baseline_rate, self.baseline_total_reward
+
+    def write_baseline_scalars(self, global_step):
+        """eval/baseline_total_reward and eval/mean_total_reward_minus_baseline of the last evaluation (after baseline())"""
+        w = self.summary_writer
+        if w is None or getattr(self, "baseline_total_reward", None) is None:
+            return
+        w.add_scalar("eval/baseline_total_reward", self.baseline_total_reward, global_step)
+        if self.log["mean_total_reward"]:
+            w.add_scalar("eval/mean_total_reward_minus_baseline", self.log["mean_total_reward"][-1] - self.baseline_total_reward, global_step)
+        w.flush()
+
     def write_log(self, total_reward_log_file):
         """The reference's two keys from env 0 (policy_monitor.py:110-118), plus mean_total_reward, std_total_reward and n_envs."""
         with open(total_reward_log_file, "w") as f:
@@ -187,3 +220,7 @@ class GridPolicyMonitor(_DeviceMonitor):
             net = _ffi_discrete.DiscreteNet(eng, rnn_length=max_seq_length, scale=scale, num_choices=n_grid, grid_lb=lb, grid_ub=ub,
                                             max_samples=1)
         self._adopt(net, own, summary_writer, max_episode_steps)
+
+    def _baseline_rates(self):
+        """The agent's own grid: the best the agent could do blind to the state."""
+        return self.net.grid

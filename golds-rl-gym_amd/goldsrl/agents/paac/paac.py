@@ -61,6 +61,9 @@ class PAACLearner(ActorLearner):
             "Solow-%d-%d-finite-eval-v0" % (p, q), global_policy_net=self.network, state_processor=self.state_processor,
             summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), learner=self, n_envs=eval_envs, rnn_length=self.rnn_length, device_id=device_id,
             max_episode_steps=int(getattr(self, "max_episode_steps", 1024)), true_window=bool(getattr(self, "true_history", False)))
+        baseline = bool(getattr(self, "baseline", False))
+        if baseline:
+            logging.info("Constant-savings baseline on the eval envs: rate %.6g, mean total_reward %.6g", *self.policy_monitor.baseline())
         every_updates = int(getattr(self, "eval_updates", 0) or 0)
         every_seconds = float(getattr(self, "eval_every", 0.0) or 0.0)
         state = {"last_eval": time.time()}
@@ -72,6 +75,8 @@ class PAACLearner(ActorLearner):
                 due = every_seconds > 0 and time.time() - state["last_eval"] >= every_seconds
             if due:
                 self.policy_monitor.eval_once()
+                if baseline:
+                    self.policy_monitor.write_baseline_scalars(int(self.global_step))
                 state["last_eval"] = time.time()
         return between_updates
 

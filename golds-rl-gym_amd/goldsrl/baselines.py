@@ -1,0 +1,80 @@
+"""Baselines a trained policy is held against.
+
+ConstantSavingsBaseline is the reference's scripts/constant_solow.py on the device: the seeded eval episode of
+`Solow-p-q-finite-eval-v0` once per constant savings rate, every (env, rate) pair in one kernel launch (include/goldsrl_sweep.h).
+A policy that does not beat the best constant rate has learned nothing about the shocks.  The selection rules are pure functions of
+the statistics, so they run without a device."""
+import numpy as np
+
+REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
+
+
+def select_best(rates, mean, mx, mn, std):
+    """constant_solow.py:16-31 on one env's per-rate statistics, in the order given: s_max = 0, max_mean = 0, stats = None, and a
+    rate wins only with a strictly greater mean.  Returns (s_max, max_mean, (max, min, std))."""
+    s_max, max_mean, stats = 0, 0, None
+    for i, s in enumerate(rates):
+        if mean[i] > max_mean:
+            max_mean, s_max = mean[i], s
+            stats = (mx[i], mn[i], std[i])
+    return s_max, max_mean, stats
+
+
+def select_best_total(rates, total):
+    """The rate with the largest mean over the envs of total (n_rates, E) -- the first one on a tie -- and that mean: the unit of
+    eval/mean_total_reward."""
+    m = np.asarray(total, np.float64).mean(axis=1)
+    i = int(np.argmax(m))
+    return rates[i], float(m[i])
+
+
+class ConstantSavingsBaseline(object):
+    """rates: the constant savings rates, played in this order (the reference's 20 by default).  engine: a Solow engine to run on
+    (the caller keeps it) instead of building the eval registration's; run() resets it."""
+
+    def __init__(self, env="Solow-1-1-finite-eval-v0", n_envs=1, rates=REFERENCE_RATES, device_id=0, max_episode_steps=1024, engine=None):
+        self.rates = np.asarray(rates, np.float64).reshape(-1)
+        if self.rates.size < 1:
+            raise ValueError("at least one rate")
+        self.max_episode_steps = int(max_episode_steps)
+        self._own = engine is None
+        if engine is None:
+            from .agents.a3c.policy_monitor import make_eval_engine
+            if not env.startswith("Solow-"):
+                raise ValueError("the constant-savings baseline exists for the Solow env only (got %r)" % (env,))
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            engine = make_eval_engine(env, n_envs, device_id, self.max_episode_steps)
+        else:
+            from . import _ffi
+            if engine.kind != _ffi.ENV_SOLOW:
+                raise ValueError("the constant-savings baseline exists for the Solow env only")
+        self.eng = engine
+        self.stats = None
+
+    def run(self, trace_env=None):
+        """Reset the envs and play every (env, rate) pair; returns (and keeps) the statistics of _ffi_sweep.solow_sweep."""
+        from . import _ffi_sweep
+        self.eng.reset()
+        self.stats = _ffi_sweep.solow_sweep(self.eng, self.rates, self.max_episode_steps, trace_env)
+        return self.stats
+
+    def _stats(self):
+        if self.stats is None:
+            self.run()
+        return self.stats
+
+    def best(self, env=0):
+        """(s_max, max_mean, (max, min, std)) of env's episode by the reference's rule, the step rewards' statistics."""
+        s = self._stats()
+        s_max, max_mean, stats = select_best(self.rates, s["mean"][:, env], s["max"][:, env], s["min"][:, env], s["std"][:, env])
+        return float(s_max), float(max_mean), None if stats is None else tuple(float(v) for v in stats)
+
+    def best_total(self):
+        """(rate, mean over the envs of the episode's total reward) of the best rate."""
+        return select_best_total(self.rates, self._stats()["total"])
+
+    def close(self):
+        if self._own and self.eng is not None:
+            self.eng.close()
+        self.eng = None

@@ -41,12 +41,23 @@ def get_arg_parser():
                         "evaluation; 0: no evaluation")
     p.add_argument('--eval-updates', default=0, type=int, dest="eval_updates",
                    help="evaluate after every K-th update; 0: when --eval-every seconds have passed")
+    p.add_argument('--baseline', action='store_true',
+                   help="play the constant-savings baseline on the eval envs before the first update (one kernel launch) and write "
+                        "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline at every evaluation (needs --eval-envs)")
     p.add_argument('--true-history', action='store_true', dest="true_history",
                    help="train and evaluate the GRU over the true last --rnn_length states of each env's episode (what the reference's "
                         "monitor feeds) instead of the worker's copies of the current state (quirk Q11)")
     p.add_argument('--max_episode_steps', default=None, type=int, dest="max_episode_steps",
                    help="TimeLimit of the training and eval envs (the registered ids have 1024)")
     return p
+
+
+def parse_args(argv=None):
+    parser = get_arg_parser()
+    args = parser.parse_args(argv)
+    if args.baseline and args.eval_envs <= 0:
+        parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs N > 0")
+    return args
 
 
 def main(args):
@@ -61,4 +72,4 @@ def main(args):
 
 
 if __name__ == '__main__':
-    main(get_arg_parser().parse_args())
+    main(parse_args())

@@ -39,6 +39,9 @@ def get_arg_parser():
                    help="evaluate the greedy policy every N updates (0: never)")
     p.add_argument("--eval-envs", "--eval_envs", dest="eval_envs", type=int, default=0,
                    help="evaluate N seeded eval episodes on the device, one kernel launch per evaluation (0: one episode driven from the host)")
+    p.add_argument("--baseline", action="store_true",
+                   help="play the constant-savings baseline on the eval envs before the first update (one kernel launch) and write "
+                        "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline at every evaluation (needs --eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -84,8 +87,16 @@ class GreedyMonitor(object):
         self.net.close()
 
 
+def parse_args(argv=None):
+    parser = get_arg_parser()
+    args = parser.parse_args(argv)
+    if args.baseline and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs N > 0 (and --eval-every > 0)")
+    return args
+
+
 def main(argv=None):
-    args = get_arg_parser().parse_args(argv)
+    args = parse_args(argv)
     eng = _ffi.Engine(_ffi.ENV_SOLOW, args.envs, device_id=args.device, seed=args.seed, solow_p=P_ORDER, solow_q=Q_ORDER,
                       max_episode_steps=1024)
     eng.reset()
@@ -105,6 +116,8 @@ def main(argv=None):
                                 max_seq_length=MAX_SEQ_LENGTH, scale=SCALE, device_id=args.device)
     elif args.eval_every > 0:
         monitor = GreedyMonitor(args.device, log_file)
+    if args.baseline:
+        logging.info("Constant-savings baseline on the eval envs: rate %.6g, mean total_reward %.6g", *monitor.baseline())
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.t_max)
@@ -122,6 +135,8 @@ def main(argv=None):
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             if args.eval_envs > 0:
                 monitor.write_scalars(step)
+                if args.baseline:
+                    monitor.write_baseline_scalars(step)
                 monitor.write_log(log_file)
             else:
                 writer.add_scalar("eval/total_reward", total_reward, step)
