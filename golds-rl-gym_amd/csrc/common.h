@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -72,6 +73,17 @@ struct SolowSweepState {
     int n_rates, max_steps, trace_env;            // of the last sweep; n_rates == 0: none yet
 };
 
+// buffers of grl_swarm_replay (swarm_replay.hip): allocated on first use, grown when a later replay is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct SwarmReplayState {
+    uint8_t *actions;                             // (cap_act) bytes: the float64 or float32 action rows
+    int32_t *seq_len, *length;                    // (cap_seq) (cap_pairs)
+    double *rewards, *trace_x, *trace_xa;         // (cap_steps) (cap_trace,80,2) (cap_trace,10,2)
+    uint8_t *finished;                            // (cap_pairs)
+    size_t cap_act, cap_seq, cap_steps, cap_pairs, cap_trace;
+    int n_seq, max_steps, trace_env;              // of the last replay; n_seq == 0: none yet
+};
+
 }  // namespace grl
 
 struct grl_handle {
@@ -94,6 +106,7 @@ struct grl_handle {
     grl::TradeState tr;
     grl::TickerState tk;
     grl::SolowSweepState swp;
+    grl::SwarmReplayState rpl;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;
     // R6 episode bookkeeping (grl_episodes_*): nullptr until enabled
@@ -126,6 +139,20 @@ int hip_fail(grl_handle *h, hipError_t e, const char *what);
         hipError_t _e = (call);                                 \
         if (_e != hipSuccess) return grl::hip_fail(h, _e, #call); \
     } while (0)
+
+// (re)allocate *p to n elements and keep grl_handle::allocs right; the old contents are dropped
+template <typename T>
+static int grow(grl_handle *h, T **p, size_t n) {
+    if (*p) {
+        auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
+        if (it != h->allocs.end()) h->allocs.erase(it);
+        GRL_HIP(h, hipFree(*p));
+        *p = nullptr;
+    }
+    GRL_HIP(h, hipMalloc((void **)p, n * sizeof(T)));
+    h->allocs.push_back(*p);
+    return GRL_OK;
+}
 
 // api.hip: accounts the step just enqueued on the handle's stream (no-op until grl_episodes_enable)
 int episodes_launch_account(grl_handle *h, int env_base = 0, int count = -1);

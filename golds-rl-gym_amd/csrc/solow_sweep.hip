@@ -13,8 +13,6 @@
 // error counter is the sweep's own.
 #include <stdlib.h>
 
-#include <algorithm>
-
 #include "common.h"
 #include "rng.h"
 #include "flat_env_dev.h"
@@ -104,19 +102,6 @@ static int sweep_rpl() {
     const char *v = getenv("GRL_SWEEP_RPL");
     if (v && (v[0] == '1' || v[0] == '2' || v[0] == '4') && v[1] == 0) return v[0] - '0';
     return 1;
-}
-
-template <typename T>
-static int grow(grl_handle *h, T **p, size_t n) {
-    if (*p) {
-        auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
-        if (it != h->allocs.end()) h->allocs.erase(it);
-        GRL_HIP(h, hipFree(*p));
-        *p = nullptr;
-    }
-    GRL_HIP(h, hipMalloc((void **)p, n * sizeof(T)));
-    h->allocs.push_back(*p);
-    return GRL_OK;
 }
 
 static int sweep_reserve(grl_handle *h, size_t n_rates, size_t pairs, size_t trace) {

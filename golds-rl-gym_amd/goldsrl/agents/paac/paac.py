@@ -194,6 +194,8 @@ class GridPAACLearner(PAACLearner):
                                     summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), saver=None,
                                     network_conf=self.network.conf,
                                     learner=self)
+            if bool(getattr(self, "baseline", False)):
+                logging.info("Scripted baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.baseline())
         state = {"last_eval": last_eval}
 
         def between_updates(counter):

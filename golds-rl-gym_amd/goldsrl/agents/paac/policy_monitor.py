@@ -235,4 +235,22 @@ class SwarmPolicyMonitor(PolicyMonitor):
             self.best_score = total_reward
             self._save_actions(total_reward, [np.asarray(a).tolist() for a in taken])
         self._summaries(global_step, total_reward, episode_length, rewards)
+        if getattr(self, "baseline_total_reward", None) is not None and self.summary_writer is not None:
+            self.summary_writer.add_scalar("eval/baseline_total_reward", self.baseline_total_reward, global_step)
+            self.summary_writer.add_scalar("eval/total_reward_minus_baseline", total_reward - self.baseline_total_reward, global_step)
+            self.summary_writer.flush()
         return total_reward, episode_length, rewards
+
+    def baseline(self):
+        """The scripted do-nothing baseline (goldsrl/baselines.py:ScriptedSwarmBaseline) on the monitor's own eval env, so it plays
+        exactly the seeded episode the policy is evaluated on: the env is reset, both scripts run in one kernel launch, and the env
+        is reset again.  Keeps baseline_name and baseline_total_reward (every later eval_once writes eval/baseline_total_reward and
+        eval/total_reward_minus_baseline) and the whole statistics in baseline_stats.  Returns the two.  The reference has no
+        counterpart."""
+        from ...baselines import ScriptedSwarmBaseline
+        self.env.reset()
+        b = ScriptedSwarmBaseline(self.env._eng)
+        self.baseline_stats = b.run()
+        self.baseline_name, self.baseline_total_reward = b.best(0)
+        self.env.reset()
+        return self.baseline_name, self.baseline_total_reward

@@ -3,7 +3,10 @@
 ConstantSavingsBaseline is the reference's scripts/constant_solow.py on the device: the seeded eval episode of
 `Solow-p-q-finite-eval-v0` once per constant savings rate, every (env, rate) pair in one kernel launch (include/goldsrl_sweep.h).
 A policy that does not beat the best constant rate has learned nothing about the shocks.  The selection rules are pure functions of
-the statistics, so they run without a device."""
+the statistics, so they run without a device.
+
+ScriptedSwarmBaseline gives Swarm the same kind of yardstick: two do-nothing scripts played on a Swarm handle in one kernel launch
+(include/goldsrl_replay.h).  The reference has no counterpart of it."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -78,3 +81,41 @@ class ConstantSavingsBaseline(object):
         if self._own and self.eng is not None:
             self.eng.close()
         self.eng = None
+
+
+class ScriptedSwarmBaseline(object):
+    """Two scripted do-nothing policies on a Swarm engine, every (env, script) pair a whole episode in one kernel launch:
+      drift   the zero action: the agents go with the wind;
+      hold    (-WIND_SPEED, 0): the action cancels the wind and the agents stand still.
+    Each script is max_episode_steps float64 rows (default: the engine's TimeLimit).  A policy whose eval/total_reward does not
+    beat the better of the two has learned nothing about herding.  The reference has no such baseline (its README shows the GIF of
+    one episode and nothing to hold it against): this one is this build's own, like the gated evaluation.  run() plays from the
+    engine's CURRENT state (reset it first) and leaves that state as it was."""
+
+    NAMES = ("drift", "hold")
+
+    def __init__(self, engine, max_episode_steps=None):
+        from . import _ffi
+        if engine.kind != _ffi.ENV_SWARM:
+            raise ValueError("the scripted baseline exists for the Swarm env only")
+        self.eng = engine
+        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if self.max_episode_steps < 1:
+            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+        self.scripts = np.zeros((2, self.max_episode_steps, 10, 2), np.float64)
+        self.scripts[1, :, :, 0] = -1.0        # -SwarmEnv.WIND_SPEED
+        self.stats = None
+
+    def run(self):
+        """Play both scripts on every env; returns (and keeps) rewards (E, 2, T), totals, length and finished (E, 2)."""
+        from .replay import SwarmReplay
+        self.stats = SwarmReplay(self.eng).play(self.scripts)
+        return self.stats
+
+    def best(self, env=0):
+        """(name, total reward) of the better script on `env` -- the first one on a tie"""
+        if self.stats is None:
+            self.run()
+        totals = self.stats["totals"][env]
+        i = int(np.argmax(totals))
+        return self.NAMES[i], float(totals[i])

@@ -71,7 +71,11 @@ _REFERENCE_FLAGS = (
 )
 
 
-def get_arg_parser():
+_BASELINE_HELP = ("play the scripted do-nothing baseline (drift / hold) on the eval env before the first update (one kernel launch) and "
+                  "write eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs --eval-every > 0)")
+
+
+def get_arg_parser(baseline_help=_BASELINE_HELP):
     p = argparse.ArgumentParser(description="PAAC on Swarm-v0 with the conv policy (device engine)")
     for flags, dest, kind, default in _REFERENCE_FLAGS:
         p.add_argument(*flags, dest=dest, type=kind, default=default)
@@ -79,6 +83,7 @@ def get_arg_parser():
                    help="'reference' reproduces paac.py:331-338's (T, E*10) indexing (quirk Q4)")
     p.add_argument('--eval-every', default=30.0, type=float, dest="eval_every",
                    help="seconds between eval episodes on Swarm-eval-v0 (paac.py:277-282); 0 disables the monitor")
+    p.add_argument('--baseline', action='store_true', help=baseline_help)
     p.add_argument('--checkpoint-every', default=0, type=int, dest="checkpoint_every", help="updates between flat-weights checkpoints")
     p.add_argument('--checkpoint-path', default='checkpoint.npz', type=str, dest="checkpoint_path")
     p.add_argument('--resume', default=None, type=str, help="flat-weights checkpoint to start from")
@@ -88,6 +93,8 @@ def get_arg_parser():
 
 
 def main(args):
+    if args.baseline and not args.eval_every > 0:
+        raise SystemExit("--baseline plays the eval env of the monitor: it needs --eval-every > 0")
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = GridPAACLearner(network_creator, env_creator, args, SwarmRunner,
                               state_processor=None if args.emulator_counts > 4096 else SwarmStateProcessor(grid_size=args.height))
