@@ -314,18 +314,15 @@ __global__ __launch_bounds__(256, 1) void disc_backward_kernel(DArgs a) {
 struct grl_dnet : grl::A3cNet {
     grl_dnet_config cfg;
     grl::DOff off;
-    int D, K;                                     // processed observation = temporal row width (2), grid points
-    // host-sample staging
-    float *d_states, *d_win, *d_adv, *d_tgt, *d_wt, *d_probs, *d_vals;
+    int K;                                        // grid points; S0 = D = 2, the processed observation
+    // the head's host-sample staging, rollout buffers and evaluation trace
+    float *d_probs;
     int32_t *d_choice;
-    // rollout
-    float *ro_states, *ro_win, *ro_probs, *ro_val, *ro_rew, *ro_done, *ro_mask, *ro_wt, *ro_adv, *ro_tgt;
+    float *ro_probs, *ro_act;                     // ro_act (T,E): the grid value each env was stepped with
     int32_t *ro_choice;
-    float *ro_act;                                // (T,E) the grid value each env was stepped with
     float *ro_term_st, *ro_term_wn, *ro_term_val;
-    float *ro_boot, *boot_states, *boot_win, *term_obs;
-    // grl_dnet_eval: the step's actions, the trace of the first ev_trace steps
-    float *ev_act, *ev_states, *ev_actions, *ev_rew, *ev_done;
+    float *term_obs;
+    float *ev_act;                                // (E): the evaluation step's actions
     int32_t *ev_choice;
 };
 
@@ -357,33 +354,6 @@ static int train_device(grl_dnet *net, int n, const float *states, const float *
     return a3c_train_finish(net, blocks, net->off.p1w, 1.0, lr0, apply, stats_host);
 }
 
-static int ensure_rollout(grl_dnet *net, int T) {
-    if (T == net->T) return GRL_OK;
-    int rc = a3c_release(net, net->ro_allocs);
-    if (rc) return rc;
-    net->T = 0;
-    const size_t E = net->h->E, R = net->cfg.rnn_length, TE = (size_t)T * E, D = net->D, K = net->K;
-    A3cGrow Al{net, net->ro_allocs};
-    Al(&net->ro_states, TE * D); Al(&net->ro_win, TE * R * D); Al(&net->ro_probs, TE * K); Al(&net->ro_choice, TE); Al(&net->ro_act, TE);
-    Al(&net->ro_val, TE); Al(&net->ro_rew, TE); Al(&net->ro_done, TE); Al(&net->ro_mask, TE); Al(&net->ro_wt, TE); Al(&net->ro_adv, TE);
-    Al(&net->ro_tgt, TE); Al(&net->ro_term_val, TE); Al(&net->ro_term_st, TE * D); Al(&net->ro_term_wn, TE * R * D);
-    if (Al.rc == GRL_OK) net->T = T;
-    return Al.rc;
-}
-
-// the trace buffers of grl_dnet_eval for `steps` steps (they only grow)
-static int ensure_eval_trace(grl_dnet *net, int steps) {
-    if (steps <= net->ev_trace_cap) return GRL_OK;
-    int rc = a3c_release(net, net->ev_allocs);
-    if (rc) return rc;
-    net->ev_trace_cap = -1;
-    const size_t SE = (size_t)steps * net->h->E, D = net->D;
-    A3cGrow Al{net, net->ev_allocs};
-    Al(&net->ev_states, SE * D); Al(&net->ev_choice, SE); Al(&net->ev_actions, SE); Al(&net->ev_rew, SE); Al(&net->ev_done, SE);
-    if (Al.rc == GRL_OK) net->ev_trace_cap = steps;
-    return Al.rc;
-}
-
 }  // namespace grl
 
 using namespace grl;
@@ -402,44 +372,26 @@ int grl_dnet_config_default(grl_dnet_config *cfg) {
 }
 
 int grl_dnet_create(grl_handle *h, const grl_dnet_config *cfg, grl_dnet **out) {
-    if (!h || !cfg || !out) return GRL_E_INVALID;
-    *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(grl_dnet_config)) return fail(h, GRL_E_INVALID, "grl_dnet_create: config size mismatch");
-    if (h->cfg.env_kind != GRL_ENV_SOLOW) return fail(h, GRL_E_INVALID, "grl_dnet_create: the savings-grid agent needs a Solow handle");
-    if (cfg->rnn_length < 1 || cfg->rnn_length > MAXR || cfg->max_samples < 1 || cfg->lr_decay_steps < 1 || !(cfg->scale != 0.f) ||
-        !(cfg->gae_lambda > 0.f && cfg->gae_lambda <= 1.f))
-        return fail(h, GRL_E_INVALID, "grl_dnet_create: config out of range (rnn_length 1..20)");
-    if (cfg->num_choices < 2 || cfg->num_choices > DKMAX || !(cfg->grid_lb < cfg->grid_ub))
-        return fail(h, GRL_E_INVALID, "grl_dnet_create: num_choices 2..64, grid_lb < grid_ub");
-    if (cfg->always_bootstrap != 1) return fail(h, GRL_E_INVALID, "grl_dnet_create: a Solow handle needs always_bootstrap = 1");
-    hipSetDevice(h->cfg.device_id);
-    grl_dnet *n = new grl_dnet();
-    n->h = h; n->cfg = *cfg;
-    n->D = DD; n->K = cfg->num_choices;
-    n->off = discrete_offsets(n->K);
-    const size_t ms = cfg->max_samples, R = cfg->rnn_length, E = h->E, D = n->D, K = n->K;
-    int rc = a3c_create_common(n, n->off.total, E);
-    A3cGrow Al{n, n->allocs, rc};
-    Al(&n->d_states, ms * D); Al(&n->d_win, ms * R * D); Al(&n->d_choice, ms); Al(&n->d_adv, ms); Al(&n->d_tgt, ms); Al(&n->d_wt, ms);
-    Al(&n->d_probs, ms * K); Al(&n->d_vals, ms);
-    Al(&n->win, E * R * D); Al(&n->ro_boot, E); Al(&n->boot_states, E * D); Al(&n->boot_win, E * R * D);
-    Al(&n->term_obs, E * D); Al(&n->ev_act, E);
-    rc = Al.rc;
-    if (rc == GRL_OK) {
-        hipError_t e = hipGetLastError();
-        const void *kernels[3] = {(const void *)disc_forward_kernel, (const void *)disc_backward_kernel, (const void *)disc_eval_kernel};
-        for (const void *k : kernels)
-            if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)A3C_LDS);
-        if (e != hipSuccess) rc = a3c_fail(n, GRL_E_HIP, std::string("grl_dnet_create: ") + hipGetErrorString(e));
-    }
-    if (rc != GRL_OK) {
-        fail(h, rc, "grl_dnet_create: " + n->err);
-        grl_dnet_destroy(n);
-        return rc;
-    }
-    hipStreamSynchronize(h->stream);
-    *out = n;
-    return GRL_OK;
+    return a3c_create(
+        "grl_dnet_create", h, cfg, out,
+        [&](const char *range) -> const char * {
+            if (h->cfg.env_kind != GRL_ENV_SOLOW) return "the savings-grid agent needs a Solow handle";
+            if (range) return range;
+            if (cfg->num_choices < 2 || cfg->num_choices > DKMAX || !(cfg->grid_lb < cfg->grid_ub)) return "num_choices 2..64, grid_lb < grid_ub";
+            return cfg->always_bootstrap != 1 ? "a Solow handle needs always_bootstrap = 1" : nullptr;
+        },
+        [&](grl_dnet *n, A3cGrow &Al) {
+            n->S0 = n->D = DD; n->K = cfg->num_choices;
+            n->off = discrete_offsets(n->K);
+            const size_t ms = cfg->max_samples, E = h->E, K = n->K, W = (size_t)cfg->rnn_length * DD;
+            n->ro_bufs = {a3c_buf("probs", &n->ro_probs, K), a3c_buf("choices", &n->ro_choice, 1), a3c_buf("actions", &n->ro_act, 1),
+                          a3c_buf("term_values", &n->ro_term_val, 1), a3c_buf("term_states", &n->ro_term_st, DD),
+                          a3c_buf("term_windows", &n->ro_term_wn, W)};
+            n->ev_bufs = {a3c_buf("choices", &n->ev_choice, 1), a3c_buf("actions", &n->ev_actions, 1)};
+            Al(&n->d_choice, ms); Al(&n->d_probs, ms * K); Al(&n->term_obs, E * DD); Al(&n->ev_act, E);
+            return (size_t)n->off.total;
+        },
+        {(const void *)disc_forward_kernel, (const void *)disc_backward_kernel, (const void *)disc_eval_kernel});
 }
 
 int grl_dnet_destroy(grl_dnet *n) { return a3c_destroy(n); }
@@ -455,38 +407,25 @@ int grl_dnet_set_action_counter(grl_dnet *n, uint64_t v) { return a3c_set_action
 int grl_dnet_set_greedy(grl_dnet *net, int32_t on) { return a3c_set_greedy(net, on); }
 
 int grl_dnet_predict(grl_dnet *net, int32_t n, const float *states, const float *windows, float *probs, float *values) {
-    if (!net || n <= 0 || !states || !windows) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_predict: bad argument");
-    if (n > net->cfg.max_samples) return a3c_fail(net, GRL_E_SIZE, "grl_dnet_predict: n exceeds max_samples");
-    hipSetDevice(net->h->cfg.device_id);
-    hipStream_t st = net->h->stream;
-    const size_t R = net->cfg.rnn_length, D = net->D, K = net->K;
-    A3C_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * D * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_win, windows, (size_t)n * R * D * 4, hipMemcpyHostToDevice, st));
+    int rc = a3c_samples_check(net, "grl_dnet_predict", n, states && windows);
+    if (rc || (rc = a3c_stage(net, n, states, windows))) return rc;
     DArgs a = dargs(net, n, net->d_states, net->d_win);
     a.probs = net->d_probs; a.vals = net->d_vals;
-    int rc = launch_fwd(net, a);
-    if (rc) return rc;
-    A3C_HIP(net, hipStreamSynchronize(st));
-    if (probs) A3C_HIP(net, hipMemcpy(probs, net->d_probs, (size_t)n * K * 4, hipMemcpyDeviceToHost));
-    if (values) A3C_HIP(net, hipMemcpy(values, net->d_vals, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    if ((rc = launch_fwd(net, a))) return rc;
+    A3C_HIP(net, hipStreamSynchronize(net->h->stream));
+    if ((rc = a3c_get(net, probs, net->d_probs, (size_t)n * net->K))) return rc;
+    return a3c_get(net, values, net->d_vals, n);
 }
 
 int grl_dnet_train(grl_dnet *net, int32_t n, const float *states, const float *windows, const int32_t *choices, const float *adv,
                    const float *targets, const float *weights, float grad_mult, float lr0, int32_t apply_update, float *stats_host) {
-    if (!net || n <= 0 || !states || !windows || !choices || !adv || !targets) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_train: bad argument");
-    if (n > net->cfg.max_samples) return a3c_fail(net, GRL_E_SIZE, "grl_dnet_train: n exceeds max_samples");
+    int rc = a3c_samples_check(net, "grl_dnet_train", n, states && windows && choices && adv && targets);
+    if (rc) return rc;
     for (int32_t i = 0; i < n; ++i)
         if (choices[i] < 0 || choices[i] >= net->K) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_train: a choice outside [0, num_choices)");
-    hipSetDevice(net->h->cfg.device_id);
-    hipStream_t st = net->h->stream;
-    const size_t R = net->cfg.rnn_length, D = net->D;
-    A3C_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * D * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_win, windows, (size_t)n * R * D * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_choice, choices, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_adv, adv, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_tgt, targets, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (weights) A3C_HIP(net, hipMemcpyAsync(net->d_wt, weights, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if ((rc = a3c_stage(net, n, states, windows)) || (rc = a3c_put(net, net->d_choice, choices, n)) ||
+        (rc = a3c_stage_targets(net, n, adv, targets, weights)))
+        return rc;
     return train_device(net, n, net->d_states, net->d_win, net->d_choice, net->d_adv, net->d_tgt, weights ? net->d_wt : nullptr, grad_mult, lr0,
                         apply_update, stats_host);
 }
@@ -495,7 +434,7 @@ int grl_dnet_rollout(grl_dnet *net, int32_t T) {
     if (!net || T < 1) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_rollout: T >= 1");
     grl_handle *h = net->h;
     hipSetDevice(h->cfg.device_id);
-    int rc = ensure_rollout(net, T);
+    int rc = a3c_ensure_rollout(net, T);
     if (rc) return rc;
     const size_t K = net->K;
     return a3c_rollout_run(
@@ -509,58 +448,28 @@ int grl_dnet_rollout(grl_dnet *net, int32_t T) {
 }
 
 int grl_dnet_eval(grl_dnet *net, int32_t max_steps, int32_t trace_steps) {
-    if (!net) return GRL_E_INVALID;
-    if (max_steps < 1 || trace_steps < 0) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_eval: max_steps >= 1, trace_steps >= 0");
-    grl_handle *h = net->h;
-    hipSetDevice(h->cfg.device_id);
-    if (trace_steps > max_steps) trace_steps = max_steps;
-    int rc = ensure_eval_trace(net, trace_steps);
+    int rc = a3c_eval_begin(net, "grl_dnet_eval", max_steps, &trace_steps);
     if (rc) return rc;
+    grl_handle *h = net->h;
     const int E = h->E;
     DEvalArgs v{};
     v.a = dargs(net, E, h->so.obs, net->win);
-    v.win = net->win; v.act = net->ev_act; v.max_steps = max_steps; v.trace_steps = trace_steps;
-    v.total = net->ev_total; v.length = net->ev_len; v.finished = net->ev_fin;
-    v.tr_states = net->ev_states; v.tr_choice = net->ev_choice; v.tr_act = net->ev_actions; v.tr_rew = net->ev_rew; v.tr_done = net->ev_done;
+    a3c_eval_args(net, v, max_steps, trace_steps);
+    v.act = net->ev_act; v.tr_choice = net->ev_choice; v.tr_act = net->ev_actions;
     hipLaunchKernelGGL(disc_eval_kernel, dim3((E + 63) / 64), dim3(256), A3C_LDS, h->stream, v, solow_params(h));
-    if ((rc = a3c_eval_finish(net, trace_steps))) return rc;
-    rc = solow_launch_reset(h, h->done_list, h->done_count, E, true);      // with the tape draw
-    if (rc) return a3c_fail(net, rc, h->err);
-    return GRL_OK;
+    return a3c_eval_finish(net, trace_steps, [&] { return solow_launch_reset(h, h->done_list, h->done_count, E, true); });      // with the tape draw
 }
 
-int grl_dnet_read_eval(grl_dnet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_read_eval: bad argument");
-    size_t SE;
-    int rc = a3c_eval_rows(net, "grl_dnet_read_eval", &SE);
-    if (rc) return rc;
-    const size_t E = net->h->E, D = net->D;
-    const A3cBuf tab[] = {
-        {"total_reward", net->ev_total, E * 8}, {"length", net->ev_len, E * 4}, {"finished", net->ev_fin, E},
-        {"states", net->ev_states, SE * D * 4}, {"choices", net->ev_choice, SE * 4}, {"actions", net->ev_actions, SE * 4},
-        {"rewards", net->ev_rew, SE * 4}, {"dones", net->ev_done, SE * 4}};
-    return a3c_read(net, "grl_dnet_read_eval", tab, "", which, host, bytes);
-}
+int grl_dnet_read_eval(grl_dnet *net, const char *which, void *host, size_t bytes) { return a3c_read_eval(net, "grl_dnet_read_eval", which, host, bytes); }
 
 int grl_dnet_train_rollout(grl_dnet *net, float lr0, float *stats_host) {
-    if (!net) return GRL_E_INVALID;
-    if (!net->T) return a3c_fail(net, GRL_E_STATE, "grl_dnet_train_rollout: no rollout yet");
-    hipSetDevice(net->h->cfg.device_id);
-    const int E = net->h->E, n = net->T * E;
-    return train_device(net, n, net->ro_states, net->ro_win, net->ro_choice, net->ro_adv, net->ro_tgt, net->ro_wt, 1.0f / (float)E, lr0, 1,
-                        stats_host);
+    return a3c_train_rollout(net, "grl_dnet_train_rollout", [&](int n, float mult) {
+        return train_device(net, n, net->ro_states, net->ro_win, net->ro_choice, net->ro_adv, net->ro_tgt, net->ro_wt, mult, lr0, 1, stats_host);
+    });
 }
 
 int grl_dnet_read_rollout(grl_dnet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return a3c_fail(net, GRL_E_INVALID, "grl_dnet_read_rollout: bad argument");
-    if (!net->T) return a3c_fail(net, GRL_E_STATE, "grl_dnet_read_rollout: no rollout yet");
-    const size_t TE = (size_t)net->T * net->h->E * 4, R = net->cfg.rnn_length, D = net->D, K = net->K;
-    const A3cBuf tab[] = {
-        {"states", net->ro_states, TE * D}, {"windows", net->ro_win, TE * R * D}, {"probs", net->ro_probs, TE * K}, {"choices", net->ro_choice, TE},
-        {"actions", net->ro_act, TE}, {"values", net->ro_val, TE}, {"rewards", net->ro_rew, TE}, {"dones", net->ro_done, TE},
-        {"weights", net->ro_wt, TE}, {"adv", net->ro_adv, TE}, {"targets", net->ro_tgt, TE}, {"term_values", net->ro_term_val, TE},
-        {"term_states", net->ro_term_st, TE * D}, {"term_windows", net->ro_term_wn, TE * R * D}, {"boot", net->ro_boot, (size_t)net->h->E * 4}};
-    return a3c_read(net, "grl_dnet_read_rollout", tab, "", which, host, bytes);
+    return a3c_read_rollout(net, "grl_dnet_read_rollout", "", which, host, bytes);
 }
 
 }  // extern "C"

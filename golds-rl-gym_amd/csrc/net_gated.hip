@@ -314,19 +314,19 @@ __global__ void gated_boot_mask_kernel(float *__restrict__ boot, const float *__
 struct grl_gnet : grl::A3cNet {
     grl_gnet_config cfg;
     grl::GOff off;
-    // host-sample staging
-    float *d_states, *d_win, *d_raw, *d_adv, *d_tgt, *d_wt, *d_probs, *d_mu, *d_sigma, *d_vals;
+    // the heads' host-sample staging, rollout buffers and evaluation trace
+    float *d_raw, *d_probs, *d_mu, *d_sigma;
     int32_t *d_choices;
-    // rollout
-    float *ro_states, *ro_win, *ro_raw, *ro_probs, *ro_mu, *ro_sigma, *ro_val, *ro_rew, *ro_done, *ro_mask, *ro_wt, *ro_adv, *ro_tgt;
-    float *ro_boot, *ro_act, *boot_states, *boot_win;      // ro_act (T,E,4): the action each env was stepped with
+    float *ro_raw, *ro_probs, *ro_mu, *ro_sigma, *ro_act;      // ro_act (T,E,4): the action each env was stepped with
     int32_t *ro_choices;
-    // grl_gnet_eval: the trace of the first ev_trace steps
-    float *ev_states, *ev_probs, *ev_mu, *ev_actions, *ev_rew, *ev_done;
+    float *ev_probs, *ev_mu;
     int32_t *ev_choices;
 };
 
 namespace grl {
+
+// per sample: assets (a choice and a raw draw each), (asset, choice) entries of probs / mu / sigma, the env's action
+constexpr size_t GA = 2, GAC = 6, GACT = 4;
 
 static GArgs gargs(grl_gnet *net, int n, const float *states, const float *win) {
     GArgs a{};
@@ -353,33 +353,8 @@ static int train_device(grl_gnet *net, int n, const float *states, const float *
     return a3c_train_finish(net, blocks, net->off.c1w, 2.0, lr0, apply, stats_host);
 }
 
-static int ensure_rollout(grl_gnet *net, int T) {
-    if (T == net->T) return GRL_OK;
-    int rc = a3c_release(net, net->ro_allocs);
-    if (rc) return rc;
-    net->T = 0;
-    const size_t E = net->h->E, R = net->cfg.rnn_length, TE = (size_t)T * E;
-    A3cGrow Al{net, net->ro_allocs};
-    Al(&net->ro_states, TE * GS0); Al(&net->ro_win, TE * R * GD); Al(&net->ro_raw, TE * 2); Al(&net->ro_probs, TE * 6);
-    Al(&net->ro_mu, TE * 6); Al(&net->ro_sigma, TE * 6); Al(&net->ro_val, TE); Al(&net->ro_rew, TE); Al(&net->ro_done, TE);
-    Al(&net->ro_mask, TE); Al(&net->ro_wt, TE); Al(&net->ro_adv, TE); Al(&net->ro_tgt, TE); Al(&net->ro_act, TE * 4);
-    Al(&net->ro_choices, TE * 2);
-    if (Al.rc == GRL_OK) net->T = T;
-    return Al.rc;
-}
-
-// the trace buffers of grl_gnet_eval for `steps` steps (they only grow)
-static int ensure_eval_trace(grl_gnet *net, int steps) {
-    if (steps <= net->ev_trace_cap) return GRL_OK;
-    int rc = a3c_release(net, net->ev_allocs);
-    if (rc) return rc;
-    net->ev_trace_cap = -1;
-    const size_t SE = (size_t)steps * net->h->E;
-    A3cGrow Al{net, net->ev_allocs};
-    Al(&net->ev_states, SE * GS0); Al(&net->ev_probs, SE * 6); Al(&net->ev_mu, SE * 6); Al(&net->ev_actions, SE * 4); Al(&net->ev_rew, SE);
-    Al(&net->ev_done, SE); Al(&net->ev_choices, SE * 2);
-    if (Al.rc == GRL_OK) net->ev_trace_cap = steps;
-    return Al.rc;
+static int no_table(grl_gnet *net) {
+    return a3c_fail(net, GRL_E_STATE, "Ticker handle has no price table yet: call grl_ticker_set_table first");
 }
 
 }  // namespace grl
@@ -399,37 +374,20 @@ int grl_gnet_config_default(grl_gnet_config *cfg) {
 }
 
 int grl_gnet_create(grl_handle *h, const grl_gnet_config *cfg, grl_gnet **out) {
-    if (!h || !cfg || !out) return GRL_E_INVALID;
-    *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(grl_gnet_config)) return fail(h, GRL_E_INVALID, "grl_gnet_create: config size mismatch");
-    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_gnet_create: the gated trader needs a Ticker handle");
-    if (cfg->rnn_length < 1 || cfg->rnn_length > MAXR || cfg->max_samples < 1 || cfg->lr_decay_steps < 1 || !(cfg->scale != 0.f) ||
-        !(cfg->gae_lambda > 0.f && cfg->gae_lambda <= 1.f))
-        return fail(h, GRL_E_INVALID, "grl_gnet_create: config out of range (rnn_length 1..20)");
-    hipSetDevice(h->cfg.device_id);
-    grl_gnet *n = new grl_gnet();
-    n->h = h; n->cfg = *cfg; n->off = gated_offsets();
-    const size_t ms = cfg->max_samples, R = cfg->rnn_length, E = h->E;
-    int rc = a3c_create_common(n, n->off.total, E);
-    A3cGrow Al{n, n->allocs, rc};
-    Al(&n->d_states, ms * GS0); Al(&n->d_win, ms * R * GD); Al(&n->d_raw, ms * 2); Al(&n->d_adv, ms); Al(&n->d_tgt, ms); Al(&n->d_wt, ms);
-    Al(&n->d_probs, ms * 6); Al(&n->d_mu, ms * 6); Al(&n->d_sigma, ms * 6); Al(&n->d_vals, ms); Al(&n->d_choices, ms * 2);
-    Al(&n->win, E * R * GD); Al(&n->ro_boot, E); Al(&n->boot_states, E * GS0); Al(&n->boot_win, E * R * GD);
-    rc = Al.rc;
-    if (rc == GRL_OK) {
-        hipError_t e = hipGetLastError();
-        for (const void *k : {(const void *)gated_forward_kernel, (const void *)gated_backward_kernel, (const void *)gated_eval_kernel})
-            if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)A3C_LDS);
-        if (e != hipSuccess) rc = a3c_fail(n, GRL_E_HIP, std::string("grl_gnet_create: ") + hipGetErrorString(e));
-    }
-    if (rc != GRL_OK) {
-        fail(h, rc, "grl_gnet_create: " + n->err);
-        grl_gnet_destroy(n);
-        return rc;
-    }
-    hipStreamSynchronize(h->stream);
-    *out = n;
-    return GRL_OK;
+    return a3c_create(
+        "grl_gnet_create", h, cfg, out,
+        [&](const char *range) { return h->cfg.env_kind != GRL_ENV_TICKER ? "the gated trader needs a Ticker handle" : range; },
+        [&](grl_gnet *n, A3cGrow &Al) {
+            n->S0 = GS0; n->D = GD; n->toff = GTOFF; n->off = gated_offsets();
+            n->ro_bufs = {a3c_buf("raw", &n->ro_raw, GA), a3c_buf("probs", &n->ro_probs, GAC), a3c_buf("mu", &n->ro_mu, GAC),
+                          a3c_buf("sigma", &n->ro_sigma, GAC), a3c_buf("choices", &n->ro_choices, GA), a3c_buf("actions", &n->ro_act, GACT)};
+            n->ev_bufs = {a3c_buf("probs", &n->ev_probs, GAC), a3c_buf("mu", &n->ev_mu, GAC), a3c_buf("choices", &n->ev_choices, GA),
+                          a3c_buf("actions", &n->ev_actions, GACT)};
+            const size_t ms = cfg->max_samples;
+            Al(&n->d_raw, ms * GA); Al(&n->d_choices, ms * GA); Al(&n->d_probs, ms * GAC); Al(&n->d_mu, ms * GAC); Al(&n->d_sigma, ms * GAC);
+            return (size_t)n->off.total;
+        },
+        {(const void *)gated_forward_kernel, (const void *)gated_backward_kernel, (const void *)gated_eval_kernel});
 }
 
 int grl_gnet_destroy(grl_gnet *n) { return a3c_destroy(n); }
@@ -445,42 +403,28 @@ int grl_gnet_set_action_counter(grl_gnet *n, uint64_t v) { return a3c_set_action
 int grl_gnet_set_greedy(grl_gnet *net, int32_t on) { return a3c_set_greedy(net, on); }
 
 int grl_gnet_predict(grl_gnet *net, int32_t n, const float *states, const float *windows, float *probs, float *mu, float *sigma, float *values) {
-    if (!net || n <= 0 || !states || !windows) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_predict: bad argument");
-    if (n > net->cfg.max_samples) return a3c_fail(net, GRL_E_SIZE, "grl_gnet_predict: n exceeds max_samples");
-    hipSetDevice(net->h->cfg.device_id);
-    hipStream_t st = net->h->stream;
-    const size_t R = net->cfg.rnn_length;
-    A3C_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * GS0 * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_win, windows, (size_t)n * R * GD * 4, hipMemcpyHostToDevice, st));
+    int rc = a3c_samples_check(net, "grl_gnet_predict", n, states && windows);
+    if (rc || (rc = a3c_stage(net, n, states, windows))) return rc;
     GArgs a = gargs(net, n, net->d_states, net->d_win);
     a.probs = net->d_probs; a.mu = net->d_mu; a.sigma = net->d_sigma; a.vals = net->d_vals;
-    int rc = launch_fwd(net, a);
-    if (rc) return rc;
-    A3C_HIP(net, hipStreamSynchronize(st));
-    if (probs) A3C_HIP(net, hipMemcpy(probs, net->d_probs, (size_t)n * 24, hipMemcpyDeviceToHost));
-    if (mu) A3C_HIP(net, hipMemcpy(mu, net->d_mu, (size_t)n * 24, hipMemcpyDeviceToHost));
-    if (sigma) A3C_HIP(net, hipMemcpy(sigma, net->d_sigma, (size_t)n * 24, hipMemcpyDeviceToHost));
-    if (values) A3C_HIP(net, hipMemcpy(values, net->d_vals, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    if ((rc = launch_fwd(net, a))) return rc;
+    A3C_HIP(net, hipStreamSynchronize(net->h->stream));
+    if ((rc = a3c_get(net, probs, net->d_probs, n * GAC)) || (rc = a3c_get(net, mu, net->d_mu, n * GAC)) ||
+        (rc = a3c_get(net, sigma, net->d_sigma, n * GAC)))
+        return rc;
+    return a3c_get(net, values, net->d_vals, n);
 }
 
 int grl_gnet_train(grl_gnet *net, int32_t n, const float *states, const float *windows, const int32_t *choices, const float *raw,
                    const float *adv, const float *targets, const float *weights, float grad_mult, float lr0, int32_t apply_update,
                    float *stats_host) {
-    if (!net || n <= 0 || !states || !windows || !choices || !raw || !adv || !targets) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_train: bad argument");
-    if (n > net->cfg.max_samples) return a3c_fail(net, GRL_E_SIZE, "grl_gnet_train: n exceeds max_samples");
-    for (int i = 0; i < 2 * n; ++i)
+    int rc = a3c_samples_check(net, "grl_gnet_train", n, states && windows && choices && raw && adv && targets);
+    if (rc) return rc;
+    for (size_t i = 0; i < n * GA; ++i)
         if (choices[i] < 0 || choices[i] > 2) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_train: choices must be 0, 1 or 2");
-    hipSetDevice(net->h->cfg.device_id);
-    hipStream_t st = net->h->stream;
-    const size_t R = net->cfg.rnn_length;
-    A3C_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * GS0 * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_win, windows, (size_t)n * R * GD * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_choices, choices, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_raw, raw, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_adv, adv, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_tgt, targets, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (weights) A3C_HIP(net, hipMemcpyAsync(net->d_wt, weights, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if ((rc = a3c_stage(net, n, states, windows)) || (rc = a3c_put(net, net->d_choices, choices, n * GA)) ||
+        (rc = a3c_put(net, net->d_raw, raw, n * GA)) || (rc = a3c_stage_targets(net, n, adv, targets, weights)))
+        return rc;
     return train_device(net, n, net->d_states, net->d_win, net->d_choices, net->d_raw, net->d_adv, net->d_tgt, weights ? net->d_wt : nullptr,
                         grad_mult, lr0, apply_update, stats_host);
 }
@@ -489,38 +433,23 @@ int grl_gnet_rollout(grl_gnet *net, int32_t T) {
     if (!net || T < 1) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_rollout: T >= 1");
     grl_handle *h = net->h;
     hipSetDevice(h->cfg.device_id);
-    if (!h->tk.table) return a3c_fail(net, GRL_E_STATE, "Ticker handle has no price table yet: call grl_ticker_set_table first");
-    int rc = ensure_rollout(net, T);
+    if (!h->tk.table) return no_table(net);
+    int rc = a3c_ensure_rollout(net, T);
     if (rc) return rc;
-    hipStream_t st = h->stream;
-    const int E = h->E, R = net->cfg.rnn_length, eb = (E + 255) / 256;
-    float *const none = nullptr;
-    hipLaunchKernelGGL((a3c_sync_kernel<GS0_t, GD_t, GTOFF_t>), dim3(eb), dim3(256), 0, st, h->elapsed, h->tk.obs, net->win, net->kstep, E, R, GS0_t{},
-                       GD_t{}, GTOFF_t{}, net->win_init ? 0 : 1);
-    net->win_init = 1;
-    for (int t = 0; t < T; ++t) {
-        const size_t o = (size_t)t * E;
-        hipLaunchKernelGGL((a3c_record_kernel<GS0_t, GD_t>), dim3(eb), dim3(256), 0, st, h->tk.obs, net->win, net->kstep, E, R, GS0_t{}, GD_t{},
-                           net->ro_states + o * GS0, net->ro_win + o * R * GD, net->ro_wt + o);
-        GArgs a = gargs(net, E, net->ro_states + o * GS0, net->ro_win + o * R * GD);
-        a.probs = net->ro_probs + o * 6; a.mu = net->ro_mu + o * 6; a.sigma = net->ro_sigma + o * 6; a.vals = net->ro_val + o;
-        a.act = net->ro_act + o * 4; a.choice_out = net->ro_choices + o * 2; a.raw_out = net->ro_raw + o * 2;
-        a.seed = h->cfg.seed; a.env_off = (uint32_t)h->cfg.env_id_offset; a.counter = (uint32_t)(net->act_counter + (uint64_t)t);
-        a.greedy = net->greedy;
-        if ((rc = launch_fwd(net, a))) return rc;
-        if ((rc = ticker_launch_step(h, net->ro_act + o * 4))) return a3c_fail(net, rc, h->err);
-        if ((rc = episodes_launch_account(h))) return a3c_fail(net, rc, h->err);
-        hipLaunchKernelGGL((a3c_post_kernel<GS0_t, GD_t, GTOFF_t>), dim3(eb), dim3(256), 0, st, h->reward, h->done, h->tk.obs, (const float *)nullptr,
-                           net->win, net->kstep, E, R, GS0_t{}, GD_t{}, GTOFF_t{}, net->ro_rew + o, net->ro_done + o, net->ro_mask + o, none, none);
-    }
-    if (!net->greedy) net->act_counter += (uint64_t)T;      // a greedy rollout draws nothing
-    // bootstrap: V of the window after the last step, 0 behind a finished episode; then the worker's GAE (worker.py:241-294)
-    hipLaunchKernelGGL((a3c_record_kernel<GS0_t, GD_t>), dim3(eb), dim3(256), 0, st, h->tk.obs, net->win, net->kstep, E, R, GS0_t{}, GD_t{},
-                       net->boot_states, net->boot_win, none);
-    GArgs b = gargs(net, E, net->boot_states, net->boot_win);
-    b.vals = net->ro_boot;
-    if ((rc = launch_fwd(net, b))) return rc;
-    hipLaunchKernelGGL(gated_boot_mask_kernel, dim3(eb), dim3(256), 0, st, net->ro_boot, net->ro_mask + (size_t)(T - 1) * E, E);
+    rc = a3c_rollout_steps(
+        net, T, net->cfg.rnn_length, h->tk.obs, GS0_t{}, GD_t{}, GTOFF_t{}, nullptr, nullptr, nullptr,
+        [&](int n, const float *states, const float *win) { return gargs(net, n, states, win); },
+        [&](GArgs &a, size_t o, int t) {
+            a.probs = net->ro_probs + o * GAC; a.mu = net->ro_mu + o * GAC; a.sigma = net->ro_sigma + o * GAC;
+            a.act = net->ro_act + o * GACT; a.choice_out = net->ro_choices + o * GA; a.raw_out = net->ro_raw + o * GA;
+            a.seed = h->cfg.seed; a.env_off = (uint32_t)h->cfg.env_id_offset; a.counter = (uint32_t)(net->act_counter + (uint64_t)t);
+            a.greedy = net->greedy;
+        },
+        [&](const GArgs &a) { return launch_fwd(net, a); }, [&](size_t o) { return ticker_launch_step(h, net->ro_act + o * GACT); });
+    if (rc) return rc;
+    // the bootstrap is 0 behind a finished episode; then the worker's GAE (worker.py:241-294)
+    const int E = h->E;
+    hipLaunchKernelGGL(gated_boot_mask_kernel, dim3((E + 255) / 256), dim3(256), 0, h->stream, net->ro_boot, net->ro_mask + (size_t)(T - 1) * E, E);
     if ((rc = launch_returns(h, net->ro_rew, net->ro_val, net->ro_mask, net->ro_boot, T, E, net->cfg.gamma, net->cfg.gae_lambda, net->cfg.scale,
                              0.f, 0.f, net->ro_tgt, net->ro_adv)))
         return a3c_fail(net, rc, h->err);
@@ -529,62 +458,34 @@ int grl_gnet_rollout(grl_gnet *net, int32_t T) {
 }
 
 int grl_gnet_eval(grl_gnet *net, int32_t max_steps, int32_t trace_steps) {
-    if (!net) return GRL_E_INVALID;
-    if (max_steps < 1 || trace_steps < 0) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_eval: max_steps >= 1, trace_steps >= 0");
-    grl_handle *h = net->h;
-    hipSetDevice(h->cfg.device_id);
-    if (!h->tk.table) return a3c_fail(net, GRL_E_STATE, "Ticker handle has no price table yet: call grl_ticker_set_table first");
-    if (h->cfg.max_episode_steps < 1)
-        return a3c_fail(net, GRL_E_STATE, "grl_gnet_eval: the handle has no max_episode_steps, an episode could run past its 1024-row price window");
-    if (trace_steps > max_steps) trace_steps = max_steps;
-    int rc = ensure_eval_trace(net, trace_steps);
+    int rc = a3c_eval_begin(net, "grl_gnet_eval", max_steps, &trace_steps, [&] {
+        if (!net->h->tk.table) return no_table(net);
+        if (net->h->cfg.max_episode_steps < 1)
+            return a3c_fail(net, GRL_E_STATE, "grl_gnet_eval: the handle has no max_episode_steps, an episode could run past its 1024-row price window");
+        return (int)GRL_OK;
+    });
     if (rc) return rc;
+    grl_handle *h = net->h;
     const int E = h->E;
     GEvalArgs v{};
     v.a = gargs(net, E, h->tk.obs, net->win);
-    v.win = net->win; v.max_steps = max_steps; v.trace_steps = trace_steps;
-    v.total = net->ev_total; v.length = net->ev_len; v.finished = net->ev_fin;
-    v.tr_states = net->ev_states; v.tr_probs = net->ev_probs; v.tr_mu = net->ev_mu; v.tr_choices = net->ev_choices;
-    v.tr_act = net->ev_actions; v.tr_rew = net->ev_rew; v.tr_done = net->ev_done;
+    a3c_eval_args(net, v, max_steps, trace_steps);
+    v.tr_probs = net->ev_probs; v.tr_mu = net->ev_mu; v.tr_choices = net->ev_choices; v.tr_act = net->ev_actions;
     hipLaunchKernelGGL(gated_eval_kernel, dim3((E + 63) / 64), dim3(256), A3C_LDS, h->stream, v, ticker_params(h));
-    if ((rc = a3c_eval_finish(net, trace_steps))) return rc;
-    if ((rc = ticker_launch_reset(h, h->done_list, h->done_count, E))) return a3c_fail(net, rc, h->err);
-    return GRL_OK;
+    return a3c_eval_finish(net, trace_steps, [&] { return ticker_launch_reset(h, h->done_list, h->done_count, E); });
 }
 
-int grl_gnet_read_eval(grl_gnet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_read_eval: bad argument");
-    size_t SE;
-    int rc = a3c_eval_rows(net, "grl_gnet_read_eval", &SE);
-    if (rc) return rc;
-    const size_t E = net->h->E;
-    const A3cBuf tab[] = {
-        {"total_reward", net->ev_total, E * 8}, {"length", net->ev_len, E * 4}, {"finished", net->ev_fin, E},
-        {"states", net->ev_states, SE * GS0 * 4}, {"probs", net->ev_probs, SE * 24}, {"mu", net->ev_mu, SE * 24},
-        {"choices", net->ev_choices, SE * 8}, {"actions", net->ev_actions, SE * 16}, {"rewards", net->ev_rew, SE * 4},
-        {"dones", net->ev_done, SE * 4}};
-    return a3c_read(net, "grl_gnet_read_eval", tab, "", which, host, bytes);
-}
+int grl_gnet_read_eval(grl_gnet *net, const char *which, void *host, size_t bytes) { return a3c_read_eval(net, "grl_gnet_read_eval", which, host, bytes); }
 
 int grl_gnet_train_rollout(grl_gnet *net, float lr0, float *stats_host) {
-    if (!net) return GRL_E_INVALID;
-    if (!net->T) return a3c_fail(net, GRL_E_STATE, "grl_gnet_train_rollout: no rollout yet");
-    hipSetDevice(net->h->cfg.device_id);
-    const int E = net->h->E, n = net->T * E;
-    return train_device(net, n, net->ro_states, net->ro_win, net->ro_choices, net->ro_raw, net->ro_adv, net->ro_tgt, net->ro_wt,
-                        1.0f / (float)E, lr0, 1, stats_host);
+    return a3c_train_rollout(net, "grl_gnet_train_rollout", [&](int n, float mult) {
+        return train_device(net, n, net->ro_states, net->ro_win, net->ro_choices, net->ro_raw, net->ro_adv, net->ro_tgt, net->ro_wt, mult, lr0, 1,
+                            stats_host);
+    });
 }
 
 int grl_gnet_read_rollout(grl_gnet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return a3c_fail(net, GRL_E_INVALID, "grl_gnet_read_rollout: bad argument");
-    if (!net->T) return a3c_fail(net, GRL_E_STATE, "grl_gnet_read_rollout: no rollout yet");
-    const size_t TE = (size_t)net->T * net->h->E * 4, R = net->cfg.rnn_length;
-    const A3cBuf tab[] = {
-        {"states", net->ro_states, TE * GS0}, {"windows", net->ro_win, TE * R * GD}, {"choices", net->ro_choices, TE * 2},
-        {"raw", net->ro_raw, TE * 2}, {"probs", net->ro_probs, TE * 6}, {"mu", net->ro_mu, TE * 6}, {"sigma", net->ro_sigma, TE * 6},
-        {"values", net->ro_val, TE}, {"rewards", net->ro_rew, TE}, {"dones", net->ro_done, TE}, {"weights", net->ro_wt, TE},
-        {"adv", net->ro_adv, TE}, {"targets", net->ro_tgt, TE}, {"actions", net->ro_act, TE * 4}, {"boot", net->ro_boot, (size_t)net->h->E * 4}};
-    return a3c_read(net, "grl_gnet_read_rollout", tab, "", which, host, bytes);
+    return a3c_read_rollout(net, "grl_gnet_read_rollout", "", which, host, bytes);
 }
 
 }  // extern "C"

@@ -268,16 +268,13 @@ __global__ __launch_bounds__(256, 1) void gauss_backward_kernel(AArgs a) {
 struct grl_anet : grl::A3cNet {
     grl_anet_config cfg;
     grl::AOff off;
-    int D, A;                                     // processed observation = temporal row width, actions
-    // host-sample staging
-    float *d_states, *d_win, *d_raw, *d_adv, *d_tgt, *d_wt, *d_mu, *d_sigma, *d_vals;
-    // rollout
-    float *ro_states, *ro_win, *ro_raw, *ro_mu, *ro_sigma, *ro_val, *ro_rew, *ro_done, *ro_mask, *ro_wt, *ro_adv, *ro_tgt;
-    float *ro_act;                                // (T,E,A) the action each env was stepped with
+    int A;                                        // actions; S0 = D = the processed observation
+    // the heads' host-sample staging, rollout buffers and evaluation trace
+    float *d_raw, *d_mu, *d_sigma;
+    float *ro_raw, *ro_mu, *ro_sigma, *ro_act;    // ro_act (T,E,A): the action each env was stepped with
     float *ro_term_st, *ro_term_wn, *ro_term_val; // ro_term_st / ro_term_wn: always_bootstrap only
-    float *ro_boot, *boot_states, *boot_win, *term_obs;
-    // grl_anet_eval: the step's actions, the trace of the first ev_trace steps
-    float *ev_act, *ev_states, *ev_mu, *ev_actions, *ev_rew, *ev_done;
+    float *term_obs;
+    float *ev_act, *ev_mu;                        // ev_act (E,A): the evaluation step's actions
 };
 
 namespace grl {
@@ -311,35 +308,6 @@ static int train_device(grl_anet *net, int n, const float *states, const float *
     return a3c_train_finish(net, blocks, net->off.m1w, (double)net->A, lr0, apply, stats_host);
 }
 
-static int ensure_rollout(grl_anet *net, int T) {
-    if (T == net->T) return GRL_OK;
-    int rc = a3c_release(net, net->ro_allocs);
-    if (rc) return rc;
-    net->T = 0;
-    const size_t E = net->h->E, R = net->cfg.rnn_length, TE = (size_t)T * E, D = net->D, A = net->A;
-    A3cGrow Al{net, net->ro_allocs};
-    Al(&net->ro_states, TE * D); Al(&net->ro_win, TE * R * D); Al(&net->ro_raw, TE * A); Al(&net->ro_mu, TE * A); Al(&net->ro_sigma, TE * A);
-    Al(&net->ro_val, TE); Al(&net->ro_rew, TE); Al(&net->ro_done, TE); Al(&net->ro_mask, TE); Al(&net->ro_wt, TE); Al(&net->ro_adv, TE);
-    Al(&net->ro_tgt, TE); Al(&net->ro_act, TE * A); Al(&net->ro_term_val, TE);
-    net->ro_term_st = net->ro_term_wn = nullptr;
-    if (net->cfg.always_bootstrap) { Al(&net->ro_term_st, TE * D); Al(&net->ro_term_wn, TE * R * D); }
-    if (Al.rc == GRL_OK) net->T = T;
-    return Al.rc;
-}
-
-// the trace buffers of grl_anet_eval for `steps` steps (they only grow)
-static int ensure_eval_trace(grl_anet *net, int steps) {
-    if (steps <= net->ev_trace_cap) return GRL_OK;
-    int rc = a3c_release(net, net->ev_allocs);
-    if (rc) return rc;
-    net->ev_trace_cap = -1;
-    const size_t SE = (size_t)steps * net->h->E, D = net->D, A = net->A;
-    A3cGrow Al{net, net->ev_allocs};
-    Al(&net->ev_states, SE * D); Al(&net->ev_mu, SE * A); Al(&net->ev_actions, SE * A); Al(&net->ev_rew, SE); Al(&net->ev_done, SE);
-    if (Al.rc == GRL_OK) net->ev_trace_cap = steps;
-    return Al.rc;
-}
-
 }  // namespace grl
 
 using namespace grl;
@@ -357,47 +325,30 @@ int grl_anet_config_default(grl_anet_config *cfg) {
 }
 
 int grl_anet_create(grl_handle *h, const grl_anet_config *cfg, grl_anet **out) {
-    if (!h || !cfg || !out) return GRL_E_INVALID;
-    *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(grl_anet_config)) return fail(h, GRL_E_INVALID, "grl_anet_create: config size mismatch");
-    const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW, trade = h->cfg.env_kind == GRL_ENV_TRADE && h->cfg.n_assets == 2;
-    if (!solow && !trade) return fail(h, GRL_E_INVALID, "grl_anet_create: the Gaussian agent needs a Solow handle or a TradeAR1 handle with 2 assets");
-    if (cfg->rnn_length < 1 || cfg->rnn_length > MAXR || cfg->max_samples < 1 || cfg->lr_decay_steps < 1 || !(cfg->scale != 0.f) ||
-        !(cfg->gae_lambda > 0.f && cfg->gae_lambda <= 1.f))
-        return fail(h, GRL_E_INVALID, "grl_anet_create: config out of range (rnn_length 1..20)");
-    if (cfg->always_bootstrap != (solow ? 1 : 0))
-        return fail(h, GRL_E_INVALID, solow ? "grl_anet_create: a Solow handle needs always_bootstrap = 1" :
-                                              "grl_anet_create: a TradeAR1 handle needs always_bootstrap = 0");
-    hipSetDevice(h->cfg.device_id);
-    grl_anet *n = new grl_anet();
-    n->h = h; n->cfg = *cfg;
-    n->D = solow ? 2 : 5; n->A = solow ? 1 : 2;
-    n->off = gauss_offsets(n->D, n->A);
-    const size_t ms = cfg->max_samples, R = cfg->rnn_length, E = h->E, D = n->D, A = n->A;
-    int rc = a3c_create_common(n, n->off.total, E);
-    A3cGrow Al{n, n->allocs, rc};
-    Al(&n->d_states, ms * D); Al(&n->d_win, ms * R * D); Al(&n->d_raw, ms * A); Al(&n->d_adv, ms); Al(&n->d_tgt, ms); Al(&n->d_wt, ms);
-    Al(&n->d_mu, ms * A); Al(&n->d_sigma, ms * A); Al(&n->d_vals, ms);
-    Al(&n->win, E * R * D); Al(&n->ro_boot, E); Al(&n->boot_states, E * D); Al(&n->boot_win, E * R * D);
-    Al(&n->term_obs, E * D); Al(&n->ev_act, E * A);
-    rc = Al.rc;
-    if (rc == GRL_OK) {
-        hipError_t e = hipGetLastError();
-        const void *kernels[3] = {solow ? (const void *)gauss_forward_kernel<2> : (const void *)gauss_forward_kernel<5>,
-                                  solow ? (const void *)gauss_backward_kernel<2> : (const void *)gauss_backward_kernel<5>,
-                                  solow ? (const void *)gauss_eval_kernel<2, SolowParams> : (const void *)gauss_eval_kernel<5, TradeParams>};
-        for (const void *k : kernels)
-            if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)A3C_LDS);
-        if (e != hipSuccess) rc = a3c_fail(n, GRL_E_HIP, std::string("grl_anet_create: ") + hipGetErrorString(e));
-    }
-    if (rc != GRL_OK) {
-        fail(h, rc, "grl_anet_create: " + n->err);
-        grl_anet_destroy(n);
-        return rc;
-    }
-    hipStreamSynchronize(h->stream);
-    *out = n;
-    return GRL_OK;
+    const bool solow = h && h->cfg.env_kind == GRL_ENV_SOLOW, trade = h && h->cfg.env_kind == GRL_ENV_TRADE && h->cfg.n_assets == 2;
+    return a3c_create(
+        "grl_anet_create", h, cfg, out,
+        [&](const char *range) -> const char * {
+            if (!solow && !trade) return "the Gaussian agent needs a Solow handle or a TradeAR1 handle with 2 assets";
+            if (range) return range;
+            if (cfg->always_bootstrap == (solow ? 1 : 0)) return nullptr;
+            return solow ? "a Solow handle needs always_bootstrap = 1" : "a TradeAR1 handle needs always_bootstrap = 0";
+        },
+        [&](grl_anet *n, A3cGrow &Al) {
+            n->S0 = n->D = solow ? 2 : 5; n->A = solow ? 1 : 2;
+            n->off = gauss_offsets(n->D, n->A);
+            const size_t ms = cfg->max_samples, E = h->E, A = n->A, D = n->D, W = (size_t)cfg->rnn_length * D;
+            const bool ab = cfg->always_bootstrap;
+            n->ro_bufs = {a3c_buf("raw", &n->ro_raw, A), a3c_buf("mu", &n->ro_mu, A), a3c_buf("sigma", &n->ro_sigma, A),
+                          a3c_buf("actions", &n->ro_act, A), a3c_buf("term_values", &n->ro_term_val, 1),
+                          a3c_buf("term_states", &n->ro_term_st, D, false, ab), a3c_buf("term_windows", &n->ro_term_wn, W, false, ab)};
+            n->ev_bufs = {a3c_buf("mu", &n->ev_mu, A), a3c_buf("actions", &n->ev_actions, A)};
+            Al(&n->d_raw, ms * A); Al(&n->d_mu, ms * A); Al(&n->d_sigma, ms * A); Al(&n->term_obs, E * D); Al(&n->ev_act, E * A);
+            return (size_t)n->off.total;
+        },
+        {solow ? (const void *)gauss_forward_kernel<2> : (const void *)gauss_forward_kernel<5>,
+         solow ? (const void *)gauss_backward_kernel<2> : (const void *)gauss_backward_kernel<5>,
+         solow ? (const void *)gauss_eval_kernel<2, SolowParams> : (const void *)gauss_eval_kernel<5, TradeParams>});
 }
 
 int grl_anet_destroy(grl_anet *n) { return a3c_destroy(n); }
@@ -413,37 +364,23 @@ int grl_anet_set_action_counter(grl_anet *n, uint64_t v) { return a3c_set_action
 int grl_anet_set_greedy(grl_anet *net, int32_t on) { return a3c_set_greedy(net, on); }
 
 int grl_anet_predict(grl_anet *net, int32_t n, const float *states, const float *windows, float *mu, float *sigma, float *values) {
-    if (!net || n <= 0 || !states || !windows) return a3c_fail(net, GRL_E_INVALID, "grl_anet_predict: bad argument");
-    if (n > net->cfg.max_samples) return a3c_fail(net, GRL_E_SIZE, "grl_anet_predict: n exceeds max_samples");
-    hipSetDevice(net->h->cfg.device_id);
-    hipStream_t st = net->h->stream;
-    const size_t R = net->cfg.rnn_length, D = net->D, A = net->A;
-    A3C_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * D * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_win, windows, (size_t)n * R * D * 4, hipMemcpyHostToDevice, st));
+    int rc = a3c_samples_check(net, "grl_anet_predict", n, states && windows);
+    if (rc || (rc = a3c_stage(net, n, states, windows))) return rc;
     AArgs a = aargs(net, n, net->d_states, net->d_win);
     a.mu = net->d_mu; a.sigma = net->d_sigma; a.vals = net->d_vals;
-    int rc = launch_fwd(net, a);
-    if (rc) return rc;
-    A3C_HIP(net, hipStreamSynchronize(st));
-    if (mu) A3C_HIP(net, hipMemcpy(mu, net->d_mu, (size_t)n * A * 4, hipMemcpyDeviceToHost));
-    if (sigma) A3C_HIP(net, hipMemcpy(sigma, net->d_sigma, (size_t)n * A * 4, hipMemcpyDeviceToHost));
-    if (values) A3C_HIP(net, hipMemcpy(values, net->d_vals, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    if ((rc = launch_fwd(net, a))) return rc;
+    A3C_HIP(net, hipStreamSynchronize(net->h->stream));
+    const size_t A = net->A;
+    if ((rc = a3c_get(net, mu, net->d_mu, n * A)) || (rc = a3c_get(net, sigma, net->d_sigma, n * A))) return rc;
+    return a3c_get(net, values, net->d_vals, n);
 }
 
 int grl_anet_train(grl_anet *net, int32_t n, const float *states, const float *windows, const float *raw, const float *adv,
                    const float *targets, const float *weights, float grad_mult, float lr0, int32_t apply_update, float *stats_host) {
-    if (!net || n <= 0 || !states || !windows || !raw || !adv || !targets) return a3c_fail(net, GRL_E_INVALID, "grl_anet_train: bad argument");
-    if (n > net->cfg.max_samples) return a3c_fail(net, GRL_E_SIZE, "grl_anet_train: n exceeds max_samples");
-    hipSetDevice(net->h->cfg.device_id);
-    hipStream_t st = net->h->stream;
-    const size_t R = net->cfg.rnn_length, D = net->D, A = net->A;
-    A3C_HIP(net, hipMemcpyAsync(net->d_states, states, (size_t)n * D * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_win, windows, (size_t)n * R * D * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_raw, raw, (size_t)n * A * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_adv, adv, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    A3C_HIP(net, hipMemcpyAsync(net->d_tgt, targets, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    if (weights) A3C_HIP(net, hipMemcpyAsync(net->d_wt, weights, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    int rc = a3c_samples_check(net, "grl_anet_train", n, states && windows && raw && adv && targets);
+    if (rc || (rc = a3c_stage(net, n, states, windows)) || (rc = a3c_put(net, net->d_raw, raw, (size_t)n * net->A)) ||
+        (rc = a3c_stage_targets(net, n, adv, targets, weights)))
+        return rc;
     return train_device(net, n, net->d_states, net->d_win, net->d_raw, net->d_adv, net->d_tgt, weights ? net->d_wt : nullptr, grad_mult, lr0,
                         apply_update, stats_host);
 }
@@ -452,7 +389,7 @@ int grl_anet_rollout(grl_anet *net, int32_t T) {
     if (!net || T < 1) return a3c_fail(net, GRL_E_INVALID, "grl_anet_rollout: T >= 1");
     grl_handle *h = net->h;
     hipSetDevice(h->cfg.device_id);
-    int rc = ensure_rollout(net, T);
+    int rc = a3c_ensure_rollout(net, T);
     if (rc) return rc;
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     const size_t A = net->A;
@@ -472,21 +409,16 @@ int grl_anet_rollout(grl_anet *net, int32_t T) {
 }
 
 int grl_anet_eval(grl_anet *net, int32_t max_steps, int32_t trace_steps) {
-    if (!net) return GRL_E_INVALID;
-    if (max_steps < 1 || trace_steps < 0) return a3c_fail(net, GRL_E_INVALID, "grl_anet_eval: max_steps >= 1, trace_steps >= 0");
-    grl_handle *h = net->h;
-    hipSetDevice(h->cfg.device_id);
-    if (trace_steps > max_steps) trace_steps = max_steps;
-    int rc = ensure_eval_trace(net, trace_steps);
+    int rc = a3c_eval_begin(net, "grl_anet_eval", max_steps, &trace_steps);
     if (rc) return rc;
+    grl_handle *h = net->h;
     hipStream_t st = h->stream;
     const bool solow = h->cfg.env_kind == GRL_ENV_SOLOW;
     const int E = h->E;
     AEvalArgs v{};
     v.a = aargs(net, E, anet_obs(net), net->win);
-    v.win = net->win; v.act = net->ev_act; v.tanh_action = solow ? 0 : 1; v.max_steps = max_steps; v.trace_steps = trace_steps;
-    v.total = net->ev_total; v.length = net->ev_len; v.finished = net->ev_fin;
-    v.tr_states = net->ev_states; v.tr_mu = net->ev_mu; v.tr_act = net->ev_actions; v.tr_rew = net->ev_rew; v.tr_done = net->ev_done;
+    a3c_eval_args(net, v, max_steps, trace_steps);
+    v.act = net->ev_act; v.tanh_action = solow ? 0 : 1; v.tr_mu = net->ev_mu; v.tr_act = net->ev_actions;
     if (solow) {
         SolowParams S = solow_params(h);
         hipLaunchKernelGGL((gauss_eval_kernel<2, SolowParams>), dim3((E + 63) / 64), dim3(256), A3C_LDS, st, v, S);
@@ -494,45 +426,21 @@ int grl_anet_eval(grl_anet *net, int32_t max_steps, int32_t trace_steps) {
         TradeParams S = trade_params(h);
         hipLaunchKernelGGL((gauss_eval_kernel<5, TradeParams>), dim3((E + 63) / 64), dim3(256), A3C_LDS, st, v, S);
     }
-    if ((rc = a3c_eval_finish(net, trace_steps))) return rc;
-    // Solow: with the tape draw
-    rc = solow ? solow_launch_reset(h, h->done_list, h->done_count, E, true) : trade_launch_reset(h, h->done_list, h->done_count, E);
-    if (rc) return a3c_fail(net, rc, h->err);
-    return GRL_OK;
+    return a3c_eval_finish(net, trace_steps, [&] {      // Solow: with the tape draw
+        return solow ? solow_launch_reset(h, h->done_list, h->done_count, E, true) : trade_launch_reset(h, h->done_list, h->done_count, E);
+    });
 }
 
-int grl_anet_read_eval(grl_anet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return a3c_fail(net, GRL_E_INVALID, "grl_anet_read_eval: bad argument");
-    size_t SE;
-    int rc = a3c_eval_rows(net, "grl_anet_read_eval", &SE);
-    if (rc) return rc;
-    const size_t E = net->h->E, D = net->D, A = net->A;
-    const A3cBuf tab[] = {
-        {"total_reward", net->ev_total, E * 8}, {"length", net->ev_len, E * 4}, {"finished", net->ev_fin, E},
-        {"states", net->ev_states, SE * D * 4}, {"mu", net->ev_mu, SE * A * 4}, {"actions", net->ev_actions, SE * A * 4},
-        {"rewards", net->ev_rew, SE * 4}, {"dones", net->ev_done, SE * 4}};
-    return a3c_read(net, "grl_anet_read_eval", tab, "", which, host, bytes);
-}
+int grl_anet_read_eval(grl_anet *net, const char *which, void *host, size_t bytes) { return a3c_read_eval(net, "grl_anet_read_eval", which, host, bytes); }
 
 int grl_anet_train_rollout(grl_anet *net, float lr0, float *stats_host) {
-    if (!net) return GRL_E_INVALID;
-    if (!net->T) return a3c_fail(net, GRL_E_STATE, "grl_anet_train_rollout: no rollout yet");
-    hipSetDevice(net->h->cfg.device_id);
-    const int E = net->h->E, n = net->T * E;
-    return train_device(net, n, net->ro_states, net->ro_win, net->ro_raw, net->ro_adv, net->ro_tgt, net->ro_wt, 1.0f / (float)E, lr0, 1,
-                        stats_host);
+    return a3c_train_rollout(net, "grl_anet_train_rollout", [&](int n, float mult) {
+        return train_device(net, n, net->ro_states, net->ro_win, net->ro_raw, net->ro_adv, net->ro_tgt, net->ro_wt, mult, lr0, 1, stats_host);
+    });
 }
 
 int grl_anet_read_rollout(grl_anet *net, const char *which, void *host, size_t bytes) {
-    if (!net || !which || !host) return a3c_fail(net, GRL_E_INVALID, "grl_anet_read_rollout: bad argument");
-    if (!net->T) return a3c_fail(net, GRL_E_STATE, "grl_anet_read_rollout: no rollout yet");
-    const size_t TE = (size_t)net->T * net->h->E * 4, R = net->cfg.rnn_length, D = net->D, A = net->A;
-    const A3cBuf tab[] = {
-        {"states", net->ro_states, TE * D}, {"windows", net->ro_win, TE * R * D}, {"raw", net->ro_raw, TE * A}, {"mu", net->ro_mu, TE * A},
-        {"sigma", net->ro_sigma, TE * A}, {"actions", net->ro_act, TE * A}, {"values", net->ro_val, TE}, {"rewards", net->ro_rew, TE}, {"dones", net->ro_done, TE},
-        {"weights", net->ro_wt, TE}, {"adv", net->ro_adv, TE}, {"targets", net->ro_tgt, TE}, {"term_values", net->ro_term_val, TE},
-        {"term_states", net->ro_term_st, TE * D}, {"term_windows", net->ro_term_wn, TE * R * D}, {"boot", net->ro_boot, (size_t)net->h->E * 4}};
-    return a3c_read(net, "grl_anet_read_rollout", tab, " exists with always_bootstrap = 1 only", which, host, bytes);
+    return a3c_read_rollout(net, "grl_anet_read_rollout", " exists with always_bootstrap = 1 only", which, host, bytes);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-"""What the ctypes bindings of the two A3C nets share (GatedNet in _ffi_gated.py, GaussNet in _ffi_gauss.py): the two C ABIs name the
-same functions behind another prefix (grl_gnet_ / grl_anet_)."""
+"""What the ctypes bindings of the three A3C nets share (GatedNet in _ffi_gated.py, GaussNet in _ffi_gauss.py, DiscreteNet in
+_ffi_discrete.py): the three C ABIs name the same functions behind another prefix (grl_gnet_ / grl_anet_ / grl_dnet_), with their
+heads' arrays in predict and train."""
 import ctypes as C
 
 import numpy as np
@@ -8,10 +9,39 @@ from . import _ffi
 
 STAT_NAMES = ("policy_loss", "value_loss", "entropy_mean", "policy_norm", "value_norm", "lr")
 _CHECKPOINT = ("params", "ms_policy", "ms_value", "global_step", "action_counter")
+_P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
+
+
+def signatures(prefix, config, predict, train):
+    """The signature dicts of one net's two headers, (training: 17 functions, evaluation: 3).  predict: the output arrays of
+    grl_*net_predict behind (net, n, states, windows); train: the input arrays of grl_*net_train between windows and weights."""
+    cfg = C.POINTER(config)
+    training = {
+        "config_default": (C.c_int, [cfg]),
+        "create": (C.c_int, [_P, cfg, C.POINTER(_P)]),
+        "destroy": (C.c_int, [_P]),
+        "last_error": (C.c_char_p, [_P]),
+        "num_params": (C.c_int64, [_P]),
+        "set_params": (C.c_int, [_P, _P, C.c_int64]),
+        "get_params": (C.c_int, [_P, _P, C.c_int64]),
+        "get_grads": (C.c_int, [_P, _I, _P, C.c_int64]),
+        "get_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+        "set_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64]),
+        "get_action_counter": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+        "set_action_counter": (C.c_int, [_P, C.c_uint64]),
+        "predict": (C.c_int, [_P, _I, _P, _P] + [_P] * len(predict)),
+        "train": (C.c_int, [_P, _I, _P, _P] + [_P] * len(train) + [_P, _F, _F, _I, _P]),      # .., weights, grad_mult, lr0, apply, stats
+        "rollout": (C.c_int, [_P, _I]),
+        "train_rollout": (C.c_int, [_P, _F, _P]),
+        "read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+    }
+    evaluation = {"set_greedy": (C.c_int, [_P, _I]), "eval": (C.c_int, [_P, _I, _I]), "read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ])}
+    return {prefix + k: v for k, v in training.items()}, {prefix + k: v for k, v in evaluation.items()}
 
 
 class A3cNet(object):
-    PREFIX = None       # "grl_gnet_" / "grl_anet_"
+    PREFIX = None       # "grl_gnet_" / "grl_anet_" / "grl_dnet_"
+    # set by the net: S0, D (the widths of a state and of a window row) and R
 
     def _create(self, engine, signatures, cfg, kw):
         """The net on the engine's handle from the C defaults overridden by kw."""
@@ -95,10 +125,29 @@ class A3cNet(object):
             self.set_action_counter(int(z["action_counter"]))
             return {k: z[k] for k in z.files if k not in _CHECKPOINT}
 
-    def _train(self, *arrays_and_scalars):
-        """grl_*net_train on pointers / scalars in the C order; the six stats by name."""
+    def _stage(self, states, windows):
+        """n and the float32 states (n,S0) and windows (n,R,D) of a predict or train call"""
+        s, w = np.ascontiguousarray(states, np.float32), np.ascontiguousarray(windows, np.float32)
+        n = s.shape[0]
+        assert s.shape == (n, self.S0) and w.shape == (n, self.R, self.D), (s.shape, w.shape)
+        return n, s, w
+
+    def _predict(self, states, windows, heads):
+        """grl_*net_predict: heads = (name, shape behind n) of the output arrays in the C order, before values."""
+        n, s, w = self._stage(states, windows)
+        out = {k: np.empty((n,) + tail, np.float32) for k, tail in heads + (("values", ()),)}
+        self._check(self._fn("predict")(self.n, n, _ffi._ptr(s), _ffi._ptr(w), *[_ffi._ptr(a) for a in out.values()]))
+        return out
+
+    def _train(self, states, windows, heads, adv, targets, weights, grad_mult, lr, apply_update):
+        """grl_*net_train: heads = (array, dtype, shape behind n) of the net's own inputs in the C order; the six stats by name."""
+        n, s, w = self._stage(states, windows)
+        arrs = [np.ascontiguousarray(a, dt) for a, dt, _ in heads] + [np.ascontiguousarray(a, np.float32) for a in (adv, targets)]
+        assert [a.shape for a in arrs] == [(n,) + tail for _, _, tail in heads] + [(n,), (n,)], [a.shape for a in arrs]
+        wt = None if weights is None else np.ascontiguousarray(weights, np.float32)
         stats = np.zeros(6, np.float32)
-        self._check(self._fn("train")(self.n, *(arrays_and_scalars + (_ffi._ptr(stats),))))
+        self._check(self._fn("train")(self.n, n, _ffi._ptr(s), _ffi._ptr(w), *[_ffi._ptr(a) for a in arrs], None if wt is None else _ffi._ptr(wt),
+                                      float(grad_mult), float(lr), 1 if apply_update else 0, _ffi._ptr(stats)))
         return dict(zip(STAT_NAMES, stats.tolist()))
 
     def rollout(self, T):

@@ -5,9 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi_a3c import STAT_NAMES, A3cNet  # noqa: F401
-
-_P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
+from ._ffi_a3c import STAT_NAMES, A3cNet, signatures  # noqa: F401
 
 SOLOW_SIZES = dict(static_size=2, temporal_size=2, num_outputs=1)
 
@@ -19,31 +17,10 @@ class GrlDnetConfig(C.Structure):
                 ("lr_decay_rate", C.c_float), ("grid_lb", C.c_double), ("grid_ub", C.c_double)]
 
 
-DNET_SIGNATURES = {
-    "grl_dnet_config_default": (C.c_int, [C.POINTER(GrlDnetConfig)]),
-    "grl_dnet_create": (C.c_int, [_P, C.POINTER(GrlDnetConfig), C.POINTER(_P)]),
-    "grl_dnet_destroy": (C.c_int, [_P]),
-    "grl_dnet_last_error": (C.c_char_p, [_P]),
-    "grl_dnet_num_params": (C.c_int64, [_P]),
-    "grl_dnet_set_params": (C.c_int, [_P, _P, C.c_int64]),
-    "grl_dnet_get_params": (C.c_int, [_P, _P, C.c_int64]),
-    "grl_dnet_get_grads": (C.c_int, [_P, _I, _P, C.c_int64]),
-    "grl_dnet_get_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
-    "grl_dnet_set_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64]),
-    "grl_dnet_get_action_counter": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
-    "grl_dnet_set_action_counter": (C.c_int, [_P, C.c_uint64]),
-    "grl_dnet_predict": (C.c_int, [_P, _I, _P, _P, _P, _P]),
-    "grl_dnet_train": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P]),
-    "grl_dnet_rollout": (C.c_int, [_P, _I]),
-    "grl_dnet_train_rollout": (C.c_int, [_P, _F, _P]),
-    "grl_dnet_read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
-}
-# include/goldsrl_discreteeval.h: a dict of its own, as the header is a file of its own (tests/test_discrete_header.py pins both)
-DNET_EVAL_SIGNATURES = {
-    "grl_dnet_set_greedy": (C.c_int, [_P, _I]),
-    "grl_dnet_eval": (C.c_int, [_P, _I, _I]),
-    "grl_dnet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
-}
+# include/goldsrl_discretenet.h's 17 training functions and include/goldsrl_discreteeval.h's three: a dict per header
+# (tests/test_discrete_header.py pins both)
+DNET_SIGNATURES, DNET_EVAL_SIGNATURES = signatures("grl_dnet_", GrlDnetConfig, predict=("probs", "values"),
+                                                   train=("choices", "adv", "targets"))
 
 
 def discrete_param_shapes(K=51, static_size=2, temporal_size=2, H=32, S=128):
@@ -86,25 +63,11 @@ class DiscreteNet(A3cNet):
         self.grid = np.linspace(self.cfg.grid_lb, self.cfg.grid_ub, self.K)
 
     def predict(self, states, windows):
-        s = np.ascontiguousarray(states, np.float32)
-        w = np.ascontiguousarray(windows, np.float32)
-        n = s.shape[0]
-        assert s.shape == (n, self.S0) and w.shape == (n, self.R, self.D), (s.shape, w.shape)
-        probs, vals = np.empty((n, self.K), np.float32), np.empty(n, np.float32)
-        self._check(self.lib.grl_dnet_predict(self.n, n, _ffi._ptr(s), _ffi._ptr(w), _ffi._ptr(probs), _ffi._ptr(vals)))
-        return {"probs": probs, "values": vals}
+        return self._predict(states, windows, (("probs", (self.K,)),))
 
     def train(self, states, windows, choices, adv, targets, weights=None, grad_mult=1.0, lr=1e-4, apply_update=True):
-        s = np.ascontiguousarray(states, np.float32)
-        n = s.shape[0]
-        w = np.ascontiguousarray(windows, np.float32)
-        ch = np.ascontiguousarray(np.asarray(choices).reshape(-1), np.int32)
-        arrs = [np.ascontiguousarray(a, np.float32) for a in (adv, targets)]
-        assert s.shape == (n, self.S0) and w.shape == (n, self.R, self.D) and ch.shape == (n,)
-        assert arrs[0].shape == (n,) and arrs[1].shape == (n,)
-        wt = None if weights is None else np.ascontiguousarray(weights, np.float32)
-        return self._train(n, _ffi._ptr(s), _ffi._ptr(w), _ffi._ptr(ch), *[_ffi._ptr(a) for a in arrs], None if wt is None else _ffi._ptr(wt),
-                           float(grad_mult), float(lr), 1 if apply_update else 0)
+        heads = [(np.asarray(choices).reshape(-1), np.int32, ())]
+        return self._train(states, windows, heads, adv, targets, weights, grad_mult, lr, apply_update)
 
     def read_rollout(self, which):
         T, E, R, D = self.T, self.eng.E, self.R, self.D

@@ -4,9 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi_a3c import STAT_NAMES, A3cNet  # noqa: F401
-
-_P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
+from ._ffi_a3c import STAT_NAMES, A3cNet, signatures  # noqa: F401
 
 N_ASSETS, N_CHOICES, STATIC_SIZE, TEMPORAL_SIZE = 2, 3, 7, 4
 
@@ -17,32 +15,10 @@ class GrlGnetConfig(C.Structure):
                 ("rms_decay", C.c_float), ("rms_epsilon", C.c_float), ("lr_decay_rate", C.c_float)]
 
 
-GNET_SIGNATURES = {
-    "grl_gnet_config_default": (C.c_int, [C.POINTER(GrlGnetConfig)]),
-    "grl_gnet_create": (C.c_int, [_P, C.POINTER(GrlGnetConfig), C.POINTER(_P)]),
-    "grl_gnet_destroy": (C.c_int, [_P]),
-    "grl_gnet_last_error": (C.c_char_p, [_P]),
-    "grl_gnet_num_params": (C.c_int64, [_P]),
-    "grl_gnet_set_params": (C.c_int, [_P, _P, C.c_int64]),
-    "grl_gnet_get_params": (C.c_int, [_P, _P, C.c_int64]),
-    "grl_gnet_get_grads": (C.c_int, [_P, _I, _P, C.c_int64]),
-    "grl_gnet_get_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
-    "grl_gnet_set_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64]),
-    "grl_gnet_get_action_counter": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
-    "grl_gnet_set_action_counter": (C.c_int, [_P, C.c_uint64]),
-    "grl_gnet_predict": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P]),
-    "grl_gnet_train": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P]),
-    "grl_gnet_rollout": (C.c_int, [_P, _I]),
-    "grl_gnet_train_rollout": (C.c_int, [_P, _F, _P]),
-    "grl_gnet_read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
-}
-# include/goldsrl_gatedeval.h: a dict of its own, as the header is a file of its own (GNET_SIGNATURES is pinned to goldsrl_gatednet.h's
-# 17 training functions by tests/test_oracle_gated.py; these three are pinned by tests/test_gated_eval_header.py)
-GNET_EVAL_SIGNATURES = {
-    "grl_gnet_set_greedy": (C.c_int, [_P, _I]),
-    "grl_gnet_eval": (C.c_int, [_P, _I, _I]),
-    "grl_gnet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
-}
+# include/goldsrl_gatednet.h's 17 training functions and include/goldsrl_gatedeval.h's three: a dict per header (pinned by
+# tests/test_gated_eval_header.py)
+GNET_SIGNATURES, GNET_EVAL_SIGNATURES = signatures("grl_gnet_", GrlGnetConfig, predict=("probs", "mu", "sigma", "values"),
+                                                   train=("choices", "raw", "adv", "targets"))
 
 
 def gated_param_shapes(static_size=STATIC_SIZE, temporal_size=TEMPORAL_SIZE, H=32, S=128):
@@ -80,30 +56,17 @@ class GatedNet(A3cNet):
     choice is the first argmax of the float32 probs, raw = mu[choice]."""
     PREFIX = "grl_gnet_"
 
+    S0, D = STATIC_SIZE, TEMPORAL_SIZE
+
     def __init__(self, engine, **kw):
         self._create(engine, dict(GNET_SIGNATURES, **GNET_EVAL_SIGNATURES), GrlGnetConfig(), kw)
 
     def predict(self, states, windows):
-        s = np.ascontiguousarray(states, np.float32)
-        w = np.ascontiguousarray(windows, np.float32)
-        n = s.shape[0]
-        assert s.shape == (n, STATIC_SIZE) and w.shape == (n, self.R, TEMPORAL_SIZE), (s.shape, w.shape)
-        probs, mu, sigma = [np.empty((n, N_ASSETS, N_CHOICES), np.float32) for _ in range(3)]
-        vals = np.empty(n, np.float32)
-        self._check(self.lib.grl_gnet_predict(self.n, n, _ffi._ptr(s), _ffi._ptr(w), _ffi._ptr(probs), _ffi._ptr(mu), _ffi._ptr(sigma),
-                                              _ffi._ptr(vals)))
-        return {"probs": probs, "mu": mu, "sigma": sigma, "values": vals}
+        return self._predict(states, windows, tuple((k, (N_ASSETS, N_CHOICES)) for k in ("probs", "mu", "sigma")))
 
     def train(self, states, windows, choices, raw, adv, targets, weights=None, grad_mult=1.0, lr=1e-4, apply_update=True):
-        s = np.ascontiguousarray(states, np.float32)
-        n = s.shape[0]
-        w = np.ascontiguousarray(windows, np.float32)
-        ch = np.ascontiguousarray(choices, np.int32)
-        arrs = [np.ascontiguousarray(a, np.float32) for a in (raw, adv, targets)]
-        assert w.shape == (n, self.R, TEMPORAL_SIZE) and ch.shape == (n, N_ASSETS) and arrs[0].shape == (n, N_ASSETS)
-        wt = None if weights is None else np.ascontiguousarray(weights, np.float32)
-        return self._train(n, _ffi._ptr(s), _ffi._ptr(w), _ffi._ptr(ch), *[_ffi._ptr(a) for a in arrs], None if wt is None else _ffi._ptr(wt),
-                           float(grad_mult), float(lr), 1 if apply_update else 0)
+        heads = [(choices, np.int32, (N_ASSETS,)), (raw, np.float32, (N_ASSETS,))]
+        return self._train(states, windows, heads, adv, targets, weights, grad_mult, lr, apply_update)
 
     def read_rollout(self, which):
         T, E, R = self.T, self.eng.E, self.R

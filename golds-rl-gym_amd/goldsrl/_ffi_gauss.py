@@ -4,9 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi_a3c import STAT_NAMES, A3cNet  # noqa: F401
-
-_P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
+from ._ffi_a3c import STAT_NAMES, A3cNet, signatures  # noqa: F401
 
 SOLOW_SIZES = dict(static_size=2, temporal_size=2, num_actions=1)       # scripts/train_solow.py:40-42
 TRADE_SIZES = dict(static_size=5, temporal_size=5, num_actions=2)       # scripts/train_trade.py (2 assets)
@@ -18,32 +16,10 @@ class GrlAnetConfig(C.Structure):
                 ("clip_norm", C.c_float), ("rms_decay", C.c_float), ("rms_epsilon", C.c_float), ("lr_decay_rate", C.c_float)]
 
 
-ANET_SIGNATURES = {
-    "grl_anet_config_default": (C.c_int, [C.POINTER(GrlAnetConfig)]),
-    "grl_anet_create": (C.c_int, [_P, C.POINTER(GrlAnetConfig), C.POINTER(_P)]),
-    "grl_anet_destroy": (C.c_int, [_P]),
-    "grl_anet_last_error": (C.c_char_p, [_P]),
-    "grl_anet_num_params": (C.c_int64, [_P]),
-    "grl_anet_set_params": (C.c_int, [_P, _P, C.c_int64]),
-    "grl_anet_get_params": (C.c_int, [_P, _P, C.c_int64]),
-    "grl_anet_get_grads": (C.c_int, [_P, _I, _P, C.c_int64]),
-    "grl_anet_get_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
-    "grl_anet_set_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64]),
-    "grl_anet_get_action_counter": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
-    "grl_anet_set_action_counter": (C.c_int, [_P, C.c_uint64]),
-    "grl_anet_predict": (C.c_int, [_P, _I, _P, _P, _P, _P, _P]),
-    "grl_anet_train": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _P, _F, _F, _I, _P]),
-    "grl_anet_rollout": (C.c_int, [_P, _I]),
-    "grl_anet_train_rollout": (C.c_int, [_P, _F, _P]),
-    "grl_anet_read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
-}
-# include/goldsrl_gausseval.h: a dict of its own, as the header is a file of its own (ANET_SIGNATURES is pinned to goldsrl_gaussnet.h's
-# 17 training functions by tests/test_oracle_gauss.py; these three are pinned by tests/test_gauss_eval_header.py)
-ANET_EVAL_SIGNATURES = {
-    "grl_anet_set_greedy": (C.c_int, [_P, _I]),
-    "grl_anet_eval": (C.c_int, [_P, _I, _I]),
-    "grl_anet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
-}
+# include/goldsrl_gaussnet.h's 17 training functions and include/goldsrl_gausseval.h's three: a dict per header (pinned by
+# tests/test_gauss_eval_header.py)
+ANET_SIGNATURES, ANET_EVAL_SIGNATURES = signatures("grl_anet_", GrlAnetConfig, predict=("mu", "sigma", "values"),
+                                                   train=("raw", "adv", "targets"))
 
 
 def gauss_param_shapes(static_size=2, temporal_size=2, num_actions=1, H=32, S=128):
@@ -92,25 +68,10 @@ class GaussNet(A3cNet):
         self.S0, self.D, self.A = self.sizes["static_size"], self.sizes["temporal_size"], self.sizes["num_actions"]
 
     def predict(self, states, windows):
-        s = np.ascontiguousarray(states, np.float32)
-        w = np.ascontiguousarray(windows, np.float32)
-        n = s.shape[0]
-        assert s.shape == (n, self.S0) and w.shape == (n, self.R, self.D), (s.shape, w.shape)
-        mu, sigma = np.empty((n, self.A), np.float32), np.empty((n, self.A), np.float32)
-        vals = np.empty(n, np.float32)
-        self._check(self.lib.grl_anet_predict(self.n, n, _ffi._ptr(s), _ffi._ptr(w), _ffi._ptr(mu), _ffi._ptr(sigma), _ffi._ptr(vals)))
-        return {"mu": mu, "sigma": sigma, "values": vals}
+        return self._predict(states, windows, (("mu", (self.A,)), ("sigma", (self.A,))))
 
     def train(self, states, windows, raw, adv, targets, weights=None, grad_mult=1.0, lr=1e-4, apply_update=True):
-        s = np.ascontiguousarray(states, np.float32)
-        n = s.shape[0]
-        w = np.ascontiguousarray(windows, np.float32)
-        arrs = [np.ascontiguousarray(a, np.float32) for a in (raw, adv, targets)]
-        assert s.shape == (n, self.S0) and w.shape == (n, self.R, self.D) and arrs[0].shape == (n, self.A)
-        assert arrs[1].shape == (n,) and arrs[2].shape == (n,)
-        wt = None if weights is None else np.ascontiguousarray(weights, np.float32)
-        return self._train(n, _ffi._ptr(s), _ffi._ptr(w), *[_ffi._ptr(a) for a in arrs], None if wt is None else _ffi._ptr(wt),
-                           float(grad_mult), float(lr), 1 if apply_update else 0)
+        return self._train(states, windows, [(raw, np.float32, (self.A,))], adv, targets, weights, grad_mult, lr, apply_update)
 
     def read_rollout(self, which):
         T, E, R, D, A = self.T, self.eng.E, self.R, self.D, self.A
