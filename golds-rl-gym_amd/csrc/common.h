@@ -73,6 +73,17 @@ struct SolowSweepState {
     int n_rates, max_steps, trace_env;            // of the last sweep; n_rates == 0: none yet
 };
 
+// buffers of grl_trade_sweep (trade_sweep.hip): allocated on first use, grown when a later sweep is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct TradeSweepState {
+    float *gains, *biases, *mn, *mx, *trace_r, *tape;   // (cap_rules) (cap_rules) (cap_pairs) (cap_pairs) (cap_trace) (cap_tape)
+    double *total, *sum_sq, *final_assets, *trace_a;     // (cap_pairs) (cap_pairs) (cap_pairs) (cap_trace)
+    int32_t *length;                                     // (cap_pairs)
+    uint8_t *finished, *depleted;                        // (cap_pairs)
+    size_t cap_rules, cap_pairs, cap_trace, cap_tape;
+    int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
+};
+
 // buffers of grl_swarm_replay (swarm_replay.hip): allocated on first use, grown when a later replay is larger, listed in
 // grl_handle::allocs so grl_destroy frees them
 struct SwarmReplayState {
@@ -107,6 +118,7 @@ struct grl_handle {
     grl::TickerState tk;
     grl::SolowSweepState swp;
     grl::SwarmReplayState rpl;
+    grl::TradeSweepState tsw;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;
     // R6 episode bookkeeping (grl_episodes_*): nullptr until enabled

@@ -297,5 +297,47 @@ __device__ __forceinline__ TradeStepOut trade_step_env(const TradeParams &R, int
     return o_;
 }
 
+// The arithmetic of trade_step_env on values the caller holds (registers, or LDS columns for many assets), for a caller that keeps
+// an env's account there and plays several scripted rules over one price path (trade_sweep.hip).  Same operations in the same
+// order as the account lines and the price line of trade_step_env above, so the two give the same bits
+// (tests/test_gpu_trade_sweep.py holds them together).  The caller walks the assets in order and calls trade_rule_action and
+// trade_asset_trade for each, then trade_account_settle once.
+
+// the scripted rule (include/goldsrl_tradesweep.h): clip(bias - gain * (p - 1), -1, 1) in float64, one IEEE operation per line,
+// rounded to the float32 action the env is stepped with
+__device__ __forceinline__ float trade_rule_action(double gain, double bias, double p) {
+    const double d = p - 1.0;
+    const double m = gain * d;
+    double x = bias - m;
+    x = fmin(fmax(x, -1.0), 1.0);
+    return (float)x;
+}
+
+// one asset's trade: buys are sized from the cash before any purchase of this step; cost and value accumulate in asset order
+__device__ __forceinline__ void trade_asset_trade(float actf, int n, double cash, double p, double &q, double &cost, double &value) {
+    const double act = (double)actf;
+    const double q_add = act > 0.0 ? (act / (double)n) * cash / p : act * q;
+    q += q_add;
+    cost += q_add * p;
+    value += q * p;
+}
+
+// the end of the account step: advances cash and assets, returns the reward; depleted = assets < MIN_CASH
+__device__ __forceinline__ float trade_account_settle(double &cash, double &assets, double cost, double value, bool &depleted) {
+    const double assets_old = assets;
+    cash = cash + (-cost);
+    assets = cash + value;
+    depleted = assets < 1.0;
+    return (float)(log(assets + 1e-4) - log(assets_old + 1e-4));
+}
+
+// _price_transition on a value: p**rho_p * exp(std_e * N(0,1))
+__device__ __forceinline__ double trade_price_next(double p, double std_e, double z) { return pow(p, 0.9) * exp(std_e * z); }
+
+// the two normals of asset pair `pr` at generator step `st` of `env`: the key and counter trade_step_env draws with
+__device__ __forceinline__ void trade_price_normals(uint64_t seed, uint32_t env_id, uint32_t st, int pairs, int pr, double &z0, double &z1) {
+    normal_pair(rng_block(seed, env_id, 0u, RS_TRADE_PRICE, st * (uint32_t)pairs + (uint32_t)pr), z0, z1);
+}
+
 
 }  // namespace grl

@@ -1,0 +1,295 @@
+// Scripted trading-rule baseline sweep for TradeAR1: every (env, rule) pair plays a whole episode from the env's current state in
+// ONE launch (C ABI: include/goldsrl_tradesweep.h).
+//
+// Mapping (that of solow_sweep.hip): one lane per env, RPL rules per lane.  The price path does not depend on the actions, so the
+// lane draws the normals and runs pow / exp once per asset and step and carries RPL accounts (cash, assets, q[n]) over it; the
+// rule's action, the trade and the two logs of the reward run per rule.  Lanes of a wave are consecutive envs; the waves of a
+// workgroup hold rule groups of the SAME 64 envs.  No workgroup talks to another, there is no barrier.
+//
+// Where p and q live: up to 16 assets in registers, in compile-time tiers NT = 2 / 4 / 8 / 16 whose loops are fully unrolled under
+// a uniform `a < n` guard (no runtime register index, no arithmetic on the unused slots).  From 17 to 64 assets (NT = 0) they are
+// LDS columns [asset][lane] of the lane's wave, (1 + RPL) * n * 512 bytes per wave; the workgroup has as many waves (4 at most)
+// as fit in the CU's 160 KB, one at 64 assets and RPL 4.  Either way the handle's global memory is read once at entry.
+//
+// The handle's state is read only: nothing here writes cash, assets, q, p, nstep, elapsed, the outputs, the done list or the
+// episode records.
+#include <math.h>
+#include <stdlib.h>
+
+#include "common.h"
+#include "rng.h"
+#include "flat_env_dev.h"
+#include "../../include/goldsrl_tradesweep.h"
+
+namespace grl {
+
+struct TradeSweepOut {
+    double *total, *sum_sq, *final_assets;
+    float *mn, *mx;
+    int32_t *length;
+    uint8_t *finished, *depleted;
+    float *trace_r;
+    double *trace_a;
+};
+
+constexpr int TSW_LDS_BYTES = 160 * 1024;
+
+// f(a) for a = 0 .. n-1: unrolled to NT slots under a uniform guard (registers), or a plain loop (LDS columns)
+template <int NT, class F>
+__device__ __forceinline__ void tsw_for(int n, F f) {
+    if constexpr (NT > 0) {
+#pragma unroll
+        for (int a = 0; a < NT; ++a)
+            if (a < n) f(a);
+    } else {
+        for (int a = 0; a < n; ++a) f(a);
+    }
+}
+
+template <int RPL, int NT>
+__global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const float *__restrict__ gains, const float *__restrict__ biases,
+                                                          int n_rules, const float *__restrict__ tape, int max_steps, int trace_env,
+                                                          TradeSweepOut O) {
+    extern __shared__ double tsw_lds[];
+    constexpr bool REG = NT > 0;
+    constexpr int NR = REG ? NT : 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int env = blockIdx.x * 64 + lane;
+    const int r0 = (blockIdx.y * waves + wave) * RPL;          // wave-uniform
+    if (r0 >= n_rules || env >= R.E) return;
+    const size_t E = R.E;
+    const int n = R.n, pairs = (n + 1) / 2;
+
+    double pr[NR], qr[RPL][NR];
+    double *col = tsw_lds + (size_t)wave * (1 + RPL) * n * 64 + lane;      // LDS form: p at col[a * 64], q of rule j at col[((1 + j) * n + a) * 64]
+    auto P = [&](int a) -> double & { if constexpr (REG) return pr[a]; else return col[(size_t)a * 64]; };
+    auto Q = [&](int j, int a) -> double & { if constexpr (REG) return qr[j][a]; else return col[((size_t)(1 + j) * n + a) * 64]; };
+
+    double gain[RPL], bias[RPL], cash[RPL], assets[RPL], tot[RPL], ssq[RPL];
+    float mn[RPL], mx[RPL];
+    int length[RPL];
+    bool live[RPL], finished[RPL], depleted[RPL];
+    const double cash0 = R.cash[env], assets0 = R.assets[env];
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) {
+        const int r = r0 + j < n_rules ? r0 + j : n_rules - 1;             // a ragged tail replays the last rule and stores nothing
+        gain[j] = (double)gains[r]; bias[j] = (double)biases[r];
+        cash[j] = cash0; assets[j] = assets0; tot[j] = 0.0; ssq[j] = 0.0;
+        mn[j] = __builtin_huge_valf(); mx[j] = -__builtin_huge_valf();
+        length[j] = 0; live[j] = true; finished[j] = false; depleted[j] = false;
+    }
+    tsw_for<NT>(n, [&](int a) {
+        P(a) = R.p[a * E + env];
+        const double q0 = R.q[a * E + env];
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) Q(j, a) = q0;
+    });
+    const uint32_t st0 = R.nstep[env];
+    const int el0 = R.elapsed[env];
+    const bool trace = env == trace_env;
+
+    for (int t = 0; t < max_steps; ++t) {
+        const bool last = R.max_steps > 0 && el0 + t + 1 >= R.max_steps;   // the TimeLimit ends every rule of the env at this step
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+            if (!live[j]) continue;
+            double cost = 0.0, value = 0.0;
+            const double c = cash[j];
+            tsw_for<NT>(n, [&](int a) {
+                const double p = P(a);
+                trade_asset_trade(trade_rule_action(gain[j], bias[j], p), n, c, p, Q(j, a), cost, value);
+            });
+            bool dep;
+            const float rew = trade_account_settle(cash[j], assets[j], cost, value, dep);
+            tot[j] += (double)rew;
+            ssq[j] += (double)rew * (double)rew;
+            mn[j] = fminf(mn[j], rew);
+            mx[j] = fmaxf(mx[j], rew);
+            length[j] = t + 1;
+            if (trace && r0 + j < n_rules) {
+                O.trace_r[(size_t)(r0 + j) * max_steps + t] = rew;
+                O.trace_a[(size_t)(r0 + j) * max_steps + t] = assets[j];
+            }
+            depleted[j] = dep;
+            finished[j] = dep || last;
+            live[j] = !finished[j];
+            any |= live[j];
+        }
+        if (!any || t + 1 == max_steps) break;
+        // _price_transition of every asset, once for all rules of the lane
+        const uint32_t st = st0 + (uint32_t)t;
+        tsw_for<(NT + 1) / 2>(pairs, [&](int k) {
+            const int a = 2 * k;
+            double z0, z1 = 0.0;
+            if (tape) {
+                z0 = (double)tape[((size_t)t * n + a) * E + env];
+                if (a + 1 < n) z1 = (double)tape[((size_t)t * n + a + 1) * E + env];
+            } else {
+                trade_price_normals(R.seed, (uint32_t)env + R.env_off, st, pairs, k, z0, z1);   // an odd n discards the last z1
+            }
+            P(a) = trade_price_next(P(a), R.std_e, z0);
+            if (a + 1 < n) P(a + 1) = trade_price_next(P(a + 1), R.std_e, z1);       // NT is even: slot a + 1 exists
+        });
+    }
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) {
+        if (r0 + j < n_rules) {
+            const size_t o = (size_t)(r0 + j) * E + env;
+            O.total[o] = tot[j]; O.sum_sq[o] = ssq[j]; O.final_assets[o] = assets[j];
+            O.mn[o] = mn[j]; O.mx[o] = mx[j];
+            O.length[o] = length[j];
+            O.finished[o] = finished[j] ? 1 : 0;
+            O.depleted[o] = depleted[j] ? 1 : 0;
+        }
+    }
+}
+
+// rules per lane: 2 is the measured best of 1 / 2 / 4 at 9 rules x 1 024 steps x 8 192 envs (4.40 / 3.32 / 5.03 ms at 2 assets,
+// 28.2 / 18.7 / 25.6 ms at 16; profiles/trade_sweep_times.json): one rule per lane pays the float64 pow / exp of the price path
+// once per rule, four leave 3 of the 9 rules' slots idle in the ragged group and run at 256 registers.  At 4 096 envs and below
+// the pairs do not fill the SIMDs and 1 is faster (2.60 / 3.30 / 5.03 ms at 2 assets).  GRL_TRADE_SWEEP_RPL picks another for that
+// measurement and for the tests.  Every value gives the same bits.
+static int trade_sweep_rpl() {
+    const char *v = getenv("GRL_TRADE_SWEEP_RPL");
+    if (v && (v[0] == '1' || v[0] == '2' || v[0] == '4') && v[1] == 0) return v[0] - '0';
+    return 2;
+}
+
+static int trade_sweep_reserve(grl_handle *h, size_t n_rules, size_t pairs, size_t trace, size_t tape) {
+    TradeSweepState &w = h->tsw;
+    if (n_rules > w.cap_rules || pairs > w.cap_pairs || trace > w.cap_trace || tape > w.cap_tape) GRL_HIP(h, hipStreamSynchronize(h->stream));
+    int rc;
+    if (n_rules > w.cap_rules) {
+        w.cap_rules = 0;
+        if ((rc = grow(h, &w.gains, n_rules)) || (rc = grow(h, &w.biases, n_rules))) return rc;
+        w.cap_rules = n_rules;
+    }
+    if (pairs > w.cap_pairs) {
+        w.cap_pairs = 0;
+        if ((rc = grow(h, &w.total, pairs)) || (rc = grow(h, &w.sum_sq, pairs)) || (rc = grow(h, &w.final_assets, pairs)) ||
+            (rc = grow(h, &w.mn, pairs)) || (rc = grow(h, &w.mx, pairs)) || (rc = grow(h, &w.length, pairs)) ||
+            (rc = grow(h, &w.finished, pairs)) || (rc = grow(h, &w.depleted, pairs)))
+            return rc;
+        w.cap_pairs = pairs;
+    }
+    if (trace > w.cap_trace) {
+        w.cap_trace = 0;
+        if ((rc = grow(h, &w.trace_r, trace)) || (rc = grow(h, &w.trace_a, trace))) return rc;
+        w.cap_trace = trace;
+    }
+    if (tape > w.cap_tape) {
+        w.cap_tape = 0;
+        if ((rc = grow(h, &w.tape, tape))) return rc;
+        w.cap_tape = tape;
+    }
+    return GRL_OK;
+}
+
+template <int RPL>
+static int trade_sweep_launch(grl_handle *h, const TradeParams &R, int n_rules, const float *tape, int max_steps, int trace_env,
+                              const TradeSweepOut &O) {
+    const TradeSweepState &w = h->tsw;
+    const int n = R.n, groups = (n_rules + RPL - 1) / RPL;
+    int waves = 4;
+    size_t lds = 0;
+    void (*kern)(TradeParams, const float *, const float *, int, const float *, int, int, TradeSweepOut);
+    if (n <= 2) kern = trade_sweep_kernel<RPL, 2>;
+    else if (n <= 4) kern = trade_sweep_kernel<RPL, 4>;
+    else if (n <= 8) kern = trade_sweep_kernel<RPL, 8>;
+    else if (n <= 16) kern = trade_sweep_kernel<RPL, 16>;
+    else {
+        kern = trade_sweep_kernel<RPL, 0>;
+        const size_t per_wave = (size_t)(1 + RPL) * n * 64 * sizeof(double);       // at most 5 * 64 * 512 = 160 KB
+        waves = (int)std::min<size_t>(4, TSW_LDS_BYTES / per_wave);
+        lds = per_wave * waves;
+        GRL_HIP(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TSW_LDS_BYTES));
+    }
+    const dim3 grid((h->E + 63) / 64, (groups + waves - 1) / waves), block(64 * waves);
+    prof_begin(h);
+    hipLaunchKernelGGL(kern, grid, block, lds, h->stream, R, w.gains, w.biases, n_rules, tape, max_steps, trace_env, O);
+    prof_end(h);
+    GRL_HIP(h, hipGetLastError());
+    return GRL_OK;
+}
+
+}  // namespace grl
+
+using namespace grl;
+
+extern "C" {
+
+int grl_trade_sweep(grl_handle *h, const float *gains_host, const float *biases_host, int32_t n_rules, const float *normals_host,
+                    int32_t max_steps, int32_t trace_env) {
+    if (!h) return GRL_E_INVALID;
+    if (h->cfg.env_kind != GRL_ENV_TRADE) return fail(h, GRL_E_INVALID, "grl_trade_sweep: not a TradeAR1 handle");
+    if (!gains_host || !biases_host) return fail(h, GRL_E_INVALID, "grl_trade_sweep: null argument");
+    if (n_rules < 1 || n_rules > 4096) return fail(h, GRL_E_INVALID, "grl_trade_sweep: n_rules must be in 1..4096");
+    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_trade_sweep: max_steps must be at least 1");
+    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_trade_sweep: trace_env must be -1 or an env index");
+    for (int i = 0; i < n_rules; ++i)
+        if (!std::isfinite(gains_host[i]) || !std::isfinite(biases_host[i]))
+            return fail(h, GRL_E_INVALID, "grl_trade_sweep: rule " + std::to_string(i) + " has a non-finite gain or bias");
+    if (!normals_host && (h->cfg.flags & GRL_F_INJECT_NOISE))
+        return fail(h, GRL_E_INVALID, "grl_trade_sweep: a handle with GRL_F_INJECT_NOISE holds the normals of one step; pass a tape");
+    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_trade_sweep: a step is in flight (grl_wait first)");
+    hipSetDevice(h->cfg.device_id);
+    TradeSweepState &w = h->tsw;
+    w.n_rules = 0;
+    const size_t pairs = (size_t)n_rules * h->E, trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
+    const size_t tape = normals_host ? (size_t)max_steps * h->cfg.n_assets * h->E : 0;
+    int rc = trade_sweep_reserve(h, n_rules, pairs, trace, tape);
+    if (rc) return rc;
+    GRL_HIP(h, hipMemcpyAsync(w.gains, gains_host, (size_t)n_rules * 4, hipMemcpyHostToDevice, h->stream));
+    GRL_HIP(h, hipMemcpyAsync(w.biases, biases_host, (size_t)n_rules * 4, hipMemcpyHostToDevice, h->stream));
+    if (tape) {
+        GRL_HIP(h, hipMemcpyAsync(w.tape, normals_host, tape * 4, hipMemcpyHostToDevice, h->stream));
+        GRL_HIP(h, hipStreamSynchronize(h->stream));     // the tape is the caller's again when the call returns
+    }
+    if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
+        GRL_HIP(h, hipMemsetAsync(w.trace_r, 0, trace * 4, h->stream));
+        GRL_HIP(h, hipMemsetAsync(w.trace_a, 0, trace * 8, h->stream));
+    }
+    const TradeParams R = trade_params(h);
+    const TradeSweepOut O{w.total, w.sum_sq, w.final_assets, w.mn, w.mx, w.length, w.finished, w.depleted, w.trace_r, w.trace_a};
+    const float *tp = tape ? w.tape : nullptr;
+    const int rpl = trade_sweep_rpl();
+    if (rpl == 1) rc = trade_sweep_launch<1>(h, R, n_rules, tp, max_steps, trace_env, O);
+    else if (rpl == 2) rc = trade_sweep_launch<2>(h, R, n_rules, tp, max_steps, trace_env, O);
+    else rc = trade_sweep_launch<4>(h, R, n_rules, tp, max_steps, trace_env, O);
+    if (rc) return rc;
+    w.n_rules = n_rules; w.max_steps = max_steps; w.trace_env = trace_env;
+    return GRL_OK;
+}
+
+int grl_trade_sweep_read(grl_handle *h, const char *which, void *host, size_t bytes) {
+    if (!h) return GRL_E_INVALID;
+    if (h->cfg.env_kind != GRL_ENV_TRADE) return fail(h, GRL_E_INVALID, "grl_trade_sweep_read: not a TradeAR1 handle");
+    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_trade_sweep_read: null argument");
+    const TradeSweepState &w = h->tsw;
+    if (w.n_rules == 0) return fail(h, GRL_E_STATE, "grl_trade_sweep_read: call grl_trade_sweep first");
+    hipSetDevice(h->cfg.device_id);
+    const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
+    const std::string s(which);
+    const void *src = nullptr;
+    size_t need = 0;
+    if (s == "total") { src = w.total; need = pairs * 8; }
+    else if (s == "sum_sq") { src = w.sum_sq; need = pairs * 8; }
+    else if (s == "final_assets") { src = w.final_assets; need = pairs * 8; }
+    else if (s == "min") { src = w.mn; need = pairs * 4; }
+    else if (s == "max") { src = w.mx; need = pairs * 4; }
+    else if (s == "length") { src = w.length; need = pairs * 4; }
+    else if (s == "finished") { src = w.finished; need = pairs; }
+    else if (s == "depleted") { src = w.depleted; need = pairs; }
+    else if (s == "trace_rewards" || s == "trace_assets") {
+        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_trade_sweep_read: the last sweep traced no env (trace_env was -1)");
+        if (s == "trace_assets") { src = w.trace_a; need = trace * 8; }
+        else { src = w.trace_r; need = trace * 4; }
+    } else return fail(h, GRL_E_INVALID, "grl_trade_sweep_read: unknown output '" + s + "'");
+    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_trade_sweep_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
+    GRL_HIP(h, hipStreamSynchronize(h->stream));
+    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+    return GRL_OK;
+}
+
+}  // extern "C"

@@ -121,8 +121,28 @@ class _DeviceMonitor(object):
         eng.reset()
         return self.baseline_rate, self.baseline_total_reward
 
+    def rule_baseline(self, rules=None):
+        """The scripted trading-rule baseline (goldsrl/baselines.py) on the monitor's own TradeAR1 eval engine: resets it and plays
+        every (env, rule) pair in one kernel launch.  The engine's price generator moves on from one evaluation to the next, so call
+        this directly before eval_once: it then plays exactly the episodes that evaluation plays.  Keeps baseline_rule (index,
+        (gain, bias)), baseline_total_reward -- the best rule's mean over the envs of the episode's total reward, the unit of
+        eval/mean_total_reward -- and the whole statistics in baseline_stats; leaves the engine reset.  Returns
+        (rule_index, (gain, bias), baseline_total_reward)."""
+        from ... import _ffi
+        from ...baselines import DEFAULT_TRADE_RULES, TradingRuleBaseline
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_TRADE:
+            raise ValueError("the trading-rule baseline exists for the TradeAR1 env only")
+        b = TradingRuleBaseline(eng, DEFAULT_TRADE_RULES if rules is None else rules, self.max_episode_steps)
+        eng.reset()
+        self.baseline_stats = b.run()
+        i, rule, total = b.best_total()
+        self.baseline_rule, self.baseline_total_reward = (i, rule), total
+        return i, rule, total
+
     def write_baseline_scalars(self, global_step):
-        """eval/baseline_total_reward and eval/mean_total_reward_minus_baseline of the last evaluation (after baseline())"""
+        """eval/baseline_total_reward and eval/mean_total_reward_minus_baseline of the last evaluation (after baseline() or
+        rule_baseline())"""
         w = self.summary_writer
         if w is None or getattr(self, "baseline_total_reward", None) is None:
             return

@@ -6,7 +6,10 @@ A policy that does not beat the best constant rate has learned nothing about the
 the statistics, so they run without a device.
 
 ScriptedSwarmBaseline gives Swarm the same kind of yardstick: two do-nothing scripts played on a Swarm handle in one kernel launch
-(include/goldsrl_replay.h).  The reference has no counterpart of it."""
+(include/goldsrl_replay.h).  The reference has no counterpart of it.
+
+TradingRuleBaseline is TradeAR1's yardstick: a family of mean-reversion rules (gain, bias), every (env, rule) pair in one kernel
+launch (include/goldsrl_tradesweep.h).  The reference has no counterpart of it either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -119,3 +122,50 @@ class ScriptedSwarmBaseline(object):
         totals = self.stats["totals"][env]
         i = int(np.argmax(totals))
         return self.NAMES[i], float(totals[i])
+
+
+# (gain, bias): gains 0 .. 100 at bias 0 -- (0, 0) holds cash -- then fully invested in equal weights, the constant action 1
+DEFAULT_TRADE_RULES = np.array([(0, 0), (1, 0), (2, 0), (5, 0), (10, 0), (20, 0), (50, 0), (100, 0), (0, 1)], np.float32)
+
+
+def select_best_rule(rules, total):
+    """The rule with the largest mean over the envs of total (n_rules, E) -- the first one on a tie.  Returns
+    (rule_index, (gain, bias), that mean)."""
+    m = np.asarray(total, np.float64).mean(axis=1)
+    i = int(np.argmax(m))
+    return i, (float(rules[i][0]), float(rules[i][1])), float(m[i])
+
+
+class TradingRuleBaseline(object):
+    """Scripted trading rules on a TradeAR1 engine, every (env, rule) pair a whole episode in one kernel launch
+    (include/goldsrl_tradesweep.h).  A rule (gain, bias) trades asset a with the action clip(bias - gain * (p_a - 1), -1, 1): the
+    log price is an AR(1) around 0 (fed_env.py:296-298), so a positive gain buys what is cheap and sells what is dear; (0, 0) holds
+    cash and (0, b) is the constant action b.  A trader whose eval/total_reward does not beat the best rule has learned less than
+    one line of script.  The reference has no such baseline: this one is this build's own, like ScriptedSwarmBaseline.  run() plays
+    from the engine's CURRENT state and leaves it as it was; it does not reset -- the price generator's counters move on from one
+    episode to the next, so when to reset is the caller's affair."""
+
+    def __init__(self, engine, rules=DEFAULT_TRADE_RULES, max_episode_steps=None):
+        from . import _ffi
+        if engine.kind != _ffi.ENV_TRADE:
+            raise ValueError("the trading-rule baseline exists for the TradeAR1 env only")
+        self.eng = engine
+        self.rules = np.asarray(rules, np.float32)
+        if self.rules.ndim != 2 or self.rules.shape[1] != 2 or self.rules.shape[0] < 1:
+            raise ValueError("rules must be (n_rules, 2) of (gain, bias)")
+        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if self.max_episode_steps < 1:
+            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+        self.stats = None
+
+    def run(self, trace_env=None, normals=None):
+        """Play every (env, rule) pair; returns (and keeps) the statistics of _ffi_tradesweep.trade_sweep."""
+        from . import _ffi_tradesweep
+        self.stats = _ffi_tradesweep.trade_sweep(self.eng, self.rules, self.max_episode_steps, trace_env, normals)
+        return self.stats
+
+    def best_total(self):
+        """(rule_index, (gain, bias), mean over the envs of the episode's total reward) of the best rule."""
+        if self.stats is None:
+            self.run()
+        return select_best_rule(self.rules, self.stats["total"])

@@ -5,7 +5,9 @@ always_bootstrap off, learning rate 1e-4.  The reference's TradeWorker cannot ru
 reading (per-action mu and sigma, the raw draw stored and trained on, tanh to the env).  Scalars go to a
 TF-events file, the checkpoint to <model_dir>/checkpoint.npz.  With --eval-every N and --eval-envs M the PolicyMonitor of
 scripts/train_trade.py:94-124 runs on the device (goldsrl/agents/a3c/policy_monitor.py): every N updates M greedy episodes of
-`TradeAR1-v0` in one kernel launch, action tanh(mu); totals go to TradeAR1.json and the eval/* scalars."""
+`TradeAR1-v0` in one kernel launch, action tanh(mu); totals go to TradeAR1.json and the eval/* scalars.  With --baseline the
+scripted trading rules of goldsrl/baselines.py play the same episodes directly before every evaluation (one more launch): the best
+rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written.  Training is untouched."""
 import argparse
 import logging
 import os
@@ -33,6 +35,9 @@ def get_arg_parser():
     p.add_argument("--eval-every", "--eval_every", dest="eval_every", type=int, default=0,
                    help="evaluate the greedy policy every N updates (0: never)")
     p.add_argument("--eval-envs", "--eval_envs", dest="eval_envs", type=int, default=64, help="eval episodes per evaluation")
+    p.add_argument("--baseline", action="store_true",
+                   help="play the scripted trading rules on the eval envs directly before every evaluation (one kernel launch) and write "
+                        "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline (needs --eval-every and --eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -41,8 +46,16 @@ def get_arg_parser():
     return p
 
 
+def parse_args(argv=None):
+    parser = get_arg_parser()
+    args = parser.parse_args(argv)
+    if args.baseline and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
+    return args
+
+
 def main(argv=None):
-    args = get_arg_parser().parse_args(argv)
+    args = parse_args(argv)
     eng = _ffi.Engine(_ffi.ENV_TRADE, args.envs, device_id=args.device, seed=args.seed, n_assets=2, max_episode_steps=1024)
     eng.reset()
     eng.episodes_enable()
@@ -73,8 +86,13 @@ def main(argv=None):
             writer.add_scalar("episode/length", float(np.mean(eps["length"])), step)
         writer.add_scalar("perf/env_steps_per_s", args.envs * args.t_max / dt, step)
         if monitor is not None and ((u + 1) % args.eval_every == 0 or u + 1 == args.updates):
+            if args.baseline:       # the price generator moves on between evaluations: the rules must see this evaluation's prices
+                i, (gain, bias), total = monitor.rule_baseline()
+                logging.info("Trading-rule baseline on the eval envs: rule %d (gain %.6g, bias %.6g), mean total_reward %.6g", i, gain, bias, total)
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             monitor.write_scalars(step)
+            if args.baseline:
+                monitor.write_baseline_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
                          episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
