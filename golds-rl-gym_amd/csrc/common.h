@@ -84,6 +84,17 @@ struct TradeSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
+// buffers of grl_ticker_sweep (ticker_sweep.hip): allocated on first use, grown when a later sweep is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct TickerSweepState {
+    float *rules, *mn, *mx, *trace_r, *trace_act;        // (cap_rules,6) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
+    double *total, *sum_sq, *final_assets, *trace_a;     // (cap_pairs) (cap_pairs) (cap_pairs) (cap_trace)
+    int32_t *length, *trades;                            // (cap_pairs)
+    uint8_t *finished, *depleted;                        // (cap_pairs)
+    size_t cap_rules, cap_pairs, cap_trace;
+    int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
+};
+
 // buffers of grl_swarm_replay (swarm_replay.hip): allocated on first use, grown when a later replay is larger, listed in
 // grl_handle::allocs so grl_destroy frees them
 struct SwarmReplayState {
@@ -119,6 +130,7 @@ struct grl_handle {
     grl::SolowSweepState swp;
     grl::SwarmReplayState rpl;
     grl::TradeSweepState tsw;
+    grl::TickerSweepState ksw;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;
     // R6 episode bookkeeping (grl_episodes_*): nullptr until enabled

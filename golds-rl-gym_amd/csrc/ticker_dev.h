@@ -141,4 +141,79 @@ __device__ __forceinline__ TickerStepOut ticker_step_env(const TickerParams &K, 
     return out;
 }
 
+// ---- the account on values, for kernels that keep it in registers (ticker_sweep.hip).  ticker_step_env above is the form on the
+// handle's arrays; the two are held together bit for bit by tests/test_gpu_ticker_sweep.py.
+
+// a scripted rule (include/goldsrl_tickersweep.h): banded target weights with an optional trend switch, float64
+struct TickerRule {
+    double up0, up1, dn0, dn1, band;
+    int lookback;
+};
+
+// one asset of the rule: value v of the position, target weight t.  One IEEE operation per line.
+__device__ __forceinline__ void ticker_rule_asset(double v, double t, double band, double total, double cash, float &choice, float &fraction) {
+    const double s = v / total;
+    const double lo = t - band;
+    const double hi = t + band;
+    double f = 0.0;
+    choice = 0.f;
+    if (s < lo) {
+        choice = 1.f;
+        const double d = t - s;
+        const double w = d * total;
+        const double c = fmax(cash, 1e-12);
+        f = w / c;
+        f = fmin(f, 1.0);
+    } else if (s > hi) {
+        choice = 2.f;
+        const double d = s - t;
+        f = d / s;
+        f = fmin(f, 1.0);
+    }
+    fraction = (float)f;
+}
+
+// the rule's action on what the observation shows (cash, q, the prices the trade executes at) and the price `back`, lookback rows
+// before: (choice0, choice1, fraction0, fraction1)
+__device__ __forceinline__ float4 ticker_rule_action(const TickerRule &U, double cash, double q0, double q1, double p0, double p1, double back) {
+    const bool up = U.lookback == 0 || p0 >= back;
+    const double t0 = up ? U.up0 : U.dn0, t1 = up ? U.up1 : U.dn1;
+    const double v0 = q0 * p0;
+    const double v1 = q1 * p1;
+    const double hold = v0 + v1;
+    const double total = cash + hold;
+    float4 act;
+    ticker_rule_asset(v0, t0, U.band, total, cash, act.x, act.z);
+    ticker_rule_asset(v1, t1, U.band, total, cash, act.y, act.w);
+    return act;
+}
+
+// the trade and the equity of ticker_step_env (fed_env.py:110-130) for valid choices, in its operation order.  log_assets is
+// log(assets + 1e-4) of the account coming in, and of the account going out afterwards: the step's reward is their difference.
+__device__ __forceinline__ float ticker_account_step(const float4 act, double p0, double p1, double &cash, double &q0, double &q1,
+                                                     double &assets, double &log_assets) {
+    const int d0 = (int)act.x, d1 = (int)act.y;
+    double c0 = (double)act.z, c1 = (double)act.w;
+    const bool b0 = d0 == 1, b1 = d1 == 1, s0 = d0 == 2, s1 = d1 == 2;
+    const double bsum = (b0 && b1) ? c0 + c1 : (b0 ? c0 : (b1 ? c1 : 0.0));
+    const double denom = fmax(bsum, 1.0);
+    if (b0) c0 = c0 / denom;
+    if (b1) c1 = c1 / denom;
+    const double up = 1.0 + TICKER_SPREAD, dn = 1.0 - TICKER_SPREAD;
+    const double a0 = b0 ? c0 * cash / (p0 * up) : (s0 ? -c0 * q0 : 0.0);
+    const double a1 = b1 ? c1 * cash / (p1 * up) : (s1 ? -c1 * q1 : 0.0);
+    q0 = q0 + a0;
+    q1 = q1 + a1;
+    const double cb0 = a0 * p0 * up, cb1 = a1 * p1 * up;
+    const double cs0 = a0 * (p0 * dn), cs1 = a1 * (p1 * dn);
+    const double sb = (b0 && b1) ? cb0 + cb1 : (b0 ? cb0 : (b1 ? cb1 : 0.0));
+    const double ss = (s0 && s1) ? cs0 + cs1 : (s0 ? cs0 : (s1 ? cs1 : 0.0));
+    cash = cash + (-sb - ss);
+    assets = cash + (q0 * p0 + q1 * p1);
+    const double la = log(assets + 1e-4);
+    const double r = la - log_assets;
+    log_assets = la;
+    return (float)r;
+}
+
 }  // namespace grl

@@ -1,0 +1,205 @@
+// Scripted rule baseline sweep for the Ticker env: every (env, rule) pair plays a whole episode from the env's current state in
+// ONE launch (C ABI: include/goldsrl_tickersweep.h).
+//
+// Mapping: one lane per pair.  The lanes of a wave are consecutive envs of ONE rule, so the rule's six parameters are wave-uniform
+// and the (n_rules, E) outputs store coalesced; the four waves of a workgroup hold four rules of the same 64 envs.  The account
+// (cash, q0, q1, assets, log(assets + 1e-4)) and the statistics stay in registers.  No LDS, no barrier, no atomics, no workgroup
+// talks to another.  Unlike TradeAR1 the price path costs no pow / exp, only a 16-byte gather from a table that sits in L2, so
+// there is nothing for several rules per lane to share: one rule per lane is the only form built.
+//
+// The row addresses do not depend on the actions: the next step's row and its lookback price are asked for before the current
+// step's divide chain.  A step is played only while the window holds the row of the observation that follows it (idx <= 1022),
+// which is where the step path raises its window error; so the row asked for ahead (idx + 1 <= 1023) is always inside the window.
+//
+// The handle's state is read only: nothing here writes the account, idx / start / elapsed / episode / nhist, the outputs, the done
+// list, err_flag or the episode records.
+#include <math.h>
+
+#include "ticker_dev.h"
+#include "../../include/goldsrl_tickersweep.h"
+
+namespace grl {
+
+struct TickerSweepOut {
+    double *total, *sum_sq, *final_assets;
+    float *mn, *mx;
+    int32_t *length, *trades;
+    uint8_t *finished, *depleted;
+    float *trace_r;
+    double *trace_a;
+    float4 *trace_act;
+};
+
+__global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const float *__restrict__ rules, int n_rules, int max_steps,
+                                                           int trace_env, TickerSweepOut O) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int env = blockIdx.x * 64 + lane;
+    const int r = blockIdx.y * 4 + wave;                       // wave-uniform
+    if (r >= n_rules || env >= K.E) return;
+    TickerRule U;
+    U.up0 = (double)rules[r * 6 + 0]; U.up1 = (double)rules[r * 6 + 1]; U.dn0 = (double)rules[r * 6 + 2]; U.dn1 = (double)rules[r * 6 + 3];
+    U.band = (double)rules[r * 6 + 4]; U.lookback = (int)rules[r * 6 + 5];
+
+    int idx = max(0, min(K.idx[env], TICKER_WINDOW - 1));      // as ticker_step_env: keep the rows inside the table
+    const int st = max(0, min(K.start[env], K.rows - TICKER_WINDOW));
+    const double *win = K.table + (size_t)st * 4;
+    const int el0 = K.elapsed[env];
+    const double2 qq = reinterpret_cast<const double2 *>(K.q)[env];
+    double cash = K.cash[env], q0 = qq.x, q1 = qq.y, assets = K.assets[env];
+    double la = log(assets + 1e-4);
+    double tot = 0.0, ssq = 0.0;
+    float mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
+    int length = 0, trades = 0;
+    bool finished = false, depleted = false;
+    const bool trace = env == trace_env;
+    const size_t tr0 = (size_t)r * max_steps;
+
+    double2 pp = *reinterpret_cast<const double2 *>(win + (size_t)idx * 4);
+    double back = win[(size_t)max(idx - U.lookback, 0) * 4];
+    for (int t = 0; t < max_steps; ++t) {
+        if (idx >= TICKER_WINDOW - 1) break;                   // no row for the observation after this step: the window is played out
+        const double2 pn = *reinterpret_cast<const double2 *>(win + (size_t)(idx + 1) * 4);
+        const double bn = win[(size_t)max(idx + 1 - U.lookback, 0) * 4];
+        const float4 act = ticker_rule_action(U, cash, q0, q1, pp.x, pp.y, back);
+        const float rew = ticker_account_step(act, pp.x, pp.y, cash, q0, q1, assets, la);
+        tot += (double)rew;
+        ssq += (double)rew * (double)rew;
+        mn = fminf(mn, rew);
+        mx = fmaxf(mx, rew);
+        length = t + 1;
+        trades += (act.x != 0.f || act.y != 0.f) ? 1 : 0;
+        if (trace) {
+            O.trace_r[tr0 + t] = rew;
+            O.trace_a[tr0 + t] = assets;
+            O.trace_act[tr0 + t] = act;
+        }
+        depleted = assets < TICKER_MIN_CASH;
+        finished = depleted || (K.max_steps > 0 && el0 + t + 1 >= K.max_steps);
+        if (finished) break;
+        idx += 1;
+        pp = pn;
+        back = bn;
+    }
+    const size_t o = (size_t)r * K.E + env;
+    O.total[o] = tot; O.sum_sq[o] = ssq; O.final_assets[o] = assets;
+    O.mn[o] = mn; O.mx[o] = mx;
+    O.length[o] = length; O.trades[o] = trades;
+    O.finished[o] = finished ? 1 : 0;
+    O.depleted[o] = depleted ? 1 : 0;
+}
+
+static int ticker_sweep_reserve(grl_handle *h, size_t n_rules, size_t pairs, size_t trace) {
+    TickerSweepState &w = h->ksw;
+    if (n_rules > w.cap_rules || pairs > w.cap_pairs || trace > w.cap_trace) GRL_HIP(h, hipStreamSynchronize(h->stream));
+    int rc;
+    if (n_rules > w.cap_rules) {
+        w.cap_rules = 0;
+        if ((rc = grow(h, &w.rules, n_rules * 6))) return rc;
+        w.cap_rules = n_rules;
+    }
+    if (pairs > w.cap_pairs) {
+        w.cap_pairs = 0;
+        if ((rc = grow(h, &w.total, pairs)) || (rc = grow(h, &w.sum_sq, pairs)) || (rc = grow(h, &w.final_assets, pairs)) ||
+            (rc = grow(h, &w.mn, pairs)) || (rc = grow(h, &w.mx, pairs)) || (rc = grow(h, &w.length, pairs)) ||
+            (rc = grow(h, &w.trades, pairs)) || (rc = grow(h, &w.finished, pairs)) || (rc = grow(h, &w.depleted, pairs)))
+            return rc;
+        w.cap_pairs = pairs;
+    }
+    if (trace > w.cap_trace) {
+        w.cap_trace = 0;
+        if ((rc = grow(h, &w.trace_r, trace)) || (rc = grow(h, &w.trace_a, trace)) || (rc = grow(h, &w.trace_act, trace * 4))) return rc;
+        w.cap_trace = trace;
+    }
+    return GRL_OK;
+}
+
+// the first thing wrong with rule i, or nullptr
+static const char *ticker_rule_fault(const float *u, const char **field) {
+    static const char *names[6] = {"up0", "up1", "dn0", "dn1", "band", "lookback"};
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(u[k])) { *field = names[k]; return "is not finite"; }
+    for (int k = 0; k < 4; ++k)
+        if (u[k] < 0.f || u[k] > 1.f) { *field = names[k]; return "is a weight outside [0, 1]"; }
+    if ((double)u[0] + (double)u[1] > 1.0) { *field = "up0 + up1"; return "is above 1"; }
+    if ((double)u[2] + (double)u[3] > 1.0) { *field = "dn0 + dn1"; return "is above 1"; }
+    if (u[4] < 0.f) { *field = names[4]; return "is negative"; }
+    if (u[5] < 0.f || u[5] > (float)(TICKER_WINDOW - 1) || u[5] != floorf(u[5])) { *field = names[5]; return "is not an integer in 0..1023"; }
+    return nullptr;
+}
+
+}  // namespace grl
+
+using namespace grl;
+
+extern "C" {
+
+int grl_ticker_sweep(grl_handle *h, const float *rules_host, int32_t n_rules, int32_t max_steps, int32_t trace_env) {
+    if (!h) return GRL_E_INVALID;
+    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: not a Ticker handle");
+    if (!rules_host) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: null argument");
+    if (!h->tk.table) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: the handle has no price table yet (grl_ticker_set_table first)");
+    if (n_rules < 1 || n_rules > 4096) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: n_rules must be in 1..4096");
+    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: max_steps must be at least 1");
+    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: trace_env must be -1 or an env index");
+    for (int i = 0; i < n_rules; ++i) {
+        const char *field = nullptr, *what = ticker_rule_fault(rules_host + (size_t)i * 6, &field);
+        if (what) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: rule " + std::to_string(i) + ": " + field + " " + what);
+    }
+    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: a step is in flight (grl_wait first)");
+    hipSetDevice(h->cfg.device_id);
+    TickerSweepState &w = h->ksw;
+    w.n_rules = 0;
+    const size_t pairs = (size_t)n_rules * h->E, trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
+    int rc = ticker_sweep_reserve(h, n_rules, pairs, trace);
+    if (rc) return rc;
+    GRL_HIP(h, hipMemcpyAsync(w.rules, rules_host, (size_t)n_rules * 6 * 4, hipMemcpyHostToDevice, h->stream));
+    if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
+        GRL_HIP(h, hipMemsetAsync(w.trace_r, 0, trace * 4, h->stream));
+        GRL_HIP(h, hipMemsetAsync(w.trace_a, 0, trace * 8, h->stream));
+        GRL_HIP(h, hipMemsetAsync(w.trace_act, 0, trace * 16, h->stream));
+    }
+    const TickerParams K = ticker_params(h);
+    const TickerSweepOut O{w.total, w.sum_sq, w.final_assets, w.mn, w.mx, w.length, w.trades, w.finished, w.depleted, w.trace_r, w.trace_a,
+                           reinterpret_cast<float4 *>(w.trace_act)};
+    const dim3 grid((h->E + 63) / 64, (n_rules + 3) / 4), block(256);
+    prof_begin(h);
+    hipLaunchKernelGGL(ticker_sweep_kernel, grid, block, 0, h->stream, K, w.rules, n_rules, max_steps, trace_env, O);
+    prof_end(h);
+    GRL_HIP(h, hipGetLastError());
+    w.n_rules = n_rules; w.max_steps = max_steps; w.trace_env = trace_env;
+    return GRL_OK;
+}
+
+int grl_ticker_sweep_read(grl_handle *h, const char *which, void *host, size_t bytes) {
+    if (!h) return GRL_E_INVALID;
+    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_ticker_sweep_read: not a Ticker handle");
+    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_ticker_sweep_read: null argument");
+    const TickerSweepState &w = h->ksw;
+    if (w.n_rules == 0) return fail(h, GRL_E_STATE, "grl_ticker_sweep_read: call grl_ticker_sweep first");
+    hipSetDevice(h->cfg.device_id);
+    const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
+    const std::string s(which);
+    const void *src = nullptr;
+    size_t need = 0;
+    if (s == "total") { src = w.total; need = pairs * 8; }
+    else if (s == "sum_sq") { src = w.sum_sq; need = pairs * 8; }
+    else if (s == "final_assets") { src = w.final_assets; need = pairs * 8; }
+    else if (s == "min") { src = w.mn; need = pairs * 4; }
+    else if (s == "max") { src = w.mx; need = pairs * 4; }
+    else if (s == "length") { src = w.length; need = pairs * 4; }
+    else if (s == "trades") { src = w.trades; need = pairs * 4; }
+    else if (s == "finished") { src = w.finished; need = pairs; }
+    else if (s == "depleted") { src = w.depleted; need = pairs; }
+    else if (s == "trace_rewards" || s == "trace_assets" || s == "trace_actions") {
+        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_ticker_sweep_read: the last sweep traced no env (trace_env was -1)");
+        if (s == "trace_assets") { src = w.trace_a; need = trace * 8; }
+        else if (s == "trace_actions") { src = w.trace_act; need = trace * 16; }
+        else { src = w.trace_r; need = trace * 4; }
+    } else return fail(h, GRL_E_INVALID, "grl_ticker_sweep_read: unknown output '" + s + "'");
+    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_ticker_sweep_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
+    GRL_HIP(h, hipStreamSynchronize(h->stream));
+    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
+    return GRL_OK;
+}
+
+}  // extern "C"

@@ -220,6 +220,22 @@ class GatedPolicyMonitor(_DeviceMonitor):
             net = _ffi_gated.GatedNet(eng, rnn_length=max_seq_length, scale=scale, max_samples=1)
         self._adopt(net, own, summary_writer, max_episode_steps)
 
+    def ticker_baseline(self, rules=None):
+        """The scripted rule baseline (goldsrl/baselines.py:TickerRuleBaseline) on the monitor's own Ticker eval engine: resets it
+        and plays every (env, rule) pair in one kernel launch.  The eval engine is reseeded at every reset, so every evaluation
+        plays these price windows: one run before the first update serves them all.  Keeps baseline_rule (index, the six
+        parameters), baseline_total_reward -- the best rule's mean over the envs of the episode's total reward, the unit of
+        eval/mean_total_reward -- and the whole statistics in baseline_stats; leaves the engine reset.  Returns
+        (rule_index, the six parameters, baseline_total_reward)."""
+        from ...baselines import DEFAULT_TICKER_RULES, TickerRuleBaseline
+        eng = self.net.eng
+        b = TickerRuleBaseline(eng, DEFAULT_TICKER_RULES if rules is None else rules, self.max_episode_steps)
+        eng.reset()
+        self.baseline_stats = b.run()
+        i, rule, total = b.best_total()
+        self.baseline_rule, self.baseline_total_reward = (i, rule), total
+        return i, rule, total
+
 
 class GridPolicyMonitor(_DeviceMonitor):
     """The PolicyMonitor of the discrete savings-grid agent.  env: the Solow eval registration's id.  n_grid, lb, ub: the

@@ -9,7 +9,11 @@ ScriptedSwarmBaseline gives Swarm the same kind of yardstick: two do-nothing scr
 (include/goldsrl_replay.h).  The reference has no counterpart of it.
 
 TradingRuleBaseline is TradeAR1's yardstick: a family of mean-reversion rules (gain, bias), every (env, rule) pair in one kernel
-launch (include/goldsrl_tradesweep.h).  The reference has no counterpart of it either."""
+launch (include/goldsrl_tradesweep.h).  The reference has no counterpart of it either.
+
+TickerRuleBaseline is the Ticker env's yardstick: banded target-weight rules with an optional trend switch -- hold cash, buy and
+hold, a constant mix, follow the trend --, every (env, rule) pair in one kernel launch (include/goldsrl_tickersweep.h).  No
+counterpart in the reference either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -169,3 +173,60 @@ class TradingRuleBaseline(object):
         if self.stats is None:
             self.run()
         return select_best_rule(self.rules, self.stats["total"])
+
+
+def _ticker_rules():
+    rows = [(0, 0, 0, 0, 1, 0), (1, 0, 1, 0, 0.5, 0), (0, 1, 0, 1, 0.5, 0)]
+    rows += [(0.5, 0.5, 0.5, 0.5, b, 0) for b in (0.25, 0.05, 0.01)]
+    rows += [(1, 0, 0, 1, 0.5, L) for L in (2, 8, 32, 128)]
+    rows += [(1, 0, 0, 0, 0.5, L) for L in (8, 32)]
+    return np.array(rows, np.float32)
+
+
+# (up0, up1, dn0, dn1, band, lookback): hold cash; buy and hold the asset; buy and hold the inverse asset; the equal mix rebalanced
+# outside a band of 0.25 / 0.05 / 0.01; the asset while the price is at or above its value L rows ago and the inverse asset
+# otherwise, L = 2 / 8 / 32 / 128; the same going to cash, L = 8 / 32
+DEFAULT_TICKER_RULES = _ticker_rules()
+
+
+def select_best_ticker_rule(rules, total):
+    """select_best_rule for six-parameter rules: the rule with the largest mean over the envs of total (n_rules, E) -- the first
+    one on a tie.  Returns (rule_index, (up0, up1, dn0, dn1, band, lookback), that mean)."""
+    m = np.asarray(total, np.float64).mean(axis=1)
+    i = int(np.argmax(m))
+    return i, tuple(float(v) for v in rules[i]), float(m[i])
+
+
+class TickerRuleBaseline(object):
+    """Scripted rules on a Ticker engine, every (env, rule) pair a whole episode in one kernel launch
+    (include/goldsrl_tickersweep.h).  A rule (up0, up1, dn0, dn1, band, lookback) holds target weights of the two assets -- (up0,
+    up1) while the price is at or above its value `lookback` rows ago (always, with lookback 0), (dn0, dn1) otherwise -- and trades
+    an asset only when its share of the account leaves the band around its target.  The env charges a 0.6 % spread on every trade:
+    holding cash totals exactly 0, buying once earns the drift of the window, whatever trades often pays the spread.  A trader
+    whose eval/mean_total_reward is below the best rule has learned less than "buy at step 0 and wait".  The reference has no such
+    baseline: this one is this build's own, like TradingRuleBaseline.  run() plays from the engine's CURRENT state and leaves it as
+    it was; it does not reset."""
+
+    def __init__(self, engine, rules=DEFAULT_TICKER_RULES, max_episode_steps=None):
+        from . import _ffi
+        from ._ffi_tickersweep import check_ticker_rules
+        if engine.kind != _ffi.ENV_TICKER:
+            raise ValueError("the Ticker rule baseline exists for the Ticker env only")
+        self.eng = engine
+        self.rules = check_ticker_rules(rules)
+        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if self.max_episode_steps < 1:
+            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+        self.stats = None
+
+    def run(self, trace_env=None):
+        """Play every (env, rule) pair; returns (and keeps) the statistics of _ffi_tickersweep.ticker_sweep."""
+        from . import _ffi_tickersweep
+        self.stats = _ffi_tickersweep.ticker_sweep(self.eng, self.rules, self.max_episode_steps, trace_env)
+        return self.stats
+
+    def best_total(self):
+        """(rule_index, the six parameters, mean over the envs of the episode's total reward) of the best rule."""
+        if self.stats is None:
+            self.run()
+        return select_best_ticker_rule(self.rules, self.stats["total"])

@@ -4,7 +4,11 @@ from a CSV (columns Open, Close, Volume) or a --table .npz (Open / Close / Volum
 through the sampler of goldsrl.envs.data; scalars go to a TF-events file, the checkpoint to <out>/checkpoint.npz.  With --eval-envs M
 the GatedPolicyMonitor (goldsrl/agents/a3c/policy_monitor.py) plays, every --eval-every updates and after the last one, M greedy
 episodes in one kernel launch on --eval-csv / --eval-table (a held-out price table; default: the training table): per asset the
-most probable choice with mu of that choice.  Totals go to <out>/Ticker.json and the eval/* scalars."""
+most probable choice with mu of that choice.  Totals go to <out>/Ticker.json and the eval/* scalars.  With --baseline the scripted
+rules of goldsrl/baselines.py (hold cash, buy and hold, a constant mix, follow the trend) play the eval envs' price windows once
+before the first update (one launch; the eval engine is reseeded at every reset, so every evaluation plays these windows): the best
+rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written at every evaluation.  Training is
+untouched."""
 import argparse
 import logging
 import os
@@ -40,6 +44,9 @@ def get_arg_parser():
     p.add_argument("--eval-envs", "--eval_envs", dest="eval_envs", type=int, default=0,
                    help="greedy eval episodes per evaluation (0: no evaluation)")
     p.add_argument("--eval-every", "--eval_every", dest="eval_every", type=int, default=10, help="evaluate every N updates")
+    p.add_argument("--baseline", action="store_true",
+                   help="play the scripted rules on the eval envs before the first update (one kernel launch) and write "
+                        "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline at every evaluation (needs --eval-envs)")
     ev = p.add_mutually_exclusive_group()
     ev.add_argument("--eval-csv", "--eval_csv", dest="eval_csv", help="held-out price table CSV for the evaluation")
     ev.add_argument("--eval-table", "--eval_table", dest="eval_table", help="held-out price table .npz for the evaluation")
@@ -55,8 +62,16 @@ def load_table(args, csv=None, table=None):
         return OpenCloseSampler(table={"Open": z[keys[0]], "Close": z[keys[1]], "Volume": z[keys[2]]})
 
 
+def parse_args(argv=None):
+    parser = get_arg_parser()
+    args = parser.parse_args(argv)
+    if args.baseline and args.eval_envs <= 0:
+        parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs M > 0")
+    return args
+
+
 def main(argv=None):
-    args = get_arg_parser().parse_args(argv)
+    args = parse_args(argv)
     sampler = load_table(args)
     eng = _ffi.Engine(_ffi.ENV_TICKER, args.envs, device_id=args.device, seed=args.seed)
     eng.ticker_set_table(sampler.data_matrix)
@@ -78,6 +93,10 @@ def main(argv=None):
         held_out = load_table(args, args.eval_csv, args.eval_table) if args.eval_csv or args.eval_table else sampler
         monitor = GatedPolicyMonitor(held_out, summary_writer=writer, n_envs=args.eval_envs, max_seq_length=args.rnn_length,
                                      scale=args.scale, device_id=args.device)
+        if args.baseline:
+            i, rule, total = monitor.ticker_baseline()
+            logging.info("Ticker rule baseline on the eval envs: rule %d (up %.6g %.6g, down %.6g %.6g, band %.6g, lookback %d), "
+                         "mean total_reward %.6g", i, rule[0], rule[1], rule[2], rule[3], rule[4], int(rule[5]), total)
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.steps)
@@ -94,6 +113,8 @@ def main(argv=None):
         if monitor is not None and ((u + 1) % args.eval_every == 0 or u + 1 == args.updates):
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             monitor.write_scalars(step)
+            if args.baseline:
+                monitor.write_baseline_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
                          episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
