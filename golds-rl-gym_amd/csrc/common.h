@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/goldsrl.h"
+#include "../../include/goldsrl_solowdp.h"
 
 namespace grl {
 
@@ -95,6 +96,24 @@ struct TickerSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
+// tables and buffers of grl_solow_dp_* (solow_dp.hip): allocated on first use, grown when a later call is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct SolowDpState {
+    grl_solow_dp_grid grid;                       // of the table in `policy`
+    double rho, theta;                            // the model the last solve used
+    double *v[2];                                 // (cap_states) each; stage t's value is in v[t & 1]
+    float *policy;                                // (cap_table): (horizon, nk, nz, ne)
+    size_t cap_states, cap_table;
+    int horizon, ne;                              // horizon == 0: no table yet
+    bool has_value;                               // v[0] holds stage 0's value (a solve, not a set_policy)
+    double *total, *sum_sq;                       // (cap_envs)
+    float *mn, *mx, *trace_a, *trace_r, *trace_k; // (cap_envs) (cap_envs) (cap_trace) x 3
+    int32_t *length, *err;                        // (cap_envs) (1)
+    uint8_t *finished;                            // (cap_envs)
+    size_t cap_envs, cap_trace;
+    int played, trace_steps;                      // of the last play; played == 0: none yet
+};
+
 // buffers of grl_swarm_replay (swarm_replay.hip): allocated on first use, grown when a later replay is larger, listed in
 // grl_handle::allocs so grl_destroy frees them
 struct SwarmReplayState {
@@ -131,6 +150,7 @@ struct grl_handle {
     grl::SwarmReplayState rpl;
     grl::TradeSweepState tsw;
     grl::TickerSweepState ksw;
+    grl::SolowDpState sdp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;
     // R6 episode bookkeeping (grl_episodes_*): nullptr until enabled

@@ -121,6 +121,22 @@ class _DeviceMonitor(object):
         eng.reset()
         return self.baseline_rate, self.baseline_total_reward
 
+    def optimal(self, grid=None, horizon=None):
+        """The optimal-savings yardstick (goldsrl/baselines.py:OptimalSavingsBaseline) on the monitor's own eval engine, so it plays
+        exactly the seeded episodes the policy is evaluated on: the backward induction (one launch per stage), then every env's
+        episode in one launch.  Keeps optimal_total_reward -- the mean over the envs of the episode's total reward, the unit of
+        eval/mean_total_reward -- and the whole statistics in optimal_stats; leaves the engine reset.  Returns the figure."""
+        from ... import _ffi
+        from ...baselines import OptimalSavingsBaseline
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_SOLOW:
+            raise ValueError("the optimal-savings yardstick exists for the Solow env only")
+        b = OptimalSavingsBaseline(grid=grid, horizon=horizon, max_episode_steps=self.max_episode_steps, engine=eng)
+        self.optimal_stats = b.run()
+        self.optimal_total_reward = b.total()
+        eng.reset()
+        return self.optimal_total_reward
+
     def rule_baseline(self, rules=None):
         """The scripted trading-rule baseline (goldsrl/baselines.py) on the monitor's own TradeAR1 eval engine: resets it and plays
         every (env, rule) pair in one kernel launch.  The engine's price generator moves on from one evaluation to the next, so call
@@ -142,13 +158,20 @@ class _DeviceMonitor(object):
 
     def write_baseline_scalars(self, global_step):
         """eval/baseline_total_reward and eval/mean_total_reward_minus_baseline of the last evaluation (after baseline() or
-        rule_baseline())"""
+        rule_baseline()); after optimal() also eval/optimal_total_reward and, with both ends known,
+        eval/mean_total_reward_share_of_gap = (mean - baseline) / (optimal - baseline)"""
         w = self.summary_writer
-        if w is None or getattr(self, "baseline_total_reward", None) is None:
+        floor, ceiling = getattr(self, "baseline_total_reward", None), getattr(self, "optimal_total_reward", None)
+        if w is None or (floor is None and ceiling is None):
             return
-        w.add_scalar("eval/baseline_total_reward", self.baseline_total_reward, global_step)
-        if self.log["mean_total_reward"]:
-            w.add_scalar("eval/mean_total_reward_minus_baseline", self.log["mean_total_reward"][-1] - self.baseline_total_reward, global_step)
+        if floor is not None:
+            w.add_scalar("eval/baseline_total_reward", floor, global_step)
+            if self.log["mean_total_reward"]:
+                w.add_scalar("eval/mean_total_reward_minus_baseline", self.log["mean_total_reward"][-1] - floor, global_step)
+        if ceiling is not None:
+            w.add_scalar("eval/optimal_total_reward", ceiling, global_step)
+            if floor is not None and self.log["mean_total_reward"] and ceiling != floor:
+                w.add_scalar("eval/mean_total_reward_share_of_gap", (self.log["mean_total_reward"][-1] - floor) / (ceiling - floor), global_step)
         w.flush()
 
     def write_log(self, total_reward_log_file):

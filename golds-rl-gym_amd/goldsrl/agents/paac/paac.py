@@ -64,6 +64,9 @@ class PAACLearner(ActorLearner):
         baseline = bool(getattr(self, "baseline", False))
         if baseline:
             logging.info("Constant-savings baseline on the eval envs: rate %.6g, mean total_reward %.6g", *self.policy_monitor.baseline())
+        optimal = bool(getattr(self, "optimal", False))
+        if optimal:
+            logging.info("Optimal savings policy on the eval envs: mean total_reward %.6g", self.policy_monitor.optimal())
         every_updates = int(getattr(self, "eval_updates", 0) or 0)
         every_seconds = float(getattr(self, "eval_every", 0.0) or 0.0)
         state = {"last_eval": time.time()}
@@ -75,7 +78,7 @@ class PAACLearner(ActorLearner):
                 due = every_seconds > 0 and time.time() - state["last_eval"] >= every_seconds
             if due:
                 self.policy_monitor.eval_once()
-                if baseline:
+                if baseline or optimal:
                     self.policy_monitor.write_baseline_scalars(int(self.global_step))
                 state["last_eval"] = time.time()
         return between_updates

@@ -5,6 +5,10 @@ ConstantSavingsBaseline is the reference's scripts/constant_solow.py on the devi
 A policy that does not beat the best constant rate has learned nothing about the shocks.  The selection rules are pure functions of
 the statistics, so they run without a device.
 
+OptimalSavingsBaseline is the other end of Solow's scale: the finite-horizon optimum by backward induction on a (k, z, e) grid, one
+kernel launch per stage, and the play of the tabulated policy on the same seeded episodes (include/goldsrl_solowdp.h).  The gap
+between the two is what there was to learn.  The reference has no counterpart of it.
+
 ScriptedSwarmBaseline gives Swarm the same kind of yardstick: two do-nothing scripts played on a Swarm handle in one kernel launch
 (include/goldsrl_replay.h).  The reference has no counterpart of it.
 
@@ -83,6 +87,63 @@ class ConstantSavingsBaseline(object):
     def best_total(self):
         """(rate, mean over the envs of the episode's total reward) of the best rate."""
         return select_best_total(self.rates, self._stats()["total"])
+
+    def close(self):
+        if self._own and self.eng is not None:
+            self.eng.close()
+        self.eng = None
+
+
+class OptimalSavingsBaseline(object):
+    """The optimal savings policy of a Solow engine with p = 1 and q in {0, 1}: solved once by backward induction on `grid` (a dict
+    of _ffi_solowdp.solow_dp_grid; default 96 x 25 x 7 with 96 actions at the engine's sigma) over `horizon` stages (default 256),
+    then played on every env from its reset state.  With more steps left than the horizon the policy of stage 0 is used: the
+    stationary rule the induction converges to.  engine: a Solow engine to run on (the caller keeps it) instead of building the eval
+    registration's; run() resets it."""
+
+    def __init__(self, env="Solow-1-1-finite-eval-v0", n_envs=1, grid=None, horizon=None, device_id=0, max_episode_steps=1024, engine=None):
+        from . import _ffi_solowdp
+        self.horizon = _ffi_solowdp.DEFAULT_HORIZON if horizon is None else int(horizon)
+        if self.horizon < 1:
+            raise ValueError("horizon must be at least 1")
+        self.max_episode_steps = int(max_episode_steps)
+        self._own = engine is None
+        if engine is None:
+            from .agents.a3c.policy_monitor import make_eval_engine
+            if not env.startswith("Solow-"):
+                raise ValueError("the optimal-savings yardstick exists for the Solow env only (got %r)" % (env,))
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            engine = make_eval_engine(env, n_envs, device_id, self.max_episode_steps)
+        else:
+            from . import _ffi
+            if engine.kind != _ffi.ENV_SOLOW:
+                raise ValueError("the optimal-savings yardstick exists for the Solow env only")
+        self.eng = engine
+        self.grid = _ffi_solowdp.solow_dp_grid(sigma=engine.cfg.solow_sigma) if grid is None else grid
+        self.solved, self.stats = False, None
+
+    def solve(self):
+        """The backward induction (once per object); the engine keeps the tables."""
+        from . import _ffi_solowdp
+        if not self.solved:
+            _ffi_solowdp.solow_dp_solve(self.eng, self.grid, self.horizon, read=False)
+            self.solved = True
+
+    def run(self, trace_steps=0):
+        """Solve if not yet solved, reset the envs and play the policy; returns (and keeps) the statistics of
+        _ffi_solowdp.solow_dp_play."""
+        from . import _ffi_solowdp
+        self.solve()
+        self.eng.reset()
+        self.stats = _ffi_solowdp.solow_dp_play(self.eng, self.max_episode_steps, trace_steps)
+        return self.stats
+
+    def total(self):
+        """The mean over the envs of the episode's total reward: the unit of eval/mean_total_reward."""
+        if self.stats is None:
+            self.run()
+        return float(np.asarray(self.stats["total"], np.float64).mean())
 
     def close(self):
         if self._own and self.eng is not None:

@@ -40,6 +40,9 @@ def get_arg_parser():
     p.add_argument('--eval-envs', default=0, type=int, dest="eval_envs",
                    help="envs of Solow-1-1-finite-eval-v0 evaluated on the device between updates (paac.py:63-77), one launch per "
                         "evaluation; 0: no evaluation")
+    p.add_argument('--optimal', action='store_true',
+                   help="solve the optimal savings policy by backward induction and play it on the eval envs before the first update; write "
+                        "eval/optimal_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap at every evaluation (needs --eval-envs)")
     p.add_argument('--eval-updates', default=0, type=int, dest="eval_updates",
                    help="evaluate after every K-th update; 0: when --eval-every seconds have passed")
     p.add_argument('--true-history', action='store_true', dest="true_history",
@@ -55,6 +58,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.baseline and args.eval_envs <= 0:
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs N > 0")
+    if args.optimal and args.eval_envs <= 0:
+        parser.error("--optimal plays the eval envs of the device monitor: it needs --eval-envs N > 0")
     return args
 
 

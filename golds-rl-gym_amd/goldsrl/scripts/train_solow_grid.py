@@ -39,6 +39,9 @@ def get_arg_parser():
     p.add_argument("--baseline", action="store_true",
                    help="play the constant-savings baseline on the eval envs before the first update (one kernel launch) and write "
                         "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline at every evaluation (needs --eval-envs)")
+    p.add_argument("--optimal", action="store_true",
+                   help="solve the optimal savings policy by backward induction and play it on the eval envs before the first update; write "
+                        "eval/optimal_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap at every evaluation (needs --eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -52,6 +55,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.baseline and not (args.eval_envs > 0 and args.eval_every > 0):
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs N > 0 (and --eval-every > 0)")
+    if args.optimal and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--optimal plays the eval envs of the device monitor: it needs --eval-envs N > 0 (and --eval-every > 0)")
     return args
 
 
@@ -76,6 +81,8 @@ def main(argv=None):
                                     n_grid=args.n_grid, max_seq_length=MAX_SEQ_LENGTH, scale=SCALE, device_id=args.device)
     if args.baseline:
         logging.info("Constant-savings baseline on the eval envs (the agent's grid): rate %.6g, mean total_reward %.6g", *monitor.baseline())
+    if args.optimal:
+        logging.info("Optimal savings policy on the eval envs: mean total_reward %.6g", monitor.optimal())
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.t_max)
@@ -92,7 +99,7 @@ def main(argv=None):
         if monitor is not None and ((u + 1) % args.eval_every == 0 or u + 1 == args.updates):
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             monitor.write_scalars(step)
-            if args.baseline:
+            if args.baseline or args.optimal:
                 monitor.write_baseline_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d", step, total_reward, episode_length)
