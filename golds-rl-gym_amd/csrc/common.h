@@ -125,6 +125,18 @@ struct SwarmReplayState {
     int n_seq, max_steps, trace_env;              // of the last replay; n_seq == 0: none yet
 };
 
+// buffers of grl_swarm_rules (swarm_rules.hip): allocated on first use, grown when a later run is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct SwarmRulesState {
+    double *rules, *offsets;                      // (cap_rules,3) (cap_rules,10,2)
+    double *rewards, *actions;                    // (cap_steps) (cap_act,10,2)
+    double *trace_x, *trace_xa;                   // (cap_trace,80,2) (cap_trace,10,2)
+    int32_t *length;                              // (cap_pairs)
+    uint8_t *finished;                            // (cap_pairs)
+    size_t cap_rules, cap_steps, cap_pairs, cap_act, cap_trace;
+    int n_rules, max_steps, trace_env, keep_actions;   // of the last run; n_rules == 0: none yet
+};
+
 }  // namespace grl
 
 struct grl_handle {
@@ -148,6 +160,7 @@ struct grl_handle {
     grl::TickerState tk;
     grl::SolowSweepState swp;
     grl::SwarmReplayState rpl;
+    grl::SwarmRulesState srl;
     grl::TradeSweepState tsw;
     grl::TickerSweepState ksw;
     grl::SolowDpState sdp;

@@ -20,6 +20,7 @@ class ActorLearner(object):
         self.true_history = getattr(args, 'true_history', False)        # the flat net under the true history window (--true-history)
         self.eval_updates = getattr(args, 'eval_updates', 0)            # > 0: evaluate after every eval_updates-th update, 0: by eval_every
         self.baseline = getattr(args, 'baseline', False)                # the baseline beside the evaluation (--baseline): constant savings for Solow, scripted drift / hold for Swarm
+        self.rule_baseline = getattr(args, 'rule_baseline', False)      # the feedback-rule baseline beside the evaluation (--rule-baseline, Swarm)
         self.optimal = getattr(args, 'optimal', False)                  # the optimal-savings yardstick beside the evaluation (--optimal, Solow)
         self.checkpoint_every = getattr(args, 'checkpoint_every', 0)    # updates between flat-weights checkpoints (0: never)
         self.checkpoint_path = getattr(args, 'checkpoint_path', 'checkpoint.npz')

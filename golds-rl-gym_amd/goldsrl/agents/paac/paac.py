@@ -199,6 +199,8 @@ class GridPAACLearner(PAACLearner):
                                     learner=self)
             if bool(getattr(self, "baseline", False)):
                 logging.info("Scripted baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.baseline())
+            if bool(getattr(self, "rule_baseline", False)):      # after --baseline: with both, the rule baseline is the one written
+                logging.info("Feedback-rule baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.rule_baseline())
         state = {"last_eval": last_eval}
 
         def between_updates(counter):

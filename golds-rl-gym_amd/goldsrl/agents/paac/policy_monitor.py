@@ -14,6 +14,7 @@ import time
 
 import numpy as np
 
+from ...baselines import DEFAULT_SWARM_RULES
 from ..a3c.policy_monitor import _DeviceMonitor
 from .emulator_runner import SolowRunner, SwarmRunner
 from .policy_v_network import ConvSingleAgentPolicyNetwork, FlatPolicyVNetwork
@@ -252,5 +253,23 @@ class SwarmPolicyMonitor(PolicyMonitor):
         b = ScriptedSwarmBaseline(self.env._eng)
         self.baseline_stats = b.run()
         self.baseline_name, self.baseline_total_reward = b.best(0)
+        self.env.reset()
+        return self.baseline_name, self.baseline_total_reward
+
+    def rule_baseline(self, rules=DEFAULT_SWARM_RULES):
+        """The feedback-rule baseline (goldsrl/baselines.py:SwarmRuleBaseline) on the monitor's own eval env: the env is reset, every
+        rule plays the seeded episode in one kernel launch, and the env is reset again.  Keeps baseline_name (the best rule, spelled
+        out), baseline_rule (its index and six numbers), baseline_total_reward (every later eval_once writes
+        eval/baseline_total_reward and eval/total_reward_minus_baseline) and the whole outputs in baseline_stats, replacing what
+        baseline() kept.  Returns (baseline_name, baseline_total_reward).  The reference has no counterpart."""
+        from ...baselines import SwarmRuleBaseline
+        self.env.reset()
+        b = SwarmRuleBaseline(self.env._eng, rules)
+        self.baseline_stats = b.run()
+        i, six, total = b.best_total()
+        self.baseline_rule = (i, six)
+        self.baseline_name = "rule %d (cancel %g, gain %g, anchor %s, offset (%g, %g), radius %g)" % (
+            (i, six[0], six[1], "nearest locust" if six[2] else "centroid") + six[3:])
+        self.baseline_total_reward = total
         self.env.reset()
         return self.baseline_name, self.baseline_total_reward

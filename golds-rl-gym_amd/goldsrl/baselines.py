@@ -17,7 +17,11 @@ launch (include/goldsrl_tradesweep.h).  The reference has no counterpart of it e
 
 TickerRuleBaseline is the Ticker env's yardstick: banded target-weight rules with an optional trend switch -- hold cash, buy and
 hold, a constant mix, follow the trend --, every (env, rule) pair in one kernel launch (include/goldsrl_tickersweep.h).  No
-counterpart in the reference either."""
+counterpart in the reference either.
+
+SwarmRuleBaseline is Swarm's closed-loop yardstick: feedback rules that steer the agents relative to the swarm's centroid or to
+their nearest locust, every (env, rule) pair in one kernel launch with the action computed on the device
+(include/goldsrl_swarmrules.h).  Its first two rules are ScriptedSwarmBaseline's scripts.  No counterpart in the reference."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -291,3 +295,60 @@ class TickerRuleBaseline(object):
         if self.stats is None:
             self.run()
         return select_best_ticker_rule(self.rules, self.stats["total"])
+
+
+def _swarm_rules():
+    rows = [(0, 0, 0, 0, 0, 0), (1, 0, 0, 0, 0, 0)]
+    rows += [(1, g, 0, ox, oy, r) for g in (5, 20) for (ox, oy) in ((0, 0), (-0.5, 0.5), (-1, 1), (-1.5, 1.5)) for r in (0.7, 1.0)]
+    rows += [(1, 5, 1, 0, 0, 0), (1, 5, 1, 0.3, -0.3, 0)]
+    return np.array(rows, np.float64)
+
+
+# (cancel, gain, anchor, off_x, off_y, radius): drift; hold; with the wind cancelled, each agent steered to its place on a ring of
+# radius 0.7 / 1.0 around the swarm's centroid moved by (0, 0) / (-0.5, 0.5) / (-1, 1) / (-1.5, 1.5) -- up-wind and above --, gain
+# 5, then gain 20; each agent steered onto its nearest locust, and to a point (0.3, -0.3) beside it, gain 5
+DEFAULT_SWARM_RULES = _swarm_rules()
+
+
+def select_best_swarm_rule(rules, totals):
+    """The rule with the largest mean over the envs of totals (E, n_rules) -- the first one on a tie.  Returns
+    (rule_index, (cancel, gain, anchor, off_x, off_y, radius), that mean)."""
+    m = np.asarray(totals, np.float64).mean(axis=0)
+    i = int(np.argmax(m))
+    return i, tuple(float(v) for v in rules[i]), float(m[i])
+
+
+class SwarmRuleBaseline(object):
+    """Closed-loop feedback rules on a Swarm engine, every (env, rule) pair a whole episode in one kernel launch
+    (include/goldsrl_swarmrules.h).  A rule (cancel, gain, anchor, off_x, off_y, radius) steers agent a towards
+    anchor + (off_x, off_y) + radius * (cos, sin)(2 pi a / 10) with the action gain * (target - position) - (cancel, 0), clipped to
+    norm 1 as the policy's actions are; the anchor is the swarm's centroid (0) or the agent's nearest locust (1).  (0, 0, ...) is
+    ScriptedSwarmBaseline's drift and (1, 0, ...) its hold, so the best rule is never below the better script.  At a distance of
+    ~2 the locusts are attracted to an agent: agents parked up-wind and above the swarm pull it against wind and gravity, which a
+    script that cannot see the swarm cannot do.  A policy whose eval/total_reward does not beat the best rule has learned less than
+    six numbers.  The reference has no such baseline: this one is this build's own, like ScriptedSwarmBaseline.  run() plays from
+    the engine's CURRENT state (reset it first) and leaves that state as it was."""
+
+    def __init__(self, engine, rules=DEFAULT_SWARM_RULES, max_episode_steps=None):
+        from . import _ffi
+        from ._ffi_swarmrules import check_swarm_rules
+        if engine.kind != _ffi.ENV_SWARM:
+            raise ValueError("the Swarm rule baseline exists for the Swarm env only")
+        self.eng = engine
+        self.rules = check_swarm_rules(rules)
+        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if self.max_episode_steps < 1:
+            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+        self.stats = None
+
+    def run(self, trace_env=None, keep_actions=False):
+        """Play every (env, rule) pair; returns (and keeps) the outputs of _ffi_swarmrules.swarm_rules."""
+        from . import _ffi_swarmrules
+        self.stats = _ffi_swarmrules.swarm_rules(self.eng, self.rules, self.max_episode_steps, keep_actions, trace_env)
+        return self.stats
+
+    def best_total(self):
+        """(rule_index, the six numbers, mean over the envs of the episode's total reward) of the best rule."""
+        if self.stats is None:
+            self.run()
+        return select_best_swarm_rule(self.rules, self.stats["totals"])

@@ -1,0 +1,54 @@
+"""`python -m goldsrl.scripts.swarm_rules` -- the feedback-rule baseline of the Swarm env (goldsrl/baselines.py:SwarmRuleBaseline)
+on `Swarm-eval-v0`: every default rule plays the seeded eval episode in ONE kernel launch, and every rule's total reward is printed
+-- the yardstick for eval/total_reward of train_paac_conv.  --json keeps the best rule's episode as {'score', 'actions'}, the
+format of the swarm-eval.json SwarmPolicyMonitor writes; --gif hands that file to goldsrl.scripts.make_swarm_gif, which replays
+the recorded actions, prints `score reproduced` and draws the episode.  The reference has no counterpart."""
+import argparse
+import json
+
+import numpy as np
+
+from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline
+
+
+def get_arg_parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--seed", type=int, default=192, help="the env's seed (192: Swarm-eval-v0's registration)")
+    p.add_argument("--json", help="write the best rule's episode here as {'score', 'actions'}")
+    p.add_argument("--gif", help="draw the best rule's episode with make_swarm_gif (seed 192 only; writes --json, default <gif>.json)")
+    p.add_argument("--device", type=int, default=0)
+    return p
+
+
+def main(argv=None):
+    parser = get_arg_parser()
+    args = parser.parse_args(argv)
+    if args.gif and args.seed != 192:
+        parser.error("--gif replays the file on Swarm-eval-v0, whose seed is 192")
+    from goldsrl.envs import registry
+    cls, max_steps, kwargs = registry["Swarm-eval-v0"]
+    kwargs = dict(kwargs, seed=args.seed)
+    env = cls(max_episode_steps=max_steps, device_id=args.device, **kwargs)
+    env.reset()
+    b = SwarmRuleBaseline(env._eng, DEFAULT_SWARM_RULES)
+    st = b.run(keep_actions=True)
+    for i, rule in enumerate(b.rules):
+        print("rule %2d  cancel %g gain %-3g anchor %d offset (%4g, %4g) radius %-3g  length %3d  total reward %.6f"
+              % ((i,) + tuple(rule[:2]) + (int(rule[2]),) + tuple(rule[3:]) + (int(st["length"][0, i]), float(st["totals"][0, i]))))
+    best, six, total = b.best_total()
+    print("best: rule %d %s, total reward %.6f; hold %.6f, drift %.6f" % (best, six, total, float(st["totals"][0, 1]), float(st["totals"][0, 0])))
+    n = int(st["length"][0, best])
+    score = float(np.sum(st["rewards"][0, best, :n]))                   # the monitor's total_reward
+    path = args.json or (args.gif + ".json" if args.gif else None)
+    if path:
+        with open(path, "w") as f:
+            json.dump({"score": score, "actions": st["actions"][0, best, :n].tolist()}, f)
+        print("wrote %s (%d actions, score %.17g)" % (path, n, score))
+    if args.gif:
+        from goldsrl.scripts import make_swarm_gif
+        make_swarm_gif.main(["--actions", path, "--out", args.gif, "--device", str(args.device)])
+    return best, six, score
+
+
+if __name__ == "__main__":
+    main()

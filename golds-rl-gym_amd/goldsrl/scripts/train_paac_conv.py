@@ -75,7 +75,7 @@ _BASELINE_HELP = ("play the scripted do-nothing baseline (drift / hold) on the e
                   "write eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs --eval-every > 0)")
 
 
-def get_arg_parser(baseline_help=_BASELINE_HELP):
+def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True):
     p = argparse.ArgumentParser(description="PAAC on Swarm-v0 with the conv policy (device engine)")
     for flags, dest, kind, default in _REFERENCE_FLAGS:
         p.add_argument(*flags, dest=dest, type=kind, default=default)
@@ -84,6 +84,12 @@ def get_arg_parser(baseline_help=_BASELINE_HELP):
     p.add_argument('--eval-every', default=30.0, type=float, dest="eval_every",
                    help="seconds between eval episodes on Swarm-eval-v0 (paac.py:277-282); 0 disables the monitor")
     p.add_argument('--baseline', action='store_true', help=baseline_help)
+    if rule_baseline:      # Swarm only: train_paac_solow builds its parser from this one without it
+        p.add_argument('--rule-baseline', action='store_true', dest="rule_baseline",
+                       help="play the feedback-rule baseline (goldsrl.baselines.DEFAULT_SWARM_RULES: drift, hold and rules that steer the agents "
+                            "relative to the swarm) on the eval env before the first update (one kernel launch), log the best rule and write "
+                            "eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs --eval-every > 0); with "
+                            "--baseline as well, the rule baseline is the one written")
     p.add_argument('--checkpoint-every', default=0, type=int, dest="checkpoint_every", help="updates between flat-weights checkpoints")
     p.add_argument('--checkpoint-path', default='checkpoint.npz', type=str, dest="checkpoint_path")
     p.add_argument('--resume', default=None, type=str, help="flat-weights checkpoint to start from")
@@ -95,6 +101,8 @@ def get_arg_parser(baseline_help=_BASELINE_HELP):
 def main(args):
     if args.baseline and not args.eval_every > 0:
         raise SystemExit("--baseline plays the eval env of the monitor: it needs --eval-every > 0")
+    if getattr(args, "rule_baseline", False) and not args.eval_every > 0:
+        raise SystemExit("--rule-baseline plays the eval env of the monitor: it needs --eval-every > 0")
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = GridPAACLearner(network_creator, env_creator, args, SwarmRunner,
                               state_processor=None if args.emulator_counts > 4096 else SwarmStateProcessor(grid_size=args.height))
