@@ -1,5 +1,6 @@
 """Scenarios in which the envs of one batch end their episodes on DIFFERENT steps, shared by tests/test_async_scenarios.py
-(CPU: the scenarios really are asynchronous, oracle alone) and tests/test_gpu_async_dones.py (GPU: the kernels against them).
+(CPU: the scenarios really are asynchronous, oracle alone), tests/test_gpu_async_dones.py (GPU: the kernels against them) and
+tests/test_gpu_conv_rollout_replay.py (GPU: the conv rollout's chunks and lanes, REPLAY_* and chunk_end_stats below).
 
 Two ways to desynchronise a batch:
   * staggered TimeLimit -- after reset(), ELAPSED is set to (7 * env + env // 64) % CAP, so with CAP = 9 every wave of 64 envs
@@ -32,6 +33,15 @@ TRADE_POLICY_DEPLETION = {
 }
 MIN_GAP = 1e-6                            # condition 3: the oracle's assets never come closer to MIN_CASH than this
 
+# The conv rollout replayed step by step (tests/test_gpu_conv_rollout_replay.py): 37 Swarm envs in chunks of 7 envs (70 samples) are
+# six chunks of 7, 7, 7, 7, 7 and 2 envs at bases 0, 7, 14, 21, 28, 35 -- four bases are no multiple of the step kernel's 4 envs per
+# block, the last chunk is smaller than one workgroup, and over four lanes chunks 4 and 5 share lanes 0 and 1 with chunks 0 and 1.
+REPLAY_E, REPLAY_CHUNK_SAMPLES, REPLAY_LANES = 37, 70, 4
+REPLAY_CHUNK_ENVS = REPLAY_CHUNK_SAMPLES // 10
+REPLAY_COUNTER0 = 1000                    # action counter the first rollout starts at
+REPLAY_ROLLOUTS, REPLAY_GRAD_T = 2, 4     # two chained rollouts of T steps, then one of 4 steps for the gradient leg
+REPLAY_NEG_ENV = 23                       # negative control: the twin's ELAPSED is off by one for this env only
+
 
 def staggered_elapsed(n_env, cap=CAP):
     env = np.arange(n_env)
@@ -56,6 +66,24 @@ def mixed_share(dones, wave=WAVE):
         mixed += int(((s > 0) & (s < d.shape[1])).sum())
         total += steps
     return mixed / total
+
+
+def chunk_end_stats(dones, chunk_envs, lanes):
+    """What a rollout that steps its envs in chunks of chunk_envs, chunk c on lane c % lanes, sees of a (steps, E) done mask:
+    mixed      per FULL chunk, the share of steps on which some of its envs are done and not all
+    per_step   ends per step, per_env  ends per env
+    shared     number of steps on which two chunks of one lane (c and c + lanes) both hold an end"""
+    dones = np.asarray(dones).astype(bool)
+    steps, n_env = dones.shape
+    bases = list(range(0, n_env, chunk_envs))
+    per_chunk = np.stack([dones[:, b:b + chunk_envs].sum(axis=1) for b in bases], axis=1)      # (steps, chunks)
+    full = [c for c, b in enumerate(bases) if b + chunk_envs <= n_env]
+    mixed = [float(((per_chunk[:, c] > 0) & (per_chunk[:, c] < chunk_envs)).mean()) for c in full]
+    held = per_chunk > 0
+    shared = np.zeros(steps, bool)
+    for c in range(len(bases) - lanes):
+        shared |= held[:, c] & held[:, c + lanes]
+    return dict(mixed=mixed, per_step=dones.sum(axis=1), per_env=dones.sum(axis=0), shared=int(shared.sum()))
 
 
 def trade_inputs(n, seed, n_env=E, steps=T):

@@ -36,6 +36,38 @@ def test_staggered_timelimit_masks_are_mixed(n_env):
     assert np.array_equal(ref, dones)
 
 
+def test_conv_rollout_replay_scenario_scatters_ends_over_chunks_and_lanes():
+    """Conditions on the input of tests/test_gpu_conv_rollout_replay.py: 37 envs in chunks of 7 over four lanes, staggered
+    TimeLimit(9), 20 steps.  Each bound is a condition of the scenario; the figure computed for these constants is printed."""
+    n, ce, nl = SC.REPLAY_E, SC.REPLAY_CHUNK_ENVS, SC.REPLAY_LANES
+    bases = list(range(0, n, ce))
+    assert ce == 7 and bases == [0, 7, 14, 21, 28, 35] and n - bases[-1] == 2      # six chunks, the last of 2 envs
+    assert sum(b % 4 != 0 for b in bases[1:]) == 4                                 # bases that are no multiple of SWARM_EPB = 4
+    assert [c % nl for c in range(len(bases))] == [0, 1, 2, 3, 0, 1]               # chunks 4 and 5 share lanes 0 and 1
+    el0 = SC.staggered_elapsed(n, SC.CAP)
+    assert el0.min() >= 0 and el0.max() < SC.CAP
+    dones = SC.timelimit_dones(el0, SC.T)
+    st = SC.chunk_end_stats(dones, ce, nl)
+    print("replay scenario: mixed share per full chunk %s, ends per step %d..%d, ends per env %d..%d, steps on which two chunks of "
+          "a lane both hold an end %d" % (["%.2f" % m for m in st["mixed"]], st["per_step"].min(), st["per_step"].max(),
+                                          st["per_env"].min(), st["per_env"].max(), st["shared"]))
+    assert len(st["mixed"]) == 5 and min(st["mixed"]) >= 0.7
+    assert st["per_step"].min() >= 1
+    assert st["per_env"].min() >= 2
+    assert st["shared"] >= 15
+    # the gradient leg: a rollout of 4 steps behind the two chained ones of 20 holds at least 10 ends
+    t0 = SC.REPLAY_ROLLOUTS * SC.T
+    later = SC.timelimit_dones(el0, t0 + SC.REPLAY_GRAD_T)
+    assert np.array_equal(later[:SC.T], dones)
+    assert later[t0:].sum() >= 10
+    # the negative control's env: one count less on its TimeLimit counter moves its first end, and only its
+    e = SC.REPLAY_NEG_ENV
+    assert el0[e] >= 1
+    off = el0.copy(); off[e] -= 1
+    diff = SC.timelimit_dones(off, SC.T) != dones
+    assert diff[:, e].any() and not np.delete(diff, e, axis=1).any()
+
+
 @pytest.mark.parametrize("source", ["injected", "generator"])
 @pytest.mark.parametrize("n", [2, 3, 16])
 def test_trade_depletion_scenarios(n, source):
