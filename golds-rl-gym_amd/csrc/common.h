@@ -96,6 +96,17 @@ struct TickerSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
+// buffers of grl_ticker_foresight (ticker_foresight.hip): allocated on first use, grown when a later call is larger, listed in
+// grl_handle::allocs so grl_destroy frees them
+struct TickerForesightState {
+    int32_t *horizons, *length, *trades;                 // (cap_h) (cap_pairs) (cap_pairs)
+    float *mn, *mx, *trace_r, *trace_act;                // (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
+    double *total, *sum_sq, *final_assets, *bound, *trace_a;   // (cap_pairs) x 4, (cap_trace)
+    uint8_t *finished, *depleted, *decisions;            // (cap_pairs) (cap_pairs) (cap_dec): (max_steps, pairs), horizon 0's plan
+    size_t cap_h, cap_pairs, cap_trace, cap_dec;
+    int n_horizons, max_steps, trace_env;                // of the last call; n_horizons == 0: none yet
+};
+
 // tables and buffers of grl_solow_dp_* (solow_dp.hip): allocated on first use, grown when a later call is larger, listed in
 // grl_handle::allocs so grl_destroy frees them
 struct SolowDpState {
@@ -163,6 +174,7 @@ struct grl_handle {
     grl::SwarmRulesState srl;
     grl::TradeSweepState tsw;
     grl::TickerSweepState ksw;
+    grl::TickerForesightState kfs;
     grl::SolowDpState sdp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;

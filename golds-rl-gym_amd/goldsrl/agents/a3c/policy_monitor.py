@@ -259,6 +259,34 @@ class GatedPolicyMonitor(_DeviceMonitor):
         self.baseline_rule, self.baseline_total_reward = (i, rule), total
         return i, rule, total
 
+    def ticker_ceiling(self, horizons=None):
+        """The foresight ceiling (goldsrl/baselines.py:TickerForesightCeiling) on the monitor's own Ticker eval engine: resets it and
+        plays every (env, horizon) pair in one kernel launch.  The eval engine is reseeded at every reset, so one run before the
+        first update holds for every evaluation, as ticker_baseline() does.  Keeps ceiling_total_reward -- the mean over the envs of
+        the total reward of the trader who knows every row of its episode, the unit of eval/mean_total_reward --, ceiling_table (one
+        (horizon, mean total, mean length, mean trades) row per horizon) and the whole statistics in ceiling_stats; leaves the
+        engine reset.  Returns ceiling_total_reward."""
+        from ...baselines import DEFAULT_TICKER_HORIZONS, TickerForesightCeiling
+        eng = self.net.eng
+        c = TickerForesightCeiling(eng, DEFAULT_TICKER_HORIZONS if horizons is None else horizons, self.max_episode_steps)
+        eng.reset()
+        self.ceiling_stats = c.run()
+        self.ceiling_table = c.table()
+        self.ceiling_total_reward = c.ceiling()
+        return self.ceiling_total_reward
+
+    def write_ceiling_scalars(self, global_step):
+        """eval/ceiling_total_reward (after ticker_ceiling()) and, with ticker_baseline()'s floor and an evaluation,
+        eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline) of the last evaluation"""
+        w, ceiling = self.summary_writer, getattr(self, "ceiling_total_reward", None)
+        if w is None or ceiling is None:
+            return
+        w.add_scalar("eval/ceiling_total_reward", ceiling, global_step)
+        floor = getattr(self, "baseline_total_reward", None)
+        if floor is not None and self.log["mean_total_reward"] and ceiling != floor:
+            w.add_scalar("eval/mean_total_reward_share_of_gap", (self.log["mean_total_reward"][-1] - floor) / (ceiling - floor), global_step)
+        w.flush()
+
 
 class GridPolicyMonitor(_DeviceMonitor):
     """The PolicyMonitor of the discrete savings-grid agent.  env: the Solow eval registration's id.  n_grid, lb, ub: the

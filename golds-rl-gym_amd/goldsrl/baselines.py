@@ -19,6 +19,9 @@ TickerRuleBaseline is the Ticker env's yardstick: banded target-weight rules wit
 hold, a constant mix, follow the trend --, every (env, rule) pair in one kernel launch (include/goldsrl_tickersweep.h).  No
 counterpart in the reference either.
 
+TickerForesightCeiling is the other end of the Ticker env's scale: a trader who knows the next H rows of the price table, or every
+row of the episode, every (env, horizon) pair in one kernel launch (include/goldsrl_tickerforesight.h).  No counterpart either.
+
 SwarmRuleBaseline is Swarm's closed-loop yardstick: feedback rules that steer the agents relative to the swarm's centroid or to
 their nearest locust, every (env, rule) pair in one kernel launch with the action computed on the device
 (include/goldsrl_swarmrules.h).  Its first two rules are ScriptedSwarmBaseline's scripts.  No counterpart in the reference."""
@@ -295,6 +298,54 @@ class TickerRuleBaseline(object):
         if self.stats is None:
             self.run()
         return select_best_ticker_rule(self.rules, self.stats["total"])
+
+
+# rows of the price table known beyond the one the trade executes at; 0: every row of the episode (the ceiling)
+DEFAULT_TICKER_HORIZONS = (1, 2, 4, 16, 64, 0)
+
+
+class TickerForesightCeiling(object):
+    """The other end of the Ticker env's scale: what a trader who knows the coming rows of the price table earns, every (env,
+    horizon) pair a whole episode in one kernel launch (include/goldsrl_tickerforesight.h).  The env is played on a fixed table
+    and its account is linear in (cash, q0, q1), so the best any policy could have done on an episode is exact: horizon 0 knows
+    every row and its total is the ceiling of eval/total_reward; a horizon H knows H rows beyond the current one and says what
+    that much foresight is worth.  The gap between TickerRuleBaseline's best rule and the ceiling is what there was to learn.  The
+    reference has no counterpart.  run() plays from the engine's CURRENT state and leaves it as it was; it does not reset."""
+
+    def __init__(self, engine, horizons=DEFAULT_TICKER_HORIZONS, max_episode_steps=None):
+        from . import _ffi
+        from ._ffi_tickerforesight import check_ticker_horizons
+        if engine.kind != _ffi.ENV_TICKER:
+            raise ValueError("the foresight ceiling exists for the Ticker env only")
+        self.eng = engine
+        self.horizons = check_ticker_horizons(horizons)
+        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if self.max_episode_steps < 1:
+            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+        self.stats = None
+
+    def run(self, trace_env=None):
+        """Play every (env, horizon) pair; returns (and keeps) the statistics of _ffi_tickerforesight.ticker_foresight."""
+        from . import _ffi_tickerforesight
+        self.stats = _ffi_tickerforesight.ticker_foresight(self.eng, self.horizons, self.max_episode_steps, trace_env)
+        return self.stats
+
+    def ceiling(self):
+        """The mean over the envs of the whole-episode column's total reward, the unit of eval/mean_total_reward."""
+        whole = np.flatnonzero(self.horizons == 0)
+        if len(whole) == 0:
+            raise ValueError("the ceiling is the column of horizon 0 (the whole episode), and the horizons hold none")
+        if self.stats is None:
+            self.run()
+        return float(self.stats["total"][whole[0]].mean())
+
+    def table(self):
+        """One row per horizon, in the order given: (horizon, mean total reward, mean length, mean trades) over the envs."""
+        if self.stats is None:
+            self.run()
+        s = self.stats
+        return [(int(h), float(s["total"][i].mean()), float(s["length"][i].mean()), float(s["trades"][i].mean()))
+                for i, h in enumerate(self.horizons)]
 
 
 def _swarm_rules():

@@ -7,8 +7,10 @@ episodes in one kernel launch on --eval-csv / --eval-table (a held-out price tab
 most probable choice with mu of that choice.  Totals go to <out>/Ticker.json and the eval/* scalars.  With --baseline the scripted
 rules of goldsrl/baselines.py (hold cash, buy and hold, a constant mix, follow the trend) play the eval envs' price windows once
 before the first update (one launch; the eval engine is reseeded at every reset, so every evaluation plays these windows): the best
-rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written at every evaluation.  Training is
-untouched."""
+rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written at every evaluation.  With --ceiling the
+foresight traders of goldsrl/baselines.py:TickerForesightCeiling play the same windows once (one launch): the mean total of every
+horizon is logged, eval/ceiling_total_reward -- the trader who knows every row of its episode -- is written at every evaluation, and
+with --baseline also eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline).  Training is untouched."""
 import argparse
 import logging
 import os
@@ -47,6 +49,10 @@ def get_arg_parser():
     p.add_argument("--baseline", action="store_true",
                    help="play the scripted rules on the eval envs before the first update (one kernel launch) and write "
                         "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline at every evaluation (needs --eval-envs)")
+    p.add_argument("--ceiling", action="store_true",
+                   help="play the foresight traders on the eval envs before the first update (one kernel launch) and write "
+                        "eval/ceiling_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap at every evaluation "
+                        "(needs --eval-envs)")
     ev = p.add_mutually_exclusive_group()
     ev.add_argument("--eval-csv", "--eval_csv", dest="eval_csv", help="held-out price table CSV for the evaluation")
     ev.add_argument("--eval-table", "--eval_table", dest="eval_table", help="held-out price table .npz for the evaluation")
@@ -67,6 +73,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.baseline and args.eval_envs <= 0:
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs M > 0")
+    if args.ceiling and args.eval_envs <= 0:
+        parser.error("--ceiling plays the eval envs of the device monitor: it needs --eval-envs M > 0")
     return args
 
 
@@ -97,6 +105,10 @@ def main(argv=None):
             i, rule, total = monitor.ticker_baseline()
             logging.info("Ticker rule baseline on the eval envs: rule %d (up %.6g %.6g, down %.6g %.6g, band %.6g, lookback %d), "
                          "mean total_reward %.6g", i, rule[0], rule[1], rule[2], rule[3], rule[4], int(rule[5]), total)
+        if args.ceiling:
+            monitor.ticker_ceiling()
+            logging.info("Ticker foresight on the eval envs, mean total_reward by rows known ahead: %s",
+                         ", ".join("%s %.6g" % ("whole episode" if h == 0 else str(h), tot) for h, tot, _, _ in monitor.ceiling_table))
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.steps)
@@ -115,6 +127,8 @@ def main(argv=None):
             monitor.write_scalars(step)
             if args.baseline:
                 monitor.write_baseline_scalars(step)
+            if args.ceiling:
+                monitor.write_ceiling_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
                          episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
