@@ -63,8 +63,11 @@ struct TickerState {
     int rows;
 };
 
-// buffers of grl_solow_sweep (solow_sweep.hip): allocated on first use, grown when a later sweep is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// The states of the whole-episode launches (host scaffold: episode_host.h).  Every buffer in them is allocated on first use, grown
+// (episode_reserve, by the cap_* group the comment beside it names) when a later call is larger, and listed in grl_handle::allocs so
+// grl_destroy frees it; the int fields at the end describe the last call and are what grl_*_read sizes its outputs by.
+
+// grl_solow_sweep (solow_sweep.hip)
 struct SolowSweepState {
     float *rates, *mn, *mx, *trace_r, *trace_k;   // (cap_rates) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace)
     double *total, *sum_sq;                       // (cap_pairs)
@@ -74,8 +77,7 @@ struct SolowSweepState {
     int n_rates, max_steps, trace_env;            // of the last sweep; n_rates == 0: none yet
 };
 
-// buffers of grl_trade_sweep (trade_sweep.hip): allocated on first use, grown when a later sweep is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// grl_trade_sweep (trade_sweep.hip)
 struct TradeSweepState {
     float *gains, *biases, *mn, *mx, *trace_r, *tape;   // (cap_rules) (cap_rules) (cap_pairs) (cap_pairs) (cap_trace) (cap_tape)
     double *total, *sum_sq, *final_assets, *trace_a;     // (cap_pairs) (cap_pairs) (cap_pairs) (cap_trace)
@@ -85,8 +87,7 @@ struct TradeSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
-// buffers of grl_ticker_sweep (ticker_sweep.hip): allocated on first use, grown when a later sweep is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// grl_ticker_sweep (ticker_sweep.hip)
 struct TickerSweepState {
     float *rules, *mn, *mx, *trace_r, *trace_act;        // (cap_rules,6) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
     double *total, *sum_sq, *final_assets, *trace_a;     // (cap_pairs) (cap_pairs) (cap_pairs) (cap_trace)
@@ -96,8 +97,7 @@ struct TickerSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
-// buffers of grl_ticker_foresight (ticker_foresight.hip): allocated on first use, grown when a later call is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// grl_ticker_foresight (ticker_foresight.hip)
 struct TickerForesightState {
     int32_t *horizons, *length, *trades;                 // (cap_h) (cap_pairs) (cap_pairs)
     float *mn, *mx, *trace_r, *trace_act;                // (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
@@ -107,8 +107,7 @@ struct TickerForesightState {
     int n_horizons, max_steps, trace_env;                // of the last call; n_horizons == 0: none yet
 };
 
-// tables and buffers of grl_solow_dp_* (solow_dp.hip): allocated on first use, grown when a later call is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// grl_solow_dp_* (solow_dp.hip): the tables of the solve and the buffers of the play
 struct SolowDpState {
     grl_solow_dp_grid grid;                       // of the table in `policy`
     double rho, theta;                            // the model the last solve used
@@ -125,8 +124,7 @@ struct SolowDpState {
     int played, trace_steps;                      // of the last play; played == 0: none yet
 };
 
-// buffers of grl_swarm_replay (swarm_replay.hip): allocated on first use, grown when a later replay is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// grl_swarm_replay (swarm_replay.hip)
 struct SwarmReplayState {
     uint8_t *actions;                             // (cap_act) bytes: the float64 or float32 action rows
     int32_t *seq_len, *length;                    // (cap_seq) (cap_pairs)
@@ -136,8 +134,7 @@ struct SwarmReplayState {
     int n_seq, max_steps, trace_env;              // of the last replay; n_seq == 0: none yet
 };
 
-// buffers of grl_swarm_rules (swarm_rules.hip): allocated on first use, grown when a later run is larger, listed in
-// grl_handle::allocs so grl_destroy frees them
+// grl_swarm_rules (swarm_rules.hip)
 struct SwarmRulesState {
     double *rules, *offsets;                      // (cap_rules,3) (cap_rules,10,2)
     double *rewards, *actions;                    // (cap_steps) (cap_act,10,2)

@@ -178,6 +178,15 @@ static inline SolowParams solow_params(grl_handle *h) {
     return S;
 }
 
+// rho_z / rho_e right-aligned, as solow_shock_next reads them
+static inline SolowShockCoef solow_shock_coef(const SolowParams &S) {
+    SolowShockCoef C{};
+    C.P = S.P; C.Q = S.Q;
+    for (int i = 0; i < S.P; ++i) C.rz[8 - S.P + i] = S.rho_z[i];
+    for (int i = 0; i < S.Q; ++i) C.re[8 - S.Q + i] = S.rho_e[i];
+    return C;
+}
+
 
 // ------------------------------------------------------------------------------------------ TradeAR1
 struct TradeParams {

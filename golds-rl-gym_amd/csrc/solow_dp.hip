@@ -17,6 +17,7 @@
 #include "common.h"
 #include "rng.h"
 #include "flat_env_dev.h"
+#include "episode_host.h"
 
 namespace grl {
 
@@ -218,21 +219,10 @@ static int dp_prepare(grl_handle *h, const char *fn, const grl_solow_dp_grid *gr
     return GRL_OK;
 }
 
-static int dp_reserve_tables(grl_handle *h, size_t n_states, size_t table) {
+static int dp_grow_tables(grl_handle *h, size_t n_states, size_t table) {
     SolowDpState &d = h->sdp;
-    if (n_states > d.cap_states || table > d.cap_table) GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (n_states > d.cap_states) {
-        d.cap_states = 0;
-        if ((rc = grow(h, &d.v[0], n_states)) || (rc = grow(h, &d.v[1], n_states))) return rc;
-        d.cap_states = n_states;
-    }
-    if (table > d.cap_table) {
-        d.cap_table = 0;
-        if ((rc = grow(h, &d.policy, table))) return rc;
-        d.cap_table = table;
-    }
-    return GRL_OK;
+    const int rc = episode_reserve(h, d.cap_states, n_states, {buf(d.v[0]), buf(d.v[1])});
+    return rc ? rc : episode_reserve(h, d.cap_table, table, {buf(d.policy)});
 }
 
 static void dp_keep(grl_handle *h, const DpArgs &A, int horizon, bool has_value) {
@@ -268,14 +258,14 @@ int grl_solow_dp_solve(grl_handle *h, const grl_solow_dp_grid *grid, int32_t hor
     hipSetDevice(h->cfg.device_id);
     SolowDpState &d = h->sdp;
     d.horizon = 0;
-    if ((rc = dp_reserve_tables(h, A.n_states, (size_t)horizon * A.n_states))) return rc;
+    if ((rc = dp_grow_tables(h, A.n_states, (size_t)horizon * A.n_states))) return rc;
     const dim3 grid_dim((A.n_states + 3) / 4), block(256);
-    prof_begin(h);
-    for (int t = horizon - 1; t >= 0; --t)
-        hipLaunchKernelGGL(solow_dp_stage_kernel, grid_dim, block, 0, h->stream, A, d.v[(t + 1) & 1], d.v[t & 1],
-                           d.policy + (size_t)t * A.n_states, t == horizon - 1 ? 1 : 0);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] {
+        for (int t = horizon - 1; t >= 0; --t)
+            hipLaunchKernelGGL(solow_dp_stage_kernel, grid_dim, block, 0, h->stream, A, d.v[(t + 1) & 1], d.v[t & 1],
+                               d.policy + (size_t)t * A.n_states, t == horizon - 1 ? 1 : 0);
+    });
+    if (rc) return rc;
     dp_keep(h, A, horizon, true);
     return GRL_OK;
 }
@@ -290,7 +280,7 @@ int grl_solow_dp_set_policy(grl_handle *h, const grl_solow_dp_grid *grid, int32_
     SolowDpState &d = h->sdp;
     d.horizon = 0;
     const size_t table = (size_t)horizon * A.n_states;
-    if ((rc = dp_reserve_tables(h, A.n_states, table))) return rc;
+    if ((rc = dp_grow_tables(h, A.n_states, table))) return rc;
     GRL_HIP(h, hipMemcpyAsync(d.policy, policy_host, table * 4, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipStreamSynchronize(h->stream));              // the caller's array may go away
     dp_keep(h, A, horizon, false);
@@ -299,54 +289,30 @@ int grl_solow_dp_set_policy(grl_handle *h, const grl_solow_dp_grid *grid, int32_
 
 int grl_solow_dp_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SOLOW) return fail(h, GRL_E_INVALID, "grl_solow_dp_read: not a Solow handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_solow_dp_read: null argument");
     const SolowDpState &d = h->sdp;
-    if (d.horizon == 0) return fail(h, GRL_E_STATE, "grl_solow_dp_read: call grl_solow_dp_solve or grl_solow_dp_set_policy first");
-    hipSetDevice(h->cfg.device_id);
     const size_t n_states = (size_t)d.grid.nk * d.grid.nz * d.ne;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "policy") { src = d.policy; need = (size_t)d.horizon * n_states * 4; }
-    else if (s == "value") {
-        if (!d.has_value) return fail(h, GRL_E_STATE, "grl_solow_dp_read: the table was set, not solved: it has no value function");
-        src = d.v[0]; need = n_states * 8;
-    } else return fail(h, GRL_E_INVALID, "grl_solow_dp_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_solow_dp_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const EpisodeOut outs[] = {
+        {"policy", d.policy, (size_t)d.horizon * n_states * 4},
+        {"value", d.v[0], n_states * 8, d.has_value ? nullptr : "the table was set, not solved: it has no value function"}};
+    return episode_read(h, "grl_solow_dp_read", GRL_ENV_SOLOW, "Solow", d.horizon != 0, "grl_solow_dp_solve or grl_solow_dp_set_policy", outs, nullptr,
+                        which, host, bytes);
 }
 
 int grl_solow_dp_play(grl_handle *h, int32_t max_steps, int32_t trace_steps) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SOLOW) return fail(h, GRL_E_INVALID, "grl_solow_dp_play: not a Solow handle");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_solow_dp_play: max_steps must be at least 1");
+    const char *fn = "grl_solow_dp_play";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_SOLOW, "Solow", true)) || (rc = episode_check_steps(h, fn, max_steps))) return rc;
     if (trace_steps < 0 || trace_steps > max_steps) return fail(h, GRL_E_INVALID, "grl_solow_dp_play: trace_steps must be in 0..max_steps");
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_solow_dp_play: a step is in flight (grl_wait first)");
+    if ((rc = episode_check_idle(h, fn))) return rc;
     SolowDpState &d = h->sdp;
     if (d.horizon == 0) return fail(h, GRL_E_STATE, "grl_solow_dp_play: call grl_solow_dp_solve or grl_solow_dp_set_policy first");
     hipSetDevice(h->cfg.device_id);
     d.played = 0;
     const size_t envs = h->E, trace = (size_t)trace_steps * envs;
-    if (envs > d.cap_envs || trace > d.cap_trace) GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (!d.err) {
-        if ((rc = grow(h, &d.err, 1))) return rc;
-    }
-    if (envs > d.cap_envs) {
-        d.cap_envs = 0;
-        if ((rc = grow(h, &d.total, envs)) || (rc = grow(h, &d.sum_sq, envs)) || (rc = grow(h, &d.mn, envs)) || (rc = grow(h, &d.mx, envs)) ||
-            (rc = grow(h, &d.length, envs)) || (rc = grow(h, &d.finished, envs)))
-            return rc;
-        d.cap_envs = envs;
-    }
-    if (trace > d.cap_trace) {
-        d.cap_trace = 0;
-        if ((rc = grow(h, &d.trace_a, trace)) || (rc = grow(h, &d.trace_r, trace)) || (rc = grow(h, &d.trace_k, trace))) return rc;
-        d.cap_trace = trace;
-    }
+    if ((!d.err && (rc = grow(h, &d.err, 1))) ||
+        (rc = episode_reserve(h, d.cap_envs, envs, {buf(d.total), buf(d.sum_sq), buf(d.mn), buf(d.mx), buf(d.length), buf(d.finished)})) ||
+        (rc = episode_reserve(h, d.cap_trace, trace, {buf(d.trace_a), buf(d.trace_r), buf(d.trace_k)})))
+        return rc;
     GRL_HIP(h, hipMemsetAsync(d.err, 0, 4, h->stream));
     if (trace) {     // rows are defined up to the env's length; the rest reads as zero
         GRL_HIP(h, hipMemsetAsync(d.trace_a, 0, trace * 4, h->stream));
@@ -355,49 +321,27 @@ int grl_solow_dp_play(grl_handle *h, int32_t max_steps, int32_t trace_steps) {
     }
     SolowParams S = solow_params(h);
     S.err_flag = d.err;
-    SolowShockCoef C{};
-    C.P = S.P; C.Q = S.Q;
-    for (int i = 0; i < S.P; ++i) C.rz[8 - S.P + i] = S.rho_z[i];
-    for (int i = 0; i < S.Q; ++i) C.re[8 - S.Q + i] = S.rho_e[i];
+    const SolowShockCoef C = solow_shock_coef(S);
     const DpArgs A = dp_kept(h);
     DpPlayOut O{d.total, d.sum_sq, d.mn, d.mx, d.length, d.finished, d.trace_a, d.trace_r, d.trace_k};
-    prof_begin(h);
-    hipLaunchKernelGGL(solow_dp_play_kernel, dim3((h->E + 63) / 64), dim3(64), 0, h->stream, S, C, A, d.policy, d.horizon, max_steps,
-                       trace_steps, O);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] {
+        hipLaunchKernelGGL(solow_dp_play_kernel, dim3((h->E + 63) / 64), dim3(64), 0, h->stream, S, C, A, d.policy, d.horizon, max_steps, trace_steps, O);
+    });
+    if (rc) return rc;
     d.played = h->E; d.trace_steps = trace_steps;
     return GRL_OK;
 }
 
 int grl_solow_dp_play_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SOLOW) return fail(h, GRL_E_INVALID, "grl_solow_dp_play_read: not a Solow handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_solow_dp_play_read: null argument");
     const SolowDpState &d = h->sdp;
-    if (d.played == 0) return fail(h, GRL_E_STATE, "grl_solow_dp_play_read: call grl_solow_dp_play first");
-    hipSetDevice(h->cfg.device_id);
     const size_t envs = h->E, trace = (size_t)d.trace_steps * envs;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "total") { src = d.total; need = envs * 8; }
-    else if (s == "sum_sq") { src = d.sum_sq; need = envs * 8; }
-    else if (s == "min") { src = d.mn; need = envs * 4; }
-    else if (s == "max") { src = d.mx; need = envs * 4; }
-    else if (s == "length") { src = d.length; need = envs * 4; }
-    else if (s == "finished") { src = d.finished; need = envs; }
-    else if (s == "actions" || s == "rewards" || s == "k") {
-        if (d.trace_steps == 0) return fail(h, GRL_E_STATE, "grl_solow_dp_play_read: the last play kept no trace (trace_steps was 0)");
-        src = s == "actions" ? d.trace_a : (s == "rewards" ? d.trace_r : d.trace_k); need = trace * 4;
-    } else return fail(h, GRL_E_INVALID, "grl_solow_dp_play_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_solow_dp_play_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int32_t flag = 0;
-    GRL_HIP(h, hipMemcpy(&flag, d.err, 4, hipMemcpyDeviceToHost));
-    if (flag) return fail(h, GRL_E_STATE, std::to_string(flag) + " env(s) popped from an empty shock tape (no TimeLimit and more than T steps)");
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = d.trace_steps == 0 ? "the last play kept no trace (trace_steps was 0)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"total", d.total, envs * 8}, {"sum_sq", d.sum_sq, envs * 8}, {"min", d.mn, envs * 4}, {"max", d.mx, envs * 4},
+        {"length", d.length, envs * 4}, {"finished", d.finished, envs},
+        {"actions", d.trace_a, trace * 4, untraced}, {"rewards", d.trace_r, trace * 4, untraced}, {"k", d.trace_k, trace * 4, untraced}};
+    return episode_read(h, "grl_solow_dp_play_read", GRL_ENV_SOLOW, "Solow", d.played != 0, "grl_solow_dp_play", outs, d.err, which, host, bytes);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "rng.h"
 #include "flat_env_dev.h"
+#include "episode_host.h"
 #include "../../include/goldsrl_sweep.h"
 
 namespace grl {
@@ -104,33 +105,6 @@ static int sweep_rpl() {
     return 1;
 }
 
-static int sweep_reserve(grl_handle *h, size_t n_rates, size_t pairs, size_t trace) {
-    SolowSweepState &w = h->swp;
-    if (n_rates > w.cap_rates || pairs > w.cap_pairs || trace > w.cap_trace) GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (!w.err) {
-        if ((rc = grow(h, &w.err, 1))) return rc;
-    }
-    if (n_rates > w.cap_rates) {
-        w.cap_rates = 0;
-        if ((rc = grow(h, &w.rates, n_rates))) return rc;
-        w.cap_rates = n_rates;
-    }
-    if (pairs > w.cap_pairs) {
-        w.cap_pairs = 0;
-        if ((rc = grow(h, &w.total, pairs)) || (rc = grow(h, &w.sum_sq, pairs)) || (rc = grow(h, &w.mn, pairs)) ||
-            (rc = grow(h, &w.mx, pairs)) || (rc = grow(h, &w.length, pairs)) || (rc = grow(h, &w.finished, pairs)))
-            return rc;
-        w.cap_pairs = pairs;
-    }
-    if (trace > w.cap_trace) {
-        w.cap_trace = 0;
-        if ((rc = grow(h, &w.trace_r, trace)) || (rc = grow(h, &w.trace_k, trace))) return rc;
-        w.cap_trace = trace;
-    }
-    return GRL_OK;
-}
-
 }  // namespace grl
 
 using namespace grl;
@@ -138,19 +112,19 @@ using namespace grl;
 extern "C" {
 
 int grl_solow_sweep(grl_handle *h, const float *rates_host, int32_t n_rates, int32_t max_steps, int32_t trace_env) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SOLOW) return fail(h, GRL_E_INVALID, "grl_solow_sweep: not a Solow handle");
-    if (!rates_host) return fail(h, GRL_E_INVALID, "grl_solow_sweep: null argument");
-    if (n_rates < 1 || n_rates > 4096) return fail(h, GRL_E_INVALID, "grl_solow_sweep: n_rates must be in 1..4096");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_solow_sweep: max_steps must be at least 1");
-    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_solow_sweep: trace_env must be -1 or an env index");
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_solow_sweep: a step is in flight (grl_wait first)");
+    const char *fn = "grl_solow_sweep";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_SOLOW, "Solow", rates_host)) || (rc = episode_check_count(h, fn, "n_rates", n_rates, 4096)) ||
+        (rc = episode_check_steps(h, fn, max_steps)) || (rc = episode_check_trace_env(h, fn, trace_env)) || (rc = episode_check_idle(h, fn)))
+        return rc;
     hipSetDevice(h->cfg.device_id);
     SolowSweepState &w = h->swp;
     w.n_rates = 0;
     const size_t pairs = (size_t)n_rates * h->E, trace = trace_env >= 0 ? (size_t)n_rates * max_steps : 0;
-    int rc = sweep_reserve(h, n_rates, pairs, trace);
-    if (rc) return rc;
+    if ((!w.err && (rc = grow(h, &w.err, 1))) || (rc = episode_reserve(h, w.cap_rates, n_rates, {buf(w.rates)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.mn), buf(w.mx), buf(w.length), buf(w.finished)})) ||
+        (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_k)})))
+        return rc;
     GRL_HIP(h, hipMemcpyAsync(w.rates, rates_host, (size_t)n_rates * 4, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.err, 0, 4, h->stream));
     if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
@@ -159,52 +133,31 @@ int grl_solow_sweep(grl_handle *h, const float *rates_host, int32_t n_rates, int
     }
     SolowParams S = solow_params(h);
     S.err_flag = w.err;
-    SolowShockCoef C{};
-    C.P = S.P; C.Q = S.Q;
-    for (int i = 0; i < S.P; ++i) C.rz[8 - S.P + i] = S.rho_z[i];
-    for (int i = 0; i < S.Q; ++i) C.re[8 - S.Q + i] = S.rho_e[i];
+    const SolowShockCoef C = solow_shock_coef(S);
     SweepOut O{w.total, w.sum_sq, w.mn, w.mx, w.length, w.finished, w.trace_r, w.trace_k};
     const int rpl = sweep_rpl();
     const int groups = (n_rates + rpl - 1) / rpl;
     const dim3 grid((h->E + 63) / 64, (groups + 3) / 4), block(256);
-    prof_begin(h);
-    if (rpl == 1) hipLaunchKernelGGL(solow_sweep_kernel<1>, grid, block, 0, h->stream, S, C, w.rates, n_rates, max_steps, trace_env, O);
-    else if (rpl == 2) hipLaunchKernelGGL(solow_sweep_kernel<2>, grid, block, 0, h->stream, S, C, w.rates, n_rates, max_steps, trace_env, O);
-    else hipLaunchKernelGGL(solow_sweep_kernel<4>, grid, block, 0, h->stream, S, C, w.rates, n_rates, max_steps, trace_env, O);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] {
+        if (rpl == 1) hipLaunchKernelGGL(solow_sweep_kernel<1>, grid, block, 0, h->stream, S, C, w.rates, n_rates, max_steps, trace_env, O);
+        else if (rpl == 2) hipLaunchKernelGGL(solow_sweep_kernel<2>, grid, block, 0, h->stream, S, C, w.rates, n_rates, max_steps, trace_env, O);
+        else hipLaunchKernelGGL(solow_sweep_kernel<4>, grid, block, 0, h->stream, S, C, w.rates, n_rates, max_steps, trace_env, O);
+    });
+    if (rc) return rc;
     w.n_rates = n_rates; w.max_steps = max_steps; w.trace_env = trace_env;
     return GRL_OK;
 }
 
 int grl_solow_sweep_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SOLOW) return fail(h, GRL_E_INVALID, "grl_solow_sweep_read: not a Solow handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_solow_sweep_read: null argument");
     const SolowSweepState &w = h->swp;
-    if (w.n_rates == 0) return fail(h, GRL_E_STATE, "grl_solow_sweep_read: call grl_solow_sweep first");
-    hipSetDevice(h->cfg.device_id);
     const size_t pairs = (size_t)w.n_rates * h->E, trace = (size_t)w.n_rates * w.max_steps;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "total") { src = w.total; need = pairs * 8; }
-    else if (s == "sum_sq") { src = w.sum_sq; need = pairs * 8; }
-    else if (s == "min") { src = w.mn; need = pairs * 4; }
-    else if (s == "max") { src = w.mx; need = pairs * 4; }
-    else if (s == "length") { src = w.length; need = pairs * 4; }
-    else if (s == "finished") { src = w.finished; need = pairs; }
-    else if (s == "trace_rewards" || s == "trace_k") {
-        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_solow_sweep_read: the last sweep traced no env (trace_env was -1)");
-        src = s == "trace_k" ? w.trace_k : w.trace_r; need = trace * 4;
-    } else return fail(h, GRL_E_INVALID, "grl_solow_sweep_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_solow_sweep_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int32_t flag = 0;
-    GRL_HIP(h, hipMemcpy(&flag, w.err, 4, hipMemcpyDeviceToHost));
-    if (flag) return fail(h, GRL_E_STATE, std::to_string(flag) + " env(s) popped from an empty shock tape (no TimeLimit and more than T steps)");
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = w.trace_env < 0 ? "the last sweep traced no env (trace_env was -1)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4},
+        {"length", w.length, pairs * 4}, {"finished", w.finished, pairs},
+        {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_k", w.trace_k, trace * 4, untraced}};
+    return episode_read(h, "grl_solow_sweep_read", GRL_ENV_SOLOW, "Solow", w.n_rates != 0, "grl_solow_sweep", outs, w.err, which, host, bytes);
 }
 
 }  // extern "C"

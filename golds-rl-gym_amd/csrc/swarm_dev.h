@@ -2,6 +2,8 @@
 // swarm_replay.hip: whole scripted episodes in one launch): the workgroup's LDS layout, the constants of envs/multiagent.py and
 // SwarmEnv._step for the 4 envs of a 320-lane workgroup (block_step).  Both files are compiled with -ffp-contract=off.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace grl {
@@ -178,6 +180,21 @@ __device__ __forceinline__ void block_step(SwarmLds &L, int tid, int el, int j, 
         L.rew[el] = -(s / (double)N_LOCUSTS);
     }
     __syncthreads();
+}
+
+// Host side of the whole-episode kernels (swarm_replay.hip, swarm_rules.hip).
+// launch(M) with decltype(M)::value the handle's arithmetic, as launch_swarm (swarm.hip) picks it for the step
+template <typename F>
+static void swarm_math_dispatch(const grl_handle *h, F &&launch) {
+    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH) launch(std::integral_constant<int, MATH_FAST>{});
+    else if (h->sw.ref_div) launch(std::integral_constant<int, MATH_REFDIV>{});
+    else launch(std::integral_constant<int, MATH_EXACT>{});
+}
+
+// the start state both kernels' parameter structs begin with
+template <typename P>
+static void swarm_start_state(const grl_handle *h, P &p) {
+    p.x = h->sw.x; p.xa = h->sw.xa; p.pnoise = h->sw.pnoise; p.anoise = h->sw.anoise; p.elapsed = h->elapsed;
 }
 
 }  // namespace grl

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "swarm_dev.h"
+#include "episode_host.h"
 #include "../../include/goldsrl_replay.h"
 
 namespace grl {
@@ -135,39 +136,6 @@ __global__ __launch_bounds__(SWARM_TPB, 1) void swarm_replay_kernel(ReplayParams
     }
 }
 
-static int replay_reserve(grl_handle *h, size_t act_bytes, size_t n_seq, size_t steps, size_t pairs, size_t trace) {
-    SwarmReplayState &w = h->rpl;
-    if (act_bytes > w.cap_act || n_seq > w.cap_seq || steps > w.cap_steps || pairs > w.cap_pairs || trace > w.cap_trace)
-        GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (act_bytes > w.cap_act) {
-        w.cap_act = 0;
-        if ((rc = grow(h, &w.actions, act_bytes))) return rc;
-        w.cap_act = act_bytes;
-    }
-    if (n_seq > w.cap_seq) {
-        w.cap_seq = 0;
-        if ((rc = grow(h, &w.seq_len, n_seq))) return rc;
-        w.cap_seq = n_seq;
-    }
-    if (steps > w.cap_steps) {
-        w.cap_steps = 0;
-        if ((rc = grow(h, &w.rewards, steps))) return rc;
-        w.cap_steps = steps;
-    }
-    if (pairs > w.cap_pairs) {
-        w.cap_pairs = 0;
-        if ((rc = grow(h, &w.length, pairs)) || (rc = grow(h, &w.finished, pairs))) return rc;
-        w.cap_pairs = pairs;
-    }
-    if (trace > w.cap_trace) {
-        w.cap_trace = 0;
-        if ((rc = grow(h, &w.trace_x, trace * N_LOCUSTS * 2)) || (rc = grow(h, &w.trace_xa, trace * N_AGENTS * 2))) return rc;
-        w.cap_trace = trace;
-    }
-    return GRL_OK;
-}
-
 }  // namespace grl
 
 using namespace grl;
@@ -176,19 +144,18 @@ extern "C" {
 
 int grl_swarm_replay(grl_handle *h, const void *actions_host, int32_t actions_f64, int32_t n_seq, int32_t max_steps,
                      const int32_t *seq_len_host, int32_t per_env, int32_t trace_env) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SWARM) return fail(h, GRL_E_INVALID, "grl_swarm_replay: not a Swarm handle");
-    if (!actions_host) return fail(h, GRL_E_INVALID, "grl_swarm_replay: null argument");
-    if (n_seq < 1 || n_seq > 4096) return fail(h, GRL_E_INVALID, "grl_swarm_replay: n_seq must be in 1..4096");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_swarm_replay: max_steps must be at least 1");
+    const char *fn = "grl_swarm_replay";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_SWARM, "Swarm", actions_host)) || (rc = episode_check_count(h, fn, "n_seq", n_seq, 4096)) ||
+        (rc = episode_check_steps(h, fn, max_steps)))
+        return rc;
     if (seq_len_host) {
         for (int i = 0; i < n_seq; ++i)
             if (seq_len_host[i] < 1 || seq_len_host[i] > max_steps)
                 return fail(h, GRL_E_INVALID, "grl_swarm_replay: seq_len[" + std::to_string(i) + "] = " + std::to_string(seq_len_host[i]) +
                                                   " is outside 1.." + std::to_string(max_steps));
     }
-    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_swarm_replay: trace_env must be -1 or an env index");
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_swarm_replay: a step is in flight (grl_wait first)");
+    if ((rc = episode_check_trace_env(h, fn, trace_env)) || (rc = episode_check_idle(h, fn))) return rc;
     const size_t pairs = (size_t)h->E * n_seq, steps = pairs * max_steps, trace = trace_env >= 0 ? (size_t)n_seq * max_steps : 0;
     if (steps > (size_t)INT32_MAX || trace * N_LOCUSTS * 2 > (size_t)INT32_MAX)
         return fail(h, GRL_E_INVALID, "grl_swarm_replay: an output of " + std::to_string(std::max(steps, trace * N_LOCUSTS * 2)) +
@@ -197,8 +164,10 @@ int grl_swarm_replay(grl_handle *h, const void *actions_host, int32_t actions_f6
     SwarmReplayState &w = h->rpl;
     w.n_seq = 0;
     const size_t act_bytes = (per_env ? pairs : (size_t)n_seq) * max_steps * N_AGENTS * 2 * (actions_f64 ? 8 : 4);
-    int rc = replay_reserve(h, act_bytes, n_seq, steps, pairs, trace);
-    if (rc) return rc;
+    if ((rc = episode_reserve(h, w.cap_act, act_bytes, {buf(w.actions)})) || (rc = episode_reserve(h, w.cap_seq, n_seq, {buf(w.seq_len)})) ||
+        (rc = episode_reserve(h, w.cap_steps, steps, {buf(w.rewards)})) || (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.length), buf(w.finished)})) ||
+        (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_x, N_LOCUSTS * 2), buf(w.trace_xa, N_AGENTS * 2)})))
+        return rc;
     GRL_HIP(h, hipMemcpyAsync(w.actions, actions_host, act_bytes, hipMemcpyHostToDevice, h->stream));
     if (seq_len_host) GRL_HIP(h, hipMemcpyAsync(w.seq_len, seq_len_host, (size_t)n_seq * 4, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.rewards, 0, steps * 8, h->stream));      // rows are defined up to the pair's length; the rest reads as zero
@@ -207,46 +176,29 @@ int grl_swarm_replay(grl_handle *h, const void *actions_host, int32_t actions_f6
         GRL_HIP(h, hipMemsetAsync(w.trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
     }
     ReplayParams P{};
-    P.x = h->sw.x; P.xa = h->sw.xa; P.pnoise = h->sw.pnoise; P.anoise = h->sw.anoise; P.elapsed = h->elapsed;
+    swarm_start_state(h, P);
     P.actions = w.actions; P.seq_len = seq_len_host ? w.seq_len : nullptr;
     P.rewards = w.rewards; P.length = w.length; P.finished = w.finished; P.trace_x = w.trace_x; P.trace_xa = w.trace_xa;
     P.E = h->E; P.n_seq = n_seq; P.max_steps = max_steps; P.limit = h->cfg.max_episode_steps;
     P.f64 = actions_f64 ? 1 : 0; P.per_env = per_env ? 1 : 0; P.trace_env = trace_env;
     const dim3 grid((unsigned)((pairs + SWARM_EPB - 1) / SWARM_EPB)), block(SWARM_TPB);
-    prof_begin(h);
-    // the handle's arithmetic, as launch_swarm (swarm.hip) picks it
-    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH) hipLaunchKernelGGL(swarm_replay_kernel<MATH_FAST>, grid, block, 0, h->stream, P);
-    else if (h->sw.ref_div) hipLaunchKernelGGL(swarm_replay_kernel<MATH_REFDIV>, grid, block, 0, h->stream, P);
-    else hipLaunchKernelGGL(swarm_replay_kernel<MATH_EXACT>, grid, block, 0, h->stream, P);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] {
+        swarm_math_dispatch(h, [&](auto M) { hipLaunchKernelGGL(swarm_replay_kernel<decltype(M)::value>, grid, block, 0, h->stream, P); });
+    });
+    if (rc) return rc;
     w.n_seq = n_seq; w.max_steps = max_steps; w.trace_env = trace_env;
     return GRL_OK;
 }
 
 int grl_swarm_replay_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SWARM) return fail(h, GRL_E_INVALID, "grl_swarm_replay_read: not a Swarm handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_swarm_replay_read: null argument");
     const SwarmReplayState &w = h->rpl;
-    if (w.n_seq == 0) return fail(h, GRL_E_STATE, "grl_swarm_replay_read: call grl_swarm_replay first");
-    hipSetDevice(h->cfg.device_id);
     const size_t pairs = (size_t)w.n_seq * h->E, trace = (size_t)w.n_seq * w.max_steps;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "rewards") { src = w.rewards; need = pairs * w.max_steps * 8; }
-    else if (s == "length") { src = w.length; need = pairs * 4; }
-    else if (s == "finished") { src = w.finished; need = pairs; }
-    else if (s == "trace_x" || s == "trace_xa") {
-        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_swarm_replay_read: the last replay traced no env (trace_env was -1)");
-        src = s == "trace_x" ? w.trace_x : w.trace_xa;
-        need = trace * (s == "trace_x" ? N_LOCUSTS : N_AGENTS) * 2 * 8;
-    } else return fail(h, GRL_E_INVALID, "grl_swarm_replay_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_swarm_replay_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = w.trace_env < 0 ? "the last replay traced no env (trace_env was -1)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"rewards", w.rewards, pairs * w.max_steps * 8}, {"length", w.length, pairs * 4}, {"finished", w.finished, pairs},
+        {"trace_x", w.trace_x, trace * N_LOCUSTS * 2 * 8, untraced}, {"trace_xa", w.trace_xa, trace * N_AGENTS * 2 * 8, untraced}};
+    return episode_read(h, "grl_swarm_replay_read", GRL_ENV_SWARM, "Swarm", w.n_seq != 0, "grl_swarm_replay", outs, nullptr, which, host, bytes);
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "swarm_dev.h"
+#include "episode_host.h"
 #include "../../include/goldsrl_swarmrules.h"
 
 namespace grl {
@@ -194,39 +195,6 @@ __global__ __launch_bounds__(SWARM_TPB, 1) void swarm_rules_kernel(RulesParams P
     }
 }
 
-static int rules_reserve(grl_handle *h, size_t n_rules, size_t steps, size_t pairs, size_t act, size_t trace) {
-    SwarmRulesState &w = h->srl;
-    if (n_rules > w.cap_rules || steps > w.cap_steps || pairs > w.cap_pairs || act > w.cap_act || trace > w.cap_trace)
-        GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (n_rules > w.cap_rules) {
-        w.cap_rules = 0;
-        if ((rc = grow(h, &w.rules, n_rules * 3)) || (rc = grow(h, &w.offsets, n_rules * N_AGENTS * 2))) return rc;
-        w.cap_rules = n_rules;
-    }
-    if (steps > w.cap_steps) {
-        w.cap_steps = 0;
-        if ((rc = grow(h, &w.rewards, steps))) return rc;
-        w.cap_steps = steps;
-    }
-    if (pairs > w.cap_pairs) {
-        w.cap_pairs = 0;
-        if ((rc = grow(h, &w.length, pairs)) || (rc = grow(h, &w.finished, pairs))) return rc;
-        w.cap_pairs = pairs;
-    }
-    if (act > w.cap_act) {
-        w.cap_act = 0;
-        if ((rc = grow(h, &w.actions, act * N_AGENTS * 2))) return rc;
-        w.cap_act = act;
-    }
-    if (trace > w.cap_trace) {
-        w.cap_trace = 0;
-        if ((rc = grow(h, &w.trace_x, trace * N_LOCUSTS * 2)) || (rc = grow(h, &w.trace_xa, trace * N_AGENTS * 2))) return rc;
-        w.cap_trace = trace;
-    }
-    return GRL_OK;
-}
-
 }  // namespace grl
 
 using namespace grl;
@@ -235,11 +203,11 @@ extern "C" {
 
 int grl_swarm_rules(grl_handle *h, const double *rules_host, const double *offsets_host, int32_t n_rules, int32_t max_steps,
                     int32_t keep_actions, int32_t trace_env) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SWARM) return fail(h, GRL_E_INVALID, "grl_swarm_rules: not a Swarm handle");
-    if (!rules_host || !offsets_host) return fail(h, GRL_E_INVALID, "grl_swarm_rules: null argument");
-    if (n_rules < 1 || n_rules > 4096) return fail(h, GRL_E_INVALID, "grl_swarm_rules: n_rules must be in 1..4096");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_swarm_rules: max_steps must be at least 1");
+    const char *fn = "grl_swarm_rules";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_SWARM, "Swarm", rules_host && offsets_host)) || (rc = episode_check_count(h, fn, "n_rules", n_rules, 4096)) ||
+        (rc = episode_check_steps(h, fn, max_steps)))
+        return rc;
     for (int i = 0; i < n_rules; ++i) {
         const double *r = rules_host + (size_t)i * 3;
         if (!std::isfinite(r[0]) || !std::isfinite(r[1]))
@@ -250,8 +218,7 @@ int grl_swarm_rules(grl_handle *h, const double *rules_host, const double *offse
             if (!std::isfinite(offsets_host[(size_t)i * N_AGENTS * 2 + k]))
                 return fail(h, GRL_E_INVALID, "grl_swarm_rules: rule " + std::to_string(i) + ": an offset is not finite");
     }
-    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_swarm_rules: trace_env must be -1 or an env index");
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_swarm_rules: a step is in flight (grl_wait first)");
+    if ((rc = episode_check_trace_env(h, fn, trace_env)) || (rc = episode_check_idle(h, fn))) return rc;
     const size_t pairs = (size_t)h->E * n_rules, steps = pairs * max_steps, act = keep_actions ? steps : 0;
     const size_t trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
     const size_t largest = std::max(std::max(steps, act * N_AGENTS * 2), trace * N_LOCUSTS * 2);
@@ -261,8 +228,11 @@ int grl_swarm_rules(grl_handle *h, const double *rules_host, const double *offse
     hipSetDevice(h->cfg.device_id);
     SwarmRulesState &w = h->srl;
     w.n_rules = 0;
-    int rc = rules_reserve(h, n_rules, steps, pairs, act, trace);
-    if (rc) return rc;
+    if ((rc = episode_reserve(h, w.cap_rules, n_rules, {buf(w.rules, 3), buf(w.offsets, N_AGENTS * 2)})) ||
+        (rc = episode_reserve(h, w.cap_steps, steps, {buf(w.rewards)})) || (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.length), buf(w.finished)})) ||
+        (rc = episode_reserve(h, w.cap_act, act, {buf(w.actions, N_AGENTS * 2)})) ||
+        (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_x, N_LOCUSTS * 2), buf(w.trace_xa, N_AGENTS * 2)})))
+        return rc;
     GRL_HIP(h, hipMemcpyAsync(w.rules, rules_host, (size_t)n_rules * 3 * 8, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemcpyAsync(w.offsets, offsets_host, (size_t)n_rules * N_AGENTS * 2 * 8, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.rewards, 0, steps * 8, h->stream));      // rows are defined up to the pair's length; the rest reads as zero
@@ -272,49 +242,30 @@ int grl_swarm_rules(grl_handle *h, const double *rules_host, const double *offse
         GRL_HIP(h, hipMemsetAsync(w.trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
     }
     RulesParams P{};
-    P.x = h->sw.x; P.xa = h->sw.xa; P.pnoise = h->sw.pnoise; P.anoise = h->sw.anoise; P.elapsed = h->elapsed;
+    swarm_start_state(h, P);
     P.rules = w.rules; P.offsets = w.offsets;
     P.rewards = w.rewards; P.length = w.length; P.finished = w.finished; P.actions = act ? w.actions : nullptr;
     P.trace_x = w.trace_x; P.trace_xa = w.trace_xa;
     P.E = h->E; P.n_rules = n_rules; P.max_steps = max_steps; P.limit = h->cfg.max_episode_steps; P.trace_env = trace_env;
     const dim3 grid((unsigned)((pairs + SWARM_EPB - 1) / SWARM_EPB)), block(SWARM_TPB);
-    prof_begin(h);
-    // the handle's arithmetic, as launch_swarm (swarm.hip) picks it: it selects block_step, never the rule's own statements
-    if (h->cfg.flags & GRL_F_SWARM_FAST_MATH) hipLaunchKernelGGL(swarm_rules_kernel<MATH_FAST>, grid, block, 0, h->stream, P);
-    else if (h->sw.ref_div) hipLaunchKernelGGL(swarm_rules_kernel<MATH_REFDIV>, grid, block, 0, h->stream, P);
-    else hipLaunchKernelGGL(swarm_rules_kernel<MATH_EXACT>, grid, block, 0, h->stream, P);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] {      // the math mode selects block_step, never the rule's own statements
+        swarm_math_dispatch(h, [&](auto M) { hipLaunchKernelGGL(swarm_rules_kernel<decltype(M)::value>, grid, block, 0, h->stream, P); });
+    });
+    if (rc) return rc;
     w.n_rules = n_rules; w.max_steps = max_steps; w.trace_env = trace_env; w.keep_actions = keep_actions ? 1 : 0;
     return GRL_OK;
 }
 
 int grl_swarm_rules_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_SWARM) return fail(h, GRL_E_INVALID, "grl_swarm_rules_read: not a Swarm handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_swarm_rules_read: null argument");
     const SwarmRulesState &w = h->srl;
-    if (w.n_rules == 0) return fail(h, GRL_E_STATE, "grl_swarm_rules_read: call grl_swarm_rules first");
-    hipSetDevice(h->cfg.device_id);
     const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "rewards") { src = w.rewards; need = pairs * w.max_steps * 8; }
-    else if (s == "length") { src = w.length; need = pairs * 4; }
-    else if (s == "finished") { src = w.finished; need = pairs; }
-    else if (s == "actions") {
-        if (!w.keep_actions) return fail(h, GRL_E_STATE, "grl_swarm_rules_read: the last run kept no actions (keep_actions was 0)");
-        src = w.actions; need = pairs * w.max_steps * N_AGENTS * 2 * 8;
-    } else if (s == "trace_x" || s == "trace_xa") {
-        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_swarm_rules_read: the last run traced no env (trace_env was -1)");
-        src = s == "trace_x" ? w.trace_x : w.trace_xa;
-        need = trace * (s == "trace_x" ? N_LOCUSTS : N_AGENTS) * 2 * 8;
-    } else return fail(h, GRL_E_INVALID, "grl_swarm_rules_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_swarm_rules_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = w.trace_env < 0 ? "the last run traced no env (trace_env was -1)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"rewards", w.rewards, pairs * w.max_steps * 8}, {"length", w.length, pairs * 4}, {"finished", w.finished, pairs},
+        {"actions", w.actions, pairs * w.max_steps * N_AGENTS * 2 * 8, w.keep_actions ? nullptr : "the last run kept no actions (keep_actions was 0)"},
+        {"trace_x", w.trace_x, trace * N_LOCUSTS * 2 * 8, untraced}, {"trace_xa", w.trace_xa, trace * N_AGENTS * 2 * 8, untraced}};
+    return episode_read(h, "grl_swarm_rules_read", GRL_ENV_SWARM, "Swarm", w.n_rules != 0, "grl_swarm_rules", outs, nullptr, which, host, bytes);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "ticker_dev.h"
+#include "episode_host.h"
 #include "../../include/goldsrl_tickerforesight.h"
 
 namespace grl {
@@ -146,37 +147,6 @@ __global__ __launch_bounds__(256) void ticker_foresight_kernel(TickerParams K, c
     O.depleted[o] = depleted ? 1 : 0;
 }
 
-static int ticker_foresight_reserve(grl_handle *h, size_t n_h, size_t pairs, size_t trace, size_t dec) {
-    TickerForesightState &w = h->kfs;
-    if (n_h > w.cap_h || pairs > w.cap_pairs || trace > w.cap_trace || dec > w.cap_dec) GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (n_h > w.cap_h) {
-        w.cap_h = 0;
-        if ((rc = grow(h, &w.horizons, n_h))) return rc;
-        w.cap_h = n_h;
-    }
-    if (pairs > w.cap_pairs) {
-        w.cap_pairs = 0;
-        if ((rc = grow(h, &w.total, pairs)) || (rc = grow(h, &w.sum_sq, pairs)) || (rc = grow(h, &w.final_assets, pairs)) ||
-            (rc = grow(h, &w.bound, pairs)) || (rc = grow(h, &w.mn, pairs)) || (rc = grow(h, &w.mx, pairs)) ||
-            (rc = grow(h, &w.length, pairs)) || (rc = grow(h, &w.trades, pairs)) || (rc = grow(h, &w.finished, pairs)) ||
-            (rc = grow(h, &w.depleted, pairs)))
-            return rc;
-        w.cap_pairs = pairs;
-    }
-    if (trace > w.cap_trace) {
-        w.cap_trace = 0;
-        if ((rc = grow(h, &w.trace_r, trace)) || (rc = grow(h, &w.trace_a, trace)) || (rc = grow(h, &w.trace_act, trace * 4))) return rc;
-        w.cap_trace = trace;
-    }
-    if (dec > w.cap_dec) {
-        w.cap_dec = 0;
-        if ((rc = grow(h, &w.decisions, dec))) return rc;
-        w.cap_dec = dec;
-    }
-    return GRL_OK;
-}
-
 }  // namespace grl
 
 using namespace grl;
@@ -184,27 +154,31 @@ using namespace grl;
 extern "C" {
 
 int grl_ticker_foresight(grl_handle *h, const int32_t *horizons, int32_t n_horizons, int32_t max_steps, int32_t trace_env) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: not a Ticker handle");
-    if (!horizons) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: null argument");
+    const char *fn = "grl_ticker_foresight";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_TICKER, "Ticker", horizons))) return rc;
     if (!h->tk.table) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: the handle has no price table yet (grl_ticker_set_table first)");
-    if (n_horizons < 1 || n_horizons > 64) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: n_horizons must be in 1..64");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: max_steps must be at least 1");
-    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: trace_env must be -1 or an env index");
+    if ((rc = episode_check_count(h, fn, "n_horizons", n_horizons, 64)) || (rc = episode_check_steps(h, fn, max_steps)) ||
+        (rc = episode_check_trace_env(h, fn, trace_env)))
+        return rc;
     bool whole = false;
     for (int i = 0; i < n_horizons; ++i) {
         if (horizons[i] < 0 || horizons[i] > TICKER_WINDOW - 1)
             return fail(h, GRL_E_INVALID, "grl_ticker_foresight: horizon " + std::to_string(i) + " is not 0 (the whole episode) or in 1..1023");
         whole = whole || horizons[i] == 0;
     }
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_ticker_foresight: a step is in flight (grl_wait first)");
+    if ((rc = episode_check_idle(h, fn))) return rc;
     hipSetDevice(h->cfg.device_id);
     TickerForesightState &w = h->kfs;
     w.n_horizons = 0;
     const size_t pairs = (size_t)n_horizons * h->E, trace = trace_env >= 0 ? (size_t)n_horizons * max_steps : 0;
     const size_t dec = whole ? (size_t)max_steps * pairs : 0;
-    int rc = ticker_foresight_reserve(h, n_horizons, pairs, trace, dec);
-    if (rc) return rc;
+    if ((rc = episode_reserve(h, w.cap_h, n_horizons, {buf(w.horizons)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.bound), buf(w.mn), buf(w.mx),
+                                                      buf(w.length), buf(w.trades), buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a), buf(w.trace_act, 4)})) ||
+        (rc = episode_reserve(h, w.cap_dec, dec, {buf(w.decisions)})))
+        return rc;
     GRL_HIP(h, hipMemcpyAsync(w.horizons, horizons, (size_t)n_horizons * 4, hipMemcpyHostToDevice, h->stream));
     if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
         GRL_HIP(h, hipMemsetAsync(w.trace_r, 0, trace * 4, h->stream));
@@ -215,45 +189,25 @@ int grl_ticker_foresight(grl_handle *h, const int32_t *horizons, int32_t n_horiz
     const TickerForesightOut O{w.total, w.sum_sq, w.final_assets, w.bound, w.mn, w.mx, w.length, w.trades, w.finished, w.depleted,
                                w.trace_r, w.trace_a, reinterpret_cast<float4 *>(w.trace_act), w.decisions};
     const dim3 grid((h->E + 63) / 64, (n_horizons + 3) / 4), block(256);
-    prof_begin(h);
-    hipLaunchKernelGGL(ticker_foresight_kernel, grid, block, 0, h->stream, K, w.horizons, n_horizons, max_steps, trace_env, O);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] { hipLaunchKernelGGL(ticker_foresight_kernel, grid, block, 0, h->stream, K, w.horizons, n_horizons, max_steps, trace_env, O); });
+    if (rc) return rc;
     w.n_horizons = n_horizons; w.max_steps = max_steps; w.trace_env = trace_env;
     return GRL_OK;
 }
 
 int grl_ticker_foresight_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_ticker_foresight_read: not a Ticker handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_ticker_foresight_read: null argument");
     const TickerForesightState &w = h->kfs;
-    if (w.n_horizons == 0) return fail(h, GRL_E_STATE, "grl_ticker_foresight_read: call grl_ticker_foresight first");
-    hipSetDevice(h->cfg.device_id);
     const size_t pairs = (size_t)w.n_horizons * h->E, trace = (size_t)w.n_horizons * w.max_steps;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "total") { src = w.total; need = pairs * 8; }
-    else if (s == "sum_sq") { src = w.sum_sq; need = pairs * 8; }
-    else if (s == "final_assets") { src = w.final_assets; need = pairs * 8; }
-    else if (s == "bound") { src = w.bound; need = pairs * 8; }
-    else if (s == "min") { src = w.mn; need = pairs * 4; }
-    else if (s == "max") { src = w.mx; need = pairs * 4; }
-    else if (s == "length") { src = w.length; need = pairs * 4; }
-    else if (s == "trades") { src = w.trades; need = pairs * 4; }
-    else if (s == "finished") { src = w.finished; need = pairs; }
-    else if (s == "depleted") { src = w.depleted; need = pairs; }
-    else if (s == "trace_rewards" || s == "trace_assets" || s == "trace_actions") {
-        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_ticker_foresight_read: the last call traced no env (trace_env was -1)");
-        if (s == "trace_assets") { src = w.trace_a; need = trace * 8; }
-        else if (s == "trace_actions") { src = w.trace_act; need = trace * 16; }
-        else { src = w.trace_r; need = trace * 4; }
-    } else return fail(h, GRL_E_INVALID, "grl_ticker_foresight_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_ticker_foresight_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = w.trace_env < 0 ? "the last call traced no env (trace_env was -1)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
+        {"bound", w.bound, pairs * 8}, {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4},
+        {"trades", w.trades, pairs * 4}, {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
+        {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced},
+        {"trace_actions", w.trace_act, trace * 16, untraced}};
+    return episode_read(h, "grl_ticker_foresight_read", GRL_ENV_TICKER, "Ticker", w.n_horizons != 0, "grl_ticker_foresight", outs, nullptr, which, host,
+                        bytes);
 }
 
 }  // extern "C"

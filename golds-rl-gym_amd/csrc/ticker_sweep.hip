@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "ticker_dev.h"
+#include "episode_host.h"
 #include "../../include/goldsrl_tickersweep.h"
 
 namespace grl {
@@ -88,31 +89,6 @@ __global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const
     O.depleted[o] = depleted ? 1 : 0;
 }
 
-static int ticker_sweep_reserve(grl_handle *h, size_t n_rules, size_t pairs, size_t trace) {
-    TickerSweepState &w = h->ksw;
-    if (n_rules > w.cap_rules || pairs > w.cap_pairs || trace > w.cap_trace) GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (n_rules > w.cap_rules) {
-        w.cap_rules = 0;
-        if ((rc = grow(h, &w.rules, n_rules * 6))) return rc;
-        w.cap_rules = n_rules;
-    }
-    if (pairs > w.cap_pairs) {
-        w.cap_pairs = 0;
-        if ((rc = grow(h, &w.total, pairs)) || (rc = grow(h, &w.sum_sq, pairs)) || (rc = grow(h, &w.final_assets, pairs)) ||
-            (rc = grow(h, &w.mn, pairs)) || (rc = grow(h, &w.mx, pairs)) || (rc = grow(h, &w.length, pairs)) ||
-            (rc = grow(h, &w.trades, pairs)) || (rc = grow(h, &w.finished, pairs)) || (rc = grow(h, &w.depleted, pairs)))
-            return rc;
-        w.cap_pairs = pairs;
-    }
-    if (trace > w.cap_trace) {
-        w.cap_trace = 0;
-        if ((rc = grow(h, &w.trace_r, trace)) || (rc = grow(h, &w.trace_a, trace)) || (rc = grow(h, &w.trace_act, trace * 4))) return rc;
-        w.cap_trace = trace;
-    }
-    return GRL_OK;
-}
-
 // the first thing wrong with rule i, or nullptr
 static const char *ticker_rule_fault(const float *u, const char **field) {
     static const char *names[6] = {"up0", "up1", "dn0", "dn1", "band", "lookback"};
@@ -134,24 +110,27 @@ using namespace grl;
 extern "C" {
 
 int grl_ticker_sweep(grl_handle *h, const float *rules_host, int32_t n_rules, int32_t max_steps, int32_t trace_env) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: not a Ticker handle");
-    if (!rules_host) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: null argument");
+    const char *fn = "grl_ticker_sweep";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_TICKER, "Ticker", rules_host))) return rc;
     if (!h->tk.table) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: the handle has no price table yet (grl_ticker_set_table first)");
-    if (n_rules < 1 || n_rules > 4096) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: n_rules must be in 1..4096");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: max_steps must be at least 1");
-    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: trace_env must be -1 or an env index");
+    if ((rc = episode_check_count(h, fn, "n_rules", n_rules, 4096)) || (rc = episode_check_steps(h, fn, max_steps)) ||
+        (rc = episode_check_trace_env(h, fn, trace_env)))
+        return rc;
     for (int i = 0; i < n_rules; ++i) {
         const char *field = nullptr, *what = ticker_rule_fault(rules_host + (size_t)i * 6, &field);
         if (what) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: rule " + std::to_string(i) + ": " + field + " " + what);
     }
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_ticker_sweep: a step is in flight (grl_wait first)");
+    if ((rc = episode_check_idle(h, fn))) return rc;
     hipSetDevice(h->cfg.device_id);
     TickerSweepState &w = h->ksw;
     w.n_rules = 0;
     const size_t pairs = (size_t)n_rules * h->E, trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
-    int rc = ticker_sweep_reserve(h, n_rules, pairs, trace);
-    if (rc) return rc;
+    if ((rc = episode_reserve(h, w.cap_rules, n_rules, {buf(w.rules, 6)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.mn), buf(w.mx), buf(w.length),
+                                                      buf(w.trades), buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a), buf(w.trace_act, 4)})))
+        return rc;
     GRL_HIP(h, hipMemcpyAsync(w.rules, rules_host, (size_t)n_rules * 6 * 4, hipMemcpyHostToDevice, h->stream));
     if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
         GRL_HIP(h, hipMemsetAsync(w.trace_r, 0, trace * 4, h->stream));
@@ -162,44 +141,24 @@ int grl_ticker_sweep(grl_handle *h, const float *rules_host, int32_t n_rules, in
     const TickerSweepOut O{w.total, w.sum_sq, w.final_assets, w.mn, w.mx, w.length, w.trades, w.finished, w.depleted, w.trace_r, w.trace_a,
                            reinterpret_cast<float4 *>(w.trace_act)};
     const dim3 grid((h->E + 63) / 64, (n_rules + 3) / 4), block(256);
-    prof_begin(h);
-    hipLaunchKernelGGL(ticker_sweep_kernel, grid, block, 0, h->stream, K, w.rules, n_rules, max_steps, trace_env, O);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
+    rc = episode_launch(h, [&] { hipLaunchKernelGGL(ticker_sweep_kernel, grid, block, 0, h->stream, K, w.rules, n_rules, max_steps, trace_env, O); });
+    if (rc) return rc;
     w.n_rules = n_rules; w.max_steps = max_steps; w.trace_env = trace_env;
     return GRL_OK;
 }
 
 int grl_ticker_sweep_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_TICKER) return fail(h, GRL_E_INVALID, "grl_ticker_sweep_read: not a Ticker handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_ticker_sweep_read: null argument");
     const TickerSweepState &w = h->ksw;
-    if (w.n_rules == 0) return fail(h, GRL_E_STATE, "grl_ticker_sweep_read: call grl_ticker_sweep first");
-    hipSetDevice(h->cfg.device_id);
     const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "total") { src = w.total; need = pairs * 8; }
-    else if (s == "sum_sq") { src = w.sum_sq; need = pairs * 8; }
-    else if (s == "final_assets") { src = w.final_assets; need = pairs * 8; }
-    else if (s == "min") { src = w.mn; need = pairs * 4; }
-    else if (s == "max") { src = w.mx; need = pairs * 4; }
-    else if (s == "length") { src = w.length; need = pairs * 4; }
-    else if (s == "trades") { src = w.trades; need = pairs * 4; }
-    else if (s == "finished") { src = w.finished; need = pairs; }
-    else if (s == "depleted") { src = w.depleted; need = pairs; }
-    else if (s == "trace_rewards" || s == "trace_assets" || s == "trace_actions") {
-        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_ticker_sweep_read: the last sweep traced no env (trace_env was -1)");
-        if (s == "trace_assets") { src = w.trace_a; need = trace * 8; }
-        else if (s == "trace_actions") { src = w.trace_act; need = trace * 16; }
-        else { src = w.trace_r; need = trace * 4; }
-    } else return fail(h, GRL_E_INVALID, "grl_ticker_sweep_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_ticker_sweep_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = w.trace_env < 0 ? "the last sweep traced no env (trace_env was -1)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
+        {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4}, {"trades", w.trades, pairs * 4},
+        {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
+        {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced},
+        {"trace_actions", w.trace_act, trace * 16, untraced}};
+    return episode_read(h, "grl_ticker_sweep_read", GRL_ENV_TICKER, "Ticker", w.n_rules != 0, "grl_ticker_sweep", outs, nullptr, which, host, bytes);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "rng.h"
 #include "flat_env_dev.h"
+#include "episode_host.h"
 #include "../../include/goldsrl_tradesweep.h"
 
 namespace grl {
@@ -156,36 +157,6 @@ static int trade_sweep_rpl() {
     return 2;
 }
 
-static int trade_sweep_reserve(grl_handle *h, size_t n_rules, size_t pairs, size_t trace, size_t tape) {
-    TradeSweepState &w = h->tsw;
-    if (n_rules > w.cap_rules || pairs > w.cap_pairs || trace > w.cap_trace || tape > w.cap_tape) GRL_HIP(h, hipStreamSynchronize(h->stream));
-    int rc;
-    if (n_rules > w.cap_rules) {
-        w.cap_rules = 0;
-        if ((rc = grow(h, &w.gains, n_rules)) || (rc = grow(h, &w.biases, n_rules))) return rc;
-        w.cap_rules = n_rules;
-    }
-    if (pairs > w.cap_pairs) {
-        w.cap_pairs = 0;
-        if ((rc = grow(h, &w.total, pairs)) || (rc = grow(h, &w.sum_sq, pairs)) || (rc = grow(h, &w.final_assets, pairs)) ||
-            (rc = grow(h, &w.mn, pairs)) || (rc = grow(h, &w.mx, pairs)) || (rc = grow(h, &w.length, pairs)) ||
-            (rc = grow(h, &w.finished, pairs)) || (rc = grow(h, &w.depleted, pairs)))
-            return rc;
-        w.cap_pairs = pairs;
-    }
-    if (trace > w.cap_trace) {
-        w.cap_trace = 0;
-        if ((rc = grow(h, &w.trace_r, trace)) || (rc = grow(h, &w.trace_a, trace))) return rc;
-        w.cap_trace = trace;
-    }
-    if (tape > w.cap_tape) {
-        w.cap_tape = 0;
-        if ((rc = grow(h, &w.tape, tape))) return rc;
-        w.cap_tape = tape;
-    }
-    return GRL_OK;
-}
-
 template <int RPL>
 static int trade_sweep_launch(grl_handle *h, const TradeParams &R, int n_rules, const float *tape, int max_steps, int trace_env,
                               const TradeSweepOut &O) {
@@ -206,11 +177,7 @@ static int trade_sweep_launch(grl_handle *h, const TradeParams &R, int n_rules, 
         GRL_HIP(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TSW_LDS_BYTES));
     }
     const dim3 grid((h->E + 63) / 64, (groups + waves - 1) / waves), block(64 * waves);
-    prof_begin(h);
-    hipLaunchKernelGGL(kern, grid, block, lds, h->stream, R, w.gains, w.biases, n_rules, tape, max_steps, trace_env, O);
-    prof_end(h);
-    GRL_HIP(h, hipGetLastError());
-    return GRL_OK;
+    return episode_launch(h, [&] { hipLaunchKernelGGL(kern, grid, block, lds, h->stream, R, w.gains, w.biases, n_rules, tape, max_steps, trace_env, O); });
 }
 
 }  // namespace grl
@@ -221,25 +188,27 @@ extern "C" {
 
 int grl_trade_sweep(grl_handle *h, const float *gains_host, const float *biases_host, int32_t n_rules, const float *normals_host,
                     int32_t max_steps, int32_t trace_env) {
-    if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_TRADE) return fail(h, GRL_E_INVALID, "grl_trade_sweep: not a TradeAR1 handle");
-    if (!gains_host || !biases_host) return fail(h, GRL_E_INVALID, "grl_trade_sweep: null argument");
-    if (n_rules < 1 || n_rules > 4096) return fail(h, GRL_E_INVALID, "grl_trade_sweep: n_rules must be in 1..4096");
-    if (max_steps < 1) return fail(h, GRL_E_INVALID, "grl_trade_sweep: max_steps must be at least 1");
-    if (trace_env < -1 || trace_env >= h->E) return fail(h, GRL_E_INVALID, "grl_trade_sweep: trace_env must be -1 or an env index");
+    const char *fn = "grl_trade_sweep";
+    int rc;
+    if ((rc = episode_open(h, fn, GRL_ENV_TRADE, "TradeAR1", gains_host && biases_host)) || (rc = episode_check_count(h, fn, "n_rules", n_rules, 4096)) ||
+        (rc = episode_check_steps(h, fn, max_steps)) || (rc = episode_check_trace_env(h, fn, trace_env)))
+        return rc;
     for (int i = 0; i < n_rules; ++i)
         if (!std::isfinite(gains_host[i]) || !std::isfinite(biases_host[i]))
             return fail(h, GRL_E_INVALID, "grl_trade_sweep: rule " + std::to_string(i) + " has a non-finite gain or bias");
     if (!normals_host && (h->cfg.flags & GRL_F_INJECT_NOISE))
         return fail(h, GRL_E_INVALID, "grl_trade_sweep: a handle with GRL_F_INJECT_NOISE holds the normals of one step; pass a tape");
-    if (h->step_in_flight) return fail(h, GRL_E_INVALID, "grl_trade_sweep: a step is in flight (grl_wait first)");
+    if ((rc = episode_check_idle(h, fn))) return rc;
     hipSetDevice(h->cfg.device_id);
     TradeSweepState &w = h->tsw;
     w.n_rules = 0;
     const size_t pairs = (size_t)n_rules * h->E, trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
     const size_t tape = normals_host ? (size_t)max_steps * h->cfg.n_assets * h->E : 0;
-    int rc = trade_sweep_reserve(h, n_rules, pairs, trace, tape);
-    if (rc) return rc;
+    if ((rc = episode_reserve(h, w.cap_rules, n_rules, {buf(w.gains), buf(w.biases)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.mn), buf(w.mx), buf(w.length),
+                                                      buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a)})) || (rc = episode_reserve(h, w.cap_tape, tape, {buf(w.tape)})))
+        return rc;
     GRL_HIP(h, hipMemcpyAsync(w.gains, gains_host, (size_t)n_rules * 4, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemcpyAsync(w.biases, biases_host, (size_t)n_rules * 4, hipMemcpyHostToDevice, h->stream));
     if (tape) {
@@ -264,32 +233,15 @@ int grl_trade_sweep(grl_handle *h, const float *gains_host, const float *biases_
 
 int grl_trade_sweep_read(grl_handle *h, const char *which, void *host, size_t bytes) {
     if (!h) return GRL_E_INVALID;
-    if (h->cfg.env_kind != GRL_ENV_TRADE) return fail(h, GRL_E_INVALID, "grl_trade_sweep_read: not a TradeAR1 handle");
-    if (!which || !host) return fail(h, GRL_E_INVALID, "grl_trade_sweep_read: null argument");
     const TradeSweepState &w = h->tsw;
-    if (w.n_rules == 0) return fail(h, GRL_E_STATE, "grl_trade_sweep_read: call grl_trade_sweep first");
-    hipSetDevice(h->cfg.device_id);
     const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
-    const std::string s(which);
-    const void *src = nullptr;
-    size_t need = 0;
-    if (s == "total") { src = w.total; need = pairs * 8; }
-    else if (s == "sum_sq") { src = w.sum_sq; need = pairs * 8; }
-    else if (s == "final_assets") { src = w.final_assets; need = pairs * 8; }
-    else if (s == "min") { src = w.mn; need = pairs * 4; }
-    else if (s == "max") { src = w.mx; need = pairs * 4; }
-    else if (s == "length") { src = w.length; need = pairs * 4; }
-    else if (s == "finished") { src = w.finished; need = pairs; }
-    else if (s == "depleted") { src = w.depleted; need = pairs; }
-    else if (s == "trace_rewards" || s == "trace_assets") {
-        if (w.trace_env < 0) return fail(h, GRL_E_STATE, "grl_trade_sweep_read: the last sweep traced no env (trace_env was -1)");
-        if (s == "trace_assets") { src = w.trace_a; need = trace * 8; }
-        else { src = w.trace_r; need = trace * 4; }
-    } else return fail(h, GRL_E_INVALID, "grl_trade_sweep_read: unknown output '" + s + "'");
-    if (need != bytes) return fail(h, GRL_E_SIZE, "grl_trade_sweep_read: '" + s + "' needs " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
-    GRL_HIP(h, hipStreamSynchronize(h->stream));
-    GRL_HIP(h, hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
-    return GRL_OK;
+    const char *untraced = w.trace_env < 0 ? "the last sweep traced no env (trace_env was -1)" : nullptr;
+    const EpisodeOut outs[] = {
+        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
+        {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4},
+        {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
+        {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced}};
+    return episode_read(h, "grl_trade_sweep_read", GRL_ENV_TRADE, "TradeAR1", w.n_rules != 0, "grl_trade_sweep", outs, nullptr, which, host, bytes);
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from ._ffi_episode import read_outputs
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
 
@@ -44,12 +45,8 @@ def swarm_replay(eng, actions, seq_len=None, trace_env=-1):
     lib = _ffi.load_library(extra_signatures=REPLAY_SIGNATURES)
     eng._check(lib.grl_swarm_replay(eng.h, _ffi._ptr(a), 1 if a.dtype == np.float64 else 0, n_seq, T,
                                     None if lens is None else _ffi._ptr(lens), 1 if per_env else 0, t_env))
-    shapes = [("rewards", (eng.E, n_seq, T), np.float64), ("length", (eng.E, n_seq), np.int32), ("finished", (eng.E, n_seq), np.uint8)]
+    out = read_outputs(eng, lib.grl_swarm_replay_read, (("rewards", np.float64, (T,)), ("length", np.int32, ()), ("finished", np.uint8, ())),
+                       (eng.E, n_seq))
     if t_env >= 0:
-        shapes += [("trace_x", (n_seq, T, 80, 2), np.float64), ("trace_xa", (n_seq, T, 10, 2), np.float64)]
-    out = {}
-    for name, shape, dt in shapes:
-        buf = np.empty(shape, dt)
-        eng._check(lib.grl_swarm_replay_read(eng.h, name.encode(), _ffi._ptr(buf), buf.nbytes))
-        out[name] = buf
+        out.update(read_outputs(eng, lib.grl_swarm_replay_read, (("trace_x", np.float64, (80, 2)), ("trace_xa", np.float64, (10, 2))), (n_seq, T)))
     return out

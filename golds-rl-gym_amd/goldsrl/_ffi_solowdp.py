@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from ._ffi_episode import read_outputs, steps_and_trace
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
 MAX_NODES = 15
@@ -72,9 +73,7 @@ def solow_dp_solve(engine, grid=None, horizon=DEFAULT_HORIZON, read=True):
     out = {"grid": grid, "horizon": int(horizon)}
     if read:
         shape = table_shape(engine, grid, horizon)
-        out["policy"], out["value"] = np.empty(shape, np.float32), np.empty(shape[1:], np.float64)
-        for name in ("policy", "value"):
-            engine._check(lib.grl_solow_dp_read(engine.h, name.encode(), _ffi._ptr(out[name]), out[name].nbytes))
+        out.update(read_outputs(engine, lib.grl_solow_dp_read, (("policy", np.float32, shape), ("value", np.float64, shape[1:])), ()))
     return out
 
 
@@ -88,8 +87,9 @@ def solow_dp_set_policy(engine, grid, policy):
     engine._check(lib.grl_solow_dp_set_policy(engine.h, C.byref(g), p.shape[0], _ffi._ptr(p)))
 
 
-_ENV_DTYPES = (("total", np.float64), ("sum_sq", np.float64), ("min", np.float32), ("max", np.float32), ("length", np.int32),
-               ("finished", np.uint8))
+_ENV_DTYPES = (("total", np.float64, ()), ("sum_sq", np.float64, ()), ("min", np.float32, ()), ("max", np.float32, ()),
+               ("length", np.int32, ()), ("finished", np.uint8, ()))
+_TRACE_DTYPES = (("actions", np.float32, ()), ("rewards", np.float32, ()), ("k", np.float32, ()))
 
 
 def solow_dp_play(engine, max_steps=None, trace_steps=0):
@@ -98,21 +98,11 @@ def solow_dp_play(engine, max_steps=None, trace_steps=0):
     (float64), min, max (float32), length (int32), finished (uint8), each (E,), and with trace_steps the first trace_steps steps of
     every env: actions, rewards and k (the capital after the step), each (trace_steps, E) float32."""
     lib = _solow(engine, "solow_dp_play")
-    if max_steps is None:
-        max_steps = int(engine.cfg.max_episode_steps)
-    if max_steps < 1:
-        raise ValueError("solow_dp_play: max_steps must be at least 1 (an engine without a TimeLimit has no default)")
-    engine._check(lib.grl_solow_dp_play(engine.h, int(max_steps), int(trace_steps)))
-    out = {}
-    for name, dt in _ENV_DTYPES:
-        a = np.empty((engine.E,), dt)
-        engine._check(lib.grl_solow_dp_play_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-        out[name] = a
+    max_steps, _ = steps_and_trace(engine, "solow_dp_play", max_steps)
+    engine._check(lib.grl_solow_dp_play(engine.h, max_steps, int(trace_steps)))
+    out = read_outputs(engine, lib.grl_solow_dp_play_read, _ENV_DTYPES, (engine.E,))
     if trace_steps > 0:
-        for name in ("actions", "rewards", "k"):
-            a = np.empty((int(trace_steps), engine.E), np.float32)
-            engine._check(lib.grl_solow_dp_play_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-            out[name] = a
+        out.update(read_outputs(engine, lib.grl_solow_dp_play_read, _TRACE_DTYPES, (int(trace_steps), engine.E)))
     return out
 
 

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
+from ._ffi_episode import read_outputs, steps_and_trace
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
 
@@ -122,24 +123,17 @@ def swarm_rules(engine, rules, max_steps=None, keep_actions=False, trace_env=Non
     r = check_swarm_rules(rules)
     off = np.ascontiguousarray(swarm_rule_offsets(r))
     head = np.ascontiguousarray(r[:, :3])
-    if max_steps is None:
-        max_steps = int(engine.cfg.max_episode_steps)
-    T = int(max_steps)
-    if T < 1:
-        raise ValueError("swarm_rules: max_steps must be at least 1 (an engine without a TimeLimit has no default)")
-    t_env = -1 if trace_env is None else int(trace_env)
+    T, t_env = steps_and_trace(engine, "swarm_rules", max_steps, trace_env)
     n = r.shape[0]
     lib = _ffi.load_library(extra_signatures=SWARMRULES_SIGNATURES)
     engine._check(lib.grl_swarm_rules(engine.h, _ffi._ptr(head), _ffi._ptr(off), n, T, 1 if keep_actions else 0, t_env))
-    shapes = [("rewards", (engine.E, n, T), np.float64), ("length", (engine.E, n), np.int32), ("finished", (engine.E, n), np.uint8)]
+    pair = [("rewards", np.float64, (T,)), ("length", np.int32, ()), ("finished", np.uint8, ())]
     if keep_actions:
-        shapes += [("actions", (engine.E, n, T, N_AGENTS, 2), np.float64)]
-    if t_env >= 0:
-        shapes += [("trace_x", (n, T, N_LOCUSTS, 2), np.float64), ("trace_xa", (n, T, N_AGENTS, 2), np.float64)]
+        pair += [("actions", np.float64, (T, N_AGENTS, 2))]
     out = {"rules": r, "offsets": off}
-    for name, shape, dt in shapes:
-        buf = np.empty(shape, dt)
-        engine._check(lib.grl_swarm_rules_read(engine.h, name.encode(), _ffi._ptr(buf), buf.nbytes))
-        out[name] = buf
+    out.update(read_outputs(engine, lib.grl_swarm_rules_read, pair, (engine.E, n)))
+    if t_env >= 0:
+        out.update(read_outputs(engine, lib.grl_swarm_rules_read,
+                                (("trace_x", np.float64, (N_LOCUSTS, 2)), ("trace_xa", np.float64, (N_AGENTS, 2))), (n, T)))
     out["totals"] = out["rewards"].sum(-1)
     return out

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi_sweep import reward_moments
+from ._ffi_episode import read_outputs, reward_moments, steps_and_trace
 from ._ffi_tickersweep import _PAIR_DTYPES, _TRACE_DTYPES, WINDOW
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
@@ -122,24 +122,13 @@ def ticker_foresight(engine, horizons, max_steps=None, trace_env=None):
         raise ValueError("ticker_foresight: the engine is not a Ticker engine")
     lib = _ffi.load_library(extra_signatures=TICKER_FORESIGHT_SIGNATURES)
     hz = check_ticker_horizons(horizons)
-    if max_steps is None:
-        max_steps = int(engine.cfg.max_episode_steps)
-    max_steps = int(max_steps)
-    if max_steps < 1:
-        raise ValueError("ticker_foresight: max_steps must be at least 1 (an engine without a TimeLimit has no default)")
-    t_env = -1 if trace_env is None else int(trace_env)
+    max_steps, t_env = steps_and_trace(engine, "ticker_foresight", max_steps, trace_env)
     n = hz.shape[0]
     engine._check(lib.grl_ticker_foresight(engine.h, _ffi._ptr(hz), n, max_steps, t_env))
     out = {"horizons": hz}
-    for name, dt in _PAIR_DTYPES + (("bound", np.float64),):
-        a = np.empty((n, engine.E), dt)
-        engine._check(lib.grl_ticker_foresight_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-        out[name] = a
+    out.update(read_outputs(engine, lib.grl_ticker_foresight_read, _PAIR_DTYPES + (("bound", np.float64, ()),), (n, engine.E)))
     if t_env >= 0:
-        for name, dt, inner in _TRACE_DTYPES:
-            a = np.empty((n, max_steps) + inner, dt)
-            engine._check(lib.grl_ticker_foresight_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-            out[name] = a
+        out.update(read_outputs(engine, lib.grl_ticker_foresight_read, _TRACE_DTYPES, (n, max_steps)))
     with np.errstate(divide="ignore", invalid="ignore"):       # a pair at the end of its window plays no step: its moments are NaN
         out["mean"], out["std"] = reward_moments(out["total"], out["sum_sq"], out["length"])
     return out

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi_sweep import reward_moments
+from ._ffi_episode import read_outputs, reward_moments, steps_and_trace
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
 
@@ -18,8 +18,9 @@ TICKER_SWEEP_SIGNATURES = {
 RULE_FIELDS = ("up0", "up1", "dn0", "dn1", "band", "lookback")
 WINDOW = 1024
 
-_PAIR_DTYPES = (("total", np.float64), ("sum_sq", np.float64), ("final_assets", np.float64), ("min", np.float32), ("max", np.float32),
-                ("length", np.int32), ("trades", np.int32), ("finished", np.uint8), ("depleted", np.uint8))
+_PAIR_DTYPES = (("total", np.float64, ()), ("sum_sq", np.float64, ()), ("final_assets", np.float64, ()), ("min", np.float32, ()),
+                ("max", np.float32, ()), ("length", np.int32, ()), ("trades", np.int32, ()), ("finished", np.uint8, ()),
+                ("depleted", np.uint8, ()))
 _TRACE_DTYPES = (("trace_rewards", np.float32, ()), ("trace_assets", np.float64, ()), ("trace_actions", np.float32, (4,)))
 
 
@@ -106,24 +107,13 @@ def ticker_sweep(engine, rules, max_steps=None, trace_env=None):
         raise ValueError("ticker_sweep: the engine is not a Ticker engine")
     lib = _ffi.load_library(extra_signatures=TICKER_SWEEP_SIGNATURES)
     r = check_ticker_rules(rules)
-    if max_steps is None:
-        max_steps = int(engine.cfg.max_episode_steps)
-    max_steps = int(max_steps)
-    if max_steps < 1:
-        raise ValueError("ticker_sweep: max_steps must be at least 1 (an engine without a TimeLimit has no default)")
-    t_env = -1 if trace_env is None else int(trace_env)
+    max_steps, t_env = steps_and_trace(engine, "ticker_sweep", max_steps, trace_env)
     n_rules = r.shape[0]
     engine._check(lib.grl_ticker_sweep(engine.h, _ffi._ptr(r), n_rules, max_steps, t_env))
     out = {"rules": r}
-    for name, dt in _PAIR_DTYPES:
-        a = np.empty((n_rules, engine.E), dt)
-        engine._check(lib.grl_ticker_sweep_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-        out[name] = a
+    out.update(read_outputs(engine, lib.grl_ticker_sweep_read, _PAIR_DTYPES, (n_rules, engine.E)))
     if t_env >= 0:
-        for name, dt, inner in _TRACE_DTYPES:
-            a = np.empty((n_rules, max_steps) + inner, dt)
-            engine._check(lib.grl_ticker_sweep_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-            out[name] = a
+        out.update(read_outputs(engine, lib.grl_ticker_sweep_read, _TRACE_DTYPES, (n_rules, max_steps)))
     with np.errstate(divide="ignore", invalid="ignore"):       # a pair at the end of its window plays no step: its moments are NaN
         out["mean"], out["std"] = reward_moments(out["total"], out["sum_sq"], out["length"])
     return out

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi_sweep import reward_moments
+from ._ffi_episode import read_outputs, reward_moments, steps_and_trace
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
 
@@ -15,9 +15,9 @@ TRADE_SWEEP_SIGNATURES = {
     "grl_trade_sweep_read": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
 }
 
-_PAIR_DTYPES = (("total", np.float64), ("sum_sq", np.float64), ("final_assets", np.float64), ("min", np.float32), ("max", np.float32),
-                ("length", np.int32), ("finished", np.uint8), ("depleted", np.uint8))
-_TRACE_DTYPES = (("trace_rewards", np.float32), ("trace_assets", np.float64))
+_PAIR_DTYPES = (("total", np.float64, ()), ("sum_sq", np.float64, ()), ("final_assets", np.float64, ()), ("min", np.float32, ()),
+                ("max", np.float32, ()), ("length", np.int32, ()), ("finished", np.uint8, ()), ("depleted", np.uint8, ()))
+_TRACE_DTYPES = (("trace_rewards", np.float32, ()), ("trace_assets", np.float64, ()))
 
 
 def rule_actions(rules, prices):
@@ -50,11 +50,7 @@ def trade_sweep(engine, rules, max_steps=None, trace_env=None, normals=None):
     if not np.isfinite(r).all():
         raise ValueError("trade_sweep: every gain and bias must be finite")
     gains, biases = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
-    if max_steps is None:
-        max_steps = int(engine.cfg.max_episode_steps)
-    max_steps = int(max_steps)
-    if max_steps < 1:
-        raise ValueError("trade_sweep: max_steps must be at least 1 (an engine without a TimeLimit has no default)")
+    max_steps, t_env = steps_and_trace(engine, "trade_sweep", max_steps, trace_env)
     tape = None
     if normals is not None:
         tape = np.asarray(normals, np.float32)
@@ -62,19 +58,12 @@ def trade_sweep(engine, rules, max_steps=None, trace_env=None, normals=None):
             raise ValueError("trade_sweep: normals must be (max_steps, E, n_assets) = %s, got %s"
                              % ((max_steps, engine.E, engine.cfg.n_assets), tape.shape))
         tape = np.ascontiguousarray(tape.transpose(0, 2, 1))        # the device layout: a * E + env per step
-    t_env = -1 if trace_env is None else int(trace_env)
     n_rules = r.shape[0]
     engine._check(lib.grl_trade_sweep(engine.h, _ffi._ptr(gains), _ffi._ptr(biases), n_rules, None if tape is None else _ffi._ptr(tape),
                                       max_steps, t_env))
     out = {"rules": np.stack([gains, biases], axis=1)}
-    for name, dt in _PAIR_DTYPES:
-        a = np.empty((n_rules, engine.E), dt)
-        engine._check(lib.grl_trade_sweep_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-        out[name] = a
+    out.update(read_outputs(engine, lib.grl_trade_sweep_read, _PAIR_DTYPES, (n_rules, engine.E)))
     if t_env >= 0:
-        for name, dt in _TRACE_DTYPES:
-            a = np.empty((n_rules, max_steps), dt)
-            engine._check(lib.grl_trade_sweep_read(engine.h, name.encode(), _ffi._ptr(a), a.nbytes))
-            out[name] = a
+        out.update(read_outputs(engine, lib.grl_trade_sweep_read, _TRACE_DTYPES, (n_rules, max_steps)))
     out["mean"], out["std"] = reward_moments(out["total"], out["sum_sq"], out["length"])
     return out

@@ -49,7 +49,46 @@ def select_best_total(rates, total):
     return rates[i], float(m[i])
 
 
-class ConstantSavingsBaseline(object):
+def _solow_engine(what, env, n_envs, device_id, max_episode_steps, engine):
+    """The engine of a Solow baseline: the caller's, or the eval registration's built here.  what: the baseline's name in the
+    refusals."""
+    if engine is not None:
+        from . import _ffi
+        if engine.kind != _ffi.ENV_SOLOW:
+            raise ValueError("%s exists for the Solow env only" % what)
+        return engine
+    from .agents.a3c.policy_monitor import make_eval_engine
+    if not env.startswith("Solow-"):
+        raise ValueError("%s exists for the Solow env only (got %r)" % (what, env))
+    if n_envs < 1:
+        raise ValueError("n_envs must be at least 1")
+    return make_eval_engine(env, n_envs, device_id, max_episode_steps)
+
+
+class _EngineBaseline(object):
+    """What the baselines share: statistics that are played once (_stats, the two Solow classes' too) and, for the five that take
+    the caller's engine, the kind check (_open) and the episode length with its default (_steps)."""
+
+    def _open(self, engine, kind, refusal):
+        """kind: the name of the env kind in _ffi, e.g. "ENV_SWARM"."""
+        from . import _ffi
+        if engine.kind != getattr(_ffi, kind):
+            raise ValueError(refusal)
+        self.eng = engine
+        self.stats = None
+
+    def _steps(self, max_episode_steps):
+        self.max_episode_steps = int(self.eng.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
+        if self.max_episode_steps < 1:
+            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+
+    def _stats(self):
+        if self.stats is None:
+            self.run()
+        return self.stats
+
+
+class ConstantSavingsBaseline(_EngineBaseline):
     """rates: the constant savings rates, played in this order (the reference's 20 by default).  engine: a Solow engine to run on
     (the caller keeps it) instead of building the eval registration's; run() resets it."""
 
@@ -59,18 +98,7 @@ class ConstantSavingsBaseline(object):
             raise ValueError("at least one rate")
         self.max_episode_steps = int(max_episode_steps)
         self._own = engine is None
-        if engine is None:
-            from .agents.a3c.policy_monitor import make_eval_engine
-            if not env.startswith("Solow-"):
-                raise ValueError("the constant-savings baseline exists for the Solow env only (got %r)" % (env,))
-            if n_envs < 1:
-                raise ValueError("n_envs must be at least 1")
-            engine = make_eval_engine(env, n_envs, device_id, self.max_episode_steps)
-        else:
-            from . import _ffi
-            if engine.kind != _ffi.ENV_SOLOW:
-                raise ValueError("the constant-savings baseline exists for the Solow env only")
-        self.eng = engine
+        self.eng = _solow_engine("the constant-savings baseline", env, n_envs, device_id, self.max_episode_steps, engine)
         self.stats = None
 
     def run(self, trace_env=None):
@@ -78,11 +106,6 @@ class ConstantSavingsBaseline(object):
         from . import _ffi_sweep
         self.eng.reset()
         self.stats = _ffi_sweep.solow_sweep(self.eng, self.rates, self.max_episode_steps, trace_env)
-        return self.stats
-
-    def _stats(self):
-        if self.stats is None:
-            self.run()
         return self.stats
 
     def best(self, env=0):
@@ -101,7 +124,7 @@ class ConstantSavingsBaseline(object):
         self.eng = None
 
 
-class OptimalSavingsBaseline(object):
+class OptimalSavingsBaseline(_EngineBaseline):
     """The optimal savings policy of a Solow engine with p = 1 and q in {0, 1}: solved once by backward induction on `grid` (a dict
     of _ffi_solowdp.solow_dp_grid; default 96 x 25 x 7 with 96 actions at the engine's sigma) over `horizon` stages (default 256),
     then played on every env from its reset state.  With more steps left than the horizon the policy of stage 0 is used: the
@@ -115,19 +138,8 @@ class OptimalSavingsBaseline(object):
             raise ValueError("horizon must be at least 1")
         self.max_episode_steps = int(max_episode_steps)
         self._own = engine is None
-        if engine is None:
-            from .agents.a3c.policy_monitor import make_eval_engine
-            if not env.startswith("Solow-"):
-                raise ValueError("the optimal-savings yardstick exists for the Solow env only (got %r)" % (env,))
-            if n_envs < 1:
-                raise ValueError("n_envs must be at least 1")
-            engine = make_eval_engine(env, n_envs, device_id, self.max_episode_steps)
-        else:
-            from . import _ffi
-            if engine.kind != _ffi.ENV_SOLOW:
-                raise ValueError("the optimal-savings yardstick exists for the Solow env only")
-        self.eng = engine
-        self.grid = _ffi_solowdp.solow_dp_grid(sigma=engine.cfg.solow_sigma) if grid is None else grid
+        self.eng = _solow_engine("the optimal-savings yardstick", env, n_envs, device_id, self.max_episode_steps, engine)
+        self.grid = _ffi_solowdp.solow_dp_grid(sigma=self.eng.cfg.solow_sigma) if grid is None else grid
         self.solved, self.stats = False, None
 
     def solve(self):
@@ -148,9 +160,7 @@ class OptimalSavingsBaseline(object):
 
     def total(self):
         """The mean over the envs of the episode's total reward: the unit of eval/mean_total_reward."""
-        if self.stats is None:
-            self.run()
-        return float(np.asarray(self.stats["total"], np.float64).mean())
+        return float(np.asarray(self._stats()["total"], np.float64).mean())
 
     def close(self):
         if self._own and self.eng is not None:
@@ -158,7 +168,7 @@ class OptimalSavingsBaseline(object):
         self.eng = None
 
 
-class ScriptedSwarmBaseline(object):
+class ScriptedSwarmBaseline(_EngineBaseline):
     """Two scripted do-nothing policies on a Swarm engine, every (env, script) pair a whole episode in one kernel launch:
       drift   the zero action: the agents go with the wind;
       hold    (-WIND_SPEED, 0): the action cancels the wind and the agents stand still.
@@ -170,16 +180,10 @@ class ScriptedSwarmBaseline(object):
     NAMES = ("drift", "hold")
 
     def __init__(self, engine, max_episode_steps=None):
-        from . import _ffi
-        if engine.kind != _ffi.ENV_SWARM:
-            raise ValueError("the scripted baseline exists for the Swarm env only")
-        self.eng = engine
-        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
-        if self.max_episode_steps < 1:
-            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
+        self._open(engine, "ENV_SWARM", "the scripted baseline exists for the Swarm env only")
+        self._steps(max_episode_steps)
         self.scripts = np.zeros((2, self.max_episode_steps, 10, 2), np.float64)
         self.scripts[1, :, :, 0] = -1.0        # -SwarmEnv.WIND_SPEED
-        self.stats = None
 
     def run(self):
         """Play both scripts on every env; returns (and keeps) rewards (E, 2, T), totals, length and finished (E, 2)."""
@@ -189,9 +193,7 @@ class ScriptedSwarmBaseline(object):
 
     def best(self, env=0):
         """(name, total reward) of the better script on `env` -- the first one on a tie"""
-        if self.stats is None:
-            self.run()
-        totals = self.stats["totals"][env]
+        totals = self._stats()["totals"][env]
         i = int(np.argmax(totals))
         return self.NAMES[i], float(totals[i])
 
@@ -208,7 +210,7 @@ def select_best_rule(rules, total):
     return i, (float(rules[i][0]), float(rules[i][1])), float(m[i])
 
 
-class TradingRuleBaseline(object):
+class TradingRuleBaseline(_EngineBaseline):
     """Scripted trading rules on a TradeAR1 engine, every (env, rule) pair a whole episode in one kernel launch
     (include/goldsrl_tradesweep.h).  A rule (gain, bias) trades asset a with the action clip(bias - gain * (p_a - 1), -1, 1): the
     log price is an AR(1) around 0 (fed_env.py:296-298), so a positive gain buys what is cheap and sells what is dear; (0, 0) holds
@@ -218,17 +220,11 @@ class TradingRuleBaseline(object):
     episode to the next, so when to reset is the caller's affair."""
 
     def __init__(self, engine, rules=DEFAULT_TRADE_RULES, max_episode_steps=None):
-        from . import _ffi
-        if engine.kind != _ffi.ENV_TRADE:
-            raise ValueError("the trading-rule baseline exists for the TradeAR1 env only")
-        self.eng = engine
+        self._open(engine, "ENV_TRADE", "the trading-rule baseline exists for the TradeAR1 env only")
         self.rules = np.asarray(rules, np.float32)
         if self.rules.ndim != 2 or self.rules.shape[1] != 2 or self.rules.shape[0] < 1:
             raise ValueError("rules must be (n_rules, 2) of (gain, bias)")
-        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
-        if self.max_episode_steps < 1:
-            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
-        self.stats = None
+        self._steps(max_episode_steps)
 
     def run(self, trace_env=None, normals=None):
         """Play every (env, rule) pair; returns (and keeps) the statistics of _ffi_tradesweep.trade_sweep."""
@@ -238,9 +234,7 @@ class TradingRuleBaseline(object):
 
     def best_total(self):
         """(rule_index, (gain, bias), mean over the envs of the episode's total reward) of the best rule."""
-        if self.stats is None:
-            self.run()
-        return select_best_rule(self.rules, self.stats["total"])
+        return select_best_rule(self.rules, self._stats()["total"])
 
 
 def _ticker_rules():
@@ -265,7 +259,7 @@ def select_best_ticker_rule(rules, total):
     return i, tuple(float(v) for v in rules[i]), float(m[i])
 
 
-class TickerRuleBaseline(object):
+class TickerRuleBaseline(_EngineBaseline):
     """Scripted rules on a Ticker engine, every (env, rule) pair a whole episode in one kernel launch
     (include/goldsrl_tickersweep.h).  A rule (up0, up1, dn0, dn1, band, lookback) holds target weights of the two assets -- (up0,
     up1) while the price is at or above its value `lookback` rows ago (always, with lookback 0), (dn0, dn1) otherwise -- and trades
@@ -276,16 +270,10 @@ class TickerRuleBaseline(object):
     it was; it does not reset."""
 
     def __init__(self, engine, rules=DEFAULT_TICKER_RULES, max_episode_steps=None):
-        from . import _ffi
         from ._ffi_tickersweep import check_ticker_rules
-        if engine.kind != _ffi.ENV_TICKER:
-            raise ValueError("the Ticker rule baseline exists for the Ticker env only")
-        self.eng = engine
+        self._open(engine, "ENV_TICKER", "the Ticker rule baseline exists for the Ticker env only")
         self.rules = check_ticker_rules(rules)
-        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
-        if self.max_episode_steps < 1:
-            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
-        self.stats = None
+        self._steps(max_episode_steps)
 
     def run(self, trace_env=None):
         """Play every (env, rule) pair; returns (and keeps) the statistics of _ffi_tickersweep.ticker_sweep."""
@@ -295,16 +283,14 @@ class TickerRuleBaseline(object):
 
     def best_total(self):
         """(rule_index, the six parameters, mean over the envs of the episode's total reward) of the best rule."""
-        if self.stats is None:
-            self.run()
-        return select_best_ticker_rule(self.rules, self.stats["total"])
+        return select_best_ticker_rule(self.rules, self._stats()["total"])
 
 
 # rows of the price table known beyond the one the trade executes at; 0: every row of the episode (the ceiling)
 DEFAULT_TICKER_HORIZONS = (1, 2, 4, 16, 64, 0)
 
 
-class TickerForesightCeiling(object):
+class TickerForesightCeiling(_EngineBaseline):
     """The other end of the Ticker env's scale: what a trader who knows the coming rows of the price table earns, every (env,
     horizon) pair a whole episode in one kernel launch (include/goldsrl_tickerforesight.h).  The env is played on a fixed table
     and its account is linear in (cash, q0, q1), so the best any policy could have done on an episode is exact: horizon 0 knows
@@ -313,16 +299,10 @@ class TickerForesightCeiling(object):
     reference has no counterpart.  run() plays from the engine's CURRENT state and leaves it as it was; it does not reset."""
 
     def __init__(self, engine, horizons=DEFAULT_TICKER_HORIZONS, max_episode_steps=None):
-        from . import _ffi
         from ._ffi_tickerforesight import check_ticker_horizons
-        if engine.kind != _ffi.ENV_TICKER:
-            raise ValueError("the foresight ceiling exists for the Ticker env only")
-        self.eng = engine
+        self._open(engine, "ENV_TICKER", "the foresight ceiling exists for the Ticker env only")
         self.horizons = check_ticker_horizons(horizons)
-        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
-        if self.max_episode_steps < 1:
-            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
-        self.stats = None
+        self._steps(max_episode_steps)
 
     def run(self, trace_env=None):
         """Play every (env, horizon) pair; returns (and keeps) the statistics of _ffi_tickerforesight.ticker_foresight."""
@@ -335,15 +315,11 @@ class TickerForesightCeiling(object):
         whole = np.flatnonzero(self.horizons == 0)
         if len(whole) == 0:
             raise ValueError("the ceiling is the column of horizon 0 (the whole episode), and the horizons hold none")
-        if self.stats is None:
-            self.run()
-        return float(self.stats["total"][whole[0]].mean())
+        return float(self._stats()["total"][whole[0]].mean())
 
     def table(self):
         """One row per horizon, in the order given: (horizon, mean total reward, mean length, mean trades) over the envs."""
-        if self.stats is None:
-            self.run()
-        s = self.stats
+        s = self._stats()
         return [(int(h), float(s["total"][i].mean()), float(s["length"][i].mean()), float(s["trades"][i].mean()))
                 for i, h in enumerate(self.horizons)]
 
@@ -369,7 +345,7 @@ def select_best_swarm_rule(rules, totals):
     return i, tuple(float(v) for v in rules[i]), float(m[i])
 
 
-class SwarmRuleBaseline(object):
+class SwarmRuleBaseline(_EngineBaseline):
     """Closed-loop feedback rules on a Swarm engine, every (env, rule) pair a whole episode in one kernel launch
     (include/goldsrl_swarmrules.h).  A rule (cancel, gain, anchor, off_x, off_y, radius) steers agent a towards
     anchor + (off_x, off_y) + radius * (cos, sin)(2 pi a / 10) with the action gain * (target - position) - (cancel, 0), clipped to
@@ -381,16 +357,10 @@ class SwarmRuleBaseline(object):
     the engine's CURRENT state (reset it first) and leaves that state as it was."""
 
     def __init__(self, engine, rules=DEFAULT_SWARM_RULES, max_episode_steps=None):
-        from . import _ffi
         from ._ffi_swarmrules import check_swarm_rules
-        if engine.kind != _ffi.ENV_SWARM:
-            raise ValueError("the Swarm rule baseline exists for the Swarm env only")
-        self.eng = engine
+        self._open(engine, "ENV_SWARM", "the Swarm rule baseline exists for the Swarm env only")
         self.rules = check_swarm_rules(rules)
-        self.max_episode_steps = int(engine.cfg.max_episode_steps if max_episode_steps is None else max_episode_steps)
-        if self.max_episode_steps < 1:
-            raise ValueError("max_episode_steps must be at least 1 (an engine without a TimeLimit has no default)")
-        self.stats = None
+        self._steps(max_episode_steps)
 
     def run(self, trace_env=None, keep_actions=False):
         """Play every (env, rule) pair; returns (and keeps) the outputs of _ffi_swarmrules.swarm_rules."""
@@ -400,6 +370,4 @@ class SwarmRuleBaseline(object):
 
     def best_total(self):
         """(rule_index, the six numbers, mean over the envs of the episode's total reward) of the best rule."""
-        if self.stats is None:
-            self.run()
-        return select_best_swarm_rule(self.rules, self.stats["totals"])
+        return select_best_swarm_rule(self.rules, self._stats()["totals"])
