@@ -87,6 +87,17 @@ struct TradeSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
+// grl_trade_foresight (trade_foresight.hip)
+struct TradeForesightState {
+    int32_t *horizons, *length, *trades;                 // (cap_h) (cap_pairs) (cap_pairs)
+    float *mn, *mx, *trace_r, *trace_act, *tape;         // (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,n) (cap_tape)
+    double *total, *sum_sq, *final_assets, *bound, *trace_a;   // (cap_pairs) x 4, (cap_trace)
+    double *path;                                        // (cap_path): (max_steps, n, E), the price path of the last call
+    uint8_t *finished, *depleted, *decisions;            // (cap_pairs) (cap_pairs) (cap_dec): (whole columns, max_steps, n, E), horizon 0's plans
+    size_t cap_h, cap_pairs, cap_trace, cap_tape, cap_path, cap_dec;
+    int n_horizons, max_steps, trace_env;                // of the last call; n_horizons == 0: none yet
+};
+
 // grl_ticker_sweep (ticker_sweep.hip)
 struct TickerSweepState {
     float *rules, *mn, *mx, *trace_r, *trace_act;        // (cap_rules,6) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
@@ -170,6 +181,7 @@ struct grl_handle {
     grl::SwarmReplayState rpl;
     grl::SwarmRulesState srl;
     grl::TradeSweepState tsw;
+    grl::TradeForesightState tfs;
     grl::TickerSweepState ksw;
     grl::TickerForesightState kfs;
     grl::SolowDpState sdp;

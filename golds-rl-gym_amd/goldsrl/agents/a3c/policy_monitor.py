@@ -156,6 +156,27 @@ class _DeviceMonitor(object):
         self.baseline_rule, self.baseline_total_reward = (i, rule), total
         return i, rule, total
 
+    def trade_ceiling(self, horizons=None):
+        """The foresight ceiling (goldsrl/baselines.py:TradeForesightCeiling) on the monitor's own TradeAR1 eval engine: resets it
+        and plays every (env, horizon) pair in one call.  The engine's price generator moves on from one evaluation to the next, so
+        call this directly before eval_once, as rule_baseline() is: it then plays exactly the episodes that evaluation plays.
+        Keeps ceiling_total_reward -- the mean over the envs of the total reward of the trader who knows every row of its episode,
+        the unit of eval/mean_total_reward --, ceiling_table (one (horizon, mean total, mean length, mean trades) row per horizon),
+        ceiling_bound (every env's bound, (E,)) and the whole statistics in ceiling_stats; leaves the engine reset.  Returns
+        ceiling_total_reward."""
+        from ... import _ffi
+        from ...baselines import DEFAULT_TRADE_HORIZONS, TradeForesightCeiling
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_TRADE:
+            raise ValueError("the foresight ceiling of TradeAR1 exists for the TradeAR1 env only")
+        c = TradeForesightCeiling(eng, DEFAULT_TRADE_HORIZONS if horizons is None else horizons, self.max_episode_steps)
+        eng.reset()
+        self.ceiling_stats = c.run()
+        self.ceiling_table = c.table()
+        self.ceiling_total_reward = c.ceiling()
+        self.ceiling_bound = c.bound()
+        return self.ceiling_total_reward
+
     def write_baseline_scalars(self, global_step):
         """eval/baseline_total_reward and eval/mean_total_reward_minus_baseline of the last evaluation (after baseline() or
         rule_baseline()); after optimal() also eval/optimal_total_reward and, with both ends known,
@@ -172,6 +193,18 @@ class _DeviceMonitor(object):
             w.add_scalar("eval/optimal_total_reward", ceiling, global_step)
             if floor is not None and self.log["mean_total_reward"] and ceiling != floor:
                 w.add_scalar("eval/mean_total_reward_share_of_gap", (self.log["mean_total_reward"][-1] - floor) / (ceiling - floor), global_step)
+        w.flush()
+
+    def write_ceiling_scalars(self, global_step):
+        """eval/ceiling_total_reward (after ticker_ceiling() or trade_ceiling()) and, with the rule baseline's floor and an
+        evaluation, eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline) of the last evaluation"""
+        w, ceiling = self.summary_writer, getattr(self, "ceiling_total_reward", None)
+        if w is None or ceiling is None:
+            return
+        w.add_scalar("eval/ceiling_total_reward", ceiling, global_step)
+        floor = getattr(self, "baseline_total_reward", None)
+        if floor is not None and self.log["mean_total_reward"] and ceiling != floor:
+            w.add_scalar("eval/mean_total_reward_share_of_gap", (self.log["mean_total_reward"][-1] - floor) / (ceiling - floor), global_step)
         w.flush()
 
     def write_log(self, total_reward_log_file):
@@ -274,18 +307,6 @@ class GatedPolicyMonitor(_DeviceMonitor):
         self.ceiling_table = c.table()
         self.ceiling_total_reward = c.ceiling()
         return self.ceiling_total_reward
-
-    def write_ceiling_scalars(self, global_step):
-        """eval/ceiling_total_reward (after ticker_ceiling()) and, with ticker_baseline()'s floor and an evaluation,
-        eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline) of the last evaluation"""
-        w, ceiling = self.summary_writer, getattr(self, "ceiling_total_reward", None)
-        if w is None or ceiling is None:
-            return
-        w.add_scalar("eval/ceiling_total_reward", ceiling, global_step)
-        floor = getattr(self, "baseline_total_reward", None)
-        if floor is not None and self.log["mean_total_reward"] and ceiling != floor:
-            w.add_scalar("eval/mean_total_reward_share_of_gap", (self.log["mean_total_reward"][-1] - floor) / (ceiling - floor), global_step)
-        w.flush()
 
 
 class GridPolicyMonitor(_DeviceMonitor):

@@ -22,6 +22,9 @@ counterpart in the reference either.
 TickerForesightCeiling is the other end of the Ticker env's scale: a trader who knows the next H rows of the price table, or every
 row of the episode, every (env, horizon) pair in one kernel launch (include/goldsrl_tickerforesight.h).  No counterpart either.
 
+TradeForesightCeiling is the other end of TradeAR1's scale: a trader who knows the next H rows of its price path, or every row of
+the episode, every (env, horizon) pair in one call (include/goldsrl_tradeforesight.h).  No counterpart either.
+
 SwarmRuleBaseline is Swarm's closed-loop yardstick: feedback rules that steer the agents relative to the swarm's centroid or to
 their nearest locust, every (env, rule) pair in one kernel launch with the action computed on the device
 (include/goldsrl_swarmrules.h).  Its first two rules are ScriptedSwarmBaseline's scripts.  No counterpart in the reference."""
@@ -66,7 +69,7 @@ def _solow_engine(what, env, n_envs, device_id, max_episode_steps, engine):
 
 
 class _EngineBaseline(object):
-    """What the baselines share: statistics that are played once (_stats, the two Solow classes' too) and, for the five that take
+    """What the baselines share: statistics that are played once (_stats, the two Solow classes' too) and, for the six that take
     the caller's engine, the kind check (_open) and the episode length with its default (_steps)."""
 
     def _open(self, engine, kind, refusal):
@@ -235,6 +238,56 @@ class TradingRuleBaseline(_EngineBaseline):
     def best_total(self):
         """(rule_index, (gain, bias), mean over the envs of the episode's total reward) of the best rule."""
         return select_best_rule(self.rules, self._stats()["total"])
+
+
+# rows of the price path known beyond the one the trade executes at; 0: every row of the episode (the ceiling).  Horizon 64 is
+# 23.3 of the default call's 23.5 ms (8 192 envs x 2 assets x 1 024 steps, profiles/trade_foresight_times.json) and earns 7e-9 more
+# than horizon 16 there; it stays, as in DEFAULT_TICKER_HORIZONS: the whole call is a tenth of one policy evaluation (228 ms)
+DEFAULT_TRADE_HORIZONS = (1, 2, 4, 16, 64, 0)
+
+
+class TradeForesightCeiling(_EngineBaseline):
+    """The other end of TradeAR1's scale: what a trader who knows the coming rows of its price path earns, every (env, horizon)
+    pair a whole episode in one call (include/goldsrl_tradeforesight.h).  The price path does not depend on the actions, the
+    account is linear in (cash, q) and there is no spread, so the best any policy could have done on an episode is exact: horizon
+    0 knows every row and its total is the ceiling of eval/total_reward; a horizon H knows H rows beyond the current one and says
+    what that much foresight is worth.  The gap between TradingRuleBaseline's best rule and the ceiling is what there was to
+    learn.  The reference has no counterpart.  run() plays from the engine's CURRENT state and leaves it as it was; it does not
+    reset -- the price generator's counters move on from one episode to the next, so when to reset is the caller's affair."""
+
+    def __init__(self, engine, horizons=DEFAULT_TRADE_HORIZONS, max_episode_steps=None):
+        from ._ffi_tradeforesight import check_trade_horizons
+        self._open(engine, "ENV_TRADE", "the foresight ceiling of TradeAR1 exists for the TradeAR1 env only")
+        self.horizons = check_trade_horizons(horizons)
+        self._steps(max_episode_steps)
+
+    def run(self, trace_env=None, normals=None):
+        """Play every (env, horizon) pair; returns (and keeps) the statistics of _ffi_tradeforesight.trade_foresight."""
+        from . import _ffi_tradeforesight
+        self.stats = _ffi_tradeforesight.trade_foresight(self.eng, self.horizons, self.max_episode_steps, trace_env, normals)
+        return self.stats
+
+    def _whole(self):
+        whole = np.flatnonzero(self.horizons == 0)
+        if len(whole) == 0:
+            raise ValueError("the ceiling is the column of horizon 0 (the whole episode), and the horizons hold none")
+        return int(whole[0])
+
+    def ceiling(self):
+        """The mean over the envs of the whole-episode column's total reward, the unit of eval/mean_total_reward."""
+        whole = self._whole()
+        return float(self._stats()["total"][whole].mean())
+
+    def bound(self):
+        """Every env's bound (E,) float64: no policy's total on that env's episode is above it."""
+        whole = self._whole()
+        return self._stats()["bound"][whole].copy()
+
+    def table(self):
+        """One row per horizon, in the order given: (horizon, mean total reward, mean length, mean trades) over the envs."""
+        s = self._stats()
+        return [(int(h), float(s["total"][i].mean()), float(s["length"][i].mean()), float(s["trades"][i].mean()))
+                for i, h in enumerate(self.horizons)]
 
 
 def _ticker_rules():

@@ -7,7 +7,10 @@ TF-events file, the checkpoint to <model_dir>/checkpoint.npz.  With --eval-every
 scripts/train_trade.py:94-124 runs on the device (goldsrl/agents/a3c/policy_monitor.py): every N updates M greedy episodes of
 `TradeAR1-v0` in one kernel launch, action tanh(mu); totals go to TradeAR1.json and the eval/* scalars.  With --baseline the
 scripted trading rules of goldsrl/baselines.py play the same episodes directly before every evaluation (one more launch): the best
-rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written.  Training is untouched."""
+rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written.  With --ceiling the foresight
+traders of goldsrl/baselines.py:TradeForesightCeiling play the same episodes directly before every evaluation too (one more call):
+the mean total of every horizon is logged, eval/ceiling_total_reward -- the trader who knows every row of its episode -- is written,
+and with --baseline also eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline).  Training is untouched."""
 import argparse
 import logging
 import os
@@ -38,6 +41,10 @@ def get_arg_parser():
     p.add_argument("--baseline", action="store_true",
                    help="play the scripted trading rules on the eval envs directly before every evaluation (one kernel launch) and write "
                         "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline (needs --eval-every and --eval-envs)")
+    p.add_argument("--ceiling", action="store_true",
+                   help="play the foresight traders on the eval envs directly before every evaluation (one more call) and write "
+                        "eval/ceiling_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap (needs --eval-every and "
+                        "--eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -51,6 +58,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.baseline and not (args.eval_envs > 0 and args.eval_every > 0):
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
+    if args.ceiling and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--ceiling plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
     return args
 
 
@@ -89,10 +98,16 @@ def main(argv=None):
             if args.baseline:       # the price generator moves on between evaluations: the rules must see this evaluation's prices
                 i, (gain, bias), total = monitor.rule_baseline()
                 logging.info("Trading-rule baseline on the eval envs: rule %d (gain %.6g, bias %.6g), mean total_reward %.6g", i, gain, bias, total)
+            if args.ceiling:        # likewise: this evaluation's prices
+                monitor.trade_ceiling()
+                logging.info("TradeAR1 foresight on the eval envs, mean total_reward by rows known ahead: %s",
+                             ", ".join("%s %.6g" % ("whole episode" if h == 0 else str(h), tot) for h, tot, _, _ in monitor.ceiling_table))
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             monitor.write_scalars(step)
             if args.baseline:
                 monitor.write_baseline_scalars(step)
+            if args.ceiling:
+                monitor.write_ceiling_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
                          episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
