@@ -8,6 +8,7 @@
 
 #include "../../include/goldsrl.h"
 #include "../../include/goldsrl_solowdp.h"
+#include "episode_dev.h"
 
 namespace grl {
 
@@ -65,55 +66,58 @@ struct TickerState {
 
 // The states of the whole-episode launches (host scaffold: episode_host.h).  Every buffer in them is allocated on first use, grown
 // (episode_reserve, by the cap_* group the comment beside it names) when a later call is larger, and listed in grl_handle::allocs so
-// grl_destroy frees it; the int fields at the end describe the last call and are what grl_*_read sizes its outputs by.
+// grl_destroy frees it; the int fields at the end describe the last call and are what grl_*_read sizes its outputs by.  `stats`
+// (episode_dev.h) is the six per-pair statistics buffers, of the cap_pairs group (cap_envs in SolowDpState).
 
 // grl_solow_sweep (solow_sweep.hip)
 struct SolowSweepState {
-    float *rates, *mn, *mx, *trace_r, *trace_k;   // (cap_rates) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace)
-    double *total, *sum_sq;                       // (cap_pairs)
-    int32_t *length, *err;                        // (cap_pairs) (1)
-    uint8_t *finished;                            // (cap_pairs)
+    PairStats stats;
+    float *rates, *trace_r, *trace_k;             // (cap_rates) (cap_trace) (cap_trace)
+    int32_t *err;                                 // (1)
     size_t cap_rates, cap_pairs, cap_trace;
     int n_rates, max_steps, trace_env;            // of the last sweep; n_rates == 0: none yet
 };
 
 // grl_trade_sweep (trade_sweep.hip)
 struct TradeSweepState {
-    float *gains, *biases, *mn, *mx, *trace_r, *tape;   // (cap_rules) (cap_rules) (cap_pairs) (cap_pairs) (cap_trace) (cap_tape)
-    double *total, *sum_sq, *final_assets, *trace_a;     // (cap_pairs) (cap_pairs) (cap_pairs) (cap_trace)
-    int32_t *length;                                     // (cap_pairs)
-    uint8_t *finished, *depleted;                        // (cap_pairs)
+    PairStats stats;
+    float *gains, *biases, *trace_r, *tape;              // (cap_rules) (cap_rules) (cap_trace) (cap_tape)
+    double *final_assets, *trace_a;                      // (cap_pairs) (cap_trace)
+    uint8_t *depleted;                                   // (cap_pairs)
     size_t cap_rules, cap_pairs, cap_trace, cap_tape;
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
 // grl_trade_foresight (trade_foresight.hip)
 struct TradeForesightState {
-    int32_t *horizons, *length, *trades;                 // (cap_h) (cap_pairs) (cap_pairs)
-    float *mn, *mx, *trace_r, *trace_act, *tape;         // (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,n) (cap_tape)
-    double *total, *sum_sq, *final_assets, *bound, *trace_a;   // (cap_pairs) x 4, (cap_trace)
+    PairStats stats;
+    int32_t *horizons, *trades;                          // (cap_h) (cap_pairs)
+    float *trace_r, *trace_act, *tape;                   // (cap_trace) (cap_trace,n) (cap_tape)
+    double *final_assets, *bound, *trace_a;              // (cap_pairs) (cap_pairs) (cap_trace)
     double *path;                                        // (cap_path): (max_steps, n, E), the price path of the last call
-    uint8_t *finished, *depleted, *decisions;            // (cap_pairs) (cap_pairs) (cap_dec): (whole columns, max_steps, n, E), horizon 0's plans
+    uint8_t *depleted, *decisions;                       // (cap_pairs) (cap_dec): (whole columns, max_steps, n, E), horizon 0's plans
     size_t cap_h, cap_pairs, cap_trace, cap_tape, cap_path, cap_dec;
     int n_horizons, max_steps, trace_env;                // of the last call; n_horizons == 0: none yet
 };
 
 // grl_ticker_sweep (ticker_sweep.hip)
 struct TickerSweepState {
-    float *rules, *mn, *mx, *trace_r, *trace_act;        // (cap_rules,6) (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
-    double *total, *sum_sq, *final_assets, *trace_a;     // (cap_pairs) (cap_pairs) (cap_pairs) (cap_trace)
-    int32_t *length, *trades;                            // (cap_pairs)
-    uint8_t *finished, *depleted;                        // (cap_pairs)
+    PairStats stats;
+    float *rules, *trace_r, *trace_act;                  // (cap_rules,6) (cap_trace) (cap_trace,4)
+    double *final_assets, *trace_a;                      // (cap_pairs) (cap_trace)
+    int32_t *trades;                                     // (cap_pairs)
+    uint8_t *depleted;                                   // (cap_pairs)
     size_t cap_rules, cap_pairs, cap_trace;
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
 // grl_ticker_foresight (ticker_foresight.hip)
 struct TickerForesightState {
-    int32_t *horizons, *length, *trades;                 // (cap_h) (cap_pairs) (cap_pairs)
-    float *mn, *mx, *trace_r, *trace_act;                // (cap_pairs) (cap_pairs) (cap_trace) (cap_trace,4)
-    double *total, *sum_sq, *final_assets, *bound, *trace_a;   // (cap_pairs) x 4, (cap_trace)
-    uint8_t *finished, *depleted, *decisions;            // (cap_pairs) (cap_pairs) (cap_dec): (max_steps, pairs), horizon 0's plan
+    PairStats stats;
+    int32_t *horizons, *trades;                          // (cap_h) (cap_pairs)
+    float *trace_r, *trace_act;                          // (cap_trace) (cap_trace,4)
+    double *final_assets, *bound, *trace_a;              // (cap_pairs) (cap_pairs) (cap_trace)
+    uint8_t *depleted, *decisions;                       // (cap_pairs) (cap_dec): (max_steps, pairs), horizon 0's plan
     size_t cap_h, cap_pairs, cap_trace, cap_dec;
     int n_horizons, max_steps, trace_env;                // of the last call; n_horizons == 0: none yet
 };
@@ -127,10 +131,9 @@ struct SolowDpState {
     size_t cap_states, cap_table;
     int horizon, ne;                              // horizon == 0: no table yet
     bool has_value;                               // v[0] holds stage 0's value (a solve, not a set_policy)
-    double *total, *sum_sq;                       // (cap_envs)
-    float *mn, *mx, *trace_a, *trace_r, *trace_k; // (cap_envs) (cap_envs) (cap_trace) x 3
-    int32_t *length, *err;                        // (cap_envs) (1)
-    uint8_t *finished;                            // (cap_envs)
+    PairStats stats;                              // a pair is an env here
+    float *trace_a, *trace_r, *trace_k;           // (cap_trace) x 3
+    int32_t *err;                                 // (1)
     size_t cap_envs, cap_trace;
     int played, trace_steps;                      // of the last play; played == 0: none yet
 };

@@ -1,7 +1,8 @@
 // The host scaffold the whole-episode launches share (solow_sweep.hip, trade_sweep.hip, trade_foresight.hip, ticker_sweep.hip,
 // ticker_foresight.hip, solow_dp.hip, swarm_replay.hip, swarm_rules.hip): one copy of what their entry points do alike -- the opening checks, the
 // argument checks with the entry point's name in the message, growing a capacity group of buffers, the profiled launch and the
-// table-driven grl_*_read.  The kernels, their parameter structs and what a launch uploads and clears stay in the .hip files.
+// table-driven grl_*_read.  The kernels, their parameter structs and what a launch uploads and clears stay in the .hip files; the
+// device half of the per-pair statistics six of them keep (RewardStats, PairStats) is the sibling header episode_dev.h.
 // Included behind common.h; static: every including translation unit has its own copy.  Functions take the C function's name:
 // every message starts with it.
 #pragma once
@@ -50,14 +51,19 @@ static EpisodeBuf buf(T *&p, size_t per = 1) { return EpisodeBuf{(void **)&p, pe
 
 // Grows the buffers of one capacity group to `need` units when that is more than `cap`.  The stream is drained first (a kernel
 // in flight may still use what is freed; a later group's drain finds the stream empty), and only if the group grows.  cap is 0
-// from before the first grow until after the last, so a failed hipMalloc leaves no stale capacity behind.
-static int episode_reserve(grl_handle *h, size_t &cap, size_t need, std::initializer_list<EpisodeBuf> bufs) {
+// from before the first grow until after the last, so a failed hipMalloc leaves no stale capacity behind.  stats: null, or the six
+// statistics buffers of the pairs, which belong to this group too.
+static int episode_reserve(grl_handle *h, size_t &cap, size_t need, std::initializer_list<EpisodeBuf> bufs, PairStats *stats = nullptr) {
     if (need <= cap) return GRL_OK;
     GRL_HIP(h, hipStreamSynchronize(h->stream));
     cap = 0;
-    for (const EpisodeBuf &b : bufs) {
-        const int rc = grow(h, (uint8_t **)b.p, need * b.bytes);
-        if (rc) return rc;
+    int rc;
+    for (const EpisodeBuf &b : bufs)
+        if ((rc = grow(h, (uint8_t **)b.p, need * b.bytes))) return rc;
+    if (stats) {
+        const EpisodeBuf six[] = {buf(stats->total), buf(stats->sum_sq), buf(stats->mn), buf(stats->mx), buf(stats->length), buf(stats->finished)};
+        for (const EpisodeBuf &b : six)
+            if ((rc = grow(h, (uint8_t **)b.p, need * b.bytes))) return rc;
     }
     cap = need;
     return GRL_OK;
@@ -79,10 +85,12 @@ static int episode_launch(grl_handle *h, F &&launch) {
 struct EpisodeOut { const char *name; const void *src; size_t bytes; const char *absent; };
 
 // The whole of a grl_*_read behind its table.  called: the launch has run (else GRL_E_STATE "call `first` first"); err_dev: null
-// or the launch's own device counter of envs that ran off the Solow shock tape, checked after the drain.
+// or the launch's own device counter of envs that ran off the Solow shock tape, checked after the drain.  stats: null, or the
+// statistics of the last call's `pairs` pairs, read as "total", "sum_sq", "min", "max", "length" and "finished".
 template <size_t N>
 static int episode_read(grl_handle *h, const char *fn, int kind, const char *kind_word, bool called, const char *first,
-                        const EpisodeOut (&outs)[N], const int32_t *err_dev, const char *which, void *host, size_t bytes) {
+                        const EpisodeOut (&outs)[N], const int32_t *err_dev, const char *which, void *host, size_t bytes,
+                        const PairStats *stats = nullptr, size_t pairs = 0) {
     int rc = episode_open(h, fn, kind, kind_word, which && host);
     if (rc) return rc;
     const std::string f(fn);
@@ -92,6 +100,13 @@ static int episode_read(grl_handle *h, const char *fn, int kind, const char *kin
     const EpisodeOut *o = nullptr;
     for (const EpisodeOut &e : outs)
         if (s == e.name) o = &e;
+    EpisodeOut stat{};                                         // a copy: the six rows end with their block
+    if (stats) {
+        const EpisodeOut six[] = {{"total", stats->total, pairs * 8}, {"sum_sq", stats->sum_sq, pairs * 8}, {"min", stats->mn, pairs * 4},
+                                  {"max", stats->mx, pairs * 4}, {"length", stats->length, pairs * 4}, {"finished", stats->finished, pairs}};
+        for (const EpisodeOut &e : six)
+            if (s == e.name) { stat = e; o = &stat; }
+    }
     if (!o) return fail(h, GRL_E_INVALID, f + ": unknown output '" + s + "'");
     if (o->absent) return fail(h, GRL_E_STATE, f + ": " + o->absent);
     if (o->bytes != bytes) return fail(h, GRL_E_SIZE, f + ": '" + s + "' needs " + std::to_string(o->bytes) + " bytes, got " + std::to_string(bytes));

@@ -4,6 +4,7 @@
 // the TradeAR1 observation transform.  Reference: fed_gym/envs/fed_env.py:161-334,
 // fed_gym/agents/paac/emulator_runner.py:48-65.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "rng.h"
 
@@ -348,5 +349,75 @@ __device__ __forceinline__ void trade_price_normals(uint64_t seed, uint32_t env_
     normal_pair(rng_block(seed, env_id, 0u, RS_TRADE_PRICE, st * (uint32_t)pairs + (uint32_t)pr), z0, z1);
 }
 
+// ---- the asset tiers of the whole-episode TradeAR1 kernels (trade_sweep.hip, trade_foresight.hip): up to 16 assets live in
+// registers, in compile-time tiers NT = 2 / 4 / 8 / 16; from 17 to 64 (NT = 0) in LDS columns or global memory.
+// f(a) for a = 0 .. n-1: unrolled to NT slots under a uniform guard (registers), or a plain loop (NT = 0)
+template <int NT, class F>
+__device__ __forceinline__ void trade_for(int n, F f) {
+    if constexpr (NT > 0) {
+#pragma unroll
+        for (int a = 0; a < NT; ++a)
+            if (a < n) f(a);
+    } else {
+        for (int a = 0; a < n; ++a) f(a);
+    }
+}
+
+// _price_transition of every asset of `env` by the draws of step index t: row t of the tape (t, n, E), or the generator at
+// st0 + t.  get(a) reads, put(a, p) writes asset a's price; pairs = (n + 1) / 2.  trade_path_kernel keeps a written-out twin.
+template <int NT, class G, class P>
+__device__ __forceinline__ void trade_prices_step(const TradeParams &R, const float *__restrict__ tape, int env, uint32_t st0, int t, int pairs, G get, P put) {
+    const size_t E = R.E;
+    const int n = R.n;
+    const uint32_t st = st0 + (uint32_t)t;
+    trade_for<(NT + 1) / 2>(pairs, [&](int k) {
+        const int a = 2 * k;
+        double z0, z1 = 0.0;
+        if (tape) {
+            z0 = (double)tape[((size_t)t * n + a) * E + env];
+            if (a + 1 < n) z1 = (double)tape[((size_t)t * n + a + 1) * E + env];
+        } else {
+            trade_price_normals(R.seed, (uint32_t)env + R.env_off, st, pairs, k, z0, z1);   // an odd n discards the last z1
+        }
+        put(a, trade_price_next(get(a), R.std_e, z0));
+        if (a + 1 < n) put(a + 1, trade_price_next(get(a + 1), R.std_e, z1));       // NT is even: slot a + 1 exists
+    });
+}
+
+constexpr int TRADE_LDS_BYTES = 160 * 1024;      // of a CU
+
+// ---- host half of the same two launches, no device code from here on.  The tier of n assets: pick(std::integral_constant<int,
+// NT>) takes the caller's instantiation(s) and returns the kernel that keeps its columns in dynamic LDS, wave_bytes per wave.
+// Registers: 4 waves a workgroup, no LDS.  NT = 0: as many waves (4 at most) as fit in the CU's LDS, all of which it is allowed.
+template <class F>
+static int trade_tier(grl_handle *h, int n, size_t wave_bytes, int &waves, size_t &lds, F pick) {
+    waves = 4; lds = 0;
+    if (n <= 2) pick(std::integral_constant<int, 2>{});
+    else if (n <= 4) pick(std::integral_constant<int, 4>{});
+    else if (n <= 8) pick(std::integral_constant<int, 8>{});
+    else if (n <= 16) pick(std::integral_constant<int, 16>{});
+    else {
+        const void *kern = pick(std::integral_constant<int, 0>{});
+        waves = (int)std::min<size_t>(4, TRADE_LDS_BYTES / wave_bytes);
+        lds = wave_bytes * waves;
+        GRL_HIP(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, TRADE_LDS_BYTES));
+    }
+    return GRL_OK;
+}
+
+// The tape of normals a whole-episode call may bring.  A handle with GRL_F_INJECT_NOISE has no generator to fall back on:
+static int trade_tape_check(grl_handle *h, const char *fn, const float *normals_host) {
+    if (!normals_host && (h->cfg.flags & GRL_F_INJECT_NOISE))
+        return fail(h, GRL_E_INVALID, std::string(fn) + ": a handle with GRL_F_INJECT_NOISE holds the normals of one step; pass a tape");
+    return GRL_OK;
+}
+
+// cells floats to the device (none: no tape); drained, so the tape is the caller's again when the call returns
+static int trade_tape_upload(grl_handle *h, float *tape_dev, const float *normals_host, size_t cells) {
+    if (!cells) return GRL_OK;
+    GRL_HIP(h, hipMemcpyAsync(tape_dev, normals_host, cells * 4, hipMemcpyHostToDevice, h->stream));
+    GRL_HIP(h, hipStreamSynchronize(h->stream));
+    return GRL_OK;
+}
 
 }  // namespace grl

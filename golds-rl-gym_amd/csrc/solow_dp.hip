@@ -101,10 +101,7 @@ __global__ __launch_bounds__(256) void solow_dp_stage_kernel(DpArgs A, const dou
 }
 
 struct DpPlayOut {
-    double *total, *sum_sq;
-    float *mn, *mx;
-    int32_t *length;
-    uint8_t *finished;
+    PairStats stats;
     float *trace_a, *trace_r, *trace_k;
 };
 
@@ -135,8 +132,8 @@ __global__ __launch_bounds__(64) void solow_dp_play_kernel(SolowParams S, SolowS
     const int env = blockIdx.x * 64 + threadIdx.x;          // a wave per workgroup: the waves spread over the CUs
     if (env >= S.E) return;
     const size_t E = S.E;
-    float k = S.k[env], mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
-    double tot = 0.0, ssq = 0.0;
+    float k = S.k[env];
+    RewardStats rs;
     float zr[8], er[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -159,10 +156,7 @@ __global__ __launch_bounds__(64) void solow_dp_play_kernel(SolowParams S, SolowS
         const float s = dp_policy_action(A, policy + (size_t)stage * A.n_states, k, zr[7], er[7]);
         const float ez = expf(zr[7]);
         const float rew = solow_capital_step(ez, S.delta, s, k);
-        tot += (double)rew;
-        ssq += (double)rew * (double)rew;
-        mn = fminf(mn, rew);
-        mx = fmaxf(mx, rew);
+        rs.add(rew);
         if (t < trace_steps) {
             const size_t o = (size_t)t * E + env;
             O.trace_a[o] = s; O.trace_r[o] = rew; O.trace_k[o] = k;
@@ -172,10 +166,7 @@ __global__ __launch_bounds__(64) void solow_dp_play_kernel(SolowParams S, SolowS
         length = t + 1;
         if (S.max_steps > 0 && el0 + length >= S.max_steps) { finished = true; break; }
     }
-    O.total[env] = tot; O.sum_sq[env] = ssq;
-    O.mn[env] = mn; O.mx[env] = mx;
-    O.length[env] = length;
-    O.finished[env] = finished ? 1 : 0;
+    O.stats.store(env, rs, length, finished);
 }
 
 // the checks grl_solow_dp_solve and grl_solow_dp_set_policy share; fills A
@@ -310,7 +301,7 @@ int grl_solow_dp_play(grl_handle *h, int32_t max_steps, int32_t trace_steps) {
     d.played = 0;
     const size_t envs = h->E, trace = (size_t)trace_steps * envs;
     if ((!d.err && (rc = grow(h, &d.err, 1))) ||
-        (rc = episode_reserve(h, d.cap_envs, envs, {buf(d.total), buf(d.sum_sq), buf(d.mn), buf(d.mx), buf(d.length), buf(d.finished)})) ||
+        (rc = episode_reserve(h, d.cap_envs, envs, {}, &d.stats)) ||
         (rc = episode_reserve(h, d.cap_trace, trace, {buf(d.trace_a), buf(d.trace_r), buf(d.trace_k)})))
         return rc;
     GRL_HIP(h, hipMemsetAsync(d.err, 0, 4, h->stream));
@@ -323,7 +314,8 @@ int grl_solow_dp_play(grl_handle *h, int32_t max_steps, int32_t trace_steps) {
     S.err_flag = d.err;
     const SolowShockCoef C = solow_shock_coef(S);
     const DpArgs A = dp_kept(h);
-    DpPlayOut O{d.total, d.sum_sq, d.mn, d.mx, d.length, d.finished, d.trace_a, d.trace_r, d.trace_k};
+    DpPlayOut O{};
+    O.stats = d.stats; O.trace_a = d.trace_a; O.trace_r = d.trace_r; O.trace_k = d.trace_k;
     rc = episode_launch(h, [&] {
         hipLaunchKernelGGL(solow_dp_play_kernel, dim3((h->E + 63) / 64), dim3(64), 0, h->stream, S, C, A, d.policy, d.horizon, max_steps, trace_steps, O);
     });
@@ -338,10 +330,8 @@ int grl_solow_dp_play_read(grl_handle *h, const char *which, void *host, size_t 
     const size_t envs = h->E, trace = (size_t)d.trace_steps * envs;
     const char *untraced = d.trace_steps == 0 ? "the last play kept no trace (trace_steps was 0)" : nullptr;
     const EpisodeOut outs[] = {
-        {"total", d.total, envs * 8}, {"sum_sq", d.sum_sq, envs * 8}, {"min", d.mn, envs * 4}, {"max", d.mx, envs * 4},
-        {"length", d.length, envs * 4}, {"finished", d.finished, envs},
         {"actions", d.trace_a, trace * 4, untraced}, {"rewards", d.trace_r, trace * 4, untraced}, {"k", d.trace_k, trace * 4, untraced}};
-    return episode_read(h, "grl_solow_dp_play_read", GRL_ENV_SOLOW, "Solow", d.played != 0, "grl_solow_dp_play", outs, d.err, which, host, bytes);
+    return episode_read(h, "grl_solow_dp_play_read", GRL_ENV_SOLOW, "Solow", d.played != 0, "grl_solow_dp_play", outs, d.err, which, host, bytes, &d.stats, envs);
 }
 
 }  // extern "C"

@@ -22,10 +22,7 @@
 namespace grl {
 
 struct SweepOut {
-    double *total, *sum_sq;
-    float *mn, *mx;
-    int32_t *length;
-    uint8_t *finished;
+    PairStats stats;
     float *trace_r, *trace_k;
 };
 
@@ -38,14 +35,13 @@ __global__ __launch_bounds__(256) void solow_sweep_kernel(SolowParams S, SolowSh
     if (r0 >= n_rates || env >= S.E) return;
     const size_t E = S.E;
 
-    float rate[RPL], k[RPL], mn[RPL], mx[RPL];
-    double tot[RPL], ssq[RPL];
+    float rate[RPL], k[RPL];
+    RewardStats rs[RPL];
     const float k0 = S.k[env];
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
         rate[j] = rates[r0 + j < n_rates ? r0 + j : n_rates - 1];      // a ragged tail replays the last rate and stores nothing
-        k[j] = k0; tot[j] = 0.0; ssq[j] = 0.0;
-        mn[j] = __builtin_huge_valf(); mx[j] = -__builtin_huge_valf();
+        k[j] = k0;
     }
     float zr[8], er[8];
 #pragma unroll
@@ -69,10 +65,7 @@ __global__ __launch_bounds__(256) void solow_sweep_kernel(SolowParams S, SolowSh
 #pragma unroll
         for (int j = 0; j < RPL; ++j) {
             const float rew = solow_capital_step(ez, S.delta, rate[j], k[j]);
-            tot[j] += (double)rew;
-            ssq[j] += (double)rew * (double)rew;
-            mn[j] = fminf(mn[j], rew);
-            mx[j] = fmaxf(mx[j], rew);
+            rs[j].add(rew);
             if (trace && r0 + j < n_rates) {
                 O.trace_r[(size_t)(r0 + j) * max_steps + t] = rew;
                 O.trace_k[(size_t)(r0 + j) * max_steps + t] = k[j];
@@ -85,13 +78,7 @@ __global__ __launch_bounds__(256) void solow_sweep_kernel(SolowParams S, SolowSh
     }
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
-        if (r0 + j < n_rates) {
-            const size_t o = (size_t)(r0 + j) * E + env;
-            O.total[o] = tot[j]; O.sum_sq[o] = ssq[j];
-            O.mn[o] = mn[j]; O.mx[o] = mx[j];
-            O.length[o] = length;
-            O.finished[o] = finished ? 1 : 0;
-        }
+        if (r0 + j < n_rates) O.stats.store((size_t)(r0 + j) * E + env, rs[j], length, finished);
     }
 }
 
@@ -122,7 +109,7 @@ int grl_solow_sweep(grl_handle *h, const float *rates_host, int32_t n_rates, int
     w.n_rates = 0;
     const size_t pairs = (size_t)n_rates * h->E, trace = trace_env >= 0 ? (size_t)n_rates * max_steps : 0;
     if ((!w.err && (rc = grow(h, &w.err, 1))) || (rc = episode_reserve(h, w.cap_rates, n_rates, {buf(w.rates)})) ||
-        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.mn), buf(w.mx), buf(w.length), buf(w.finished)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {}, &w.stats)) ||
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_k)})))
         return rc;
     GRL_HIP(h, hipMemcpyAsync(w.rates, rates_host, (size_t)n_rates * 4, hipMemcpyHostToDevice, h->stream));
@@ -134,7 +121,8 @@ int grl_solow_sweep(grl_handle *h, const float *rates_host, int32_t n_rates, int
     SolowParams S = solow_params(h);
     S.err_flag = w.err;
     const SolowShockCoef C = solow_shock_coef(S);
-    SweepOut O{w.total, w.sum_sq, w.mn, w.mx, w.length, w.finished, w.trace_r, w.trace_k};
+    SweepOut O{};
+    O.stats = w.stats; O.trace_r = w.trace_r; O.trace_k = w.trace_k;
     const int rpl = sweep_rpl();
     const int groups = (n_rates + rpl - 1) / rpl;
     const dim3 grid((h->E + 63) / 64, (groups + 3) / 4), block(256);
@@ -153,11 +141,8 @@ int grl_solow_sweep_read(grl_handle *h, const char *which, void *host, size_t by
     const SolowSweepState &w = h->swp;
     const size_t pairs = (size_t)w.n_rates * h->E, trace = (size_t)w.n_rates * w.max_steps;
     const char *untraced = w.trace_env < 0 ? "the last sweep traced no env (trace_env was -1)" : nullptr;
-    const EpisodeOut outs[] = {
-        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4},
-        {"length", w.length, pairs * 4}, {"finished", w.finished, pairs},
-        {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_k", w.trace_k, trace * 4, untraced}};
-    return episode_read(h, "grl_solow_sweep_read", GRL_ENV_SOLOW, "Solow", w.n_rates != 0, "grl_solow_sweep", outs, w.err, which, host, bytes);
+    const EpisodeOut outs[] = {{"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_k", w.trace_k, trace * 4, untraced}};
+    return episode_read(h, "grl_solow_sweep_read", GRL_ENV_SOLOW, "Solow", w.n_rates != 0, "grl_solow_sweep", outs, w.err, which, host, bytes, &w.stats, pairs);
 }
 
 }  // extern "C"

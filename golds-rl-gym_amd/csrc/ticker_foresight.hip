@@ -23,10 +23,10 @@
 namespace grl {
 
 struct TickerForesightOut {
-    double *total, *sum_sq, *final_assets, *bound;
-    float *mn, *mx;
-    int32_t *length, *trades;
-    uint8_t *finished, *depleted;
+    PairStats stats;
+    double *final_assets, *bound;
+    int32_t *trades;
+    uint8_t *depleted;
     float *trace_r;
     double *trace_a;
     float4 *trace_act;
@@ -94,8 +94,7 @@ __global__ __launch_bounds__(256) void ticker_foresight_kernel(TickerParams K, c
         bound = log(v + 1e-4) - la;
     }
 
-    double tot = 0.0, ssq = 0.0;
-    float mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
+    RewardStats rs;
     int length = 0, trades = 0;
     bool finished = false, depleted = false;
     const bool trace = env == trace_env;
@@ -123,10 +122,7 @@ __global__ __launch_bounds__(256) void ticker_foresight_kernel(TickerParams K, c
         const int c0 = d & 3, c1 = d >> 2;
         const float4 act = make_float4((float)c0, (float)c1, c0 ? 1.f : 0.f, c1 ? 1.f : 0.f);
         const float rew = ticker_account_step(act, pp.x, pp.y, cash, q0, q1, assets, la);
-        tot += (double)rew;
-        ssq += (double)rew * (double)rew;
-        mn = fminf(mn, rew);
-        mx = fmaxf(mx, rew);
+        rs.add(rew);
         length = t + 1;
         trades += d != 0 ? 1 : 0;
         if (trace) {
@@ -140,10 +136,8 @@ __global__ __launch_bounds__(256) void ticker_foresight_kernel(TickerParams K, c
         pp = pn;
         d = dnext;
     }
-    O.total[o] = tot; O.sum_sq[o] = ssq; O.final_assets[o] = assets; O.bound[o] = bound;
-    O.mn[o] = mn; O.mx[o] = mx;
-    O.length[o] = length; O.trades[o] = trades;
-    O.finished[o] = finished ? 1 : 0;
+    O.stats.store(o, rs, length, finished);
+    O.final_assets[o] = assets; O.bound[o] = bound; O.trades[o] = trades;
     O.depleted[o] = depleted ? 1 : 0;
 }
 
@@ -174,8 +168,7 @@ int grl_ticker_foresight(grl_handle *h, const int32_t *horizons, int32_t n_horiz
     const size_t pairs = (size_t)n_horizons * h->E, trace = trace_env >= 0 ? (size_t)n_horizons * max_steps : 0;
     const size_t dec = whole ? (size_t)max_steps * pairs : 0;
     if ((rc = episode_reserve(h, w.cap_h, n_horizons, {buf(w.horizons)})) ||
-        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.bound), buf(w.mn), buf(w.mx),
-                                                      buf(w.length), buf(w.trades), buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.final_assets), buf(w.bound), buf(w.trades), buf(w.depleted)}, &w.stats)) ||
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a), buf(w.trace_act, 4)})) ||
         (rc = episode_reserve(h, w.cap_dec, dec, {buf(w.decisions)})))
         return rc;
@@ -186,8 +179,9 @@ int grl_ticker_foresight(grl_handle *h, const int32_t *horizons, int32_t n_horiz
         GRL_HIP(h, hipMemsetAsync(w.trace_act, 0, trace * 16, h->stream));
     }
     const TickerParams K = ticker_params(h);
-    const TickerForesightOut O{w.total, w.sum_sq, w.final_assets, w.bound, w.mn, w.mx, w.length, w.trades, w.finished, w.depleted,
-                               w.trace_r, w.trace_a, reinterpret_cast<float4 *>(w.trace_act), w.decisions};
+    TickerForesightOut O{};
+    O.stats = w.stats; O.final_assets = w.final_assets; O.bound = w.bound; O.trades = w.trades; O.depleted = w.depleted; O.dec = w.decisions;
+    O.trace_r = w.trace_r; O.trace_a = w.trace_a; O.trace_act = reinterpret_cast<float4 *>(w.trace_act);
     const dim3 grid((h->E + 63) / 64, (n_horizons + 3) / 4), block(256);
     rc = episode_launch(h, [&] { hipLaunchKernelGGL(ticker_foresight_kernel, grid, block, 0, h->stream, K, w.horizons, n_horizons, max_steps, trace_env, O); });
     if (rc) return rc;
@@ -201,13 +195,12 @@ int grl_ticker_foresight_read(grl_handle *h, const char *which, void *host, size
     const size_t pairs = (size_t)w.n_horizons * h->E, trace = (size_t)w.n_horizons * w.max_steps;
     const char *untraced = w.trace_env < 0 ? "the last call traced no env (trace_env was -1)" : nullptr;
     const EpisodeOut outs[] = {
-        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
-        {"bound", w.bound, pairs * 8}, {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4},
-        {"trades", w.trades, pairs * 4}, {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
+        {"final_assets", w.final_assets, pairs * 8}, {"bound", w.bound, pairs * 8}, {"trades", w.trades, pairs * 4},
+        {"depleted", w.depleted, pairs},
         {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced},
         {"trace_actions", w.trace_act, trace * 16, untraced}};
     return episode_read(h, "grl_ticker_foresight_read", GRL_ENV_TICKER, "Ticker", w.n_horizons != 0, "grl_ticker_foresight", outs, nullptr, which, host,
-                        bytes);
+                        bytes, &w.stats, pairs);
 }
 
 }  // extern "C"

@@ -22,10 +22,10 @@
 namespace grl {
 
 struct TickerSweepOut {
-    double *total, *sum_sq, *final_assets;
-    float *mn, *mx;
-    int32_t *length, *trades;
-    uint8_t *finished, *depleted;
+    PairStats stats;
+    double *final_assets;
+    int32_t *trades;
+    uint8_t *depleted;
     float *trace_r;
     double *trace_a;
     float4 *trace_act;
@@ -48,8 +48,7 @@ __global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const
     const double2 qq = reinterpret_cast<const double2 *>(K.q)[env];
     double cash = K.cash[env], q0 = qq.x, q1 = qq.y, assets = K.assets[env];
     double la = log(assets + 1e-4);
-    double tot = 0.0, ssq = 0.0;
-    float mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
+    RewardStats rs;
     int length = 0, trades = 0;
     bool finished = false, depleted = false;
     const bool trace = env == trace_env;
@@ -63,10 +62,7 @@ __global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const
         const double bn = win[(size_t)max(idx + 1 - U.lookback, 0) * 4];
         const float4 act = ticker_rule_action(U, cash, q0, q1, pp.x, pp.y, back);
         const float rew = ticker_account_step(act, pp.x, pp.y, cash, q0, q1, assets, la);
-        tot += (double)rew;
-        ssq += (double)rew * (double)rew;
-        mn = fminf(mn, rew);
-        mx = fmaxf(mx, rew);
+        rs.add(rew);
         length = t + 1;
         trades += (act.x != 0.f || act.y != 0.f) ? 1 : 0;
         if (trace) {
@@ -82,10 +78,8 @@ __global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const
         back = bn;
     }
     const size_t o = (size_t)r * K.E + env;
-    O.total[o] = tot; O.sum_sq[o] = ssq; O.final_assets[o] = assets;
-    O.mn[o] = mn; O.mx[o] = mx;
-    O.length[o] = length; O.trades[o] = trades;
-    O.finished[o] = finished ? 1 : 0;
+    O.stats.store(o, rs, length, finished);
+    O.final_assets[o] = assets; O.trades[o] = trades;
     O.depleted[o] = depleted ? 1 : 0;
 }
 
@@ -127,8 +121,7 @@ int grl_ticker_sweep(grl_handle *h, const float *rules_host, int32_t n_rules, in
     w.n_rules = 0;
     const size_t pairs = (size_t)n_rules * h->E, trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
     if ((rc = episode_reserve(h, w.cap_rules, n_rules, {buf(w.rules, 6)})) ||
-        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.mn), buf(w.mx), buf(w.length),
-                                                      buf(w.trades), buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.final_assets), buf(w.trades), buf(w.depleted)}, &w.stats)) ||
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a), buf(w.trace_act, 4)})))
         return rc;
     GRL_HIP(h, hipMemcpyAsync(w.rules, rules_host, (size_t)n_rules * 6 * 4, hipMemcpyHostToDevice, h->stream));
@@ -138,8 +131,9 @@ int grl_ticker_sweep(grl_handle *h, const float *rules_host, int32_t n_rules, in
         GRL_HIP(h, hipMemsetAsync(w.trace_act, 0, trace * 16, h->stream));
     }
     const TickerParams K = ticker_params(h);
-    const TickerSweepOut O{w.total, w.sum_sq, w.final_assets, w.mn, w.mx, w.length, w.trades, w.finished, w.depleted, w.trace_r, w.trace_a,
-                           reinterpret_cast<float4 *>(w.trace_act)};
+    TickerSweepOut O{};
+    O.stats = w.stats; O.final_assets = w.final_assets; O.trades = w.trades; O.depleted = w.depleted;
+    O.trace_r = w.trace_r; O.trace_a = w.trace_a; O.trace_act = reinterpret_cast<float4 *>(w.trace_act);
     const dim3 grid((h->E + 63) / 64, (n_rules + 3) / 4), block(256);
     rc = episode_launch(h, [&] { hipLaunchKernelGGL(ticker_sweep_kernel, grid, block, 0, h->stream, K, w.rules, n_rules, max_steps, trace_env, O); });
     if (rc) return rc;
@@ -153,12 +147,10 @@ int grl_ticker_sweep_read(grl_handle *h, const char *which, void *host, size_t b
     const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
     const char *untraced = w.trace_env < 0 ? "the last sweep traced no env (trace_env was -1)" : nullptr;
     const EpisodeOut outs[] = {
-        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
-        {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4}, {"trades", w.trades, pairs * 4},
-        {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
+        {"final_assets", w.final_assets, pairs * 8}, {"trades", w.trades, pairs * 4}, {"depleted", w.depleted, pairs},
         {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced},
         {"trace_actions", w.trace_act, trace * 16, untraced}};
-    return episode_read(h, "grl_ticker_sweep_read", GRL_ENV_TICKER, "Ticker", w.n_rules != 0, "grl_ticker_sweep", outs, nullptr, which, host, bytes);
+    return episode_read(h, "grl_ticker_sweep_read", GRL_ENV_TICKER, "Ticker", w.n_rules != 0, "grl_ticker_sweep", outs, nullptr, which, host, bytes, &w.stats, pairs);
 }
 
 }  // extern "C"

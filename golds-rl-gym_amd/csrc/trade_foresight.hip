@@ -5,14 +5,14 @@
 //    written once, float64 [row][asset][env], with the sweep's own draws (trade_price_normals at st0 + t, or the tape) and the
 //    sweep's own trade_price_next.  Rows at or past an env's m are written as zero.  Every horizon -- and the host, through the
 //    "prices" output -- then sees the device's own pow / exp bits.
-// 2. trade_foresight_kernel: the mapping of ticker_foresight_kernel.  One lane per pair; the lanes of a wave are consecutive envs of
-//    ONE horizon, so H and the branch between the two forms are wave-uniform, a path row is n coalesced loads and the
-//    (n_horizons, E) outputs store coalesced; the waves of a workgroup hold horizons of the same 64 envs.  No barrier, no atomics.
+// 2. trade_foresight_kernel: one lane per pair; the lanes of a wave are consecutive envs of ONE horizon, so H and the branch between
+//    the two forms are wave-uniform, a path row is n coalesced loads and the (n_horizons, E) outputs store coalesced; the waves of a
+//    workgroup hold horizons of the same 64 envs.  No barrier, no atomics.
 //
-// Where q and B live: the tiers of trade_sweep.hip.  Up to 16 assets in registers, NT = 2 / 4 / 8 / 16, loops fully unrolled under a
-// uniform `a < n` guard, with the row in use and the row asked for next in registers too.  From 17 to 64 assets (NT = 0) q and B are
-// LDS columns [asset][lane] of the lane's wave, n * 1 024 bytes per wave, and a price is loaded where it is used; the workgroup has
-// as many waves (4 at most) as fit in the CU's 160 KB, two at 64 assets.
+// Where q and B live: in the asset tiers of flat_env_dev.h (trade_for in the kernels, trade_tier on the host).  Up to 16 assets in
+// registers, NT = 2 / 4 / 8 / 16, loops fully unrolled under a uniform `a < n` guard, with the row in use and the row asked for next
+// in registers too.  From 17 to 64 assets (NT = 0) q and B are LDS columns [asset][lane] of the lane's wave, n * 1 024 bytes per
+// wave, and a price is loaded where it is used; the workgroup has as many waves (4 at most) as fit in the CU's 160 KB, two at 64.
 //
 // H > 0: every step runs its backward loop over at most H + 1 rows.  The row addresses do not depend on the arithmetic, so each
 // iteration asks for row j - 1 before row j's divisions.
@@ -34,30 +34,17 @@
 namespace grl {
 
 struct TradeForesightOut {
-    double *total, *sum_sq, *final_assets, *bound;
-    float *mn, *mx;
-    int32_t *length, *trades;
-    uint8_t *finished, *depleted;
+    PairStats stats;
+    double *final_assets, *bound;
+    int32_t *trades;
+    uint8_t *depleted;
     float *trace_r;
     double *trace_a;
     float *trace_act;
     uint8_t *dec;
 };
 
-constexpr int TFS_LDS_BYTES = 160 * 1024;
 constexpr size_t TFS_MAX_PATH = (size_t)1 << 28;       // max_steps * n_assets * E: 2 GiB of path, 256 MiB per whole-episode plan
-
-// f(a) for a = 0 .. n-1: unrolled to NT slots under a uniform guard (registers), or a plain loop (LDS columns); as tsw_for
-template <int NT, class F>
-__device__ __forceinline__ void tfs_for(int n, F f) {
-    if constexpr (NT > 0) {
-#pragma unroll
-        for (int a = 0; a < NT; ++a)
-            if (a < n) f(a);
-    } else {
-        for (int a = 0; a < n; ++a) f(a);
-    }
-}
 
 // the steps of a pair, depletion aside
 __device__ __forceinline__ int trade_foresight_steps(const TradeParams &R, int env, int max_steps) {
@@ -81,11 +68,11 @@ __global__ __launch_bounds__(256) void trade_path_kernel(TradeParams R, const fl
     // the row before t: in registers, or (17 assets and more) read back by the lane that wrote it
     auto prev = [&](int t, int a) -> double { if constexpr (REG) return pr[a]; else return out[((size_t)(t - 1) * n + a) * E]; };
     auto put = [&](int t, int a, double p) { if constexpr (REG) pr[a] = p; out[((size_t)t * n + a) * E] = p; };
-    tfs_for<NT>(n, [&](int a) { put(0, a, R.p[a * E + env]); });
+    trade_for<NT>(n, [&](int a) { put(0, a, R.p[a * E + env]); });
     for (int t = 1; t < max_steps; ++t) {
         if (t < m) {
-            const uint32_t st = st0 + (uint32_t)(t - 1);
-            tfs_for<(NT + 1) / 2>(pairs, [&](int k) {
+            const uint32_t st = st0 + (uint32_t)(t - 1);   // trade_prices_step written out: as a call it is 0.5 % slower here
+            trade_for<(NT + 1) / 2>(pairs, [&](int k) {
                 const int a = 2 * k;
                 double z0, z1 = 0.0;
                 if (tape) {
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(256) void trade_path_kernel(TradeParams R, const fl
                 if (a + 1 < n) put(t, a + 1, trade_price_next(prev(t, a + 1), R.std_e, z1));   // NT is even: slot a + 1 exists
             });
         } else {
-            tfs_for<NT>(n, [&](int a) { out[((size_t)t * n + a) * E] = 0.0; });
+            trade_for<NT>(n, [&](int a) { out[((size_t)t * n + a) * E] = 0.0; });
         }
     }
 }
@@ -125,10 +112,10 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
     auto B = [&](int a) -> double & { if constexpr (REG) return br[a]; else return col[(size_t)(n + a) * 64]; };
     const double *pth = path + env;                            // row j, asset a: pth[(j * n + a) * E]
     auto load = [&](double (&dst)[NR], int j) {                // registers only: the whole row j
-        if constexpr (REG) tfs_for<NT>(n, [&](int a) { dst[a] = pth[((size_t)j * n + a) * E]; });
+        if constexpr (REG) trade_for<NT>(n, [&](int a) { dst[a] = pth[((size_t)j * n + a) * E]; });
     };
     auto take = [&]() {                                        // the row asked for becomes the row in use
-        if constexpr (REG) tfs_for<NT>(n, [&](int a) { pc[a] = pn[a]; });
+        if constexpr (REG) trade_for<NT>(n, [&](int a) { pc[a] = pn[a]; });
     };
     auto price = [&](int j, int a) -> double { if constexpr (REG) return pc[a]; else return pth[((size_t)j * n + a) * E]; };
 
@@ -136,7 +123,7 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
     // 1 buy, 2 sell
     auto row = [&](int j, double &A, auto seen) {
         double g = 0.0;
-        tfs_for<NT>(n, [&](int a) {
+        trade_for<NT>(n, [&](int a) {
             const double p = price(j, a);
             const double b = B(a);
             const double x = b / p;
@@ -162,7 +149,7 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
     const int m = trade_foresight_steps(R, env, max_steps);
     const int last = m - 1;
     double cash = R.cash[env], assets = R.assets[env];
-    tfs_for<NT>(n, [&](int a) { Q(a) = R.q[a * E + env]; });
+    trade_for<NT>(n, [&](int a) { Q(a) = R.q[a * E + env]; });
     const size_t o = (size_t)r * E + env;
 
     double bound = __builtin_nan("");
@@ -174,22 +161,21 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
         dec = plane;
         double A = 1.0;
         load(pc, last);
-        tfs_for<NT>(n, [&](int a) { B(a) = price(last, a); });
+        trade_for<NT>(n, [&](int a) { B(a) = price(last, a); });
         for (int j = last; j >= 0; --j) {
             load(pn, max(j - 1, 0));
             row(j, A, [&](int a, double, int c) { plane[((size_t)j * n + a) * E] = (uint8_t)c; });
             take();
         }
         double v = cash * A;
-        tfs_for<NT>(n, [&](int a) {
+        trade_for<NT>(n, [&](int a) {
             const double w = Q(a) * B(a);
             v = v + w;
         });
         bound = log(v + 1e-4) - log(assets + 1e-4);
     }
 
-    double tot = 0.0, ssq = 0.0;
-    float mn = __builtin_huge_valf(), mx = -__builtin_huge_valf();
+    RewardStats rs;
     int length = 0, trades = 0;
     bool finished = false, depleted = false;
     const bool trace = env == trace_env;
@@ -210,12 +196,12 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
         if (H == 0) {
             take();
             load(pn, min(t + 1, last));
-            tfs_for<NT>(n, [&](int a) { trade(a, price(t, a), dec[((size_t)t * n + a) * E]); });
+            trade_for<NT>(n, [&](int a) { trade(a, price(t, a), dec[((size_t)t * n + a) * E]); });
         } else {
             const int e = min(t + H, last);
             double A = 1.0;
             load(pc, e);
-            tfs_for<NT>(n, [&](int a) { B(a) = price(e, a); });
+            trade_for<NT>(n, [&](int a) { B(a) = price(e, a); });
             for (int j = e; j > t; --j) {
                 load(pn, j - 1);
                 row(j, A, nothing);
@@ -225,10 +211,7 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
         }
         bool dep;
         const float rew = trade_account_settle(cash, assets, cost, value, dep);
-        tot += (double)rew;
-        ssq += (double)rew * (double)rew;
-        mn = fminf(mn, rew);
-        mx = fmaxf(mx, rew);
+        rs.add(rew);
         length = t + 1;
         trades += traded ? 1 : 0;
         if (trace) {
@@ -239,10 +222,8 @@ __global__ __launch_bounds__(256) void trade_foresight_kernel(TradeParams R, con
         finished = dep || (R.max_steps > 0 && el0 + t + 1 >= R.max_steps);
         if (finished) break;
     }
-    O.total[o] = tot; O.sum_sq[o] = ssq; O.final_assets[o] = assets; O.bound[o] = bound;
-    O.mn[o] = mn; O.mx[o] = mx;
-    O.length[o] = length; O.trades[o] = trades;
-    O.finished[o] = finished ? 1 : 0;
+    O.stats.store(o, rs, length, finished);
+    O.final_assets[o] = assets; O.bound[o] = bound; O.trades[o] = trades;
     O.depleted[o] = depleted ? 1 : 0;
 }
 
@@ -257,22 +238,15 @@ static int trade_foresight_launch(grl_handle *h, const TradeParams &R, int n_hor
                                   const TradeForesightOut &O, bool path_only) {
     const TradeForesightState &w = h->tfs;
     const int n = R.n;
-    int waves = 4;
-    size_t lds = 0;
+    int waves; size_t lds;
     void (*pathk)(TradeParams, const float *, int, double *);
     void (*playk)(TradeParams, const int32_t *, int, int, int, const double *, TradeForesightOut);
-    if (n <= 2) { pathk = trade_path_kernel<2>; playk = trade_foresight_kernel<2>; }
-    else if (n <= 4) { pathk = trade_path_kernel<4>; playk = trade_foresight_kernel<4>; }
-    else if (n <= 8) { pathk = trade_path_kernel<8>; playk = trade_foresight_kernel<8>; }
-    else if (n <= 16) { pathk = trade_path_kernel<16>; playk = trade_foresight_kernel<16>; }
-    else {
-        pathk = trade_path_kernel<0>; playk = trade_foresight_kernel<0>;
-        const size_t per_wave = (size_t)2 * n * 64 * sizeof(double);               // at most 2 * 64 * 512 = 64 KB
-        waves = (int)std::min<size_t>(4, TFS_LDS_BYTES / per_wave);
-        lds = per_wave * waves;
-        GRL_HIP(h, hipFuncSetAttribute((const void *)playk, hipFuncAttributeMaxDynamicSharedMemorySize, TFS_LDS_BYTES));
-    }
-    int rc = episode_launch(h, [&] { hipLaunchKernelGGL(pathk, dim3((h->E + 255) / 256), dim3(256), 0, h->stream, R, tape, max_steps, w.path); });
+    const size_t per_wave = (size_t)2 * n * 64 * sizeof(double);                   // at most 2 * 64 * 512 = 64 KB
+    int rc = trade_tier(h, n, per_wave, waves, lds, [&](auto nt) {
+        pathk = trade_path_kernel<decltype(nt)::value>; return (const void *)(playk = trade_foresight_kernel<decltype(nt)::value>);
+    });
+    if (rc) return rc;
+    rc = episode_launch(h, [&] { hipLaunchKernelGGL(pathk, dim3((h->E + 255) / 256), dim3(256), 0, h->stream, R, tape, max_steps, w.path); });
     if (rc || path_only) return rc;
     const dim3 grid((h->E + 63) / 64, (n_horizons + waves - 1) / waves), block(64 * waves);
     return episode_launch(h, [&] { hipLaunchKernelGGL(playk, grid, block, lds, h->stream, R, w.horizons, n_horizons, max_steps, trace_env, w.path, O); });
@@ -302,34 +276,29 @@ int grl_trade_foresight(grl_handle *h, const int32_t *horizons, int32_t n_horizo
     if (cells > TFS_MAX_PATH)
         return fail(h, GRL_E_INVALID, "grl_trade_foresight: max_steps * n_assets * E = " + std::to_string(cells) + " is over the limit of " +
                                           std::to_string(TFS_MAX_PATH) + " (2^28) path cells");
-    if (!normals_host && (h->cfg.flags & GRL_F_INJECT_NOISE))
-        return fail(h, GRL_E_INVALID, "grl_trade_foresight: a handle with GRL_F_INJECT_NOISE holds the normals of one step; pass a tape");
-    if ((rc = episode_check_idle(h, fn))) return rc;
+    if ((rc = trade_tape_check(h, fn, normals_host)) || (rc = episode_check_idle(h, fn))) return rc;
     hipSetDevice(h->cfg.device_id);
     TradeForesightState &w = h->tfs;
     w.n_horizons = 0;
     const size_t pairs = (size_t)n_horizons * h->E, trace = trace_env >= 0 ? (size_t)n_horizons * max_steps : 0;
     const size_t tape = normals_host ? cells : 0;
     if ((rc = episode_reserve(h, w.cap_h, n_horizons, {buf(w.horizons)})) ||
-        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.bound), buf(w.mn), buf(w.mx),
-                                                      buf(w.length), buf(w.trades), buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.final_assets), buf(w.bound), buf(w.trades), buf(w.depleted)}, &w.stats)) ||
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a), buf(w.trace_act, n)})) ||
         (rc = episode_reserve(h, w.cap_tape, tape, {buf(w.tape)})) || (rc = episode_reserve(h, w.cap_path, cells, {buf(w.path)})) ||
         (rc = episode_reserve(h, w.cap_dec, whole * cells, {buf(w.decisions)})))
         return rc;
     GRL_HIP(h, hipMemcpyAsync(w.horizons, horizons, (size_t)n_horizons * 4, hipMemcpyHostToDevice, h->stream));
-    if (tape) {
-        GRL_HIP(h, hipMemcpyAsync(w.tape, normals_host, tape * 4, hipMemcpyHostToDevice, h->stream));
-        GRL_HIP(h, hipStreamSynchronize(h->stream));     // the tape is the caller's again when the call returns
-    }
+    if ((rc = trade_tape_upload(h, w.tape, normals_host, tape))) return rc;
     if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
         GRL_HIP(h, hipMemsetAsync(w.trace_r, 0, trace * 4, h->stream));
         GRL_HIP(h, hipMemsetAsync(w.trace_a, 0, trace * 8, h->stream));
         GRL_HIP(h, hipMemsetAsync(w.trace_act, 0, trace * n * 4, h->stream));
     }
     const TradeParams R = trade_params(h);
-    const TradeForesightOut O{w.total, w.sum_sq, w.final_assets, w.bound, w.mn, w.mx, w.length, w.trades, w.finished, w.depleted,
-                              w.trace_r, w.trace_a, w.trace_act, w.decisions};
+    TradeForesightOut O{};
+    O.stats = w.stats; O.final_assets = w.final_assets; O.bound = w.bound; O.trades = w.trades; O.depleted = w.depleted;
+    O.trace_r = w.trace_r; O.trace_a = w.trace_a; O.trace_act = w.trace_act; O.dec = w.decisions;
     const bool path_only = trade_foresight_path_only();
     if ((rc = trade_foresight_launch(h, R, n_horizons, tape ? w.tape : nullptr, max_steps, trace_env, O, path_only)) || path_only) return rc;
     w.n_horizons = n_horizons; w.max_steps = max_steps; w.trace_env = trace_env;
@@ -343,14 +312,12 @@ int grl_trade_foresight_read(grl_handle *h, const char *which, void *host, size_
     const size_t pairs = (size_t)w.n_horizons * h->E, trace = (size_t)w.n_horizons * w.max_steps;
     const char *untraced = w.trace_env < 0 ? "the last call traced no env (trace_env was -1)" : nullptr;
     const EpisodeOut outs[] = {
-        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
-        {"bound", w.bound, pairs * 8}, {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4},
-        {"trades", w.trades, pairs * 4}, {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
-        {"prices", w.path, (size_t)w.max_steps * n * h->E * 8},
+        {"final_assets", w.final_assets, pairs * 8}, {"bound", w.bound, pairs * 8}, {"trades", w.trades, pairs * 4},
+        {"depleted", w.depleted, pairs}, {"prices", w.path, (size_t)w.max_steps * n * h->E * 8},
         {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced},
         {"trace_actions", w.trace_act, trace * n * 4, untraced}};
     return episode_read(h, "grl_trade_foresight_read", GRL_ENV_TRADE, "TradeAR1", w.n_horizons != 0, "grl_trade_foresight", outs, nullptr, which, host,
-                        bytes);
+                        bytes, &w.stats, pairs);
 }
 
 }  // extern "C"

@@ -25,27 +25,12 @@
 namespace grl {
 
 struct TradeSweepOut {
-    double *total, *sum_sq, *final_assets;
-    float *mn, *mx;
-    int32_t *length;
-    uint8_t *finished, *depleted;
+    PairStats stats;
+    double *final_assets;
+    uint8_t *depleted;
     float *trace_r;
     double *trace_a;
 };
-
-constexpr int TSW_LDS_BYTES = 160 * 1024;
-
-// f(a) for a = 0 .. n-1: unrolled to NT slots under a uniform guard (registers), or a plain loop (LDS columns)
-template <int NT, class F>
-__device__ __forceinline__ void tsw_for(int n, F f) {
-    if constexpr (NT > 0) {
-#pragma unroll
-        for (int a = 0; a < NT; ++a)
-            if (a < n) f(a);
-    } else {
-        for (int a = 0; a < n; ++a) f(a);
-    }
-}
 
 template <int RPL, int NT>
 __global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const float *__restrict__ gains, const float *__restrict__ biases,
@@ -66,8 +51,8 @@ __global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const f
     auto P = [&](int a) -> double & { if constexpr (REG) return pr[a]; else return col[(size_t)a * 64]; };
     auto Q = [&](int j, int a) -> double & { if constexpr (REG) return qr[j][a]; else return col[((size_t)(1 + j) * n + a) * 64]; };
 
-    double gain[RPL], bias[RPL], cash[RPL], assets[RPL], tot[RPL], ssq[RPL];
-    float mn[RPL], mx[RPL];
+    double gain[RPL], bias[RPL], cash[RPL], assets[RPL];
+    RewardStats rs[RPL];
     int length[RPL];
     bool live[RPL], finished[RPL], depleted[RPL];
     const double cash0 = R.cash[env], assets0 = R.assets[env];
@@ -75,11 +60,10 @@ __global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const f
     for (int j = 0; j < RPL; ++j) {
         const int r = r0 + j < n_rules ? r0 + j : n_rules - 1;             // a ragged tail replays the last rule and stores nothing
         gain[j] = (double)gains[r]; bias[j] = (double)biases[r];
-        cash[j] = cash0; assets[j] = assets0; tot[j] = 0.0; ssq[j] = 0.0;
-        mn[j] = __builtin_huge_valf(); mx[j] = -__builtin_huge_valf();
+        cash[j] = cash0; assets[j] = assets0;
         length[j] = 0; live[j] = true; finished[j] = false; depleted[j] = false;
     }
-    tsw_for<NT>(n, [&](int a) {
+    trade_for<NT>(n, [&](int a) {
         P(a) = R.p[a * E + env];
         const double q0 = R.q[a * E + env];
 #pragma unroll
@@ -97,16 +81,13 @@ __global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const f
             if (!live[j]) continue;
             double cost = 0.0, value = 0.0;
             const double c = cash[j];
-            tsw_for<NT>(n, [&](int a) {
+            trade_for<NT>(n, [&](int a) {
                 const double p = P(a);
                 trade_asset_trade(trade_rule_action(gain[j], bias[j], p), n, c, p, Q(j, a), cost, value);
             });
             bool dep;
             const float rew = trade_account_settle(cash[j], assets[j], cost, value, dep);
-            tot[j] += (double)rew;
-            ssq[j] += (double)rew * (double)rew;
-            mn[j] = fminf(mn[j], rew);
-            mx[j] = fmaxf(mx[j], rew);
+            rs[j].add(rew);
             length[j] = t + 1;
             if (trace && r0 + j < n_rules) {
                 O.trace_r[(size_t)(r0 + j) * max_steps + t] = rew;
@@ -119,29 +100,14 @@ __global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const f
         }
         if (!any || t + 1 == max_steps) break;
         // _price_transition of every asset, once for all rules of the lane
-        const uint32_t st = st0 + (uint32_t)t;
-        tsw_for<(NT + 1) / 2>(pairs, [&](int k) {
-            const int a = 2 * k;
-            double z0, z1 = 0.0;
-            if (tape) {
-                z0 = (double)tape[((size_t)t * n + a) * E + env];
-                if (a + 1 < n) z1 = (double)tape[((size_t)t * n + a + 1) * E + env];
-            } else {
-                trade_price_normals(R.seed, (uint32_t)env + R.env_off, st, pairs, k, z0, z1);   // an odd n discards the last z1
-            }
-            P(a) = trade_price_next(P(a), R.std_e, z0);
-            if (a + 1 < n) P(a + 1) = trade_price_next(P(a + 1), R.std_e, z1);       // NT is even: slot a + 1 exists
-        });
+        trade_prices_step<NT>(R, tape, env, st0, t, pairs, [&](int a) { return P(a); }, [&](int a, double p) { P(a) = p; });
     }
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
         if (r0 + j < n_rules) {
             const size_t o = (size_t)(r0 + j) * E + env;
-            O.total[o] = tot[j]; O.sum_sq[o] = ssq[j]; O.final_assets[o] = assets[j];
-            O.mn[o] = mn[j]; O.mx[o] = mx[j];
-            O.length[o] = length[j];
-            O.finished[o] = finished[j] ? 1 : 0;
-            O.depleted[o] = depleted[j] ? 1 : 0;
+            O.stats.store(o, rs[j], length[j], finished[j]);
+            O.final_assets[o] = assets[j]; O.depleted[o] = depleted[j] ? 1 : 0;
         }
     }
 }
@@ -162,20 +128,11 @@ static int trade_sweep_launch(grl_handle *h, const TradeParams &R, int n_rules, 
                               const TradeSweepOut &O) {
     const TradeSweepState &w = h->tsw;
     const int n = R.n, groups = (n_rules + RPL - 1) / RPL;
-    int waves = 4;
-    size_t lds = 0;
+    int waves; size_t lds;
     void (*kern)(TradeParams, const float *, const float *, int, const float *, int, int, TradeSweepOut);
-    if (n <= 2) kern = trade_sweep_kernel<RPL, 2>;
-    else if (n <= 4) kern = trade_sweep_kernel<RPL, 4>;
-    else if (n <= 8) kern = trade_sweep_kernel<RPL, 8>;
-    else if (n <= 16) kern = trade_sweep_kernel<RPL, 16>;
-    else {
-        kern = trade_sweep_kernel<RPL, 0>;
-        const size_t per_wave = (size_t)(1 + RPL) * n * 64 * sizeof(double);       // at most 5 * 64 * 512 = 160 KB
-        waves = (int)std::min<size_t>(4, TSW_LDS_BYTES / per_wave);
-        lds = per_wave * waves;
-        GRL_HIP(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TSW_LDS_BYTES));
-    }
+    const size_t per_wave = (size_t)(1 + RPL) * n * 64 * sizeof(double);           // at most 5 * 64 * 512 = 160 KB
+    const int rc = trade_tier(h, n, per_wave, waves, lds, [&](auto nt) { return (const void *)(kern = trade_sweep_kernel<RPL, decltype(nt)::value>); });
+    if (rc) return rc;
     const dim3 grid((h->E + 63) / 64, (groups + waves - 1) / waves), block(64 * waves);
     return episode_launch(h, [&] { hipLaunchKernelGGL(kern, grid, block, lds, h->stream, R, w.gains, w.biases, n_rules, tape, max_steps, trace_env, O); });
 }
@@ -196,31 +153,26 @@ int grl_trade_sweep(grl_handle *h, const float *gains_host, const float *biases_
     for (int i = 0; i < n_rules; ++i)
         if (!std::isfinite(gains_host[i]) || !std::isfinite(biases_host[i]))
             return fail(h, GRL_E_INVALID, "grl_trade_sweep: rule " + std::to_string(i) + " has a non-finite gain or bias");
-    if (!normals_host && (h->cfg.flags & GRL_F_INJECT_NOISE))
-        return fail(h, GRL_E_INVALID, "grl_trade_sweep: a handle with GRL_F_INJECT_NOISE holds the normals of one step; pass a tape");
-    if ((rc = episode_check_idle(h, fn))) return rc;
+    if ((rc = trade_tape_check(h, fn, normals_host)) || (rc = episode_check_idle(h, fn))) return rc;
     hipSetDevice(h->cfg.device_id);
     TradeSweepState &w = h->tsw;
     w.n_rules = 0;
     const size_t pairs = (size_t)n_rules * h->E, trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
     const size_t tape = normals_host ? (size_t)max_steps * h->cfg.n_assets * h->E : 0;
     if ((rc = episode_reserve(h, w.cap_rules, n_rules, {buf(w.gains), buf(w.biases)})) ||
-        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.total), buf(w.sum_sq), buf(w.final_assets), buf(w.mn), buf(w.mx), buf(w.length),
-                                                      buf(w.finished), buf(w.depleted)})) ||
+        (rc = episode_reserve(h, w.cap_pairs, pairs, {buf(w.final_assets), buf(w.depleted)}, &w.stats)) ||
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_r), buf(w.trace_a)})) || (rc = episode_reserve(h, w.cap_tape, tape, {buf(w.tape)})))
         return rc;
     GRL_HIP(h, hipMemcpyAsync(w.gains, gains_host, (size_t)n_rules * 4, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemcpyAsync(w.biases, biases_host, (size_t)n_rules * 4, hipMemcpyHostToDevice, h->stream));
-    if (tape) {
-        GRL_HIP(h, hipMemcpyAsync(w.tape, normals_host, tape * 4, hipMemcpyHostToDevice, h->stream));
-        GRL_HIP(h, hipStreamSynchronize(h->stream));     // the tape is the caller's again when the call returns
-    }
+    if ((rc = trade_tape_upload(h, w.tape, normals_host, tape))) return rc;
     if (trace) {     // rows are defined up to the pair's length; the rest reads as zero
         GRL_HIP(h, hipMemsetAsync(w.trace_r, 0, trace * 4, h->stream));
         GRL_HIP(h, hipMemsetAsync(w.trace_a, 0, trace * 8, h->stream));
     }
     const TradeParams R = trade_params(h);
-    const TradeSweepOut O{w.total, w.sum_sq, w.final_assets, w.mn, w.mx, w.length, w.finished, w.depleted, w.trace_r, w.trace_a};
+    TradeSweepOut O{};
+    O.stats = w.stats; O.final_assets = w.final_assets; O.depleted = w.depleted; O.trace_r = w.trace_r; O.trace_a = w.trace_a;
     const float *tp = tape ? w.tape : nullptr;
     const int rpl = trade_sweep_rpl();
     if (rpl == 1) rc = trade_sweep_launch<1>(h, R, n_rules, tp, max_steps, trace_env, O);
@@ -237,11 +189,9 @@ int grl_trade_sweep_read(grl_handle *h, const char *which, void *host, size_t by
     const size_t pairs = (size_t)w.n_rules * h->E, trace = (size_t)w.n_rules * w.max_steps;
     const char *untraced = w.trace_env < 0 ? "the last sweep traced no env (trace_env was -1)" : nullptr;
     const EpisodeOut outs[] = {
-        {"total", w.total, pairs * 8}, {"sum_sq", w.sum_sq, pairs * 8}, {"final_assets", w.final_assets, pairs * 8},
-        {"min", w.mn, pairs * 4}, {"max", w.mx, pairs * 4}, {"length", w.length, pairs * 4},
-        {"finished", w.finished, pairs}, {"depleted", w.depleted, pairs},
+        {"final_assets", w.final_assets, pairs * 8}, {"depleted", w.depleted, pairs},
         {"trace_rewards", w.trace_r, trace * 4, untraced}, {"trace_assets", w.trace_a, trace * 8, untraced}};
-    return episode_read(h, "grl_trade_sweep_read", GRL_ENV_TRADE, "TradeAR1", w.n_rules != 0, "grl_trade_sweep", outs, nullptr, which, host, bytes);
+    return episode_read(h, "grl_trade_sweep_read", GRL_ENV_TRADE, "TradeAR1", w.n_rules != 0, "grl_trade_sweep", outs, nullptr, which, host, bytes, &w.stats, pairs);
 }
 
 }  // extern "C"

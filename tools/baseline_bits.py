@@ -1,4 +1,4 @@
-"""The seven whole-episode baseline launches on small fixed scenarios, a SHA-256 per output buffer: do two builds compute the same
+"""The eight whole-episode baseline launches on small fixed scenarios, a SHA-256 per output buffer: do two builds compute the same
 bits?  And, with --calls, does a call cost the host the same?
 
     python tools/baseline_bits.py [--baseline PARENT_CHECKOUT] [--json OUT]
@@ -11,6 +11,8 @@ a script that runs out) ends pairs early.
 solow_sweep       70 envs, 5 rates x 40 steps then 3 x 17, TimeLimit 24 from 3 steps in; GRL_SWEEP_RPL 1 and 2.
 trade_sweep       70 envs, 2 and 17 assets (the register and the LDS form), 5 rules x 40 steps then 3 x 17, GRL_TRADE_SWEEP_RPL 1 and
                   2, the engine's own normals and a tape.
+trade_foresight   70 envs, 2 and 17 assets, horizons (0, 1, 16) x 40 steps then (4, 0) x 9, TimeLimit 24 from 3 steps in, the engine's
+                  own normals and a tape.
 ticker_sweep      70 envs on the table of tests/golden/ticker_rules.npz, 5 rules x 40 steps then 3 x 9, TimeLimit 30.
 ticker_foresight  the same engine, horizons (0, 1, 16) x 40 steps then (4, 0) x 9.
 solow_dp          70 envs, the tests' small grid, 4 stages: policy and value, then play 30 steps with trace_steps 30, then 12 with 5.
@@ -87,6 +89,21 @@ def trade_sweep(_ffi):
     return out
 
 
+def trade_foresight(_ffi):
+    from goldsrl._ffi_tradeforesight import trade_foresight as play
+    out = {}
+    for n in (2, 17):
+        eng = stepped(_ffi.Engine(_ffi.ENV_TRADE, 70, seed=7, n_assets=n, max_episode_steps=24), np.full((70, n), 0.2, np.float32))
+        for tape in (False, True):
+            def run(big):
+                steps = 40 if big else 9
+                normals = np.random.RandomState(steps).normal(size=(steps, 70, n)).astype(np.float32) if tape else None
+                return play(eng, (0, 1, 16) if big else (4, 0), steps, 69 if big else 3, normals)
+            out["n%d.%s" % (n, "tape" if tape else "own")] = twice(run)
+        eng.close()
+    return out
+
+
 def ticker_engine(_ffi, E, cap):
     matrix = np.load(os.path.join(GOLDEN, "ticker_rules.npz"))["matrix"]
     starts = np.random.RandomState(5).randint(0, matrix.shape[0] - 1024 + 1, size=E)
@@ -148,7 +165,7 @@ def swarm_rules(_ffi):
     return out
 
 
-SCENARIOS = (solow_sweep, trade_sweep, ticker_sweep, ticker_foresight, solow_dp, swarm_replay, swarm_rules)
+SCENARIOS = (solow_sweep, trade_sweep, trade_foresight, ticker_sweep, ticker_foresight, solow_dp, swarm_replay, swarm_rules)
 
 
 def flat(d, prefix=""):
@@ -160,9 +177,10 @@ def flat(d, prefix=""):
 
 def call_times(_ffi):
     """microseconds per call (launch + read of length) of each launch at 1 env, 1 item, 1 step"""
-    from goldsrl import _ffi_replay, _ffi_solowdp, _ffi_swarmrules, _ffi_sweep, _ffi_tickerforesight, _ffi_tickersweep, _ffi_tradesweep
+    from goldsrl import (_ffi_replay, _ffi_solowdp, _ffi_swarmrules, _ffi_sweep, _ffi_tickerforesight, _ffi_tickersweep, _ffi_tradeforesight,
+                         _ffi_tradesweep)
     sigs = {}
-    for m, name in ((_ffi_sweep, "SWEEP"), (_ffi_tradesweep, "TRADE_SWEEP"), (_ffi_tickersweep, "TICKER_SWEEP"),
+    for m, name in ((_ffi_sweep, "SWEEP"), (_ffi_tradesweep, "TRADE_SWEEP"), (_ffi_tradeforesight, "TRADE_FORESIGHT"), (_ffi_tickersweep, "TICKER_SWEEP"),
                     (_ffi_tickerforesight, "TICKER_FORESIGHT"), (_ffi_solowdp, "SOLOW_DP"), (_ffi_replay, "REPLAY"), (_ffi_swarmrules, "SWARMRULES")):
         sigs.update(getattr(m, name + "_SIGNATURES"))
     lib = _ffi.load_library(extra_signatures=sigs)
@@ -180,6 +198,7 @@ def call_times(_ffi):
     launches = {
         "solow_sweep": (solow, lambda h: lib.grl_solow_sweep(h, p(f32), 1, 1, -1), lib.grl_solow_sweep_read),
         "trade_sweep": (trade, lambda h: lib.grl_trade_sweep(h, p(f32), p(f32), 1, None, 1, -1), lib.grl_trade_sweep_read),
+        "trade_foresight": (trade, lambda h: lib.grl_trade_foresight(h, p(i32), 1, None, 1, -1), lib.grl_trade_foresight_read),
         "ticker_sweep": (ticker, lambda h: lib.grl_ticker_sweep(h, p(f32), 1, 1, -1), lib.grl_ticker_sweep_read),
         "ticker_foresight": (ticker, lambda h: lib.grl_ticker_foresight(h, p(i32), 1, 1, -1), lib.grl_ticker_foresight_read),
         "solow_dp_play": (solow, lambda h: lib.grl_solow_dp_play(h, 1, 0), lib.grl_solow_dp_play_read),
