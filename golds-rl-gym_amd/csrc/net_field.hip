@@ -16,6 +16,7 @@
 #include "../../include/goldsrl_fieldnet.h"
 #include "common.h"
 #include "net_paac_host.h"
+#include "rng.h"
 
 namespace grl {
 
@@ -329,6 +330,16 @@ __global__ void field_finalize_kernel(const double *__restrict__ part, int npart
 
 }  // namespace grl
 
+namespace grl {
+// the activations of a forward pass over n samples: the net's own (max_samples) or the rollout gradient step's workspace
+struct FieldActs {
+    float *x[FIELD_MAX_LAYERS + 1];
+    uint8_t *idx[FIELD_MAX_LAYERS];
+    float *d1, *d2, *p1, *p2, *v1, *v2;
+};
+struct FieldRollout;      // net_field_rollout.inc
+}  // namespace grl
+
 struct grl_fieldnet : grl::PaacNet {
     grl_fieldnet_config cfg;
     grl::FieldOff off;
@@ -345,6 +356,8 @@ struct grl_fieldnet : grl::PaacNet {
     float *d_act, *d_adv, *d_y;
     int32_t *d_pos;
     double *stats64;
+    long param_version = 0;      // moves with every change of the parameters: the rollout's column-major head copies follow it
+    grl::FieldRollout *ro = nullptr;
 };
 
 namespace grl {
@@ -359,24 +372,40 @@ static inline unsigned nb(long total) { return (unsigned)((total + 255) / 256); 
         default: { constexpr int kA = 4; CALL; } break; \
     }
 
-static int field_forward(grl_fieldnet *net, int n) {
+// convs + pools, the dense stack, pol2 and the value tower of n samples whose images are in a.x[0]
+static void field_trunk(grl_fieldnet *net, const FieldActs &a, int n) {
     hipStream_t st = net->h->stream;
     const float *P = net->params;
     const FieldOff &o = net->off;
     for (int l = 0; l < net->L; ++l) {
         const long total = (long)n * (net->lh[l] / 2) * (net->lw[l] / 2) * net->F;
-        hipLaunchKernelGGL(field_conv_pool_kernel, dim3(nb(total)), dim3(256), 0, st, net->x[l], P + o.cw[l], P + o.cb[l], total, net->lh[l],
-                           net->lw[l], net->lc[l], net->F, net->x[l + 1], net->idx[l]);
+        hipLaunchKernelGGL(field_conv_pool_kernel, dim3(nb(total)), dim3(256), 0, st, a.x[l], P + o.cw[l], P + o.cb[l], total, net->lh[l],
+                           net->lw[l], net->lc[l], net->F, a.x[l + 1], a.idx[l]);
     }
     auto dense = [&](const float *in, long w, long b, int K, int J, float *out) {
         hipLaunchKernelGGL(field_dense_kernel, dim3(nb((long)n * J)), dim3(256), 0, st, in, P + w, P + b, (long)n, K, J, 1, out);
     };
-    dense(net->x[net->L], o.d1w, o.d1b, net->D0, 2 * FIELD_FC, net->d1);
-    dense(net->d1, o.d2w, o.d2b, 2 * FIELD_FC, FIELD_FC, net->d2);
-    dense(net->d2, o.p1w, o.p1b, FIELD_FC, 2 * FIELD_FC, net->p1);
-    dense(net->p1, o.p2w, o.p2b, 2 * FIELD_FC, net->P2, net->p2);
-    dense(net->d2, o.v1w, o.v1b, FIELD_FC, 2 * FIELD_FC, net->v1);
-    dense(net->v1, o.v2w, o.v2b, 2 * FIELD_FC, FIELD_FC, net->v2);
+    dense(a.x[net->L], o.d1w, o.d1b, net->D0, 2 * FIELD_FC, a.d1);
+    dense(a.d1, o.d2w, o.d2b, 2 * FIELD_FC, FIELD_FC, a.d2);
+    dense(a.d2, o.p1w, o.p1b, FIELD_FC, 2 * FIELD_FC, a.p1);
+    dense(a.p1, o.p2w, o.p2b, 2 * FIELD_FC, net->P2, a.p2);
+    dense(a.d2, o.v1w, o.v1b, FIELD_FC, 2 * FIELD_FC, a.v1);
+    dense(a.v1, o.v2w, o.v2b, 2 * FIELD_FC, FIELD_FC, a.v2);
+}
+
+static FieldActs field_net_acts(const grl_fieldnet *net) {
+    FieldActs a;
+    for (int l = 0; l <= net->L; ++l) a.x[l] = net->x[l];
+    for (int l = 0; l < net->L; ++l) a.idx[l] = net->idx[l];
+    a.d1 = net->d1; a.d2 = net->d2; a.p1 = net->p1; a.p2 = net->p2; a.v1 = net->v1; a.v2 = net->v2;
+    return a;
+}
+
+static int field_forward(grl_fieldnet *net, int n) {
+    hipStream_t st = net->h->stream;
+    const float *P = net->params;
+    const FieldOff &o = net->off;
+    field_trunk(net, field_net_acts(net), n);
     FIELD_DISPATCH(net->A, hipLaunchKernelGGL(field_heads_fwd_kernel<kA>, dim3((n + 3) / 4), dim3(256), 0, st, net->p2, net->v2, net->d_pos, P, o, n,
                                               net->P2, net->HWA, net->cfg.width, net->cfg.scale, net->mu, net->sigma, net->vs));
     PAAC_HIP(net, hipGetLastError());
@@ -395,6 +424,8 @@ static int field_upload(grl_fieldnet *net, int n, const float *states, const int
 }
 
 }  // namespace grl
+
+#include "net_field_rollout.inc"
 
 using namespace grl;
 
@@ -474,6 +505,7 @@ int grl_fieldnet_create(grl_handle *h, const grl_fieldnet_config *cfg, grl_field
 int grl_fieldnet_destroy(grl_fieldnet *n) {
     if (!n) return GRL_OK;
     grl_sync_for_destroy(n->h);      // the handle may have been destroyed first (finaliser order of a host binding)
+    delete n->ro;
     paac_free(n);
     delete n;
     return GRL_OK;
@@ -482,7 +514,10 @@ int grl_fieldnet_destroy(grl_fieldnet *n) {
 const char *grl_fieldnet_last_error(const grl_fieldnet *n) { return paac_last_error(n); }
 int64_t grl_fieldnet_num_params(const grl_fieldnet *n) { return paac_num_params(n); }
 
-int grl_fieldnet_set_params(grl_fieldnet *n, const float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->params : nullptr, (float *)host, cnt, true); }
+int grl_fieldnet_set_params(grl_fieldnet *n, const float *host, int64_t cnt) {
+    if (n) n->param_version += 1;
+    return paac_copy_flat(n, nullptr, n ? n->params : nullptr, (float *)host, cnt, true);
+}
 int grl_fieldnet_get_params(grl_fieldnet *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->params : nullptr, host, cnt, false); }
 int grl_fieldnet_get_grads(grl_fieldnet *n, float *host, int64_t cnt) { return paac_copy_flat(n, nullptr, n ? n->grads : nullptr, host, cnt, false); }
 
@@ -561,6 +596,7 @@ int grl_fieldnet_train(grl_fieldnet *net, int32_t n, const float *states, const 
                        net->stats);
     if (apply_update) {
         net->adam_t += 1;
+        net->param_version += 1;
         hipLaunchKernelGGL(paac_adam_kernel<>, dim3(nb(o.total)), dim3(256), 0, st, net->params, G, net->adam_m, net->adam_v, o.total, net->stats,
                            adam_lr_t(lr, net->adam_t));
     }

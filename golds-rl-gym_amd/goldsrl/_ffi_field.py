@@ -1,11 +1,12 @@
-"""ctypes binding of ConvPolicyVFieldNetwork on the device (C ABI: include/goldsrl_fieldnet.h)."""
+"""ctypes binding of ConvPolicyVFieldNetwork on the device (C ABI: include/goldsrl_fieldnet.h, and include/goldsrl_fieldrollout.h
+for acting and learning on a Swarm handle)."""
 import ctypes as C
 
 import numpy as np
 
 from . import _ffi, _ffi_paac
 
-_P, _I, _F = C.c_void_p, C.c_int32, C.c_float
+_P, _I, _F, _SZ = C.c_void_p, C.c_int32, C.c_float, C.c_size_t
 
 
 class GrlFieldnetConfig(C.Structure):
@@ -26,6 +27,27 @@ FIELD_SIGNATURES = {
     "grl_fieldnet_predict": (C.c_int, [_P, _I, _P, _P, _P, _P, _P]),
     "grl_fieldnet_train": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, _F, _I, _P]),
 }
+
+# include/goldsrl_fieldrollout.h
+FIELD_ROLLOUT_SIGNATURES = {
+    "grl_fieldnet_rollout_bind": (C.c_int, [_P, _F]),
+    "grl_fieldnet_predict_swarm": (C.c_int, [_P, _P, _P, _P]),
+    "grl_fieldnet_debug_grid": (C.c_int, [_P, _I, _P, _P, _P, _SZ]),
+    "grl_fieldnet_rollout": (C.c_int, [_P, _I, _I]),
+    "grl_fieldnet_train_rollout": (C.c_int, [_P, _F, _P]),
+    "grl_fieldnet_train_rollout_grads": (C.c_int, [_P, _P]),
+    "grl_fieldnet_read_rollout": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+    "grl_fieldnet_get_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "grl_fieldnet_set_optimizer_state": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64]),
+    "grl_fieldnet_get_action_counter": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "grl_fieldnet_set_action_counter": (C.c_int, [_P, C.c_uint64]),
+}
+
+# grl_fieldnet_read_rollout: name -> (shape behind (T,), per (E or B), dtype)
+_ROLLOUT_BUFFERS = {"actions": ("B", (2,), np.float32), "env_actions": ("B", (2,), np.float32), "mu": ("B", (2,), np.float32),
+                    "sigma": ("B", (2,), np.float32), "values": ("B", (), np.float32), "rewards": ("B", (), np.float32),
+                    "y": ("B", (), np.float32), "adv": ("B", (), np.float32), "dones": ("E", (), np.uint8),
+                    "locust_bins": ("E", (80, 2), np.uint8), "agent_bins": ("E", (10, 2), np.uint8), "positions": ("E", (10, 2), np.uint8)}
 
 
 def field_param_shapes(height=32, width=32, channels=3, filters=5, conv_layers=2, num_actions=3, fc_hidden=32):
@@ -49,11 +71,11 @@ def glorot_uniform_flat(seed=3, **geometry):
     return _ffi_paac.glorot_uniform_flat(field_param_shapes(**geometry), seed)
 
 
-class FieldNet(_ffi_paac.PaacNet):
+class FieldNet(_ffi_paac.PaacRolloutNet):
     PREFIX = "grl_fieldnet_"
 
     def __init__(self, engine, **kw):
-        self._create(engine, FIELD_SIGNATURES, GrlFieldnetConfig(), kw)
+        self._create(engine, dict(FIELD_SIGNATURES, **FIELD_ROLLOUT_SIGNATURES), GrlFieldnetConfig(), kw)
 
     def _inputs(self, states, positions):
         c = self.cfg
@@ -78,3 +100,38 @@ class FieldNet(_ffi_paac.PaacNet):
         if a.shape != (n, int(self.cfg.num_actions)) or adv.shape != (n,) or y.shape != (n,):
             raise ValueError("train: actions (n,A), advantages (n,), critic_target (n,) expected")
         return self._stats4("train", n, _ffi._ptr(s), _ffi._ptr(p), _ffi._ptr(a), _ffi._ptr(adv), _ffi._ptr(y), lr, 1 if apply_update else 0)
+
+    # -- acting and learning on the Swarm handle the net was created on (include/goldsrl_fieldrollout.h)
+    def rollout_bind(self, gamma):
+        self._check(self.lib.grl_fieldnet_rollout_bind(self.n, gamma))
+
+    def predict_swarm(self):
+        """predict on the handle's current observation: B = 10 * E agent-samples in env-major order."""
+        B = self.eng.E * 10
+        mu, sg, vs = np.empty((B, 2), np.float32), np.empty((B, 2), np.float32), np.empty(B, np.float32)
+        self._check(self.lib.grl_fieldnet_predict_swarm(self.n, _ffi._ptr(mu), _ffi._ptr(sg), _ffi._ptr(vs)))
+        return {"mu": mu, "sigma": sg, "vs": vs}
+
+    def debug_grid(self, locust_bins, agent_bins):
+        """The (n_envs, G, G, 2) density images the device builds from host observations."""
+        lb = np.ascontiguousarray(locust_bins, np.uint8); ab = np.ascontiguousarray(agent_bins, np.uint8)
+        G = int(self.cfg.height)
+        out = np.empty((lb.shape[0], G, G, 2), np.float32)
+        self._check(self.lib.grl_fieldnet_debug_grid(self.n, lb.shape[0], _ffi._ptr(lb), _ffi._ptr(ab), _ffi._ptr(out), out.nbytes))
+        return out
+
+    def rollout(self, T, layout=0):
+        self._check(self.lib.grl_fieldnet_rollout(self.n, T, layout))
+
+    def read_rollout(self, which, T=None):
+        """A buffer of the last rollout of T steps by name; "boot" is (B,)."""
+        E = self.eng.E
+        if which == "boot":
+            a = np.empty(E * 10, np.float32)
+        else:
+            if which not in _ROLLOUT_BUFFERS:
+                raise ValueError("unknown rollout buffer %r" % (which,))
+            per, inner, dtype = _ROLLOUT_BUFFERS[which]
+            a = np.empty((int(T), E * 10 if per == "B" else E) + inner, dtype)
+        self._check(self.lib.grl_fieldnet_read_rollout(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
+        return a

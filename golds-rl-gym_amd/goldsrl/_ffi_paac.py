@@ -91,8 +91,8 @@ class PaacNet(object):
         return dict(zip(STAT_NAMES, stats.tolist()))
 
 
-class PaacTrainerNet(PaacNet):
-    """What the two nets that act, train over rollouts and train over ranks have (ConvNet, FlatNet)."""
+class PaacRolloutNet(PaacNet):
+    """What the nets that act and train over rollouts on the device have (ConvNet, FlatNet, FieldNet)."""
 
     def get_optimizer_state(self):
         """Adam moments and the number of updates applied: with the parameters, the estimator's whole training state."""
@@ -133,6 +133,10 @@ class PaacTrainerNet(PaacNet):
     def train_rollout_grads(self):
         """Loss + backward over the last rollout only: the local mean gradient stays in the net (get_grads)."""
         return self._stats4("train_rollout_grads")
+
+
+class PaacTrainerNet(PaacRolloutNet):
+    """What the two nets that also train over ranks have (ConvNet, FlatNet)."""
 
     def set_grads(self, flat):
         a = np.ascontiguousarray(flat, np.float32)

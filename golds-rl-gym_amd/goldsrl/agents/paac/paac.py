@@ -10,6 +10,7 @@ from ... import _ffi
 from ... import distributed as D
 from ... import rollout as R
 from .actor_learner import ActorLearner
+from .policy_v_network import ConvPolicyVFieldNetwork
 
 
 class _Update(R._GradientExchange):
@@ -174,6 +175,10 @@ class GridPAACLearner(PAACLearner):
         if isinstance(self.device, str) and ':' in self.device:
             device_id = int(self.device.rsplit(':', 1)[1])
         ranks = self._ranks()
+        # the field policy (one density image per env, include/goldsrl_fieldrollout.h) runs through the same calls on one device
+        field = isinstance(self.network, ConvPolicyVFieldNetwork)
+        if field and ranks.world > 1:
+            raise ValueError("ConvPolicyVFieldNetwork trains on one device: its net has no communicator (WORLD_SIZE = %d)" % ranks.world)
         device_id = ranks.local_rank if ranks.world > 1 else device_id
         self.engine = _ffi.Engine(_ffi.ENV_SWARM, self.emulator_counts, device_id=device_id, grid_size=self.network.height,
                                   seed=int(getattr(self, "seed", 1692)), max_episode_steps=int(getattr(self, "max_episode_steps", 128)),
@@ -191,8 +196,9 @@ class GridPAACLearner(PAACLearner):
         if eval_every > 0 and ranks.rank == 0:      # only rank 0 evaluates: the other ranks build neither the monitor nor its env
             from ...envs import make
             from ..state_processors import SwarmStateProcessor
-            from .policy_monitor import ScalarWriter, SwarmPolicyMonitor
-            pe = SwarmPolicyMonitor(env=make("Swarm-eval-v0"), global_policy_net=self.network,
+            from .policy_monitor import FieldSwarmPolicyMonitor, ScalarWriter, SwarmPolicyMonitor
+            pe = (FieldSwarmPolicyMonitor if field else SwarmPolicyMonitor)(
+                                    env="Swarm-eval-v0" if field else make("Swarm-eval-v0"), global_policy_net=self.network,
                                     state_processor=SwarmStateProcessor(grid_size=self.network.height),
                                     summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), saver=None,
                                     network_conf=self.network.conf,

@@ -17,7 +17,7 @@ import numpy as np
 from ...baselines import DEFAULT_SWARM_RULES
 from ..a3c.policy_monitor import _DeviceMonitor
 from .emulator_runner import SolowRunner, SwarmRunner
-from .policy_v_network import ConvSingleAgentPolicyNetwork, FlatPolicyVNetwork
+from .policy_v_network import ConvPolicyVFieldNetwork, ConvSingleAgentPolicyNetwork, FlatPolicyVNetwork
 
 
 class ScalarWriter(object):
@@ -273,3 +273,30 @@ class SwarmPolicyMonitor(PolicyMonitor):
         self.baseline_total_reward = total
         self.env.reset()
         return self.baseline_name, self.baseline_total_reward
+
+
+class FieldSwarmPolicyMonitor(SwarmPolicyMonitor):
+    """SwarmPolicyMonitor for ConvPolicyVFieldNetwork: one episode of the registered eval env on a one-env handle of the NET's grid
+    size (the registration's own handle observes on the conv policy's 84-cell grid).  Per step the policy reads the handle's current
+    observation (grl_fieldnet_predict_swarm) and acts greedily: the action is the norm-clipped mu, handed to the env as float64
+    rows, so swarm-eval.json replays in make_swarm_gif's default arithmetic.  Scalars, the kept best episode and the --baseline /
+    --rule-baseline yardsticks are SwarmPolicyMonitor's.  The reference never built a monitor for this net."""
+
+    def __init__(self, env="Swarm-eval-v0", global_policy_net=None, state_processor=None, summary_writer=None, saver=None, network_conf=None,
+                 learner=None):
+        from ...envs import registry
+        conf = network_conf if network_conf is not None else global_policy_net.conf
+        cls, max_steps, kwargs = registry[env]
+        super(FieldSwarmPolicyMonitor, self).__init__(cls(max_episode_steps=max_steps, grid_size=conf['height'], **kwargs), global_policy_net,
+                                                      state_processor, summary_writer, saver, conf, learner)
+
+    def _bind(self):
+        self.policy_net.bind(self.env._eng, max_samples=1, gamma=0.99)      # gamma: the bind checks the geometry against the handle
+
+    def get_action_from_policy(self, processed_state, history, positions, sess=None):
+        mu = self.policy_net.net.predict_swarm()['mu']
+        return SwarmRunner.transform_actions_for_env(mu).astype(np.float64)
+
+    @staticmethod
+    def _create_policy_estimator(conf):
+        return ConvPolicyVFieldNetwork(conf)

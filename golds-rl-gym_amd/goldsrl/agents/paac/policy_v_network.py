@@ -117,11 +117,15 @@ class ConvPolicyVFieldNetwork(object):
         return dict(height=self.height, width=self.width, channels=self.channels, filters=self.filters, conv_layers=self.conv_layers,
                     num_actions=self.num_actions)
 
-    def bind(self, engine, seed=3, max_samples=256):
+    def bind(self, engine, seed=3, max_samples=256, gamma=None):
+        """gamma given: the net is to act and learn on `engine`, a Swarm batch of grid_size == height == width (2 channels,
+        2 actions) -- net.rollout / net.train_rollout with that discount (include/goldsrl_fieldrollout.h)."""
         clip = self.clip_norm if self.clip_norm_type == 'global' else 0.0
         self.net = _ffi_field.FieldNet(engine, max_samples=max_samples, scale=self.scale, entropy_beta=self.entropy_beta, clip_norm=clip,
                                        **self._geometry())
         self.net.set_params(_ffi_field.glorot_uniform_flat(seed, **self._geometry()))
+        if gamma is not None:
+            self.net.rollout_bind(gamma)
         return self
 
     def predict(self, states, histories, positions, session=None):

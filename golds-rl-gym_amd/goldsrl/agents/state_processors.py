@@ -44,6 +44,22 @@ class SwarmStateProcessor(StateProcessor):
         return np.stack([counts[:, :, 0] / float(len(state[0])), counts[:, :, 1] / float(len(state[1]))], axis=-1)
 
 
+def swarm_field_inputs(locust_bins, agent_bins, positions, grid):
+    """The two inputs of ConvPolicyVFieldNetwork from the Swarm handle's compact observation (locust_bins (E,80,2), agent_bins
+    (E,10,2), positions (E,10,2)): process_state's density image per env as float32 -- state[bx, by, 0] = float32(count of locusts
+    in bin (bx, by) / 80.0), [.., 1] = float32(count of agents / 10.0), bins 255 (outside the box) not counted -- and the agents'
+    (height_idx, width_idx).  Returns (states float32 (E,G,G,2), positions int32 (E,10,2)).  The numpy restatement of what
+    csrc/net_field_rollout.inc builds on the device."""
+    lb, ab = np.asarray(locust_bins, np.uint8), np.asarray(agent_bins, np.uint8)
+    E, G = lb.shape[0], int(grid)
+    counts = np.zeros((E, G, G, 2), np.int64)
+    for ch, bins in ((0, lb), (1, ab)):
+        e, k = np.nonzero(bins[:, :, 0] != 255)
+        np.add.at(counts, (e, bins[e, k, 0], bins[e, k, 1], ch), 1)
+    states = np.stack([counts[..., 0] / 80.0, counts[..., 1] / 10.0], axis=-1).astype(np.float32)
+    return states, np.ascontiguousarray(positions, np.int32).reshape(E, 10, 2)
+
+
 class SolowStateProcessor(StateProcessor):
     def __init__(self):
         super(SolowStateProcessor, self).__init__(np.array([100., 1.]))

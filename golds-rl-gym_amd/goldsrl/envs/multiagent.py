@@ -28,14 +28,15 @@ class SwarmEnv(object):
     dt = 0.05
     N_BURN_IN = 10
 
-    def __init__(self, seed=None, max_episode_steps=None, device_id=0, generator_seed=None):
+    def __init__(self, seed=None, max_episode_steps=None, device_id=0, generator_seed=None, grid_size=None):
         self.n_seed = seed
         self.states = None
         self.t = 0
         flags = _ffi.F_RESEED_EACH_RESET if seed else 0    # `if self.n_seed: np.random.seed(...)` on every reset
         gseed = generator_seed if generator_seed is not None else (seed if seed else 1692)
+        kw = {} if grid_size is None else {"grid_size": int(grid_size)}      # the observation's grid (the field policy's height)
         self._eng = _ffi.Engine(_ffi.ENV_SWARM, 1, device_id=device_id, seed=int(gseed), flags=flags,
-                                max_episode_steps=int(max_episode_steps or 0))
+                                max_episode_steps=int(max_episode_steps or 0), **kw)
         self.np_random = None       # the reference's generator stream of a seeded env, continued after the reset draws
 
     # gym.Env public API (gym 0.9.x forwards to the underscore hooks)

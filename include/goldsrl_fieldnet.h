@@ -65,4 +65,7 @@ int grl_fieldnet_train(grl_fieldnet *net, int32_t n, const float *states, const 
 #ifdef __cplusplus
 }
 #endif
+
+#include "goldsrl_fieldrollout.h"
+
 #endif /* GOLDSRL_FIELDNET_H */
