@@ -17,6 +17,8 @@
 #include "common.h"
 #include "net_paac_host.h"
 #include "rng.h"
+#include "swarm_dev.h"
+#include "episode_host.h"
 
 namespace grl {
 
@@ -426,6 +428,7 @@ static int field_upload(grl_fieldnet *net, int n, const float *states, const int
 }  // namespace grl
 
 #include "net_field_rollout.inc"
+#include "net_field_eval.inc"
 
 using namespace grl;
 
@@ -505,6 +508,7 @@ int grl_fieldnet_create(grl_handle *h, const grl_fieldnet_config *cfg, grl_field
 int grl_fieldnet_destroy(grl_fieldnet *n) {
     if (!n) return GRL_OK;
     grl_sync_for_destroy(n->h);      // the handle may have been destroyed first (finaliser order of a host binding)
+    fe_release(n);
     delete n->ro;
     paac_free(n);
     delete n;

@@ -25,8 +25,20 @@ constexpr int FR_SPLIT = 128;                  // samples per slab of a split we
 constexpr int FR_KT = 8;                       // rows of a dense weight gradient per lane
 constexpr size_t FR_LDS_BYTES = 64 * 1024;
 
+// the outputs of the last grl_fieldnet_eval (net_field_eval.inc); the buffers are on the handle's allocation list (episode_reserve)
+struct FieldEval {
+    double *rewards = nullptr, *actions = nullptr;                                       // (cap_steps) (cap_act,10,2)
+    int32_t *length = nullptr;                                                          // (cap_envs)
+    uint8_t *finished = nullptr;
+    float *tr_mu = nullptr, *tr_sigma = nullptr, *tr_value = nullptr, *tr_raw = nullptr; // (cap_trace,10,2) x2, (cap_trace), (cap_trace,10,2)
+    uint8_t *tr_lb = nullptr, *tr_ab = nullptr, *tr_pos = nullptr;                       // (cap_trace,80,2) (cap_trace,10,2) x2
+    double *tr_x = nullptr, *tr_xa = nullptr;                                           // (cap_trace,80,2) (cap_trace,10,2)
+    size_t cap_steps = 0, cap_act = 0, cap_envs = 0, cap_trace = 0;
+    int max_steps = 0, trace_env = -1, keep_actions = 0;                                // of the last call; max_steps == 0: none yet
+};
+
 struct FieldRollout {
-    int fused = -1;                // -1: environment not read yet
+    int fused = -1;               // -1: environment not read yet
     bool headt = true;
     float gamma = 0.99f;
     long headt_version = -1;
@@ -44,6 +56,7 @@ struct FieldRollout {
     float *dxl[FIELD_MAX_LAYERS + 1], *dzc = nullptr, *cslab = nullptr, *slab = nullptr;
     float *dd1 = nullptr, *dd2 = nullptr, *dp1 = nullptr, *dp2 = nullptr, *dv1 = nullptr, *dv2 = nullptr, *dzh = nullptr, *zvs = nullptr;
     int32_t *cell_count = nullptr, *cell_off = nullptr, *cell_list = nullptr;      // the chunk's agent-samples listed per grid cell
+    FieldEval ev;                  // grl_fieldnet_eval's outputs (net_field_eval.inc)
 };
 
 // element (k, col) of a head matrix: base[k * sk + col * sc] -- row-major mu_w (sk = HWA, sc = 1) or the column-major copy (1, P2)
@@ -82,25 +95,35 @@ __global__ __launch_bounds__(256) void field_grid_kernel(const uint8_t *__restri
     }
 }
 
-// a = mu + sigma * N(0,1) (paac.py:418) in float64, then SwarmRunner.transform_actions_for_env (emulator_runner.py:113-118)
+// SwarmRunner.transform_actions_for_env (emulator_runner.py:113-118): transform_kernel's statements (rollout_math.hip)
+__device__ __forceinline__ float2 field_norm_clip(float2 r) {
+    const float d = sqrtf(r.x * r.x + r.y * r.y);
+    if (d >= 1.0f) { r.x /= d; r.y /= d; }
+    return r;
+}
+
+// a = mu + sigma * N(0,1) (paac.py:418) in float64, then the norm clip
 __device__ __forceinline__ void field_sample_one(float2 m, float2 s, uint64_t seed, uint32_t env_id, uint32_t counter, uint32_t agent, float2 *raw,
                                                  float2 *envact) {
     double e0, e1;
     normal_pair(rng_block(seed, env_id, counter, RS_FIELD_ACTION, agent), e0, e1);
-    float2 r = make_float2((float)((double)m.x + (double)s.x * e0), (float)((double)m.y + (double)s.y * e1));
+    const float2 r = make_float2((float)((double)m.x + (double)s.x * e0), (float)((double)m.y + (double)s.y * e1));
     *raw = r;
-    const float d = sqrtf(r.x * r.x + r.y * r.y);
-    if (d >= 1.0f) { r.x /= d; r.y /= d; }
-    *envact = r;
+    *envact = field_norm_clip(r);
 }
 
-struct FieldStepArgs {
-    const uint8_t *lb, *ab, *pos;      // the handle's observation
+// what one env's forward reads besides its observation (field_env_forward)
+struct FieldFwdArgs {
     const float *P;
     HeadView hv;
     FieldOff o;
-    int G, F, L, P2, HWA, D0, m0n, m1n, nenv;
+    int G, F, L, P2, HWA, D0, m0n, m1n;
     float scale;
+};
+
+struct FieldStepArgs : FieldFwdArgs {
+    const uint8_t *lb, *ab, *pos;      // the handle's observation
+    int nenv;
     float *mu, *sigma, *vs;            // (B,2) (B,2) (B)
     float *raw, *envact;               // (B,2) each, or nullptr: no sampling, no record
     uint64_t seed;
@@ -118,34 +141,45 @@ __device__ __forceinline__ void field_record_obs(const FieldStepArgs &a, int i, 
     }
 }
 
+// U > 1: U rows' loads in flight per wait (the whole-episode kernel, whose compiler otherwise waits for every load); the sum's order stays
+template <int U>
 __device__ __forceinline__ void field_lds_dense(const float *in, const float *__restrict__ w, const float *__restrict__ b, int K, int J, float *out, int t0,
                                                 int nt) {
     for (int j = t0; j < J; j += nt) {
         float acc = b[j];
-        for (int k = 0; k < K; ++k) acc += in[k] * w[(long)k * J + j];
+        if (U > 1) {
+#pragma unroll U
+            for (int k = 0; k < K; ++k) acc += in[k] * w[(long)k * J + j];
+        } else {
+            for (int k = 0; k < K; ++k) acc += in[k] * w[(long)k * J + j];
+        }
         out[j] = fmaxf(acc, 0.f);
     }
 }
 
-// One step's forward of one env per workgroup, out of LDS; sums in the order of field_conv_pool / field_dense / field_heads_fwd.
-__global__ __launch_bounds__(256) void field_fused_step_kernel(FieldStepArgs a) {
-    extern __shared__ float lds[];
-    const int env = blockIdx.x, tid = threadIdx.x, G = a.G, n0 = G * G * 2;
+// floats of one env's forward in LDS: the image, the two pooled maps, d1 d2 p1 v1 v2, p2
+static size_t field_fwd_floats(int G, int m0n, int m1n, int P2) { return (size_t)G * G * 2 + m0n + m1n + 64 + 32 + 64 + 64 + 32 + P2; }
+
+// One env's forward out of LDS (field_fwd_floats) on the nt lanes of its workgroup (whole waves, at least two); sums in the order of
+// field_conv_pool / field_dense / field_heads_fwd.  lb / ab / pos: the env's compact observation, in global memory or in LDS -- bytes
+// written just before the call are ordered by the first barrier below.  emit(agent, mu, sigma, vs) runs on lane 0 of the agent's
+// wave; no barrier follows it.  Every output element is one lane's sequential sum and the head sums are 64-lane field_wave_sums,
+// so nt decides which lane computes an element, not its bits (field_fused_step_kernel: 256 lanes, field_eval_kernel: 320).
+template <int U = 0, typename EMIT>
+__device__ __forceinline__ void field_env_forward(const FieldFwdArgs &a, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, float *lds, int tid,
+                                                  int nt, EMIT &&emit) {
+    const int G = a.G, n0 = G * G * 2;
     float *img = lds, *m0 = img + n0, *m1 = m0 + a.m0n, *d1 = m1 + a.m1n, *d2 = d1 + 64, *p1 = d2 + 32, *v1 = p1 + 64, *v2 = v1 + 64, *p2 = v2 + 32;
-    if (a.raw) {
-        if (env == 0 && tid == 0 && a.done_count) *a.done_count = 0;      // the env step that follows on this stream appends to it
-        field_record_obs(a, env * 256 + tid, gridDim.x * 256);
-    }
     int *cnt = reinterpret_cast<int *>(img);
-    for (int i = tid; i < n0; i += 256) cnt[i] = 0;
+    for (int i = tid; i < n0; i += nt) cnt[i] = 0;
     __syncthreads();
     if (tid < N_POINTS) {
-        const uint8_t *b = tid < N_LOCUSTS ? a.lb + (long)env * (N_LOCUSTS * 2) + tid * 2 : a.ab + (long)env * (N_AGENTS * 2) + (tid - N_LOCUSTS) * 2;
+        const uint8_t *b = tid < N_LOCUSTS ? lb + tid * 2 : ab + (tid - N_LOCUSTS) * 2;
         const int bx = b[0], by = b[1];
         if (bx < G && by < G) atomicAdd(&cnt[(bx * G + by) * 2 + (tid < N_LOCUSTS ? 0 : 1)], 1);
     }
     __syncthreads();
-    for (int i = tid; i < n0; i += 256) {
+    for (int i = tid; i < n0; i += nt) {
         const int c = cnt[i];
         img[i] = field_density(c, i & 1);
     }
@@ -156,7 +190,7 @@ __global__ __launch_bounds__(256) void field_fused_step_kernel(FieldStepArgs a) 
         float *out = (l & 1) ? m1 : m0;
         const float *w = a.P + a.o.cw[l], *b = a.P + a.o.cb[l];
         const int F = a.F, H2 = H / 2, total = H2 * H2 * F;
-        for (int i = tid; i < total; i += 256) {
+        for (int i = tid; i < total; i += nt) {
             const int f = i % F, x2 = (i / F) % H2, y2 = i / (F * H2);
             float best = 0.f;
             for (int d = 0; d < 4; ++d) {
@@ -182,23 +216,24 @@ __global__ __launch_bounds__(256) void field_fused_step_kernel(FieldStepArgs a) 
         in = out; H = H2; Cin = F;
     }
     const FieldOff &o = a.o;
-    field_lds_dense(in, a.P + o.d1w, a.P + o.d1b, a.D0, 64, d1, tid, 256);
+    field_lds_dense<U>(in, a.P + o.d1w, a.P + o.d1b, a.D0, 64, d1, tid, nt);
     __syncthreads();
-    field_lds_dense(d1, a.P + o.d2w, a.P + o.d2b, 64, 32, d2, tid, 256);
+    field_lds_dense<U>(d1, a.P + o.d2w, a.P + o.d2b, 64, 32, d2, tid, nt);
     __syncthreads();
-    if (tid < 128) field_lds_dense(d2, a.P + o.p1w, a.P + o.p1b, 32, 64, p1, tid, 128);      // the two towers side by side
-    else field_lds_dense(d2, a.P + o.v1w, a.P + o.v1b, 32, 64, v1, tid - 128, 128);
+    const int half = nt / 2;      // the two towers side by side: 128 + 128 lanes of 256, 160 + 160 of 320
+    if (tid < half) field_lds_dense<U>(d2, a.P + o.p1w, a.P + o.p1b, 32, 64, p1, tid, half);
+    else field_lds_dense<U>(d2, a.P + o.v1w, a.P + o.v1b, 32, 64, v1, tid - half, nt - half);
     __syncthreads();
-    field_lds_dense(p1, a.P + o.p2w, a.P + o.p2b, 64, a.P2, p2, tid, 256);
-    field_lds_dense(v1, a.P + o.v2w, a.P + o.v2b, 64, 32, v2, tid, 256);
+    field_lds_dense<U>(p1, a.P + o.p2w, a.P + o.p2b, 64, a.P2, p2, tid, nt);
+    field_lds_dense<U>(v1, a.P + o.v2w, a.P + o.v2b, 64, 32, v2, tid, nt);
     __syncthreads();
     // the ten agents: a wave per agent, lanes over the rows of its 2A columns
-    const int wave = tid >> 6, lane = tid & 63;
+    const int wave = tid >> 6, lane = tid & 63, waves = nt >> 6;
     float zv = lane < FIELD_FC ? v2[lane] * a.P[o.v3w + lane] : 0.f;
     zv = field_wave_sum(zv) + a.P[o.v3b];
     const float vs = -a.scale * (zv > 20.f ? zv : log1pf(expf(zv)));
-    for (int ag = wave; ag < FR_AGENTS; ag += 4) {
-        const uint8_t *pp = a.pos + (long)env * (N_AGENTS * 2) + ag * 2;
+    for (int ag = wave; ag < FR_AGENTS; ag += waves) {
+        const uint8_t *pp = pos + ag * 2;
         const int px = min((int)pp[0], G - 1), py = min((int)pp[1], G - 1);
         const long col = (long)(px * G + py) * FR_A;
         const float *mw = a.hv.mu + col * a.hv.sc, *sw = a.hv.sg + col * a.hv.sc;
@@ -211,16 +246,30 @@ __global__ __launch_bounds__(256) void field_fused_step_kernel(FieldStepArgs a) 
         }
         mx = field_wave_sum(mx); sx = field_wave_sum(sx); my = field_wave_sum(my); sy = field_wave_sum(sy);
         if (lane == 0) {
-            const long i = (long)env * FR_AGENTS + ag;
             const float2 m = make_float2(tanhf(mx + a.P[o.mub + col]), tanhf(my + a.P[o.mub + col + 1]));
             const float2 s = make_float2(1.0f / (1.0f + expf(-(sx + a.P[o.sgb + col]))), 1.0f / (1.0f + expf(-(sy + a.P[o.sgb + col + 1]))));
-            reinterpret_cast<float2 *>(a.mu)[i] = m;
-            reinterpret_cast<float2 *>(a.sigma)[i] = s;
-            a.vs[i] = vs;
-            if (a.raw) field_sample_one(m, s, a.seed, (uint32_t)env + a.env_off, a.counter, (uint32_t)ag, reinterpret_cast<float2 *>(a.raw) + i,
-                                        reinterpret_cast<float2 *>(a.envact) + i);
+            emit(ag, m, s, vs);
         }
     }
+}
+
+// One step's forward of one env per workgroup, from the handle's observation in global memory.
+__global__ __launch_bounds__(256) void field_fused_step_kernel(FieldStepArgs a) {
+    extern __shared__ float lds[];
+    const int env = blockIdx.x, tid = threadIdx.x;
+    if (a.raw) {
+        if (env == 0 && tid == 0 && a.done_count) *a.done_count = 0;      // the env step that follows on this stream appends to it
+        field_record_obs(a, env * 256 + tid, gridDim.x * 256);
+    }
+    field_env_forward(a, a.lb + (long)env * (N_LOCUSTS * 2), a.ab + (long)env * (N_AGENTS * 2), a.pos + (long)env * (N_AGENTS * 2), lds, tid, 256,
+                      [&](int ag, float2 m, float2 s, float vs) {
+                          const long i = (long)env * FR_AGENTS + ag;
+                          reinterpret_cast<float2 *>(a.mu)[i] = m;
+                          reinterpret_cast<float2 *>(a.sigma)[i] = s;
+                          a.vs[i] = vs;
+                          if (a.raw) field_sample_one(m, s, a.seed, (uint32_t)env + a.env_off, a.counter, (uint32_t)ag, reinterpret_cast<float2 *>(a.raw) + i,
+                                                      reinterpret_cast<float2 *>(a.envact) + i);
+                      });
 }
 
 // the heads of agent-samples [0, n) of a chunk whose env-rows are in p2 / v2: sample i reads row i / 10.  One wave per sample,
@@ -538,7 +587,7 @@ static int fr_prepare(grl_fieldnet *net, const char *fn) {
         const int G = net->cfg.height;
         r->m0n = (G / 2) * (G / 2) * net->F;
         r->m1n = net->L >= 2 ? (G / 4) * (G / 4) * net->F : 0;
-        r->lds_bytes = ((size_t)G * G * 2 + r->m0n + r->m1n + 64 + 32 + 64 + 64 + 32 + net->P2) * sizeof(float);
+        r->lds_bytes = field_fwd_floats(G, r->m0n, r->m1n, net->P2) * sizeof(float);
         const size_t B = (size_t)net->h->E * FR_AGENTS;
         if ((rc = paac_alloc(net, &r->cur_mu, B * FR_A)) || (rc = paac_alloc(net, &r->cur_sg, B * FR_A)) || (rc = paac_alloc(net, &r->cur_vs, B))) return rc;
         if (r->headt && ((rc = paac_alloc(net, &r->muwt, (size_t)net->P2 * net->HWA)) || (rc = paac_alloc(net, &r->sgwt, (size_t)net->P2 * net->HWA)))) return rc;

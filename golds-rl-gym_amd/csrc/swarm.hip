@@ -37,22 +37,6 @@ struct SwarmParams {
     int no_wind;                 // MODE_STEP: SwarmEnv._step(v_action, add_wind=False) -- the agents' action row is used as it is (multiagent.py:33-36)
 };
 
-// searchsorted(edges, v, 'right') for edges = linspace(lo, hi, G+1) as numpy builds them:
-// edge(k) = k*step + lo (two roundings), edge(G) = hi exactly (state_processors.py:31 via histogramdd).
-__device__ __forceinline__ double edge_at(int k, double lo, double hi, double step, int G) {
-    return (k >= G) ? hi : ((double)k * step + lo);
-}
-__device__ __forceinline__ int count_edges_le(double v, double lo, double hi, double step, int G) {
-    if (!(v >= lo)) return 0;        // below the first edge (or NaN)
-    if (v >= hi) return G + 1;
-    double gf = floor((v - lo) / step);
-    int g = (gf > (double)G) ? G : (int)gf;   // guess: index of the last edge <= v
-    if (g < 0) g = 0;
-    for (int it = 0; it < 4 && g < G && edge_at(g + 1, lo, hi, step, G) <= v; ++it) ++g;
-    for (int it = 0; it < 4 && g > 0 && edge_at(g, lo, hi, step, G) > v; ++it) --g;
-    return g + 1;
-}
-
 enum { MODE_STEP = 0, MODE_OBSERVE = 1, MODE_RESET = 2 };
 
 // The body of swarm_kernel / swarm_kernel_refdiv; MATH selects pair_term's arithmetic.
@@ -241,41 +225,19 @@ __device__ __forceinline__ void swarm_body(const SwarmParams &P) {
 
     // ---- observation: process_state (state_processors.py:29-42) -------------------------------
     if (P.flags & GRL_F_SWARM_NO_OBSERVE) return;
-    if (j == 0) {   // np.mean(vstack([x, xa]), axis=0)[0]: sequential row-by-row sum, then /90
-        double s = L.p[el][0].x;
-        for (int i = 1; i < N_POINTS; ++i) s += L.p[el][i].x;
-        L.meanx[el] = s / (double)N_POINTS;
-    }
+    if (j == 0) L.meanx[el] = swarm_mean_x(L.p[el]);
     __syncthreads();
     const int G = P.grid;
-    const double ylo = 0.0, yhi = 6.0;                 // [0, 2*HEIGHT]  (state_processors.py:27)
-    const double ystep = (yhi - ylo) / (double)G;
     {
-        double m = L.meanx[el];
-        double lo = m - 1.5, hi = m + 1.5;             // WIDTH/2 (state_processors.py:27)
-        double step = (hi - lo) / (double)G;
-        int cx = count_edges_le(xj, lo, hi, step, G);
-        int cy = count_edges_le(yj, ylo, yhi, ystep, G);
-        int bx = (xj == hi) ? G - 1 : cx - 1;          // histogramdd: a value on the last edge joins the last bin
-        int by = (yj == yhi) ? G - 1 : cy - 1;
-        bool in = bx >= 0 && bx < G && by >= 0 && by < G;
-        if (active) reinterpret_cast<uint16_t *>(P.lbins)[(size_t)env * N_LOCUSTS + j] = in ? (uint16_t)(bx | (by << 8)) : (uint16_t)0xFFFF;
+        int cx, cy;
+        const uint16_t bin = swarm_point_bin(xj, yj, L.meanx[el], G, cx, cy);
+        if (active) reinterpret_cast<uint16_t *>(P.lbins)[(size_t)env * N_LOCUSTS + j] = bin;
     }
     if (aactive) {
-        double2 q = L.p[ea][N_LOCUSTS + a];
-        double m = L.meanx[ea];
-        double lo = m - 1.5, hi = m + 1.5;
-        double step = (hi - lo) / (double)G;
-        int cx = count_edges_le(q.x, lo, hi, step, G);
-        int cy = count_edges_le(q.y, ylo, yhi, ystep, G);
-        int bx = (q.x == hi) ? G - 1 : cx - 1;
-        int by = (q.y == yhi) ? G - 1 : cy - 1;
-        bool in = bx >= 0 && bx < G && by >= 0 && by < G;
-        reinterpret_cast<uint16_t *>(P.abins)[(size_t)aenv * N_AGENTS + a] = in ? (uint16_t)(bx | (by << 8)) : (uint16_t)0xFFFF;
-        // np.digitize == count of edges <= v, clamped to G-1 (state_processors.py:35-40, quirk Q2)
-        int px = cx >= G ? G - 1 : cx;
-        int py = cy >= G ? G - 1 : cy;
-        reinterpret_cast<uint16_t *>(P.pos)[(size_t)aenv * N_AGENTS + a] = (uint16_t)(px | (py << 8));
+        const double2 q = L.p[ea][N_LOCUSTS + a];
+        int cx, cy;
+        reinterpret_cast<uint16_t *>(P.abins)[(size_t)aenv * N_AGENTS + a] = swarm_point_bin(q.x, q.y, L.meanx[ea], G, cx, cy);
+        reinterpret_cast<uint16_t *>(P.pos)[(size_t)aenv * N_AGENTS + a] = swarm_point_pos(cx, cy, G);
     }
 }
 

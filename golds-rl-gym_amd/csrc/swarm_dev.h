@@ -1,6 +1,7 @@
 // Device-side Swarm arithmetic shared by the translation units that step a Swarm env (swarm.hip: the step / reset / observe kernels,
-// swarm_replay.hip: whole scripted episodes in one launch): the workgroup's LDS layout, the constants of envs/multiagent.py and
-// SwarmEnv._step for the 4 envs of a 320-lane workgroup (block_step).  Both files are compiled with -ffp-contract=off.
+// swarm_replay.hip / swarm_rules.hip: whole scripted or rule-driven episodes in one launch, net_field_eval.inc: the field policy's): the
+// workgroup's LDS layout, the constants of envs/multiagent.py, SwarmEnv._step for the 4 envs of a 320-lane workgroup (block_step) and the
+// compact observation of one point.  Every file is compiled with -ffp-contract=off.
 #pragma once
 #include <type_traits>
 
@@ -180,6 +181,53 @@ __device__ __forceinline__ void block_step(SwarmLds &L, int tid, int el, int j, 
         L.rew[el] = -(s / (double)N_LOCUSTS);
     }
     __syncthreads();
+}
+
+// ---- the compact observation: SwarmStateProcessor.process_state (state_processors.py:29-42) from positions in LDS / registers
+// (swarm.hip's step, reset and observe kernels; net_field_eval.inc's whole-episode kernel)
+
+// searchsorted(edges, v, 'right') for edges = linspace(lo, hi, G+1) as numpy builds them:
+// edge(k) = k*step + lo (two roundings), edge(G) = hi exactly (state_processors.py:31 via histogramdd).
+__device__ __forceinline__ double edge_at(int k, double lo, double hi, double step, int G) {
+    return (k >= G) ? hi : ((double)k * step + lo);
+}
+__device__ __forceinline__ int count_edges_le(double v, double lo, double hi, double step, int G) {
+    if (!(v >= lo)) return 0;        // below the first edge (or NaN)
+    if (v >= hi) return G + 1;
+    double gf = floor((v - lo) / step);
+    int g = (gf > (double)G) ? G : (int)gf;   // guess: index of the last edge <= v
+    if (g < 0) g = 0;
+    for (int it = 0; it < 4 && g < G && edge_at(g + 1, lo, hi, step, G) <= v; ++it) ++g;
+    for (int it = 0; it < 4 && g > 0 && edge_at(g, lo, hi, step, G) > v; ++it) --g;
+    return g + 1;
+}
+
+// np.mean(vstack([x, xa]), axis=0)[0] of an env's 90 points: sequential row-by-row sum, then /90
+__device__ __forceinline__ double swarm_mean_x(const double2 *pts) {
+    double s = pts[0].x;
+    for (int i = 1; i < N_POINTS; ++i) s += pts[i].x;
+    return s / (double)N_POINTS;
+}
+
+// The bin pair of one point as bx | by << 8, 0xFFFF outside the box; cx / cy: the counts of edges <= the point's coordinates.
+__device__ __forceinline__ uint16_t swarm_point_bin(double px, double py, double meanx, int G, int &cx, int &cy) {
+    const double ylo = 0.0, yhi = 6.0;                 // [0, 2*HEIGHT]  (state_processors.py:27)
+    const double ystep = (yhi - ylo) / (double)G;
+    double lo = meanx - 1.5, hi = meanx + 1.5;         // WIDTH/2 (state_processors.py:27)
+    double step = (hi - lo) / (double)G;
+    cx = count_edges_le(px, lo, hi, step, G);
+    cy = count_edges_le(py, ylo, yhi, ystep, G);
+    int bx = (px == hi) ? G - 1 : cx - 1;              // histogramdd: a value on the last edge joins the last bin
+    int by = (py == yhi) ? G - 1 : cy - 1;
+    bool in = bx >= 0 && bx < G && by >= 0 && by < G;
+    return in ? (uint16_t)(bx | (by << 8)) : (uint16_t)0xFFFF;
+}
+
+// an agent's position pair: np.digitize == count of edges <= v, clamped to G-1 (state_processors.py:35-40, quirk Q2)
+__device__ __forceinline__ uint16_t swarm_point_pos(int cx, int cy, int G) {
+    int px = cx >= G ? G - 1 : cx;
+    int py = cy >= G ? G - 1 : cy;
+    return (uint16_t)(px | (py << 8));
 }
 
 // Host side of the whole-episode kernels (swarm_replay.hip, swarm_rules.hip).

@@ -43,6 +43,17 @@ FIELD_ROLLOUT_SIGNATURES = {
     "grl_fieldnet_set_action_counter": (C.c_int, [_P, C.c_uint64]),
 }
 
+# include/goldsrl_fieldeval.h
+FIELD_EVAL_SIGNATURES = {
+    "grl_fieldnet_eval": (C.c_int, [_P, _I, _I, _I, _I, _I]),
+    "grl_fieldnet_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+}
+
+# grl_fieldnet_read_eval: the traced env's outputs, name -> (shape behind (max_steps,), dtype)
+_EVAL_TRACE = {"trace_mu": ((10, 2), np.float32), "trace_sigma": ((10, 2), np.float32), "trace_value": ((), np.float32),
+               "trace_raw": ((10, 2), np.float32), "trace_locust_bins": ((80, 2), np.uint8), "trace_agent_bins": ((10, 2), np.uint8),
+               "trace_positions": ((10, 2), np.uint8), "trace_x": ((80, 2), np.float64), "trace_xa": ((10, 2), np.float64)}
+
 # grl_fieldnet_read_rollout: name -> (shape behind (T,), per (E or B), dtype)
 _ROLLOUT_BUFFERS = {"actions": ("B", (2,), np.float32), "env_actions": ("B", (2,), np.float32), "mu": ("B", (2,), np.float32),
                     "sigma": ("B", (2,), np.float32), "values": ("B", (), np.float32), "rewards": ("B", (), np.float32),
@@ -75,7 +86,7 @@ class FieldNet(_ffi_paac.PaacRolloutNet):
     PREFIX = "grl_fieldnet_"
 
     def __init__(self, engine, **kw):
-        self._create(engine, dict(FIELD_SIGNATURES, **FIELD_ROLLOUT_SIGNATURES), GrlFieldnetConfig(), kw)
+        self._create(engine, dict(FIELD_SIGNATURES, **dict(FIELD_ROLLOUT_SIGNATURES, **FIELD_EVAL_SIGNATURES)), GrlFieldnetConfig(), kw)
 
     def _inputs(self, states, positions):
         c = self.cfg
@@ -118,6 +129,37 @@ class FieldNet(_ffi_paac.PaacRolloutNet):
         G = int(self.cfg.height)
         out = np.empty((lb.shape[0], G, G, 2), np.float32)
         self._check(self.lib.grl_fieldnet_debug_grid(self.n, lb.shape[0], _ffi._ptr(lb), _ffi._ptr(ab), _ffi._ptr(out), out.nbytes))
+        return out
+
+    # -- whole episodes in one launch (include/goldsrl_fieldeval.h)
+    def read_eval(self, which, max_steps):
+        """An output of the last eval of max_steps steps by name."""
+        E, S = self.eng.E, int(max_steps)
+        if which in _EVAL_TRACE:
+            inner, dtype = _EVAL_TRACE[which]
+            a = np.empty((S,) + inner, dtype)
+        else:
+            shape, dtype = {"rewards": ((E, S), np.float64), "length": ((E,), np.int32), "finished": ((E,), np.uint8),
+                            "actions": ((E, S, 10, 2), np.float64)}.get(which, ((0,), np.uint8))      # an unknown name is the library's to refuse
+            a = np.empty(shape, dtype)
+        self._check(self.lib.grl_fieldnet_read_eval(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
+        return a
+
+    def eval(self, max_steps, greedy=True, rows32=False, keep_actions=False, trace_env=-1):
+        """Every env of the engine plays one episode from its CURRENT state (reset first), at most max_steps steps, in one kernel
+        launch; the engine and the net are left as they were.  greedy: the action is the norm-clipped mu, else mu + sigma N(0,1)
+        drawn with the rollout's noise key at the net's action counter (which stays).  rows32: step with the float32 row, as the
+        training rollout does, else with its float64 widening (SwarmEnv.step called directly).  Returns rewards (E,S) float64,
+        length (E), finished (E), total_reward (E) -- the float64 sum in step order -- plus actions (E,S,10,2) with keep_actions
+        and the trace_* outputs of env trace_env."""
+        S = int(max_steps)
+        self._check(self.lib.grl_fieldnet_eval(self.n, S, 1 if greedy else 0, 1 if rows32 else 0, 1 if keep_actions else 0, int(trace_env)))
+        names = ["rewards", "length", "finished"] + (["actions"] if keep_actions else []) + (sorted(_EVAL_TRACE) if trace_env >= 0 else [])
+        out = {k: self.read_eval(k, S) for k in names}
+        total = np.zeros(self.eng.E, np.float64)
+        for t in range(S):      # step order; rewards past an env's length are zero
+            total = total + out["rewards"][:, t]
+        out["total_reward"] = total
         return out
 
     def rollout(self, T, layout=0):

@@ -202,7 +202,7 @@ class GridPAACLearner(PAACLearner):
                                     state_processor=SwarmStateProcessor(grid_size=self.network.height),
                                     summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), saver=None,
                                     network_conf=self.network.conf,
-                                    learner=self)
+                                    learner=self, **({"n_envs": max(1, int(getattr(self, "eval_envs", 1) or 1))} if field else {}))
             if bool(getattr(self, "baseline", False)):
                 logging.info("Scripted baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.baseline())
             if bool(getattr(self, "rule_baseline", False)):      # after --baseline: with both, the rule baseline is the one written

@@ -231,6 +231,10 @@ class SwarmPolicyMonitor(PolicyMonitor):
             return self.get_action_from_policy(None, None, None, sess)
 
         rewards, taken = self._play(self.env.reset(), choose)
+        return self._episode_played(global_step, rewards, taken)
+
+    def _episode_played(self, global_step, rewards, taken):
+        """What eval_once does with the episode once it is played: the kept best episode, the scalars, the return value."""
         total_reward, episode_length = float(np.sum(rewards)), len(rewards)
         if total_reward > self.best_score:
             self.best_score = total_reward
@@ -280,18 +284,54 @@ class FieldSwarmPolicyMonitor(SwarmPolicyMonitor):
     size (the registration's own handle observes on the conv policy's 84-cell grid).  Per step the policy reads the handle's current
     observation (grl_fieldnet_predict_swarm) and acts greedily: the action is the norm-clipped mu, handed to the env as float64
     rows, so swarm-eval.json replays in make_swarm_gif's default arithmetic.  Scalars, the kept best episode and the --baseline /
-    --rule-baseline yardsticks are SwarmPolicyMonitor's.  The reference never built a monitor for this net."""
+    --rule-baseline yardsticks are SwarmPolicyMonitor's.  The reference never built a monitor for this net.
+
+    device_episode (the default): the whole episode is one kernel launch (FieldNet.eval, include/goldsrl_fieldeval.h) -- the same
+    greedy float64-row episode bit for bit, without the ~400 blocking round trips of the host loop.  device_episode=False, or a
+    geometry whose env does not fit the kernel's LDS, plays the host loop.  n_envs > 1 (device episodes only) evaluates on n_envs
+    seeded episodes: env 0 is the registration's, env k the one of seed + k; eval_once still returns env 0's episode and keeps
+    every env's in total_rewards / episode_lengths, with eval/mean_total_reward among the scalars."""
 
     def __init__(self, env="Swarm-eval-v0", global_policy_net=None, state_processor=None, summary_writer=None, saver=None, network_conf=None,
-                 learner=None):
+                 learner=None, n_envs=1, device_episode=True):
         from ...envs import registry
         conf = network_conf if network_conf is not None else global_policy_net.conf
         cls, max_steps, kwargs = registry[env]
-        super(FieldSwarmPolicyMonitor, self).__init__(cls(max_episode_steps=max_steps, grid_size=conf['height'], **kwargs), global_policy_net,
-                                                      state_processor, summary_writer, saver, conf, learner)
+        if n_envs < 1:
+            raise ValueError("n_envs must be at least 1")
+        if n_envs > 1 and not device_episode:
+            raise ValueError("the host loop plays one env; n_envs = %d needs device_episode" % n_envs)
+        self.n_envs, self.device_episode, self.max_episode_steps = int(n_envs), bool(device_episode), int(max_steps or 0)
+        self.total_rewards, self.episode_lengths = None, None       # every env's, of the last device evaluation
+        more = {"n_envs": self.n_envs} if self.n_envs > 1 else {}
+        super(FieldSwarmPolicyMonitor, self).__init__(cls(max_episode_steps=max_steps, grid_size=conf['height'], **dict(kwargs, **more)),
+                                                      global_policy_net, state_processor, summary_writer, saver, conf, learner)
 
     def _bind(self):
-        self.policy_net.bind(self.env._eng, max_samples=1, gamma=0.99)      # gamma: the bind checks the geometry against the handle
+        self.policy_net.bind(self.env._eng, max_samples=self.n_envs, gamma=0.99)      # gamma: the bind checks the geometry against the handle
+
+    def eval_once(self, sess=None, max_sequence_length=5, actions=None):
+        from ... import _ffi
+        if not self.device_episode or actions or self.max_episode_steps < 1:      # a replayed queue and an env without TimeLimit are the host loop's
+            return super(FieldSwarmPolicyMonitor, self).eval_once(sess, max_sequence_length, actions)
+        global_step = self.copy_params()
+        self.env.reset()
+        try:
+            r = self.policy_net.net.eval(self.max_episode_steps, greedy=True, rows32=False, keep_actions=True)
+        except _ffi.GrlError as e:
+            if e.code != _ffi.E_STATE or self.n_envs > 1:
+                raise
+            self.device_episode = False      # the geometry is past the kernel's LDS budget
+            return super(FieldSwarmPolicyMonitor, self).eval_once(sess, max_sequence_length, actions)
+        lengths = [int(n) for n in r["length"]]
+        episodes = [[float(v) for v in r["rewards"][e, :lengths[e]]] for e in range(self.n_envs)]
+        self.total_rewards = np.array([float(np.sum(rew)) for rew in episodes])
+        self.episode_lengths = np.array(lengths)
+        out = self._episode_played(global_step, episodes[0], [r["actions"][0, t] for t in range(lengths[0])])
+        if self.n_envs > 1 and self.summary_writer is not None:
+            self.summary_writer.add_scalar("eval/mean_total_reward", float(self.total_rewards.mean()), global_step)
+            self.summary_writer.flush()
+        return out
 
     def get_action_from_policy(self, processed_state, history, positions, sess=None):
         mu = self.policy_net.net.predict_swarm()['mu']

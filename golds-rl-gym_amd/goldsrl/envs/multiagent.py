@@ -28,14 +28,19 @@ class SwarmEnv(object):
     dt = 0.05
     N_BURN_IN = 10
 
-    def __init__(self, seed=None, max_episode_steps=None, device_id=0, generator_seed=None, grid_size=None):
+    def __init__(self, seed=None, max_episode_steps=None, device_id=0, generator_seed=None, grid_size=None, n_envs=1):
+        """n_envs > 1 (a device monitor's eval set): env 0 is the env described above, env k of a seeded env is the episode of seed
+        n + k; reset() and `states` speak of env 0, step() needs the one-env handle."""
+        if n_envs < 1:
+            raise ValueError("n_envs must be at least 1")
         self.n_seed = seed
+        self.n_envs = int(n_envs)
         self.states = None
         self.t = 0
         flags = _ffi.F_RESEED_EACH_RESET if seed else 0    # `if self.n_seed: np.random.seed(...)` on every reset
         gseed = generator_seed if generator_seed is not None else (seed if seed else 1692)
         kw = {} if grid_size is None else {"grid_size": int(grid_size)}      # the observation's grid (the field policy's height)
-        self._eng = _ffi.Engine(_ffi.ENV_SWARM, 1, device_id=device_id, seed=int(gseed), flags=flags,
+        self._eng = _ffi.Engine(_ffi.ENV_SWARM, self.n_envs, device_id=device_id, seed=int(gseed), flags=flags,
                                 max_episode_steps=int(max_episode_steps or 0), **kw)
         self.np_random = None       # the reference's generator stream of a seeded env, continued after the reset draws
 
@@ -51,15 +56,17 @@ class SwarmEnv(object):
 
     def _reset(self):
         if self.n_seed:
-            rs = np.random.RandomState(self.n_seed)                       # np.random.seed(self.n_seed) (multiagent.py:47-48)
-            x = rs.rand(self.N_LOCUSTS, 2)                                # draw order of multiagent.py:51-56
-            xa = rs.rand(self.N_AGENTS, 2)
-            random_actions = rs.normal(size=(self.N_BURN_IN, self.N_AGENTS, 2))
-            agent_noise = rs.normal(size=(128 + self.N_BURN_IN, self.N_AGENTS, 2))
-            particle_noise = rs.normal(size=(128 + self.N_BURN_IN, self.N_LOCUSTS, 2))
-            # rows 0..9 drive the burn-in, row 10 every later step (self.t stays 10: quirk Q1); rows 11.. are never read
-            self._eng.swarm_reset_injected(x[None], xa[None], random_actions[None], agent_noise[None, :self.N_BURN_IN + 1],
-                                           particle_noise[None, :self.N_BURN_IN + 1])
+            draws = []
+            for k in reversed(range(self.n_envs)):                            # env 0 last: its generator is the one np_random continues
+                rs = np.random.RandomState(self.n_seed + k)                   # np.random.seed(self.n_seed) (multiagent.py:47-48)
+                x = rs.rand(self.N_LOCUSTS, 2)                                # draw order of multiagent.py:51-56
+                xa = rs.rand(self.N_AGENTS, 2)
+                random_actions = rs.normal(size=(self.N_BURN_IN, self.N_AGENTS, 2))
+                agent_noise = rs.normal(size=(128 + self.N_BURN_IN, self.N_AGENTS, 2))
+                particle_noise = rs.normal(size=(128 + self.N_BURN_IN, self.N_LOCUSTS, 2))
+                # rows 0..9 drive the burn-in, row 10 every later step (self.t stays 10: quirk Q1); rows 11.. are never read
+                draws.insert(0, (x, xa, random_actions, agent_noise[:self.N_BURN_IN + 1], particle_noise[:self.N_BURN_IN + 1]))
+            self._eng.swarm_reset_injected(*[np.stack(col) for col in zip(*draws)])
             self.np_random = rs
         else:
             self._eng.reset()
@@ -69,6 +76,8 @@ class SwarmEnv(object):
 
     def _step(self, v_action, add_wind=True):
         v_action = np.asarray(v_action)
+        if self.n_envs != 1:
+            raise ValueError("step() drives a one-env SwarmEnv; this one has %d envs (FieldNet.eval plays them)" % self.n_envs)
         if not add_wind:                        # multiagent.py:35-36 skipped: the agents move by the action alone
             self._eng.swarm_step_opts(v_action.reshape(1, self.N_AGENTS, 2), add_wind=False)
         elif v_action.dtype == np.float32:      # what the worker reads from the float32 shared array (quirk Q7)

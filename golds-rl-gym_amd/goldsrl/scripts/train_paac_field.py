@@ -36,6 +36,9 @@ def get_arg_parser():
     p.description = "PAAC on Swarm-v0 with the field policy (device engine)"
     p.set_defaults(height=20, filters=5)
     p.add_argument('--conv_layers', dest='conv_layers', type=int, default=2)
+    p.add_argument('--eval-envs', default=1, type=int, dest="eval_envs",
+                   help="seeded episodes of Swarm-eval-v0 per evaluation (--eval-every), all in one kernel launch; env 0 is the registration's "
+                        "episode, the one the scalars and swarm-eval.json speak of; above 1 eval/mean_total_reward is written too")
     return p
 
 

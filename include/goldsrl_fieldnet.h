@@ -67,5 +67,6 @@ int grl_fieldnet_train(grl_fieldnet *net, int32_t n, const float *states, const 
 #endif
 
 #include "goldsrl_fieldrollout.h"
+#include "goldsrl_fieldeval.h"
 
 #endif /* GOLDSRL_FIELDNET_H */
