@@ -131,6 +131,19 @@ struct NetLane {
     bool train_ready;
 };
 
+// grl_net_eval (net_conv_eval.inc): the evaluation's own buffers, sized on first use and grown on demand, and what the last call kept
+struct NetEval {
+    double *rewards, *normals;                    // (cap_steps) (cap_norm,10,2)
+    int32_t *length;                              // (cap_envs)
+    uint8_t *finished, *alive;                    // (cap_envs) x 2
+    float *envact, *actions;                      // (cap_envs,10,2): the step's env action rows; (cap_act,10,2)
+    float *tr_mu, *tr_sigma, *tr_raw, *tr_value;  // (cap_trace,10,2) x 3, (cap_trace,10)
+    size_t cap_steps, cap_norm, cap_envs, cap_act, cap_trace;
+    int max_steps, trace_env, keep_actions;       // of the last evaluation; max_steps == 0: none (or an invalid one)
+    bool unchecked;                               // its forward passes' range flag has not been read yet
+    int flag_before;                              // the device's range flag as the evaluation found it (a rollout's, not yet trained on)
+};
+
 struct grl_net : NetLane, grl::PaacCommNet {      // stats: [8..9] loss scale S and 1/S, [10] bits of the head-gradient bound, [12] the range latch
     grl_net_config cfg;
     int chunk;                 // samples per pass
@@ -202,6 +215,7 @@ struct grl_net : NetLane, grl::PaacCommNet {      // stats: [8..9] loss scale S 
     size_t keep_free_cap, keep_headroom, keep_free_seen;
     int resident_last;         // the last train_rollout* pass read the rollout's resident activations
     float last_inv_total;      // 1 / samples of the last gradient pass (grl_net_apply_grads)
+    NetEval ev;
     // lanes
     NetLane lanes[GRL_MAX_LANES];
     hipStream_t lane_stream[GRL_MAX_LANES];      // [0] = the handle's stream
@@ -1499,3 +1513,4 @@ int grl_net_profile_read_tags(grl_net *n, int32_t ntags, int32_t *launches, floa
 }  // extern "C"
 
 #include "net_train.inc"
+#include "net_conv_eval.inc"

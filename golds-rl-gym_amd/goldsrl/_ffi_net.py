@@ -55,6 +55,15 @@ NET_SIGNATURES = {
     "grl_net_profile_read_tags": (C.c_int, [_P, _I, _P, _P, _P]),
 }
 
+# include/goldsrl_neteval.h
+NET_EVAL_SIGNATURES = {
+    "grl_net_eval": (C.c_int, [_P, _I, _I, _P, _I, _I]),
+    "grl_net_read_eval": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
+}
+
+# grl_net_read_eval: the traced env's outputs, name -> shape behind (max_steps,); all float32
+_EVAL_TRACE = {"trace_mu": (10, 2), "trace_sigma": (10, 2), "trace_raw": (10, 2), "trace_value": (10,)}
+
 NET_CONV_SINGLE_AGENT = 0
 
 # (name, shape) in flat-vector order == tf.trainable_variables() creation order
@@ -84,7 +93,7 @@ class ConvNet(_ffi_paac.PaacTrainerNet):
     PREFIX = "grl_net_"
 
     def __init__(self, engine, **kw):
-        self._create(engine, NET_SIGNATURES, GrlNetConfig(), kw, NET_CONV_SINGLE_AGENT)
+        self._create(engine, dict(NET_SIGNATURES, **NET_EVAL_SIGNATURES), GrlNetConfig(), kw, NET_CONV_SINGLE_AGENT)
 
     def predict(self):
         B, A = self.eng.E * 10, int(self.cfg.num_actions)
@@ -128,6 +137,44 @@ class ConvNet(_ffi_paac.PaacTrainerNet):
         a = np.empty(shape, dtype)
         self._check(self.lib.grl_net_read_rollout(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
         return a
+
+    # -- whole evaluation episodes on the engine, nothing read back per step (include/goldsrl_neteval.h)
+    def read_eval(self, which, max_steps):
+        """An output of the last eval of max_steps steps by name.  The first read after an eval raises E_RANGE when a forward pass of
+        it left the fp16 range: the net is on the fp32 form then (unless the fallback is off); reset the env and eval again."""
+        E, S = self.eng.E, int(max_steps)
+        if which in _EVAL_TRACE:
+            a = np.empty((S,) + _EVAL_TRACE[which], np.float32)
+        else:
+            shape, dtype = {"rewards": ((E, S), np.float64), "length": ((E,), np.int32), "finished": ((E,), np.uint8),
+                            "actions": ((E, S, 10, 2), np.float32)}.get(which, ((0,), np.uint8))      # an unknown name is the library's to refuse
+            a = np.empty(shape, dtype)
+        self._check(self.lib.grl_net_read_eval(self.n, which.encode(), _ffi._ptr(a), a.nbytes))
+        return a
+
+    def eval(self, max_steps, greedy=False, normals=None, keep_actions=False, trace_env=-1):
+        """Every env of the engine plays one episode from its CURRENT state (reset first), at most max_steps steps, enqueued as
+        one pipeline (per step and chunk: forward, action, env step, accounting) and read back once.  The engine's env state
+        advances as a host loop's would; the net's parameters, optimizer state, action counter and last rollout stay as they were.
+        greedy: the action is the norm-clipped mu; else mu + sigma z with z = normals[env, t] -- (E, max_steps, 10, 2) float64, e.g.
+        a seeded generator's draws -- or, without normals, the rollout's keyed noise at the net's action counter (which stays).
+        The env steps with the float32 row.  Returns rewards (E,S) float64, length (E), finished (E), total_reward (E) -- the
+        float64 sum in step order -- plus actions (E,S,10,2) float32 with keep_actions and the trace_* outputs of env trace_env."""
+        S = int(max_steps)
+        z = None
+        if normals is not None:
+            z = np.ascontiguousarray(normals, np.float64)
+            if z.shape != (self.eng.E, S, 10, 2):
+                raise ValueError("eval: normals must be %s, got %s" % ((self.eng.E, S, 10, 2), z.shape))
+        self._check(self.lib.grl_net_eval(self.n, S, 1 if greedy else 0, None if z is None else _ffi._ptr(z), 1 if keep_actions else 0, int(trace_env)))
+        self.eng.wait()      # the join, as behind rollout(); the reads below find the streams drained
+        names = ["rewards", "length", "finished"] + (["actions"] if keep_actions else []) + (sorted(_EVAL_TRACE) if trace_env >= 0 else [])
+        out = {k: self.read_eval(k, S) for k in names}
+        total = np.zeros(self.eng.E, np.float64)
+        for t in range(S):      # step order; rewards past an env's length are zero
+            total = total + out["rewards"][:, t]
+        out["total_reward"] = total
+        return out
 
     def read_activation(self, which, shape):
         a = np.empty(shape, np.float32)

@@ -196,13 +196,17 @@ class GridPAACLearner(PAACLearner):
         if eval_every > 0 and ranks.rank == 0:      # only rank 0 evaluates: the other ranks build neither the monitor nor its env
             from ...envs import make
             from ..state_processors import SwarmStateProcessor
-            from .policy_monitor import FieldSwarmPolicyMonitor, ScalarWriter, SwarmPolicyMonitor
-            pe = (FieldSwarmPolicyMonitor if field else SwarmPolicyMonitor)(
-                                    env="Swarm-eval-v0" if field else make("Swarm-eval-v0"), global_policy_net=self.network,
+            from .policy_monitor import DeviceSwarmPolicyMonitor, FieldSwarmPolicyMonitor, ScalarWriter, SwarmPolicyMonitor
+            eval_envs = int(getattr(self, "eval_envs", 0) or 0)
+            # the conv policy: eval_envs = 0 is the host-loop monitor, N >= 1 plays N seeded episodes on the device (env 0: the same episode)
+            device = not field and eval_envs >= 1
+            pe = (FieldSwarmPolicyMonitor if field else DeviceSwarmPolicyMonitor if device else SwarmPolicyMonitor)(
+                                    env="Swarm-eval-v0" if field or device else make("Swarm-eval-v0"), global_policy_net=self.network,
                                     state_processor=SwarmStateProcessor(grid_size=self.network.height),
                                     summary_writer=self._open_summaries() or ScalarWriter(self.debugging_folder), saver=None,
                                     network_conf=self.network.conf,
-                                    learner=self, **({"n_envs": max(1, int(getattr(self, "eval_envs", 1) or 1))} if field else {}))
+                                    learner=self, **({"n_envs": max(1, eval_envs)} if field or device else {}))
+            self.policy_monitor = pe      # cleanup() closes the engines and nets a device monitor built
             if bool(getattr(self, "baseline", False)):
                 logging.info("Scripted baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.baseline())
             if bool(getattr(self, "rule_baseline", False)):      # after --baseline: with both, the rule baseline is the one written
@@ -219,5 +223,9 @@ class GridPAACLearner(PAACLearner):
         return self._loop(net, ranks, lambda: net.rollout(self.max_local_steps, layout), max_updates, between_updates)
 
     def cleanup(self):
+        mon = getattr(self, "policy_monitor", None)
+        if mon is not None and hasattr(mon, "close"):      # DeviceSwarmPolicyMonitor: two engines, two nets
+            mon.close()
+        self.policy_monitor = None
         if self.network.net is not None:
             self.network.net.close()

@@ -279,6 +279,98 @@ class SwarmPolicyMonitor(PolicyMonitor):
         return self.baseline_name, self.baseline_total_reward
 
 
+class DeviceSwarmPolicyMonitor(SwarmPolicyMonitor):
+    """SwarmPolicyMonitor with the episodes played on the device (ConvNet.eval, include/goldsrl_neteval.h): `n_envs` seeded episodes of
+    the eval registration -- env 0 is the registration's episode (seed 192), env k the one of seed 192 + k -- enqueued as pipelines
+    and read back once, instead of a blocking predict, a draw, a transform, a step and four reads per step.
+
+    The noise is the host loop's: after the reset, env k's generator (SwarmEnv.np_randoms) draws the episode's normals as one
+    (S, 10, 2) block, the same stream as S draws of (10, 2), and the device forms a = mu + sigma * z from them.  So env 0's episode
+    is, bit for bit, the one SwarmPolicyMonitor.eval_once plays; it is what eval_once returns and what the kept best episode in
+    swarm-eval.json, the scalars and the baseline scalars speak of.  Every env's total and length are kept in total_rewards /
+    episode_lengths, and with n_envs > 1 eval/mean_total_reward is written too.  greedy=True acts with the norm-clipped mu.
+
+    Two handles.  The shared evaluation of the trunk (csrc/net_shared.inc) associates an env's sums by the union of its chunk's masks,
+    so an env's bits depend on its chunk mates: env 0 inside a three-env chunk differs from the one-env episode in the ninth digit
+    of its total.  One env per chunk would keep every env's bits but costs a chunk's launches per env and step (measured 349 ms
+    at 16 envs against 46 in one chunk, profiles/conv_eval_times.json).  So env 0 plays alone on `env`, the registration's own
+    one-env handle -- exactly the parent's episode, and what baseline() / rule_baseline() (inherited) play and leave reset -- and
+    envs 1.. play in one chunk on `rest_env` (seed 193, n_envs - 1 envs) under a second copy of the policy; the two evaluations are
+    run one behind the other."""
+
+    def __init__(self, env="Swarm-eval-v0", global_policy_net=None, state_processor=None, summary_writer=None, saver=None, network_conf=None,
+                 learner=None, n_envs=1, greedy=False):
+        from ...envs import registry
+        cls, max_steps, kwargs = registry[env]
+        if n_envs < 1:
+            raise ValueError("n_envs must be at least 1")
+        if not max_steps or not kwargs.get("seed"):
+            raise ValueError("no device evaluation for env %r: it plays the seeded episodes of a registration with a TimeLimit" % (env,))
+        self.n_envs, self.greedy, self.max_episode_steps = int(n_envs), bool(greedy), int(max_steps)
+        self.total_rewards, self.episode_lengths = None, None       # every env's, of the last evaluation
+        conf = network_conf if network_conf is not None else global_policy_net.conf
+        super(DeviceSwarmPolicyMonitor, self).__init__(cls(max_episode_steps=max_steps, **kwargs), global_policy_net, state_processor,
+                                                       summary_writer, saver, conf, learner)
+        self.rest_env, self.rest_net = None, None
+        if self.n_envs > 1:
+            self.rest_env = cls(max_episode_steps=max_steps, **dict(kwargs, seed=kwargs["seed"] + 1, n_envs=self.n_envs - 1))
+            self.rest_net = self._create_policy_estimator(conf).bind(self.rest_env._eng)      # one chunk up to 8 192 envs
+
+    def copy_params(self):
+        flat = self.global_policy_net.get_flat_params()
+        for net in (self.policy_net, self.rest_net):
+            if net is not None:
+                net.set_flat_params(flat)
+        return int(self.learner.global_step) if self.learner is not None else 0
+
+    def _episodes(self):
+        """Reset, draw, play: the outputs of ConvNet.eval for env 0 and for envs 1.., one evaluation behind the other (the range flag
+        of the GEMMs is one word per device: it speaks of one net's work at a time).  The two policy copies are two nets, each with
+        its own arithmetic form: one whose forward pass left the fp16 range has moved to the fp32 form when its read raises E_RANGE,
+        and plays its own episodes once more from a reset; the other net is not touched by that."""
+        from ... import _ffi
+        S, out = self.max_episode_steps, []
+
+        def play(e, n):
+            e.reset()
+            normals = None if self.greedy else np.stack([rs.normal(size=(S, 10, 2)) for rs in e.np_randoms])
+            return n.net.eval(S, greedy=self.greedy, normals=normals, keep_actions=e is self.env)
+
+        for e, n in ((self.env, self.policy_net), (self.rest_env, self.rest_net)):
+            if e is None:
+                continue
+            try:
+                out.append(play(e, n))
+            except _ffi.GrlError as err:
+                if err.code != _ffi.E_RANGE:
+                    raise
+                out.append(play(e, n))
+        return out
+
+    def eval_once(self, sess=None, max_sequence_length=5, actions=None):
+        if actions:      # a replayed queue is the host loop's, on env 0
+            return super(DeviceSwarmPolicyMonitor, self).eval_once(sess, max_sequence_length, actions)
+        global_step = self.copy_params()
+        out = self._episodes()
+        lengths = [int(n) for r in out for n in r["length"]]
+        rows = [row for r in out for row in r["rewards"]]
+        episodes = [[float(v) for v in rows[e][:lengths[e]]] for e in range(self.n_envs)]
+        self.total_rewards = np.array([float(np.sum(rew)) for rew in episodes])
+        self.episode_lengths = np.array(lengths)
+        played = self._episode_played(global_step, episodes[0], [out[0]["actions"][0, t] for t in range(lengths[0])])
+        if self.n_envs > 1 and self.summary_writer is not None:
+            self.summary_writer.add_scalar("eval/mean_total_reward", float(self.total_rewards.mean()), global_step)
+            self.summary_writer.flush()
+        return played
+
+    def close(self):
+        """Closes the nets and engines the monitor built."""
+        for net, env in ((self.policy_net, self.env), (self.rest_net, self.rest_env)):
+            if net is not None:
+                net.net.close()
+                env._eng.close()
+
+
 class FieldSwarmPolicyMonitor(SwarmPolicyMonitor):
     """SwarmPolicyMonitor for ConvPolicyVFieldNetwork: one episode of the registered eval env on a one-env handle of the NET's grid
     size (the registration's own handle observes on the conv policy's 84-cell grid).  Per step the policy reads the handle's current

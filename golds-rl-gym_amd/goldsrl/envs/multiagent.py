@@ -56,7 +56,7 @@ class SwarmEnv(object):
 
     def _reset(self):
         if self.n_seed:
-            draws = []
+            draws, self.np_randoms = [], []                                   # np_randoms[k]: env k's generator behind its reset draws
             for k in reversed(range(self.n_envs)):                            # env 0 last: its generator is the one np_random continues
                 rs = np.random.RandomState(self.n_seed + k)                   # np.random.seed(self.n_seed) (multiagent.py:47-48)
                 x = rs.rand(self.N_LOCUSTS, 2)                                # draw order of multiagent.py:51-56
@@ -66,6 +66,7 @@ class SwarmEnv(object):
                 particle_noise = rs.normal(size=(128 + self.N_BURN_IN, self.N_LOCUSTS, 2))
                 # rows 0..9 drive the burn-in, row 10 every later step (self.t stays 10: quirk Q1); rows 11.. are never read
                 draws.insert(0, (x, xa, random_actions, agent_noise[:self.N_BURN_IN + 1], particle_noise[:self.N_BURN_IN + 1]))
+                self.np_randoms.insert(0, rs)
             self._eng.swarm_reset_injected(*[np.stack(col) for col in zip(*draws)])
             self.np_random = rs
         else:

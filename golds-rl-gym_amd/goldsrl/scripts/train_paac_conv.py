@@ -75,7 +75,9 @@ _BASELINE_HELP = ("play the scripted do-nothing baseline (drift / hold) on the e
                   "write eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs --eval-every > 0)")
 
 
-def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True):
+def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True, eval_envs=True):
+    """eval_envs: this script's --eval-envs; the scripts that build their parser from this one and have an --eval-envs of their own
+    (train_paac_field, train_paac_solow) switch it off."""
     p = argparse.ArgumentParser(description="PAAC on Swarm-v0 with the conv policy (device engine)")
     for flags, dest, kind, default in _REFERENCE_FLAGS:
         p.add_argument(*flags, dest=dest, type=kind, default=default)
@@ -83,6 +85,12 @@ def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True):
                    help="'reference' reproduces paac.py:331-338's (T, E*10) indexing (quirk Q4)")
     p.add_argument('--eval-every', default=30.0, type=float, dest="eval_every",
                    help="seconds between eval episodes on Swarm-eval-v0 (paac.py:277-282); 0 disables the monitor")
+    if eval_envs:
+        p.add_argument('--eval-envs', default=0, type=int, dest="eval_envs",
+                       help="0: one eval episode driven from the host, step by step (the reference's monitor).  N >= 1: N seeded episodes of "
+                            "Swarm-eval-v0 per evaluation played on the device and read back once; env 0 is the registration's episode (the "
+                            "same episode, bit for bit), the one the scalars and swarm-eval.json speak of; above 1 eval/mean_total_reward is "
+                            "written too (needs --eval-every > 0)")
     p.add_argument('--baseline', action='store_true', help=baseline_help)
     if rule_baseline:      # Swarm only: train_paac_solow builds its parser from this one without it
         p.add_argument('--rule-baseline', action='store_true', dest="rule_baseline",
@@ -103,6 +111,8 @@ def main(args):
         raise SystemExit("--baseline plays the eval env of the monitor: it needs --eval-every > 0")
     if getattr(args, "rule_baseline", False) and not args.eval_every > 0:
         raise SystemExit("--rule-baseline plays the eval env of the monitor: it needs --eval-every > 0")
+    if getattr(args, "eval_envs", 0) > 0 and not args.eval_every > 0:
+        raise SystemExit("--eval-envs sizes the eval set of the monitor: it needs --eval-every > 0")
     network_creator, env_creator = get_network_and_environment_creator(args)
     learner = GridPAACLearner(network_creator, env_creator, args, SwarmRunner,
                               state_processor=None if args.emulator_counts > 4096 else SwarmStateProcessor(grid_size=args.height))

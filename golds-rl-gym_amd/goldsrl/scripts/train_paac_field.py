@@ -32,7 +32,7 @@ def get_network_and_environment_creator(args, random_seed=3):
 
 
 def get_arg_parser():
-    p = train_paac_conv.get_arg_parser()
+    p = train_paac_conv.get_arg_parser(eval_envs=False)
     p.description = "PAAC on Swarm-v0 with the field policy (device engine)"
     p.set_defaults(height=20, filters=5)
     p.add_argument('--conv_layers', dest='conv_layers', type=int, default=2)

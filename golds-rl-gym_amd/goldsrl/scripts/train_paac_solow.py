@@ -36,7 +36,7 @@ def get_network_and_environment_creator(args, random_seed=3):
 def get_arg_parser():
     p = _conv_parser(baseline_help="play the constant-savings baseline on the eval envs before the first update (one kernel launch) and write "
                                    "eval/baseline_total_reward and eval/mean_total_reward_minus_baseline at every evaluation (needs --eval-envs)",
-                     rule_baseline=False)
+                     rule_baseline=False, eval_envs=False)
     p.set_defaults(scale=100.)              # train_paac_solow.py:122 (the conv script uses 1000)
     p.add_argument('--eval-envs', default=0, type=int, dest="eval_envs",
                    help="envs of Solow-1-1-finite-eval-v0 evaluated on the device between updates (paac.py:63-77), one launch per "

@@ -206,4 +206,7 @@ int grl_net_profile_read_tags(grl_net *net, int32_t ntags, int32_t *launches, fl
 #ifdef __cplusplus
 }
 #endif
+
+#include "goldsrl_neteval.h" /* whole evaluation episodes on the handle, no host round trip per step */
+
 #endif /* GOLDSRL_NET_H */
