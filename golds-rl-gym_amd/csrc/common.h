@@ -159,6 +159,20 @@ struct SwarmRulesState {
     int n_rules, max_steps, trace_env, keep_actions;   // of the last run; n_rules == 0: none yet
 };
 
+// grl_swarm_plan (swarm_plan.hip)
+struct SwarmPlanState {
+    double *rules, *offsets;                      // (cap_rules,3) (cap_rules,10,2)
+    double *x, *xa;                               // (cap_envs,80,2) (cap_envs,10,2): the plan's working copy of the positions
+    int32_t *length;                              // (cap_envs): steps played; the plan's clock
+    uint8_t *finished;                            // (cap_envs)
+    double *rewards, *actions;                    // (cap_steps) (cap_act,10,2)
+    double *trace_x, *trace_xa;                   // (cap_trace,80,2) (cap_trace,10,2)
+    int32_t *choices;                             // (cap_dec): (E, decisions)
+    double *scores;                               // (cap_scores): (E, decisions, n_rules)
+    size_t cap_rules, cap_envs, cap_steps, cap_act, cap_trace, cap_dec, cap_scores;
+    int n_rules, max_steps, decisions, trace_env, keep_actions;   // of the last run; n_rules == 0: none yet
+};
+
 }  // namespace grl
 
 struct grl_handle {
@@ -183,6 +197,7 @@ struct grl_handle {
     grl::SolowSweepState swp;
     grl::SwarmReplayState rpl;
     grl::SwarmRulesState srl;
+    grl::SwarmPlanState spl;
     grl::TradeSweepState tsw;
     grl::TradeForesightState tfs;
     grl::TickerSweepState ksw;

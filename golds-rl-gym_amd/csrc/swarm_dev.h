@@ -230,7 +230,7 @@ __device__ __forceinline__ uint16_t swarm_point_pos(int cx, int cy, int G) {
     return (uint16_t)(px | (py << 8));
 }
 
-// Host side of the whole-episode kernels (swarm_replay.hip, swarm_rules.hip).
+// Host side of the whole-episode kernels (swarm_replay.hip, swarm_rules.hip, swarm_plan.hip).
 // launch(M) with decltype(M)::value the handle's arithmetic, as launch_swarm (swarm.hip) picks it for the step
 template <typename F>
 static void swarm_math_dispatch(const grl_handle *h, F &&launch) {

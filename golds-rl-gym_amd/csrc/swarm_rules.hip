@@ -13,7 +13,7 @@
 // the HBM traffic of a step is one 8-byte reward per pair and, when asked for, the 160-byte action row per pair and 1 440 bytes of
 // positions per pair of the traced env.
 //
-// The rule's arithmetic is float64, one IEEE operation per statement (the file is compiled with -ffp-contract=off), `/` and sqrt
+// The rule's arithmetic (rule_action, swarm_rule_dev.h) is float64, one IEEE operation per statement (the file is compiled with -ffp-contract=off), `/` and sqrt
 // correctly rounded in every one of the handle's three math modes: MATH selects block_step only.  The centroid is a SEQUENTIAL sum in
 // index order -- the order is part of the contract (goldsrl/_ffi_swarmrules.py:swarm_rule_actions is the same statements in numpy).
 //
@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "swarm_dev.h"
+#include "swarm_rule_dev.h"
 #include "episode_host.h"
 #include "../../include/goldsrl_swarmrules.h"
 
@@ -40,59 +41,6 @@ struct RulesParams {
     double *trace_x, *trace_xa;   // (n_rules, max_steps, 80, 2) (n_rules, max_steps, 10, 2)
     int E, n_rules, max_steps, limit, trace_env;
 };
-
-// The action of agent a of one pair from the pair's points as they stand before the step: pts[0..79] the locusts, pts[80 + a] the
-// agent.  Each statement is one rounding.
-__device__ __forceinline__ void rule_action(const double2 *pts, int a, double cancel, double gain, int anchor, double offx, double offy,
-                                            double &ax, double &ay) {
-    const double2 me = pts[N_LOCUSTS + a];
-    double cx, cy;
-    if (anchor == 0) {             // the centroid: a sequential sum, index order
-        cx = 0.0;
-        cy = 0.0;
-#pragma unroll 8
-        for (int j = 0; j < N_LOCUSTS; ++j) {
-            const double2 q = pts[j];
-            cx = cx + q.x;
-            cy = cy + q.y;
-        }
-        cx = cx / 80.0;
-        cy = cy / 80.0;
-    } else {                       // the nearest locust: strict <, so the first index wins a tie
-        double best;
-        {
-            const double2 q = pts[0];
-            const double dx = q.x - me.x, dy = q.y - me.y;
-            const double sx = dx * dx, sy = dy * dy;
-            best = sx + sy;
-            cx = q.x;
-            cy = q.y;
-        }
-#pragma unroll 8
-        for (int j = 1; j < N_LOCUSTS; ++j) {
-            const double2 q = pts[j];
-            const double dx = q.x - me.x, dy = q.y - me.y;
-            const double sx = dx * dx, sy = dy * dy;
-            const double d2 = sx + sy;
-            if (d2 < best) {
-                best = d2;
-                cx = q.x;
-                cy = q.y;
-            }
-        }
-    }
-    const double tx = cx + offx, ty = cy + offy;
-    const double ex = tx - me.x, ey = ty - me.y;
-    const double gx = gain * ex;
-    ax = gx - cancel;
-    ay = gain * ey;
-    const double qx = ax * ax, qy = ay * ay;
-    const double d = sqrt(qx + qy);
-    if (d >= 1.0) {                // transform_actions_for_env: a row of norm >= 1 is divided by its norm
-        ax = ax / d;
-        ay = ay / d;
-    }
-}
 
 // One dependent chain per workgroup, as the replay: latency counts, waves per SIMD do not, so one wave per SIMD as the second launch
 // bound lets the pair loop keep everything in registers.
@@ -208,17 +156,9 @@ int grl_swarm_rules(grl_handle *h, const double *rules_host, const double *offse
     if ((rc = episode_open(h, fn, GRL_ENV_SWARM, "Swarm", rules_host && offsets_host)) || (rc = episode_check_count(h, fn, "n_rules", n_rules, 4096)) ||
         (rc = episode_check_steps(h, fn, max_steps)))
         return rc;
-    for (int i = 0; i < n_rules; ++i) {
-        const double *r = rules_host + (size_t)i * 3;
-        if (!std::isfinite(r[0]) || !std::isfinite(r[1]))
-            return fail(h, GRL_E_INVALID, "grl_swarm_rules: rule " + std::to_string(i) + ": cancel or gain is not finite");
-        if (!(r[2] == 0.0 || r[2] == 1.0))
-            return fail(h, GRL_E_INVALID, "grl_swarm_rules: rule " + std::to_string(i) + ": anchor must be 0 (centroid) or 1 (nearest locust)");
-        for (int k = 0; k < N_AGENTS * 2; ++k)
-            if (!std::isfinite(offsets_host[(size_t)i * N_AGENTS * 2 + k]))
-                return fail(h, GRL_E_INVALID, "grl_swarm_rules: rule " + std::to_string(i) + ": an offset is not finite");
-    }
-    if ((rc = episode_check_trace_env(h, fn, trace_env)) || (rc = episode_check_idle(h, fn))) return rc;
+    if ((rc = swarm_check_rule_table(h, fn, rules_host, offsets_host, n_rules)) || (rc = episode_check_trace_env(h, fn, trace_env)) ||
+        (rc = episode_check_idle(h, fn)))
+        return rc;
     const size_t pairs = (size_t)h->E * n_rules, steps = pairs * max_steps, act = keep_actions ? steps : 0;
     const size_t trace = trace_env >= 0 ? (size_t)n_rules * max_steps : 0;
     const size_t largest = std::max(std::max(steps, act * N_AGENTS * 2), trace * N_LOCUSTS * 2);

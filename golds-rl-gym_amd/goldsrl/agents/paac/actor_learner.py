@@ -21,7 +21,8 @@ class ActorLearner(object):
         self.eval_updates = getattr(args, 'eval_updates', 0)            # > 0: evaluate after every eval_updates-th update, 0: by eval_every
         self.baseline = getattr(args, 'baseline', False)                # the baseline beside the evaluation (--baseline): constant savings for Solow, scripted drift / hold for Swarm
         self.rule_baseline = getattr(args, 'rule_baseline', False)      # the feedback-rule baseline beside the evaluation (--rule-baseline, Swarm)
-        self.optimal = getattr(args, 'optimal', False)                  # the optimal-savings yardstick beside the evaluation (--optimal, Solow)
+        self.plan_baseline = getattr(args, 'plan_baseline', None)       # (horizon, replan) of the rule planner beside the evaluation (--plan-baseline, Swarm)
+        self.optimal = getattr(args, 'optimal', False)                 # the optimal-savings yardstick beside the evaluation (--optimal, Solow)
         self.checkpoint_every = getattr(args, 'checkpoint_every', 0)    # updates between flat-weights checkpoints (0: never)
         self.checkpoint_path = getattr(args, 'checkpoint_path', 'checkpoint.npz')
         self.resume = getattr(args, 'resume', None)

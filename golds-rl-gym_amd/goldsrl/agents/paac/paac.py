@@ -211,6 +211,9 @@ class GridPAACLearner(PAACLearner):
                 logging.info("Scripted baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.baseline())
             if bool(getattr(self, "rule_baseline", False)):      # after --baseline: with both, the rule baseline is the one written
                 logging.info("Feedback-rule baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.rule_baseline())
+            plan = getattr(self, "plan_baseline", None)         # last: with the others as well, the plan is the one written
+            if plan:
+                logging.info("Rule-planner baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.plan_baseline(*plan))
         state = {"last_eval": last_eval}
 
         def between_updates(counter):

@@ -278,6 +278,22 @@ class SwarmPolicyMonitor(PolicyMonitor):
         self.env.reset()
         return self.baseline_name, self.baseline_total_reward
 
+    def plan_baseline(self, horizon=8, replan=4, rules=DEFAULT_SWARM_RULES):
+        """The receding-horizon rule planner (goldsrl/baselines.py:SwarmRulePlanner) on the monitor's own eval env: the env is reset,
+        the planner plays the seeded episode in one call -- every rule `horizon` steps ahead, the best committed for `replan` steps,
+        again -- and the env is reset again.  Keeps baseline_name, baseline_total_reward (every later eval_once writes
+        eval/baseline_total_reward and eval/total_reward_minus_baseline) and the whole outputs, the committed actions among them, in
+        baseline_stats, replacing what baseline() or rule_baseline() kept.  Returns (baseline_name, baseline_total_reward).  The
+        reference has no counterpart."""
+        from ...baselines import SwarmRulePlanner
+        self.env.reset()
+        b = SwarmRulePlanner(self.env._eng, rules, horizon, replan)
+        self.baseline_stats = b.run(keep_actions=True)
+        self.baseline_name = "plan (horizon %d, replan %d, %d rules, %d switches)" % (b.horizon, b.replan, len(b.rules), b.switches())
+        self.baseline_total_reward = b.total()
+        self.env.reset()
+        return self.baseline_name, self.baseline_total_reward
+
 
 class DeviceSwarmPolicyMonitor(SwarmPolicyMonitor):
     """SwarmPolicyMonitor with the episodes played on the device (ConvNet.eval, include/goldsrl_neteval.h): `n_envs` seeded episodes of

@@ -27,7 +27,11 @@ the episode, every (env, horizon) pair in one call (include/goldsrl_tradeforesig
 
 SwarmRuleBaseline is Swarm's closed-loop yardstick: feedback rules that steer the agents relative to the swarm's centroid or to
 their nearest locust, every (env, rule) pair in one kernel launch with the action computed on the device
-(include/goldsrl_swarmrules.h).  Its first two rules are ScriptedSwarmBaseline's scripts.  No counterpart in the reference."""
+(include/goldsrl_swarmrules.h).  Its first two rules are ScriptedSwarmBaseline's scripts.  No counterpart in the reference.
+
+SwarmRulePlanner is the other end of Swarm's scale: a receding-horizon planner that looks every rule of the same table H steps
+ahead, commits the best for K steps and plans again, the whole planned episode in one call (include/goldsrl_swarmplan.h).  No
+counterpart either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -424,3 +428,36 @@ class SwarmRuleBaseline(_EngineBaseline):
     def best_total(self):
         """(rule_index, the six numbers, mean over the envs of the episode's total reward) of the best rule."""
         return select_best_swarm_rule(self.rules, self._stats()["totals"])
+
+
+class SwarmRulePlanner(_EngineBaseline):
+    """A controller that REACTS, from the same rule table: at every decision each env plays every rule `horizon` steps ahead from
+    where it stands, commits the rule with the best sum for `replan` steps and plans again, the whole planned episode enqueued in
+    one call (include/goldsrl_swarmplan.h).  Swarm's noise is one fixed row at amplitude 1e-4 after the burn-in (quirk Q1), so the
+    env is deterministic from a given state and the lookahead knows nothing a policy could not.  What it earns above the best fixed
+    rule is what switching among the rules is worth.  run() plays from the engine's CURRENT state (reset it first) and leaves that
+    state as it was.  No counterpart in the reference."""
+
+    def __init__(self, engine, rules=DEFAULT_SWARM_RULES, horizon=8, replan=4, max_episode_steps=None):
+        from ._ffi_swarmrules import check_swarm_rules
+        self._open(engine, "ENV_SWARM", "the Swarm rule planner exists for the Swarm env only")
+        self.rules = check_swarm_rules(rules)
+        self.horizon, self.replan = int(horizon), int(replan)
+        if not 1 <= self.replan <= self.horizon:
+            raise ValueError("1 <= replan <= horizon is required, got horizon %d, replan %d" % (self.horizon, self.replan))
+        self._steps(max_episode_steps)
+
+    def run(self, trace_env=None, keep_actions=False):
+        """Plan every env's episode; returns (and keeps) the outputs of _ffi_swarmplan.swarm_plan."""
+        from . import _ffi_swarmplan
+        self.stats = _ffi_swarmplan.swarm_plan(self.eng, self.rules, self.horizon, self.replan, self.max_episode_steps, keep_actions, trace_env)
+        return self.stats
+
+    def total(self):
+        """The mean over the envs of the planned episode's total reward."""
+        return float(self._stats()["totals"].mean())
+
+    def switches(self):
+        """The number of decisions, over all envs, whose choice differs from the env's choice before."""
+        c = self._stats()["choices"]
+        return int(((c[:, 1:] != c[:, :-1]) & (c[:, 1:] >= 0)).sum())

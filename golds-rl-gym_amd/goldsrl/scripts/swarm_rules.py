@@ -2,13 +2,25 @@
 on `Swarm-eval-v0`: every default rule plays the seeded eval episode in ONE kernel launch, and every rule's total reward is printed
 -- the yardstick for eval/total_reward of train_paac_conv.  --json keeps the best rule's episode as {'score', 'actions'}, the
 format of the swarm-eval.json SwarmPolicyMonitor writes; --gif hands that file to goldsrl.scripts.make_swarm_gif, which replays
-the recorded actions, prints `score reproduced` and draws the episode.  The reference has no counterpart."""
+the recorded actions, prints `score reproduced` and draws the episode.  --plan H[:K] also plays the receding-horizon planner over the
+same rules (goldsrl/baselines.py:SwarmRulePlanner) and keeps ITS episode instead.  The reference has no counterpart."""
 import argparse
 import json
 
 import numpy as np
 
-from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline
+from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline, SwarmRulePlanner
+
+
+def plan_arg(text):
+    """--plan (and the trainers' --plan-baseline): 'H' or 'H:K' as (horizon, replan) with 1 <= K <= H; K defaults to H."""
+    try:
+        parts = [int(v) for v in text.split(":")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2) or not 1 <= parts[-1] <= parts[0]:
+        raise argparse.ArgumentTypeError("expected H or H:K with 1 <= K <= H, got %r" % text)
+    return parts[0], parts[-1]
 
 
 def get_arg_parser():
@@ -16,6 +28,9 @@ def get_arg_parser():
     p.add_argument("--seed", type=int, default=192, help="the env's seed (192: Swarm-eval-v0's registration)")
     p.add_argument("--json", help="write the best rule's episode here as {'score', 'actions'}")
     p.add_argument("--gif", help="draw the best rule's episode with make_swarm_gif (seed 192 only; writes --json, default <gif>.json)")
+    p.add_argument("--plan", type=plan_arg, default=None, metavar="H[:K]",
+                   help="also play the receding-horizon planner over the same rules (every rule H steps ahead, the best committed for K "
+                        "steps, default K = H, again; one call) and print its total beside the rules'; --json / --gif then keep the planned episode")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -38,11 +53,21 @@ def main(argv=None):
     best, six, total = b.best_total()
     print("best: rule %d %s, total reward %.6f; hold %.6f, drift %.6f" % (best, six, total, float(st["totals"][0, 1]), float(st["totals"][0, 0])))
     n = int(st["length"][0, best])
-    score = float(np.sum(st["rewards"][0, best, :n]))                   # the monitor's total_reward
+    rewards, actions = st["rewards"][0, best, :n], st["actions"][0, best, :n]
+    if args.plan:
+        horizon, replan = args.plan
+        pl = SwarmRulePlanner(env._eng, DEFAULT_SWARM_RULES, horizon, replan)
+        ps = pl.run(keep_actions=True)
+        n = int(ps["length"][0])
+        rewards, actions = ps["rewards"][0, :n], ps["actions"][0, :n]
+        c = ps["choices"][0]
+        print("plan: horizon %d, replan %d: %d decisions, %d switches, rules chosen %s, length %d, total reward %.6f (%+.6f on the best rule)"
+              % (horizon, replan, int((c >= 0).sum()), pl.switches(), sorted(set(int(v) for v in c[c >= 0])), n, pl.total(), pl.total() - total))
+    score = float(np.sum(rewards))                                      # the monitor's total_reward
     path = args.json or (args.gif + ".json" if args.gif else None)
     if path:
         with open(path, "w") as f:
-            json.dump({"score": score, "actions": st["actions"][0, best, :n].tolist()}, f)
+            json.dump({"score": score, "actions": actions.tolist()}, f)
         print("wrote %s (%d actions, score %.17g)" % (path, n, score))
     if args.gif:
         from goldsrl.scripts import make_swarm_gif

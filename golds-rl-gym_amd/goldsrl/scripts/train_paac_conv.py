@@ -10,6 +10,7 @@ from goldsrl.agents.paac.emulator_runner import SwarmRunner
 from goldsrl.agents.paac.paac import GridPAACLearner
 from goldsrl.agents.paac.policy_v_network import ConvSingleAgentPolicyNetwork
 from goldsrl.agents.state_processors import SwarmStateProcessor
+from goldsrl.scripts.swarm_rules import plan_arg
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO)
 
@@ -75,6 +76,13 @@ _BASELINE_HELP = ("play the scripted do-nothing baseline (drift / hold) on the e
                   "write eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs --eval-every > 0)")
 
 
+def check_baseline_flags(args):
+    """The three yardstick flags play the monitor's eval env: refused without it."""
+    for flag, dest in (("--baseline", "baseline"), ("--rule-baseline", "rule_baseline"), ("--plan-baseline", "plan_baseline")):
+        if getattr(args, dest, None) and not args.eval_every > 0:
+            raise SystemExit("%s plays the eval env of the monitor: it needs --eval-every > 0" % flag)
+
+
 def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True, eval_envs=True):
     """eval_envs: this script's --eval-envs; the scripts that build their parser from this one and have an --eval-envs of their own
     (train_paac_field, train_paac_solow) switch it off."""
@@ -98,6 +106,12 @@ def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True, eval_envs=T
                             "relative to the swarm) on the eval env before the first update (one kernel launch), log the best rule and write "
                             "eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs --eval-every > 0); with "
                             "--baseline as well, the rule baseline is the one written")
+        p.add_argument('--plan-baseline', type=plan_arg, default=None, dest="plan_baseline", metavar="H[:K]",
+                       help="play the receding-horizon rule planner (goldsrl.baselines.SwarmRulePlanner: every default rule H steps ahead, the "
+                            "best committed for K steps, default K = H, again) on the eval env before the first update (one call), log its "
+                            "total and write eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs "
+                            "--eval-every > 0); with --rule-baseline or --baseline as well, the plan is the one written: it is the highest "
+                            "of the three")
     p.add_argument('--checkpoint-every', default=0, type=int, dest="checkpoint_every", help="updates between flat-weights checkpoints")
     p.add_argument('--checkpoint-path', default='checkpoint.npz', type=str, dest="checkpoint_path")
     p.add_argument('--resume', default=None, type=str, help="flat-weights checkpoint to start from")
@@ -107,10 +121,7 @@ def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True, eval_envs=T
 
 
 def main(args):
-    if args.baseline and not args.eval_every > 0:
-        raise SystemExit("--baseline plays the eval env of the monitor: it needs --eval-every > 0")
-    if getattr(args, "rule_baseline", False) and not args.eval_every > 0:
-        raise SystemExit("--rule-baseline plays the eval env of the monitor: it needs --eval-every > 0")
+    check_baseline_flags(args)
     if getattr(args, "eval_envs", 0) > 0 and not args.eval_every > 0:
         raise SystemExit("--eval-envs sizes the eval set of the monitor: it needs --eval-every > 0")
     network_creator, env_creator = get_network_and_environment_creator(args)

@@ -43,10 +43,7 @@ def get_arg_parser():
 
 
 def main(args):
-    if args.baseline and not args.eval_every > 0:
-        raise SystemExit("--baseline plays the eval env of the monitor: it needs --eval-every > 0")
-    if getattr(args, "rule_baseline", False) and not args.eval_every > 0:
-        raise SystemExit("--rule-baseline plays the eval env of the monitor: it needs --eval-every > 0")
+    train_paac_conv.check_baseline_flags(args)
     if args.height % (2 ** args.conv_layers):
         raise SystemExit("--height must be a multiple of 2^conv_layers")
     network_creator, env_creator = get_network_and_environment_creator(args)
