@@ -173,6 +173,20 @@ struct SwarmPlanState {
     int n_rules, max_steps, decisions, trace_env, keep_actions;   // of the last run; n_rules == 0: none yet
 };
 
+// grl_swarm_search (swarm_search.hip); cap_gc counts (generation, candidate) pairs, cap_gen generations + 1
+struct SwarmSearchState {
+    double *normals, *cand;                       // (cap_gc,5) (cap_gc,6): the host's normals; the six-number rows as played
+    double *rules, *offsets;                      // (cap_gc,3) (cap_gc,10,2): generation g's table is the lookahead's at g * C
+    double *fit;                                  // (cap_gc)
+    int32_t *order;                               // (cap_gc)
+    double *scores;                               // (cap_scores): (E, G, C)
+    double *mean, *std;                           // (cap_gen,5) each
+    int32_t *length;                              // (cap_envs): zero, the lookahead's clock
+    uint8_t *finished;                            // (cap_envs): zero
+    size_t cap_gc, cap_scores, cap_gen, cap_envs;
+    int G, C;                                     // of the last run; G == 0: none yet
+};
+
 }  // namespace grl
 
 struct grl_handle {
@@ -198,6 +212,7 @@ struct grl_handle {
     grl::SwarmReplayState rpl;
     grl::SwarmRulesState srl;
     grl::SwarmPlanState spl;
+    grl::SwarmSearchState ssr;
     grl::TradeSweepState tsw;
     grl::TradeForesightState tfs;
     grl::TickerSweepState ksw;

@@ -1,5 +1,6 @@
 // The feedback rule of the Swarm env (include/goldsrl_swarmrules.h), shared by the translation units that act by it (swarm_rules.hip:
-// whole episodes per rule; swarm_plan.hip: the receding-horizon planner over the same table): the device statements of one action
+// whole episodes per rule; swarm_plan.hip: the receding-horizon planner over the same table; swarm_search.hip: the search over a rule's
+// numbers): the device statements of one action
 // and the host's checks of a rule table.  One copy, so the two entry points cannot drift apart in a rounding or a refusal.
 // Every including file is compiled with -ffp-contract=off.
 #pragma once

@@ -214,6 +214,9 @@ class GridPAACLearner(PAACLearner):
             plan = getattr(self, "plan_baseline", None)         # last: with the others as well, the plan is the one written
             if plan:
                 logging.info("Rule-planner baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.plan_baseline(*plan))
+            search = getattr(self, "search_baseline", None)     # scalars of its own; the others' stay what they are
+            if search:
+                logging.info("Tuned-rule baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.search_baseline(*search))
         state = {"last_eval": last_eval}
 
         def between_updates(counter):

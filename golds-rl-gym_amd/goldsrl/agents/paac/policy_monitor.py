@@ -244,6 +244,10 @@ class SwarmPolicyMonitor(PolicyMonitor):
             self.summary_writer.add_scalar("eval/baseline_total_reward", self.baseline_total_reward, global_step)
             self.summary_writer.add_scalar("eval/total_reward_minus_baseline", total_reward - self.baseline_total_reward, global_step)
             self.summary_writer.flush()
+        if getattr(self, "search_baseline_total_reward", None) is not None and self.summary_writer is not None:
+            self.summary_writer.add_scalar("eval/search_baseline_total_reward", self.search_baseline_total_reward, global_step)
+            self.summary_writer.add_scalar("eval/total_reward_minus_search_baseline", total_reward - self.search_baseline_total_reward, global_step)
+            self.summary_writer.flush()
         return total_reward, episode_length, rewards
 
     def baseline(self):
@@ -293,6 +297,28 @@ class SwarmPolicyMonitor(PolicyMonitor):
         self.baseline_total_reward = b.total()
         self.env.reset()
         return self.baseline_name, self.baseline_total_reward
+
+    def search_baseline(self, generations=8, candidates=32, elites=8, rules=DEFAULT_SWARM_RULES):
+        """The tuned fixed rule (goldsrl/baselines.py:SwarmRuleSearch) on the monitor's own eval env: the env is reset, the search
+        starts from the best rule of `rules` on the seeded episode and runs in one call, and the env is reset again.  Keeps
+        search_baseline_name, search_baseline_rule (the six numbers), search_baseline_total_reward (every later eval_once writes
+        eval/search_baseline_total_reward and eval/total_reward_minus_search_baseline) and the search's outputs in search_stats.  What
+        baseline(), rule_baseline() or plan_baseline() kept stays, and with it every scalar they write; only when none of them has
+        run does the search also supply baseline_name and baseline_total_reward.  Returns (search_baseline_name,
+        search_baseline_total_reward).  The reference has no counterpart."""
+        from ...baselines import SwarmRuleSearch
+        self.env.reset()
+        b = SwarmRuleSearch(self.env._eng, None, generations, candidates, elites, rules=rules)
+        self.search_stats = b.run()
+        six, total = b.best()
+        mine = getattr(self, "baseline_total_reward", None) is None or getattr(self, "baseline_name", 0) == getattr(self, "search_baseline_name", 1)
+        self.search_baseline_rule, self.search_baseline_total_reward = six, total
+        self.search_baseline_name = "tuned rule (cancel %g, gain %g, anchor %s, offset (%g, %g), radius %g; %d generations of %d, %d elites)" % (
+            (six[0], six[1], "nearest locust" if six[2] else "centroid") + six[3:] + (b.generations, b.candidates, b.elites))
+        if mine:
+            self.baseline_name, self.baseline_total_reward = self.search_baseline_name, total
+        self.env.reset()
+        return self.search_baseline_name, self.search_baseline_total_reward
 
 
 class DeviceSwarmPolicyMonitor(SwarmPolicyMonitor):

@@ -31,7 +31,11 @@ their nearest locust, every (env, rule) pair in one kernel launch with the actio
 
 SwarmRulePlanner is the other end of Swarm's scale: a receding-horizon planner that looks every rule of the same table H steps
 ahead, commits the best for K steps and plans again, the whole planned episode in one call (include/goldsrl_swarmplan.h).  No
-counterpart either."""
+counterpart either.
+
+SwarmRuleSearch stands between the two: the best FIXED rule a cross-entropy search over the rule's five real numbers finds from
+the best rule of the table, every generation of every candidate on every env in one call (include/goldsrl_swarmsearch.h).  A
+yardstick that does not depend on what somebody typed into a table.  No counterpart either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -461,3 +465,46 @@ class SwarmRulePlanner(_EngineBaseline):
         """The number of decisions, over all envs, whose choice differs from the env's choice before."""
         c = self._stats()["choices"]
         return int(((c[:, 1:] != c[:, :-1]) & (c[:, 1:] >= 0)).sum())
+
+
+class SwarmRuleSearch(_EngineBaseline):
+    """The best fixed rule near a start: a cross-entropy search over (cancel, gain, off_x, off_y, radius) under the start's anchor,
+    `generations` generations of `candidates` candidates refitted over `elites` elites, every candidate's episode on every env of
+    the engine, all enqueued in one call (include/goldsrl_swarmsearch.h; the scheme is written there).  start=None plays
+    SwarmRuleBaseline over `rules` on the same envs first and starts from its best rule: plain refitting from nowhere stalls far
+    below the table's best (LABNOTES.md).  Candidate 0 of every generation is the best so far, so the found rule is never below the
+    start.  A policy whose eval/mean_total_reward is below it has learned less than five numbers.  run() plays from the engine's
+    CURRENT state (reset it first) and leaves that state as it was.  No counterpart in the reference."""
+
+    def __init__(self, engine, start=None, generations=8, candidates=32, elites=8, seed=0, spread=None, floor=None, lo=None, hi=None,
+                 normals=None, rules=DEFAULT_SWARM_RULES, max_episode_steps=None):
+        from . import _ffi_swarmsearch as S
+        self._open(engine, "ENV_SWARM", "the Swarm rule search exists for the Swarm env only")
+        self._steps(max_episode_steps)
+        self.start = None if start is None else S.check_swarm_rules(np.asarray(start, np.float64).reshape(1, -1))[0]
+        self.rules = S.check_swarm_rules(rules)
+        self.generations, self.candidates, self.elites, self.seed, self.normals = int(generations), int(candidates), int(elites), seed, normals
+        self.box = {"spread": S.DEFAULT_SPREAD if spread is None else spread, "floor": S.DEFAULT_FLOOR if floor is None else floor,
+                    "lo": S.DEFAULT_LO if lo is None else lo, "hi": S.DEFAULT_HI if hi is None else hi}
+        self.start_total = None                       # the table's best total, when the start came from the table
+
+    def run(self):
+        """Search; returns (and keeps) the outputs of _ffi_swarmsearch.swarm_search."""
+        from . import _ffi_swarmsearch as S
+        if self.start is None:
+            _, six, self.start_total = SwarmRuleBaseline(self.eng, self.rules, self.max_episode_steps).best_total()
+            self.start = np.array(six, np.float64)
+        self.stats = S.swarm_search(self.eng, self.start, generations=self.generations, candidates=self.candidates, elites=self.elites,
+                                    seed=self.seed, normals=self.normals, max_steps=self.max_episode_steps, **self.box)
+        return self.stats
+
+    def best(self):
+        """((cancel, gain, anchor, off_x, off_y, radius), the mean over the envs of its episode's total reward)."""
+        s = self._stats()
+        return s["best_rule"], s["best_fit"]
+
+    def play_best(self, trace_env=None, keep_actions=False):
+        """The found rule played through swarm_rules, so that its episode can be kept: the outputs of _ffi_swarmrules.swarm_rules
+        for a table of that one rule."""
+        from . import _ffi_swarmrules
+        return _ffi_swarmrules.swarm_rules(self.eng, np.array([self.best()[0]], np.float64), self.max_episode_steps, keep_actions, trace_env)

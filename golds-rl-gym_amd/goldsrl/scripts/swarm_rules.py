@@ -3,13 +3,15 @@ on `Swarm-eval-v0`: every default rule plays the seeded eval episode in ONE kern
 -- the yardstick for eval/total_reward of train_paac_conv.  --json keeps the best rule's episode as {'score', 'actions'}, the
 format of the swarm-eval.json SwarmPolicyMonitor writes; --gif hands that file to goldsrl.scripts.make_swarm_gif, which replays
 the recorded actions, prints `score reproduced` and draws the episode.  --plan H[:K] also plays the receding-horizon planner over the
-same rules (goldsrl/baselines.py:SwarmRulePlanner) and keeps ITS episode instead.  The reference has no counterpart."""
+same rules (goldsrl/baselines.py:SwarmRulePlanner) and keeps ITS episode instead.  --search G[:C[:K]] tunes the best rule's five real
+numbers (goldsrl/baselines.py:SwarmRuleSearch, one call), prints every generation's best and keeps the found rule's episode.  The
+reference has no counterpart."""
 import argparse
 import json
 
 import numpy as np
 
-from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline, SwarmRulePlanner
+from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline, SwarmRulePlanner, SwarmRuleSearch
 
 
 def plan_arg(text):
@@ -23,6 +25,23 @@ def plan_arg(text):
     return parts[0], parts[-1]
 
 
+def search_arg(text):
+    """--search (and the trainers' --search-baseline): 'G', 'G:C' or 'G:C:K' as (generations, candidates, elites) with G >= 1,
+    2 <= C <= 1024 and 1 <= K <= C; C defaults to 32 and K to min(8, C)."""
+    try:
+        parts = [int(v) for v in text.split(":")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2, 3):
+        raise argparse.ArgumentTypeError("expected G, G:C or G:C:K, got %r" % text)
+    G = parts[0]
+    C = parts[1] if len(parts) > 1 else 32
+    K = parts[2] if len(parts) > 2 else min(8, C)
+    if G < 1 or not 2 <= C <= 1024 or not 1 <= K <= C:
+        raise argparse.ArgumentTypeError("expected G >= 1, 2 <= C <= 1024 and 1 <= K <= C, got %r" % text)
+    return G, C, K
+
+
 def get_arg_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--seed", type=int, default=192, help="the env's seed (192: Swarm-eval-v0's registration)")
@@ -31,6 +50,10 @@ def get_arg_parser():
     p.add_argument("--plan", type=plan_arg, default=None, metavar="H[:K]",
                    help="also play the receding-horizon planner over the same rules (every rule H steps ahead, the best committed for K "
                         "steps, default K = H, again; one call) and print its total beside the rules'; --json / --gif then keep the planned episode")
+    p.add_argument("--search", type=search_arg, default=None, metavar="G[:C[:K]]",
+                   help="also tune the best rule's five real numbers under its anchor: G generations of C candidates (default 32) refitted "
+                        "over K elites (default 8), one call; prints every generation's best; --json / --gif then keep the found rule's "
+                        "episode (after --plan as well, the found rule's is the one kept)")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -63,6 +86,19 @@ def main(argv=None):
         c = ps["choices"][0]
         print("plan: horizon %d, replan %d: %d decisions, %d switches, rules chosen %s, length %d, total reward %.6f (%+.6f on the best rule)"
               % (horizon, replan, int((c >= 0).sum()), pl.switches(), sorted(set(int(v) for v in c[c >= 0])), n, pl.total(), pl.total() - total))
+    if args.search:
+        G, C, K = args.search
+        se = SwarmRuleSearch(env._eng, six, G, C, K)
+        ss = se.run()
+        for g in range(G):
+            print("search: generation %d best %.6f  (cancel %g gain %g anchor %d offset (%g, %g) radius %g)"
+                  % ((g, float(ss["best_per_generation"][g])) + tuple(ss["candidates"][g, ss["order"][g, 0]])))
+        found, fit = se.best()
+        ps = se.play_best(keep_actions=True)
+        n = int(ps["length"][0, 0])
+        rewards, actions = ps["rewards"][0, 0, :n], ps["actions"][0, 0, :n]
+        print("search: %d generations of %d candidates, %d elites: rule %s, length %d, total reward %.6f (%+.6f on the best rule)"
+              % (G, C, K, found, n, fit, fit - total))
     score = float(np.sum(rewards))                                      # the monitor's total_reward
     path = args.json or (args.gif + ".json" if args.gif else None)
     if path:

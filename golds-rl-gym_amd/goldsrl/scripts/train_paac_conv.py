@@ -10,7 +10,7 @@ from goldsrl.agents.paac.emulator_runner import SwarmRunner
 from goldsrl.agents.paac.paac import GridPAACLearner
 from goldsrl.agents.paac.policy_v_network import ConvSingleAgentPolicyNetwork
 from goldsrl.agents.state_processors import SwarmStateProcessor
-from goldsrl.scripts.swarm_rules import plan_arg
+from goldsrl.scripts.swarm_rules import plan_arg, search_arg
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO)
 
@@ -77,8 +77,9 @@ _BASELINE_HELP = ("play the scripted do-nothing baseline (drift / hold) on the e
 
 
 def check_baseline_flags(args):
-    """The three yardstick flags play the monitor's eval env: refused without it."""
-    for flag, dest in (("--baseline", "baseline"), ("--rule-baseline", "rule_baseline"), ("--plan-baseline", "plan_baseline")):
+    """The four yardstick flags play the monitor's eval env: refused without it."""
+    for flag, dest in (("--baseline", "baseline"), ("--rule-baseline", "rule_baseline"), ("--plan-baseline", "plan_baseline"),
+                       ("--search-baseline", "search_baseline")):
         if getattr(args, dest, None) and not args.eval_every > 0:
             raise SystemExit("%s plays the eval env of the monitor: it needs --eval-every > 0" % flag)
 
@@ -112,6 +113,12 @@ def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True, eval_envs=T
                             "total and write eval/baseline_total_reward and eval/total_reward_minus_baseline at every evaluation (needs "
                             "--eval-every > 0); with --rule-baseline or --baseline as well, the plan is the one written: it is the highest "
                             "of the three")
+        p.add_argument('--search-baseline', type=search_arg, default=None, dest="search_baseline", metavar="G[:C[:K]]",
+                       help="tune the best default rule's five real numbers on the eval env before the first update "
+                            "(goldsrl.baselines.SwarmRuleSearch: G generations of C candidates refitted over K elites, default 32 and 8; one "
+                            "call), log the found rule and write eval/search_baseline_total_reward and eval/total_reward_minus_search_baseline "
+                            "at every evaluation (needs --eval-every > 0); it also supplies eval/baseline_total_reward and "
+                            "eval/total_reward_minus_baseline when no other baseline flag is given, and leaves them alone otherwise")
     p.add_argument('--checkpoint-every', default=0, type=int, dest="checkpoint_every", help="updates between flat-weights checkpoints")
     p.add_argument('--checkpoint-path', default='checkpoint.npz', type=str, dest="checkpoint_path")
     p.add_argument('--resume', default=None, type=str, help="flat-weights checkpoint to start from")
