@@ -187,6 +187,28 @@ struct SwarmSearchState {
     int G, C;                                     // of the last run; G == 0: none yet
 };
 
+// grl_swarm_cemplan (swarm_cemplan.hip); T = C + n_rules rows per env in the working table
+struct SwarmCemPlanState {
+    double *lib_rules, *lib_offsets;              // (cap_rules,3) (cap_rules,10,2): the library as uploaded
+    double *normals;                              // (cap_z,5): (D, G, C, 5)
+    double *x, *xa;                               // (cap_envs,80,2) (cap_envs,10,2): the call's working copy of the positions
+    int32_t *length, *pick;                       // (cap_envs): steps committed, the call's clock; the commit's own choice (always 0)
+    uint8_t *finished;                            // (cap_envs)
+    double *cur_mean, *one;                       // (cap_envs,5): the env's mean between decisions; (cap_envs): the commit's one score
+    double *rewards, *actions;                    // (cap_steps) (cap_act,10,2)
+    double *trace_x, *trace_xa;                   // (cap_trace,80,2) (cap_trace,10,2)
+    double *table_rules, *table_offsets;          // (cap_table,3) (cap_table,10,2): (E, T), the generation's candidates, then the library
+    int32_t *choices;                             // (cap_dec): (E, D)
+    double *chosen_rules, *chosen_offsets;        // (cap_dec,3) (cap_dec,10,2): the commit's table, one row per env and decision
+    double *look0;                                // (cap_look0): (E, D, T), generation 0's scores and the library's from one launch
+    double *lib_scores;                           // (cap_lib): (E, D, n_rules)
+    double *cand, *scores;                        // (cap_gc,6) (cap_gc): (E, D, G, C)
+    int32_t *order;                               // (cap_gc)
+    double *mean, *std;                           // (cap_gen,5) each: (E, D, G + 1)
+    size_t cap_rules, cap_z, cap_envs, cap_steps, cap_act, cap_trace, cap_table, cap_dec, cap_look0, cap_lib, cap_gc, cap_gen;
+    int n_rules, max_steps, decisions, G, C, trace_env, keep_actions;   // of the last run; C == 0: none yet
+};
+
 }  // namespace grl
 
 struct grl_handle {
@@ -213,6 +235,7 @@ struct grl_handle {
     grl::SwarmRulesState srl;
     grl::SwarmPlanState spl;
     grl::SwarmSearchState ssr;
+    grl::SwarmCemPlanState scp;
     grl::TradeSweepState tsw;
     grl::TradeForesightState tfs;
     grl::TickerSweepState ksw;

@@ -1,7 +1,7 @@
 // The step loop of the receding-horizon rule planner of the Swarm env, shared by the translation units that enqueue it
 // (swarm_plan.hip: lookahead and commit of every decision; swarm_search.hip: the lookahead instance as the evaluation of a
-// generation of candidate rules).  One copy of the loop, so a search's score is the planner's lookahead score with
-// horizon = max_steps, and both are the bits grl_swarm_rules gives from the same state.
+// generation of candidate rules; swarm_cemplan.hip: both instances over a table per env).  One copy of the loop, so a search's
+// score is the planner's lookahead score with horizon = max_steps, and both are the bits grl_swarm_rules gives from the same state.
 // Every including file is compiled with -ffp-contract=off.
 #pragma once
 #include <limits.h>
@@ -27,6 +27,7 @@ struct PlanParams {
     double *actions;                              // (E, max_steps, 10, 2) or null
     double *trace_x, *trace_xa;                   // (max_steps, 80, 2) (max_steps, 10, 2)
     int E, n_rules, horizon, replan, max_steps, limit, trace_env, D, d;
+    int stride;                                   // PER_ENV: rows of the table between one env's block and the next (>= n_rules)
 };
 
 // One dependent chain per workgroup, as the rules' kernel: latency counts, waves per SIMD do not (cdna_hip_programming.md: occupancy
@@ -36,7 +37,10 @@ struct PlanParams {
 // SIMD -- below swarm_rules_kernel's 134 / 138 / 150: it has no reward, action or trace address to keep.  Commit: 140 / 144 / 156 VGPRs,
 // 10 192 bytes of LDS (the arg-max's 1 280 bytes of candidate indices), 3 waves per SIMD.  0 bytes of scratch in all six.
 // Measured: profiles/swarm_plan_times.json.
-template <int MATH, bool COMMIT>
+// PER_ENV: every env has a table of its own, unit (env, r) reads row env * stride + r of rules and offsets (swarm_cemplan.hip); one
+// more multiply-add before the loop, nothing inside it.  Lookahead 118 / 122 / 118 VGPRs, commit 140 / 144 / 156 as without it,
+// 0 bytes of scratch.  The two-parameter instances compile to the assembly they had (profiles/swarm_cemplan_isa_same.txt).
+template <int MATH, bool COMMIT, bool PER_ENV = false>
 __global__ __launch_bounds__(SWARM_TPB, 1) void swarm_plan_kernel(PlanParams P) {
     __shared__ SwarmLds L;
     __shared__ int n_end[SWARM_EPB], t_limit[SWARM_EPB];      // steps until this call's share or the TimeLimit ends the unit (0: none); the TimeLimit's share
@@ -131,10 +135,10 @@ __global__ __launch_bounds__(SWARM_TPB, 1) void swarm_plan_kernel(PlanParams P) 
     double cancel = 0, gain = 0, offx = 0, offy = 0;           // the agent lane's rule, in registers for the whole loop
     int anchor = 0;
     if (aactive) {
-        const int arule = rule_of[ea];
-        const double *r = P.rules + (size_t)arule * 3;
+        const size_t arule = (PER_ENV ? (size_t)aenv * P.stride : 0) + rule_of[ea];
+        const double *r = P.rules + arule * 3;
         cancel = r[0]; gain = r[1]; anchor = r[2] != 0.0 ? 1 : 0;          // the host admits 0 and 1 only
-        double2 o = reinterpret_cast<const double2 *>(P.offsets)[(size_t)arule * N_AGENTS + a];
+        double2 o = reinterpret_cast<const double2 *>(P.offsets)[arule * N_AGENTS + a];
         offx = o.x; offy = o.y;
     }
     const int rule = rule_of[el], t0 = t_first[el], at0 = agent_lane ? t_first[ea] : 0;

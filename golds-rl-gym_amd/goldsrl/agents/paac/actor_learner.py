@@ -23,6 +23,7 @@ class ActorLearner(object):
         self.rule_baseline = getattr(args, 'rule_baseline', False)      # the feedback-rule baseline beside the evaluation (--rule-baseline, Swarm)
         self.plan_baseline = getattr(args, 'plan_baseline', None)       # (horizon, replan) of the rule planner beside the evaluation (--plan-baseline, Swarm)
         self.search_baseline = getattr(args, 'search_baseline', None)   # (generations, candidates, elites) of the rule search beside the evaluation (--search-baseline, Swarm)
+        self.cem_plan_baseline = getattr(args, 'cem_plan_baseline', None)   # (horizon, replan, generations, candidates, elites) of the search planner (--cem-plan-baseline, Swarm)
         self.optimal = getattr(args, 'optimal', False)                 # the optimal-savings yardstick beside the evaluation (--optimal, Solow)
         self.checkpoint_every = getattr(args, 'checkpoint_every', 0)    # updates between flat-weights checkpoints (0: never)
         self.checkpoint_path = getattr(args, 'checkpoint_path', 'checkpoint.npz')

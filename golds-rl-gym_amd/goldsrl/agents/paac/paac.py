@@ -217,6 +217,9 @@ class GridPAACLearner(PAACLearner):
             search = getattr(self, "search_baseline", None)     # scalars of its own; the others' stay what they are
             if search:
                 logging.info("Tuned-rule baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.search_baseline(*search))
+            cem = getattr(self, "cem_plan_baseline", None)      # scalars of its own, as the search's
+            if cem:
+                logging.info("Search-planner baseline on Swarm-eval-v0: %s, total_reward %.6g", *pe.cem_plan_baseline(*cem))
         state = {"last_eval": last_eval}
 
         def between_updates(counter):

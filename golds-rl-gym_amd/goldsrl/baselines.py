@@ -35,7 +35,12 @@ counterpart either.
 
 SwarmRuleSearch stands between the two: the best FIXED rule a cross-entropy search over the rule's five real numbers finds from
 the best rule of the table, every generation of every candidate on every env in one call (include/goldsrl_swarmsearch.h).  A
-yardstick that does not depend on what somebody typed into a table.  No counterpart either."""
+yardstick that does not depend on what somebody typed into a table.  No counterpart either.
+
+SwarmSearchPlanner is the top of the scale: the planner with the search in the place of its table.  At every decision each env
+tunes the rule's five numbers by a short search over lookaheads from where it stands and commits the result unless a rule of the
+table looks better, the whole planned episode in one call (include/goldsrl_swarmcemplan.h).  What a controller earns that reacts
+AND may pick any rule of the family.  No counterpart either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -508,3 +513,50 @@ class SwarmRuleSearch(_EngineBaseline):
         for a table of that one rule."""
         from . import _ffi_swarmrules
         return _ffi_swarmrules.swarm_rules(self.eng, np.array([self.best()[0]], np.float64), self.max_episode_steps, keep_actions, trace_env)
+
+
+class SwarmSearchPlanner(_EngineBaseline):
+    """A controller that reacts and may pick ANY rule of the six-number family: at every decision each env runs `generations`
+    generations of `candidates` candidates refitted over `elites` elites around its own mean, every candidate and every rule of
+    `rules` played `horizon` steps ahead from where the env stands; the searched rule is committed for `replan` steps if it beats
+    the table's best strictly (and becomes the env's mean), else that table rule is; then the env plans again.  The whole planned
+    episode of every env is enqueued in one call (include/goldsrl_swarmcemplan.h; the scheme is written there).  start=None plays
+    SwarmRuleBaseline over `rules` on the same envs first and starts from its best rule, as SwarmRuleSearch does; the start's anchor
+    is the searched rules'.  rules=None: no table, every decision commits a searched rule.  run() plays from the engine's CURRENT
+    state (reset it first) and leaves that state as it was.  No counterpart in the reference."""
+
+    def __init__(self, engine, rules=DEFAULT_SWARM_RULES, start=None, horizon=8, replan=4, generations=2, candidates=12, elites=4, seed=0,
+                 spread=None, floor=None, lo=None, hi=None, normals=None, max_episode_steps=None):
+        from . import _ffi_swarmsearch as S
+        self._open(engine, "ENV_SWARM", "the Swarm search planner exists for the Swarm env only")
+        self._steps(max_episode_steps)
+        self.rules = None if rules is None or len(rules) == 0 else S.check_swarm_rules(rules)
+        self.start = None if start is None else S.check_swarm_rules(np.asarray(start, np.float64).reshape(1, -1))[0]
+        if self.start is None and self.rules is None:
+            raise ValueError("without a table of rules the search planner needs a start")
+        self.horizon, self.replan = int(horizon), int(replan)
+        if not 1 <= self.replan <= self.horizon:
+            raise ValueError("1 <= replan <= horizon is required, got horizon %d, replan %d" % (self.horizon, self.replan))
+        self.generations, self.candidates, self.elites, self.seed, self.normals = int(generations), int(candidates), int(elites), seed, normals
+        self.box = {"spread": S.DEFAULT_SPREAD if spread is None else spread, "floor": S.DEFAULT_FLOOR if floor is None else floor,
+                    "lo": S.DEFAULT_LO if lo is None else lo, "hi": S.DEFAULT_HI if hi is None else hi}
+        self.start_total = None                       # the table's best total, when the start came from the table
+
+    def run(self, trace_env=None, keep_actions=False):
+        """Plan every env's episode; returns (and keeps) the outputs of _ffi_swarmcemplan.swarm_cemplan."""
+        from . import _ffi_swarmcemplan
+        if self.start is None:
+            _, six, self.start_total = SwarmRuleBaseline(self.eng, self.rules, self.max_episode_steps).best_total()
+            self.start = np.array(six, np.float64)
+        self.stats = _ffi_swarmcemplan.swarm_cemplan(
+            self.eng, self.rules, self.start, self.horizon, self.replan, self.generations, self.candidates, self.elites, seed=self.seed,
+            normals=self.normals, max_steps=self.max_episode_steps, keep_actions=keep_actions, trace_env=trace_env, **self.box)
+        return self.stats
+
+    def total(self):
+        """The mean over the envs of the planned episode's total reward."""
+        return float(self._stats()["totals"].mean())
+
+    def searched(self):
+        """The number of decisions, over all envs, that committed a searched rule."""
+        return int(self._stats()["searched"])

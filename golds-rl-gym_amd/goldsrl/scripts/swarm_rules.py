@@ -4,14 +4,15 @@ on `Swarm-eval-v0`: every default rule plays the seeded eval episode in ONE kern
 format of the swarm-eval.json SwarmPolicyMonitor writes; --gif hands that file to goldsrl.scripts.make_swarm_gif, which replays
 the recorded actions, prints `score reproduced` and draws the episode.  --plan H[:K] also plays the receding-horizon planner over the
 same rules (goldsrl/baselines.py:SwarmRulePlanner) and keeps ITS episode instead.  --search G[:C[:K]] tunes the best rule's five real
-numbers (goldsrl/baselines.py:SwarmRuleSearch, one call), prints every generation's best and keeps the found rule's episode.  The
-reference has no counterpart."""
+numbers (goldsrl/baselines.py:SwarmRuleSearch, one call), prints every generation's best and keeps the found rule's episode.
+--cem-plan H[:K[:G[:C[:M]]]] plays the search planner (goldsrl/baselines.py:SwarmSearchPlanner, one call), which tunes the rule at
+every decision, prints its total and keeps ITS episode.  The reference has no counterpart."""
 import argparse
 import json
 
 import numpy as np
 
-from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline, SwarmRulePlanner, SwarmRuleSearch
+from goldsrl.baselines import DEFAULT_SWARM_RULES, SwarmRuleBaseline, SwarmRulePlanner, SwarmRuleSearch, SwarmSearchPlanner
 
 
 def plan_arg(text):
@@ -42,6 +43,25 @@ def search_arg(text):
     return G, C, K
 
 
+def cem_plan_arg(text):
+    """--cem-plan (and the trainers' --cem-plan-baseline): 'H[:K[:G[:C[:M]]]]' as (horizon, replan, generations, candidates, elites)
+    with 1 <= K <= H, G >= 1, 2 <= C <= 1024 and 1 <= M <= C; K defaults to H, G to 2, C to 12 and M to min(4, C)."""
+    try:
+        parts = [int(v) for v in text.split(":")]
+    except ValueError:
+        parts = []
+    if not 1 <= len(parts) <= 5:
+        raise argparse.ArgumentTypeError("expected H[:K[:G[:C[:M]]]], got %r" % text)
+    H = parts[0]
+    K = parts[1] if len(parts) > 1 else H
+    G = parts[2] if len(parts) > 2 else 2
+    C = parts[3] if len(parts) > 3 else 12
+    M = parts[4] if len(parts) > 4 else min(4, C)
+    if not 1 <= K <= H or G < 1 or not 2 <= C <= 1024 or not 1 <= M <= C:
+        raise argparse.ArgumentTypeError("expected 1 <= K <= H, G >= 1, 2 <= C <= 1024 and 1 <= M <= C, got %r" % text)
+    return H, K, G, C, M
+
+
 def get_arg_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--seed", type=int, default=192, help="the env's seed (192: Swarm-eval-v0's registration)")
@@ -54,6 +74,11 @@ def get_arg_parser():
                    help="also tune the best rule's five real numbers under its anchor: G generations of C candidates (default 32) refitted "
                         "over K elites (default 8), one call; prints every generation's best; --json / --gif then keep the found rule's "
                         "episode (after --plan as well, the found rule's is the one kept)")
+    p.add_argument("--cem-plan", type=cem_plan_arg, default=None, dest="cem_plan", metavar="H[:K[:G[:C[:M]]]]",
+                   help="also play the search planner from the best rule: at every decision G generations (default 2) of C candidates "
+                        "(default 12) refitted over M elites (default 4), every candidate and every rule H steps ahead, the better "
+                        "committed for K steps (default K = H), again; one call; --json / --gif then keep its episode (after --plan and "
+                        "--search as well)")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -99,6 +124,17 @@ def main(argv=None):
         rewards, actions = ps["rewards"][0, 0, :n], ps["actions"][0, 0, :n]
         print("search: %d generations of %d candidates, %d elites: rule %s, length %d, total reward %.6f (%+.6f on the best rule)"
               % (G, C, K, found, n, fit, fit - total))
+    if args.cem_plan:
+        H, K, G, C, M = args.cem_plan
+        cp = SwarmSearchPlanner(env._eng, DEFAULT_SWARM_RULES, six, H, K, G, C, M)
+        cs = cp.run(keep_actions=True)
+        n = int(cs["length"][0])
+        rewards, actions = cs["rewards"][0, :n], cs["actions"][0, :n]
+        ch = cs["choices"][0]
+        print("cem-plan: horizon %d, replan %d, %d generations of %d, %d elites: %d decisions, %d searched, library rules chosen %s, length %d, "
+              "total reward %.6f (%+.6f on the best rule)"
+              % (H, K, G, C, M, int((ch >= 0).sum()), cp.searched(), sorted(set(int(v) for v in ch[(ch >= 0) & (ch < len(DEFAULT_SWARM_RULES))])),
+                 n, cp.total(), cp.total() - total))
     score = float(np.sum(rewards))                                      # the monitor's total_reward
     path = args.json or (args.gif + ".json" if args.gif else None)
     if path:

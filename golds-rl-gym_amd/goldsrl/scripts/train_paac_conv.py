@@ -10,7 +10,7 @@ from goldsrl.agents.paac.emulator_runner import SwarmRunner
 from goldsrl.agents.paac.paac import GridPAACLearner
 from goldsrl.agents.paac.policy_v_network import ConvSingleAgentPolicyNetwork
 from goldsrl.agents.state_processors import SwarmStateProcessor
-from goldsrl.scripts.swarm_rules import plan_arg, search_arg
+from goldsrl.scripts.swarm_rules import cem_plan_arg, plan_arg, search_arg
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO)
 
@@ -77,9 +77,9 @@ _BASELINE_HELP = ("play the scripted do-nothing baseline (drift / hold) on the e
 
 
 def check_baseline_flags(args):
-    """The four yardstick flags play the monitor's eval env: refused without it."""
+    """The five yardstick flags play the monitor's eval env: refused without it."""
     for flag, dest in (("--baseline", "baseline"), ("--rule-baseline", "rule_baseline"), ("--plan-baseline", "plan_baseline"),
-                       ("--search-baseline", "search_baseline")):
+                       ("--search-baseline", "search_baseline"), ("--cem-plan-baseline", "cem_plan_baseline")):
         if getattr(args, dest, None) and not args.eval_every > 0:
             raise SystemExit("%s plays the eval env of the monitor: it needs --eval-every > 0" % flag)
 
@@ -119,6 +119,13 @@ def get_arg_parser(baseline_help=_BASELINE_HELP, rule_baseline=True, eval_envs=T
                             "call), log the found rule and write eval/search_baseline_total_reward and eval/total_reward_minus_search_baseline "
                             "at every evaluation (needs --eval-every > 0); it also supplies eval/baseline_total_reward and "
                             "eval/total_reward_minus_baseline when no other baseline flag is given, and leaves them alone otherwise")
+        p.add_argument('--cem-plan-baseline', type=cem_plan_arg, default=None, dest="cem_plan_baseline", metavar="H[:K[:G[:C[:M]]]]",
+                       help="play the search planner (goldsrl.baselines.SwarmSearchPlanner: at every decision G generations of C candidates "
+                            "refitted over M elites, every candidate and default rule H steps ahead, the better committed for K steps; defaults "
+                            "K = H, 2, 12 and 4; one call) on the eval env before the first update, log its total and write "
+                            "eval/cem_plan_baseline_total_reward and eval/total_reward_minus_cem_plan_baseline at every evaluation (needs "
+                            "--eval-every > 0); it also supplies eval/baseline_total_reward and eval/total_reward_minus_baseline when no other "
+                            "baseline flag is given, and leaves them alone otherwise")
     p.add_argument('--checkpoint-every', default=0, type=int, dest="checkpoint_every", help="updates between flat-weights checkpoints")
     p.add_argument('--checkpoint-path', default='checkpoint.npz', type=str, dest="checkpoint_path")
     p.add_argument('--resume', default=None, type=str, help="flat-weights checkpoint to start from")
