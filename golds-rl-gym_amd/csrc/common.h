@@ -111,6 +111,18 @@ struct TickerSweepState {
     int n_rules, max_steps, trace_env;                   // of the last sweep; n_rules == 0: none yet
 };
 
+// grl_ticker_search (ticker_search.hip); cap_gc counts (generation, candidate) pairs, cap_gen generations + 1
+struct TickerSearchState {
+    double *normals;                                     // (cap_gc,6): the host's normals
+    float *cand;                                         // (cap_gc,6): the rows as played; generation g's table is the evaluation's at g * C
+    double *fit;                                         // (cap_gc)
+    int32_t *order;                                      // (cap_gc)
+    double *scores;                                      // (cap_scores): (G, C, E)
+    double *mean, *std;                                  // (cap_gen,6) each
+    size_t cap_gc, cap_scores, cap_gen;
+    int G, C;                                            // of the last run; G == 0: none yet
+};
+
 // grl_ticker_foresight (ticker_foresight.hip)
 struct TickerForesightState {
     PairStats stats;
@@ -239,6 +251,7 @@ struct grl_handle {
     grl::TradeSweepState tsw;
     grl::TradeForesightState tfs;
     grl::TickerSweepState ksw;
+    grl::TickerSearchState kse;
     grl::TickerForesightState kfs;
     grl::SolowDpState sdp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle

@@ -7,15 +7,14 @@
 // talks to another.  Unlike TradeAR1 the price path costs no pow / exp, only a 16-byte gather from a table that sits in L2, so
 // there is nothing for several rules per lane to share: one rule per lane is the only form built.
 //
-// The row addresses do not depend on the actions: the next step's row and its lookback price are asked for before the current
-// step's divide chain.  A step is played only while the window holds the row of the observation that follows it (idx <= 1022),
-// which is where the step path raises its window error; so the row asked for ahead (idx + 1 <= 1023) is always inside the window.
+// The step loop is ticker_sweep_play of ticker_sweep_dev.h, which the rule search (ticker_search.hip) instantiates as well; what this
+// kernel keeps of a pair is TickerSweepSink below.
 //
 // The handle's state is read only: nothing here writes the account, idx / start / elapsed / episode / nhist, the outputs, the done
 // list, err_flag or the episode records.
 #include <math.h>
 
-#include "ticker_dev.h"
+#include "ticker_sweep_dev.h"
 #include "episode_host.h"
 #include "../../include/goldsrl_tickersweep.h"
 
@@ -31,70 +30,38 @@ struct TickerSweepOut {
     float4 *trace_act;
 };
 
-__global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const float *__restrict__ rules, int n_rules, int max_steps,
-                                                           int trace_env, TickerSweepOut O) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int env = blockIdx.x * 64 + lane;
-    const int r = blockIdx.y * 4 + wave;                       // wave-uniform
-    if (r >= n_rules || env >= K.E) return;
-    TickerRule U;
-    U.up0 = (double)rules[r * 6 + 0]; U.up1 = (double)rules[r * 6 + 1]; U.dn0 = (double)rules[r * 6 + 2]; U.dn1 = (double)rules[r * 6 + 3];
-    U.band = (double)rules[r * 6 + 4]; U.lookback = (int)rules[r * 6 + 5];
-
-    int idx = max(0, min(K.idx[env], TICKER_WINDOW - 1));      // as ticker_step_env: keep the rows inside the table
-    const int st = max(0, min(K.start[env], K.rows - TICKER_WINDOW));
-    const double *win = K.table + (size_t)st * 4;
-    const int el0 = K.elapsed[env];
-    const double2 qq = reinterpret_cast<const double2 *>(K.q)[env];
-    double cash = K.cash[env], q0 = qq.x, q1 = qq.y, assets = K.assets[env];
-    double la = log(assets + 1e-4);
+// what the sweep keeps of a pair: the statistics and the trades in registers, the traced env's steps, the final account
+struct TickerSweepSink {
+    const TickerSweepOut &O;
+    const size_t o, tr0;                                       // the pair's slot; its first trace row
+    const bool trace;
     RewardStats rs;
-    int length = 0, trades = 0;
-    bool finished = false, depleted = false;
-    const bool trace = env == trace_env;
-    const size_t tr0 = (size_t)r * max_steps;
-
-    double2 pp = *reinterpret_cast<const double2 *>(win + (size_t)idx * 4);
-    double back = win[(size_t)max(idx - U.lookback, 0) * 4];
-    for (int t = 0; t < max_steps; ++t) {
-        if (idx >= TICKER_WINDOW - 1) break;                   // no row for the observation after this step: the window is played out
-        const double2 pn = *reinterpret_cast<const double2 *>(win + (size_t)(idx + 1) * 4);
-        const double bn = win[(size_t)max(idx + 1 - U.lookback, 0) * 4];
-        const float4 act = ticker_rule_action(U, cash, q0, q1, pp.x, pp.y, back);
-        const float rew = ticker_account_step(act, pp.x, pp.y, cash, q0, q1, assets, la);
+    int trades = 0;
+    __device__ __forceinline__ void step(int t, const float4 act, float rew, double assets) {
         rs.add(rew);
-        length = t + 1;
         trades += (act.x != 0.f || act.y != 0.f) ? 1 : 0;
         if (trace) {
             O.trace_r[tr0 + t] = rew;
             O.trace_a[tr0 + t] = assets;
             O.trace_act[tr0 + t] = act;
         }
-        depleted = assets < TICKER_MIN_CASH;
-        finished = depleted || (K.max_steps > 0 && el0 + t + 1 >= K.max_steps);
-        if (finished) break;
-        idx += 1;
-        pp = pn;
-        back = bn;
     }
-    const size_t o = (size_t)r * K.E + env;
-    O.stats.store(o, rs, length, finished);
-    O.final_assets[o] = assets; O.trades[o] = trades;
-    O.depleted[o] = depleted ? 1 : 0;
-}
+    __device__ __forceinline__ void finish(int length, bool finished, bool depleted, double assets) {
+        O.stats.store(o, rs, length, finished);
+        O.final_assets[o] = assets; O.trades[o] = trades;
+        O.depleted[o] = depleted ? 1 : 0;
+    }
+};
 
-// the first thing wrong with rule i, or nullptr
-static const char *ticker_rule_fault(const float *u, const char **field) {
-    static const char *names[6] = {"up0", "up1", "dn0", "dn1", "band", "lookback"};
-    for (int k = 0; k < 6; ++k)
-        if (!std::isfinite(u[k])) { *field = names[k]; return "is not finite"; }
-    for (int k = 0; k < 4; ++k)
-        if (u[k] < 0.f || u[k] > 1.f) { *field = names[k]; return "is a weight outside [0, 1]"; }
-    if ((double)u[0] + (double)u[1] > 1.0) { *field = "up0 + up1"; return "is above 1"; }
-    if ((double)u[2] + (double)u[3] > 1.0) { *field = "dn0 + dn1"; return "is above 1"; }
-    if (u[4] < 0.f) { *field = names[4]; return "is negative"; }
-    if (u[5] < 0.f || u[5] > (float)(TICKER_WINDOW - 1) || u[5] != floorf(u[5])) { *field = names[5]; return "is not an integer in 0..1023"; }
-    return nullptr;
+__global__ __launch_bounds__(256) void ticker_sweep_kernel(TickerParams K, const float *__restrict__ rules, int n_rules, int max_steps,
+                                                           int trace_env, TickerSweepOut O) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int env = blockIdx.x * 64 + lane;
+    const int r = blockIdx.y * 4 + wave;                       // wave-uniform
+    if (r >= n_rules || env >= K.E) return;
+    const TickerRule U = ticker_rule_load(rules, r);
+    TickerSweepSink S{O, (size_t)r * K.E + env, (size_t)r * max_steps, env == trace_env};
+    ticker_sweep_play(K, U, env, max_steps, S);
 }
 
 }  // namespace grl

@@ -308,6 +308,51 @@ class GatedPolicyMonitor(_DeviceMonitor):
         self.ceiling_total_reward = c.ceiling()
         return self.ceiling_total_reward
 
+    def ticker_search_baseline(self, generations=8, candidates=32, elites=8, starts=None, tune_table=None, **search_kw):
+        """The tuned rule (goldsrl/baselines.py:TickerRuleSearch): the six numbers of the rule family a cross-entropy search finds,
+        every generation in one call.  With tune_table (the training table, or its sampler) the search runs on a second eval-style
+        engine of the same n_envs on that table and the found rule is then played on the monitor's own engine -- six numbers fitted
+        in sample, played out of sample; without it the search runs on the monitor's own engine.  starts: a list of start rules
+        (default: the best default rule where the search runs).  Keeps search_baseline_rule, search_baseline_total_reward -- the
+        found rule's mean total on the monitor's engine, what evaluations are compared with --,
+        search_baseline_in_sample_total_reward -- its fit where it was tuned; the same number without tune_table -- and every
+        start's (start, rule, fit) in search_baseline_results; leaves the engine reset.  The scalars of ticker_baseline() and
+        ticker_ceiling() are not touched.  Returns (rule, search_baseline_total_reward)."""
+        from ...baselines import TickerRuleSearch
+        eng = self.net.eng
+        tuned_on = eng if tune_table is None else make_ticker_eval_engine(tune_table, self.n_envs, eng.cfg.device_id, self.max_episode_steps)
+        try:
+            tuned_on.reset()
+            b = TickerRuleSearch(tuned_on, starts=starts, generations=generations, candidates=candidates, elites=elites,
+                                 max_episode_steps=self.max_episode_steps, **search_kw)
+            rule, fit = b.best()
+            self.search_baseline_results = b.results
+            if tune_table is None:
+                total = fit
+            else:
+                eng.reset()
+                total = b.play_on(eng)
+        finally:
+            if tuned_on is not eng:
+                tuned_on.close()
+        self.search_baseline_rule, self.search_baseline_total_reward, self.search_baseline_in_sample_total_reward = rule, total, fit
+        self._search_tuned_elsewhere = tune_table is not None
+        eng.reset()
+        return rule, total
+
+    def write_search_baseline_scalars(self, global_step):
+        """eval/search_baseline_total_reward and eval/mean_total_reward_minus_search_baseline of the last evaluation (after
+        ticker_search_baseline()), and eval/search_baseline_in_sample_total_reward when the rule was tuned on another table"""
+        w, total = self.summary_writer, getattr(self, "search_baseline_total_reward", None)
+        if w is None or total is None:
+            return
+        w.add_scalar("eval/search_baseline_total_reward", total, global_step)
+        if self.log["mean_total_reward"]:
+            w.add_scalar("eval/mean_total_reward_minus_search_baseline", self.log["mean_total_reward"][-1] - total, global_step)
+        if self._search_tuned_elsewhere:
+            w.add_scalar("eval/search_baseline_in_sample_total_reward", self.search_baseline_in_sample_total_reward, global_step)
+        w.flush()
+
 
 class GridPolicyMonitor(_DeviceMonitor):
     """The PolicyMonitor of the discrete savings-grid agent.  env: the Solow eval registration's id.  n_grid, lb, ub: the

@@ -40,7 +40,12 @@ yardstick that does not depend on what somebody typed into a table.  No counterp
 SwarmSearchPlanner is the top of the scale: the planner with the search in the place of its table.  At every decision each env
 tunes the rule's five numbers by a short search over lookaheads from where it stands and commits the result unless a rule of the
 table looks better, the whole planned episode in one call (include/goldsrl_swarmcemplan.h).  What a controller earns that reacts
-AND may pick any rule of the family.  No counterpart either."""
+AND may pick any rule of the family.  No counterpart either.
+
+TickerRuleSearch is the Ticker env's counterpart of SwarmRuleSearch: the best six numbers of the banded-target rule family a
+cross-entropy search finds from the best default rule (or from a list of starts), every generation in one call
+(include/goldsrl_tickersearch.h), and that rule played on another engine: tuned on the training table, played on the held-out
+one.  No counterpart either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -388,6 +393,69 @@ class TickerForesightCeiling(_EngineBaseline):
         s = self._stats()
         return [(int(h), float(s["total"][i].mean()), float(s["length"][i].mean()), float(s["trades"][i].mean()))
                 for i, h in enumerate(self.horizons)]
+
+
+class TickerRuleSearch(_EngineBaseline):
+    """The best rule of the six-number family near a start: a cross-entropy search over (up0, up1, dn0, dn1, band, lookback),
+    `generations` generations of `candidates` candidates refitted over `elites` elites, every candidate's episode on every env of
+    the engine, all enqueued in one call (include/goldsrl_tickersearch.h; the scheme is written there).  start=None plays
+    TickerRuleBaseline over `rules` on the same envs first and starts from its best rule; starts: a list of start rules instead, one
+    call per start, the best found rule kept and every start's result reported in `results`.  Candidate 0 of every generation is
+    the best so far, so a found rule is never below its start on the envs it was tuned on.  Tuned on the training table and played
+    on a held-out one (play_on) it is the yardstick "six numbers fitted in sample, played out of sample": a trader below it has
+    learned less than a curve-fitted script.  spread, floor, lo, hi: None for _ffi_tickersearch.ticker_search_defaults of each
+    start.  run() plays from the engine's CURRENT state (reset it first) and leaves that state as it was.  No counterpart in the
+    reference."""
+
+    def __init__(self, engine, start=None, starts=None, generations=8, candidates=32, elites=8, seed=0, spread=None, floor=None, lo=None,
+                 hi=None, normals=None, rules=DEFAULT_TICKER_RULES, max_episode_steps=None):
+        from ._ffi_tickersweep import check_ticker_rules
+        self._open(engine, "ENV_TICKER", "the Ticker rule search exists for the Ticker env only")
+        self._steps(max_episode_steps)
+        if start is not None and starts is not None:
+            raise ValueError("give start or starts, not both")
+        if starts is not None:
+            self.starts = check_ticker_rules(np.asarray(starts, np.float32).reshape(-1, 6))
+        else:
+            self.starts = None if start is None else check_ticker_rules(np.asarray(start, np.float32).reshape(1, 6))
+        self.rules = check_ticker_rules(rules)
+        self.generations, self.candidates, self.elites, self.seed, self.normals = int(generations), int(candidates), int(elites), seed, normals
+        self.box = {"spread": spread, "floor": floor, "lo": lo, "hi": hi}
+        self.start_total = None                       # the table's best total, when the start came from the table
+        self.results = None
+
+    def run(self):
+        """Search from every start; keeps `results`, one (start, best_rule, best_fit) row per start in the order given, and returns
+        (and keeps) the outputs of _ffi_tickersearch.ticker_search for the start whose found rule is best (the first on a tie)."""
+        from . import _ffi_tickersearch as S
+        if self.starts is None:
+            _, six, self.start_total = TickerRuleBaseline(self.eng, self.rules, self.max_episode_steps).best_total()
+            self.starts = np.array([six], np.float32)
+        self.results, self.stats = [], None
+        for start in self.starts:
+            out = S.ticker_search(self.eng, start, generations=self.generations, candidates=self.candidates, elites=self.elites,
+                                  seed=self.seed, normals=self.normals, max_steps=self.max_episode_steps, **self.box)
+            self.results.append((tuple(float(v) for v in start), out["best_rule"], out["best_fit"]))
+            if self.stats is None or out["best_fit"] > self.stats["best_fit"]:
+                self.stats = out
+        return self.stats
+
+    def best(self):
+        """((up0, up1, dn0, dn1, band, lookback), the mean over the envs of its episode's total reward where it was tuned)."""
+        s = self._stats()
+        return s["best_rule"], s["best_fit"]
+
+    def play_on(self, other_engine, rule=None):
+        """The mean over the envs of other_engine of the total reward of the found rule (or `rule`), played through
+        grl_ticker_sweep from that engine's CURRENT state for this search's episode length: the found rule out of sample.  The
+        mean is the search's fit statement (adds in env order, one division), so on the engine it was tuned on it is best()[1]."""
+        from . import _ffi_tickersweep
+        six = np.array([self.best()[0] if rule is None else rule], np.float32)
+        total = _ffi_tickersweep.ticker_sweep(other_engine, six, self.max_episode_steps)["total"][0]
+        s = np.float64(0.0)
+        for v in total:
+            s = s + v
+        return float(s / np.float64(len(total)))
 
 
 def _swarm_rules():

@@ -10,7 +10,13 @@ before the first update (one launch; the eval engine is reseeded at every reset,
 rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written at every evaluation.  With --ceiling the
 foresight traders of goldsrl/baselines.py:TickerForesightCeiling play the same windows once (one launch): the mean total of every
 horizon is logged, eval/ceiling_total_reward -- the trader who knows every row of its episode -- is written at every evaluation, and
-with --baseline also eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline).  Training is untouched."""
+with --baseline also eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline).  With --search-baseline G[:C[:K]]
+the six numbers of the rule family are tuned by a cross-entropy search (goldsrl/baselines.py:TickerRuleSearch, every generation in one
+call) -- on the TRAINING table when --eval-csv / --eval-table names a held-out one, and the found rule is then played on the eval
+envs: six numbers fitted in sample, played out of sample.  The rule and both totals are logged before the first update;
+eval/search_baseline_total_reward, eval/mean_total_reward_minus_search_baseline and, when tuned on another table,
+eval/search_baseline_in_sample_total_reward are written at every evaluation; the scalars of --baseline and --ceiling are left alone.
+Training is untouched."""
 import argparse
 import logging
 import os
@@ -22,6 +28,7 @@ import numpy as np
 from goldsrl import _ffi, _ffi_gated
 from goldsrl.agents.a3c.policy_monitor import GatedPolicyMonitor
 from goldsrl.envs.data.sampler import OpenCloseSampler
+from goldsrl.scripts.swarm_rules import search_arg
 from goldsrl.utils_tfevents import EventFileWriter
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO)
@@ -53,6 +60,11 @@ def get_arg_parser():
                    help="play the foresight traders on the eval envs before the first update (one kernel launch) and write "
                         "eval/ceiling_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap at every evaluation "
                         "(needs --eval-envs)")
+    p.add_argument("--search-baseline", "--search_baseline", dest="search_baseline", type=search_arg, default=None, metavar="G[:C[:K]]",
+                   help="tune the rule's six numbers before the first update: G generations of C candidates (default 32) refitted over K "
+                        "elites (default 8), one call, on the training table when a held-out eval table is given; writes "
+                        "eval/search_baseline_total_reward and eval/mean_total_reward_minus_search_baseline at every evaluation "
+                        "(needs --eval-envs)")
     ev = p.add_mutually_exclusive_group()
     ev.add_argument("--eval-csv", "--eval_csv", dest="eval_csv", help="held-out price table CSV for the evaluation")
     ev.add_argument("--eval-table", "--eval_table", dest="eval_table", help="held-out price table .npz for the evaluation")
@@ -75,6 +87,8 @@ def parse_args(argv=None):
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs M > 0")
     if args.ceiling and args.eval_envs <= 0:
         parser.error("--ceiling plays the eval envs of the device monitor: it needs --eval-envs M > 0")
+    if args.search_baseline and args.eval_envs <= 0:
+        parser.error("--search-baseline plays the eval envs of the device monitor: it needs --eval-envs M > 0")
     return args
 
 
@@ -109,6 +123,13 @@ def main(argv=None):
             monitor.ticker_ceiling()
             logging.info("Ticker foresight on the eval envs, mean total_reward by rows known ahead: %s",
                          ", ".join("%s %.6g" % ("whole episode" if h == 0 else str(h), tot) for h, tot, _, _ in monitor.ceiling_table))
+        if args.search_baseline:
+            G, C, K = args.search_baseline
+            rule, total = monitor.ticker_search_baseline(G, C, K, tune_table=sampler if held_out is not sampler else None)
+            logging.info("Ticker tuned rule (%d generations of %d candidates, %d elites, tuned on the %s table): up %.6g %.6g, down %.6g "
+                         "%.6g, band %.6g, lookback %d; mean total_reward on the eval envs %.6g, where it was tuned %.6g", G, C, K,
+                         "training" if held_out is not sampler else "eval", rule[0], rule[1], rule[2], rule[3], rule[4], int(rule[5]),
+                         total, monitor.search_baseline_in_sample_total_reward)
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.steps)
@@ -129,6 +150,8 @@ def main(argv=None):
                 monitor.write_baseline_scalars(step)
             if args.ceiling:
                 monitor.write_ceiling_scalars(step)
+            if args.search_baseline:
+                monitor.write_search_baseline_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
                          episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
