@@ -11,7 +11,8 @@
 //   update     swarm_cemplan_update_kernel, one workgroup per env, lane c owning candidate c: rank and refit of the generation
 //              before, then the next generation's rows into the env's block; after the last generation the choice between the
 //              searched rule and the library's best, the chosen row into the commit's table, the env's new mean.  The candidate,
-//              rank and refit statements are the device functions of swarm_search_dev.h, which swarm_search_update_kernel calls too.
+//              rank and refit statements are the device functions of swarm_search_dev.h and, what knows nothing of Swarm, of
+//              search_dev.h, which swarm_search_update_kernel calls too.
 //   commit     swarm_plan_kernel<MATH, true, true> over a table of one row per env: the chosen rows of this decision.
 // 2 G + 2 launches per decision, D = ceil(max_steps / replan) decisions, all on the handle's stream; nothing is read back between
 // them.  The handle's state is read only: the call keeps its own copy of (x, xa) per env and its own clock.
@@ -172,7 +173,7 @@ int grl_swarm_cemplan(grl_handle *h, const double *rules_host, const double *off
     if ((rc = episode_open(h, fn, GRL_ENV_SWARM, "Swarm", mean0 && std0 && floor && lo && hi && ring && normals && (n_rules == 0 || (rules_host && offsets_host)))))
         return rc;
     if (n_rules < 0 || n_rules > 4096) return fail(h, GRL_E_INVALID, "grl_swarm_cemplan: n_rules must be in 0..4096");
-    if ((rc = search_check_counts(h, fn, anchor, G, C, M)) || (rc = episode_check_steps(h, fn, max_steps))) return rc;
+    if ((rc = search_check_anchor(h, fn, anchor)) || (rc = search_check_counts(h, fn, G, C, M)) || (rc = episode_check_steps(h, fn, max_steps))) return rc;
     if (horizon < 1) return fail(h, GRL_E_INVALID, "grl_swarm_cemplan: horizon must be at least 1");
     if (replan < 1 || replan > horizon) return fail(h, GRL_E_INVALID, "grl_swarm_cemplan: replan must be in 1..horizon");
     if ((rc = swarm_check_rule_table(h, fn, rules_host, offsets_host, n_rules)) || (rc = search_check_box(h, fn, mean0, std0, floor, lo, hi, ring)) ||
@@ -183,12 +184,9 @@ int grl_swarm_cemplan(grl_handle *h, const double *rules_host, const double *off
     const size_t dec = E * D, gc = dec * G * C, gen = dec * ((size_t)G + 1), look0 = dec * T, lib = dec * R, zn = D * G * C, table = E * T;
     const size_t largest = std::max(std::max(std::max(gc * 6, look0), std::max(dec, table) * N_AGENTS * 2),
                                     std::max(std::max(steps, act * N_AGENTS * 2), std::max(trace * N_LOCUSTS * 2, std::max(zn, gen) * SEARCH_P)));
-    if (largest > (size_t)INT32_MAX)
-        return fail(h, GRL_E_INVALID, "grl_swarm_cemplan: an output of " + std::to_string(largest) +
-                                          " elements does not fit in int32 (fewer envs, steps, generations, candidates or rules per call)");
-    for (size_t i = 0; i < zn * SEARCH_P; ++i)
-        if (!std::isfinite(normals[i])) return fail(h, GRL_E_INVALID, "grl_swarm_cemplan: normals[" + std::to_string(i) + "] is not finite");
-    if ((rc = episode_check_idle(h, fn))) return rc;
+    if ((rc = search_check_int32(h, fn, largest, "fewer envs, steps, generations, candidates or rules per call")) ||
+        (rc = search_check_normals(h, fn, normals, zn * SEARCH_P)) || (rc = episode_check_idle(h, fn)))
+        return rc;
     hipSetDevice(h->cfg.device_id);
     SwarmCemPlanState &w = h->scp;
     w.C = 0;

@@ -7,8 +7,9 @@
 //   update    one workgroup: the fit of every candidate (a sequential sum over the envs), its rank, the refit of mean and std over
 //             the elites, and the next generation's candidates, rule rows and offsets.  Launched once before generation 0, where it
 //             only clamps the start and builds the table, and once after the last, where it builds none: G + 1 launches.  The
-//             statements themselves are device functions of swarm_search_dev.h, which the per-env planner (swarm_cemplan.hip)
-//             calls too: they exist in that one form.
+//             statements themselves are device functions: the clamp, the draw, the rank and the refit of search_dev.h (the Ticker
+//             search's too), the Swarm row of swarm_search_dev.h, which the per-env planner (swarm_cemplan.hip) calls too: they
+//             exist in that one form.
 // The handle's state is read only: positions, noise rows and elapsed are read, nothing of it is written.
 #include <limits.h>
 #include <math.h>
@@ -92,17 +93,13 @@ int grl_swarm_search(grl_handle *h, int32_t anchor, const double *mean0, const d
     const char *fn = "grl_swarm_search";
     int rc;
     if ((rc = episode_open(h, fn, GRL_ENV_SWARM, "Swarm", mean0 && std0 && floor && lo && hi && ring && normals))) return rc;
-    if ((rc = search_check_counts(h, fn, anchor, G, C, K)) || (rc = episode_check_steps(h, fn, max_steps)) ||
+    if ((rc = search_check_anchor(h, fn, anchor)) || (rc = search_check_counts(h, fn, G, C, K)) || (rc = episode_check_steps(h, fn, max_steps)) ||
         (rc = search_check_box(h, fn, mean0, std0, floor, lo, hi, ring)))
         return rc;
     const size_t E = (size_t)h->E, gc = (size_t)G * C, scores = E * gc;
-    const size_t largest = std::max(scores, gc * N_AGENTS * 2);
-    if (largest > (size_t)INT32_MAX)
-        return fail(h, GRL_E_INVALID, "grl_swarm_search: an output of " + std::to_string(largest) +
-                                          " elements does not fit in int32 (fewer envs, generations or candidates per call)");
-    for (size_t i = 0; i < gc * SEARCH_P; ++i)
-        if (!std::isfinite(normals[i])) return fail(h, GRL_E_INVALID, "grl_swarm_search: normals[" + std::to_string(i) + "] is not finite");
-    if ((rc = episode_check_idle(h, fn))) return rc;
+    if ((rc = search_check_int32(h, fn, std::max(scores, gc * N_AGENTS * 2), "fewer envs, generations or candidates per call")) ||
+        (rc = search_check_normals(h, fn, normals, gc * SEARCH_P)) || (rc = episode_check_idle(h, fn)))
+        return rc;
     hipSetDevice(h->cfg.device_id);
     SwarmSearchState &w = h->ssr;
     w.G = 0;

@@ -1,19 +1,16 @@
-// The statements of the cross-entropy search over a Swarm rule's five real numbers (include/goldsrl_swarmsearch.h: 1 start,
-// 2-4 candidates, incumbent and rows, 7 rank, 8 refit), shared by the translation units whose kernels run them (swarm_search.hip:
-// one distribution for all envs, one workgroup; swarm_cemplan.hip: one distribution and one workgroup per env, at every decision of a
-// planned episode) and the host's checks of the box.  One copy, so the planner's candidates, ranks and refits are the search's bits.
+// What is Swarm's own in the cross-entropy search over a Swarm rule's five real numbers (include/goldsrl_swarmsearch.h: 1 start,
+// 2-4 candidates, incumbent and rows): where the five stand in a six-number row, the box, the ring and the anchor, the candidate's
+// rule row and offsets, and the host's checks of them.  The clamp, the draw, the rank (7) and the refit (8) are search_dev.h's, which
+// the Ticker search shares.  Included by the translation units whose kernels run the statements (swarm_search.hip: one distribution
+// for all envs, one workgroup; swarm_cemplan.hip: one distribution and one workgroup per env, at every decision of a planned
+// episode).  One copy, so the planner's candidates, ranks and refits are the search's bits.
 // Every including file is compiled with -ffp-contract=off.
 #pragma once
-#include <math.h>
-
-#include <string>
-
-#include "common.h"
+#include "search_dev.h"
 
 namespace grl {
 
 constexpr int SEARCH_P = 5;                       // cancel, gain, off_x, off_y, radius
-constexpr int SEARCH_MAX_C = 1024;                // one workgroup ranks a generation
 __host__ __device__ constexpr int search_col(int k) { return k < 2 ? k : k + 1; }      // where parameter k stands in a six-number row
 
 // what the statements read beside the distribution: the start, the spreads and the box, the ring and the anchor
@@ -23,55 +20,13 @@ struct SearchBox {
     double anchor;
 };
 
-// the first operand wins a tie (goldsrl_swarmsearch.h); a select, never v_max/v_min, whose order of signed zeros is their own
-__device__ __forceinline__ double first_max(double a, double b) { return a >= b ? a : b; }
-__device__ __forceinline__ double first_min(double a, double b) { return a <= b ? a : b; }
-
 // 1 start: parameter k of the start, clamped into the box
-__device__ __forceinline__ double search_start(const SearchBox &B, int k) { return first_min(first_max(B.mean0[k], B.lo[k]), B.hi[k]); }
+__device__ __forceinline__ double search_start(const SearchBox &B, int k) { return search_clamp(B.mean0[k], B.lo[k], B.hi[k]); }
 
-// 7 rank: how many candidates stand before this one.  Called by EVERY lane of the workgroup (two barriers inside); lane c < C owns
-// candidate c with fit f.  Leaves fit_s[c] = f and order_s[rank] = c in LDS for the lanes behind the second barrier, and writes
-// order_out[rank] = c.  Fits that are no total order (a NaN) leave ranks unclaimed: those slots of order_s stay indices.
-__device__ __forceinline__ void search_rank(double *fit_s, int *order_s, int c, int C, double f, int32_t *order_out) {
-    const bool mine = c < C;
-    if (mine) {
-        fit_s[c] = f;
-        order_s[c] = c;
-    }
-    __syncthreads();
-    if (mine) {
-        int rank = 0;
-        for (int i = 0; i < C; ++i) {
-            const double o = fit_s[i];
-            rank += (o > f || (o == f && i < c)) ? 1 : 0;
-        }
-        order_s[rank] = c;                        // rank < C: at most the C - 1 others count
-        order_out[rank] = c;
-    }
-    __syncthreads();
-}
-
-// 8 refit of parameter k over the K elites rows[order_s[0..K-1]] (six-number rows): two sequential chains in rank order
+// 8 refit of parameter k: search_dev.h's two chains, over six-number rows.  (Through this call the two update kernels compile to the
+// instructions they had; with search_refit_rows written out at the call sites the compiler swapped two of them.)
 __device__ __forceinline__ void search_refit(const double *rows, const int *order_s, int K, int k, double floor, double &mean, double &std) {
-    const int col = search_col(k);
-    const double kk = (double)K;
-    double m = 0.0;
-    for (int i = 0; i < K; ++i) {
-        const double p = rows[(size_t)order_s[i] * 6 + col];
-        m = m + p;
-    }
-    m = m / kk;
-    double s = 0.0;
-    for (int i = 0; i < K; ++i) {
-        const double p = rows[(size_t)order_s[i] * 6 + col];
-        const double d = p - m;
-        const double q = d * d;
-        s = s + q;
-    }
-    const double v = s / kk;
-    mean = m;
-    std = first_max(sqrt(v), floor);
+    search_refit_rows<double>(rows, 6, order_s, K, search_col(k), floor, mean, std);
 }
 
 // 2-4: one candidate's six-number row, rule row and offsets.  incumbent: null, or the six numbers candidate 0 copies bit for bit
@@ -90,13 +45,7 @@ __device__ __forceinline__ void search_build(const SearchBox &B, const double *m
         }
     } else {                                      // 2 candidates
 #pragma unroll
-        for (int k = 0; k < SEARCH_P; ++k) {
-            double v = std[k] * z[k];
-            v = mean[k] + v;
-            v = first_max(v, B.lo[k]);
-            v = first_min(v, B.hi[k]);
-            six[search_col(k)] = v;
-        }
+        for (int k = 0; k < SEARCH_P; ++k) six[search_col(k)] = search_draw(mean[k], std[k], z[k], B.lo[k], B.hi[k]);
         six[2] = B.anchor;
     }
 #pragma unroll
@@ -112,21 +61,9 @@ __device__ __forceinline__ void search_build(const SearchBox &B, const double *m
     }
 }
 
-// The host's checks of the anchor and the counts, of the box and the ring.  fn: the C function's name, with which every message starts.
-static int search_check_five(grl_handle *h, const char *fn, const char *noun, const double *v, bool non_negative) {
-    for (int k = 0; k < SEARCH_P; ++k) {
-        if (!std::isfinite(v[k])) return fail(h, GRL_E_INVALID, std::string(fn) + ": " + noun + "[" + std::to_string(k) + "] is not finite");
-        if (non_negative && v[k] < 0) return fail(h, GRL_E_INVALID, std::string(fn) + ": " + noun + "[" + std::to_string(k) + "] is negative");
-    }
-    return GRL_OK;
-}
-
-static int search_check_counts(grl_handle *h, const char *fn, int anchor, int G, int C, int K) {
-    const std::string f(fn);
-    if (anchor != 0 && anchor != 1) return fail(h, GRL_E_INVALID, f + ": anchor must be 0 (centroid) or 1 (nearest locust)");
-    if (G < 1) return fail(h, GRL_E_INVALID, f + ": G must be at least 1");
-    if (C < 2 || C > SEARCH_MAX_C) return fail(h, GRL_E_INVALID, f + ": C must be in 2.." + std::to_string(SEARCH_MAX_C));
-    if (K < 1 || K > C) return fail(h, GRL_E_INVALID, f + ": K must be in 1..C");
+// The host's checks of the anchor, the box and the ring.  fn: the C function's name, with which every message starts.
+static int search_check_anchor(grl_handle *h, const char *fn, int anchor) {
+    if (anchor != 0 && anchor != 1) return fail(h, GRL_E_INVALID, std::string(fn) + ": anchor must be 0 (centroid) or 1 (nearest locust)");
     return GRL_OK;
 }
 
@@ -134,10 +71,10 @@ static int search_check_box(grl_handle *h, const char *fn, const double *mean0, 
                             const double *hi, const double *ring) {
     const std::string f(fn);
     int rc;
-    if ((rc = search_check_five(h, fn, "mean0", mean0, false)) || (rc = search_check_five(h, fn, "std0", std0, true)) ||
-        (rc = search_check_five(h, fn, "floor", floor, true)) || (rc = search_check_five(h, fn, "lo", lo, false)) ||
-        (rc = search_check_five(h, fn, "hi", hi, false)))
-        return rc;
+    const struct { const char *noun; const double *v; bool non_negative; } five[] = {
+        {"mean0", mean0, false}, {"std0", std0, true}, {"floor", floor, true}, {"lo", lo, false}, {"hi", hi, false}};
+    for (const auto &v : five)
+        if ((rc = search_check_vector(h, fn, v.noun, v.v, SEARCH_P, nullptr, v.non_negative))) return rc;
     for (int k = 0; k < SEARCH_P; ++k)
         if (lo[k] > hi[k]) return fail(h, GRL_E_INVALID, f + ": lo[" + std::to_string(k) + "] is above hi[" + std::to_string(k) + "]");
     for (int k = 0; k < N_AGENTS * 2; ++k)

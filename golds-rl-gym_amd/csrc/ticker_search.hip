@@ -7,7 +7,7 @@
 //   update    ticker_search_update_kernel, one workgroup: the fit of every candidate (a sequential sum over the envs), its rank, the
 //             refit of mean and std over the elites, and the next generation's table.  After the last generation it builds none.
 // Generation 0's table, mean[0] and std[0] are a function of the arguments alone: the host computes them with the same
-// __host__ __device__ statements (ticker_search_dev.h) and uploads them with the normals.
+// __host__ __device__ statements (ticker_search_dev.h; the clamp and the draw: search_dev.h) and uploads them with the normals.
 // The handle's state is read only, and so are the sweep's last results (h->ksw): the search has buffers of its own.
 #include <limits.h>
 #include <math.h>
@@ -54,7 +54,7 @@ struct TickerSearchParams {
 };
 
 // One workgroup of 1 024 lanes, lane c owning candidate c; lanes past C only keep the barriers (every lane reaches all of them: no
-// early return).  The fit's scores come through LDS in coalesced tiles (search_fit_sum of ticker_search_dev.h; a lane reading its own
+// early return).  The fit's scores come through LDS in coalesced tiles (search_fit_sum of search_dev.h; a lane reading its own
 // row, 8 bytes at a stride of E * 8, made this kernel a sixth of the call at 8 192 envs x 64 candidates).  The other chains are short
 // and latency bound, and there is one workgroup: the kernel exists to keep the generations on the device (measured:
 // profiles/ticker_search_times.json).
@@ -94,21 +94,13 @@ __global__ __launch_bounds__(SEARCH_MAX_C) void ticker_search_update_kernel(Tick
 
 static const char *const TSEARCH_NAMES[TSEARCH_P] = {"up0", "up1", "dn0", "dn1", "band", "lookback"};
 
-static int tsearch_check_six(grl_handle *h, const std::string &f, const char *noun, const double *v, bool non_negative) {
-    for (int k = 0; k < TSEARCH_P; ++k) {
-        const std::string at = f + ": " + noun + "[" + std::to_string(k) + "] (" + TSEARCH_NAMES[k] + ")";
-        if (!std::isfinite(v[k])) return fail(h, GRL_E_INVALID, at + " is not finite");
-        if (non_negative && v[k] < 0) return fail(h, GRL_E_INVALID, at + " is negative");
-    }
-    return GRL_OK;
-}
-
 // the box holds rules only: weights in [0, 1], a band >= 0, a lookback in 0..1023
-static int tsearch_check_box(grl_handle *h, const std::string &f, const double *std0, const double *floor, const double *lo, const double *hi) {
+static int tsearch_check_box(grl_handle *h, const char *fn, const double *std0, const double *floor, const double *lo, const double *hi) {
+    const std::string f(fn);
     int rc;
-    if ((rc = tsearch_check_six(h, f, "std0", std0, true)) || (rc = tsearch_check_six(h, f, "floor", floor, true)) ||
-        (rc = tsearch_check_six(h, f, "lo", lo, false)) || (rc = tsearch_check_six(h, f, "hi", hi, false)))
-        return rc;
+    const struct { const char *noun; const double *v; bool non_negative; } six[] = {{"std0", std0, true}, {"floor", floor, true}, {"lo", lo, false}, {"hi", hi, false}};
+    for (const auto &v : six)
+        if ((rc = search_check_vector(h, fn, v.noun, v.v, TSEARCH_P, TSEARCH_NAMES, v.non_negative))) return rc;
     for (int k = 0; k < TSEARCH_P; ++k) {
         const std::string i = "[" + std::to_string(k) + "]";
         if (lo[k] > hi[k]) return fail(h, GRL_E_INVALID, f + ": lo" + i + " is above hi" + i + " (" + TSEARCH_NAMES[k] + ")");
@@ -133,18 +125,14 @@ int grl_ticker_search(grl_handle *h, const float *start, const double *std0, con
     int rc;
     if ((rc = episode_open(h, fn, GRL_ENV_TICKER, "Ticker", start && std0 && floor && lo && hi && normals))) return rc;
     if (!h->tk.table) return fail(h, GRL_E_INVALID, f + ": the handle has no price table yet (grl_ticker_set_table first)");
-    if ((rc = search_check_counts(h, fn, 0, G, C, K)) || (rc = episode_check_steps(h, fn, max_steps))) return rc;
+    if ((rc = search_check_counts(h, fn, G, C, K)) || (rc = episode_check_steps(h, fn, max_steps))) return rc;
     const char *field = nullptr, *what = ticker_rule_fault(start, &field);
     if (what) return fail(h, GRL_E_INVALID, f + ": start: " + field + " " + what);
-    if ((rc = tsearch_check_box(h, f, std0, floor, lo, hi))) return rc;
+    if ((rc = tsearch_check_box(h, fn, std0, floor, lo, hi))) return rc;
     const size_t E = (size_t)h->E, gc = (size_t)G * C, scores = E * gc;
-    const size_t largest = std::max(scores, gc * TSEARCH_P);
-    if (largest > (size_t)INT32_MAX)
-        return fail(h, GRL_E_INVALID, f + ": an output of " + std::to_string(largest) +
-                                          " elements does not fit in int32 (fewer envs, generations or candidates per call)");
-    for (size_t i = 0; i < gc * TSEARCH_P; ++i)
-        if (!std::isfinite(normals[i])) return fail(h, GRL_E_INVALID, f + ": normals[" + std::to_string(i) + "] is not finite");
-    if ((rc = episode_check_idle(h, fn))) return rc;
+    if ((rc = search_check_int32(h, fn, std::max(scores, gc * TSEARCH_P), "fewer envs, generations or candidates per call")) ||
+        (rc = search_check_normals(h, fn, normals, gc * TSEARCH_P)) || (rc = episode_check_idle(h, fn)))
+        return rc;
     hipSetDevice(h->cfg.device_id);
     TickerSearchState &w = h->kse;
     w.G = 0;
@@ -160,7 +148,7 @@ int grl_ticker_search(grl_handle *h, const float *start, const double *std0, con
 
     double mean0[TSEARCH_P], sd0[TSEARCH_P];      // 1 start, and generation 0's table (2-4)
     for (int k = 0; k < TSEARCH_P; ++k) {
-        mean0[k] = ticker_search_clamp((double)start[k], lo[k], hi[k]);
+        mean0[k] = search_clamp((double)start[k], lo[k], hi[k]);
         sd0[k] = std0[k];
     }
     std::vector<float> table0((size_t)C * TSEARCH_P);

@@ -11,8 +11,9 @@ import numpy as np
 from . import _ffi
 from ._ffi_episode import read_outputs, steps_and_trace
 from ._ffi_swarmrules import MAX_RULES, N_AGENTS, N_LOCUSTS, check_swarm_rules, swarm_rule_offsets, swarm_rules
-from ._ffi_swarmsearch import (DEFAULT_FLOOR, DEFAULT_HI, DEFAULT_LO, DEFAULT_SPREAD, MAX_CANDIDATES, SEARCH_COLS, SEARCH_FIELDS,
+from ._ffi_swarmsearch import (DEFAULT_FLOOR, DEFAULT_HI, DEFAULT_LO, DEFAULT_SPREAD, SEARCH_COLS, SEARCH_FIELDS,
                                swarm_search_candidates, swarm_search_refit, swarm_search_ring, swarm_search_start)
+from ._search import BOX_NAMES, check_box, check_counts, check_normals, check_vectors
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
 
@@ -35,27 +36,13 @@ def _check_cemplan(engine, fn_name, rules, start, horizon, replan, generations, 
     H, K = int(horizon), int(replan)
     if H < 1 or K < 1 or K > H:
         raise ValueError("%s: 1 <= replan <= horizon is required, got horizon %d, replan %d" % (fn_name, H, K))
-    G, Cn, M = int(generations), int(candidates), int(elites)
-    if G < 1 or not 2 <= Cn <= MAX_CANDIDATES or not 1 <= M <= Cn:
-        raise ValueError("%s: generations >= 1, 2 <= candidates <= %d and 1 <= elites <= candidates are required, got %d, %d, %d"
-                         % (fn_name, MAX_CANDIDATES, G, Cn, M))
-    five = []
-    for name, v in (("spread", spread), ("floor", floor), ("lo", lo), ("hi", hi)):
-        a = np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1))
-        if a.shape != (5,) or not np.isfinite(a).all():
-            raise ValueError("%s: %s must be 5 finite numbers over %s" % (fn_name, name, (SEARCH_FIELDS,)))
-        five.append(a)
-    spread, floor, lo, hi = five
-    if (spread < 0).any() or (floor < 0).any() or (lo > hi).any():
-        raise ValueError("%s: spread >= 0, floor >= 0 and lo <= hi are required" % fn_name)
+    G, Cn, M = check_counts(fn_name, generations, candidates, elites)
+    spread, floor, lo, hi = check_vectors(fn_name, BOX_NAMES, (spread, floor, lo, hi), None, SEARCH_FIELDS)
+    check_box(fn_name, spread, floor, lo, hi)
     T, t_env = steps_and_trace(engine, fn_name, max_steps, trace_env)
     D = (T + K - 1) // K
-    if normals is None:
-        normals = np.random.default_rng(seed).standard_normal((D, G, Cn, 5))
-    z = np.ascontiguousarray(np.asarray(normals, np.float64))
-    if z.shape != (D, G, Cn, 5) or not np.isfinite(z).all():
-        raise ValueError("%s: normals must be (decisions, generations, candidates, 5) finite numbers with decisions = "
-                         "ceil(max_steps / replan) = %d, got shape %s" % (fn_name, D, z.shape))
+    z = check_normals(fn_name, normals, seed, (D, G, Cn, 5),
+                      "(decisions, generations, candidates, 5) finite numbers with decisions = ceil(max_steps / replan) = %d" % D)
     return r, start, spread, floor, lo, hi, H, K, G, Cn, M, z, T, t_env, D
 
 

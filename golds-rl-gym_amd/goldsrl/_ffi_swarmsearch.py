@@ -1,13 +1,16 @@
 """ctypes binding of the cross-entropy search over the five real numbers of a Swarm feedback rule (C ABI and the scheme, statement
 by statement: include/goldsrl_swarmsearch.h): every generation of every candidate on every env of the engine enqueued in one call.
-swarm_search_candidates and swarm_search_refit are the numpy statements of the scheme, device-free; swarm_search_host is the same
-search composed on the host from them and grl_swarm_rules: the documented slow path, and the oracle the device is held to."""
+swarm_search_candidates and swarm_search_refit are the numpy statements of the scheme, device-free (what of them knows nothing of
+Swarm is _search.py's, shared with the Ticker search); swarm_search_host is the same search composed on the host from them and
+grl_swarm_rules: the documented slow path, and the oracle the device is held to."""
 import ctypes as C
 
 import numpy as np
 
 from . import _ffi
 from ._ffi_episode import read_outputs, steps_and_trace
+from ._search import (BOX_NAMES, MAX_CANDIDATES, check_box, check_counts, check_normals, check_vectors, search_clamp, search_draw, search_refit,  # noqa: F401
+                      search_summary)
 from ._ffi_swarmrules import N_AGENTS, check_swarm_rules, swarm_rule_offsets, swarm_rules
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
@@ -20,7 +23,6 @@ SWARMSEARCH_SIGNATURES = {
 
 SEARCH_FIELDS = ("cancel", "gain", "off_x", "off_y", "radius")
 SEARCH_COLS = (0, 1, 3, 4, 5)                       # where they stand in a six-number row (cancel, gain, anchor, off_x, off_y, radius)
-MAX_CANDIDATES = 1024
 DEFAULT_SPREAD = (0.0, 2.0, 0.5, 0.5, 0.3)
 DEFAULT_FLOOR = (0.0, 0.05, 0.01, 0.01, 0.01)
 DEFAULT_LO = (0.0, 0.0, -4.0, -4.0, 0.0)
@@ -34,31 +36,17 @@ def swarm_search_ring():
     return np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=-1))
 
 
-def _first_max(a, b):
-    return np.where(a >= b, a, b)                   # the first operand wins a tie, as the device's select
-
-
-def _first_min(a, b):
-    return np.where(a <= b, a, b)
-
-
 def swarm_search_start(mean0, lo, hi):
     """Step 1 of the scheme: the start clamped into the box."""
-    m, lo, hi = (np.asarray(v, np.float64) for v in (mean0, lo, hi))
-    return _first_min(_first_max(m, lo), hi)
+    return search_clamp(*(np.asarray(v, np.float64) for v in (mean0, lo, hi)))
 
 
 def swarm_search_candidates(mean, std, z, lo, hi, anchor, incumbent):
     """Steps 2 to 4 of the scheme for one generation.  mean, std, lo, hi: (5,); z: (C, 5) normals, row 0 ignored; incumbent: the
     six-number row that is candidate 0.  Returns (candidates (C, 6), offsets (C, 10, 2)) float64."""
-    mean, std, lo, hi = (np.asarray(v, np.float64) for v in (mean, std, lo, hi))
     z = np.asarray(z, np.float64)
-    v = std[None] * z
-    v = mean[None] + v
-    v = _first_max(v, lo[None])
-    v = _first_min(v, hi[None])
     cand = np.empty((z.shape[0], 6), np.float64)
-    cand[:, SEARCH_COLS] = v
+    cand[:, SEARCH_COLS] = search_draw(mean, std, z, lo, hi)
     cand[:, 2] = np.float64(anchor)
     cand[0] = np.asarray(incumbent, np.float64)
     ring = swarm_search_ring()
@@ -73,59 +61,19 @@ def swarm_search_candidates(mean, std, z, lo, hi, anchor, incumbent):
 def swarm_search_refit(fit, candidates, elites, floor):
     """Steps 7 and 8 of the scheme.  fit (C,), candidates (C, 6).  Returns (order (C,) int32: by fit descending, a tie to the smaller
     index; mean (5,); std (5,)), the two sequential chains over the K elites in rank order."""
-    fit, cand = np.asarray(fit, np.float64), np.asarray(candidates, np.float64)
-    K = int(elites)
-    order = np.array(sorted(range(len(fit)), key=lambda c: (-fit[c], c)), np.int32)
-    p = cand[order[:K]][:, SEARCH_COLS]                                  # (K, 5)
-    kk = np.float64(K)
-    m = np.zeros(5, np.float64)
-    for i in range(K):
-        m = m + p[i]
-    mean = m / kk
-    s = np.zeros(5, np.float64)
-    for i in range(K):
-        d = p[i] - mean
-        q = d * d
-        s = s + q
-    v = s / kk
-    sd = np.sqrt(v)
-    return order, mean, _first_max(sd, np.asarray(floor, np.float64))
+    return search_refit(fit, np.asarray(candidates, np.float64)[:, SEARCH_COLS], int(elites), floor)
 
 
 def _check_search(engine, fn_name, start, spread, floor, lo, hi, generations, candidates, elites, seed, normals, max_steps):
     if engine.kind != _ffi.ENV_SWARM:
         raise ValueError("%s: the engine is not a Swarm engine" % fn_name)
     start = check_swarm_rules(np.asarray(start, np.float64).reshape(1, -1))[0]
-    G, Cn, K = int(generations), int(candidates), int(elites)
-    if G < 1 or not 2 <= Cn <= MAX_CANDIDATES or not 1 <= K <= Cn:
-        raise ValueError("%s: generations >= 1, 2 <= candidates <= %d and 1 <= elites <= candidates are required, got %d, %d, %d"
-                         % (fn_name, MAX_CANDIDATES, G, Cn, K))
-    five = []
-    for name, v in (("spread", spread), ("floor", floor), ("lo", lo), ("hi", hi)):
-        a = np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1))
-        if a.shape != (5,) or not np.isfinite(a).all():
-            raise ValueError("%s: %s must be 5 finite numbers over %s" % (fn_name, name, (SEARCH_FIELDS,)))
-        five.append(a)
-    spread, floor, lo, hi = five
-    if (spread < 0).any() or (floor < 0).any() or (lo > hi).any():
-        raise ValueError("%s: spread >= 0, floor >= 0 and lo <= hi are required" % fn_name)
-    if normals is None:
-        normals = np.random.default_rng(seed).standard_normal((G, Cn, 5))
-    z = np.ascontiguousarray(np.asarray(normals, np.float64))
-    if z.shape != (G, Cn, 5) or not np.isfinite(z).all():
-        raise ValueError("%s: normals must be (generations, candidates, 5) finite numbers, got shape %s" % (fn_name, z.shape))
+    G, Cn, K = check_counts(fn_name, generations, candidates, elites)
+    spread, floor, lo, hi = check_vectors(fn_name, BOX_NAMES, (spread, floor, lo, hi), None, SEARCH_FIELDS)
+    check_box(fn_name, spread, floor, lo, hi)
+    z = check_normals(fn_name, normals, seed, (G, Cn, 5), "(generations, candidates, 5) finite numbers")
     T, _ = steps_and_trace(engine, fn_name, max_steps)
     return start, spread, floor, lo, hi, G, Cn, K, z, T
-
-
-def _summary(out):
-    """best_rule, best_fit and best_per_generation from the seven outputs."""
-    G = out["fit"].shape[0]
-    first = out["order"][:, 0]
-    out["best_per_generation"] = out["fit"][np.arange(G), first]
-    out["best_rule"] = tuple(float(v) for v in out["candidates"][G - 1, first[G - 1]])
-    out["best_fit"] = float(out["best_per_generation"][G - 1])
-    return out
 
 
 def swarm_search(engine, start, spread=DEFAULT_SPREAD, floor=DEFAULT_FLOOR, lo=DEFAULT_LO, hi=DEFAULT_HI, generations=8, candidates=32,
@@ -149,7 +97,7 @@ def swarm_search(engine, start, spread=DEFAULT_SPREAD, floor=DEFAULT_FLOOR, lo=D
                        (G, Cn))
     out.update(read_outputs(engine, lib.grl_swarm_search_read, (("scores", np.float64, (G, Cn)),), (engine.E,)))
     out.update(read_outputs(engine, lib.grl_swarm_search_read, (("mean", np.float64, (5,)), ("std", np.float64, (5,))), (G + 1,)))
-    return _summary(out)
+    return search_summary(out)
 
 
 def swarm_search_host(engine, start, spread=DEFAULT_SPREAD, floor=DEFAULT_FLOOR, lo=DEFAULT_LO, hi=DEFAULT_HI, generations=8, candidates=32,
@@ -182,4 +130,4 @@ def swarm_search_host(engine, start, spread=DEFAULT_SPREAD, floor=DEFAULT_FLOOR,
         out["candidates"][g], out["offsets"][g] = cand, off
         out["order"][g], out["mean"][g + 1], out["std"][g + 1] = swarm_search_refit(out["fit"][g], cand, K, floor)
         incumbent = cand[out["order"][g, 0]].copy()
-    return _summary(out)
+    return search_summary(out)

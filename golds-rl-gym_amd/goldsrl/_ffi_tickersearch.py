@@ -1,7 +1,8 @@
 """ctypes binding of the cross-entropy search over the six numbers of a Ticker rule (C ABI and the scheme, statement by statement:
 include/goldsrl_tickersearch.h): every generation of every candidate on every env of the engine enqueued in one call.
 ticker_search_start, ticker_search_rows, ticker_search_candidates and ticker_search_refit are the numpy statements of the scheme,
-device-free; ticker_search_host is the same search composed on the host from them and grl_ticker_sweep: the documented slow path,
+device-free (the clamp, the draw, the rank and the refit chains are _search.py's, shared with the Swarm searches);
+ticker_search_host is the same search composed on the host from them and grl_ticker_sweep: the documented slow path,
 and the oracle the device is held to.
 
 The defaults (ticker_search_defaults): a spread of 0.2 on the four weights, 0.1 on the band and max(3, lookback / 4) on the lookback,
@@ -14,6 +15,8 @@ import numpy as np
 
 from . import _ffi
 from ._ffi_episode import read_outputs, steps_and_trace
+from ._search import (BOX_NAMES, MAX_CANDIDATES, check_box, check_counts, check_normals, check_vectors, search_clamp, search_draw,  # noqa: F401
+                      search_rank as ticker_search_rank, search_refit, search_summary)
 from ._ffi_tickersweep import RULE_FIELDS, WINDOW, check_ticker_rules, ticker_sweep
 
 _P, _I, _SZ = C.c_void_p, C.c_int32, C.c_size_t
@@ -24,7 +27,6 @@ TICKERSEARCH_SIGNATURES = {
     "grl_ticker_search_read": (C.c_int, [_P, C.c_char_p, _P, _SZ]),
 }
 
-MAX_CANDIDATES = 1024
 DEFAULT_SPREAD = (0.2, 0.2, 0.2, 0.2, 0.1, 3.0)       # the lookback's grows with the start's: ticker_search_defaults
 DEFAULT_FLOOR = (0.01, 0.01, 0.01, 0.01, 0.005, 0.5)
 DEFAULT_LO = (0.0, 0.0, 0.0, 0.0, 0.0, 1.0)
@@ -44,18 +46,9 @@ def ticker_search_defaults(start):
     return spread, floor, lo, hi
 
 
-def _first_max(a, b):
-    return np.where(a >= b, a, b)                   # the first operand wins a tie, as the device's select
-
-
-def _first_min(a, b):
-    return np.where(a <= b, a, b)
-
-
 def ticker_search_start(start, lo, hi):
     """Statement 1: the float32 start widened and clamped into the box."""
-    m = np.asarray(start, np.float32).astype(np.float64)
-    return _first_min(_first_max(m, np.asarray(lo, np.float64)), np.asarray(hi, np.float64))
+    return search_clamp(np.asarray(start, np.float32).astype(np.float64), np.asarray(lo, np.float64), np.asarray(hi, np.float64))
 
 
 def ticker_search_rows(v, return_corrected=False):
@@ -83,12 +76,7 @@ def ticker_search_rows(v, return_corrected=False):
 def ticker_search_candidates(mean, std, z, lo, hi, incumbent=None, return_corrected=False):
     """Statements 2 to 4 for one generation.  mean, std, lo, hi: (6,); z: (C, 6) normals, row 0 ignored; incumbent: the float32 row
     that is candidate 0, or None in generation 0 (statement 3 of the mean).  Returns the (C, 6) float32 table."""
-    mean, std, lo, hi = (np.asarray(v, np.float64) for v in (mean, std, lo, hi))
-    z = np.asarray(z, np.float64)
-    v = std[None] * z
-    v = mean[None] + v
-    v = _first_max(v, lo[None])
-    v = _first_min(v, hi[None])
+    v = search_draw(mean, std, z, lo, hi)
     if incumbent is None:
         v[0] = mean
     rows, corrected = ticker_search_rows(v, True)
@@ -98,69 +86,24 @@ def ticker_search_candidates(mean, std, z, lo, hi, incumbent=None, return_correc
     return (rows, corrected) if return_corrected else rows
 
 
-def ticker_search_rank(fit):
-    """Statement 7: the candidates by fit descending, a tie going to the smaller index.  (C,) int32."""
-    fit = np.asarray(fit, np.float64)
-    return np.array(sorted(range(len(fit)), key=lambda c: (-fit[c], c)), np.int32)
-
-
 def ticker_search_refit(fit, rows, elites, floor):
     """Statements 7 and 8.  fit (C,), rows (C, 6) float32.  Returns (order (C,) int32, mean (6,), std (6,)), the two sequential
     chains over the K elites in rank order."""
-    order = ticker_search_rank(fit)
-    K = int(elites)
-    p = np.asarray(rows, np.float32)[order[:K]].astype(np.float64)          # (K, 6)
-    kk = np.float64(K)
-    m = np.zeros(p.shape[1], np.float64)
-    for i in range(K):
-        m = m + p[i]
-    mean = m / kk
-    s = np.zeros(p.shape[1], np.float64)
-    for i in range(K):
-        d = p[i] - mean
-        q = d * d
-        s = s + q
-    v = s / kk
-    sd = np.sqrt(v)
-    return order, mean, _first_max(sd, np.asarray(floor, np.float64))
+    return search_refit(fit, np.asarray(rows, np.float32).astype(np.float64), int(elites), floor)
 
 
 def _check_search(engine, fn_name, start, spread, floor, lo, hi, generations, candidates, elites, seed, normals, max_steps):
     if engine.kind != _ffi.ENV_TICKER:
         raise ValueError("%s: the engine is not a Ticker engine" % fn_name)
     start = check_ticker_rules(np.asarray(start, np.float32).reshape(1, -1))[0]
-    G, Cn, K = int(generations), int(candidates), int(elites)
-    if G < 1 or not 2 <= Cn <= MAX_CANDIDATES or not 1 <= K <= Cn:
-        raise ValueError("%s: generations >= 1, 2 <= candidates <= %d and 1 <= elites <= candidates are required, got %d, %d, %d"
-                         % (fn_name, MAX_CANDIDATES, G, Cn, K))
-    six = []
-    for name, v, default in zip(("spread", "floor", "lo", "hi"), (spread, floor, lo, hi), ticker_search_defaults(start)):
-        a = default if v is None else np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1))
-        if a.shape != (6,) or not np.isfinite(a).all():
-            raise ValueError("%s: %s must be 6 finite numbers over %s" % (fn_name, name, (RULE_FIELDS,)))
-        six.append(a)
-    spread, floor, lo, hi = six
-    if (spread < 0).any() or (floor < 0).any() or (lo > hi).any():
-        raise ValueError("%s: spread >= 0, floor >= 0 and lo <= hi are required" % fn_name)
+    G, Cn, K = check_counts(fn_name, generations, candidates, elites)
+    spread, floor, lo, hi = check_vectors(fn_name, BOX_NAMES, (spread, floor, lo, hi), ticker_search_defaults(start), RULE_FIELDS)
+    check_box(fn_name, spread, floor, lo, hi)
     if (lo < 0).any() or (hi[:4] > 1).any() or hi[5] > WINDOW - 1:
         raise ValueError("%s: the box must hold rules only: weights in [0, 1], a band >= 0, a lookback in 0..%d" % (fn_name, WINDOW - 1))
-    if normals is None:
-        normals = np.random.default_rng(seed).standard_normal((G, Cn, 6))
-    z = np.ascontiguousarray(np.asarray(normals, np.float64))
-    if z.shape != (G, Cn, 6) or not np.isfinite(z).all():
-        raise ValueError("%s: normals must be (generations, candidates, 6) finite numbers, got shape %s" % (fn_name, z.shape))
+    z = check_normals(fn_name, normals, seed, (G, Cn, 6), "(generations, candidates, 6) finite numbers")
     T, _ = steps_and_trace(engine, fn_name, max_steps)
     return start, spread, floor, lo, hi, G, Cn, K, z, T
-
-
-def _summary(out):
-    """best_rule, best_fit and best_per_generation from the six outputs."""
-    G = out["fit"].shape[0]
-    first = out["order"][:, 0]
-    out["best_per_generation"] = out["fit"][np.arange(G), first]
-    out["best_rule"] = tuple(float(v) for v in out["candidates"][G - 1, first[G - 1]])
-    out["best_fit"] = float(out["best_per_generation"][G - 1])
-    return out
 
 
 def ticker_search(engine, start, spread=None, floor=None, lo=None, hi=None, generations=8, candidates=32, elites=8, seed=0, normals=None,
@@ -181,7 +124,7 @@ def ticker_search(engine, start, spread=None, floor=None, lo=None, hi=None, gene
                        (("candidates", np.float32, (6,)), ("scores", np.float64, (engine.E,)), ("fit", np.float64, ()), ("order", np.int32, ())),
                        (G, Cn))
     out.update(read_outputs(engine, lib.grl_ticker_search_read, (("mean", np.float64, (6,)), ("std", np.float64, (6,))), (G + 1,)))
-    return _summary(out)
+    return search_summary(out)
 
 
 def ticker_search_host(engine, start, spread=None, floor=None, lo=None, hi=None, generations=8, candidates=32, elites=8, seed=0,
@@ -210,4 +153,4 @@ def ticker_search_host(engine, start, spread=None, floor=None, lo=None, hi=None,
         out["candidates"][g] = rows
         out["order"][g], out["mean"][g + 1], out["std"][g + 1] = ticker_search_refit(out["fit"][g], rows, K, floor)
         incumbent = rows[out["order"][g, 0]].copy()
-    return _summary(out)
+    return search_summary(out)
