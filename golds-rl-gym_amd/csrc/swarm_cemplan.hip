@@ -203,17 +203,12 @@ int grl_swarm_cemplan(grl_handle *h, const double *rules_host, const double *off
         (rc = episode_reserve(h, w.cap_gen, gen, {buf(w.mean, SEARCH_P), buf(w.std, SEARCH_P)})))
         return rc;
     if (R) {
-        GRL_HIP(h, hipMemcpyAsync(w.lib_rules, rules_host, R * 3 * 8, hipMemcpyHostToDevice, h->stream));
-        GRL_HIP(h, hipMemcpyAsync(w.lib_offsets, offsets_host, R * N_AGENTS * 2 * 8, hipMemcpyHostToDevice, h->stream));
+        if ((rc = swarm_upload_rule_table(h, w.lib_rules, w.lib_offsets, rules_host, offsets_host, R))) return rc;
         GRL_HIP(h, hipMemsetAsync(w.lib_scores, 0, lib * 8, h->stream));
     }
     GRL_HIP(h, hipMemcpyAsync(w.normals, normals, zn * SEARCH_P * 8, hipMemcpyHostToDevice, h->stream));
-    // the working copy starts as the handle's positions; the call's clock at zero
-    GRL_HIP(h, hipMemcpyAsync(w.x, h->sw.x, E * N_LOCUSTS * 2 * 8, hipMemcpyDeviceToDevice, h->stream));
-    GRL_HIP(h, hipMemcpyAsync(w.xa, h->sw.xa, E * N_AGENTS * 2 * 8, hipMemcpyDeviceToDevice, h->stream));
-    GRL_HIP(h, hipMemsetAsync(w.length, 0, E * 4, h->stream));
+    if ((rc = swarm_start_copy(h, w.x, w.xa, w.length, w.finished))) return rc;
     GRL_HIP(h, hipMemsetAsync(w.pick, 0, E * 4, h->stream));
-    GRL_HIP(h, hipMemsetAsync(w.finished, 0, E, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.cur_mean, 0, E * SEARCH_P * 8, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.one, 0, E * 8, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.table_rules, 0, table * 3 * 8, h->stream));
@@ -228,11 +223,7 @@ int grl_swarm_cemplan(grl_handle *h, const double *rules_host, const double *off
     GRL_HIP(h, hipMemsetAsync(w.order, 0, gc * 4, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.mean, 0, gen * SEARCH_P * 8, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.std, 0, gen * SEARCH_P * 8, h->stream));
-    if (act) GRL_HIP(h, hipMemsetAsync(w.actions, 0, act * N_AGENTS * 2 * 8, h->stream));
-    if (trace) {
-        GRL_HIP(h, hipMemsetAsync(w.trace_x, 0, trace * N_LOCUSTS * 2 * 8, h->stream));
-        GRL_HIP(h, hipMemsetAsync(w.trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
-    }
+    if ((rc = swarm_zero_kept(h, w.actions, act, w.trace_x, w.trace_xa, trace))) return rc;
 
     CemParams S{};
     S.z = w.normals; S.lib_rules = w.lib_rules; S.lib_offsets = w.lib_offsets; S.length = w.length; S.finished = w.finished;

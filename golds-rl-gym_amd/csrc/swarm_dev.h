@@ -245,4 +245,24 @@ static void swarm_start_state(const grl_handle *h, P &p) {
     p.x = h->sw.x; p.xa = h->sw.xa; p.pnoise = h->sw.pnoise; p.anoise = h->sw.anoise; p.elapsed = h->elapsed;
 }
 
+// A call's own copy of the positions and its own clock (the planners): the copy starts as the handle's positions, the clock at zero.
+static int swarm_start_copy(grl_handle *h, double *x, double *xa, int32_t *length, uint8_t *finished) {
+    const size_t E = (size_t)h->E;
+    GRL_HIP(h, hipMemcpyAsync(x, h->sw.x, E * N_LOCUSTS * 2 * 8, hipMemcpyDeviceToDevice, h->stream));
+    GRL_HIP(h, hipMemcpyAsync(xa, h->sw.xa, E * N_AGENTS * 2 * 8, hipMemcpyDeviceToDevice, h->stream));
+    GRL_HIP(h, hipMemsetAsync(length, 0, E * 4, h->stream));
+    GRL_HIP(h, hipMemsetAsync(finished, 0, E, h->stream));
+    return GRL_OK;
+}
+
+// The kept actions (act rows; 0: none kept) and the traced env's positions (trace rows; 0: no env traced) read as zero past a unit's length.
+static int swarm_zero_kept(grl_handle *h, double *actions, size_t act, double *trace_x, double *trace_xa, size_t trace) {
+    if (act) GRL_HIP(h, hipMemsetAsync(actions, 0, act * N_AGENTS * 2 * 8, h->stream));
+    if (trace) {
+        GRL_HIP(h, hipMemsetAsync(trace_x, 0, trace * N_LOCUSTS * 2 * 8, h->stream));
+        GRL_HIP(h, hipMemsetAsync(trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
+    }
+    return GRL_OK;
+}
+
 }  // namespace grl

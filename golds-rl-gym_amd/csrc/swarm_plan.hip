@@ -58,21 +58,13 @@ int grl_swarm_plan(grl_handle *h, const double *rules_host, const double *offset
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_x, N_LOCUSTS * 2), buf(w.trace_xa, N_AGENTS * 2)})) ||
         (rc = episode_reserve(h, w.cap_dec, dec, {buf(w.choices)})) || (rc = episode_reserve(h, w.cap_scores, scores, {buf(w.scores)})))
         return rc;
-    GRL_HIP(h, hipMemcpyAsync(w.rules, rules_host, (size_t)n_rules * 3 * 8, hipMemcpyHostToDevice, h->stream));
-    GRL_HIP(h, hipMemcpyAsync(w.offsets, offsets_host, (size_t)n_rules * N_AGENTS * 2 * 8, hipMemcpyHostToDevice, h->stream));
-    // the working copy starts as the handle's positions; the plan's clock at zero
-    GRL_HIP(h, hipMemcpyAsync(w.x, h->sw.x, E * N_LOCUSTS * 2 * 8, hipMemcpyDeviceToDevice, h->stream));
-    GRL_HIP(h, hipMemcpyAsync(w.xa, h->sw.xa, E * N_AGENTS * 2 * 8, hipMemcpyDeviceToDevice, h->stream));
-    GRL_HIP(h, hipMemsetAsync(w.length, 0, E * 4, h->stream));
-    GRL_HIP(h, hipMemsetAsync(w.finished, 0, E, h->stream));
+    if ((rc = swarm_upload_rule_table(h, w.rules, w.offsets, rules_host, offsets_host, n_rules)) ||
+        (rc = swarm_start_copy(h, w.x, w.xa, w.length, w.finished)))
+        return rc;
     GRL_HIP(h, hipMemsetAsync(w.rewards, 0, steps * 8, h->stream));      // rows are defined up to the env's length; the rest reads as zero
     GRL_HIP(h, hipMemsetAsync(w.scores, 0, scores * 8, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.choices, 0xFF, dec * 4, h->stream));     // -1 past the env's last decision
-    if (act) GRL_HIP(h, hipMemsetAsync(w.actions, 0, act * N_AGENTS * 2 * 8, h->stream));
-    if (trace) {
-        GRL_HIP(h, hipMemsetAsync(w.trace_x, 0, trace * N_LOCUSTS * 2 * 8, h->stream));
-        GRL_HIP(h, hipMemsetAsync(w.trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
-    }
+    if ((rc = swarm_zero_kept(h, w.actions, act, w.trace_x, w.trace_xa, trace))) return rc;
     PlanParams P{};
     swarm_start_state(h, P);
     P.x = w.x; P.xa = w.xa; P.wx = w.x; P.wxa = w.xa;

@@ -171,10 +171,7 @@ int grl_swarm_replay(grl_handle *h, const void *actions_host, int32_t actions_f6
     GRL_HIP(h, hipMemcpyAsync(w.actions, actions_host, act_bytes, hipMemcpyHostToDevice, h->stream));
     if (seq_len_host) GRL_HIP(h, hipMemcpyAsync(w.seq_len, seq_len_host, (size_t)n_seq * 4, hipMemcpyHostToDevice, h->stream));
     GRL_HIP(h, hipMemsetAsync(w.rewards, 0, steps * 8, h->stream));      // rows are defined up to the pair's length; the rest reads as zero
-    if (trace) {
-        GRL_HIP(h, hipMemsetAsync(w.trace_x, 0, trace * N_LOCUSTS * 2 * 8, h->stream));
-        GRL_HIP(h, hipMemsetAsync(w.trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
-    }
+    if ((rc = swarm_zero_kept(h, nullptr, 0, w.trace_x, w.trace_xa, trace))) return rc;      // a replay keeps no actions: they are its input
     ReplayParams P{};
     swarm_start_state(h, P);
     P.actions = w.actions; P.seq_len = seq_len_host ? w.seq_len : nullptr;

@@ -82,4 +82,11 @@ static int swarm_check_rule_table(grl_handle *h, const char *fn, const double *r
     return GRL_OK;
 }
 
+// a checked table onto the device, on the handle's stream
+static int swarm_upload_rule_table(grl_handle *h, double *rules, double *offsets, const double *rules_host, const double *offsets_host, size_t n_rules) {
+    GRL_HIP(h, hipMemcpyAsync(rules, rules_host, n_rules * 3 * 8, hipMemcpyHostToDevice, h->stream));
+    GRL_HIP(h, hipMemcpyAsync(offsets, offsets_host, n_rules * N_AGENTS * 2 * 8, hipMemcpyHostToDevice, h->stream));
+    return GRL_OK;
+}
+
 }  // namespace grl

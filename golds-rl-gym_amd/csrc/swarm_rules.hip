@@ -173,14 +173,9 @@ int grl_swarm_rules(grl_handle *h, const double *rules_host, const double *offse
         (rc = episode_reserve(h, w.cap_act, act, {buf(w.actions, N_AGENTS * 2)})) ||
         (rc = episode_reserve(h, w.cap_trace, trace, {buf(w.trace_x, N_LOCUSTS * 2), buf(w.trace_xa, N_AGENTS * 2)})))
         return rc;
-    GRL_HIP(h, hipMemcpyAsync(w.rules, rules_host, (size_t)n_rules * 3 * 8, hipMemcpyHostToDevice, h->stream));
-    GRL_HIP(h, hipMemcpyAsync(w.offsets, offsets_host, (size_t)n_rules * N_AGENTS * 2 * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = swarm_upload_rule_table(h, w.rules, w.offsets, rules_host, offsets_host, n_rules))) return rc;
     GRL_HIP(h, hipMemsetAsync(w.rewards, 0, steps * 8, h->stream));      // rows are defined up to the pair's length; the rest reads as zero
-    if (act) GRL_HIP(h, hipMemsetAsync(w.actions, 0, act * N_AGENTS * 2 * 8, h->stream));
-    if (trace) {
-        GRL_HIP(h, hipMemsetAsync(w.trace_x, 0, trace * N_LOCUSTS * 2 * 8, h->stream));
-        GRL_HIP(h, hipMemsetAsync(w.trace_xa, 0, trace * N_AGENTS * 2 * 8, h->stream));
-    }
+    if ((rc = swarm_zero_kept(h, w.actions, act, w.trace_x, w.trace_xa, trace))) return rc;
     RulesParams P{};
     swarm_start_state(h, P);
     P.rules = w.rules; P.offsets = w.offsets;
