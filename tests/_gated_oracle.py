@@ -57,7 +57,8 @@ def init(seed=3):
 
 
 def _sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    with np.errstate(over="ignore"):          # exp(-x) = inf far below 0: 1 / inf = 0 is the limit, the same bits without the warning
+        return 1.0 / (1.0 + np.exp(-x))
 
 
 def _softplus(x):
@@ -120,7 +121,8 @@ def losses(p, states, windows, choices, raw, adv, targets, weights=None, mult=1.
     cp = mult * w * np.asarray(adv, np.float64)
     pl = np.sum(nll * cp[:, None])
     vl = np.sum(mult * w * 0.5 * (values - np.asarray(targets, np.float64)) ** 2 / scale)
-    ent = -(probs * np.log(probs)).sum(-1) + 0.5 + LOG_SQRT_2PI + np.log(sc)
+    plogp = np.where(probs > 0, probs * np.log(np.where(probs > 0, probs, 1.0)), 0.0)      # 0 log 0 = 0 (a float64 softmax can underflow)
+    ent = -plogp.sum(-1) + 0.5 + LOG_SQRT_2PI + np.log(sc)
     ent_mean = np.sum(w[:, None] * ent) / (2.0 * np.sum(w)) if np.sum(w) > 0 else 0.0
     return pl, vl, ent_mean
 

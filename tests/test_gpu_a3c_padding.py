@@ -1,4 +1,4 @@
-"""GPU: the lanes a 64-sample workgroup of the two A3C nets has past the last sample are inert (csrc/net_a3c_core.inc: the shared trunk
+"""GPU: the lanes a 64-sample workgroup of the three A3C nets has past the last sample are inert (csrc/net_a3c_core.inc: the shared trunk
 reads a real sample's rows for them, the kernels give them weight 0).  70 samples are one full group and a group of 6; the same 70
 followed by 58 OTHER samples of weight 0 fill both groups.  Both runs are two workgroups with the same slab order, padded and
 weight-0 lanes only ever add +-0 to a sum, so everything the 70 produce is equal bit for bit -- no tolerance."""
@@ -10,11 +10,16 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N, FULL, R = 70, 128, 5
+N, FULL, R, K = 70, 128, 5, 64
 
 
 def _make(kind):
-    from goldsrl import _ffi, _ffi_gated, _ffi_gauss
+    from goldsrl import _ffi, _ffi_discrete, _ffi_gated, _ffi_gauss
+    if kind == "discrete":
+        eng = _ffi.Engine(_ffi.ENV_SOLOW, 4, seed=7)
+        net = _ffi_discrete.DiscreteNet(eng, rnn_length=R, max_samples=FULL, num_choices=K)
+        net.set_params(_ffi_discrete.default_init_discrete(5, K))
+        return eng, net, 2, 2, 1
     if kind == "gated":
         eng = _ffi.Engine(_ffi.ENV_TICKER, 4, seed=7)
         eng.ticker_set_table(np.load(os.path.join(ROOT, "tests", "golden", "ticker.npz"))["matrix"])
@@ -28,7 +33,7 @@ def _make(kind):
     return eng, net, sizes["static_size"], sizes["temporal_size"], sizes["num_actions"]
 
 
-@pytest.mark.parametrize("kind", ["gated", "solow", "trade"])
+@pytest.mark.parametrize("kind", ["gated", "solow", "trade", "discrete"])
 def test_lanes_past_the_last_sample_are_inert(kind):
     eng, net, S0, D, A = _make(kind)
     rng = np.random.RandomState(11)
@@ -42,6 +47,9 @@ def test_lanes_past_the_last_sample_are_inert(kind):
     wt[N - 1] = 1.0
     wt[N:] = 0.0
     extra = (rng.randint(0, 3, size=(FULL, 2)).astype(np.int32),) if kind == "gated" else ()
+    heads = extra + (raw,)
+    if kind == "discrete":      # its only head input is the choice
+        heads = (rng.randint(0, K, size=FULL).astype(np.int32),)
 
     few, full = net.predict(states[:N], win[:N]), net.predict(states, win)
     assert sorted(few) == sorted(full)
@@ -49,7 +57,7 @@ def test_lanes_past_the_last_sample_are_inert(kind):
         assert np.array_equal(few[k], full[k][:N]), k
 
     def train(n):
-        st = net.train(states[:n], win[:n], *[a[:n] for a in extra + (raw, adv, tgt)], weights=wt[:n], apply_update=False)
+        st = net.train(states[:n], win[:n], *[a[:n] for a in heads + (adv, tgt)], weights=wt[:n], apply_update=False)
         return st, net.get_grads("policy"), net.get_grads("value")
 
     (st_few, gp_few, gv_few), (st_full, gp_full, gv_full) = train(N), train(FULL)

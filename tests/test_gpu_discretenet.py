@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import _a3c_replay_checks as RC
 import _grid_oracle as D
 
 pytestmark = pytest.mark.gpu
@@ -223,14 +224,10 @@ def test_rollout_replay(E):
     r = _read(net)
     assert net.get_action_counter() == 1000 + T
     assert r["choices"].dtype == np.int32 and r["dones"][cap - 1].all() and not r["dones"][:cap - 1].any()
-    grid = D.grid(K)
-    # the sampler on the device's OWN float32 probabilities and the oracle's u: exact.  (On the oracle's probabilities a u within
-    # 1e-7 of a cumulative sum would make a correct kernel fail.)
-    for t in range(T):
-        u = D.draws(eng.cfg.seed, np.arange(E) + 1000, 1000 + t)
-        want = np.array([D.choose(r["probs"][t, e], u[e]) for e in range(E)])
-        assert np.array_equal(r["choices"][t], want), t
-    assert np.array_equal(r["actions"], grid[r["choices"]].astype(np.float32))
+    # the sampler on the device's OWN float32 probabilities and the oracle's u: exact; the actions are the grid's points
+    # (tests/_a3c_replay_checks.py)
+    assert r["choices"].shape == (T, E)
+    RC.discrete_acting(r, eng.cfg.seed, np.arange(E) + 1000, 1000, K)
     assert len(np.unique(r["choices"])) > K // 2
     # probs and values against the oracle on the recorded inputs, and bit-equal to predict on them
     p = _as64(K, flat)

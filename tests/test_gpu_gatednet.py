@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import _a3c_replay_checks as RC
 import _gated_oracle as G
 from oracle import ticker as TK
 
@@ -191,13 +192,9 @@ def test_rollout_replay():
                                            "weights", "adv", "targets", "boot")}
     eps = eng.episodes_read()
     assert net.get_action_counter() == 1000 + T
-    # draws: rebuilt from the recorded probs / mu / sigma
-    for t in range(T):
-        u, nz = G.draws(eng.cfg.seed, np.arange(E), 1000 + t)
-        for e in range(0, E, 37):
-            ch, raw, _ = G.act(r["probs"][t, e], r["mu"][t, e], r["sigma"][t, e], u[e], nz[e])
-            assert np.array_equal(ch, r["choices"][t, e]), (t, e)
-            assert np.array_equal(raw, r["raw"][t, e]), (t, e)
+    # draws: rebuilt from the recorded probs / mu / sigma (tests/_a3c_replay_checks.py)
+    assert r["choices"].shape == (T, E, 2)
+    RC.gated_acting(r, eng.cfg.seed, np.arange(E), 1000, stride=37)
     # windows and weights follow from the recorded states and dones (fresh episodes at the first step: the engine was just reset)
     win, wts = G.replay_windows(r["states"], r["dones"], R)
     np.testing.assert_array_equal(r["windows"], win)

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import _a3c_replay_checks as RC
 import _gauss_oracle as A
 from oracle import oracle as O
 
@@ -290,17 +291,10 @@ def test_rollout_replay(kind):
     eps = eng.episodes_read()
     assert net.get_action_counter() == 1000 + T
     assert r["dones"][cap - 1].all() and r["dones"].sum() >= 2 * E
-    # draws: rebuilt from the recorded mu / sigma, bit-equal
+    # draws: rebuilt from the recorded mu / sigma, bit-equal; the env actions from them (tests/_a3c_replay_checks.py)
     acts = r["actions"]                   # what the envs were stepped with, as the device computed it
-    for t in range(T):
-        nz = A.draws(eng.cfg.seed, np.arange(E), 1000 + t, Aa)
-        raw = (r["mu"][t].astype(np.float64) + r["sigma"][t].astype(np.float64) * nz).astype(np.float32)
-        assert np.array_equal(raw, r["raw"][t]), t
-        for e in range(0, E, 37):
-            raw1, ea = A.act(r["mu"][t, e], r["sigma"][t, e], nz[e], tanh_action=(kind == "trade"))
-            assert np.array_equal(raw1, r["raw"][t, e]), (t, e)
-            np.testing.assert_allclose(acts[t, e], ea, rtol=1e-6, atol=0)      # the worker's sigmoid / tanh of the raw draw, to float32
-    assert (np.abs(acts) <= 1).all() and (kind == "trade" or (acts >= 0).all())
+    assert r["raw"].shape == (T, E, Aa)
+    RC.gauss_acting(r, eng.cfg.seed, np.arange(E), 1000, tanh_action=(kind == "trade"), stride=37)
     # windows and weights follow from the recorded states and dones (fresh episodes at the first step: the engine was just reset)
     if ab:
         win, wts, twin = A.replay_windows(r["states"], r["dones"], R, r["term_states"])
