@@ -12,6 +12,8 @@
 // All partial sums are combined in a fixed order, so a gradient is bitwise reproducible run to run
 // (conv1's LDS accumulation is float64, its order-dependence is below float32 resolution).
 
+#include "net_slab_plan.h"
+
 namespace grl {
 
 static inline double host_now_ms() {
@@ -81,6 +83,18 @@ static float *slabb_take(grl_net *net, size_t count) {
     float *p = net->slabb + net->slabb_used;
     net->slabb_used += count;
     return p;
+}
+
+// the slabs of a split-M launch: sized by slab_plan (net_slab_plan.h), taken from the slab buffer; `what` is the call site's message
+// (nullptr with the message set: the caller returns GRL_E_INVALID)
+static float *slab_plan_take(grl_net *net, int wg_target, int tiles, int min_chunks, int rows, size_t floats_per_chunk, const char *what,
+                             int *chunks, int *mc = nullptr) {
+    const SlabPlan pl = slab_plan(wg_target, tiles, min_chunks, rows, floats_per_chunk, slab_left(net));
+    float *slab = pl.chunks < 1 ? nullptr : slab_take(net, (size_t)pl.chunks * floats_per_chunk);
+    if (!slab) paac_fail(net, GRL_E_INVALID, what);
+    *chunks = pl.chunks;
+    if (mc) *mc = pl.mc;
+    return slab;
 }
 
 constexpr size_t kSlab64Doubles = (size_t)2048 * 4096;      // float64 partials of the conv1 weight gradient: <= 2048 workgroups x 4096 (or 512 x 6144)
@@ -735,17 +749,10 @@ template <int BM, int BN, int WGM, int WGN, class AG>
 static int tn_launch(grl_net *net, int rd, AG ag, int I, const float *dY, int J, float *gdst, int accumulate = 1, double flop_rows = 0.0,
                      int min_chunks = 0, int wgs = 0) {
     const int M = ag.rows;
-    const int tiles = (I / BM) * (J / BN);
-    int chunks = ((wgs > 0 ? wgs : net->tn_wgs) + tiles - 1) / tiles;
-    if (min_chunks > chunks) chunks = min_chunks;       // short per-workgroup K loops where only part of the rows is live (compact slots)
-    if (chunks > 1024) chunks = 1024;
-    if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-    if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "tn_launch: slab too small");
-    int mc = ((M + chunks - 1) / chunks + 31) / 32 * 32;
-    chunks = (M + mc - 1) / mc;
     const long n = (long)I * J;
-    float *slab = slab_take(net, (size_t)chunks * n);
-    if (!slab) return paac_fail(net, GRL_E_INVALID, "tn_launch: slab too small");
+    int chunks, mc;
+    float *slab = slab_plan_take(net, wgs > 0 ? wgs : net->tn_wgs, (I / BM) * (J / BN), min_chunks, M, (size_t)n, "tn_launch: slab too small", &chunks, &mc);
+    if (!slab) return GRL_E_INVALID;
     {
         GemmTimer t(net, 2.0 * (flop_rows > 0.0 ? flop_rows : (double)M) * (double)I * J);
         launch_tn<BM, BN, WGM, WGN, AG>(net, dim3(I / BM, J / BN, chunks), net->h->stream, ag, dY, J, mc, slab);
@@ -774,17 +781,11 @@ __global__ __launch_bounds__(256) void slot_range_masks_kernel(const int *__rest
 // (slab_reduce_taps_kernel: its body is a job of reduce_batch_kernel since round 4, net_reduce.inc)
 static int slot_wgrad_launch(grl_net *net, int n, float *gw3, double flop_rows, int min_chunks) {
     constexpr int BM = 64, BN = 64, I = 576, J = 64;
-    const int M = n * 9, tiles = (I / BM) * (J / BN);
-    int chunks = (net->tn_wgs + tiles - 1) / tiles;
+    const int M = n * 9;
     if (net->swgrad_chunks > 0) min_chunks = net->swgrad_chunks;
-    if (min_chunks > chunks) chunks = min_chunks;
-    if (chunks > 1024) chunks = 1024;
-    if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-    if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "slot_wgrad_launch: slab too small");
-    const int mc = ((M + chunks - 1) / chunks + 31) / 32 * 32;
-    chunks = (M + mc - 1) / mc;
-    float *slab = slab_take(net, (size_t)chunks * I * J);
-    if (!slab) return paac_fail(net, GRL_E_INVALID, "slot_wgrad_launch: slab too small");
+    int chunks, mc;
+    float *slab = slab_plan_take(net, net->tn_wgs, (I / BM) * (J / BN), min_chunks, M, (size_t)I * J, "slot_wgrad_launch: slab too small", &chunks, &mc);
+    if (!slab) return GRL_E_INVALID;
     hipStream_t st = net->h->stream;
     const bool skip = net->patch_skip != 0;
     if (skip) hipLaunchKernelGGL(slot_range_masks_kernel, dim3(chunks), dim3(256), 0, st, net->sperm, net->stap, net->sbase + n, mc, net->szmask);
@@ -875,26 +876,22 @@ static int backward_chunk(grl_net *net, const TrainBufs &tb, const uint8_t *lb, 
     if (rc != GRL_OK) rq_reset(net);
     return rc;
 }
-static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, int nenv,
-                               const float *actions, const float *adv, const float *y, float inv_total, long slot,
-                               const float *pmu, const float *psg, const float *pval) {
-    hipStream_t st = net->h->stream;
-    const float *P = net->params;
-    float *Gr = net->grads;
-    const int n = nenv * 10;
-    bind_activations(net, slot);
-    // pmu / psg / pval: the heads' outputs the ROLLOUT computed for these samples (same parameters, same kernel: the same bits); with
-    // the dense stack resident too, the gradient step does not evaluate the heads again (49 us and 252 MB per chunk)
-    const bool have_heads = slot >= 0 && pmu && psg && pval;
-    int rc = forward_chunk(net, lb, ab, pos, nenv, tb.cmu, tb.csigma, tb.cvs, slot >= 0, have_heads);
-    if (rc) return rc;
-    // the observation's index record for conv1's backward helpers at the end of this pass: a small kernel, enqueued here so that it runs
-    // behind the GEMMs in between (lane scratch like the trunk lists: rebuilt per pass, not kept with the rollout)
-    if (net->shared_trunk && net->obs_index && (rc = obs_index(net, lb, ab, pos, nenv, net->obsrec, st, 2))) return rc;
-    const float *hmu = have_heads ? pmu : tb.cmu, *hsg = have_heads ? psg : tb.csigma, *hvs = have_heads ? pval : tb.cvs;
+// ---- the stages of a chunk's backward pass, in the order backward_chunk_body runs them.  What every stage works on:
+struct BwdCtx {
+    grl_net *net;
+    hipStream_t st;
+    const float *P;      // parameters
+    float *Gr;           // the lane's gradient accumulator
+    int n, nenv;         // agent-samples and envs of the chunk
+    bool trunk;          // trunk_skip && expand2_gemm: the trunk's row lists exist (trunk_index ran in this chunk's forward_chunk)
+};
+
+// head data gradients AND head weights / biases (one slab row per workgroup).  Queues: RD_HEADS
+static int bwd_heads(const BwdCtx &c, const TrainBufs &tb, const float *hmu, const float *hsg, const float *hvs, const float *actions,
+                     const float *adv, const float *y, float inv_total) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
     const HeadOff &ho = net->ho;
     const int HS = heads_slab(ho.A), NW = 1024 * ho.A + 2 * ho.A;      // NW: [muw|mub|sgw|sgb], contiguous in the flat vector
-    // head data gradients AND head weights / biases (one slab row per workgroup)
     int chunks = (n + 4 * kHeadRows - 1) / (4 * kHeadRows);
     if (chunks > 1024) chunks = 1024;
     const int HS2 = HS + 768;      // + the bias rows of pol1 (512) and v2 (256): column sums of gp1 / gv2, taken while they are written
@@ -909,8 +906,14 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
         j.d0 = Gr + ho.muw; j.p1 = Gr + ho.v3w; j.p2 = Gr + ConvOffsets::p1b; j.p3 = Gr + net->ho.v2b; j.d1 = tb.stats64;
         rq_push(net, RD_HEADS, j);
     }
-    // ---- data gradients (dY * W^T with the ReLU mask of the producing layer fused)
-    net->prof_tag_cur = net->shared_trunk ? PT_DENSE_DGRAD : PT_PER_AGENT;
+    return GRL_OK;
+}
+
+// ---- data gradients (dY * W^T with the ReLU mask of the producing layer fused)
+// the dense stack's, common to both trunks.  Queues: RD_V1B, RD_D2B, RD_D1B
+static int bwd_dense_dgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    const HeadOff &ho = net->ho;
     const size_t csum_floats = ((size_t)n / 128 + 2) * kW128M * 512;
     float *cs1 = slabb_take(net, csum_floats), *cs2 = slabb_take(net, csum_floats), *cs3 = slabb_take(net, csum_floats);
     if (!cs1 || !cs2 || !cs3) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
@@ -926,145 +929,14 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     rowk_launch<128, 128, kW128M, kW128N>(net, DenseRows{net->gd2, n, 256, 256}, P + ConvOffsets::d2w, 256, 512,
                                       EpiGradSum{net->gd1, 512, net->d1, cs3}, 2.0 * n * 256 * 512);
     csum_reduce(net, RD_D1B, cs3, n, 512, Gr + ConvOffsets::d1b);
-    if (!net->shared_trunk)
-        rowk_launch<256, 64, kW256M, kW256N>(net, DenseRows{net->gd1, n, 512, 512}, P + ConvOffsets::d1w, 512, 3136,
-                                   EpiGrad{net->ga3, 3136, net->a3}, 2.0 * n * 512 * 3136);
-    if (net->shared_trunk) {
-        // dense1's data gradient on the shared a3 (net_patch.inc): all 3136 inputs once per env on the agent-summed gd1,
-        // the 1600 patch inputs per agent (group-sorted rows), then the exact mask corrections -> DZ3 per env, dz3 per patch
-        hipLaunchKernelGGL(reduce_agents_kernel, dim3((unsigned)(((size_t)nenv * 128 + 255) / 256)), dim3(256), 0, st, net->gd1, nenv, 128,
-                           net->gd1sh);
-        net->prof_tag_cur = PT_ENV_DGRAD;
-        const bool trunk3 = net->trunk_skip && net->expand2_gemm;
-        if (trunk3) {
-            // only the pixels of the chunk's union mask; of the others nothing but the sum over the envs is used: G = column sums of
-            // gd1sh, trunk_upix / trunk_uadd below (and the rank-1 rows of the weight gradient further down)
-            int cch = (nenv + 31) / 32;
-            if (cch > 2048) cch = 2048;
-            const int cmc = (nenv + cch - 1) / cch;
-            cch = (nenv + cmc - 1) / cmc;
-            float *gslab = slab_take(net, (size_t)cch * 512);
-            if (!gslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small");
-            hipLaunchKernelGGL(colsum_kernel, dim3(1, cch), dim3(256), 0, st, (const float *)net->gd1sh, nenv, 512, cmc, gslab);
-            hipLaunchKernelGGL(slab_reduce_narrow_kernel, dim3((512 + kNarrowCols - 1) / kNarrowCols), dim3(256), 0, st, gslab, cch, 512, net->tug, 0);
-            rowk_launch<256, 64, kW256M, kW256N>(net, DenseRowsNU{{net->gd1sh, nenv, 512, 512}, net->tumask}, P + ConvOffsets::d1w, 512, 3136,
-                                       EpiStore{net->gsh3, 3136}, 2.0 * nenv * 512 * 64.0 * trunk_union_pixels(net));
-        } else {
-            rowk_launch<256, 64, kW256M, kW256N>(net, DenseRows{net->gd1sh, nenv, 512, 512}, P + ConvOffsets::d1w, 512, 3136,
-                                       EpiStore{net->gsh3, 3136}, 2.0 * nenv * 512 * 3136);
-        }
-        {
-            PatchRows g{net->gd1, net->perm, net->tilegroup, net->ptiles * 256, 512, 512, 1, nullptr, nullptr, net->patch_skip ? net->tmask : nullptr, nullptr};
-            net->prof_tag_cur = PT_PATCH_DGRAD;
-            GemmTimer t(net, 2.0 * n * 512 * 1600 * net->pfrac[1]);
-            if (net->pdgrad_pair) {      // two live pixels per 128-wide N tile: 13 tiles cover any support
-                PatchRowsPairN gp{g};
-                // (measured on this instance, round 5, interior / rim us per chunk: as is 339 / 139; without the scheduling fences 334 / 135; two
-                // LDS buffers 331 / 134; launch order instead of the XCD-aware one 370 / 139; the one-accumulator form 848 / 333)
-                launch_rowk<128, 128, kW128M, kW128N, PatchRowsPairN, EpiPermStore, true>(net, dim3(13, net->ptiles * 2), st, gp, P + ConvOffsets::d1w, 512, 1600,
-                                                                                          EpiPermStore{net->g3p, net->perm, 1600});
-            } else if (net->pdgrad_xcd)
-                launch_rowk<256, 64, kW256M, kW256N, PatchRows, EpiPermStore, true>(net, dim3(1600 / 64, net->ptiles), st, g, P + ConvOffsets::d1w, 512, 1600, EpiPermStore{net->g3p, net->perm, 1600});
-            else
-                launch_rowk<256, 64, kW256M, kW256N, PatchRows, EpiPermStore, false>(net, dim3(1600 / 64, net->ptiles), st, g, P + ConvOffsets::d1w, 512, 1600, EpiPermStore{net->g3p, net->perm, 1600});
-        }
-        // (round 5: the same sums with every pixel of the env's map added up by its OWNER thread in agent order -- no LDS fold, one barrier
-        // per env instead of thirteen, 60 registers, bit-identical -- measured 138 / 234 us per chunk (rim / interior) against 110 / 187:
-        // this kernel moves ~0.5 / 1.0 GB per launch, most of it L2 / MALL hits the miss counters do not show, in 256-byte granules, and the
-        // fold walks an agent's support in memory order where the owner form reads one granule per covering agent)
-        static const int hg3 = resident_grid((const void *)agent_dz3_kernel, 2048);
-        maybe_evict(net);
-        hipLaunchKernelGGL(agent_dz3_kernel, dim3(nenv < hg3 ? nenv : hg3), dim3(256), 0, st, net->gsh3, net->g3p, net->a3sh, net->m3,
-                           net->org, net->patch_skip ? net->smask : nullptr, nenv, net->dz3sh, net->dz3p, net->slab1b,
-                           trunk3 ? (const unsigned *)net->tcmask : (const unsigned *)nullptr, trunk3 ? net->tslab + 2048 * 64 : (float *)nullptr,
-                           trunk3 ? (const float *)(net->tbgz3 + 64) : (const float *)nullptr,
-                           trunk3 ? (const unsigned *)net->tumask : (const unsigned *)nullptr);
-        if (trunk3) {
-            // sum of DZ3 over the unaffected conv3 pixels: the rank-1 term of conv3's weight gradient (trunk_rank1_kernel); over all pixels:
-            // conv3's bias gradient of this chunk, added by trunk_closed3_kernel, which also needs it
-            RJob two[2] = {};
-            two[0].kind = RJ_NARROW; two[0].blocks = (64 + kNarrowCols - 1) / kNarrowCols; two[0].i0 = nenv < hg3 ? nenv : hg3; two[0].i1 = 0; two[0].n = 64;
-            two[0].p0 = net->tslab + 2048 * 64; two[0].d0 = net->tsums + 128;
-            two[1] = two[0]; two[1].p0 = net->slab1b; two[1].d0 = net->tsums + 192;
-            rb_launch(net, two, 2);
-            // the pixels outside the union mask, which agent_dz3 did not see
-            hipLaunchKernelGGL(trunk_upix_kernel, dim3(49), dim3(256), 0, st, P + ConvOffsets::d1w, (const float *)net->tug, (const unsigned *)net->tumask,
-                               net->tuspix);
-            hipLaunchKernelGGL(trunk_uadd_kernel, dim3(1), dim3(64), 0, st, (const float *)net->tuspix, (const float *)(net->tbgz3 + 64), net->tsums);
-        } else {
-            RJob j{};      // conv3's bias gradient
-            j.kind = RJ_NARROW; j.blocks = (64 + kNarrowCols - 1) / kNarrowCols; j.i0 = nenv < hg3 ? nenv : hg3; j.i1 = 1; j.n = 64; j.p0 = net->slab1b; j.d0 = Gr + ConvOffsets::c3b;
-            rq_push(net, RD_C3B, j);
-        }
-        // conv3's data gradient on the shared a2 (net_shared.inc): per-env T3 of the agent-summed dz3 under the shared
-        // mask, T3(dz3_a) at the <= 9 touched pixels of every agent, then the exact per-agent mask corrections
-        net->prof_tag_cur = PT_ENV_DGRAD;
-        if (trunk3) {      // at the affected conv2 rows only: the others enter the conv2-level gradients as a sum (trunk_closed3_kernel)
-            float *cs4 = slabb_take(net, ((size_t)nenv * 81 / 128 + 2) * 4 * 64);
-            if (!cs4) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
-            rowk_launch<128, 64, 4, 1, false, 1, true>(net, GatherT3Rows{net->dz3sh, net->trowlist, net->trows_n, nenv * 81}, net->w3t, 576, 64,
-                                       EpiGradRowsSum{net->dz2, 64, net->a2sh, cs4, net->trowlist, net->trows_n},
-                                       2.0 * trunk_live(net, 0, (double)nenv * 81) * 576 * 64);
-            hipLaunchKernelGGL(colsum_live_kernel, dim3(kLiveParts), dim3(256), 0, st, (const float *)cs4, (const int *)net->trows_n, 128, 4, 64,
-                               net->cfold);
-        } else if (nenv % 256 == 0)
-            rowk_launch<256, 64, 4, 1, false>(net, GatherT3PM{net->dz3sh, nenv * 81, nenv}, net->w3t, 576, 64,
-                                       EpiGradPM{net->dz2, net->a2sh, nenv, 81, 64}, 2.0 * nenv * 441 * 64 * 64);
-        else
-            rowk_launch<256, 64, 4, 1, false>(net, GatherT3{net->dz3sh, nenv * 81}, net->w3t, 576, 64, EpiGrad{net->dz2, 64, net->a2sh},
-                                       2.0 * nenv * 81 * 576 * 64);
-        net->prof_tag_cur = PT_SLOT_DGRAD;
-        hipLaunchKernelGGL(slot_rowdesc_kernel, dim3((n * 9 + 255) / 256), dim3(256), 0, st, net->rowagent, net->ulist, net->org, net->sbase + n,
-                           net->sperm, n * 9, net->rowdesc);
-        {   // 128 x 64 tiles on four waves with one accumulator set (four waves per SIMD): 78.5 -> 71 us per chunk against the 256 x 64
-            // four-wave form (interior 187 -> 180); the 256 x 64 eight-wave form measured 87.5 (222)
-            SlotGatherT3P g3{net->dz3p, net->rowdesc, n * 9, net->sbase + n, net->sperm, net->patch_skip ? net->stmask : nullptr, nullptr};
-            GemmTimer t(net, 2.0 * slot_rows_for_flops(net, n) * 576 * 64 * net->sfrac);
-            // (round 5: a contiguous range of row tiles per XCD, as the conv3 patch gather has it, changed nothing of this launch's L2-miss
-            // fetch -- 0.82 GB with every agent in the interior either way -- and cost 178 -> 191 us there, 71 -> 89 on the rim: not used)
-            launch_rowk<128, 64, 4, 1, SlotGatherT3P, EpiPermStore, true, true, 1, true>(net, dim3(1, (n * 9 + 127) / 128), st, g3, net->w3t, 576, 64,
-                                                                                         EpiPermStore{net->gsl, net->sperm, 64});
-        }
-        static const int hg2 = resident_grid((const void *)agent_dz2_kernel, 2048);
-        maybe_evict(net);
-        const bool trunk = net->trunk_skip && net->expand2_gemm;      // the trunk's row lists exist (trunk_index ran in this chunk's forward_chunk)
-        float *slab1b_dz2 = net->slab1b + (size_t)2048 * 64;
-        hipLaunchKernelGGL(agent_dz2_kernel, dim3(nenv < hg2 ? nenv : hg2), dim3(256), 0, st, net->gsl, net->m2s, net->a2sh, net->ulist,
-                           net->sbase, nenv, net->dz2, net->dza, slab1b_dz2, trunk ? (const unsigned *)net->tamask : (const unsigned *)nullptr,
-                           trunk ? 1 : 0);
-        if (trunk) {      // tsums[0..63]: dz2 summed over all rows (conv2's bias gradient of the chunk), [64..127]: over the unaffected rows
-            hipLaunchKernelGGL(slab_reduce_narrow_kernel, dim3((64 + kNarrowCols - 1) / kNarrowCols), dim3(256), 0, st, slab1b_dz2, nenv < hg2 ? nenv : hg2, 64, net->tsums, 0);
-            hipLaunchKernelGGL(trunk_closed3_kernel, dim3(1), dim3(256), 0, st, P + ConvOffsets::c3w, (const float *)(net->tbgz + 64),
-                               (const float *)net->cfold, net->tsums, Gr + ConvOffsets::c3b);
-        } else {
-            RJob j{};      // conv2's bias gradient
-            j.kind = RJ_NARROW; j.blocks = (64 + kNarrowCols - 1) / kNarrowCols; j.i0 = nenv < hg2 ? nenv : hg2; j.i1 = 1; j.n = 64; j.p0 = slab1b_dz2; j.d0 = Gr + ConvOffsets::c2b;
-            rq_push(net, RD_C2B, j);
-        }
-        // conv2 / conv1 gradients once per ENV on the agent-summed dz2
-        net->prof_tag_cur = PT_ENV_DGRAD;
-        // dS = relu'(S) . T2(DZ2): the mask comes from the stored pre-activation, the column sums (conv1's bias gradient up to
-        // the per-agent corrections agent_ds_kernel adds) from the epilogue
-        float *cs5 = slabb_take(net, ((size_t)nenv * 100 / 128 + 2) * kW128M * 128);
-        if (!cs5) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
-        if (trunk) {      // at the touched 2x2 pixel blocks only: nobody reads dS anywhere else (net_shared.inc, trunk_mark_kernel)
-            rowk_launch<128, 128, 2, 2, false>(net, GatherT2Rows{net->dz2, net->tblklist, net->trows_n + 1, nenv * 100}, net->w2t, 256, 128,
-                                        EpiGradStride2Rows{net->gt, net->sraw, cs5, P + ConvOffsets::c1b, net->tblklist, net->trows_n + 1},
-                                        2.0 * trunk_live(net, 1, (double)nenv * 100) * 256 * 128);
-            hipLaunchKernelGGL(fold_class_sums_kernel, dim3(kFoldParts), dim3(256), 0, st, cs5, (nenv * 100 + 127) / 128 * 2, net->cfold,
-                               (const int *)(net->trows_n + 1));
-        } else {
-            rowk_launch<128, 128, 2, 2, false>(net, GatherT2{net->dz2, nenv * 100}, net->w2t, 256, 128,
-                                        EpiGradStride2<true, true>{net->gt, net->sraw, cs5}, 2.0 * nenv * 100 * 256 * 128);
-            hipLaunchKernelGGL(fold_class_sums_kernel, dim3(kFoldParts), dim3(256), 0, st, cs5, (nenv * 100 + 127) / 128 * 2, net->cfold,
-                               (const int *)nullptr);
-        }
-        {   // cfold is not written again in this chunk: the final fold into conv1's bias gradient is queued
-            RJob j{};
-            j.kind = RJ_FOLDFINAL; j.blocks = 1; j.p0 = net->cfold; j.d0 = Gr + ConvOffsets::c1b;
-            rq_push(net, RD_C1B, j);
-        }
-    } else {
+    return GRL_OK;
+}
+
+// the per-agent trunk (GRL_NET_F_PER_AGENT_TRUNK, the A/B reference): dense1, conv3 and conv2 on every agent's own rows.  Queues nothing
+static int bwd_per_agent_dgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    rowk_launch<256, 64, kW256M, kW256N>(net, DenseRows{net->gd1, n, 512, 512}, P + ConvOffsets::d1w, 512, 3136,
+                               EpiGrad{net->ga3, 3136, net->a3}, 2.0 * n * 512 * 3136);
     if (n % 256 == 0)     // pixel-major rows: taps outside the 7x7 image are skipped per workgroup (441 of 729 remain)
         rowk_launch<256, 64, 4, 1, false>(net, GatherT3PM{net->ga3, n * 81, n}, net->w3t, 576, 64, EpiGradPM{net->ga2, net->a2, n, 81, 64},
                                    2.0 * n * 441 * 64 * 64);
@@ -1074,200 +946,411 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     // w2t is [4 classes * 32 ci][256]: one N=128 GEMM, the gathered A tile is loaded once for all four classes
     rowk_launch<128, 128, 2, 2, false>(net, GatherT2{net->ga2, n * 100}, net->w2t, 256, 128, EpiGradStride2<true>{net->ga1, net->a1, nullptr},
                                 2.0 * n * 100 * 256 * 128);
+    return GRL_OK;
+}
+
+// dense1's data gradient on the shared a3 (net_patch.inc): all 3136 inputs once per env on the agent-summed gd1,
+// the 1600 patch inputs per agent (group-sorted rows); the exact mask corrections follow in bwd_conv3_dgrad.  Queues nothing
+static int bwd_dense1_dgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    hipLaunchKernelGGL(reduce_agents_kernel, dim3((unsigned)(((size_t)nenv * 128 + 255) / 256)), dim3(256), 0, st, net->gd1, nenv, 128,
+                       net->gd1sh);
+    net->prof_tag_cur = PT_ENV_DGRAD;
+    if (trunk) {
+        // only the pixels of the chunk's union mask; of the others nothing but the sum over the envs is used: G = column sums of
+        // gd1sh, trunk_upix / trunk_uadd below (and the rank-1 rows of the weight gradient further down)
+        int cch = (nenv + 31) / 32;
+        if (cch > 2048) cch = 2048;
+        const int cmc = (nenv + cch - 1) / cch;
+        cch = (nenv + cmc - 1) / cmc;
+        float *gslab = slab_take(net, (size_t)cch * 512);
+        if (!gslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small");
+        hipLaunchKernelGGL(colsum_kernel, dim3(1, cch), dim3(256), 0, st, (const float *)net->gd1sh, nenv, 512, cmc, gslab);
+        hipLaunchKernelGGL(slab_reduce_narrow_kernel, dim3((512 + kNarrowCols - 1) / kNarrowCols), dim3(256), 0, st, gslab, cch, 512, net->tug, 0);
+        rowk_launch<256, 64, kW256M, kW256N>(net, DenseRowsNU{{net->gd1sh, nenv, 512, 512}, net->tumask}, P + ConvOffsets::d1w, 512, 3136,
+                                   EpiStore{net->gsh3, 3136}, 2.0 * nenv * 512 * 64.0 * trunk_union_pixels(net));
+    } else {
+        rowk_launch<256, 64, kW256M, kW256N>(net, DenseRows{net->gd1sh, nenv, 512, 512}, P + ConvOffsets::d1w, 512, 3136,
+                                   EpiStore{net->gsh3, 3136}, 2.0 * nenv * 512 * 3136);
     }
-    PAAC_HIP(net, hipGetLastError());
-    // ---- weight gradients
-    net->prof_tag_cur = net->shared_trunk ? PT_DENSE_WGRAD : PT_PER_AGENT;
+    {
+        PatchRows g{net->gd1, net->perm, net->tilegroup, net->ptiles * 256, 512, 512, 1, nullptr, nullptr, net->patch_skip ? net->tmask : nullptr, nullptr};
+        net->prof_tag_cur = PT_PATCH_DGRAD;
+        GemmTimer t(net, 2.0 * n * 512 * 1600 * net->pfrac[1]);
+        if (net->pdgrad_pair) {      // two live pixels per 128-wide N tile: 13 tiles cover any support
+            PatchRowsPairN gp{g};
+            // (measured on this instance, round 5, interior / rim us per chunk: as is 339 / 139; without the scheduling fences 334 / 135; two
+            // LDS buffers 331 / 134; launch order instead of the XCD-aware one 370 / 139; the one-accumulator form 848 / 333)
+            launch_rowk<128, 128, kW128M, kW128N, PatchRowsPairN, EpiPermStore, true>(net, dim3(13, net->ptiles * 2), st, gp, P + ConvOffsets::d1w, 512, 1600,
+                                                                                      EpiPermStore{net->g3p, net->perm, 1600});
+        } else if (net->pdgrad_xcd)
+            launch_rowk<256, 64, kW256M, kW256N, PatchRows, EpiPermStore, true>(net, dim3(1600 / 64, net->ptiles), st, g, P + ConvOffsets::d1w, 512, 1600, EpiPermStore{net->g3p, net->perm, 1600});
+        else
+            launch_rowk<256, 64, kW256M, kW256N, PatchRows, EpiPermStore, false>(net, dim3(1600 / 64, net->ptiles), st, g, P + ConvOffsets::d1w, 512, 1600, EpiPermStore{net->g3p, net->perm, 1600});
+    }
+    return GRL_OK;
+}
+
+// the exact mask corrections of dense1's data gradient -> DZ3 per env, dz3 per patch (agent_dz3), then conv3's data gradient on the
+// shared a2.  Queues: RD_C3B (without the trunk skip; with it trunk_closed3_kernel adds conv3's bias gradient in bwd_slot_dgrad)
+static int bwd_conv3_dgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    // (round 5: the same sums with every pixel of the env's map added up by its OWNER thread in agent order -- no LDS fold, one barrier
+    // per env instead of thirteen, 60 registers, bit-identical -- measured 138 / 234 us per chunk (rim / interior) against 110 / 187:
+    // this kernel moves ~0.5 / 1.0 GB per launch, most of it L2 / MALL hits the miss counters do not show, in 256-byte granules, and the
+    // fold walks an agent's support in memory order where the owner form reads one granule per covering agent)
+    static const int hg3 = resident_grid((const void *)agent_dz3_kernel, 2048);
+    maybe_evict(net);
+    hipLaunchKernelGGL(agent_dz3_kernel, dim3(nenv < hg3 ? nenv : hg3), dim3(256), 0, st, net->gsh3, net->g3p, net->a3sh, net->m3,
+                       net->org, net->patch_skip ? net->smask : nullptr, nenv, net->dz3sh, net->dz3p, net->slab1b,
+                       trunk ? (const unsigned *)net->tcmask : (const unsigned *)nullptr, trunk ? net->tslab + 2048 * 64 : (float *)nullptr,
+                       trunk ? (const float *)(net->tbgz3 + 64) : (const float *)nullptr,
+                       trunk ? (const unsigned *)net->tumask : (const unsigned *)nullptr);
+    if (trunk) {
+        // sum of DZ3 over the unaffected conv3 pixels: the rank-1 term of conv3's weight gradient (trunk_rank1_kernel); over all pixels:
+        // conv3's bias gradient of this chunk, added by trunk_closed3_kernel, which also needs it
+        RJob two[2] = {};
+        two[0].kind = RJ_NARROW; two[0].blocks = (64 + kNarrowCols - 1) / kNarrowCols; two[0].i0 = nenv < hg3 ? nenv : hg3; two[0].i1 = 0; two[0].n = 64;
+        two[0].p0 = net->tslab + 2048 * 64; two[0].d0 = net->tsums + 128;
+        two[1] = two[0]; two[1].p0 = net->slab1b; two[1].d0 = net->tsums + 192;
+        rb_launch(net, two, 2);
+        // the pixels outside the union mask, which agent_dz3 did not see
+        hipLaunchKernelGGL(trunk_upix_kernel, dim3(49), dim3(256), 0, st, P + ConvOffsets::d1w, (const float *)net->tug, (const unsigned *)net->tumask,
+                           net->tuspix);
+        hipLaunchKernelGGL(trunk_uadd_kernel, dim3(1), dim3(64), 0, st, (const float *)net->tuspix, (const float *)(net->tbgz3 + 64), net->tsums);
+    } else {
+        RJob j{};      // conv3's bias gradient
+        j.kind = RJ_NARROW; j.blocks = (64 + kNarrowCols - 1) / kNarrowCols; j.i0 = nenv < hg3 ? nenv : hg3; j.i1 = 1; j.n = 64; j.p0 = net->slab1b; j.d0 = Gr + ConvOffsets::c3b;
+        rq_push(net, RD_C3B, j);
+    }
+    // conv3's data gradient on the shared a2 (net_shared.inc): per-env T3 of the agent-summed dz3 under the shared
+    // mask, T3(dz3_a) at the <= 9 touched pixels of every agent, then the exact per-agent mask corrections
+    net->prof_tag_cur = PT_ENV_DGRAD;
+    if (trunk) {      // at the affected conv2 rows only: the others enter the conv2-level gradients as a sum (trunk_closed3_kernel)
+        float *cs4 = slabb_take(net, ((size_t)nenv * 81 / 128 + 2) * 4 * 64);
+        if (!cs4) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
+        rowk_launch<128, 64, 4, 1, false, 1, true>(net, GatherT3Rows{net->dz3sh, net->trowlist, net->trows_n, nenv * 81}, net->w3t, 576, 64,
+                                   EpiGradRowsSum{net->dz2, 64, net->a2sh, cs4, net->trowlist, net->trows_n},
+                                   2.0 * trunk_live(net, 0, (double)nenv * 81) * 576 * 64);
+        hipLaunchKernelGGL(colsum_live_kernel, dim3(kLiveParts), dim3(256), 0, st, (const float *)cs4, (const int *)net->trows_n, 128, 4, 64,
+                           net->cfold);
+    } else if (nenv % 256 == 0)
+        rowk_launch<256, 64, 4, 1, false>(net, GatherT3PM{net->dz3sh, nenv * 81, nenv}, net->w3t, 576, 64,
+                                   EpiGradPM{net->dz2, net->a2sh, nenv, 81, 64}, 2.0 * nenv * 441 * 64 * 64);
+    else
+        rowk_launch<256, 64, 4, 1, false>(net, GatherT3{net->dz3sh, nenv * 81}, net->w3t, 576, 64, EpiGrad{net->dz2, 64, net->a2sh},
+                                   2.0 * nenv * 81 * 576 * 64);
+    return GRL_OK;
+}
+
+// T3(dz3_a) at the <= 9 touched pixels of every agent, then the exact per-agent mask corrections of conv3's data gradient (agent_dz2).
+// Queues: RD_C2B (without the trunk skip)
+static int bwd_slot_dgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    net->prof_tag_cur = PT_SLOT_DGRAD;
+    hipLaunchKernelGGL(slot_rowdesc_kernel, dim3((n * 9 + 255) / 256), dim3(256), 0, st, net->rowagent, net->ulist, net->org, net->sbase + n,
+                       net->sperm, n * 9, net->rowdesc);
+    {   // 128 x 64 tiles on four waves with one accumulator set (four waves per SIMD): 78.5 -> 71 us per chunk against the 256 x 64
+        // four-wave form (interior 187 -> 180); the 256 x 64 eight-wave form measured 87.5 (222)
+        SlotGatherT3P g3{net->dz3p, net->rowdesc, n * 9, net->sbase + n, net->sperm, net->patch_skip ? net->stmask : nullptr, nullptr};
+        GemmTimer t(net, 2.0 * slot_rows_for_flops(net, n) * 576 * 64 * net->sfrac);
+        // (round 5: a contiguous range of row tiles per XCD, as the conv3 patch gather has it, changed nothing of this launch's L2-miss
+        // fetch -- 0.82 GB with every agent in the interior either way -- and cost 178 -> 191 us there, 71 -> 89 on the rim: not used)
+        launch_rowk<128, 64, 4, 1, SlotGatherT3P, EpiPermStore, true, true, 1, true>(net, dim3(1, (n * 9 + 127) / 128), st, g3, net->w3t, 576, 64,
+                                                                                     EpiPermStore{net->gsl, net->sperm, 64});
+    }
+    static const int hg2 = resident_grid((const void *)agent_dz2_kernel, 2048);
+    maybe_evict(net);
+    float *slab1b_dz2 = net->slab1b + (size_t)2048 * 64;
+    hipLaunchKernelGGL(agent_dz2_kernel, dim3(nenv < hg2 ? nenv : hg2), dim3(256), 0, st, net->gsl, net->m2s, net->a2sh, net->ulist,
+                       net->sbase, nenv, net->dz2, net->dza, slab1b_dz2, trunk ? (const unsigned *)net->tamask : (const unsigned *)nullptr,
+                       trunk ? 1 : 0);
+    if (trunk) {      // tsums[0..63]: dz2 summed over all rows (conv2's bias gradient of the chunk), [64..127]: over the unaffected rows
+        hipLaunchKernelGGL(slab_reduce_narrow_kernel, dim3((64 + kNarrowCols - 1) / kNarrowCols), dim3(256), 0, st, slab1b_dz2, nenv < hg2 ? nenv : hg2, 64, net->tsums, 0);
+        hipLaunchKernelGGL(trunk_closed3_kernel, dim3(1), dim3(256), 0, st, P + ConvOffsets::c3w, (const float *)(net->tbgz + 64),
+                           (const float *)net->cfold, net->tsums, Gr + ConvOffsets::c3b);
+    } else {
+        RJob j{};      // conv2's bias gradient
+        j.kind = RJ_NARROW; j.blocks = (64 + kNarrowCols - 1) / kNarrowCols; j.i0 = nenv < hg2 ? nenv : hg2; j.i1 = 1; j.n = 64; j.p0 = slab1b_dz2; j.d0 = Gr + ConvOffsets::c2b;
+        rq_push(net, RD_C2B, j);
+    }
+    return GRL_OK;
+}
+
+// conv2 / conv1 gradients once per ENV on the agent-summed dz2.  Queues: RD_C1B
+static int bwd_conv2_dgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    net->prof_tag_cur = PT_ENV_DGRAD;
+    // dS = relu'(S) . T2(DZ2): the mask comes from the stored pre-activation, the column sums (conv1's bias gradient up to
+    // the per-agent corrections agent_ds_kernel adds) from the epilogue
+    float *cs5 = slabb_take(net, ((size_t)nenv * 100 / 128 + 2) * kW128M * 128);
+    if (!cs5) return paac_fail(net, GRL_E_INVALID, "backward_chunk: column-sum buffer too small");
+    if (trunk) {      // at the touched 2x2 pixel blocks only: nobody reads dS anywhere else (net_shared.inc, trunk_mark_kernel)
+        rowk_launch<128, 128, 2, 2, false>(net, GatherT2Rows{net->dz2, net->tblklist, net->trows_n + 1, nenv * 100}, net->w2t, 256, 128,
+                                    EpiGradStride2Rows{net->gt, net->sraw, cs5, P + ConvOffsets::c1b, net->tblklist, net->trows_n + 1},
+                                    2.0 * trunk_live(net, 1, (double)nenv * 100) * 256 * 128);
+        hipLaunchKernelGGL(fold_class_sums_kernel, dim3(kFoldParts), dim3(256), 0, st, cs5, (nenv * 100 + 127) / 128 * 2, net->cfold,
+                           (const int *)(net->trows_n + 1));
+    } else {
+        rowk_launch<128, 128, 2, 2, false>(net, GatherT2{net->dz2, nenv * 100}, net->w2t, 256, 128,
+                                    EpiGradStride2<true, true>{net->gt, net->sraw, cs5}, 2.0 * nenv * 100 * 256 * 128);
+        hipLaunchKernelGGL(fold_class_sums_kernel, dim3(kFoldParts), dim3(256), 0, st, cs5, (nenv * 100 + 127) / 128 * 2, net->cfold,
+                           (const int *)nullptr);
+    }
+    {   // cfold is not written again in this chunk: the final fold into conv1's bias gradient is queued
+        RJob j{};
+        j.kind = RJ_FOLDFINAL; j.blocks = 1; j.p0 = net->cfold; j.d0 = Gr + ConvOffsets::c1b;
+        rq_push(net, RD_C1B, j);
+    }
+    return GRL_OK;
+}
+
+// ---- weight gradients
+// the dense stack's, common to both trunks.  Queues: RD_V2W, RD_V1W, RD_P1W, RD_D2W
+static int bwd_dense_wgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    int rc;
     if ((rc = tn_launch<128, 128, 2, 2>(net, RD_V2W, DenseRows{net->v1, n, 512, 512}, 512, net->gv2, 256, Gr + net->ho.v2w, 1, 0.0, 0, net->tn_wgs_dense))) return rc;
     if ((rc = tn_launch<128, 128, 2, 2>(net, RD_V1W, DenseRows{net->d2, n, 256, 256}, 256, net->gv1, 512, Gr + net->ho.v1w, 1, 0.0, 0, net->tn_wgs_dense))) return rc;
     if ((rc = tn_launch<128, 128, 2, 2>(net, RD_P1W, DenseRows{net->d2, n, 256, 256}, 256, net->gp1, 512, Gr + ConvOffsets::p1w, 1, 0.0, 0, net->tn_wgs_dense))) return rc;
     if ((rc = tn_launch<128, 128, 2, 2>(net, RD_D2W, DenseRows{net->d1, n, 512, 512}, 512, net->gd2, 256, Gr + ConvOffsets::d2w, 1, 0.0, 0, net->tn_wgs_dense))) return rc;
-    if (net->shared_trunk) {
-        // dW_dense1 = a3sh^T (sum_a gd1_a) per env + per-group d3^T gd1 on the patch rows
-        net->prof_tag_cur = PT_ENV_WGRAD;
-        if (net->trunk_skip && net->expand2_gemm) {      // rows of the union mask's pixels; the others are a3bg (x) G (slab_reduce_umask_kernel)
-            constexpr int I = 3136, J = 512, tiles = (I / 64) * (J / 128);
-            int chunks = (net->tn_wgs + tiles - 1) / tiles;
-            if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-            if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "dense1 per-env weight gradient: slab too small");
-            const int mc = ((nenv + chunks - 1) / chunks + 31) / 32 * 32;
-            chunks = (nenv + mc - 1) / mc;
-            float *slab = slab_take(net, (size_t)chunks * I * J);
-            if (!slab) return paac_fail(net, GRL_E_INVALID, "dense1 per-env weight gradient: slab too small");
-            {
-                GemmTimer t(net, 2.0 * nenv * 64.0 * trunk_union_pixels(net) * J);
-                launch_tn<64, 128, 2, 2, DenseRowsIU>(net, dim3(I / 64, J / 128, chunks), st, DenseRowsIU{{net->a3sh, nenv, 3136, 3136}, net->tumask},
-                                                      net->gd1sh, J, mc, slab);
-            }
-            RJob j{};
-            j.kind = RJ_UMASK; j.blocks = (int)(((long)I * J + 255) / 256); j.i0 = chunks; j.n = (long)I * J; j.p0 = slab; j.p1 = net->tumask;
-            j.p2 = net->tbgz3 + 64; j.p3 = net->tug; j.d0 = Gr + ConvOffsets::d1w;
-            rq_push(net, RD_D1W, j);
-        } else if ((rc = tn_launch<64, 128, 2, 2>(net, RD_D1W, DenseRows{net->a3sh, nenv, 3136, 3136}, 3136, net->gd1sh, 512, Gr + ConvOffsets::d1w))) return rc;
+    return GRL_OK;
+}
+
+// dW_dense1 = a3sh^T (sum_a gd1_a) per env + per-group d3^T gd1 on the patch rows.  Queues: RD_D1W twice (per env, then the patch slices)
+static int bwd_dense1_wgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    int rc;
+    net->prof_tag_cur = PT_ENV_WGRAD;
+    if (trunk) {      // rows of the union mask's pixels; the others are a3bg (x) G (slab_reduce_umask_kernel)
+        constexpr int I = 3136, J = 512;
+        int chunks, mc;
+        float *slab = slab_plan_take(net, net->tn_wgs, (I / 64) * (J / 128), 0, nenv, (size_t)I * J, "dense1 per-env weight gradient: slab too small", &chunks, &mc);
+        if (!slab) return GRL_E_INVALID;
         {
-            float *pslab = slab_take(net, (size_t)net->pslices * 1600 * 512);
-            if (!pslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small for the patch slices");
-            PatchRows g{net->d3, net->perm, net->tilegroup, net->ptiles * 256, 1600, 1600, 0, net->sbeg, net->send, net->patch_skip ? net->tmask : nullptr,
-                        net->patch_skip ? net->zmask : nullptr};
-            {
-                net->prof_tag_cur = PT_PATCH_WGRAD;
-                GemmTimer t(net, 2.0 * n * 1600 * 512 * net->pfrac[2]);
-                if (net->pwgrad_pair) {      // two live pixels per 128-wide I tile: 13 tiles cover any support
-                    PatchRowsPair gp{g};
-                    if (net->pwgrad_xcd == 1)
-                        launch_tn<128, 128, 2, 2, PatchRowsPair, 1>(net, dim3(13, 512 / 128, net->pslices), st, gp, net->gd1, 512, 0, pslab);
-                    else
-                        launch_tn<128, 128, 2, 2, PatchRowsPair, 0>(net, dim3(13, 512 / 128, net->pslices), st, gp, net->gd1, 512, 0, pslab);
-                } else if (net->pwgrad_xcd == 1)
-                    launch_tn<64, 128, 2, 2, PatchRows, 1>(net, dim3(1600 / 64, 512 / 128, net->pslices), st, g, net->gd1, 512, 0, pslab);
-                else if (net->pwgrad_xcd == 2)
-                    launch_tn<64, 128, 2, 2, PatchRows, 2>(net, dim3(1600 / 64, 512 / 128, net->pslices), st, g, net->gd1, 512, 0, pslab);
-                else
-                    launch_tn<64, 128, 2, 2, PatchRows, 0>(net, dim3(1600 / 64, 512 / 128, net->pslices), st, g, net->gd1, 512, 0, pslab);
-            }
-            RJob j{};
-            j.kind = RJ_PATCH; j.blocks = 3136 * 128 / 256; j.i0 = net->pslices; j.p0 = pslab; j.p1 = net->sgrp; j.p2 = net->patch_skip ? net->zmask : nullptr;
-            j.d0 = Gr + ConvOffsets::d1w;
-            rq_push(net, RD_D1W, j);
+            GemmTimer t(net, 2.0 * nenv * 64.0 * trunk_union_pixels(net) * J);
+            launch_tn<64, 128, 2, 2, DenseRowsIU>(net, dim3(I / 64, J / 128, chunks), st, DenseRowsIU{{net->a3sh, nenv, 3136, 3136}, net->tumask},
+                                                  net->gd1sh, J, mc, slab);
         }
-    } else {
-        if ((rc = tn_launch<64, 128, 2, 2>(net, RD_D1W, DenseRows{net->a3, n, 3136, 3136}, 3136, net->gd1, 512, Gr + ConvOffsets::d1w))) return rc;
+        RJob j{};
+        j.kind = RJ_UMASK; j.blocks = (int)(((long)I * J + 255) / 256); j.i0 = chunks; j.n = (long)I * J; j.p0 = slab; j.p1 = net->tumask;
+        j.p2 = net->tbgz3 + 64; j.p3 = net->tug; j.d0 = Gr + ConvOffsets::d1w;
+        rq_push(net, RD_D1W, j);
+    } else if ((rc = tn_launch<64, 128, 2, 2>(net, RD_D1W, DenseRows{net->a3sh, nenv, 3136, 3136}, 3136, net->gd1sh, 512, Gr + ConvOffsets::d1w))) return rc;
+    {
+        float *pslab = slab_take(net, (size_t)net->pslices * 1600 * 512);
+        if (!pslab) return paac_fail(net, GRL_E_INVALID, "backward_chunk: slab too small for the patch slices");
+        PatchRows g{net->d3, net->perm, net->tilegroup, net->ptiles * 256, 1600, 1600, 0, net->sbeg, net->send, net->patch_skip ? net->tmask : nullptr,
+                    net->patch_skip ? net->zmask : nullptr};
+        {
+            net->prof_tag_cur = PT_PATCH_WGRAD;
+            GemmTimer t(net, 2.0 * n * 1600 * 512 * net->pfrac[2]);
+            if (net->pwgrad_pair) {      // two live pixels per 128-wide I tile: 13 tiles cover any support
+                PatchRowsPair gp{g};
+                if (net->pwgrad_xcd == 1)
+                    launch_tn<128, 128, 2, 2, PatchRowsPair, 1>(net, dim3(13, 512 / 128, net->pslices), st, gp, net->gd1, 512, 0, pslab);
+                else
+                    launch_tn<128, 128, 2, 2, PatchRowsPair, 0>(net, dim3(13, 512 / 128, net->pslices), st, gp, net->gd1, 512, 0, pslab);
+            } else if (net->pwgrad_xcd == 1)
+                launch_tn<64, 128, 2, 2, PatchRows, 1>(net, dim3(1600 / 64, 512 / 128, net->pslices), st, g, net->gd1, 512, 0, pslab);
+            else if (net->pwgrad_xcd == 2)
+                launch_tn<64, 128, 2, 2, PatchRows, 2>(net, dim3(1600 / 64, 512 / 128, net->pslices), st, g, net->gd1, 512, 0, pslab);
+            else
+                launch_tn<64, 128, 2, 2, PatchRows, 0>(net, dim3(1600 / 64, 512 / 128, net->pslices), st, g, net->gd1, 512, 0, pslab);
+        }
+        RJob j{};
+        j.kind = RJ_PATCH; j.blocks = 3136 * 128 / 256; j.i0 = net->pslices; j.p0 = pslab; j.p1 = net->sgrp; j.p2 = net->patch_skip ? net->zmask : nullptr;
+        j.d0 = Gr + ConvOffsets::d1w;
+        rq_push(net, RD_D1W, j);
     }
-    if (net->shared_trunk) {
-        // dW3 = patches(a2sh)^T DZ3 + sum over (agent, slot) of (a2_a - a2sh)[u] (x) dz3_a[u - tap]
-        net->prof_tag_cur = PT_ENV_WGRAD;
-        if (net->trunk_skip && net->expand2_gemm) {      // the affected conv3 rows + the rank-1 term of the rest (see conv2's below)
-            constexpr int I = 576, J = 64, tiles = (I / 64) * (J / 64);
-            int chunks = (net->tn_wgs + tiles - 1) / tiles;
-            if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-            if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "conv3 weight gradient: slab too small");
-            float *slab = slab_take(net, (size_t)chunks * I * J);
-            if (!slab) return paac_fail(net, GRL_E_INVALID, "conv3 weight gradient: slab too small");
-            GatherConv3Rows ag{net->a2sh, net->tc3list, net->trows_n + 2, net->tbgimg3, nenv * 49, chunks};
-            {
-                GemmTimer t(net, 2.0 * trunk_live(net, 2, (double)nenv * 49) * I * J);
-                launch_tn<64, 64, 2, 2, GatherConv3Rows>(net, dim3(I / 64, J / 64, chunks), st, ag, net->dz3sh, J, 0, slab);
-            }
-            RJob j{};
-            j.kind = RJ_SLAB; j.blocks = (I * J + 255) / 256; j.i0 = chunks; j.i1 = 1; j.n = (long)I * J; j.p0 = slab; j.d0 = Gr + ConvOffsets::c3w;
-            rq_push(net, RD_C3W, j);
-            RJob r{};      // the rank-1 term of the unaffected rows (trunk_rank1_kernel)
-            r.kind = RJ_RANK1; r.blocks = I * J / 256; r.i0 = 63; r.p0 = net->tbgz + 64; r.p1 = net->tsums + 128; r.d0 = Gr + ConvOffsets::c3w;
-            rq_push(net, RD_C3W, r);
-        } else if ((rc = tn_launch<64, 64, 2, 2>(net, RD_C3W, GatherConv3{net->a2sh, nenv * 49}, 576, net->dz3sh, 64, Gr + ConvOffsets::c3w))) return rc;
-        net->prof_tag_cur = PT_SLOT_WGRAD;
-        // >= 684 row ranges: the gather loop is bound by the latency of its loads, one K-tile in flight per workgroup at three
-        // workgroups per CU, so its time falls with the workgroups in flight (round 5, rim / interior us per chunk: 228 ranges 175 / 235,
-        // 456: 124 / 237, 684: 89 / 237, 912: 107 / 241)
-        if ((rc = slot_wgrad_launch(net, n, Gr + ConvOffsets::c3w, slot_rows_for_flops(net, n), 684))) return rc;
-        net->prof_tag_cur = PT_ENV_WGRAD;
-        if (net->trunk_skip && net->expand2_gemm) {
-            // the affected rows of every env (trunk_index), dealt evenly to the row ranges on the device; the rest of the rows are one
-            // constant patch: trunk_closed_kernel adds their rank-1 term (and the two closed-form bias parts)
-            constexpr int I = 512, J = 64, tiles = (I / 128) * (J / 64);
-            int chunks = (net->tn_wgs + tiles - 1) / tiles;
-            if ((size_t)chunks * I * J > slab_left(net)) chunks = (int)(slab_left(net) / ((size_t)I * J));
-            if (chunks < 1) return paac_fail(net, GRL_E_INVALID, "conv2 weight gradient: slab too small");
-            float *slab = slab_take(net, (size_t)chunks * I * J);
-            if (!slab) return paac_fail(net, GRL_E_INVALID, "conv2 weight gradient: slab too small");
-            GatherConv2ReluRows ag{net->sraw, net->trowlist, net->trows_n, net->tbgimg, nenv * 81, chunks};
-            {
-                GemmTimer t(net, 2.0 * trunk_live(net, 0, (double)nenv * 81) * I * J);
-                launch_tn<128, 64, 2, 2, GatherConv2ReluRows>(net, dim3(I / 128, J / 64, chunks), st, ag, net->dz2, J, 0, slab);
-            }
-            RJob j{};
-            j.kind = RJ_SLAB; j.blocks = (I * J + 255) / 256; j.i0 = chunks; j.i1 = 1; j.n = (long)I * J; j.p0 = slab; j.d0 = Gr + ConvOffsets::c2w;
-            rq_push(net, RD_C2W, j);
-            // trunk_closed_kernel's three parts: the rank-1 background term of dW2, conv1's closed-form bias part, conv2's bias gradient
-            RJob w{};
-            w.kind = RJ_CLOSED_W; w.blocks = 128; w.p0 = P + ConvOffsets::c1b; w.p1 = net->tsums + 64; w.d0 = Gr + ConvOffsets::c2w;
-            rq_push(net, RD_C2W, w);
-            RJob b1{};
-            b1.kind = RJ_CLOSED_B1; b1.blocks = 1; b1.p0 = P + ConvOffsets::c1b; b1.p1 = P + ConvOffsets::c2w; b1.p2 = net->tsums; b1.d0 = Gr + ConvOffsets::c1b;
-            rq_push(net, RD_C1B, b1);
-            RJob b2{};
-            b2.kind = RJ_CLOSED_B2; b2.blocks = 1; b2.p0 = net->tsums; b2.d0 = Gr + ConvOffsets::c2b;
-            rq_push(net, RD_C2B, b2);
-        } else if ((rc = tn_launch<128, 64, 2, 2>(net, RD_C2W, GatherConv2Relu{net->sraw, nenv * 81}, 512, net->dz2, 64, Gr + ConvOffsets::c2w))) return rc;
-    } else {
-        if ((rc = tn_launch<64, 64, 2, 2>(net, RD_C3W, GatherConv3{net->a2, n * 49}, 576, net->ga3, 64, Gr + ConvOffsets::c3w))) return rc;
-        if ((rc = tn_launch<128, 64, 2, 2>(net, RD_C2W, GatherConv2{net->a1, n * 81}, 512, net->ga2, 64, Gr + ConvOffsets::c2w))) return rc;
-    }
+    return GRL_OK;
+}
+
+// dW3 = patches(a2sh)^T DZ3 + sum over (agent, slot) of (a2_a - a2sh)[u] (x) dz3_a[u - tap].  Queues: RD_C3W (with the trunk skip: the
+// affected rows, then the rank-1 term), then RD_C3W again for the slot correction
+static int bwd_conv3_wgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    int rc;
+    net->prof_tag_cur = PT_ENV_WGRAD;
+    if (trunk) {      // the affected conv3 rows + the rank-1 term of the rest (see conv2's below)
+        constexpr int I = 576, J = 64;
+        int chunks;      // rows 0: they are dealt to the row ranges on the device
+        float *slab = slab_plan_take(net, net->tn_wgs, (I / 64) * (J / 64), 0, 0, (size_t)I * J, "conv3 weight gradient: slab too small", &chunks);
+        if (!slab) return GRL_E_INVALID;
+        GatherConv3Rows ag{net->a2sh, net->tc3list, net->trows_n + 2, net->tbgimg3, nenv * 49, chunks};
+        {
+            GemmTimer t(net, 2.0 * trunk_live(net, 2, (double)nenv * 49) * I * J);
+            launch_tn<64, 64, 2, 2, GatherConv3Rows>(net, dim3(I / 64, J / 64, chunks), st, ag, net->dz3sh, J, 0, slab);
+        }
+        RJob j{};
+        j.kind = RJ_SLAB; j.blocks = (I * J + 255) / 256; j.i0 = chunks; j.i1 = 1; j.n = (long)I * J; j.p0 = slab; j.d0 = Gr + ConvOffsets::c3w;
+        rq_push(net, RD_C3W, j);
+        RJob r{};      // the rank-1 term of the unaffected rows (trunk_rank1_kernel)
+        r.kind = RJ_RANK1; r.blocks = I * J / 256; r.i0 = 63; r.p0 = net->tbgz + 64; r.p1 = net->tsums + 128; r.d0 = Gr + ConvOffsets::c3w;
+        rq_push(net, RD_C3W, r);
+    } else if ((rc = tn_launch<64, 64, 2, 2>(net, RD_C3W, GatherConv3{net->a2sh, nenv * 49}, 576, net->dz3sh, 64, Gr + ConvOffsets::c3w))) return rc;
+    net->prof_tag_cur = PT_SLOT_WGRAD;
+    // >= 684 row ranges: the gather loop is bound by the latency of its loads, one K-tile in flight per workgroup at three
+    // workgroups per CU, so its time falls with the workgroups in flight (round 5, rim / interior us per chunk: 228 ranges 175 / 235,
+    // 456: 124 / 237, 684: 89 / 237, 912: 107 / 241)
+    if ((rc = slot_wgrad_launch(net, n, Gr + ConvOffsets::c3w, slot_rows_for_flops(net, n), 684))) return rc;
+    return GRL_OK;
+}
+
+// conv2's weight gradient once per env.  Queues: RD_C2W (with the trunk skip: the affected rows, then RD_C2W, RD_C1B, RD_C2B for
+// trunk_closed_kernel's three parts)
+static int bwd_conv2_wgrad(const BwdCtx &c) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    int rc;
+    net->prof_tag_cur = PT_ENV_WGRAD;
+    if (trunk) {
+        // the affected rows of every env (trunk_index), dealt evenly to the row ranges on the device; the rest of the rows are one
+        // constant patch: trunk_closed_kernel adds their rank-1 term (and the two closed-form bias parts)
+        constexpr int I = 512, J = 64;
+        int chunks;      // rows 0: dealt on the device
+        float *slab = slab_plan_take(net, net->tn_wgs, (I / 128) * (J / 64), 0, 0, (size_t)I * J, "conv2 weight gradient: slab too small", &chunks);
+        if (!slab) return GRL_E_INVALID;
+        GatherConv2ReluRows ag{net->sraw, net->trowlist, net->trows_n, net->tbgimg, nenv * 81, chunks};
+        {
+            GemmTimer t(net, 2.0 * trunk_live(net, 0, (double)nenv * 81) * I * J);
+            launch_tn<128, 64, 2, 2, GatherConv2ReluRows>(net, dim3(I / 128, J / 64, chunks), st, ag, net->dz2, J, 0, slab);
+        }
+        RJob j{};
+        j.kind = RJ_SLAB; j.blocks = (I * J + 255) / 256; j.i0 = chunks; j.i1 = 1; j.n = (long)I * J; j.p0 = slab; j.d0 = Gr + ConvOffsets::c2w;
+        rq_push(net, RD_C2W, j);
+        // trunk_closed_kernel's three parts: the rank-1 background term of dW2, conv1's closed-form bias part, conv2's bias gradient
+        RJob w{};
+        w.kind = RJ_CLOSED_W; w.blocks = 128; w.p0 = P + ConvOffsets::c1b; w.p1 = net->tsums + 64; w.d0 = Gr + ConvOffsets::c2w;
+        rq_push(net, RD_C2W, w);
+        RJob b1{};
+        b1.kind = RJ_CLOSED_B1; b1.blocks = 1; b1.p0 = P + ConvOffsets::c1b; b1.p1 = P + ConvOffsets::c2w; b1.p2 = net->tsums; b1.d0 = Gr + ConvOffsets::c1b;
+        rq_push(net, RD_C1B, b1);
+        RJob b2{};
+        b2.kind = RJ_CLOSED_B2; b2.blocks = 1; b2.p0 = net->tsums; b2.d0 = Gr + ConvOffsets::c2b;
+        rq_push(net, RD_C2B, b2);
+    } else if ((rc = tn_launch<128, 64, 2, 2>(net, RD_C2W, GatherConv2Relu{net->sraw, nenv * 81}, 512, net->dz2, 64, Gr + ConvOffsets::c2w))) return rc;
+    return GRL_OK;
+}
+
+// the per-agent trunk's weight and bias gradients of dense1 and the convolutions.  Queues: RD_D1W, RD_C3W, RD_C2W, RD_C3B, RD_C2B, RD_C1B;
+// conv1's weight gradient is reduced at once
+static int bwd_per_agent_wgrad(const BwdCtx &c, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    int rc;
+    if ((rc = tn_launch<64, 128, 2, 2>(net, RD_D1W, DenseRows{net->a3, n, 3136, 3136}, 3136, net->gd1, 512, Gr + ConvOffsets::d1w))) return rc;
+    if ((rc = tn_launch<64, 64, 2, 2>(net, RD_C3W, GatherConv3{net->a2, n * 49}, 576, net->ga3, 64, Gr + ConvOffsets::c3w))) return rc;
+    if ((rc = tn_launch<128, 64, 2, 2>(net, RD_C2W, GatherConv2{net->a1, n * 81}, 512, net->ga2, 64, Gr + ConvOffsets::c2w))) return rc;
     // ---- bias gradients
     // (the bias gradients of v2 and pol1 -- column sums of gv2 / gp1 -- come out of heads_backward_kernel's slab row)
-    if (!net->shared_trunk && (rc = colsum_launch(net, RD_C3B, net->ga3, n * 49, 64, Gr + ConvOffsets::c3b))) return rc;      // shared: out of agent_dz3_kernel
-    int blocks = nenv < 512 ? nenv : 512;
-    if (net->shared_trunk) {
-        // per-agent corrections: dW2 (+=), one-hot taps of dW1 (+=), and gt: T2(DZ2) -> dS in place
-        static const int hgs = resident_grid((const void *)agent_ds_kernel, 2048);
-        const int dblocks = nenv < hgs ? nenv : hgs, npad = net->npad;
-        maybe_evict(net);
-        const int t2rows = (n + 127) / 128 * 128;      // rows of the class GEMMs' last tile exist as (invalid) descriptors
-        hipLaunchKernelGGL(gather_t2_kernel, dim3((t2rows + kT2Agents - 1) / kT2Agents), dim3(256), 0, st, net->sraw, pos, net->ulist, net->sbase,
-                           P + ConvOffsets::c1w, n, npad, t2rows, net->t2desc, net->dl2);
-        net->prof_tag_cur = PT_CLASS_CORR;
-        {   // the four parity classes in one launch each (they are launch-latency bound one by one): T2 rows and dW2
-            const int cpc = 64;                                        // row ranges per class: 4 x 64 x 8 tiles = 2 048 workgroups
-            const int mc = ((n + cpc - 1) / cpc + 31) / 32 * 32;
-            T2SlotGather g{net->dza, net->t2desc, 4 * npad, npad, n, 32, cpc};
-            {
-                GemmTimer t(net, 4 * 2.0 * n * 256 * 32);
-                launch_rowk<128, 32, 4, 1, T2SlotGather, EpiStore>(net, dim3(1, 4 * npad / 128), st, g, net->w2t, 256, 32, EpiStore{net->tt2, 32});
-            }
-            float *cslab = slab_take(net, (size_t)4 * cpc * 8192);
-            if (!cslab) return paac_fail(net, GRL_E_INVALID, "class corrections: slab too small");
-            {
-                GemmTimer t(net, 4 * 2.0 * n * 256 * 32);
-                launch_tn<64, 32, 4, 1, T2SlotGather>(net, dim3(256 / 64, 1, 4 * cpc), st, g, net->dl2, 32, mc, cslab);      // one tap per I tile: its validity is per row
-            }
-            RJob j{};      // the grouped slab sum and conv2_corr_add's re-indexing into dW2 in one queued job
-            j.kind = RJ_GROUPS_C2; j.blocks = 4 * 8192 / 256; j.i0 = cpc; j.p0 = cslab; j.d0 = Gr + ConvOffsets::c2w;
-            rq_push(net, RD_C2W, j);
-        }
-        float *slab1h = net->slab1h, *slab1b_ds = net->slab1b + (size_t)2 * 2048 * 64;
-        // (both forms on the parent kernels' grids: the workgroup an env falls to decides the order of the sums)
-        if (net->obs_index)
-            hipLaunchKernelGGL(agent_ds_indexed_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, (const unsigned *)net->obsrec, net->tt2, npad, net->gt,
-                               P + ConvOffsets::c1w, nenv, slab1h, slab1b_ds);
-        else
-            hipLaunchKernelGGL(agent_ds_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, pos, net->tt2, npad, net->gt, P + ConvOffsets::c1w,
-                               nenv, slab1h, slab1b_ds);
+    if ((rc = colsum_launch(net, RD_C3B, net->ga3, n * 49, 64, Gr + ConvOffsets::c3b))) return rc;      // shared: out of agent_dz3_kernel
+    if ((rc = colsum_launch(net, RD_C2B, net->ga2, n * 81, 64, Gr + ConvOffsets::c2b))) return rc;
+    if ((rc = colsum_launch(net, RD_C1B, net->ga1, n * 400, 32, Gr + ConvOffsets::c1b))) return rc;
+    // ---- conv1 weights (sparse)
+    const int blocks = nenv < 512 ? nenv : 512;
+    hipLaunchKernelGGL(conv1_wgrad_kernel, dim3(blocks), dim3(256), 0, st, lb, ab, pos, net->ga1, nenv, net->h->cfg.grid_size,
+                       net->slab64, (const float *)nullptr);
+    hipLaunchKernelGGL(slab64_reduce_kernel, dim3(6144 / 256), dim3(256), 0, st, net->slab64, blocks, 6144, Gr + ConvOffsets::c1w);
+    return GRL_OK;
+}
+
+// per-agent corrections: dW2 (+=), one-hot taps of dW1 (+=), and gt: T2(DZ2) -> dS in place; then conv1's weight gradient.
+// Queues: RD_C2W, RD_C1W_HOT, RD_C1B, RD_C1W_CNT
+static int bwd_class_corr_conv1(const BwdCtx &c, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos) {
+    const auto [net, st, P, Gr, n, nenv, trunk] = c;
+    static const int hgs = resident_grid((const void *)agent_ds_kernel, 2048);
+    const int dblocks = nenv < hgs ? nenv : hgs, npad = net->npad;
+    maybe_evict(net);
+    const int t2rows = (n + 127) / 128 * 128;      // rows of the class GEMMs' last tile exist as (invalid) descriptors
+    hipLaunchKernelGGL(gather_t2_kernel, dim3((t2rows + kT2Agents - 1) / kT2Agents), dim3(256), 0, st, net->sraw, pos, net->ulist, net->sbase,
+                       P + ConvOffsets::c1w, n, npad, t2rows, net->t2desc, net->dl2);
+    net->prof_tag_cur = PT_CLASS_CORR;
+    {   // the four parity classes in one launch each (they are launch-latency bound one by one): T2 rows and dW2
+        const int cpc = 64;                                        // row ranges per class: 4 x 64 x 8 tiles = 2 048 workgroups
+        const int mc = ((n + cpc - 1) / cpc + 31) / 32 * 32;
+        T2SlotGather g{net->dza, net->t2desc, 4 * npad, npad, n, 32, cpc};
         {
-            RJob j{};
-            j.kind = RJ_ONEHOT; j.blocks = 2048 / 16; j.i0 = dblocks; j.p0 = slab1h; j.d0 = Gr + ConvOffsets::c1w;
-            rq_push(net, RD_C1W_HOT, j);
-            // conv1's bias gradient: the base part came out of the T2 GEMM's epilogue, agent_ds_kernel adds the sums of its corrections
-            RJob b{};
-            b.kind = RJ_NARROW; b.blocks = (32 + kNarrowCols - 1) / kNarrowCols; b.i0 = dblocks; b.i1 = 1; b.n = 32; b.p0 = slab1b_ds; b.d0 = Gr + ConvOffsets::c1b;
-            rq_push(net, RD_C1B, b);
+            GemmTimer t(net, 4 * 2.0 * n * 256 * 32);
+            launch_rowk<128, 32, 4, 1, T2SlotGather, EpiStore>(net, dim3(1, 4 * npad / 128), st, g, net->w2t, 256, 32, EpiStore{net->tt2, 32});
         }
-        // one resident wave of workgroups at six waves per SIMD (80 registers, 20 bytes of scratch): the kernel is a per-env chain of
-        // dependent steps, so its time falls with the workgroups in flight -- 768: 175 us per 8 192-env chunk, 1 024: 143, 1 280: 121-125, 1 536:
-        // 116 (round 4; the 32 KB LDS accumulators that had made 1 280 slower than 1 024 in round 3 are registers since then)
-        static const int hgw = resident_grid((const void *)conv1_wgrad_shared_kernel, 1536);
-        // conv1_wgrad_indexed_kernel runs on THIS grid too, taken from the other kernel's occupancy on purpose: the workgroup an env falls to
-        // decides the order of the slab sums, and GRL_OBS_INDEX=off / on are held bit for bit against each other (tests/test_gpu_obs_index.py).
-        // Both kernels are bound to six waves per SIMD, so the grid is one resident wave of workgroups for either.  Without that test the
-        // barrier-free kernel could take fewer, wider workgroups (fewer 32 KB slabs to write and reduce): not measured.
-        const int wblocks = nenv < hgw ? nenv : hgw;
-        if (net->obs_index)
-            hipLaunchKernelGGL(conv1_wgrad_indexed_kernel, dim3(wblocks), dim3(256), 0, st, (const unsigned *)net->obsrec, (const float *)net->gt, nenv,
-                               net->slab64);
-        else
-            hipLaunchKernelGGL(conv1_wgrad_shared_kernel, dim3(wblocks), dim3(256), 0, st, lb, ab, (const float *)net->gt, nenv,
-                               net->h->cfg.grid_size, net->slab64);
-        RJob j{};
-        j.kind = RJ_SLAB64; j.blocks = 4096 / 16; j.i0 = wblocks; j.p0 = net->slab64; j.d0 = Gr + ConvOffsets::c1w;
-        rq_push(net, RD_C1W_CNT, j);
-    } else {
-        if ((rc = colsum_launch(net, RD_C2B, net->ga2, n * 81, 64, Gr + ConvOffsets::c2b))) return rc;
-        if ((rc = colsum_launch(net, RD_C1B, net->ga1, n * 400, 32, Gr + ConvOffsets::c1b))) return rc;
-        // ---- conv1 weights (sparse)
-        hipLaunchKernelGGL(conv1_wgrad_kernel, dim3(blocks), dim3(256), 0, st, lb, ab, pos, net->ga1, nenv, net->h->cfg.grid_size,
-                           net->slab64, (const float *)nullptr);
+        float *cslab = slab_take(net, (size_t)4 * cpc * 8192);
+        if (!cslab) return paac_fail(net, GRL_E_INVALID, "class corrections: slab too small");
+        {
+            GemmTimer t(net, 4 * 2.0 * n * 256 * 32);
+            launch_tn<64, 32, 4, 1, T2SlotGather>(net, dim3(256 / 64, 1, 4 * cpc), st, g, net->dl2, 32, mc, cslab);      // one tap per I tile: its validity is per row
+        }
+        RJob j{};      // the grouped slab sum and conv2_corr_add's re-indexing into dW2 in one queued job
+        j.kind = RJ_GROUPS_C2; j.blocks = 4 * 8192 / 256; j.i0 = cpc; j.p0 = cslab; j.d0 = Gr + ConvOffsets::c2w;
+        rq_push(net, RD_C2W, j);
     }
-    if (!net->shared_trunk)
-        hipLaunchKernelGGL(slab64_reduce_kernel, dim3(6144 / 256), dim3(256), 0, st, net->slab64, blocks, 6144, Gr + ConvOffsets::c1w);
+    float *slab1h = net->slab1h, *slab1b_ds = net->slab1b + (size_t)2 * 2048 * 64;
+    // (both forms on the parent kernels' grids: the workgroup an env falls to decides the order of the sums)
+    if (net->obs_index)
+        hipLaunchKernelGGL(agent_ds_indexed_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, (const unsigned *)net->obsrec, net->tt2, npad, net->gt,
+                           P + ConvOffsets::c1w, nenv, slab1h, slab1b_ds);
+    else
+        hipLaunchKernelGGL(agent_ds_kernel, dim3(dblocks), dim3(256), 0, st, net->sraw, pos, net->tt2, npad, net->gt, P + ConvOffsets::c1w,
+                           nenv, slab1h, slab1b_ds);
+    {
+        RJob j{};
+        j.kind = RJ_ONEHOT; j.blocks = 2048 / 16; j.i0 = dblocks; j.p0 = slab1h; j.d0 = Gr + ConvOffsets::c1w;
+        rq_push(net, RD_C1W_HOT, j);
+        // conv1's bias gradient: the base part came out of the T2 GEMM's epilogue, agent_ds_kernel adds the sums of its corrections
+        RJob b{};
+        b.kind = RJ_NARROW; b.blocks = (32 + kNarrowCols - 1) / kNarrowCols; b.i0 = dblocks; b.i1 = 1; b.n = 32; b.p0 = slab1b_ds; b.d0 = Gr + ConvOffsets::c1b;
+        rq_push(net, RD_C1B, b);
+    }
+    // one resident wave of workgroups at six waves per SIMD (80 registers, 20 bytes of scratch): the kernel is a per-env chain of
+    // dependent steps, so its time falls with the workgroups in flight -- 768: 175 us per 8 192-env chunk, 1 024: 143, 1 280: 121-125, 1 536:
+    // 116 (round 4; the 32 KB LDS accumulators that had made 1 280 slower than 1 024 in round 3 are registers since then)
+    static const int hgw = resident_grid((const void *)conv1_wgrad_shared_kernel, 1536);
+    // conv1_wgrad_indexed_kernel runs on THIS grid too, taken from the other kernel's occupancy on purpose: the workgroup an env falls to
+    // decides the order of the slab sums, and GRL_OBS_INDEX=off / on are held bit for bit against each other (tests/test_gpu_obs_index.py).
+    // Both kernels are bound to six waves per SIMD, so the grid is one resident wave of workgroups for either.  Without that test the
+    // barrier-free kernel could take fewer, wider workgroups (fewer 32 KB slabs to write and reduce): not measured.
+    const int wblocks = nenv < hgw ? nenv : hgw;
+    if (net->obs_index)
+        hipLaunchKernelGGL(conv1_wgrad_indexed_kernel, dim3(wblocks), dim3(256), 0, st, (const unsigned *)net->obsrec, (const float *)net->gt, nenv,
+                           net->slab64);
+    else
+        hipLaunchKernelGGL(conv1_wgrad_shared_kernel, dim3(wblocks), dim3(256), 0, st, lb, ab, (const float *)net->gt, nenv,
+                           net->h->cfg.grid_size, net->slab64);
+    RJob j{};
+    j.kind = RJ_SLAB64; j.blocks = 4096 / 16; j.i0 = wblocks; j.p0 = net->slab64; j.d0 = Gr + ConvOffsets::c1w;
+    rq_push(net, RD_C1W_CNT, j);
+    return GRL_OK;
+}
+
+// The stages above in the one order that keeps the gradient's bits.  Two things here are order, not style:
+//  - rq_push per destination (RD_*): the k-th job queued for a destination runs in phase k of rq_flush, so the order of the pushes is the
+//    order of the float sums into that gradient (RD_D1W: per env, then the patch slices; RD_C3W, RD_C2W, RD_C1B, RD_C2B likewise);
+//  - slab_take / slabb_take, in order and size: a request that does not fit flushes the queue first, and the jobs queued by then are
+//    summed into the gradient ahead of every later one.  A stage that moves, or a slab that changes size, moves that point.
+static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, int nenv,
+                               const float *actions, const float *adv, const float *y, float inv_total, long slot,
+                               const float *pmu, const float *psg, const float *pval) {
+    const BwdCtx c{net, net->h->stream, net->params, net->grads, nenv * 10, nenv, net->trunk_skip && net->expand2_gemm};
+    const bool shared = net->shared_trunk;
+    bind_activations(net, slot);
+    // pmu / psg / pval: the heads' outputs the ROLLOUT computed for these samples (same parameters, same kernel: the same bits); with
+    // the dense stack resident too, the gradient step does not evaluate the heads again (49 us and 252 MB per chunk)
+    const bool have_heads = slot >= 0 && pmu && psg && pval;
+    int rc = forward_chunk(net, lb, ab, pos, nenv, tb.cmu, tb.csigma, tb.cvs, slot >= 0, have_heads);
+    if (rc) return rc;
+    // the observation's index record for conv1's backward helpers at the end of this pass: a small kernel, enqueued here so that it runs
+    // behind the GEMMs in between (lane scratch like the trunk lists: rebuilt per pass, not kept with the rollout)
+    if (shared && net->obs_index && (rc = obs_index(net, lb, ab, pos, nenv, net->obsrec, c.st, 2))) return rc;
+    if ((rc = bwd_heads(c, tb, have_heads ? pmu : tb.cmu, have_heads ? psg : tb.csigma, have_heads ? pval : tb.cvs, actions, adv, y, inv_total))) return rc;
+    net->prof_tag_cur = shared ? PT_DENSE_DGRAD : PT_PER_AGENT;
+    if ((rc = bwd_dense_dgrad(c))) return rc;
+    if (shared) {
+        if ((rc = bwd_dense1_dgrad(c)) || (rc = bwd_conv3_dgrad(c)) || (rc = bwd_slot_dgrad(c)) || (rc = bwd_conv2_dgrad(c))) return rc;
+    } else if ((rc = bwd_per_agent_dgrad(c))) return rc;
+    PAAC_HIP(net, hipGetLastError());
+    net->prof_tag_cur = shared ? PT_DENSE_WGRAD : PT_PER_AGENT;
+    if ((rc = bwd_dense_wgrad(c))) return rc;
+    if (shared) {
+        if ((rc = bwd_dense1_wgrad(c)) || (rc = bwd_conv3_wgrad(c)) || (rc = bwd_conv2_wgrad(c)) || (rc = bwd_class_corr_conv1(c, lb, ab, pos))) return rc;
+    } else if ((rc = bwd_per_agent_wgrad(c, lb, ab, pos))) return rc;
     PAAC_HIP(net, hipGetLastError());
     // the chunk's queued folds into the lane's gradient accumulator: one launch per phase (net_reduce.inc)
     return rq_flush(net);

@@ -1,9 +1,13 @@
 """The three PAAC nets (conv on Swarm, flat GRU on Solow and TradeAR1, field net) on small fixed scenarios, a SHA-256 per buffer: do
 two builds compute the same bits?
 
-    python tools/paac_bits.py [--baseline PARENT_CHECKOUT] [--json OUT]
+    python tools/paac_bits.py [--baseline PARENT_CHECKOUT] [--json OUT] [--conv-envs N --conv-chunk C]
 
-conv     3 envs (30 samples, chunks of 20: one full and a ragged one).
+conv     3 envs (30 samples, chunks of 20: one full and a ragged one) and 256 envs (one chunk of 2560 samples: the pixel-major
+         branches of nenv % 256 == 0), in every configuration of CONV_CONFIGS: the create flags and the GRL_* knobs that choose a
+         launch of the gradient step.  The knobs are read when the net is created and some are per-process statics, so each
+         configuration runs in a fresh child process with its own environment, one after the other.
+         --conv-envs N --conv-chunk C: one more run at that size, default configuration only.
 solow    70 envs (one full 64-sample group and a ragged one), rnn 5.          Each of the two flat envs three times: as it is, with
 trade    TradeAR1 with 2 assets, 70 envs.                                     set_keep_activations(True), and with a world-size-1
                                                                               communicator (comm_init + comm_broadcast_params) in front.
@@ -28,6 +32,26 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LOSSES = ("loss", "policy_loss", "critic_loss_mean")
 FLAT = tuple((k, v) for k in ("solow", "trade") for v in ("", ".keep", ".comm"))
+# name -> (GrlNetConfig.reserved flags, environment of the child process)
+CONV_CONFIGS = {
+    "default": (0, {}),
+    "per_agent_trunk": (1, {}), "recompute_forward": (2, {}), "single_stream": (4, {}),
+    "trunk_skip_off": (0, {"GRL_TRUNK_SKIP": "off"}),
+    "expand2_lds": (0, {"GRL_NET_EXPAND2": "lds"}),
+    "patch_skip_off": (0, {"GRL_PATCH_SKIP": "off"}),
+    "obs_index_off": (0, {"GRL_OBS_INDEX": "off"}),
+    "pwgrad_pair_off": (0, {"GRL_PATCH_WGRAD_PAIR": "off"}),
+    "pwgrad_pair_off_xcd0": (0, {"GRL_PATCH_WGRAD_PAIR": "off", "GRL_PATCH_WGRAD_XCD": "0"}),
+    "pwgrad_pair_off_xcd2": (0, {"GRL_PATCH_WGRAD_PAIR": "off", "GRL_PATCH_WGRAD_XCD": "2"}),
+    "pwgrad_xcd0": (0, {"GRL_PATCH_WGRAD_XCD": "0"}),
+    "pdgrad_pair_off": (0, {"GRL_PATCH_DGRAD_PAIR": "off"}),
+    "pdgrad_pair_off_xcd0": (0, {"GRL_PATCH_DGRAD_PAIR": "off", "GRL_PATCH_DGRAD_XCD": "0"}),
+    "swgrad_pair_off": (0, {"GRL_SLOT_WGRAD_PAIR": "off"}),
+    "swgrad_chunks3": (0, {"GRL_SLOT_WGRAD_CHUNKS": "3"}),
+    "tn_wgs256": (0, {"GRL_TN_WGS": "256"}),
+    "tn_wgs_dense128": (0, {"GRL_TN_WGS_DENSE": "128"}),
+}
+CONV_SIZES = ((3, 20), (256, 2560))      # (envs, max_chunk_samples)
 
 
 def sha(a):
@@ -64,12 +88,12 @@ def trainer(net, rollout, read, exact):
     return out, fig
 
 
-def conv():
+def conv(E, chunk, flags):
     from goldsrl import _ffi, _ffi_net
-    E, T = 3, 2
+    T = 2
     eng = _ffi.Engine(_ffi.ENV_SWARM, E, seed=1692)
     eng.reset()
-    net = _ffi_net.ConvNet(eng, max_chunk_samples=20)
+    net = _ffi_net.ConvNet(eng, max_chunk_samples=chunk, reserved=flags)
     net.set_params(_ffi_net.glorot_uniform_flat(seed=3))
     B = E * 10
     shapes = {"actions": ((T, B, 2), np.float32), "values": ((T, B), np.float32), "rewards": ((T, B), np.float32), "y": ((T, B), np.float32),
@@ -82,6 +106,22 @@ def conv():
     res = trainer(net, rollout, lambda: [(k, net.read_rollout(k, s, d)) for k, (s, d) in shapes.items()], True)
     net.close(); eng.close()
     return res
+
+
+def conv_configs(a):
+    """every configuration at every size, a child process each: -> {"conv.<config>.<envs>x<chunk>": (hashes, figures)}"""
+    runs = {}
+    tmp = (a.json or os.path.join(os.getcwd(), "paac_bits.json")) + ".conv"
+    for name, (_, env) in CONV_CONFIGS.items():
+        print("conv configuration %s" % name, file=sys.stderr, flush=True)
+        cmd = [sys.executable, os.path.abspath(__file__), "--root", a.root, "--conv-config", name, "--json", tmp]
+        if name == "default" and a.conv_envs:
+            cmd += ["--conv-envs", str(a.conv_envs), "--conv-chunk", str(a.conv_chunk)]
+        subprocess.run(cmd, check=True, env=dict(os.environ, **env), stdout=subprocess.DEVNULL)
+        with open(tmp) as f:
+            runs.update({k: (v, {}) for k, v in json.load(f)["hashes"].items()})
+        os.remove(tmp)
+    return runs
 
 
 def flat(kind, variant):
@@ -141,15 +181,26 @@ def main():
     p.add_argument("--root", default=os.path.dirname(HERE), help="the checkout whose library and package run")
     p.add_argument("--baseline", help="a built checkout of the commit to compare against")
     p.add_argument("--json", help="write the result here as well")
+    p.add_argument("--conv-envs", type=int, default=0, help="one more conv run with this many envs (default configuration only)")
+    p.add_argument("--conv-chunk", type=int, default=0, help="max_chunk_samples of that run")
+    p.add_argument("--conv-config", help="(the child process of one configuration: the conv scenario alone, at every size)")
     a = p.parse_args()
+    if bool(a.conv_envs) != bool(a.conv_chunk):
+        p.error("--conv-envs and --conv-chunk go together")
     sys.path.insert(0, os.path.join(os.path.abspath(a.root), "golds-rl-gym_amd"))
-    runs = {"conv": conv(), "field": field()}
-    for kind, variant in FLAT:
-        runs[kind + variant] = flat(kind, variant)
+    if a.conv_config:
+        sizes = CONV_SIZES + (((a.conv_envs, a.conv_chunk),) if a.conv_envs else ())
+        runs = {"conv.%s.%dx%d" % (a.conv_config, E, c): conv(E, c, CONV_CONFIGS[a.conv_config][0]) for E, c in sizes}
+    else:
+        runs = conv_configs(a)
+        runs["field"] = field()
+        for kind, variant in FLAT:
+            runs[kind + variant] = flat(kind, variant)
     out = {"hashes": {k: v[0] for k, v in runs.items()}, "figures_rtol_1e-6": {k: v[1] for k, v in runs.items() if v[1]}}
     if a.baseline:
         tmp = (a.json or os.path.join(os.getcwd(), "paac_bits.json")) + ".baseline"
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--root", a.baseline, "--json", tmp], check=True,
+        extra = ["--conv-envs", str(a.conv_envs), "--conv-chunk", str(a.conv_chunk)] if a.conv_envs else []
+        subprocess.run([sys.executable, os.path.abspath(__file__), "--root", a.baseline, "--json", tmp] + extra, check=True,
                        env={k: v for k, v in os.environ.items() if k != "PYTHONPATH"}, stdout=subprocess.DEVNULL)
         with open(tmp) as f:
             base = json.load(f)
