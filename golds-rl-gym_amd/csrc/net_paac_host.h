@@ -210,12 +210,18 @@ __global__ __launch_bounds__(BLOCK) void paac_sumsq_kernel(const float *__restri
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-// tf.train.AdamOptimizer (TF 1.4): m, v update, p -= lr_t * m / (sqrt(v) + eps), lr_t folded on the host; stats[4] = the clip factor
+// tf.train.AdamOptimizer (TF 1.4): m, v update, p -= lr_t * m / (sqrt(v) + eps), lr_t folded on the host; stats[4] = the clip factor.
+// The one Adam arithmetic of the tree: beta1, 1 - beta1, beta2, 1 - beta2 and eps are the float32 literals below (1.0f - 0.999f
+// computed in float32 is 1.3e-5 low, relative: 216 roundings of v).
+// range_flag (nullptr: no check): the sticky fp16-range flag of the conv net's GEMMs (net_gemm.h).  When it is set the gradient of
+// this pass was computed from inf / NaN operands: the update is skipped ON THE DEVICE, so the call that then fails with
+// GRL_E_RANGE leaves the parameters and the Adam moments exactly as they were (with ranks the flag is max-reduced next to the
+// gradient: every replica skips together).
 template <typename F = float>
 __global__ void paac_adam_kernel(F *__restrict__ p, const F *__restrict__ g, F *__restrict__ m, F *__restrict__ v, long n,
-                                 const float *__restrict__ stats, float lr_t) {
+                                 const float *__restrict__ stats, float lr_t, const int *__restrict__ range_flag = nullptr) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || (range_flag && *range_flag)) return;
     float gi = g[i] * stats[4];
     float mi = 0.9f * m[i] + 0.1f * gi;
     float vi = 0.999f * v[i] + 0.001f * gi * gi;

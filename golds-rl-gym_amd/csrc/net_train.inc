@@ -655,22 +655,6 @@ __global__ void finalize_stats_kernel(const double *__restrict__ partial, int np
     stats[4] = grad_scale * (clip_norm > 0.f ? clip_norm / fmaxf(norm, clip_norm) : 1.0f);
 }
 
-// tf.train.AdamOptimizer (TF 1.4): m,v update, p -= lr_t * m / (sqrt(v) + eps), lr_t folded on the host
-// range_flag: the sticky fp16-range flag of the GEMMs (net_gemm.h).  When it is set the gradient of this pass was computed from
-// inf / NaN operands: the update is skipped ON THE DEVICE, so the call that then fails with GRL_E_RANGE leaves the parameters and
-// the Adam moments exactly as they were (with ranks the flag is max-reduced next to the gradient: every replica skips together).
-__global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
-                            long n, const float *__restrict__ stats, float lr_t, float b1, float b2, float eps,
-                            const int *__restrict__ range_flag) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || *range_flag) return;
-    float gi = g[i] * stats[4];
-    float mi = b1 * m[i] + (1.0f - b1) * gi;
-    float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
-}
-
 // after Adam: the flag of the gradient pass (what Adam just looked at) moves into the net's latch word and the device flag starts
 // from zero for what follows -- the background pass of refresh_transposes runs fp16 GEMMs on the UPDATED parameters, and a flag
 // raised there says nothing about the update that was just applied (train_apply)
@@ -1436,9 +1420,8 @@ static int train_apply(grl_net *net, float inv_total, float lr, int apply_update
         net->adam_t += 1;
         net->param_version += 1;
         const float lr_t = adam_lr_t(lr, net->adam_t);
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((net->ho.total + 255) / 256)), dim3(256), 0, st, net->params, net->grads,
-                           net->adam_m, net->adam_v, (long)net->ho.total, net->stats, lr_t, 0.9f, 0.999f, 1e-8f,
-                           (const int *)range_flag_ptr(net));
+        hipLaunchKernelGGL(paac_adam_kernel<>, dim3((unsigned)((net->ho.total + 255) / 256)), dim3(256), 0, st, net->params, net->grads,
+                           net->adam_m, net->adam_v, (long)net->ho.total, net->stats, lr_t, (const int *)range_flag_ptr(net));
         // the gradient pass's flag is settled HERE: what refresh_transposes' background GEMMs raise belongs to the next pass
         hipLaunchKernelGGL(range_latch_kernel, dim3(1), dim3(1), 0, st, range_flag_ptr(net), latch);
         refresh_transposes(net);
@@ -1457,7 +1440,7 @@ static int train_apply(grl_net *net, float inv_total, float lr, int apply_update
     if (apply_update) {
         int lflag = 0;
         PAAC_HIP(net, hipMemcpy(&lflag, latch, sizeof(int), hipMemcpyDeviceToHost));
-        if (lflag) {      // rollout + backward of this update: adam_kernel skipped the update on the device, parameters and moments are intact
+        if (lflag) {      // rollout + backward of this update: paac_adam_kernel skipped the update on the device, parameters and moments are intact
             net->range_bits_last = lflag;
             net->adam_t -= 1;      // (param_version stays advanced: the retry recomputes its forward passes in the form it runs in)
             // (the background pass ran on the unchanged parameters: whatever it raised is that of the rows already in use)

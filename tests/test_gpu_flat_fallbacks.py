@@ -25,6 +25,7 @@ import contextlib
 import numpy as np
 import pytest
 
+import _adam_oracle as AO
 import _async_scenarios as SC
 import _flat_cases as FC
 import _flat_oracle as FO
@@ -252,17 +253,10 @@ def test_a_net_without_an_argument_slot_rolls_out_as_the_graph_of_launches(case,
 def _adam_bounds(params, grads, opt, opt1, params1, lr, clip_norm):
     """Section d of test_the_keeping_rollout_and_its_update_match_the_oracle: clip + Adam on the device's own gradient, every
     operation to float32 rounding."""
-    gc, _ = NN.clip_by_global_norm(grads.astype(np.float64), clip_norm)
-    m0, v0, step = opt["adam_m"].astype(np.float64), opt["adam_v"].astype(np.float64), opt["adam_step"]
-    p_ref, m_ref, v_ref = NN.adam_step(params.astype(np.float64), gc, m0, v0, step + 1, lr)
+    step = opt["adam_step"]
     assert opt1["adam_step"] == step + 1
-    u = 8 * 2.0 ** -24
-    m_tol = u * (np.abs(m0) + np.abs(gc))
-    assert (np.abs(opt1["adam_m"] - m_ref) <= m_tol).all()
-    assert (np.abs(opt1["adam_v"] - v_ref) <= u * v_ref + 1e-37).all()
-    lr_t = lr * np.sqrt(1 - 0.999 ** (step + 1)) / (1 - 0.9 ** (step + 1))
-    p_tol = u * np.abs(p_ref) + lr_t * (m_tol + u * np.abs(m_ref)) / (np.sqrt(v_ref) + 1e-8)
-    assert (np.abs(params1 - p_ref) <= p_tol).all(), np.abs(params1 - p_ref).max()
+    ref = AO.reference(grads, opt["adam_m"], opt["adam_v"], params, step + 1, lr, clip_norm)
+    AO.assert_within(ref, params1, opt1["adam_m"], opt1["adam_v"])
     assert not np.array_equal(params1, params)
 
 

@@ -121,7 +121,7 @@ else:
     f = one(P + "_trace/*/*_kernel_trace.csv")
     rows = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(f)))
     # the two timed updates end with adam_kernel; the window = from the adam of the warm-up update to the adam ending timed update 2
-    adams = [e for s, e, k in rows if k.startswith("grl::adam_kernel")]
+    adams = [e for s, e, k in rows if "adam_kernel" in k]
     lo, hi = adams[0], adams[2]
     sel = [r for r in rows if lo <= r[0] and r[1] <= hi]
     busy, cur_s, cur_e = 0, None, None

@@ -1,8 +1,8 @@
 """Four-stream timeline of the timed configuration from a rocprofv3 --kernel-trace CSV: how much of the wall clock runs with 1, 2, 3, 4+
 kernels in flight, which kernels are the ones running ALONE (and for how long), per-queue busy shares, and the longest stretches during
 which only small-grid kernels are resident.  usage: python tools/trace_concurrency.py <trace dir> [updates in the window = 2]
-(window: bench.py --steps 2 --warmup 1 ends every update with adam_kernel; from the warm-up update's to the second timed update's --
-the single-stream roofline pass that follows is left out)."""
+(window: bench.py --steps 2 --warmup 1 ends every update with its Adam kernel -- grl::adam_kernel in older traces, paac_adam_kernel<float>
+since; from the warm-up update's to the second timed update's -- the single-stream roofline pass that follows is left out)."""
 import collections, csv, glob, re, sys
 f = glob.glob(sys.argv[1] + "/*/*_kernel_trace.csv")[0]
 rows = []
@@ -11,7 +11,7 @@ for r in csv.DictReader(open(f)):
     wg = int(r.get("Workgroup_Size_X", r.get("Workgroup_Size", 256)) or 256) * max(1, int(r.get("Workgroup_Size_Y", 1) or 1))
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", "?"), g // max(wg, 1)))
 rows.sort()
-adams = [e for s, e, k, q, w in rows if k.startswith("grl::adam_kernel")]
+adams = [e for s, e, k, q, w in rows if "adam_kernel" in k]
 nupd = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 lo, hi = adams[0], adams[nupd]
 sel = [r for r in rows if lo <= r[0] and r[1] <= hi]
