@@ -17,6 +17,7 @@
 
 #include "../../include/goldsrl_net.h"
 #include "common.h"
+#include "net_conv_switches.h"
 #include "net_gemm.h"
 #include "net_paac_host.h"
 #include "net_reduce.inc"
@@ -64,170 +65,159 @@ using GatherT2 = ConvGather<10, 10, 1, 1, -1, -1, 2, 2, 64, 9, 9, true>;      //
 constexpr int GRL_MAX_LANES = 8;
 constexpr int kLossScaleAt = 8, kLossBoundAt = 10;      // slots of grl_net::stats (net_train.inc: loss scale)
 constexpr int kRangeLatchAt = 12;                        // int: the range flag of a gradient pass, latched before the post-update background pass (train_apply)
-struct NetLane {
-    float *grads;              // this lane's gradient accumulator (lane 0's is THE gradient; lane 1's is added before the all-reduce)
+struct NetLane {      // NetLane{} is a lane with nothing allocated: every pointer null
+    float *grads = nullptr;    // this lane's gradient accumulator (lane 0's is THE gradient; the others' are added before the all-reduce)
     // forward activations (chunk)
-    float *a1, *a2, *a3, *d1, *d2, *p1, *v1, *v2;
+    float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *d1 = nullptr, *d2 = nullptr, *p1 = nullptr, *v1 = nullptr, *v2 = nullptr;
     // gradients of activations (chunk)
-    float *ga1, *ga2, *ga3, *gd1, *gd2, *gp1, *gv1, *gv2;
+    float *ga1 = nullptr, *ga2 = nullptr, *ga3 = nullptr, *gd1 = nullptr, *gd2 = nullptr, *gp1 = nullptr, *gv1 = nullptr, *gv2 = nullptr;
     // shared-trunk evaluation of conv1/conv2 (net_shared.inc): per-ENV tensors
-    float *sraw, *z2sh, *dz2, *gt;
+    float *sraw = nullptr, *z2sh = nullptr, *dz2 = nullptr, *gt = nullptr;
     // shared conv3 gradients: per-env a2sh = relu(z2sh), DZ3; per (agent, slot <= 9 touched conv2 pixels): pixel id,
     // a2_a[u], a2_a[u] - a2sh[u], T3(dz3_a)[u], masked dz2_a[u]; tmpw3: correction GEMM output before the tap flip
-    float *a2sh, *d2s, *gsl, *dza, *dz3sh, *tmpw3;
-    unsigned long long *m2s;   // ReLU mask of the touched conv2 pixels: one word of 64 channel bits per compact slot row
-    float *dl2, *tt2, *tmpw2;   // conv2-level corrections as class-major GEMM operands (net_shared.inc)
-    int2 *t2desc;               // ... and the gather descriptors of their A rows (T2SlotGather)
+    float *a2sh = nullptr, *d2s = nullptr, *gsl = nullptr, *dza = nullptr, *dz3sh = nullptr, *tmpw3 = nullptr;
+    unsigned long long *m2s = nullptr;   // ReLU mask of the touched conv2 pixels: one word of 64 channel bits per compact slot row
+    float *dl2 = nullptr, *tt2 = nullptr, *tmpw2 = nullptr;   // conv2-level corrections as class-major GEMM operands (net_shared.inc)
+    int2 *t2desc = nullptr;     // ... and the gather descriptors of their A rows (T2SlotGather)
     // shared conv3 forward: z3sh = conv3(a2sh) + b3 per env; the per-slot products (a2_a - a2sh)[u] . W3[tap]
     // (n*9 x 576) live in the a2 buffer, which has no other use in shared-trunk mode
-    float *z3sh;
+    float *z3sh = nullptr;
     // dense1 on the shared a3 (net_patch.inc): per-env a3sh and ysh = W^T a3sh + b; per agent the 5x5 patch values v3 and
     // differences d3 (1600 floats); group-sorted sample order for the patch GEMMs
-    float *a3sh, *d3, *ysh;
-    unsigned long long *m3;    // ReLU mask of the agent's 5x5 patch of a3: 25 words of 64 channel bits per sample
-    float *gd1sh, *gsh3, *g3p, *dz3p;     // gradient side: per-env sum of gd1, its dense1 data gradient, per-agent patch gradients
-    int *perm, *goffp, *blkcnt, *blkoff, *sbeg, *send, *sgrp, *binbase;
-    unsigned short *pkey, *prank;      // sort key of a sample (group, column span, row span) and its rank inside its workgroup (net_patch.inc)
-    unsigned *smask, *tmask, *zmask, *wmask;   // 25-bit patch support per sample / union per 128 sorted rows / per weight-gradient slice / slice union per sample
-    int *slot_of;                      // sorted slot of a sample (inverse of perm)
-    int2 *rowdesc;                     // gather descriptors of the compact slot rows (slot_rowdesc_kernel)
+    float *a3sh = nullptr, *d3 = nullptr, *ysh = nullptr;
+    unsigned long long *m3 = nullptr;    // ReLU mask of the agent's 5x5 patch of a3: 25 words of 64 channel bits per sample
+    float *gd1sh = nullptr, *gsh3 = nullptr, *g3p = nullptr, *dz3p = nullptr;     // gradient side: per-env sum of gd1, its dense1 data gradient, per-agent patch gradients
+    int *perm = nullptr, *goffp = nullptr, *blkcnt = nullptr, *blkoff = nullptr, *sbeg = nullptr, *send = nullptr, *sgrp = nullptr, *binbase = nullptr;
+    unsigned short *pkey = nullptr, *prank = nullptr;      // sort key of a sample (group, column span, row span) and its rank inside its workgroup (net_patch.inc)
+    unsigned *smask = nullptr, *tmask = nullptr, *zmask = nullptr, *wmask = nullptr;   // 25-bit patch support per sample / union per 128 sorted rows / per weight-gradient slice / slice union per sample
+    int *slot_of = nullptr;            // sorted slot of a sample (inverse of perm)
+    int2 *rowdesc = nullptr;           // gather descriptors of the compact slot rows (slot_rowdesc_kernel)
     // tap-class order of the slot rows (slot_sort, net_shared.inc): key / rank / live-tap mask per row, sort scratch, sorted -> compact
     // row, live-tap union per 256 sorted rows
-    unsigned char *skey;
-    unsigned short *srank, *stap;
-    int *sblkcnt, *sblkoff, *sbinbase, *sperm;
+    unsigned char *skey = nullptr;
+    unsigned short *srank = nullptr, *stap = nullptr;
+    int *sblkcnt = nullptr, *sblkoff = nullptr, *sbinbase = nullptr, *sperm = nullptr;
     // the shared trunk's affected conv2 rows (trunk_index, net_shared.inc): 81-bit mask per env, row list + live count
-    unsigned *tamask, *tbmask, *tcmask, *tnmask;      // (tnmask: blocks of sraw anybody reads) + 100-bit mask of touched 2x2 conv1 pixel blocks, 49-bit mask of affected conv3 outputs
-    int *trowlist, *tblklist, *tc3list, *trows_n, *twgcnt, *twgoff;      // their lists, live counts [conv2 rows, blocks, conv3 rows], scan scratch
-    unsigned *tumask;          // union of the chunk's conv3 masks (2 words)
-    unsigned *obsrec;          // the chunk's observation index records (obs_index_kernel, net_shared.inc): kObsWords words per env, rebuilt per backward pass
-    unsigned *tneed2;          // conv2 pixels inside the 3 x 3 windows of that union (3 words): what conv3 reads of a2sh
-    float *tubias;             // dense1's per-env bias under that union (trunk_ubias_kernel)
-    float *tug, *tuspix;       // gradient side: G = column sums of gd1sh (512), per-pixel closed-form sums (49 x 64)
-    float *tslab, *tsums;      // tslab: per-workgroup sums of dz2 over unaffected rows; tsums: [dz2 total 64 | unaffected 64]
-    unsigned *stmask, *szmask;      // ... and per row range of the slot weight gradient (slot_wgrad_launch)
-    int *sbase, *rowagent, *sblk;      // compact slot rows (net_shared.inc): prefix of per-sample slot counts, row -> sample, scan scratch
-    signed char *tilegroup, *org;
-    signed char *ulist;
-    float *slab;               // split-M partial sums
-    float *slab1h;             // one-hot conv1 tap partials of agent_ds_kernel
-    float *slabb;              // per-wave-tile column sums written by the EpiGradSum / EpiGradStride2 data-gradient GEMMs (bias gradients)
-    float *slab1b;             // per-workgroup sums of agent_ds_kernel's dS corrections (conv1's bias gradient)
-    float *cfold;              // kFoldParts x 32 partial sums of fold_class_sums_kernel
+    unsigned *tamask = nullptr, *tbmask = nullptr, *tcmask = nullptr, *tnmask = nullptr;      // (tnmask: blocks of sraw anybody reads) + 100-bit mask of touched 2x2 conv1 pixel blocks, 49-bit mask of affected conv3 outputs
+    int *trowlist = nullptr, *tblklist = nullptr, *tc3list = nullptr, *trows_n = nullptr, *twgcnt = nullptr, *twgoff = nullptr;      // their lists, live counts [conv2 rows, blocks, conv3 rows], scan scratch
+    unsigned *tumask = nullptr;          // union of the chunk's conv3 masks (2 words)
+    unsigned *obsrec = nullptr;          // the chunk's observation index records (obs_index_kernel, net_shared.inc): kObsWords words per env, rebuilt per backward pass
+    unsigned *tneed2 = nullptr;          // conv2 pixels inside the 3 x 3 windows of that union (3 words): what conv3 reads of a2sh
+    float *tubias = nullptr;             // dense1's per-env bias under that union (trunk_ubias_kernel)
+    float *tug = nullptr, *tuspix = nullptr;       // gradient side: G = column sums of gd1sh (512), per-pixel closed-form sums (49 x 64)
+    float *tslab = nullptr, *tsums = nullptr;      // tslab: per-workgroup sums of dz2 over unaffected rows; tsums: [dz2 total 64 | unaffected 64]
+    unsigned *stmask = nullptr, *szmask = nullptr;      // ... and per row range of the slot weight gradient (slot_wgrad_launch)
+    int *sbase = nullptr, *rowagent = nullptr, *sblk = nullptr;      // compact slot rows (net_shared.inc): prefix of per-sample slot counts, row -> sample, scan scratch
+    signed char *tilegroup = nullptr, *org = nullptr, *ulist = nullptr;
+    float *slab = nullptr;               // split-M partial sums
+    float *slab1h = nullptr;             // one-hot conv1 tap partials of agent_ds_kernel
+    float *slabb = nullptr;              // per-wave-tile column sums written by the EpiGradSum / EpiGradStride2 data-gradient GEMMs (bias gradients)
+    float *slab1b = nullptr;             // per-workgroup sums of agent_ds_kernel's dS corrections (conv1's bias gradient)
+    float *cfold = nullptr;              // kFoldParts x 32 partial sums of fold_class_sums_kernel
     // conv2 corrections as a GEMM (net_shared.inc): A rows, class sort, canonical-slot maps
-    float *carow;
-    int *cperm, *cblkcnt, *cblkoff, *cgoff, *cslot, *cinv;
-    signed char *ctilegroup;
-    double *slab64;
-    float *ro_mu;              // chunk-sized scratch of the gradient step (cmu csigma cvs dzh cact cadv cy)
-    float *ws_a3, *ws_d1, *ws_d2, *ws_p1, *ws_v1, *ws_v2, *ws_a3sh, *ws_d3;   // chunk workspace (the default binding)
-    unsigned long long *ws_m3;
+    float *carow = nullptr;
+    int *cperm = nullptr, *cblkcnt = nullptr, *cblkoff = nullptr, *cgoff = nullptr, *cslot = nullptr, *cinv = nullptr;
+    signed char *ctilegroup = nullptr;
+    double *slab64 = nullptr;
+    float *ro_mu = nullptr;              // chunk-sized scratch of the gradient step (cmu csigma cvs dzh cact cadv cy)
+    float *ws_a3 = nullptr, *ws_d1 = nullptr, *ws_d2 = nullptr, *ws_p1 = nullptr, *ws_v1 = nullptr, *ws_v2 = nullptr, *ws_a3sh = nullptr, *ws_d3 = nullptr;   // chunk workspace (the default binding)
     // sign bits of d2 / v1 (4 + 8 words of 64 column bits per sample: EpiBiasActBits, net_gemm.h), bound like the activations
-    unsigned long long *mb_d2, *mb_v1, *ws_mb;
-    float *ws_sraw, *ws_a2sh, *ws_d2s;
-    unsigned long long *ws_m2s;
-    signed char *ws_ulist;
-    void *ws_idx[24];          // the chunk workspace of the index lists GRL_IDX_LIST names (bound like the activations at keep level 3)
-    bool train_ready;
+    unsigned long long *mb_d2 = nullptr, *mb_v1 = nullptr, *ws_mb = nullptr, *ws_m3 = nullptr, *ws_m2s = nullptr;
+    float *ws_sraw = nullptr, *ws_a2sh = nullptr, *ws_d2s = nullptr;
+    signed char *ws_ulist = nullptr;
+    void *ws_idx[24] = {};     // the chunk workspace of the index lists GRL_IDX_LIST names (bound like the activations at keep level 3)
+    bool train_ready = false;
 };
 
 // grl_net_eval (net_conv_eval.inc): the evaluation's own buffers, sized on first use and grown on demand, and what the last call kept
 struct NetEval {
-    double *rewards, *normals;                    // (cap_steps) (cap_norm,10,2)
-    int32_t *length;                              // (cap_envs)
-    uint8_t *finished, *alive;                    // (cap_envs) x 2
-    float *envact, *actions;                      // (cap_envs,10,2): the step's env action rows; (cap_act,10,2)
-    float *tr_mu, *tr_sigma, *tr_raw, *tr_value;  // (cap_trace,10,2) x 3, (cap_trace,10)
-    size_t cap_steps, cap_norm, cap_envs, cap_act, cap_trace;
-    int max_steps, trace_env, keep_actions;       // of the last evaluation; max_steps == 0: none (or an invalid one)
-    bool unchecked;                               // its forward passes' range flag has not been read yet
-    int flag_before;                              // the device's range flag as the evaluation found it (a rollout's, not yet trained on)
+    double *rewards = nullptr, *normals = nullptr;      // (cap_steps) (cap_norm,10,2)
+    int32_t *length = nullptr;                          // (cap_envs)
+    uint8_t *finished = nullptr, *alive = nullptr;      // (cap_envs) x 2
+    float *envact = nullptr, *actions = nullptr;        // (cap_envs,10,2): the step's env action rows; (cap_act,10,2)
+    float *tr_mu = nullptr, *tr_sigma = nullptr, *tr_raw = nullptr, *tr_value = nullptr;      // (cap_trace,10,2) x 3, (cap_trace,10)
+    size_t cap_steps = 0, cap_norm = 0, cap_envs = 0, cap_act = 0, cap_trace = 0;
+    int max_steps = 0, trace_env = 0, keep_actions = 0; // of the last evaluation; max_steps == 0: none (or an invalid one)
+    bool unchecked = false;                             // its forward passes' range flag has not been read yet
+    int flag_before = 0;                                // the device's range flag as the evaluation found it (a rollout's, not yet trained on)
 };
 
-struct grl_net : NetLane, grl::PaacCommNet {      // stats: [8..9] loss scale S and 1/S, [10] bits of the head-gradient bound, [12] the range latch
-    grl_net_config cfg;
-    int chunk;                 // samples per pass
-    float *paramsT;            // W^T of every GEMM layer at the same flat offsets ([N][K]: the forward's Bt operand)
-    float *w3t, *w2t;          // rearranged conv weights for the data gradients
-    float *w3f;                // w3f[(tap,co)][ci] = W3[tap][ci][co] (slot product GEMM of conv3's forward)
-    float *wpvT;               // [pol1_w | v1_w] transposed side by side: (1024, 256), the B operand of the one GEMM that computes both from d2
-    int shared_trunk;
-    // GEMM arithmetic: 0 = three fp16 products (operands must stay inside the fp16 range), 1 = v_mfma_f32_16x16x4_f32 (no range
-    // limit, 103 instead of 200 TFLOP/s).  A pass that raised the range flag switches the net to 1 (range_fallback below).
-    double sfrac;              // likewise for the conv3 slot GEMMs: executed share of the 9 taps (per 256-row tile)
-    double pfrac[3];           // executed share of the dense1 patch GEMMs' FLOPs in the last sorted chunk (profiling pass only; else 1)
+// stats: [8..9] loss scale S and 1/S, [10] bits of the head-gradient bound, [12] the range latch.  ConvSwitches (net_conv_switches.h):
+// what the environment chose when the net was created -- net->trunk_skip, net->gemm_f32, net->tn_wgs, ...; the table there says what
+// each one selects.  gemm_f32 and range_return_k move afterwards (the range fallback and its way back, grl_net_set_*).
+struct grl_net : NetLane, grl::PaacCommNet, grl::ConvSwitches {
+    grl_net_config cfg = {};
+    int chunk = 0;                       // samples per pass
+    float *paramsT = nullptr;            // W^T of every GEMM layer at the same flat offsets ([N][K]: the forward's Bt operand)
+    float *w3t = nullptr, *w2t = nullptr;      // rearranged conv weights for the data gradients
+    float *w3f = nullptr;                // w3f[(tap,co)][ci] = W3[tap][ci][co] (slot product GEMM of conv3's forward)
+    float *wpvT = nullptr;               // [pol1_w | v1_w] transposed side by side: (1024, 256), the B operand of the one GEMM that computes both from d2
+    int shared_trunk = 1;                // 0: GRL_NET_F_PER_AGENT_TRUNK, the plain per-agent evaluation (the A/B reference)
+    double pfrac[3] = {1.0, 1.0, 1.0};   // executed share of the dense1 patch GEMMs' FLOPs in the last sorted chunk (profiling pass only; else 1)
+    double sfrac = 1.0;                  // likewise for the conv3 slot GEMMs: executed share of the 9 taps (per 256-row tile)
     // the background's way through the trunk (trunk_background, net_shared.inc; per parameter version): the all-b1 image, [z2 | a2] of
     // its conv2 row, a2 at all 81 pixels, [z3 | a3] of its conv3 row, the one-row list of those passes
-    float *tbgimg, *tbgz, *tbgimg3, *tbgz3, *tybg;      // tybg[49][512]: a background pixel's contribution to dense1 (trunk_ybg_kernel)
-    int *tbglist;
-    int obs_index;             // 1: conv1's backward helpers read the observation's index record (GRL_OBS_INDEX=off: the kernels that index inside)
-    int trunk_skip;            // 1: conv2's forward / weight gradient / transposed convolution run over the rows the env's bins reach (GRL_TRUNK_SKIP=off: all rows)
-    int patch_skip;            // 1: the dense1 patch GEMMs skip what the support masks say is zero (GRL_PATCH_SKIP=off: the plain 5x5 patch)
-    int gemm_f32, range_fallback_on, range_fallbacks, range_bits_last, update_skipped_last;
+    float *tbgimg = nullptr, *tbgz = nullptr, *tbgimg3 = nullptr, *tbgz3 = nullptr, *tybg = nullptr;      // tybg[49][512]: a background pixel's contribution to dense1 (trunk_ybg_kernel)
+    int *tbglist = nullptr;
+    int range_fallbacks = 0, range_bits_last = 0, update_skipped_last = 0;
     // the way back: gemm_f32 was set BY a range violation (not by GRL_NET_GEMM=f32 / grl_net_set_gemm_f32), updates in a row whose
-    // largest |GEMM output| stayed below 65 504 / 4, how many of them take the net back (0: never), how often that happened
-    int f32_by_fallback, f32_clean_passes, range_return_k, range_returns;
-    float absmax_last;
-    int loss_scale_on;         // per-pass power-of-two scale of the head gradients (net_train.inc); GRL_NET_LOSS_SCALE=off disables it
-    int acc1;                  // gemm_rowk instances built with ACC1 use it (GRL_NET_ACC1=off: the two-accumulator form everywhere)
-    int expand3_gather;        // conv3's per-agent corrections as a gather GEMM at the patch pixels (default; GRL_NET_EXPAND3=prod: slot products + expansion kernel)
-    int expand2_gemm, ctiles;  // conv2's per-agent corrections as a class-sorted GEMM (default) or the LDS-resident kernel (GRL_NET_EXPAND2=lds)
-    float *w2corr;             // [4 classes][576][128] kernel slices of that GEMM, rebuilt with the transposes
-    grl::HeadOff ho;           // offsets of the head / value parameters for this net's num_actions
-    int npad, ptiles, pslices, pslice_rows, pwgrad_xcd, pdgrad_xcd, pwgrad_pair, pdgrad_pair, swgrad_pair, swgrad_chunks, slots_xcd;
-    int tn_wgs, tn_wgs_dense;  // workgroups a split-M weight-gradient launch aims at (slab count = tn_wgs / tiles)      // dense1 patch weight gradient: slice length and tile order (tuning knobs)
-    size_t slab_floats, slab_used, slabb_floats, slabb_used;      // bump allocation of a chunk's partial-sum regions (net_train.inc)
+    // largest |GEMM output| stayed below 65 504 / 4 (range_return_k of them take the net back), how often that happened
+    int f32_by_fallback = 0, f32_clean_passes = 0, range_returns = 0;
+    float absmax_last = 0.f;
+    float *w2corr = nullptr;             // [4 classes][576][128] kernel slices of conv2's correction GEMM, rebuilt with the transposes
+    grl::HeadOff ho = {};                // offsets of the head / value parameters for this net's num_actions
+    int npad = 0, ptiles = 0, ctiles = 0, pslices = 0;      // derived from the chunk: rows padded to 256, tiles of the patch / class sorts, weight-gradient slices
+    size_t slab_floats = 0, slab_used = 0, slabb_floats = 0, slabb_used = 0;      // bump allocation of a chunk's partial-sum regions (net_train.inc)
     std::vector<grl::RJob> rq;      // the chunk's queued reductions (net_reduce.inc)
     std::vector<int> rq_dst;
     // rollout storage (allocated by grl_net_rollout)
-    int T, B;
-    uint8_t *ro_lb, *ro_ab, *ro_pos, *ro_done;      // ro_done (T,E): episode_over after each step (R6 / tests; the grid return ignores it, Q5)
-    float *ro_act, *ro_envact, *ro_val, *ro_rew, *ro_y, *ro_adv, *ro_boot, *ro_pmu, *ro_psg;
-    float *mu, *sigma, *vs;    // (B,2) (B,2) (B) of the last predict
-    uint8_t *tmp_lb, *tmp_ab, *tmp_pos;
-    int tmp_envs;
-    bool prof_on;
+    int T = 0, B = 0;
+    uint8_t *ro_lb = nullptr, *ro_ab = nullptr, *ro_pos = nullptr, *ro_done = nullptr;      // ro_done (T,E): episode_over after each step (R6 / tests; the grid return ignores it, Q5)
+    float *ro_act = nullptr, *ro_envact = nullptr, *ro_val = nullptr, *ro_rew = nullptr, *ro_y = nullptr, *ro_adv = nullptr, *ro_boot = nullptr, *ro_pmu = nullptr, *ro_psg = nullptr;
+    float *mu = nullptr, *sigma = nullptr, *vs = nullptr;    // (B,2) (B,2) (B) of the last predict
+    uint8_t *tmp_lb = nullptr, *tmp_ab = nullptr, *tmp_pos = nullptr;
+    int tmp_envs = 0;
+    bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;
     std::vector<unsigned char> prof_tag;     // GRL_PROF_TAG_* of every bracketed launch
     std::vector<double> prof_launch_flops;
-    int prof_tag_cur;
-    size_t prof_used;
-    double prof_flops;
-    int last_n;                // samples in the last chunk (for read_activation)
+    int prof_tag_cur = 0;
+    size_t prof_used = 0;
+    double prof_flops = 0.0;
+    int last_n = 0;            // samples in the last chunk (for read_activation)
     // host clocks of the actor loop (grl_net_host_times)
-    long ht_rollouts, ht_updates;
-    double ht_rollout_ms, ht_train_enq_ms, ht_train_wait_ms;
-    double ht_train_t0;      // steady-clock ms at the entry of the gradient step in flight (0: none)
+    long ht_rollouts = 0, ht_updates = 0;
+    double ht_rollout_ms = 0.0, ht_train_enq_ms = 0.0, ht_train_wait_ms = 0.0;
+    double ht_train_t0 = 0.0;      // steady-clock ms at the entry of the gradient step in flight (0: none)
     // Rollout-resident activations: the rollout's forward pass writes its activations of every (step, chunk) into one
     // T*B-sample buffer (what 288 GB of HBM is for) and the gradient step reads them back instead of recomputing the
     // forward pass.  Exact: parameters do not change between the two (paac.py:302-387).  keep_version tracks that;
-    // GRL_NET_F_RECOMPUTE_FORWARD or too little free memory selects recomputation.
-    int keep_level;            // 0: nothing resident, 1: conv3/dense activations, 2: + the per-env trunk tensors the gradient step reads
+    // GRL_NET_F_RECOMPUTE_FORWARD or too little free memory selects recomputation.  How the level is chosen: ensure_rollout_bufs
+    // (net_train.inc) under keep_max_level / keep_free_cap of the switches; grl_net_keep_info reports the outcome.
+    int keep_level = 0;        // 0: nothing resident, 1: conv3/dense activations, 2: + the per-env trunk tensors the gradient step reads
                                // 3: + the chunk's index lists (GRL_IDX_LIST)
-    float *keep;
-    size_t keep_slots;
-    long param_version, keep_version;
-    // How the level is chosen (ensure_rollout_bufs, net_train.inc), read when the net is created: GRL_NET_KEEP_LEVEL=1..3 is the
-    // highest level tried (default 3); GRL_NET_KEEP_FREE_MB caps the free memory the choice sees (a comparison only: nothing is
-    // allocated for it), so that the descent 3 -> 2 -> 1 -> 0 can be walked at any size.  grl_net_keep_info reports the outcome.
-    int keep_max_level;
-    bool keep_free_capped;
-    size_t keep_free_cap, keep_headroom, keep_free_seen;
-    int resident_last;         // the last train_rollout* pass read the rollout's resident activations
-    float last_inv_total;      // 1 / samples of the last gradient pass (grl_net_apply_grads)
+    float *keep = nullptr;     // keep_slots slots of keep_floats_per_slot(level) floats
+    size_t keep_slots = 0;
+    long param_version = 0, keep_version = -1;
+    size_t keep_headroom = 0, keep_free_seen = 0;
+    int resident_last = 0;     // the last train_rollout* pass read the rollout's resident activations
+    float last_inv_total = 0.f;      // 1 / samples of the last gradient pass (grl_net_apply_grads)
     NetEval ev;
-    // lanes
-    NetLane lanes[GRL_MAX_LANES];
-    hipStream_t lane_stream[GRL_MAX_LANES];      // [0] = the handle's stream
-    hipEvent_t ev_fork, ev_join[GRL_MAX_LANES];
+    NetLane lanes[GRL_MAX_LANES];      // the parked workspaces; the current lane's lives in the NetLane base (use_lane)
+    hipStream_t lane_stream[GRL_MAX_LANES] = {};      // [0] = the handle's stream
+    hipEvent_t ev_fork = nullptr, ev_join[GRL_MAX_LANES] = {};
     // The index kernels of a forward pass that depend on the agents' positions alone (slot lists, class / slot / patch sorts: ~17 small
     // launches, each a dependent step of a few us) run on a side stream per lane beside the env-level trunk (net_shared.inc,
     // forward_conv12_shared): with one chunk per step -- 4 096 or 8 192 envs per GPU -- nothing else hides them (round 5).
-    hipStream_t side_stream[GRL_MAX_LANES];
-    hipEvent_t ev_side0[GRL_MAX_LANES], ev_side1[GRL_MAX_LANES], ev_side2[GRL_MAX_LANES];
-    int idx_side, side_now, pitem_on_side;      // side_now: set by grl_net_rollout while it enqueues a one-chunk-per-step rollout
-    int nlanes, cur_lane, last_lane;
+    hipStream_t side_stream[GRL_MAX_LANES] = {};
+    hipEvent_t ev_side0[GRL_MAX_LANES] = {}, ev_side1[GRL_MAX_LANES] = {}, ev_side2[GRL_MAX_LANES] = {};
+    int idx_side = 0, side_now = 0, pitem_on_side = 0;      // idx_side: lane 0 has a side stream; side_now: set by grl_net_rollout while it enqueues a one-chunk-per-step rollout
+    int nlanes = 1, cur_lane = 0, last_lane = 0;
 };
+static_assert(GRL_MAX_LANES == 8, "GRL_NET_LANES's row in net_conv_switches.h admits 1..8");
+
+namespace grl { static int lanes_fork(grl_net *net); static int lanes_join(grl_net *net); }
+#include "net_lane_scope.h"      // LanePass: the two above as a scope
 
 namespace grl {
 
@@ -239,8 +229,17 @@ static void use_lane(grl_net *net, int k) {
     net->h->stream = net->lane_stream[k];
     net->cur_lane = k;
 }
+// the handle enqueues on `now` (a lane's side stream) until the scope ends, whichever way it ends.  use_lane and this are the only
+// two places that move h->stream once grl_create has made it.
+struct StreamScope {
+    hipStream_t &slot, back;
+    StreamScope(grl_handle *h, hipStream_t now) : slot(h->stream), back(h->stream) { slot = now; }
+    ~StreamScope() { slot = back; }
+};
+// side_now (a one-chunk-per-step rollout or evaluation is being enqueued) goes back to 0 with the scope
+struct SideOff { grl_net *n; ~SideOff() { n->side_now = 0; } };
 static int lanes_active(const grl_net *net) { return net->prof_on ? 1 : net->nlanes; }
-// lane 1 sees everything enqueued on the main stream so far
+// every lane sees everything enqueued on the main stream (lane 0's) so far
 static int lanes_fork(grl_net *net) {
     if (lanes_active(net) < 2) return GRL_OK;
     use_lane(net, 0);
@@ -248,7 +247,7 @@ static int lanes_fork(grl_net *net) {
     for (int k = 1; k < net->nlanes; ++k) PAAC_HIP(net, hipStreamWaitEvent(net->lane_stream[k], net->ev_fork, 0));
     return GRL_OK;
 }
-// the main stream sees everything enqueued on lane 1; lane 0 becomes current again
+// the main stream sees everything enqueued on the other lanes; lane 0 becomes current again (first, so also when a call below fails)
 static int lanes_join(grl_net *net) {
     use_lane(net, 0);
     if (lanes_active(net) < 2) return GRL_OK;
@@ -831,97 +830,55 @@ static int forward_chunk(grl_net *net, const uint8_t *lb, const uint8_t *ab, con
 static int forward_all(grl_net *net, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, int n_envs, float *mu, float *sigma,
                        float *vs, long slot0 = -1) {
     const int ce = net->chunk / 10;
-    int rc = lanes_fork(net);
+    LanePass pass(net);
+    int rc = pass.begin();
     if (rc) return rc;
     const int nl = lanes_active(net);
     for (int e0 = 0; e0 < n_envs; e0 += ce) {
         int ne = n_envs - e0 < ce ? n_envs - e0 : ce;
-        use_lane(net, (e0 / ce) % nl);      // independent chunks alternate between the two streams
+        use_lane(net, (e0 / ce) % nl);      // independent chunks go round the lanes
         net->last_lane = net->cur_lane;
         bind_activations(net, slot0 < 0 ? -1 : slot0 + e0 / ce);
         rc = forward_chunk(net, lb + (size_t)e0 * 160, ab + (size_t)e0 * 20, pos + (size_t)e0 * 20, ne,
                            mu + (size_t)e0 * 10 * net->ho.A, sigma + (size_t)e0 * 10 * net->ho.A, vs + (size_t)e0 * 10);
-        if (rc) { (void)lanes_join(net); return rc; }
+        if (rc) return rc;
     }
-    return lanes_join(net);
+    return pass.finish();
 }
 
 // forward-pass workspace of the lane currently loaded into *net
 static int alloc_lane_forward(grl_net *n) {
     const size_t c = n->chunk;
+    const size_t ce = c / 10, b256 = (c + 255) / 256, ps = (size_t)n->pslices, pt = (size_t)n->ptiles, ct = (size_t)n->ctiles;
     int rc = GRL_OK;
-    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };
+    auto A = [&](auto **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };      // the order below is the order of the hipMallocs
     A(&n->grads, n->ho.total);
     // a2: the per-agent conv2 tensor of the dense form; in shared-trunk mode the workspace of conv3's gather form (net_patch.inc:
     // canonical cell blocks of ctiles * 256 rows, then the items' descriptors, tap masks, tile masks and sort counters)
-    const size_t gather_ws = (size_t)n->ctiles * 256 * 576 + (c * 25 + 256) * 4 + (c * 25 + 1024) + 2 * ((c + 255) / 256 + 1) * 64 + 4096;
+    const size_t gather_ws = ct * 256 * 576 + (c * 25 + 256) * 4 + (c * 25 + 1024) + 2 * (b256 + 1) * 64 + 4096;
     A(&n->a2, std::max(c * 5184, gather_ws)); A(&n->d1, c * 512); A(&n->d2, c * 256); A(&n->p1, c * 512); A(&n->v1, c * 512); A(&n->v2, c * 256);
     if (!n->shared_trunk) { A(&n->a1, c * 12800); A(&n->a3, c * 3136); }       // per-agent tensors the shared evaluation never forms
-    A(&n->sraw, (c / 10) * 12800); A(&n->z2sh, (c / 10) * 5184);
-    A(&n->a2sh, (c / 10) * 5184); A(&n->d2s, c * 9 * 64); if (rc == GRL_OK) rc = paac_alloc(n, &n->m2s, c * 9); A(&n->z3sh, (c / 10) * 3136);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->ulist, c * 9);
-    A(&n->a3sh, (c / 10) * 3136); A(&n->d3, c * 1600); if (rc == GRL_OK) rc = paac_alloc(n, &n->m3, c * 25); A(&n->ysh, (c / 10) * 512);
+    A(&n->sraw, ce * 12800); A(&n->z2sh, ce * 5184); A(&n->a2sh, ce * 5184); A(&n->d2s, c * 9 * 64); A(&n->m2s, c * 9); A(&n->z3sh, ce * 3136);
+    A(&n->ulist, c * 9); A(&n->a3sh, ce * 3136); A(&n->d3, c * 1600); A(&n->m3, c * 25); A(&n->ysh, ce * 512); A(&n->ws_mb, c * 12);
     n->ws_a3 = n->a3; n->ws_d1 = n->d1; n->ws_d2 = n->d2; n->ws_p1 = n->p1; n->ws_v1 = n->v1; n->ws_v2 = n->v2;
     n->ws_a3sh = n->a3sh; n->ws_d3 = n->d3; n->ws_m3 = n->m3;
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->ws_mb, c * 12);
     n->mb_d2 = n->ws_mb; n->mb_v1 = n->ws_mb + c * 4;
-    n->ws_sraw = n->sraw; n->ws_a2sh = n->a2sh; n->ws_d2s = n->d2s; n->ws_m2s = n->m2s; n->ws_ulist = n->ulist;
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->perm, (size_t)n->ptiles * 256);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->goffp, 32);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sbeg, n->pslices);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->send, n->pslices);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sgrp, n->pslices);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->blkcnt, ((c + 255) / 256) * PATCH_KEYS);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->blkoff, ((c + 255) / 256) * PATCH_KEYS);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->binbase, PATCH_KEYS);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->pkey, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->prank, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->smask, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tmask, (size_t)n->ptiles * 2 + 2);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->zmask, (size_t)n->pslices);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->wmask, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->slot_of, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tilegroup, (size_t)n->ptiles);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->org, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sbase, c + 1);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->rowagent, c * 9);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->rowdesc, c * 9);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sblk, 1024);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->skey, c * 9);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->srank, c * 9);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->stap, c * 9);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sblkcnt, ((c * 9 + 1023) / 1024 + 1) * 25);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sblkoff, ((c * 9 + 1023) / 1024 + 1) * 25);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sbinbase, 32);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->sperm, c * 9 + 256);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->stmask, (c * 9 + 255) / 256 + 1);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->szmask, 1024);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tamask, (c / 10) * 3 + 3);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->obsrec, (c / 10 + 1) * kObsWords);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tbmask, (c / 10) * 4 + 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tcmask, (c / 10) * 2 + 2);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tnmask, (c / 10) * 4 + 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->trowlist, (c / 10) * 81 + 256);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tblklist, (c / 10) * 100 + 256);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tc3list, (c / 10) * 49 + 256);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->trows_n, 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->twgcnt, ((c / 10 + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->twgoff, ((c / 10 + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tumask, 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tneed2, 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tubias, 512);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tug, 512);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tuspix, 49 * 64);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tslab, 2 * 2048 * 64);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tsums, 256);
-    A(&n->carow, c * 128);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->cperm, (size_t)n->ctiles * 256);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->cblkcnt, ((c + 255) / 256) * 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->cblkoff, ((c + 255) / 256) * 4);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->cgoff, 8);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->cslot, c * 9);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->cinv, c);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->ctilegroup, (size_t)n->ctiles);
+    n->ws_sraw = n->sraw; n->ws_a2sh = n->a2sh; n->ws_d2s = n->d2s; n->ws_m2s = n->m2s; n->ws_ulist = n->ulist;      // (the default binding: bind_activations)
+    A(&n->perm, pt * 256); A(&n->goffp, 32); A(&n->sbeg, ps); A(&n->send, ps); A(&n->sgrp, ps);      // the patch sort (net_patch.inc)
+    A(&n->blkcnt, b256 * PATCH_KEYS); A(&n->blkoff, b256 * PATCH_KEYS); A(&n->binbase, PATCH_KEYS); A(&n->pkey, c); A(&n->prank, c);
+    A(&n->smask, c); A(&n->tmask, pt * 2 + 2); A(&n->zmask, ps); A(&n->wmask, c); A(&n->slot_of, c); A(&n->tilegroup, pt); A(&n->org, c);
+    // the compact slot rows and their tap-class sort; the trunk's masks and row lists, the observation's index record (net_shared.inc)
+    A(&n->sbase, c + 1); A(&n->rowagent, c * 9); A(&n->rowdesc, c * 9); A(&n->sblk, 1024); A(&n->skey, c * 9); A(&n->srank, c * 9); A(&n->stap, c * 9);
+    A(&n->sblkcnt, ((c * 9 + 1023) / 1024 + 1) * 25); A(&n->sblkoff, ((c * 9 + 1023) / 1024 + 1) * 25); A(&n->sbinbase, 32);
+    A(&n->sperm, c * 9 + 256); A(&n->stmask, (c * 9 + 255) / 256 + 1); A(&n->szmask, 1024);
+    const size_t twg = ((ce + TRUNK_ENVS - 1) / TRUNK_ENVS + 1) * 3;
+    A(&n->tamask, ce * 3 + 3); A(&n->obsrec, (ce + 1) * kObsWords); A(&n->tbmask, ce * 4 + 4); A(&n->tcmask, ce * 2 + 2); A(&n->tnmask, ce * 4 + 4);
+    A(&n->trowlist, ce * 81 + 256); A(&n->tblklist, ce * 100 + 256); A(&n->tc3list, ce * 49 + 256); A(&n->trows_n, 4);
+    A(&n->twgcnt, twg); A(&n->twgoff, twg); A(&n->tumask, 4); A(&n->tneed2, 4); A(&n->tubias, 512); A(&n->tug, 512); A(&n->tuspix, 49 * 64);
+    A(&n->tslab, 2 * 2048 * 64); A(&n->tsums, 256);
+    A(&n->carow, c * 128);      // conv2's corrections as a GEMM: A rows, class sort, canonical-slot maps
+    A(&n->cperm, ct * 256); A(&n->cblkcnt, b256 * 4); A(&n->cblkoff, b256 * 4); A(&n->cgoff, 8); A(&n->cslot, c * 9);
+    A(&n->cinv, c); A(&n->ctilegroup, ct);
     if (rc == GRL_OK) {
         grl_net *net = n;
         int k = 0;
@@ -935,14 +892,12 @@ static int alloc_lane_forward(grl_net *n) {
 
 static int ensure_tmp_obs(grl_net *net, int n_envs) {
     if (net->tmp_envs >= n_envs) return GRL_OK;
-    int rc;
-    if ((rc = paac_alloc(net, &net->tmp_lb, (size_t)n_envs * 160))) return rc;
-    if ((rc = paac_alloc(net, &net->tmp_ab, (size_t)n_envs * 20))) return rc;
-    if ((rc = paac_alloc(net, &net->tmp_pos, (size_t)n_envs * 20))) return rc;
-    float *m, *s, *v;
-    if ((rc = paac_alloc(net, &m, (size_t)n_envs * 10 * net->ho.A))) return rc;
-    if ((rc = paac_alloc(net, &s, (size_t)n_envs * 10 * net->ho.A))) return rc;
-    if ((rc = paac_alloc(net, &v, (size_t)n_envs * 10))) return rc;
+    const size_t e = n_envs, heads = e * 10 * net->ho.A;
+    int rc = GRL_OK;
+    auto A = [&](auto **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(net, p, cnt); };
+    float *m = nullptr, *s = nullptr, *v = nullptr;
+    A(&net->tmp_lb, e * 160); A(&net->tmp_ab, e * 20); A(&net->tmp_pos, e * 20); A(&m, heads); A(&s, heads); A(&v, e * 10);
+    if (rc) return rc;
     net->mu = m; net->sigma = s; net->vs = v;
     net->tmp_envs = n_envs;
     return GRL_OK;
@@ -957,7 +912,7 @@ __global__ void grl_wait_kernel(long long ticks) {
     const long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
 }
-// picks a stream that runs BESIDE lane 0 (see grl_net_create) into n->side_stream[0], or leaves it null
+// picks a stream that runs BESIDE lane 0 (see side_stream_setup) into n->side_stream[0], or leaves it null
 static int side_stream_pick(grl_net *n) {
     hipStream_t lane = n->lane_stream[0];
     hipEvent_t e0 = nullptr, e1 = nullptr, ec = nullptr;
@@ -993,6 +948,25 @@ static int side_stream_pick(grl_net *n) {
     (void)hipGetLastError();
     return GRL_OK;
 }
+// The index side stream of lane 0 (used by a rollout with ONE chunk per step: grl_net_rollout; not in the single-stream profiling
+// configuration; GRL_NET_IDX_SIDE=off: never).  It must sit on ANOTHER hardware queue than lane 0: the runtime deals the streams of
+// a process onto four queues by their use counts, so after other handles and nets have come and gone a new stream may land on
+// the lane's own queue -- the side work then serialises with the lane and the events cost on top (49.3 instead of 43.4 ms per
+// 4 096-env update inside bench.py's shard leg, where lane 0 and its side stream shared queue 3; without it 45.7).  The HIP API does
+// not name a stream's queue, so up to five candidates are TIMED against the lane -- two 60 us waits side by side take 60 us on two
+// queues and 120 on one -- and the first that runs beside it is kept.  (Streams of another priority, or more than four queues,
+// are no way out: kernels of extra queues of one process interleave with ~40 us per 5 us kernel: 72 and 61 ms.)
+// Never an error: a net without a side stream (idx_side stays 0) runs the index kernels on the lane.
+static void side_stream_setup(grl_net *n) {
+    const bool want = !(n->cfg.reserved & GRL_NET_F_SINGLE_STREAM) && n->idx_side_asked;
+    if (want && side_stream_pick(n) == GRL_OK && n->side_stream[0]) {
+        const bool ok = hipEventCreateWithFlags(&n->ev_side0[0], hipEventDisableTiming) == hipSuccess &&
+                        hipEventCreateWithFlags(&n->ev_side1[0], hipEventDisableTiming) == hipSuccess &&
+                        hipEventCreateWithFlags(&n->ev_side2[0], hipEventDisableTiming) == hipSuccess;
+        n->idx_side = ok ? 1 : 0;
+    }
+    (void)hipGetLastError();
+}
 
 extern "C" {
 
@@ -1023,88 +997,34 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
         return fail(h, GRL_E_INVALID, "grl_net_create: max_chunk_samples must be a multiple of 10 in 10..131072");
     if (cfg->num_actions < 1 || cfg->num_actions > GRL_MAX_ACTIONS)
         return fail(h, GRL_E_INVALID, "grl_net_create: num_actions must be in 1..4");
-    bool free_capped = false;
-    unsigned long long free_mb = 0;
-    if (const char *e = getenv("GRL_NET_KEEP_FREE_MB")) {      // decimal digits only, below 2^44: anything else is refused, not read as 0
-        char *end = nullptr;
-        free_mb = strtoull(e, &end, 10);
-        if (*e < '0' || *e > '9' || *end != 0 || free_mb >= (1ull << 44))
-            return fail(h, GRL_E_INVALID, "grl_net_create: GRL_NET_KEEP_FREE_MB must be a number of MB (decimal digits)");
-        free_capped = true;
-    }
+    // the switches (net_conv_switches.h), before anything exists that a refusal would have to take down again
+    ConvSwitches sw;
+    const char *refused = nullptr;
+    if (conv_switches_read([](const char *name) -> const char * { return getenv(name); }, &sw, &refused))
+        return fail(h, GRL_E_INVALID, std::string("grl_net_create: ") + refused);
+    static_assert(PATCH_SLICE_ROWS == 1024, "GRL_PATCH_SLICE's default in net_conv_switches.h");
     hipSetDevice(h->cfg.device_id);
     grl_net *n = new grl_net();
+    static_cast<ConvSwitches &>(*n) = sw;
     n->h = h; n->cfg = *cfg; n->chunk = cfg->max_chunk_samples; n->alloc_waits = true;
     n->ho = head_offsets(cfg->num_actions); n->num_params = n->ho.total;
-    n->T = 0; n->B = 0; n->tmp_envs = 0; n->prof_on = false; n->prof_used = 0; n->prof_flops = 0; n->last_n = 0; n->prof_tag_cur = 0;
-    n->ro_lb = nullptr; n->slab_floats = 0; n->slab_used = 0; n->slabb_floats = 0; n->slabb_used = 0; n->w3t = n->w2t = nullptr;
-    n->mu = n->sigma = n->vs = nullptr;
-    n->keep_level = 0;
-    n->ht_rollouts = n->ht_updates = 0; n->ht_rollout_ms = n->ht_train_enq_ms = n->ht_train_wait_ms = 0.0; n->ht_train_t0 = 0.0;
-    n->keep = nullptr; n->keep_slots = 0; n->param_version = 0; n->keep_version = -1;
-    n->keep_max_level = 3; n->keep_free_capped = false; n->keep_free_cap = 0; n->keep_headroom = 0; n->keep_free_seen = 0;
-    n->resident_last = 0;
-    if (const char *e = getenv("GRL_NET_KEEP_LEVEL")) n->keep_max_level = atoi(e);      // A/B: 2 = re-index in the gradient step
-    n->keep_free_capped = free_capped; n->keep_free_cap = (size_t)free_mb << 20;
-    n->shared_trunk = (cfg->reserved & GRL_NET_F_PER_AGENT_TRUNK) ? 0 : 1;     // the plain per-agent evaluation is the A/B reference
-    n->cur_lane = 0; n->last_lane = 0;
-    for (int k = 0; k < GRL_MAX_LANES; ++k) { n->lane_stream[k] = nullptr; n->ev_join[k] = nullptr; n->side_stream[k] = nullptr; n->ev_side0[k] = n->ev_side1[k] = n->ev_side2[k] = nullptr; }
-    n->idx_side = 0; n->side_now = 0; n->pitem_on_side = 0;
-    n->lane_stream[0] = h->stream; n->ev_fork = nullptr; n->nlanes = 1;
+    n->shared_trunk = (cfg->reserved & GRL_NET_F_PER_AGENT_TRUNK) ? 0 : 1;
+    n->lane_stream[0] = h->stream;
+    // sizes that follow from the chunk
     const size_t c = n->chunk;
     n->ptiles = (int)((c + 255) / 256) + 9;
     n->ctiles = (int)((c + 255) / 256) + 4;
-    {   // A/B switch of the conv2 corrections (default: GEMM)
-        const char *lsk = getenv("GRL_NET_LOSS_SCALE");      // "off": S = 1, to show what the scale is for (tests)
-        n->loss_scale_on = (lsk && strcmp(lsk, "off") == 0) ? 0 : 1;
-        const char *gm = getenv("GRL_NET_GEMM"), *rf = getenv("GRL_NET_RANGE_FALLBACK");
-        n->gemm_f32 = (gm && strcmp(gm, "f32") == 0) ? 1 : 0;                    // force the fp32-MFMA form from the start (tests, A/B)
-        n->range_fallback_on = (rf && strcmp(rf, "off") == 0) ? 0 : 1;            // off: a range violation fails the call (GRL_E_RANGE) and nothing else
-        n->range_fallbacks = 0; n->range_bits_last = 0; n->update_skipped_last = 0;
-        n->f32_by_fallback = 0; n->f32_clean_passes = 0; n->range_returns = 0; n->absmax_last = 0.f;
-        n->range_return_k = 4;
-        if (const char *rr = getenv("GRL_NET_RANGE_RETURN")) n->range_return_k = strcmp(rr, "off") == 0 ? 0 : std::max(0, atoi(rr));
-        const char *psk = getenv("GRL_PATCH_SKIP");
-        n->patch_skip = (psk && strcmp(psk, "off") == 0) ? 0 : 1;
-        const char *oix = getenv("GRL_OBS_INDEX");
-        n->obs_index = (oix && strcmp(oix, "off") == 0) ? 0 : 1;
-        const char *tsk = getenv("GRL_TRUNK_SKIP");
-        n->trunk_skip = (tsk && strcmp(tsk, "off") == 0) ? 0 : 1;
-        n->pfrac[0] = n->pfrac[1] = n->pfrac[2] = 1.0; n->sfrac = 1.0;
-        const char *e2 = getenv("GRL_NET_EXPAND2");
-        n->expand2_gemm = (e2 && strcmp(e2, "lds") == 0) ? 0 : 1;
-        { const char *e3 = getenv("GRL_NET_EXPAND3"); n->expand3_gather = (e3 && strcmp(e3, "prod") == 0) ? 0 : 1;
-          const char *a1 = getenv("GRL_NET_ACC1"); n->acc1 = (a1 && strcmp(a1, "off") == 0) ? 0 : 1; }
-    }
-    n->pslice_rows = PATCH_SLICE_ROWS; n->pwgrad_xcd = 1;      // a row slice per XCD: A and B of a slice fetched once (under the support masks and the lighter traffic of round 3 this order wins by 0.7 %; 2 was the choice for the plain patch)
-    if (const char *e = getenv("GRL_PATCH_SLICE")) { const int v = atoi(e); if (v == 256 || v == 512 || v == 1024 || v == 2048 || v == 4096 || v == 8192) n->pslice_rows = v; }
-    if (const char *e = getenv("GRL_PATCH_WGRAD_XCD")) n->pwgrad_xcd = atoi(e);
-    n->pwgrad_pair = 1;      // 128 x 128 tiles over pairs of live patch pixels (PatchRowsPair, net_gemm.h); off: the 64 x 128 per-pixel tiles of round 3 (A/B, equality test)
-    if (const char *e = getenv("GRL_PATCH_WGRAD_PAIR")) n->pwgrad_pair = strcmp(e, "off") != 0 && strcmp(e, "0") != 0;
-    n->pdgrad_pair = 1;      // the same for the data gradient's N axis (PatchRowsPairN): 128 x 128 tiles on eight waves; off: 256 x 64 per pixel
-    if (const char *e = getenv("GRL_PATCH_DGRAD_PAIR")) n->pdgrad_pair = strcmp(e, "off") != 0 && strcmp(e, "0") != 0;
-    n->swgrad_pair = 1;      // conv3's slot weight gradient on 128 x 64 tiles of two live taps (SlotGatherT3PPair); off: 64 x 64 per tap
-    if (const char *e = getenv("GRL_SLOT_WGRAD_PAIR")) n->swgrad_pair = strcmp(e, "off") != 0 && strcmp(e, "0") != 0;
-    n->slots_xcd = 1;        // the sorted gather GEMMs keep a contiguous range of row tiles on one XCD (gemm_rowk, XCD_ORDER = 2); GRL_SLOTS_XCD=off: round-robin tiles
-    if (const char *e = getenv("GRL_SLOTS_XCD")) n->slots_xcd = strcmp(e, "off") != 0 && strcmp(e, "0") != 0;
-    n->swgrad_chunks = 0;    // tuning knob: row ranges of that launch (0: the default of the call site)
-    if (const char *e = getenv("GRL_SLOT_WGRAD_CHUNKS")) n->swgrad_chunks = std::max(0, atoi(e));
-    n->pdgrad_xcd = 1;      // M tile per XCD (A fetched once): 40.6 -> 38.5 ms per update at 81 920-sample chunks; spread (0) was faster at 40 960
-    n->tn_wgs = 1024; n->tn_wgs_dense = 512;
-    if (const char *e = getenv("GRL_TN_WGS")) { const int v = atoi(e); if (v >= 256 && v <= 4096) n->tn_wgs = v; }
-    if (const char *e = getenv("GRL_TN_WGS_DENSE")) { const int v = atoi(e); if (v >= 128 && v <= 4096) n->tn_wgs_dense = v; }
-    if (const char *e = getenv("GRL_PATCH_DGRAD_XCD")) n->pdgrad_xcd = atoi(e) != 0;
     n->pslices = (int)((c + n->pslice_rows - 1) / n->pslice_rows) + 9;
     n->npad = (int)((c + 255) / 256 * 256);
+    // what the net owns once, then what every lane owns
     int rc = GRL_OK;
-    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };
+    auto A = [&](auto **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(n, p, cnt); };
     A(&n->params, n->ho.total); A(&n->paramsT, n->ho.total); A(&n->adam_m, n->ho.total); A(&n->adam_v, n->ho.total);
     A(&n->w3f, 576 * 64); A(&n->stats, 16); A(&n->wpvT, (size_t)1024 * 256); A(&n->w2corr, 4 * 576 * 128);
-    A(&n->tbgimg, 12800); A(&n->tbgz, 128); A(&n->tbgimg3, 5184); A(&n->tbgz3, 128); A(&n->tybg, 49 * 512);
-    if (rc == GRL_OK) rc = paac_alloc(n, &n->tbglist, 4);
-    int nlanes = (cfg->reserved & GRL_NET_F_SINGLE_STREAM) ? 1 : 4;      // measured at 32 768 envs: 1.41 / 1.22 / 1.16 / 1.13 / 1.14 s per update with 1 / 2 / 3 / 4 / 8
-    if (const char *env = getenv("GRL_NET_LANES")) { int v = atoi(env); if (v >= 1 && v <= GRL_MAX_LANES) nlanes = v; }      // tuning knob
-    for (int k = 0; k < nlanes && rc == GRL_OK; ++k) {       // lane k's forward workspace (allocated into *n, then parked)
+    A(&n->tbgimg, 12800); A(&n->tbgz, 128); A(&n->tbgimg3, 5184); A(&n->tbgz3, 128); A(&n->tybg, 49 * 512); A(&n->tbglist, 4);
+    // the lanes: lane k's forward workspace is allocated into *n, then parked; streams and events for lanes 1.. ; then lane 0's side stream
+    const int nlanes = sw.lanes_asked ? sw.lanes_asked : (cfg->reserved & GRL_NET_F_SINGLE_STREAM) ? 1 : 4;
+    for (int k = 0; k < nlanes && rc == GRL_OK; ++k) {
         static_cast<NetLane &>(*n) = NetLane{};
         rc = alloc_lane_forward(n);
         n->lanes[k] = static_cast<NetLane &>(*n);
@@ -1117,26 +1037,7 @@ int grl_net_create(grl_handle *h, const grl_net_config *cfg, grl_net **out) {
                  hipEventCreateWithFlags(&n->ev_join[k], hipEventDisableTiming) == hipSuccess;
         if (!ok) rc = paac_fail(n, GRL_E_HIP, "creating the lane streams/events failed");
     }
-    if (rc == GRL_OK) n->nlanes = nlanes;
-    // The index side stream of lane 0 (used by a rollout with ONE chunk per step: grl_net_rollout; not in the single-stream profiling
-    // configuration; GRL_NET_IDX_SIDE=off: never).  It must sit on ANOTHER hardware queue than lane 0: the runtime deals the streams of
-    // a process onto four queues by their use counts, so after other handles and nets have come and gone a new stream may land on
-    // the lane's own queue -- the side work then serialises with the lane and the events cost on top (49.3 instead of 43.4 ms per
-    // 4 096-env update inside bench.py's shard leg, where lane 0 and its side stream shared queue 3; without it 45.7).  The HIP API does
-    // not name a stream's queue, so up to five candidates are TIMED against the lane -- two 60 us waits side by side take 60 us on two
-    // queues and 120 on one -- and the first that runs beside it is kept.  (Streams of another priority, or more than four queues,
-    // are no way out: kernels of extra queues of one process interleave with ~40 us per 5 us kernel: 72 and 61 ms.)
-    {
-        const char *e = getenv("GRL_NET_IDX_SIDE");
-        const bool want = !(cfg->reserved & GRL_NET_F_SINGLE_STREAM) && !(e && (!strcmp(e, "off") || !strcmp(e, "0"))) && rc == GRL_OK;
-        if (want && side_stream_pick(n) == GRL_OK && n->side_stream[0]) {
-            const bool ok = hipEventCreateWithFlags(&n->ev_side0[0], hipEventDisableTiming) == hipSuccess &&
-                            hipEventCreateWithFlags(&n->ev_side1[0], hipEventDisableTiming) == hipSuccess &&
-                            hipEventCreateWithFlags(&n->ev_side2[0], hipEventDisableTiming) == hipSuccess;
-            n->idx_side = ok ? 1 : 0;
-        }
-        (void)hipGetLastError();
-    }
+    if (rc == GRL_OK) { n->nlanes = nlanes; side_stream_setup(n); } else (void)hipGetLastError();      // (either way the thread's last error is cleared here)
     if (rc == GRL_OK && hipFuncSetAttribute((const void *)expand_conv2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)EXP2_LDS_BYTES) != hipSuccess)
         rc = paac_fail(n, GRL_E_HIP, "hipFuncSetAttribute(expand_conv2_kernel)");
@@ -1164,9 +1065,7 @@ int grl_net_destroy(grl_net *n) {
     }
     for (int k = 0; k < GRL_MAX_LANES; ++k) {
         if (n->side_stream[k]) { hipStreamSynchronize(n->side_stream[k]); hipStreamDestroy(n->side_stream[k]); }
-        if (n->ev_side0[k]) hipEventDestroy(n->ev_side0[k]);
-        if (n->ev_side1[k]) hipEventDestroy(n->ev_side1[k]);
-        if (n->ev_side2[k]) hipEventDestroy(n->ev_side2[k]);
+        for (hipEvent_t e : {n->ev_side0[k], n->ev_side1[k], n->ev_side2[k]}) if (e) hipEventDestroy(e);
     }
     if (n->ev_fork) hipEventDestroy(n->ev_fork);
     paac_free(n);
@@ -1295,18 +1194,22 @@ static int download_heads(grl_net *n, int B, float *mu_host, float *sigma_host, 
     return GRL_OK;
 }
 
+// forward over device observations and the heads to the host; a pass that left the fp16 range runs once more on the fp32 form
+static int predict_checked(grl_net *n, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, int n_envs, float *mu_host, float *sigma_host,
+                           float *vs_host) {
+    for (int again = 0;; ++again) {
+        int rc = forward_all(n, lb, ab, pos, n_envs, n->mu, n->sigma, n->vs);
+        if (rc) return rc;
+        rc = download_heads(n, n_envs * 10, mu_host, sigma_host, vs_host);
+        if (rc != GRL_E_RANGE || again || !range_fall_back(n)) return rc;
+    }
+}
+
 int grl_net_predict(grl_net *n, float *mu_host, float *sigma_host, float *vs_host) {
     if (!n) return GRL_E_INVALID;
     hipSetDevice(n->h->cfg.device_id);
     grl_handle *h = n->h;
-    int rc = forward_all(n, h->sw.lbins, h->sw.abins, h->sw.pos, h->E, n->mu, n->sigma, n->vs);
-    if (rc) return rc;
-    rc = download_heads(n, h->E * 10, mu_host, sigma_host, vs_host);
-    if (rc == GRL_E_RANGE && range_fall_back(n)) {      // once more on the fp32 form
-        if ((rc = forward_all(n, h->sw.lbins, h->sw.abins, h->sw.pos, h->E, n->mu, n->sigma, n->vs))) return rc;
-        rc = download_heads(n, h->E * 10, mu_host, sigma_host, vs_host);
-    }
-    return rc;
+    return predict_checked(n, h->sw.lbins, h->sw.abins, h->sw.pos, h->E, mu_host, sigma_host, vs_host);
 }
 
 int grl_net_predict_obs(grl_net *n, int32_t n_envs, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, float *mu_host,
@@ -1318,14 +1221,7 @@ int grl_net_predict_obs(grl_net *n, int32_t n_envs, const uint8_t *lb, const uin
     PAAC_HIP(n, hipMemcpyAsync(n->tmp_lb, lb, (size_t)n_envs * 160, hipMemcpyHostToDevice, n->h->stream));
     PAAC_HIP(n, hipMemcpyAsync(n->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, n->h->stream));
     PAAC_HIP(n, hipMemcpyAsync(n->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, n->h->stream));
-    rc = forward_all(n, n->tmp_lb, n->tmp_ab, n->tmp_pos, n_envs, n->mu, n->sigma, n->vs);
-    if (rc) return rc;
-    rc = download_heads(n, n_envs * 10, mu_host, sigma_host, vs_host);
-    if (rc == GRL_E_RANGE && range_fall_back(n)) {
-        if ((rc = forward_all(n, n->tmp_lb, n->tmp_ab, n->tmp_pos, n_envs, n->mu, n->sigma, n->vs))) return rc;
-        rc = download_heads(n, n_envs * 10, mu_host, sigma_host, vs_host);
-    }
-    return rc;
+    return predict_checked(n, n->tmp_lb, n->tmp_ab, n->tmp_pos, n_envs, mu_host, sigma_host, vs_host);
 }
 
 int grl_net_debug_obs_index(grl_net *n, int32_t n_envs, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, uint32_t *host, size_t bytes) {

@@ -97,34 +97,20 @@ static int eval_grow(grl_net *net, T **p, size_t count) {
 
 static int eval_reserve(grl_net *net, size_t steps, size_t envs, size_t norm, size_t act, size_t trace) {
     NetEval &v = net->ev;
-    int rc;
-    if (steps > v.cap_steps) {
-        v.cap_steps = 0;
-        if ((rc = eval_grow(net, &v.rewards, steps))) return rc;
-        v.cap_steps = steps;
-    }
+    int rc = GRL_OK;
+    auto G = [&](auto **p, size_t cnt) { if (rc == GRL_OK) rc = eval_grow(net, p, cnt); };
+    // a capacity reads 0 while its buffers are being replaced, and stays there when one of them fails
+    if (steps > v.cap_steps) { v.cap_steps = 0; G(&v.rewards, steps); if (rc) return rc; v.cap_steps = steps; }
     if (envs > v.cap_envs) {
-        v.cap_envs = 0;
-        if ((rc = eval_grow(net, &v.length, envs)) || (rc = eval_grow(net, &v.finished, envs)) || (rc = eval_grow(net, &v.alive, envs)) ||
-            (rc = eval_grow(net, &v.envact, envs * 20)))
-            return rc;
+        v.cap_envs = 0; G(&v.length, envs); G(&v.finished, envs); G(&v.alive, envs); G(&v.envact, envs * 20);
+        if (rc) return rc;
         v.cap_envs = envs;
     }
-    if (norm > v.cap_norm) {
-        v.cap_norm = 0;
-        if ((rc = eval_grow(net, &v.normals, norm * 20))) return rc;
-        v.cap_norm = norm;
-    }
-    if (act > v.cap_act) {
-        v.cap_act = 0;
-        if ((rc = eval_grow(net, &v.actions, act * 20))) return rc;
-        v.cap_act = act;
-    }
+    if (norm > v.cap_norm) { v.cap_norm = 0; G(&v.normals, norm * 20); if (rc) return rc; v.cap_norm = norm; }
+    if (act > v.cap_act) { v.cap_act = 0; G(&v.actions, act * 20); if (rc) return rc; v.cap_act = act; }
     if (trace > v.cap_trace) {
-        v.cap_trace = 0;
-        if ((rc = eval_grow(net, &v.tr_mu, trace * 20)) || (rc = eval_grow(net, &v.tr_sigma, trace * 20)) || (rc = eval_grow(net, &v.tr_raw, trace * 20)) ||
-            (rc = eval_grow(net, &v.tr_value, trace * 10)))
-            return rc;
+        v.cap_trace = 0; G(&v.tr_mu, trace * 20); G(&v.tr_sigma, trace * 20); G(&v.tr_raw, trace * 20); G(&v.tr_value, trace * 10);
+        if (rc) return rc;
         v.cap_trace = trace;
     }
     return GRL_OK;
@@ -154,11 +140,12 @@ static int eval_enqueue(grl_net *net, int S, int greedy, bool drawn_host, bool k
         PAAC_HIP(net, hipMemsetAsync(v.tr_value, 0, (size_t)S * 40, h->stream));
     }
     // the lanes, as grl_net_rollout deals them: chunk c always runs on lane c % nl, one fork (behind the fills above), one join
-    int rc = lanes_fork(net);
+    LanePass pass(net);
+    int rc = pass.begin();
     if (rc) return rc;
     const int nl = lanes_active(net);
     net->side_now = nchunks == 1;      // one chunk per step: lane 0's side stream takes the forward's index kernels
-    struct SideOff { grl_net *n; ~SideOff() { n->side_now = 0; } } side_off{net};
+    SideOff side_off{net};
     EvalStep P{};
     P.mu = net->mu; P.sigma = net->sigma; P.vs = net->vs;
     P.normals = drawn_host ? v.normals : nullptr;
@@ -175,19 +162,16 @@ static int eval_enqueue(grl_net *net, int S, int greedy, bool drawn_host, bool k
             bind_activations(net, -1);
             rc = forward_chunk(net, h->sw.lbins + (size_t)e0 * 160, h->sw.abins + (size_t)e0 * 20, h->sw.pos + (size_t)e0 * 20, ne,
                                net->mu + (size_t)e0 * 20, net->sigma + (size_t)e0 * 20, net->vs + (size_t)e0 * 10);
-            if (rc) { (void)lanes_join(net); return rc; }
+            if (rc) return rc;
             P.i0 = e0 * 10; P.n = ne * 10; P.t = t;
             P.counter = (uint32_t)(net->act_counter + (unsigned long)t);      // the rollout's key; the counter itself stays
             P.done_count = h->done_count + net->cur_lane;
             hipLaunchKernelGGL(eval_action_kernel, dim3((ne * 10 + 255) / 256), dim3(256), 0, st, P);
-            if ((rc = swarm_launch_step_range(h, v.envact, e0, ne, net->cur_lane, true))) {
-                (void)lanes_join(net);
-                return paac_fail(net, rc, h->err);
-            }
+            if ((rc = swarm_launch_step_range(h, v.envact, e0, ne, net->cur_lane, true))) return paac_fail(net, rc, h->err);
             hipLaunchKernelGGL(eval_account_kernel, dim3((ne + 255) / 256), dim3(256), 0, st, (const double *)h->sw.reward64, (const uint8_t *)h->done, e0,
                                ne, S, t, v.rewards, v.length, v.finished, v.alive);
         }
-    if ((rc = lanes_join(net))) return rc;
+    if ((rc = pass.finish())) return rc;
     PAAC_HIP(net, hipGetLastError());
     return GRL_OK;
 }

@@ -1222,7 +1222,7 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
     if (side) {      // (enqueued behind the trunk's kernels: the queues are served in the order their work arrives)
         hipStream_t ss = net->side_stream[net->cur_lane];
         PAAC_HIP(net, hipStreamWaitEvent(ss, net->ev_side0[net->cur_lane], 0));
-        net->h->stream = ss;      // slot_index / patch_sort enqueue on the handle's current stream
+        StreamScope on_side(net->h, ss);      // slot_index / patch_sort enqueue on the handle's current stream; every way out of this block puts st back
         int rc = slot_index(net, pos, n);
         if (rc == GRL_OK) {
             const int nb = (n + 255) / 256;
@@ -1239,7 +1239,6 @@ static int forward_conv12_shared(grl_net *net, const uint8_t *lb, const uint8_t 
                 net->pitem_on_side = rc == GRL_OK;
             }
         }
-        net->h->stream = st;
         if (rc) return rc;
     }
     if (side) {      // the main stream goes on when the side stream's lists are there

@@ -694,13 +694,13 @@ static int ensure_train_bufs(grl_net *net) {
     if (net->train_ready) return GRL_OK;
     size_t c = net->chunk;
     int rc = GRL_OK;
-    auto A = [&](float **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(net, p, cnt); };
+    auto A = [&](auto **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(net, p, cnt); };
     if (!net->shared_trunk) { A(&net->ga1, c * 12800); A(&net->ga2, c * 5184); A(&net->ga3, c * 3136); }
     A(&net->gd1, c * 512); A(&net->gd2, c * 256); A(&net->gp1, c * 512 * 2); net->gv1 = net->gp1 + c * 512; A(&net->gv2, c * 256);
     if (!net->w3t) { A(&net->w3t, 576 * 64); A(&net->w2t, 4 * 256 * 32); }      // shared by the lanes (read-only during a pass)
     A(&net->dz2, (c / 10) * 5184); A(&net->gt, (c / 10) * 12800);
     A(&net->gsl, c * 9 * 64); A(&net->dza, c * 9 * 64); A(&net->dz3sh, (c / 10) * 3136); A(&net->tmpw3, 576 * 64);
-    if (rc == GRL_OK) rc = paac_alloc(net, &net->t2desc, (size_t)4 * net->npad);
+    A(&net->t2desc, (size_t)4 * net->npad);
     A(&net->dl2, (size_t)4 * net->npad * 32); A(&net->tt2, (size_t)4 * net->npad * 32);
     A(&net->tmpw2, 4 * 256 * 32);
     A(&net->gd1sh, (c / 10) * 512); A(&net->gsh3, (c / 10) * 3136); A(&net->g3p, c * 1600); A(&net->dz3p, c * 1600);
@@ -723,7 +723,7 @@ static int ensure_train_bufs(grl_net *net) {
     }
     A(&net->slab1b, (size_t)3 * 2048 * 64);      // agent_dz3, agent_dz2, agent_ds: a region each
     A(&net->cfold, (size_t)kFoldParts * 32);
-    if (rc == GRL_OK) rc = paac_alloc(net, &net->slab64, kSlab64Doubles + 4096);
+    A(&net->slab64, kSlab64Doubles + 4096);
     A(&net->ro_mu, c * (3 * (size_t)net->ho.A + net->ho.dz + 3));      // cmu csigma cvs dzh cact cadv cy
     if (rc == GRL_OK) net->train_ready = true;
     return rc;
@@ -1340,7 +1340,8 @@ static int backward_chunk_body(grl_net *net, const TrainBufs &tb, const uint8_t 
     return rq_flush(net);
 }
 
-// prepares every active lane (buffers, zeroed gradient accumulator and loss sums); lane 0 is current afterwards
+// prepares every active lane (buffers, zeroed gradient accumulator and loss sums); lane 0 is current afterwards.  It makes lanes
+// current itself (no fork yet): its callers hold a LanePass from before the call
 static int train_begin(grl_net *net, TrainBufs *tb) {
     static_assert(sizeof(double) == 8, "");
     const size_t c = net->chunk;
@@ -1385,7 +1386,7 @@ static int train_scale_and_fork(grl_net *net, float inv_total) {
     return lanes_fork(net);
 }
 
-// lane 1's gradient accumulator and loss sums folded into lane 0's (fixed order: deterministic)
+// lane k's gradient accumulator and loss sums folded into lane 0's (one launch per lane, k = 1, 2, ...: a fixed order, deterministic)
 __global__ void lane_fold_kernel(float *__restrict__ g0, const float *__restrict__ g1, long n, double *__restrict__ s0,
                                  const double *__restrict__ s1) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1394,9 +1395,10 @@ __global__ void lane_fold_kernel(float *__restrict__ g0, const float *__restrict
 }
 
 // joins the lanes, folds their gradient accumulators and loss sums into lane 0's (fixed order) and removes the loss scale
-static int train_fold(grl_net *net, const TrainBufs *tbs) {
+static int train_fold(LanePass<grl_net> &pass, const TrainBufs *tbs) {
+    grl_net *net = pass.net;
     const int nl = lanes_active(net);
-    int jrc = lanes_join(net);
+    int jrc = pass.finish();
     if (jrc) return jrc;
     for (int k = 1; k < nl; ++k)
         hipLaunchKernelGGL(lane_fold_kernel, dim3((unsigned)((net->ho.total + 255) / 256)), dim3(256), 0, net->h->stream, net->grads,
@@ -1466,35 +1468,30 @@ static int train_apply(grl_net *net, float inv_total, float lr, int apply_update
     return paac_read_stats(net, stats_host);
 }
 
-static int train_finish(grl_net *net, const TrainBufs *tbs, float inv_total, float lr, int apply_update, float *stats_host) {
-    int rc = train_fold(net, tbs);
+// reduce: 0 = local statistics only (no all-reduce; the caller applies nothing)
+static int train_finish(LanePass<grl_net> &pass, const TrainBufs *tbs, float inv_total, float lr, int apply_update, float *stats_host, int reduce = 1) {
+    grl_net *net = pass.net;
+    int rc = train_fold(pass, tbs);
     if (rc) return rc;
     net->last_inv_total = inv_total;
     float grad_scale = 1.0f;
     // the GEMMs' range words [flag, largest |output| of the fp32 form as float bits: non-negative floats order like their bits] travel
     // with the gradient (max over ranks): a rank whose pass overflowed makes EVERY replica skip the update and fail the call, instead
     // of erroring alone and leaving its peers blocked in the next collective
-    if ((rc = paac_allreduce_grads(net, net->grads, range_flag_ptr(net), &grad_scale))) return rc;
+    if (reduce && (rc = paac_allreduce_grads(net, net->grads, range_flag_ptr(net), &grad_scale))) return rc;
     return train_apply(net, inv_total, lr, apply_update, grad_scale, stats_host);
 }
 
 static int ensure_rollout_bufs(grl_net *net, int T) {
     const int E = net->h->E, B = E * 10;
     if (net->ro_lb && net->T >= T) return GRL_OK;
-    int rc;
-    if ((rc = paac_alloc(net, &net->ro_lb, (size_t)T * E * 160))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_ab, (size_t)T * E * 20))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_pos, (size_t)T * E * 20))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_act, (size_t)T * B * 2))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_envact, (size_t)B * 2))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_val, (size_t)T * B))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_rew, (size_t)T * B))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_y, (size_t)T * B))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_adv, (size_t)T * B))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_boot, (size_t)B))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_done, (size_t)T * E))) return rc;
-    if ((rc = paac_alloc(net, &net->ro_pmu, (size_t)T * B * 2))) return rc;      // the policy the actions were drawn from: the gradient
-    if ((rc = paac_alloc(net, &net->ro_psg, (size_t)T * B * 2))) return rc;      // step bounds its head gradients with it (loss scale)
+    const size_t TE = (size_t)T * E, TB = (size_t)T * B;
+    int rc = GRL_OK;
+    auto A = [&](auto **p, size_t cnt) { if (rc == GRL_OK) rc = paac_alloc(net, p, cnt); };
+    A(&net->ro_lb, TE * 160); A(&net->ro_ab, TE * 20); A(&net->ro_pos, TE * 20); A(&net->ro_act, TB * 2); A(&net->ro_envact, (size_t)B * 2);
+    A(&net->ro_val, TB); A(&net->ro_rew, TB); A(&net->ro_y, TB); A(&net->ro_adv, TB); A(&net->ro_boot, (size_t)B); A(&net->ro_done, TE);
+    A(&net->ro_pmu, TB * 2); A(&net->ro_psg, TB * 2);      // the policy the actions were drawn from: the gradient step bounds its head gradients with it (loss scale)
+    if (rc) return rc;
     net->T = T; net->B = B;
     // rollout-resident activations when they fit (with headroom for the training workspace and RCCL)
     if (net->keep) { (void)hipFree(net->keep); net->keep = nullptr; net->keep_slots = 0; }
@@ -1555,10 +1552,11 @@ int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
     // the lanes never wait for each other inside the rollout: the fp64 VALU-bound env step and the memory-bound helper kernels of
     // one chunk overlap the MFMA GEMMs of the others, and there is ONE join, before the returns.  (A lock-step rollout -- forward
     // of all chunks, join, one env step over the whole batch, per time step -- left the matrix pipe idle during every env step.)
-    if ((rc = lanes_fork(net))) return rc;
+    LanePass pass(net);
+    if ((rc = pass.begin())) return rc;
     const int nl = lanes_active(net);
     net->side_now = nchunks == 1;      // one chunk per step: nothing hides the forward's index kernels -- lane 0's side stream takes them
-    struct SideOff { grl_net *n; ~SideOff() { n->side_now = 0; } } side_off{net};
+    SideOff side_off{net};
     const unsigned long counter0 = net->act_counter;
     net->act_counter += (unsigned long)T;
     for (int t = 0; t <= T; ++t)
@@ -1571,14 +1569,14 @@ int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
                 bind_activations(net, -1);
                 rc = forward_chunk(net, h->sw.lbins + (size_t)e0 * 160, h->sw.abins + (size_t)e0 * 20, h->sw.pos + (size_t)e0 * 20, ne,
                                    net->mu + (size_t)e0 * 20, net->sigma + (size_t)e0 * 20, net->ro_boot + (size_t)e0 * 10);
-                if (rc) { (void)lanes_join(net); return rc; }
+                if (rc) return rc;
                 continue;
             }
             bind_activations(net, net->keep_version >= 0 ? (long)t * nchunks + c : -1);
             rc = forward_chunk(net, h->sw.lbins + (size_t)e0 * 160, h->sw.abins + (size_t)e0 * 20, h->sw.pos + (size_t)e0 * 20, ne,
                                net->ro_pmu + ((size_t)t * B + (size_t)e0 * 10) * 2, net->ro_psg + ((size_t)t * B + (size_t)e0 * 10) * 2,
                                net->ro_val + (size_t)t * B + (size_t)e0 * 10);
-            if (rc) { (void)lanes_join(net); return rc; }
+            if (rc) return rc;
             // states[t] = shared_states (paac.py:319): the sampling launch also keeps the compact observation the action was chosen from
             // and zeroes the lane's done counter for the step that follows
             ObsRecord rec{reinterpret_cast<const uint32_t *>(h->sw.lbins + (size_t)e0 * 160), reinterpret_cast<const uint32_t *>(h->sw.abins + (size_t)e0 * 20),
@@ -1589,14 +1587,12 @@ int grl_net_rollout(grl_net *net, int32_t T, int32_t reward_layout) {
                                net->ro_psg + (size_t)t * B * 2, e0 * 10, ne * 10, h->cfg.seed,
                                (uint32_t)h->cfg.env_id_offset, (uint32_t)(counter0 + (unsigned long)t), net->ro_act + (size_t)t * B * 2, net->ro_envact, rec);
             if ((rc = swarm_launch_step_range(h, net->ro_envact, e0, ne, net->cur_lane, true)) ||
-                (rc = episodes_launch_account(h, e0, ne))) {      // R6 (paac.py:331-349), when enabled on the handle
-                (void)lanes_join(net);
+                (rc = episodes_launch_account(h, e0, ne)))      // R6 (paac.py:331-349), when enabled on the handle
                 return paac_fail(net, rc, h->err);
-            }
             hipLaunchKernelGGL(reward_layout_kernel, dim3((ne * 10 + 255) / 256), dim3(256), 0, st, h->reward, e0, ne, reward_layout,
                                net->ro_rew + (size_t)t * B, (const uint8_t *)h->done, net->ro_done + (size_t)t * E);
         }
-    if ((rc = lanes_join(net))) return rc;
+    if ((rc = pass.finish())) return rc;
     // n-step returns over all columns (paac.py:360-372)
     if ((rc = launch_returns(h, net->ro_rew, net->ro_val, nullptr, net->ro_boot, T, B, net->cfg.gamma, 1.0f, net->cfg.scale, 0.f, 0.f,
                              net->ro_y, net->ro_adv)))
@@ -1617,17 +1613,16 @@ static int train_rollout_impl(grl_net *net, float lr, float *stats_host, int fin
     hipSetDevice(h->cfg.device_id);
     net->ht_train_t0 = host_now_ms();
     TrainBufs tb[GRL_MAX_LANES];
+    LanePass pass(net);
     int rc = train_begin(net, tb);
-    if (rc) { (void)lanes_join(net); return rc; }
+    if (rc) return rc;
     const int E = h->E, B = E * 10, T = net->T, ce = net->chunk / 10;
     const float inv_total = 1.0f / ((float)T * (float)B);
     const int nchunks = (E + ce - 1) / ce, nl = lanes_active(net);
     // same parameters as during the rollout (paac.py:302-387), so its mu / sigma / values are the gradient step's
     if ((rc = train_bound_rows(net, net->ro_pmu, net->ro_psg, net->ro_val, net->ro_act, net->ro_adv, net->ro_y, (long)T * B)) ||
-        (rc = train_scale_and_fork(net, inv_total))) {
-        (void)lanes_join(net);
+        (rc = train_scale_and_fork(net, inv_total)))
         return rc;
-    }
     const bool resident = net->keep && net->keep_version >= 0 && net->keep_version == net->param_version;
     net->resident_last = resident ? 1 : 0;      // grl_net_keep_info
     long ci = 0;
@@ -1635,16 +1630,14 @@ static int train_rollout_impl(grl_net *net, float lr, float *stats_host, int fin
         for (int e0 = 0; e0 < E; e0 += ce, ++ci) {
             int ne = E - e0 < ce ? E - e0 : ce;
             size_t s0 = (size_t)t * B + (size_t)e0 * 10;
-            use_lane(net, (int)(ci % nl));      // independent chunks alternate between the streams
+            use_lane(net, (int)(ci % nl));      // independent chunks go round the lanes
             rc = backward_chunk(net, tb[net->cur_lane], net->ro_lb + ((size_t)t * E + e0) * 160, net->ro_ab + ((size_t)t * E + e0) * 20,
                                 net->ro_pos + ((size_t)t * E + e0) * 20, ne, net->ro_act + s0 * 2, net->ro_adv + s0, net->ro_y + s0,
                                 inv_total, resident ? (long)t * nchunks + e0 / ce : -1, net->ro_pmu + s0 * 2, net->ro_psg + s0 * 2, net->ro_val + s0);
-            if (rc) { (void)lanes_join(net); return rc; }
+            if (rc) return rc;
         }
-    if (finish) return train_finish(net, tb, inv_total, lr, 1, stats_host);
-    if ((rc = train_fold(net, tb))) return rc;
-    net->last_inv_total = inv_total;
-    return train_apply(net, inv_total, 0.f, 0, 1.0f, stats_host);
+    const int apply_update = finish, reduce = finish;      // finish == 0: fold and local statistics only, nothing reduced or applied
+    return train_finish(pass, tb, inv_total, apply_update ? lr : 0.f, apply_update, stats_host, reduce);
 }
 
 // A gradient step that left the fp16 range (GRL_E_RANGE from train_apply: Adam was skipped on the device, nothing changed) switches
@@ -1695,18 +1688,22 @@ static int train_obs_impl(grl_net *net, int32_t n_envs, const uint8_t *lb, const
     PAAC_HIP(net, hipMemcpyAsync(net->tmp_ab, ab, (size_t)n_envs * 20, hipMemcpyHostToDevice, st0));
     PAAC_HIP(net, hipMemcpyAsync(net->tmp_pos, pos, (size_t)n_envs * 20, hipMemcpyHostToDevice, st0));
     TrainBufs tb[GRL_MAX_LANES];
-    if ((rc = train_begin(net, tb))) { (void)lanes_join(net); return rc; }
+    LanePass pass(net);      // from here on every way out joins: lane 0 and the handle's own stream are current again
+    if ((rc = train_begin(net, tb))) return rc;
     const int ce = net->chunk / 10, nl = lanes_active(net);
     const float inv_total = 1.0f / (float)(n_envs * 10);
+    // a chunk's actions, advantages and targets into lane buffers t, on stream st
+    auto stage = [&](const TrainBufs &t, size_t s0, int ne, hipStream_t st) {
+        hipError_t e = hipMemcpyAsync(t.cact, actions + s0 * net->ho.A, (size_t)ne * 10 * net->ho.A * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.cadv, advantages + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.cy, critic_target + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st);
+        return e == hipSuccess ? GRL_OK : paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(e));
+    };
     // the loss scale needs the heads of every sample before the first backward pass: one forward sweep on lane 0
     for (int e0 = 0; e0 < n_envs; e0 += ce) {
         const int ne = n_envs - e0 < ce ? n_envs - e0 : ce;
-        const size_t s0 = (size_t)e0 * 10;
         const TrainBufs &t = tb[0];
-        hipError_t ce = hipMemcpyAsync(t.cact, actions + s0 * net->ho.A, (size_t)ne * 10 * net->ho.A * 4, hipMemcpyHostToDevice, st0);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(t.cadv, advantages + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st0);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(t.cy, critic_target + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st0);
-        if (ce != hipSuccess) return paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(ce));
+        if ((rc = stage(t, (size_t)e0 * 10, ne, st0))) return rc;
         bind_activations(net, -1);
         if ((rc = forward_chunk(net, net->tmp_lb + (size_t)e0 * 160, net->tmp_ab + (size_t)e0 * 20, net->tmp_pos + (size_t)e0 * 20, ne, t.cmu,
                                 t.csigma, t.cvs)) ||
@@ -1714,25 +1711,20 @@ static int train_obs_impl(grl_net *net, int32_t n_envs, const uint8_t *lb, const
             return rc;
         PAAC_HIP(net, hipStreamSynchronize(st0));      // host staging buffers are reused by the next chunk
     }
-    if ((rc = train_scale_and_fork(net, inv_total))) { (void)lanes_join(net); return rc; }
+    if ((rc = train_scale_and_fork(net, inv_total))) return rc;
     for (int e0 = 0; e0 < n_envs; e0 += ce) {
         int ne = n_envs - e0 < ce ? n_envs - e0 : ce;
-        size_t s0 = (size_t)e0 * 10;
         use_lane(net, (e0 / ce) % nl);
         hipStream_t st = net->h->stream;
         const TrainBufs &t = tb[net->cur_lane];
-        // every error exit after use_lane() goes through lanes_join(): it restores the handle's stream and lane 0
-        hipError_t ce = hipMemcpyAsync(t.cact, actions + s0 * net->ho.A, (size_t)ne * 10 * net->ho.A * 4, hipMemcpyHostToDevice, st);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(t.cadv, advantages + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(t.cy, critic_target + s0, (size_t)ne * 10 * 4, hipMemcpyHostToDevice, st);
-        rc = ce == hipSuccess ? backward_chunk(net, t, net->tmp_lb + (size_t)e0 * 160, net->tmp_ab + (size_t)e0 * 20,
-                                               net->tmp_pos + (size_t)e0 * 20, ne, t.cact, t.cadv, t.cy, inv_total)
-                              : paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipMemcpyAsync: ") + hipGetErrorString(ce));
-        if (rc == GRL_OK && (ce = hipStreamSynchronize(st)) != hipSuccess)      // host staging buffers are reused by the next chunk
-            rc = paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipStreamSynchronize: ") + hipGetErrorString(ce));
-        if (rc) { (void)lanes_join(net); return rc; }
+        if ((rc = stage(t, (size_t)e0 * 10, ne, st)) ||
+            (rc = backward_chunk(net, t, net->tmp_lb + (size_t)e0 * 160, net->tmp_ab + (size_t)e0 * 20, net->tmp_pos + (size_t)e0 * 20, ne, t.cact,
+                                 t.cadv, t.cy, inv_total)))
+            return rc;
+        if (hipError_t e = hipStreamSynchronize(st))      // host staging buffers are reused by the next chunk
+            return paac_fail(net, GRL_E_HIP, std::string("grl_net_train_obs: hipStreamSynchronize: ") + hipGetErrorString(e));
     }
-    return train_finish(net, tb, inv_total, lr, apply_update, stats_host);
+    return train_finish(pass, tb, inv_total, lr, apply_update, stats_host);
 }
 
 int grl_net_train_obs(grl_net *net, int32_t n_envs, const uint8_t *lb, const uint8_t *ab, const uint8_t *pos, const float *actions,
