@@ -226,7 +226,7 @@ int grl_create(const grl_config *cfg, grl_handle **out) {
     h->prof_on = false; h->prof_used = 0;
     h->ep_total = nullptr; h->ep_len = nullptr; h->ep_steps = nullptr; h->ep_rec = nullptr; h->ep_count = nullptr; h->ep_capacity = 0;
     h->stream = nullptr; h->ev0 = nullptr; h->ev1 = nullptr;
-    h->sw = {}; h->so = {}; h->tr = {}; h->tk = {}; h->swp = {}; h->rpl = {}; h->srl = {}; h->spl = {}; h->ssr = {}; h->scp = {}; h->tsw = {}; h->tfs = {}; h->ksw = {}; h->kse = {}; h->kfs = {}; h->sdp = {};
+    h->sw = {}; h->so = {}; h->tr = {}; h->tk = {}; h->swp = {}; h->rpl = {}; h->srl = {}; h->spl = {}; h->ssr = {}; h->scp = {}; h->tsw = {}; h->tfs = {}; h->tse = {}; h->ksw = {}; h->kse = {}; h->kfs = {}; h->sdp = {};
     int rc = GRL_OK;
     auto bail = [&](int code) {
         g_create_error = h->err;

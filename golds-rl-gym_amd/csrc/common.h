@@ -100,6 +100,19 @@ struct TradeForesightState {
     int n_horizons, max_steps, trace_env;                // of the last call; n_horizons == 0: none yet
 };
 
+// grl_trade_search (trade_search.hip); cap_gc counts (generation, candidate) pairs, cap_gen generations + 1
+struct TradeSearchState {
+    double *normals;                                     // (cap_gc,4): the host's normals
+    float *cand;                                         // (cap_gc,4): the rows as played; generation g's table is the evaluation's at g * C
+    double *fit;                                         // (cap_gc)
+    int32_t *order;                                      // (cap_gc)
+    double *scores;                                      // (cap_scores): (G, C, E)
+    double *mean, *std;                                  // (cap_gen,4) each
+    float *tape;                                         // (cap_tape)
+    size_t cap_gc, cap_scores, cap_gen, cap_tape;
+    int G, C;                                            // of the last run; G == 0: none yet
+};
+
 // grl_ticker_sweep (ticker_sweep.hip)
 struct TickerSweepState {
     PairStats stats;
@@ -250,6 +263,7 @@ struct grl_handle {
     grl::SwarmCemPlanState scp;
     grl::TradeSweepState tsw;
     grl::TradeForesightState tfs;
+    grl::TradeSearchState tse;
     grl::TickerSweepState ksw;
     grl::TickerSearchState kse;
     grl::TickerForesightState kfs;

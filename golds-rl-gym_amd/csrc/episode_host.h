@@ -1,5 +1,5 @@
 // The host scaffold the whole-episode launches share (solow_sweep.hip, trade_sweep.hip, trade_foresight.hip, ticker_sweep.hip,
-// ticker_foresight.hip, solow_dp.hip, swarm_replay.hip, swarm_rules.hip, swarm_plan.hip, swarm_search.hip, swarm_cemplan.hip, ticker_search.hip): one copy of what their entry points do alike -- the opening checks, the
+// ticker_foresight.hip, solow_dp.hip, swarm_replay.hip, swarm_rules.hip, swarm_plan.hip, swarm_search.hip, swarm_cemplan.hip, ticker_search.hip, trade_search.hip): one copy of what their entry points do alike -- the opening checks, the
 // argument checks with the entry point's name in the message, growing a capacity group of buffers, the profiled launch and the
 // table-driven grl_*_read.  The kernels, their parameter structs and what a launch uploads and clears stay in the .hip files; the
 // device half of the per-pair statistics six of them keep (RewardStats, PairStats) is the sibling header episode_dev.h; the checks

@@ -314,14 +314,20 @@ __device__ __forceinline__ TradeStepOut trade_step_env(const TradeParams &R, int
 // trade_asset_trade for each, then trade_account_settle once.
 
 // the scripted rule (include/goldsrl_tradesweep.h): clip(bias - gain * (p - 1), -1, 1) in float64, one IEEE operation per line,
-// rounded to the float32 action the env is stepped with
-__device__ __forceinline__ float trade_rule_action(double gain, double bias, double p) {
-    const double d = p - 1.0;
-    const double m = gain * d;
+// rounded to the float32 action the env is stepped with (trade_rule_action, below its four-number form).
+// the four-number rule of the search (include/goldsrl_tradesearch.h): a gain for each side of a reference level `ref`, the side a
+// select on the sign of p - ref (d == 0 takes gain_sell; m is 0 either way).  The same one-operation lines; with gain_buy ==
+// gain_sell the select has one operand and ref = 1.0 makes the lines trade_rule_action's, which is that call.
+__device__ __forceinline__ float trade_rule4_action(double gain_buy, double gain_sell, double bias, double ref, double p) {
+    const double d = p - ref;
+    const double g = d < 0.0 ? gain_buy : gain_sell;
+    const double m = g * d;
     double x = bias - m;
     x = fmin(fmax(x, -1.0), 1.0);
     return (float)x;
 }
+
+__device__ __forceinline__ float trade_rule_action(double gain, double bias, double p) { return trade_rule4_action(gain, gain, bias, 1.0, p); }
 
 // one asset's trade: buys are sized from the cash before any purchase of this step; cost and value accumulate in asset order
 __device__ __forceinline__ void trade_asset_trade(float actf, int n, double cash, double p, double &q, double &cost, double &value) {

@@ -1,7 +1,7 @@
 // The statements of a cross-entropy search that know nothing of the env whose rule is searched (the numbering is that of
 // include/goldsrl_swarmsearch.h and include/goldsrl_tickersearch.h: 1 and 2 the clamp and the draw, 6 the fit's sum, 7 rank, 8 refit),
 // and the host's checks of what every such search takes: the counts, the per-parameter vectors, the normals, the output sizes.  One
-// copy for swarm_search.hip, swarm_cemplan.hip and ticker_search.hip (through swarm_search_dev.h and ticker_search_dev.h, which add
+// copy for swarm_search.hip, swarm_cemplan.hip, ticker_search.hip and trade_search.hip (through their *_search_dev.h, which add
 // their rule's row and box), so a tie rule, a message or the refit is changed in one place and the searches cannot drift apart.
 // Every including file is compiled with -ffp-contract=off.
 #pragma once

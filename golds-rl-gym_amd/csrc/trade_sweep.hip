@@ -16,9 +16,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
-#include "rng.h"
-#include "flat_env_dev.h"
+#include "trade_sweep_dev.h"
 #include "episode_host.h"
 #include "../../include/goldsrl_tradesweep.h"
 
@@ -32,84 +30,48 @@ struct TradeSweepOut {
     double *trace_a;
 };
 
+// what the sweep keeps of a lane's RPL pairs: the statistics of the step rewards, the trace of one env, the final account
+template <int RPL>
+struct TradeSweepSink {
+    RewardStats rs[RPL];
+    const TradeSweepOut &O;
+    size_t E;
+    int env, r0, n_rules, max_steps;
+    bool trace;
+    __device__ __forceinline__ void step(int j, int t, float rew, double assets) {
+        rs[j].add(rew);
+        if (trace && r0 + j < n_rules) {
+            O.trace_r[(size_t)(r0 + j) * max_steps + t] = rew;
+            O.trace_a[(size_t)(r0 + j) * max_steps + t] = assets;
+        }
+    }
+    __device__ __forceinline__ void finish(int j, int length, bool finished, bool depleted, double assets) {
+        if (r0 + j < n_rules) {
+            const size_t o = (size_t)(r0 + j) * E + env;
+            O.stats.store(o, rs[j], length, finished);
+            O.final_assets[o] = assets; O.depleted[o] = depleted ? 1 : 0;
+        }
+    }
+};
+
+// the step loop is trade_sweep_play's (trade_sweep_dev.h), which the search's evaluation instantiates too
 template <int RPL, int NT>
 __global__ __launch_bounds__(256) void trade_sweep_kernel(TradeParams R, const float *__restrict__ gains, const float *__restrict__ biases,
                                                           int n_rules, const float *__restrict__ tape, int max_steps, int trace_env,
                                                           TradeSweepOut O) {
     extern __shared__ double tsw_lds[];
-    constexpr bool REG = NT > 0;
-    constexpr int NR = REG ? NT : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
     const int env = blockIdx.x * 64 + lane;
     const int r0 = (blockIdx.y * waves + wave) * RPL;          // wave-uniform
     if (r0 >= n_rules || env >= R.E) return;
-    const size_t E = R.E;
-    const int n = R.n, pairs = (n + 1) / 2;
-
-    double pr[NR], qr[RPL][NR];
-    double *col = tsw_lds + (size_t)wave * (1 + RPL) * n * 64 + lane;      // LDS form: p at col[a * 64], q of rule j at col[((1 + j) * n + a) * 64]
-    auto P = [&](int a) -> double & { if constexpr (REG) return pr[a]; else return col[(size_t)a * 64]; };
-    auto Q = [&](int j, int a) -> double & { if constexpr (REG) return qr[j][a]; else return col[((size_t)(1 + j) * n + a) * 64]; };
-
-    double gain[RPL], bias[RPL], cash[RPL], assets[RPL];
-    RewardStats rs[RPL];
-    int length[RPL];
-    bool live[RPL], finished[RPL], depleted[RPL];
-    const double cash0 = R.cash[env], assets0 = R.assets[env];
+    TradeRule2 U[RPL];
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
         const int r = r0 + j < n_rules ? r0 + j : n_rules - 1;             // a ragged tail replays the last rule and stores nothing
-        gain[j] = (double)gains[r]; bias[j] = (double)biases[r];
-        cash[j] = cash0; assets[j] = assets0;
-        length[j] = 0; live[j] = true; finished[j] = false; depleted[j] = false;
+        U[j].gain = (double)gains[r]; U[j].bias = (double)biases[r];
     }
-    trade_for<NT>(n, [&](int a) {
-        P(a) = R.p[a * E + env];
-        const double q0 = R.q[a * E + env];
-#pragma unroll
-        for (int j = 0; j < RPL; ++j) Q(j, a) = q0;
-    });
-    const uint32_t st0 = R.nstep[env];
-    const int el0 = R.elapsed[env];
-    const bool trace = env == trace_env;
-
-    for (int t = 0; t < max_steps; ++t) {
-        const bool last = R.max_steps > 0 && el0 + t + 1 >= R.max_steps;   // the TimeLimit ends every rule of the env at this step
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < RPL; ++j) {
-            if (!live[j]) continue;
-            double cost = 0.0, value = 0.0;
-            const double c = cash[j];
-            trade_for<NT>(n, [&](int a) {
-                const double p = P(a);
-                trade_asset_trade(trade_rule_action(gain[j], bias[j], p), n, c, p, Q(j, a), cost, value);
-            });
-            bool dep;
-            const float rew = trade_account_settle(cash[j], assets[j], cost, value, dep);
-            rs[j].add(rew);
-            length[j] = t + 1;
-            if (trace && r0 + j < n_rules) {
-                O.trace_r[(size_t)(r0 + j) * max_steps + t] = rew;
-                O.trace_a[(size_t)(r0 + j) * max_steps + t] = assets[j];
-            }
-            depleted[j] = dep;
-            finished[j] = dep || last;
-            live[j] = !finished[j];
-            any |= live[j];
-        }
-        if (!any || t + 1 == max_steps) break;
-        // _price_transition of every asset, once for all rules of the lane
-        trade_prices_step<NT>(R, tape, env, st0, t, pairs, [&](int a) { return P(a); }, [&](int a, double p) { P(a) = p; });
-    }
-#pragma unroll
-    for (int j = 0; j < RPL; ++j) {
-        if (r0 + j < n_rules) {
-            const size_t o = (size_t)(r0 + j) * E + env;
-            O.stats.store(o, rs[j], length[j], finished[j]);
-            O.final_assets[o] = assets[j]; O.depleted[o] = depleted[j] ? 1 : 0;
-        }
-    }
+    TradeSweepSink<RPL> S{{}, O, (size_t)R.E, env, r0, n_rules, max_steps, env == trace_env};
+    trade_sweep_play<RPL, NT>(R, U, tape, env, tsw_lds + (size_t)wave * (1 + RPL) * R.n * 64 + lane, max_steps, S);
 }
 
 // rules per lane: 2 is the measured best of 1 / 2 / 4 at 9 rules x 1 024 steps x 8 192 envs (4.40 / 3.32 / 5.03 ms at 2 assets,

@@ -1,5 +1,5 @@
 """What the bindings of the whole-episode launches (_ffi_sweep, _ffi_tradesweep, _ffi_tradeforesight, _ffi_tickersweep,
-_ffi_tickerforesight, _ffi_solowdp, _ffi_replay, _ffi_swarmrules, _ffi_swarmplan, _ffi_swarmsearch, _ffi_swarmcemplan, _ffi_tickersearch) do alike: the max_steps default and its refusal, trace_env as the C side takes it, the read-back
+_ffi_tickerforesight, _ffi_solowdp, _ffi_replay, _ffi_swarmrules, _ffi_swarmplan, _ffi_swarmsearch, _ffi_swarmcemplan, _ffi_tickersearch, _ffi_tradesearch) do alike: the max_steps default and its refusal, trace_env as the C side takes it, the read-back
 of a table of outputs, and the moments of the step rewards.  Nothing here loads the library."""
 import numpy as np
 

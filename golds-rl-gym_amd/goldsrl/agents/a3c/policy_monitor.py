@@ -27,6 +27,7 @@ import time
 import numpy as np
 
 ENVS = ("Solow-%d-%d-finite-eval-v0", "TradeAR1-v0")
+TRADE_TUNE_SEED = 1693      # of the engine PolicyMonitor.search_baseline tunes on: the eval registration's 1692 is the monitor's own
 
 
 def make_eval_engine(env, n_envs, device_id=0, max_episode_steps=1024):
@@ -256,6 +257,56 @@ class PolicyMonitor(_DeviceMonitor):
                 if got is not None and got != exp:
                     raise ValueError("%s = %r, the device net of %s has %r" % (name, got, env, exp))
         self._adopt(net, own, summary_writer, max_episode_steps)
+
+    def search_baseline(self, generations=8, candidates=32, elites=8, starts=None, tune_seed=TRADE_TUNE_SEED, **search_kw):
+        """The tuned rule (goldsrl/baselines.py:TradeRuleSearch): the four numbers (gain_buy, gain_sell, bias, ref) a cross-entropy
+        search finds, every generation in one call.  The eval engine's price generator moves on between evaluations, so there is
+        no fixed set of episodes to tune on: the FIRST call tunes, on a second eval-style TradeAR1 engine of the same n_envs
+        and n_assets with its own seed (tune_seed) -- and so does a later call whose arguments differ from those the kept rule
+        was tuned with --, and keeps search_baseline_rule, search_baseline_in_sample_total_reward (its fit
+        there) and every start's (start, rule, fit) in search_baseline_results.  EVERY call then resets the monitor's own engine
+        and plays the kept rule on it (_ffi_tradesearch.trade_search_play): called directly before eval_once, as rule_baseline()
+        is, it plays exactly the episodes that evaluation plays -- four numbers fitted in sample, played out of sample.  Keeps
+        search_baseline_total_reward, the unit of eval/mean_total_reward, and every env's total in search_baseline_totals; leaves
+        the engine reset.  starts: a list of start rules (default: the best default rule on the tuning engine, lifted to (g, g, b,
+        1)).  The scalars of rule_baseline() and trade_ceiling() are not touched.  Measured at the registration's 2 assets (64 envs x
+        256 steps, LABNOTES AC) the tuned rule gains 0.010 in sample and nothing on other seeds, so expect a total near
+        rule_baseline()'s here; at 16 assets it keeps 0.07 out of sample.  Returns (rule, search_baseline_total_reward)."""
+        from ... import _ffi, _ffi_tradesearch
+        from ...baselines import TradeRuleSearch
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_TRADE:
+            raise ValueError("the TradeAR1 rule search exists for the TradeAR1 env only")
+        asked = (int(generations), int(candidates), int(elites), None if starts is None else np.asarray(starts, np.float32).tobytes(),
+                 int(tune_seed), sorted((k, np.asarray(v).tobytes() if v is not None else None) for k, v in search_kw.items()))
+        if getattr(self, "_search_baseline_asked", None) != asked:
+            tuned_on = _ffi.Engine(_ffi.ENV_TRADE, self.n_envs, device_id=eng.cfg.device_id, seed=int(tune_seed), n_assets=eng.cfg.n_assets,
+                                   max_episode_steps=self.max_episode_steps)
+            try:
+                tuned_on.reset()
+                b = TradeRuleSearch(tuned_on, generations, candidates, elites, starts=starts, max_episode_steps=self.max_episode_steps,
+                                    **search_kw)
+                self.search_baseline_rule, self.search_baseline_in_sample_total_reward = b.best()
+                self.search_baseline_results = b.results
+                self._search_baseline_asked = asked
+            finally:
+                tuned_on.close()
+        eng.reset()
+        self.search_baseline_totals = _ffi_tradesearch.trade_search_play(eng, self.search_baseline_rule, self.max_episode_steps)
+        self.search_baseline_total_reward = _ffi_tradesearch.fit_mean(self.search_baseline_totals)
+        return self.search_baseline_rule, self.search_baseline_total_reward
+
+    def write_search_baseline_scalars(self, global_step):
+        """eval/search_baseline_total_reward, eval/mean_total_reward_minus_search_baseline of the last evaluation and
+        eval/search_baseline_in_sample_total_reward (after search_baseline())"""
+        w, total = self.summary_writer, getattr(self, "search_baseline_total_reward", None)
+        if w is None or total is None:
+            return
+        w.add_scalar("eval/search_baseline_total_reward", total, global_step)
+        if self.log["mean_total_reward"]:
+            w.add_scalar("eval/mean_total_reward_minus_search_baseline", self.log["mean_total_reward"][-1] - total, global_step)
+        w.add_scalar("eval/search_baseline_in_sample_total_reward", self.search_baseline_in_sample_total_reward, global_step)
+        w.flush()
 
 
 class GatedPolicyMonitor(_DeviceMonitor):

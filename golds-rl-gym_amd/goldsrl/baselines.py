@@ -45,7 +45,13 @@ AND may pick any rule of the family.  No counterpart either.
 TickerRuleSearch is the Ticker env's counterpart of SwarmRuleSearch: the best six numbers of the banded-target rule family a
 cross-entropy search finds from the best default rule (or from a list of starts), every generation in one call
 (include/goldsrl_tickersearch.h), and that rule played on another engine: tuned on the training table, played on the held-out
-one.  No counterpart either."""
+one.  No counterpart either.
+
+TradeRuleSearch is TradeAR1's counterpart: the best four numbers (gain_buy, gain_sell, bias, ref) of a rule family that gives each
+side of the trade a gain of its own and lets the level prices revert to move, found by a cross-entropy search from the best default
+rule (or from a list of starts), every generation in one call (include/goldsrl_tradesearch.h), and that rule played on another
+engine: tuned on one set of seeds, played on another.  It stands between TradingRuleBaseline and TradeForesightCeiling.  No
+counterpart either."""
 import numpy as np
 
 REFERENCE_RATES = np.linspace(0.05, 0.95, 20)       # constant_solow.py:19
@@ -306,6 +312,62 @@ class TradeForesightCeiling(_EngineBaseline):
         s = self._stats()
         return [(int(h), float(s["total"][i].mean()), float(s["length"][i].mean()), float(s["trades"][i].mean()))
                 for i, h in enumerate(self.horizons)]
+
+
+class TradeRuleSearch(_EngineBaseline):
+    """The best rule of the four-number family near a start: a cross-entropy search over (gain_buy, gain_sell, bias, ref),
+    `generations` generations of `candidates` candidates refitted over `elites` elites, every candidate's episode on every env of
+    the engine, all enqueued in one call (include/goldsrl_tradesearch.h; the scheme is written there).  starts=None plays
+    TradingRuleBaseline over `rules` on the same envs first and starts from its best rule (gain, bias) lifted to (gain, gain, bias,
+    1), which is that rule bit for bit; starts: a list of start rules instead, one call per start, the best found rule kept and
+    every start's result reported in `results`.  Candidate 0 of every generation is the best so far, so a found rule is never
+    below its start on the envs it was tuned on.  Tuned on one engine and played on one with another seed (play_on) it is the
+    yardstick "four numbers fitted in sample, played out of sample".  spread, floor, lo, hi: None for
+    _ffi_tradesearch.trade_search_defaults of each start.  run() plays from the engine's CURRENT state and leaves it as it was, the
+    price generator's counters included; it does not reset.  No counterpart in the reference."""
+
+    def __init__(self, engine, generations=8, candidates=32, elites=8, starts=None, seed=0, spread=None, floor=None, lo=None, hi=None,
+                 normals=None, rules=DEFAULT_TRADE_RULES, max_episode_steps=None):
+        from ._ffi_tradesearch import check_trade_rule4
+        self._open(engine, "ENV_TRADE", "the TradeAR1 rule search exists for the TradeAR1 env only")
+        self._steps(max_episode_steps)
+        self.starts = None if starts is None else np.array([check_trade_rule4("TradeRuleSearch", r) for r in np.asarray(starts, np.float32).reshape(-1, 4)])
+        self.rules = np.asarray(rules, np.float32)
+        self.generations, self.candidates, self.elites, self.seed, self.normals = int(generations), int(candidates), int(elites), seed, normals
+        self.box = {"spread": spread, "floor": floor, "lo": lo, "hi": hi}
+        self.start_total = None                       # the table's best total, when the start came from the table
+        self.results = None
+
+    def run(self, tape=None):
+        """Search from every start; keeps `results`, one (start, best_rule, best_fit) row per start in the order given, and returns
+        (and keeps) the outputs of _ffi_tradesearch.trade_search for the start whose found rule is best (the first on a tie).
+        tape: the price normals, as TradingRuleBaseline.run's `normals`."""
+        from . import _ffi_tradesearch as S
+        if self.starts is None:
+            b = TradingRuleBaseline(self.eng, self.rules, self.max_episode_steps)
+            b.run(normals=tape)
+            _, (gain, bias), self.start_total = b.best_total()
+            self.starts = np.array([(gain, gain, bias, 1.0)], np.float32)
+        self.results, self.stats = [], None
+        for start in self.starts:
+            out = S.trade_search(self.eng, start, generations=self.generations, candidates=self.candidates, elites=self.elites,
+                                 seed=self.seed, normals=self.normals, max_steps=self.max_episode_steps, tape=tape, **self.box)
+            self.results.append((tuple(float(v) for v in start), out["best_rule"], out["best_fit"]))
+            if self.stats is None or out["best_fit"] > self.stats["best_fit"]:
+                self.stats = out
+        return self.stats
+
+    def best(self):
+        """((gain_buy, gain_sell, bias, ref), the mean over the envs of its episode's total reward where it was tuned)."""
+        s = self._stats()
+        return s["best_rule"], s["best_fit"]
+
+    def play_on(self, other_engine, rule=None, tape=None):
+        """The mean over the envs of other_engine of the total reward of the found rule (or `rule`), played from that engine's
+        CURRENT state for this search's episode length (_ffi_tradesearch.trade_search_play): the found rule out of sample.  The
+        mean is the search's fit statement (adds in env order, one division), so on the engine it was tuned on it is best()[1]."""
+        from . import _ffi_tradesearch as S
+        return S.fit_mean(S.trade_search_play(other_engine, self.best()[0] if rule is None else rule, self.max_episode_steps, tape))
 
 
 def _ticker_rules():

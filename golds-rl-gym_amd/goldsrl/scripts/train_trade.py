@@ -10,7 +10,12 @@ scripted trading rules of goldsrl/baselines.py play the same episodes directly b
 rule is logged, eval/baseline_total_reward and eval/mean_total_reward_minus_baseline are written.  With --ceiling the foresight
 traders of goldsrl/baselines.py:TradeForesightCeiling play the same episodes directly before every evaluation too (one more call):
 the mean total of every horizon is logged, eval/ceiling_total_reward -- the trader who knows every row of its episode -- is written,
-and with --baseline also eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline).  Training is untouched."""
+and with --baseline also eval/mean_total_reward_share_of_gap = (mean - baseline) / (ceiling - baseline).  With --search-baseline
+G[:C[:K]] the four-number rule of goldsrl/baselines.py:TradeRuleSearch is tuned once, before the first evaluation, on a second
+eval-style engine with its own seed (G generations of C candidates, K elites, one device call) and played on the eval envs directly
+before every evaluation: the rule and both totals are logged, eval/search_baseline_total_reward,
+eval/mean_total_reward_minus_search_baseline and eval/search_baseline_in_sample_total_reward are written; the scalars of --baseline
+and --ceiling are left alone.  Training is untouched."""
 import argparse
 import logging
 import os
@@ -21,6 +26,7 @@ import numpy as np
 
 from goldsrl import _ffi, _ffi_gauss
 from goldsrl.agents.a3c.policy_monitor import PolicyMonitor
+from goldsrl.scripts.swarm_rules import search_arg
 from goldsrl.utils_tfevents import EventFileWriter
 
 logging.basicConfig(stream=sys.stdout, level=logging.INFO)
@@ -45,6 +51,11 @@ def get_arg_parser():
                    help="play the foresight traders on the eval envs directly before every evaluation (one more call) and write "
                         "eval/ceiling_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap (needs --eval-every and "
                         "--eval-envs)")
+    p.add_argument("--search-baseline", "--search_baseline", dest="search_baseline", type=search_arg, default=None, metavar="G[:C[:K]]",
+                   help="tune the four-number rule once on a second eval-style engine (G generations of C candidates, default 32, K "
+                        "elites, default 8), play it on the eval envs directly before every evaluation and write "
+                        "eval/search_baseline_total_reward, eval/mean_total_reward_minus_search_baseline and "
+                        "eval/search_baseline_in_sample_total_reward (needs --eval-every and --eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -60,6 +71,8 @@ def parse_args(argv=None):
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
     if args.ceiling and not (args.eval_envs > 0 and args.eval_every > 0):
         parser.error("--ceiling plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
+    if args.search_baseline and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--search-baseline plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
     return args
 
 
@@ -102,8 +115,15 @@ def main(argv=None):
                 monitor.trade_ceiling()
                 logging.info("TradeAR1 foresight on the eval envs, mean total_reward by rows known ahead: %s",
                              ", ".join("%s %.6g" % ("whole episode" if h == 0 else str(h), tot) for h, tot, _, _ in monitor.ceiling_table))
+            if args.search_baseline:    # tuned once on other seeds; played on this evaluation's prices
+                G, C, K = args.search_baseline
+                rule, total = monitor.search_baseline(G, C, K)
+                logging.info("Tuned rule (gain_buy %.6g, gain_sell %.6g, bias %.6g, ref %.6g) on the eval envs: mean total_reward %.6g "
+                             "(in sample %.6g)", *(rule + (total, monitor.search_baseline_in_sample_total_reward)))
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             monitor.write_scalars(step)
+            if args.search_baseline:
+                monitor.write_search_baseline_scalars(step)
             if args.baseline:
                 monitor.write_baseline_scalars(step)
             if args.ceiling:
