@@ -8,6 +8,7 @@
 
 #include "../../include/goldsrl.h"
 #include "../../include/goldsrl_solowdp.h"
+#include "../../include/goldsrl_tradedp.h"
 #include "episode_dev.h"
 
 namespace grl {
@@ -163,6 +164,23 @@ struct SolowDpState {
     int played, trace_steps;                      // of the last play; played == 0: none yet
 };
 
+// grl_trade_dp_* (trade_dp.hip): the tables of the solve and the buffers of the play
+struct TradeDpState {
+    grl_trade_dp_grid grid;                       // of the table in `policy`
+    double *v[2];                                 // (cap_states) each, [price node][share node]: stage j's value is in v[j & 1]
+    double *value;                                // (cap_states), [share node][price node]: the top stage's, as it is read
+    float *policy;                                // (cap_table): (horizon, [nu]^n, [nx]^n, n)
+    size_t cap_states, cap_table;
+    int horizon;                                  // horizon == 0: no table yet
+    bool has_value;                               // `value` holds V_horizon (a solve, not a set_policy)
+    PairStats stats;                              // a pair is an env here
+    double *final_assets, *trace_a;               // (cap_envs) (cap_trace)
+    uint8_t *depleted;                            // (cap_envs)
+    float *trace_act, *trace_r, *tape;            // (cap_trace, n) (cap_trace) (cap_tape)
+    size_t cap_envs, cap_trace, cap_tape;
+    int played, trace_steps;                      // of the last play; played == 0: none yet
+};
+
 // grl_swarm_replay (swarm_replay.hip)
 struct SwarmReplayState {
     uint8_t *actions;                             // (cap_act) bytes: the float64 or float32 action rows
@@ -268,6 +286,7 @@ struct grl_handle {
     grl::TickerSearchState kse;
     grl::TickerForesightState kfs;
     grl::SolowDpState sdp;
+    grl::TradeDpState tdp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;
     // R6 episode bookkeeping (grl_episodes_*): nullptr until enabled

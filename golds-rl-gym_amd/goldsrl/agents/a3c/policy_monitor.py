@@ -178,6 +178,39 @@ class _DeviceMonitor(object):
         self.ceiling_bound = c.bound()
         return self.ceiling_total_reward
 
+    def trade_optimal(self, grid=None, horizon=None):
+        """The attainable optimum (goldsrl/baselines.py:TradeOptimalBaseline) on the monitor's own TradeAR1 eval engine: the FIRST
+        call -- and a later one with another grid or horizon -- solves the env's model by backward induction, EVERY call resets
+        the engine and plays the table on it in one launch.  The engine's price generator moves on from one evaluation to the next,
+        so call this directly before eval_once, as trade_ceiling() is: it then plays exactly the episodes that evaluation plays.
+        Keeps attainable_total_reward -- the mean over the envs of the episode's total reward, the unit of eval/mean_total_reward
+        -- and the whole statistics in attainable_stats; leaves the engine reset.  Returns attainable_total_reward."""
+        from ... import _ffi
+        from ...baselines import TradeOptimalBaseline
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_TRADE:
+            raise ValueError("the attainable optimum of TradeAR1 exists for the TradeAR1 env only")
+        asked = (None if grid is None else sorted((k, np.asarray(v).tobytes()) for k, v in grid.items()), horizon)
+        if getattr(self, "_trade_optimal_asked", None) != asked:
+            self._trade_optimal = TradeOptimalBaseline(eng, grid, horizon, self.max_episode_steps)
+            self._trade_optimal_asked = asked
+        eng.reset()
+        self.attainable_stats = self._trade_optimal.run()
+        self.attainable_total_reward = self._trade_optimal.total()
+        return self.attainable_total_reward
+
+    def write_trade_optimal_scalars(self, global_step):
+        """eval/optimal_total_reward (after trade_optimal()) and, with the rule baseline's floor and an evaluation,
+        eval/mean_total_reward_share_of_attainable_gap = (mean - baseline) / (optimal - baseline) of the last evaluation"""
+        w, top = self.summary_writer, getattr(self, "attainable_total_reward", None)
+        if w is None or top is None:
+            return
+        w.add_scalar("eval/optimal_total_reward", top, global_step)
+        floor = getattr(self, "baseline_total_reward", None)
+        if floor is not None and self.log["mean_total_reward"] and top != floor:
+            w.add_scalar("eval/mean_total_reward_share_of_attainable_gap", (self.log["mean_total_reward"][-1] - floor) / (top - floor), global_step)
+        w.flush()
+
     def write_baseline_scalars(self, global_step):
         """eval/baseline_total_reward and eval/mean_total_reward_minus_baseline of the last evaluation (after baseline() or
         rule_baseline()); after optimal() also eval/optimal_total_reward and, with both ends known,

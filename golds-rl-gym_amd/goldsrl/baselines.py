@@ -314,6 +314,46 @@ class TradeForesightCeiling(_EngineBaseline):
                 for i, h in enumerate(self.horizons)]
 
 
+class TradeOptimalBaseline(_EngineBaseline):
+    """The attainable optimum of TradeAR1 (include/goldsrl_tradedp.h): the best non-anticipating policy of the env's own stochastic
+    model for 1 or 2 assets, solved once by backward induction on `grid` (a dict of _ffi_tradedp.trade_dp_grid; default: its
+    default sizes at the engine's shock) over `horizon` stages (default _ffi_tradedp.DEFAULT_HORIZON), then played on every env.
+    With more price moves left than the horizon the top row is used: the stationary rule the induction converges to.  The played
+    total is attained by a feedback rule, so it is a lower bound on what can be learned; TradeForesightCeiling's bound on the same
+    path stands above it, and the gap between the two is closed to every trader that cannot see ahead.  run() plays from the
+    engine's CURRENT state and leaves it as it was, as the other TradeAR1 baselines do; it does not reset."""
+
+    def __init__(self, engine, grid=None, horizon=None, max_episode_steps=None):
+        from . import _ffi_tradedp
+        self._open(engine, "ENV_TRADE", "the attainable optimum of TradeAR1 exists for the TradeAR1 env only")
+        if engine.cfg.n_assets > 2:
+            raise ValueError("the attainable optimum of TradeAR1 covers n_assets 1 and 2 (the grid grows by two dimensions per asset)")
+        self.horizon = _ffi_tradedp.DEFAULT_HORIZON if horizon is None else int(horizon)
+        if self.horizon < 1:
+            raise ValueError("horizon must be at least 1")
+        self.grid = _ffi_tradedp.trade_dp_grid(std_p=engine.cfg.trade_std_p) if grid is None else grid
+        self._steps(max_episode_steps)
+        self.solved = False
+
+    def solve(self):
+        """The backward induction (once per object); the engine keeps the tables."""
+        from . import _ffi_tradedp
+        if not self.solved:
+            _ffi_tradedp.trade_dp_solve(self.eng, self.grid, self.horizon, read=False)
+            self.solved = True
+
+    def run(self, trace_steps=0, normals=None):
+        """Solve if not yet solved and play the policy; returns (and keeps) the statistics of _ffi_tradedp.trade_dp_play."""
+        from . import _ffi_tradedp
+        self.solve()
+        self.stats = _ffi_tradedp.trade_dp_play(self.eng, self.max_episode_steps, trace_steps, normals)
+        return self.stats
+
+    def total(self):
+        """The mean over the envs of the episode's total reward: the unit of eval/mean_total_reward."""
+        return float(np.asarray(self._stats()["total"], np.float64).mean())
+
+
 class TradeRuleSearch(_EngineBaseline):
     """The best rule of the four-number family near a start: a cross-entropy search over (gain_buy, gain_sell, bias, ref),
     `generations` generations of `candidates` candidates refitted over `elites` elites, every candidate's episode on every env of

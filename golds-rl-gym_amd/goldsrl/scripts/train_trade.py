@@ -15,7 +15,10 @@ G[:C[:K]] the four-number rule of goldsrl/baselines.py:TradeRuleSearch is tuned 
 eval-style engine with its own seed (G generations of C candidates, K elites, one device call) and played on the eval envs directly
 before every evaluation: the rule and both totals are logged, eval/search_baseline_total_reward,
 eval/mean_total_reward_minus_search_baseline and eval/search_baseline_in_sample_total_reward are written; the scalars of --baseline
-and --ceiling are left alone.  Training is untouched."""
+and --ceiling are left alone.  With --optimal the attainable optimum of goldsrl/baselines.py:TradeOptimalBaseline -- the env's own
+model solved once by backward induction, before the first evaluation -- is played on the eval envs directly before every
+evaluation (one more launch): eval/optimal_total_reward is written and, with --baseline, eval/mean_total_reward_share_of_attainable_gap
+= (mean - baseline) / (optimal - baseline); the scalars of the other three flags are left alone.  Training is untouched."""
 import argparse
 import logging
 import os
@@ -56,6 +59,10 @@ def get_arg_parser():
                         "elites, default 8), play it on the eval envs directly before every evaluation and write "
                         "eval/search_baseline_total_reward, eval/mean_total_reward_minus_search_baseline and "
                         "eval/search_baseline_in_sample_total_reward (needs --eval-every and --eval-envs)")
+    p.add_argument("--optimal", action="store_true",
+                   help="solve the env's model once by backward induction, play the table on the eval envs directly before every "
+                        "evaluation (one more launch) and write eval/optimal_total_reward and, with --baseline, "
+                        "eval/mean_total_reward_share_of_attainable_gap (needs --eval-every and --eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -73,6 +80,8 @@ def parse_args(argv=None):
         parser.error("--ceiling plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
     if args.search_baseline and not (args.eval_envs > 0 and args.eval_every > 0):
         parser.error("--search-baseline plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
+    if args.optimal and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--optimal plays the eval envs of the device monitor: it needs --eval-every N > 0 and --eval-envs M > 0")
     return args
 
 
@@ -120,6 +129,8 @@ def main(argv=None):
                 rule, total = monitor.search_baseline(G, C, K)
                 logging.info("Tuned rule (gain_buy %.6g, gain_sell %.6g, bias %.6g, ref %.6g) on the eval envs: mean total_reward %.6g "
                              "(in sample %.6g)", *(rule + (total, monitor.search_baseline_in_sample_total_reward)))
+            if args.optimal:        # solved once; played on this evaluation's prices
+                logging.info("Attainable optimum on the eval envs: mean total_reward %.6g", monitor.trade_optimal())
             total_reward, episode_length = monitor.eval_once(net.get_params())[:2]
             monitor.write_scalars(step)
             if args.search_baseline:
@@ -128,6 +139,8 @@ def main(argv=None):
                 monitor.write_baseline_scalars(step)
             if args.ceiling:
                 monitor.write_ceiling_scalars(step)
+            if args.optimal:
+                monitor.write_trade_optimal_scalars(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d, mean over %d envs %.6g", step, total_reward,
                          episode_length, monitor.n_envs, monitor.log["mean_total_reward"][-1])
