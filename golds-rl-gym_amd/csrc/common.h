@@ -8,6 +8,7 @@
 
 #include "../../include/goldsrl.h"
 #include "../../include/goldsrl_solowdp.h"
+#include "../../include/goldsrl_solowarmadp.h"
 #include "../../include/goldsrl_tradedp.h"
 #include "episode_dev.h"
 
@@ -164,6 +165,21 @@ struct SolowDpState {
     int played, trace_steps;                      // of the last play; played == 0: none yet
 };
 
+// grl_solow_arma_dp_* (solow_arma_dp.hip): the tables of the solve and the buffers of the play
+struct SolowArmaDpState {
+    grl_solow_arma_dp_grid grid;                  // of the table in `policy`
+    double *v[2];                                 // (cap_states) each; stage t's value is in v[t & 1]
+    float *policy;                                // (cap_table): (horizon, nx[0], .., nx[m-1], nk)
+    size_t cap_states, cap_table;
+    int horizon;                                  // horizon == 0: no table yet
+    bool has_value;                               // v[0] holds stage 0's value (a solve, not a set_policy)
+    PairStats stats;                              // a pair is an env here
+    float *trace_a, *trace_r, *trace_k;           // (cap_trace) x 3
+    int32_t *err;                                 // (1)
+    size_t cap_envs, cap_trace;
+    int played, trace_steps;                      // of the last play; played == 0: none yet
+};
+
 // grl_trade_dp_* (trade_dp.hip): the tables of the solve and the buffers of the play
 struct TradeDpState {
     grl_trade_dp_grid grid;                       // of the table in `policy`
@@ -286,6 +302,7 @@ struct grl_handle {
     grl::TickerSearchState kse;
     grl::TickerForesightState kfs;
     grl::SolowDpState sdp;
+    grl::SolowArmaDpState sad;
     grl::TradeDpState tdp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;

@@ -18,6 +18,7 @@
 #include "rng.h"
 #include "flat_env_dev.h"
 #include "episode_host.h"
+#include "dp_axis.h"
 
 namespace grl {
 
@@ -30,17 +31,6 @@ struct DpArgs {
     double rho, theta, delta;
     int ne, n_states;
 };
-
-// position on a uniform axis of n points from lo in steps of `step`, clamped to the axis: the lower neighbour and the share of
-// the upper one.  A NaN lands on point 0, so the index is always inside the table.
-struct DpCoord { int i; double f; };
-__device__ __forceinline__ DpCoord dp_coord(double x, double lo, double step, int n) {
-    double u = (x - lo) / step;
-    u = fmin(fmax(u, 0.0), (double)(n - 1));
-    int i = (int)u;
-    if (i > n - 2) i = n - 2;
-    return DpCoord{i, u - (double)i};
-}
 
 // bilinear look-up in the (k, z) plane `je` of a row-major (nk, nz, ne) table
 template <typename T>

@@ -6,7 +6,8 @@ A policy that does not beat the best constant rate has learned nothing about the
 the statistics, so they run without a device.
 
 OptimalSavingsBaseline is the other end of Solow's scale: the finite-horizon optimum by backward induction on a (k, z, e) grid, one
-kernel launch per stage, and the play of the tabulated policy on the same seeded episodes (include/goldsrl_solowdp.h).  The gap
+kernel launch per stage, and the play of the tabulated policy on the same seeded episodes (include/goldsrl_solowdp.h; for the
+orders beyond p = 1, q <= 1 on the forecasts of the ARMA shock, include/goldsrl_solowarmadp.h).  The gap
 between the two is what there was to learn.  The reference has no counterpart of it.
 
 ScriptedSwarmBaseline gives Swarm the same kind of yardstick: two do-nothing scripts played on a Swarm handle in one kernel launch
@@ -152,37 +153,43 @@ class ConstantSavingsBaseline(_EngineBaseline):
 
 
 class OptimalSavingsBaseline(_EngineBaseline):
-    """The optimal savings policy of a Solow engine with p = 1 and q in {0, 1}: solved once by backward induction on `grid` (a dict
-    of _ffi_solowdp.solow_dp_grid; default 96 x 25 x 7 with 96 actions at the engine's sigma) over `horizon` stages (default 256),
-    then played on every env from its reset state.  With more steps left than the horizon the policy of stage 0 is used: the
-    stationary rule the induction converges to.  engine: a Solow engine to run on (the caller keeps it) instead of building the eval
-    registration's; run() resets it."""
+    """The optimal savings policy of a Solow engine: solved once by backward induction on `grid` over `horizon` stages, then played
+    on every env from its reset state.  With p = 1 and q in {0, 1} the induction is _ffi_solowdp's on (k, z, e) (grid: a dict of
+    solow_dp_grid; default 96 x 25 x 7 with 96 actions, 256 stages); every other order takes _ffi_solowarmadp's on the shock's
+    m = max(p, q + 1) forecasts (grid: a dict of solow_arma_dp_grid; default 48 x 9 per axis x 3 with 48 actions, 128 stages), which
+    exists for m <= 4.  With more steps left than the horizon the policy of stage 0 is used: the stationary rule the induction
+    converges to.  engine: a Solow engine to run on (the caller keeps it) instead of building the eval registration's; run() resets
+    it."""
 
     def __init__(self, env="Solow-1-1-finite-eval-v0", n_envs=1, grid=None, horizon=None, device_id=0, max_episode_steps=1024, engine=None):
-        from . import _ffi_solowdp
-        self.horizon = _ffi_solowdp.DEFAULT_HORIZON if horizon is None else int(horizon)
-        if self.horizon < 1:
-            raise ValueError("horizon must be at least 1")
+        from . import _ffi_solowarmadp, _ffi_solowdp
         self.max_episode_steps = int(max_episode_steps)
         self._own = engine is None
         self.eng = _solow_engine("the optimal-savings yardstick", env, n_envs, device_id, self.max_episode_steps, engine)
-        self.grid = _ffi_solowdp.solow_dp_grid(sigma=self.eng.cfg.solow_sigma) if grid is None else grid
+        cfg = self.eng.cfg
+        if cfg.solow_p == 1 and cfg.solow_q <= 1:
+            self._solve, self._play, default = _ffi_solowdp.solow_dp_solve, _ffi_solowdp.solow_dp_play, _ffi_solowdp.DEFAULT_HORIZON
+            self.grid = _ffi_solowdp.solow_dp_grid(sigma=cfg.solow_sigma) if grid is None else grid
+        else:
+            self._solve, self._play, default = _ffi_solowarmadp.solow_arma_dp_solve, _ffi_solowarmadp.solow_arma_dp_play, _ffi_solowarmadp.DEFAULT_HORIZON
+            self.grid = _ffi_solowarmadp.engine_grid(self.eng) if grid is None else grid
+        self.horizon = default if horizon is None else int(horizon)
+        if self.horizon < 1:
+            raise ValueError("horizon must be at least 1")
         self.solved, self.stats = False, None
 
     def solve(self):
         """The backward induction (once per object); the engine keeps the tables."""
-        from . import _ffi_solowdp
         if not self.solved:
-            _ffi_solowdp.solow_dp_solve(self.eng, self.grid, self.horizon, read=False)
+            self._solve(self.eng, self.grid, self.horizon, read=False)
             self.solved = True
 
     def run(self, trace_steps=0):
         """Solve if not yet solved, reset the envs and play the policy; returns (and keeps) the statistics of
-        _ffi_solowdp.solow_dp_play."""
-        from . import _ffi_solowdp
+        _ffi_solowdp.solow_dp_play (_ffi_solowarmadp.solow_arma_dp_play: the same outputs)."""
         self.solve()
         self.eng.reset()
-        self.stats = _ffi_solowdp.solow_dp_play(self.eng, self.max_episode_steps, trace_steps)
+        self.stats = self._play(self.eng, self.max_episode_steps, trace_steps)
         return self.stats
 
     def total(self):
