@@ -9,6 +9,7 @@
 #include "../../include/goldsrl.h"
 #include "../../include/goldsrl_solowdp.h"
 #include "../../include/goldsrl_solowarmadp.h"
+#include "../../include/goldsrl_solowforesight.h"
 #include "../../include/goldsrl_tradedp.h"
 #include "episode_dev.h"
 
@@ -180,6 +181,19 @@ struct SolowArmaDpState {
     int played, trace_steps;                      // of the last play; played == 0: none yet
 };
 
+// grl_solow_foresight (solow_foresight.hip)
+struct SolowForesightState {
+    grl_solow_foresight_grid grid;                // of the last call
+    PairStats stats;                              // a pair is an env here
+    double *value;                                // (cap_envs)
+    int32_t *clamped, *err;                       // (cap_envs) (1)
+    float *ez;                                    // (cap_path): (max_steps, E)
+    uint8_t *decisions;                           // (cap_dec): (envs of a launch, max_steps, nk)
+    float *trace_a, *trace_r, *trace_k;           // (cap_trace) x 3
+    size_t cap_envs, cap_path, cap_dec, cap_trace;
+    int played, max_steps, trace_steps, launches; // of the last call; played == 0: none yet
+};
+
 // grl_trade_dp_* (trade_dp.hip): the tables of the solve and the buffers of the play
 struct TradeDpState {
     grl_trade_dp_grid grid;                       // of the table in `policy`
@@ -303,6 +317,7 @@ struct grl_handle {
     grl::TickerForesightState kfs;
     grl::SolowDpState sdp;
     grl::SolowArmaDpState sad;
+    grl::SolowForesightState sfs;
     grl::TradeDpState tdp;
     std::vector<void *> allocs;   // everything hipMalloc'ed by the handle
     std::vector<void *> user_allocs;

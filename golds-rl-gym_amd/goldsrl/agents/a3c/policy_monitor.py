@@ -138,6 +138,30 @@ class _DeviceMonitor(object):
         eng.reset()
         return self.optimal_total_reward
 
+    def ceiling(self, grid=None):
+        """The perfect-foresight ceiling (goldsrl/baselines.py:SolowForesightCeiling) on the monitor's own Solow eval engine, so it
+        plans and plays exactly the seeded episodes the policy is evaluated on, every order, one launch.  The engine is reseeded at
+        every reset, so once is enough.  Keeps ceiling_total_reward -- the mean over the envs of the played episode's total reward,
+        the unit of eval/mean_total_reward -- and the whole outputs in ceiling_stats; leaves the engine reset.  Returns the figure."""
+        from ... import _ffi
+        from ...baselines import SolowForesightCeiling
+        eng = self.net.eng
+        if eng.kind != _ffi.ENV_SOLOW:
+            raise ValueError("the foresight ceiling of Solow exists for the Solow env only")
+        c = SolowForesightCeiling(grid=grid, max_episode_steps=self.max_episode_steps, engine=eng)
+        self.ceiling_stats = c.run()
+        self.ceiling_total_reward = c.ceiling()
+        eng.reset()
+        return self.ceiling_total_reward
+
+    def write_solow_ceiling_scalar(self, global_step):
+        """eval/ceiling_total_reward (after ceiling()) and nothing else: the scalars of baseline() and optimal() stay as they are"""
+        w, top = self.summary_writer, getattr(self, "ceiling_total_reward", None)
+        if w is None or top is None:
+            return
+        w.add_scalar("eval/ceiling_total_reward", top, global_step)
+        w.flush()
+
     def rule_baseline(self, rules=None):
         """The scripted trading-rule baseline (goldsrl/baselines.py) on the monitor's own TradeAR1 eval engine: resets it and plays
         every (env, rule) pair in one kernel launch.  The engine's price generator moves on from one evaluation to the next, so call

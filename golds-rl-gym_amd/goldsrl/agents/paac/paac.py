@@ -68,6 +68,9 @@ class PAACLearner(ActorLearner):
         optimal = bool(getattr(self, "optimal", False))
         if optimal:
             logging.info("Optimal savings policy on the eval envs: mean total_reward %.6g", self.policy_monitor.optimal())
+        ceiling = bool(getattr(self, "ceiling", False))
+        if ceiling:
+            logging.info("Foresight ceiling on the eval envs: mean total_reward %.6g", self.policy_monitor.ceiling())
         every_updates = int(getattr(self, "eval_updates", 0) or 0)
         every_seconds = float(getattr(self, "eval_every", 0.0) or 0.0)
         state = {"last_eval": time.time()}
@@ -81,6 +84,8 @@ class PAACLearner(ActorLearner):
                 self.policy_monitor.eval_once()
                 if baseline or optimal:
                     self.policy_monitor.write_baseline_scalars(int(self.global_step))
+                if ceiling:
+                    self.policy_monitor.write_solow_ceiling_scalar(int(self.global_step))
                 state["last_eval"] = time.time()
         return between_updates
 

@@ -10,6 +10,10 @@ kernel launch per stage, and the play of the tabulated policy on the same seeded
 orders beyond p = 1, q <= 1 on the forecasts of the ARMA shock, include/goldsrl_solowarmadp.h).  The gap
 between the two is what there was to learn.  The reference has no counterpart of it.
 
+SolowForesightCeiling is the top of Solow's scale, at every order: each env's own episode solved by backward induction on capital
+along the shock path its tape fixes, and played, one workgroup per env in one launch (include/goldsrl_solowforesight.h).  What lies
+between the induction's policy and it is the price of not knowing the shocks.  No counterpart either.
+
 ScriptedSwarmBaseline gives Swarm the same kind of yardstick: two do-nothing scripts played on a Swarm handle in one kernel launch
 (include/goldsrl_replay.h).  The reference has no counterpart of it.
 
@@ -195,6 +199,44 @@ class OptimalSavingsBaseline(_EngineBaseline):
     def total(self):
         """The mean over the envs of the episode's total reward: the unit of eval/mean_total_reward."""
         return float(np.asarray(self._stats()["total"], np.float64).mean())
+
+    def close(self):
+        if self._own and self.eng is not None:
+            self.eng.close()
+        self.eng = None
+
+
+class SolowForesightCeiling(_EngineBaseline):
+    """The perfect-foresight ceiling of a Solow engine at ANY order (include/goldsrl_solowforesight.h): the shock path of an episode
+    is fixed by the tape its reset drew, so every env solves its own episode by backward induction on capital alone (`grid`: a dict
+    of _ffi_solowforesight.solow_foresight_grid; default 96 k nodes x 96 rates on a range derived from the engine's delta and
+    sigma) and plays the plan, all in one launch.  The played total is attained by a plan that knows the shocks: what lies between
+    OptimalSavingsBaseline and it is the price of not knowing them, and no policy earns more than the true ceiling, which on the
+    paths measured lies between the played total and the grid's own value (value()).  engine: a Solow engine to run on (the caller
+    keeps it) instead of building the eval registration's; run() resets it."""
+
+    def __init__(self, env="Solow-1-1-finite-eval-v0", n_envs=1, grid=None, device_id=0, max_episode_steps=1024, engine=None):
+        from . import _ffi_solowforesight
+        self.max_episode_steps = int(max_episode_steps)
+        self._own = engine is None
+        self.eng = _solow_engine("the foresight ceiling of Solow", env, n_envs, device_id, self.max_episode_steps, engine)
+        self.grid = _ffi_solowforesight.solow_foresight_grid(self.eng) if grid is None else grid
+        self.stats = None
+
+    def run(self, trace_steps=0):
+        """Reset the envs, plan and play; returns (and keeps) the outputs of _ffi_solowforesight.solow_foresight."""
+        from . import _ffi_solowforesight
+        self.eng.reset()
+        self.stats = _ffi_solowforesight.solow_foresight(self.eng, self.max_episode_steps, trace_steps, self.grid)
+        return self.stats
+
+    def ceiling(self):
+        """The mean over the envs of the played episode's total reward: the unit of eval/mean_total_reward."""
+        return float(np.asarray(self._stats()["total"], np.float64).mean())
+
+    def value(self):
+        """The mean over the envs of the grid's own value V_0(k_0)."""
+        return float(np.asarray(self._stats()["value"], np.float64).mean())
 
     def close(self):
         if self._own and self.eng is not None:

@@ -42,6 +42,8 @@ def get_arg_parser():
     p.add_argument("--optimal", action="store_true",
                    help="solve the optimal savings policy by backward induction and play it on the eval envs before the first update; write "
                         "eval/optimal_total_reward and, with --baseline, eval/mean_total_reward_share_of_gap at every evaluation (needs --eval-envs)")
+    p.add_argument("--ceiling", action="store_true",
+                   help="plan and play the perfect-foresight ceiling on the eval envs before the first update (one kernel launch, any order) and write eval/ceiling_total_reward at every evaluation (needs --eval-envs)")
     p.add_argument("--lr", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--device", type=int, default=0)
@@ -57,6 +59,8 @@ def parse_args(argv=None):
         parser.error("--baseline plays the eval envs of the device monitor: it needs --eval-envs N > 0 (and --eval-every > 0)")
     if args.optimal and not (args.eval_envs > 0 and args.eval_every > 0):
         parser.error("--optimal plays the eval envs of the device monitor: it needs --eval-envs N > 0 (and --eval-every > 0)")
+    if args.ceiling and not (args.eval_envs > 0 and args.eval_every > 0):
+        parser.error("--ceiling plays the eval envs of the device monitor: it needs --eval-envs N > 0 (and --eval-every > 0)")
     return args
 
 
@@ -83,6 +87,8 @@ def main(argv=None):
         logging.info("Constant-savings baseline on the eval envs (the agent's grid): rate %.6g, mean total_reward %.6g", *monitor.baseline())
     if args.optimal:
         logging.info("Optimal savings policy on the eval envs: mean total_reward %.6g", monitor.optimal())
+    if args.ceiling:
+        logging.info("Foresight ceiling on the eval envs: mean total_reward %.6g", monitor.ceiling())
     for u in range(args.updates):
         t0 = time.time()
         net.rollout(args.t_max)
@@ -101,6 +107,8 @@ def main(argv=None):
             monitor.write_scalars(step)
             if args.baseline or args.optimal:
                 monitor.write_baseline_scalars(step)
+            if args.ceiling:
+                monitor.write_solow_ceiling_scalar(step)
             monitor.write_log(log_file)
             logging.info("Eval results at step %d: total_reward %.6g, episode_length %d", step, total_reward, episode_length)
         writer.flush()
