@@ -1,4 +1,4 @@
-// Included inside namespace grl by net_gated.hip (the Ticker gated trader), net_gauss.hip (the Gaussian Solow / TradeAR1 agent) and
+// Included inside namespace grl by net_gated.hip (the Ticker gated trader), net_gauss.hip (the Gaussian Solow / TradeAR1 agent), net_gridtrade.hip (the TradeAR1 grid trader) and
 // net_discrete.hip (the discrete savings-grid Solow agent): the device code the A3C nets share -- the LDS row layout, the GRU trunk forward and backward, the in-place dx, the window rules
 // with their per-env kernels and the update.  static / inline: every including translation unit has its own copy.  The including
 // file defines first

@@ -1,6 +1,6 @@
-// The host scaffold the A3C nets share (net_gated.hip, net_gauss.hip, net_discrete.hip): the state grl_gnet, grl_anet and grl_dnet
-// derive from and one copy of what they do alike:
-//   - the members all three own (parameters, optimizer, staging, rollout and bootstrap buffers, the evaluation's results and trace)
+// The host scaffold the A3C nets share (net_gated.hip, net_gauss.hip, net_discrete.hip, net_gridtrade.hip): the state grl_gnet, grl_anet,
+// grl_dnet and grl_gtnet derive from and one copy of what they do alike:
+//   - the members all of them own (parameters, optimizer, staging, rollout and bootstrap buffers, the evaluation's results and trace)
 //   - one list per net of its rollout buffers and one of its evaluation buffers (A3cBuf: name, slot, bytes per row), from which
 //     they are allocated (a3c_ensure_*) and read back by name (a3c_read_*): a width is written once, where the entry is made
 //   - create (a3c_create), parameter / optimizer copies, the checks and staging copies of predict / train

@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the three A3C nets share (GatedNet in _ffi_gated.py, GaussNet in _ffi_gauss.py, DiscreteNet in
-_ffi_discrete.py): the three C ABIs name the same functions behind another prefix (grl_gnet_ / grl_anet_ / grl_dnet_), with their
-heads' arrays in predict and train."""
+"""What the ctypes bindings of the four A3C nets share (GatedNet in _ffi_gated.py, GaussNet in _ffi_gauss.py, DiscreteNet in
+_ffi_discrete.py, GridTradeNet in _ffi_gridtrade.py): the C ABIs name the same functions behind another prefix (grl_gnet_ / grl_anet_ /
+grl_dnet_ / grl_gtnet_), with their heads' arrays in predict and train."""
 import ctypes as C
 
 import numpy as np

@@ -3,11 +3,13 @@ GaussianPolicyEstimator (:241-334) and ValueEstimator (:338-417) on the shared r
 parameters, as the reference's two graphs share the "shared" variable scope).  The gated trader (goldsrl._ffi_gated.GatedNet)
 exists for the Ticker sizes only: 2 assets x 3 choices, static input 7, temporal rows 4; the Gaussian agent
 (goldsrl._ffi_gauss.GaussNet) for the Solow sizes (2, 2, 1 action) and the 2-asset TradeAR1 sizes (5, 5, 2 actions); the discrete
-savings-grid agent (goldsrl._ffi_discrete.DiscreteNet) for the Solow sizes with one output of 2..64 choices; hidden sizes 32 / 128."""
+savings-grid agent (goldsrl._ffi_discrete.DiscreteNet) for the Solow sizes with one output of 2..64 choices; the grid trader
+(goldsrl._ffi_gridtrade.GridTradeNet) for the 2-asset TradeAR1 sizes with two outputs of 2..48 choices; hidden sizes 32 / 128."""
 import numpy as np
 
 from ..._ffi_discrete import DiscreteNet
 from ..._ffi_gauss import GaussNet
+from ..._ffi_gridtrade import GridTradeNet
 
 
 def _check_sizes(static_size, temporal_size, static_hidden_size, num_assets=2):
@@ -65,21 +67,35 @@ def _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size, n
                          "(got %r, num_outputs=%r, num_choices=%r)" % (want + (net.K, got, num_outputs, num_choices)))
 
 
+def _check_gridtrade_sizes(net, static_size, temporal_size, static_hidden_size, num_outputs=None, num_choices=None):
+    got = (static_size, temporal_size, static_hidden_size)
+    want = (net.S0, net.D, 128)
+    if got != want or (num_outputs is not None and num_outputs != net.O) or (num_choices is not None and num_choices != net.K):
+        raise ValueError("the net was built for static_size=%d, temporal_size=%d, static_hidden_size=%d, num_outputs=%d, num_choices=%d "
+                         "(got %r, num_outputs=%r, num_choices=%r)" % (want + (net.O, net.K, got, num_outputs, num_choices)))
+
+
 class DiscretePolicyEstimator(object):
-    """predict() returns the reference's key: probs, (n, num_outputs = 1, num_choices).  lb and ub are accepted as the reference's
-    constructor accepts them; it does not use them either (the grid is the worker's, the net's grid_lb / grid_ub here)."""
+    """predict() returns the reference's key: probs, (n, num_outputs, num_choices).  num_outputs = 1 binds to a DiscreteNet (the
+    Solow savings grid), num_outputs = 2 to a GridTradeNet (one grid per asset of TradeAR1).  lb and ub are accepted as the
+    reference's constructor accepts them; it does not use them either (the grid is the worker's, the net's grid_lb / grid_ub here)."""
 
     def __init__(self, num_outputs, num_choices, static_size, temporal_size, shared_layer=None, static_hidden_size=128, reuse=False,
                  trainable=True, learning_rate=1e-4, seed=None, lb=-5., ub=5., net=None):
-        if not isinstance(net, DiscreteNet):
-            raise ValueError("pass net=DiscreteNet(solow_engine, num_choices=...): the estimators are facades over one device net")
-        _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size, num_outputs, num_choices)
+        if isinstance(net, GridTradeNet):
+            _check_gridtrade_sizes(net, static_size, temporal_size, static_hidden_size, num_outputs, num_choices)
+        elif not isinstance(net, DiscreteNet):
+            raise ValueError("pass net=DiscreteNet(solow_engine, num_choices=...) or, for two outputs, net=GridTradeNet(trade_engine, "
+                             "num_choices=...): the estimators are facades over one device net")
+        else:
+            _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size, num_outputs, num_choices)
         self.net, self.num_outputs, self.num_choices = net, num_outputs, num_choices
         self.static_size, self.temporal_size, self.learning_rate = static_size, temporal_size, learning_rate
 
     def predict(self, state, history, sess=None, batch=False):
         s, h = _batch(state, _window(history, self.net.R), batch)
-        return {"probs": self.net.predict(s, h)["probs"][:, None, :]}
+        probs = self.net.predict(s, h)["probs"]
+        return {"probs": probs if probs.ndim == 3 else probs[:, None, :]}
 
 
 def _check_gauss_sizes(net, static_size, temporal_size, static_hidden_size, num_actions=None):
@@ -118,6 +134,8 @@ class ValueEstimator(object):
             _check_gauss_sizes(net, static_size, temporal_size, static_hidden_size)
         elif isinstance(net, DiscreteNet):
             _check_discrete_sizes(net, static_size, temporal_size, static_hidden_size)
+        elif isinstance(net, GridTradeNet):
+            _check_gridtrade_sizes(net, static_size, temporal_size, static_hidden_size)
         else:
             _check_sizes(static_size, temporal_size, static_hidden_size)
         if net is None:

@@ -20,7 +20,10 @@ price window at every evaluation; the table may be another one than the training
 GridPolicyMonitor is the monitor of the discrete savings-grid agent (grl_dnet_eval, include/goldsrl_discreteeval.h) on the Solow
 eval registration.  The reference's PolicyMonitor cannot evaluate that agent -- it reads preds["mu"] -- and GridSolowWorker's own
 greedy path cannot run (get_greedy_action hands the grid value to transform_raw_action, which indexes it, worker.py:370-376).  The
-rule is the evident intention: choice = the first index of the largest float32 probability, action = grid[choice]."""
+rule is the evident intention: choice = the first index of the largest float32 probability, action = grid[choice].
+
+GridTradeMonitor is the same rule per asset for the grid trader (grl_gtnet_eval, include/goldsrl_gridtradenet.h) on the TradeAR1
+eval registration, with the PolicyMonitor's TradeAR1 yardsticks."""
 import json
 import time
 
@@ -364,6 +367,29 @@ class PolicyMonitor(_DeviceMonitor):
             w.add_scalar("eval/mean_total_reward_minus_search_baseline", self.log["mean_total_reward"][-1] - total, global_step)
         w.add_scalar("eval/search_baseline_in_sample_total_reward", self.search_baseline_in_sample_total_reward, global_step)
         w.flush()
+
+
+class GridTradeMonitor(PolicyMonitor):
+    """The PolicyMonitor of the grid trader (grl_gtnet_eval, include/goldsrl_gridtradenet.h) on the TradeAR1 eval registration:
+    per asset, choice = the first index of the largest float32 probability, action = grid[choice], every episode in one launch.
+    n_grid, lb, ub: the agent's grid.  rule_baseline(), search_baseline(), trade_optimal() and trade_ceiling() are the
+    PolicyMonitor's, unchanged: call them directly before eval_once, as for the Gaussian trader.  net: an evaluation net to use
+    instead of building one (its `eng` is the eval engine)."""
+
+    def __init__(self, env="TradeAR1-v0", summary_writer=None, n_envs=1, n_grid=17, lb=-1.0, ub=1.0, max_seq_length=20, scale=1.0,
+                 device_id=0, max_episode_steps=1024, net=None):
+        own = net is None
+        if net is None:
+            from ... import _ffi_gridtrade
+            if n_envs < 1:
+                raise ValueError("n_envs must be at least 1")
+            if env != "TradeAR1-v0":
+                raise ValueError("the grid trader exists for the TradeAR1 env only (got %r)" % (env,))
+            eng = make_eval_engine(env, n_envs, device_id, int(max_episode_steps))
+            net = _ffi_gridtrade.GridTradeNet(eng, rnn_length=max_seq_length, scale=scale, num_choices=n_grid, grid_lb=lb, grid_ub=ub,
+                                              max_samples=1)
+        PolicyMonitor.__init__(self, env, summary_writer=summary_writer, max_episode_steps=max_episode_steps, net=net)
+        self._own = own
 
 
 class GatedPolicyMonitor(_DeviceMonitor):
