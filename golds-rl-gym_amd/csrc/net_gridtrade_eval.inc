@@ -9,30 +9,18 @@
 // (no value behind a terminal state) has no part here.  The workgroup leaves when none of its envs is still playing, or after
 // max_steps.
 //
-// Nothing here restates arithmetic: a3c_trunk / gt_probs_fwd / gt_softmax / gt_greedy / gt_grid, trade_step_env (flat_env_dev.h)
+// Nothing here restates arithmetic: a3c_trunk / grid_probs_fwd / grid_softmax / grid_greedy / grid_value, trade_step_env (flat_env_dev.h)
 // and a3c_window_restart / a3c_window_step are the functions the per-step rollout path runs, the trunk and the tower in the forward
 // kernel's instantiation (LOOP = false), so the two agree bit for bit.  The window, the observation and the env state stay in global
 // memory: lane l of wave 0 writes them for env l of the group, all four waves read them behind the barrier.  The two outputs'
 // choices and grid values pass from their waves to wave 0 through the O rows, which the forward uses for the value head only.
 
-struct GEvalArgs {
-    GArgs a;                            // P, o, n = E, R, K; states = the handle's processed observation (E,5), win = the net's windows
-    float *win;                         // (E,R,5), the same buffer as a.win
-    float *act;                         // (E,O) the actions each env is stepped with
-    int max_steps, trace_steps;
-    double *total;                      // (E)
-    int32_t *length;                    // (E)
-    uint8_t *finished;                  // (E)
-    float *tr_states, *tr_act, *tr_rew, *tr_done;      // (trace_steps, E, ..) or null
-    int32_t *tr_choice;
-};
-
 // With K = 48 the two outputs fill the dL/dx rows, so nothing fits behind the probabilities: the step's grid values, choices and
 // the liveness word live in the O rows, at any K.
-constexpr int L_EV_ACT = L_O, L_EV_CH = L_O + GO, L_EV_LIVE = L_O + 2 * GO;
+constexpr int L_EV_ACT = L_O, L_EV_CH = L_O + GRID_O, L_EV_LIVE = L_O + 2 * GRID_O;
 static_assert(L_EV_LIVE < L_O + 16, "the eval rows overflow the O rows");
 
-__global__ __launch_bounds__(256, 1) void gt_eval_kernel(GEvalArgs v, TradeParams S) {
+__global__ __launch_bounds__(256, 1) void gt_eval_kernel(GridEvalArgs v, TradeParams S) {
     extern __shared__ float lds[];
     float *PR = lds + L_LG * LS, *ACT = lds + L_EV_ACT * LS;
     int *CH = reinterpret_cast<int *>(lds + L_EV_CH * LS), *live = reinterpret_cast<int *>(lds + L_EV_LIVE * LS);
@@ -40,42 +28,42 @@ __global__ __launch_bounds__(256, 1) void gt_eval_kernel(GEvalArgs v, TradeParam
     const int sbase = blockIdx.x * 64, s = sbase + lane, n = v.a.n, R = v.a.R, K = v.a.K;
     const bool mine = wave == 0 && s < n;            // this lane steps env s
     const int ss = s < n ? s : n - 1;                // lanes past n stay inside their own group's rows
-    float *w = v.win + (size_t)ss * R * GD;
-    const float *obs = v.a.states + (size_t)ss * GD;
-    float *ea = v.act + (size_t)ss * GO;
+    float *w = v.win + (size_t)ss * R * GRID_D;
+    const float *obs = v.a.states + (size_t)ss * GRID_D;
+    float *ea = v.act + (size_t)ss * GRID_O;
     bool active = mine;
     double total = 0.0;
     int len = 0, k = 0;
-    if (mine) a3c_window_restart(w, R, GD, obs);     // history = [state] (policy_monitor.py:63-65)
+    if (mine) a3c_window_restart(w, R, GRID_D, obs);     // history = [state] (policy_monitor.py:63-65)
     __syncthreads();
 #pragma unroll 1
     for (int step = 0; step < v.max_steps; ++step) {
-        a3c_trunk<GD, GD, false>(v.a, lds, sbase, nullptr);
-        gt_probs_fwd<false>(v.a, lds);
-        if (wave < GO) {                             // wave o: output o of every env of the group
+        a3c_trunk<GRID_D, GRID_D, false>(v.a, lds, sbase, nullptr);
+        grid_probs_fwd<false>(v.a, lds);
+        if (wave < GRID_O) {                             // wave o: output o of every env of the group
             float *PRo = PR + wave * K * LS;
-            gt_softmax(PRo, K, lane);
-            const int ch = gt_greedy(PRo, K, lane);
+            grid_softmax(PRo, K, lane);
+            const int ch = grid_greedy(PRo, K, lane);
             CH[wave * LS + lane] = ch;
-            ACT[wave * LS + lane] = gt_grid(ch, K, v.a.lb, v.a.ub);
+            ACT[wave * LS + lane] = grid_value(ch, K, v.a.lb, v.a.ub);
         }
         __syncthreads();
         if (wave == 0) {
             if (active) {
                 const bool tr = step < v.trace_steps;
                 const size_t row = (size_t)step * n + s;
-                for (int i = 0; i < GO; ++i) ea[i] = ACT[i * LS + lane];
+                for (int i = 0; i < GRID_O; ++i) ea[i] = ACT[i * LS + lane];
                 if (tr) {
-                    for (int i = 0; i < GD; ++i) v.tr_states[row * GD + i] = obs[i];
-                    for (int i = 0; i < GO; ++i) {
-                        v.tr_choice[row * GO + i] = CH[i * LS + lane];
-                        v.tr_act[row * GO + i] = ACT[i * LS + lane];
+                    for (int i = 0; i < GRID_D; ++i) v.tr_states[row * GRID_D + i] = obs[i];
+                    for (int i = 0; i < GRID_O; ++i) {
+                        v.tr_choice[row * GRID_O + i] = CH[i * LS + lane];
+                        v.tr_act[row * GRID_O + i] = ACT[i * LS + lane];
                     }
                 }
                 const TradeStepOut o = trade_step_env(S, s, ea);
                 total += (double)o.reward;            // total_reward += reward (policy_monitor.py:80)
                 ++len;
-                k = a3c_window_step(w, R, GD, k, o.done, obs);
+                k = a3c_window_step(w, R, GRID_D, k, o.done, obs);
                 if (tr) {
                     v.tr_rew[row] = o.reward;
                     v.tr_done[row] = o.done ? 1.0f : 0.0f;

@@ -1,14 +1,15 @@
-"""The three A3C nets (gated Ticker trader; Gaussian agent on Solow and TradeAR1; discrete savings-grid agent on Solow, "grid") on
-one fixed scenario, a SHA-256 per buffer: do two builds compute the same bits?
+"""The four A3C nets (gated Ticker trader; Gaussian agent on Solow and TradeAR1; discrete savings-grid agent on Solow, "grid"; grid
+trader on the 2-asset TradeAR1, "gridtrade") on one fixed scenario, a SHA-256 per buffer: do two builds compute the same bits?
 
     python tools/a3c_bits.py [--baseline PARENT_CHECKOUT] [--json OUT]
 
 70 envs (one full 64-sample group and a group of 6, so lanes past the last sample are exercised), rnn_length 5 (gated, Solow, grid
-with 51 grid points) / 20 (TradeAR1), episodes capped at 5 steps so that dones -- the window restart and, for Solow, the terminal
-value pass -- fall inside the rollouts: rollout(3) + train_rollout twice, then eval(max_steps=8, trace_steps=8).  Hashed: every
-read_rollout buffer of the second rollout, the parameters, both RMSProp vectors and the six stats after the second update, every output of eval.  TradeAR1's
-window of 20 rows never fills in 6 steps, so its two updates carry weight 0 throughout; therefore every net also takes one host
-train(apply_update=False) on the 70 recorded samples of the last step with weights 1, 0, 1, 0, .. and both gradients are hashed.
+with 51 grid points) / 20 (TradeAR1: the Gaussian agent and the grid trader with 17 grid points per asset), episodes capped at 5
+steps so that dones -- the window restart and, for Solow, the terminal value pass -- fall inside the rollouts: rollout(3) +
+train_rollout twice, then eval(max_steps=8, trace_steps=8).  Hashed: every read_rollout buffer of the second rollout, the parameters,
+both RMSProp vectors and the six stats after the second update, every output of eval.  TradeAR1's window of 20 rows never fills in 6
+steps, so its two updates carry weight 0 throughout; therefore every net also takes one host train(apply_update=False) on the 70
+recorded samples of the last step with weights 1, 0, 1, 0, .. and both gradients are hashed.
 
 --baseline names a built checkout of the commit to compare against; the scenario then runs from it too, in a fresh process of the
 same job (this script, with --root), and every hash must be equal: the exit status says so."""
@@ -22,8 +23,8 @@ import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ENVS, CAP, RNN, GRID_K = 70, 5, {"gated": 5, "solow": 5, "trade": 20, "grid": 5}, 51
-KINDS = ("gated", "solow", "trade", "grid")
+ENVS, CAP, RNN, GRID_K, GRIDTRADE_K = 70, 5, {"gated": 5, "solow": 5, "trade": 20, "grid": 5, "gridtrade": 20}, 51, 17
+KINDS = ("gated", "solow", "trade", "grid", "gridtrade")
 ROLLOUT = {"gated": ("states", "windows", "choices", "raw", "probs", "mu", "sigma", "values", "rewards", "dones", "weights", "adv", "targets",
                      "actions", "boot"),
            "solow": ("states", "windows", "raw", "mu", "sigma", "actions", "values", "rewards", "dones", "weights", "adv", "targets",
@@ -31,15 +32,16 @@ ROLLOUT = {"gated": ("states", "windows", "choices", "raw", "probs", "mu", "sigm
            "trade": ("states", "windows", "raw", "mu", "sigma", "actions", "values", "rewards", "dones", "weights", "adv", "targets",
                      "term_values", "boot"),
            "grid": ("states", "windows", "probs", "choices", "actions", "values", "rewards", "dones", "weights", "adv", "targets",
-                    "term_values", "term_states", "term_windows", "boot")}
+                    "term_values", "term_states", "term_windows", "boot"),
+           "gridtrade": ("states", "windows", "probs", "choices", "actions", "values", "rewards", "dones", "weights", "adv", "targets", "boot")}
 # what the net's train takes between windows and weights, and what its constructor takes besides rnn_length and max_samples
 TRAIN = {"gated": ("choices", "raw", "adv", "targets"), "solow": ("raw", "adv", "targets"), "trade": ("raw", "adv", "targets"),
-         "grid": ("choices", "adv", "targets")}
-EXTRA = {"gated": {}, "solow": {"scale": 100.0}, "trade": {}, "grid": {"num_choices": GRID_K}}
+         "grid": ("choices", "adv", "targets"), "gridtrade": ("choices", "adv", "targets")}      # gridtrade's choices: (70, 2)
+EXTRA = {"gated": {}, "solow": {"scale": 100.0}, "trade": {}, "grid": {"num_choices": GRID_K}, "gridtrade": {"num_choices": GRIDTRADE_K}}
 
 
 def make(kind, root, seed=3):
-    from goldsrl import _ffi, _ffi_discrete, _ffi_gated, _ffi_gauss
+    from goldsrl import _ffi, _ffi_discrete, _ffi_gated, _ffi_gauss, _ffi_gridtrade
     if kind == "gated":
         eng = _ffi.Engine(_ffi.ENV_TICKER, ENVS, seed=seed, max_episode_steps=CAP)
         eng.ticker_set_table(np.load(os.path.join(root, "tests", "golden", "ticker.npz"))["matrix"])
@@ -53,6 +55,10 @@ def make(kind, root, seed=3):
         eng = _ffi.Engine(_ffi.ENV_SOLOW, ENVS, seed=seed, max_episode_steps=CAP)
         net = _ffi_discrete.DiscreteNet(eng, rnn_length=RNN[kind], max_samples=1, **EXTRA[kind])
         net.set_params(_ffi_discrete.default_init_discrete(seed, GRID_K))
+    elif kind == "gridtrade":
+        eng = _ffi.Engine(_ffi.ENV_TRADE, ENVS, seed=seed, n_assets=2, max_episode_steps=CAP)
+        net = _ffi_gridtrade.GridTradeNet(eng, rnn_length=RNN[kind], max_samples=1, **EXTRA[kind])
+        net.set_params(_ffi_gridtrade.default_init_gridtrade(seed, GRIDTRADE_K))
     else:
         eng = _ffi.Engine(_ffi.ENV_TRADE, ENVS, seed=seed, n_assets=2, max_episode_steps=CAP)
         net = _ffi_gauss.GaussNet(eng, rnn_length=RNN[kind], max_samples=1, **EXTRA[kind])
