@@ -203,7 +203,16 @@ __device__ __forceinline__ int grid_act(const GridArgs &a, const float *PRo, int
 
 // one launch per forward pass (predict, a rollout step, the bootstraps); with a.act: the draws or the arg-maxes and the grid
 // values.  A pass that asks for values only (the bootstraps) skips the probs tower.
-__device__ __forceinline__ void grid_forward(GridArgs a, float *lds) {
+//
+// TEACH (a second instantiation, the grid trader's teach rollout; GridNoTeach: the kernel as it always was): while waves 0 .. O-1
+// run their heads, wave 2 + o computes tt.teacher(o, s), output o's teacher action for env s, and leaves it in row 1 + o of the O
+// rows (free until the value head, which writes row 0 behind a barrier).  Behind the barrier wave o hands its own grid value and
+// the teacher's action to tt.mix, which says what the env is stepped with.
+struct GridNoTeach { static constexpr bool on = false; };
+template <typename TEACH = GridNoTeach>
+__device__ __forceinline__ void grid_forward(GridArgs a, float *lds, const TEACH &tt = TEACH()) {
+    constexpr bool teach = TEACH::on;
+    static_assert(!teach || 2 * GRID_O <= 4, "the teacher needs a wave per output beside the heads'");
     float *O = lds + L_O * LS, *PR = lds + L_LG * LS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sbase = blockIdx.x * 64, s = sbase + lane, K = a.K, OK = GRID_O * K;
     const bool valid = s < a.n;
@@ -217,6 +226,9 @@ __device__ __forceinline__ void grid_forward(GridArgs a, float *lds) {
         grid_probs_fwd<false>(a, lds);
         float *PRo = PR + (wave < GRID_O ? wave : 0) * K * LS;
         if (wave < GRID_O) grid_softmax(PRo, K, lane);
+        if constexpr (teach) {
+            if (a.act && valid && wave >= 2 && wave < 2 + GRID_O) O[(wave - 1) * LS + lane] = tt.teacher(a, wave - 2, s);
+        }
         __syncthreads();
         if (a.probs) {           // (n,O,K): the group's rows are contiguous and row o * K + j is element (o, j): coalesced
             const int cnt = (a.n - sbase < 64 ? a.n - sbase : 64) * OK;
@@ -228,7 +240,9 @@ __device__ __forceinline__ void grid_forward(GridArgs a, float *lds) {
         if (a.act && valid && wave < GRID_O) {
             const int ch = grid_act(a, PRo, wave, lane, s);
             a.choice_out[(size_t)s * GRID_O + wave] = ch;
-            a.act[(size_t)s * GRID_O + wave] = grid_value(ch, K, a.lb, a.ub);
+            const float own = grid_value(ch, K, a.lb, a.ub);
+            if constexpr (teach) a.act[(size_t)s * GRID_O + wave] = tt.mix(a, own, O[(wave + 1) * LS + lane], s);
+            else a.act[(size_t)s * GRID_O + wave] = own;
         }
     }
     if (a.vals) {                // uniform
@@ -244,20 +258,33 @@ __device__ __forceinline__ void grid_forward(GridArgs a, float *lds) {
 // The forward is recomputed per 64-sample group; with a single policy tower nothing is parked in scratch.  Wave o sums output o's
 // terms and writes its dz in place; wave 0 also the value loss.  The workgroup loops over groups blockIdx.x, + gridDim.x, ..; its
 // slab holds [policy P | value P] (cleared by the caller), reduced in a fixed order (no float atomics on gradients).
-__device__ __forceinline__ void grid_backward(GridArgs a, float *lds) {
+//
+// TEACH (a second instantiation, the supervised update): the head's gradient is the cross-entropy to a soft label on the grid, mass
+// y_lo = 1 - w on point lo and y_hi = w on lo + 1, with no advantage:
+//   policy  c * sum_o -(y_lo log(p_lo + 1e-7) + y_hi log(p_hi + 1e-7));  with r_k = y_k * p_k / (p_k + 1e-7):
+//           dz_{o,j} = c * (p_{o,j} * (r_lo + r_hi) - r_j).  A term with y_k = 0 is skipped: 0 * log never appears.
+// Value loss, entropy and the reduction are the same statements.  Agreement: the weighted count of (sample, output) pairs whose
+// arg-max (grid_greedy) is the label's heavier point, lo on a tie, summed into tl.agree.
+struct GridLabels {
+    const int32_t *lo;                  // (n,O) in [0, K - 2]
+    const float *w;                     // (n,O) in [0, 1]
+    double *agree;                      // (1), cleared by the caller
+};
+template <bool TEACH = false>
+__device__ __forceinline__ void grid_backward(GridArgs a, float *lds, GridLabels tl = GridLabels{}) {
     float *O = lds + L_O * LS, *PR = lds + L_LG * LS;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, K = a.K;
     const long Pn = a.o.total;
     float *Gp = a.slab + (size_t)blockIdx.x * 2 * Pn, *Gv = Gp + Pn;
     float *scr = a.scratch + (size_t)blockIdx.x * a3c_scratch_trunk_rows(a.R) * 64;
     const int groups = (a.n + 63) / 64;
-    double lp = 0.0, lv = 0.0, ent = 0.0, wsum = 0.0;
+    double lp = 0.0, lv = 0.0, ent = 0.0, wsum = 0.0, agree = 0.0;
     for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
         const int sbase = grp * 64, s = sbase + lane;
         const bool valid = s < a.n;
         const int ss = valid ? s : 0;
         const float wt = valid ? (a.wt ? a.wt[ss] : 1.0f) : 0.f;
-        const float c = a.mult * wt, adv = a.adv[ss], cp = c * adv;
+        const float c = a.mult * wt, adv = TEACH ? 1.0f : a.adv[ss], cp = c * adv;
         const int len = a3c_length(a.win + (size_t)ss * a.R * GRID_D, a.R, GRID_D);
         a3c_trunk<GRID_D, GRID_D, true>(a, lds, sbase, scr);
         // ---- probs tower: each output's dz over its own probabilities, in place, on its own wave
@@ -265,19 +292,45 @@ __device__ __forceinline__ void grid_backward(GridArgs a, float *lds) {
         if (wave < GRID_O) {
             float *PRo = PR + wave * K * LS;
             grid_softmax(PRo, K, lane);
-            int ch = a.choice[(size_t)ss * GRID_O + wave];
-            ch = ch < 0 ? 0 : (ch >= K ? K - 1 : ch);      // the host checks its samples; the rollout's are in range
-            const float pc = PRo[ch * LS + lane], f = cp * (pc / (pc + 1e-7f));
-            float h = 0.f;
-            for (int j = 0; j < K; ++j) {
-                const float p = PRo[j * LS + lane];
-                h += p * logf(p + 1e-7f);
-                PRo[j * LS + lane] = f * (p - (j == ch ? 1.0f : 0.0f));
-            }
-            if (valid && wt != 0.f) {      // weight-0 samples add nothing
-                lp += (double)(cp * -logf(pc + 1e-7f));
-                ent += (double)wt * (double)(-h);
-                if (wave == 0) wsum += (double)wt;
+            if constexpr (TEACH) {
+                int lo = tl.lo[(size_t)ss * GRID_O + wave];
+                lo = lo < 0 ? 0 : (lo > K - 2 ? K - 2 : lo);      // the host checks its samples; the rollout's are in range
+                const float w = tl.w[(size_t)ss * GRID_O + wave], ylo = 1.0f - w;
+                const float plo = PRo[lo * LS + lane], phi = PRo[(lo + 1) * LS + lane];
+                const bool on_lo = ylo > 0.f, on_hi = w > 0.f;
+                const float rlo = on_lo ? ylo * (plo / (plo + 1e-7f)) : 0.f, rhi = on_hi ? w * (phi / (phi + 1e-7f)) : 0.f, rs = rlo + rhi;
+                const int top = grid_greedy(PRo, K, lane);
+                float h = 0.f;
+                for (int j = 0; j < K; ++j) {
+                    const float p = PRo[j * LS + lane];
+                    h += p * logf(p + 1e-7f);
+                    const float pr = p * rs;
+                    PRo[j * LS + lane] = c * (pr - (j == lo ? rlo : (j == lo + 1 ? rhi : 0.f)));
+                }
+                if (valid && wt != 0.f) {      // weight-0 samples add nothing
+                    float ce = 0.f;
+                    if (on_lo) ce += ylo * logf(plo + 1e-7f);
+                    if (on_hi) ce += w * logf(phi + 1e-7f);
+                    lp += (double)(c * -ce);
+                    ent += (double)wt * (double)(-h);
+                    if (top == (w > 0.5f ? lo + 1 : lo)) agree += (double)wt;
+                    if (wave == 0) wsum += (double)wt;
+                }
+            } else {
+                int ch = a.choice[(size_t)ss * GRID_O + wave];
+                ch = ch < 0 ? 0 : (ch >= K ? K - 1 : ch);      // the host checks its samples; the rollout's are in range
+                const float pc = PRo[ch * LS + lane], f = cp * (pc / (pc + 1e-7f));
+                float h = 0.f;
+                for (int j = 0; j < K; ++j) {
+                    const float p = PRo[j * LS + lane];
+                    h += p * logf(p + 1e-7f);
+                    PRo[j * LS + lane] = f * (p - (j == ch ? 1.0f : 0.0f));
+                }
+                if (valid && wt != 0.f) {      // weight-0 samples add nothing
+                    lp += (double)(cp * -logf(pc + 1e-7f));
+                    ent += (double)wt * (double)(-h);
+                    if (wave == 0) wsum += (double)wt;
+                }
             }
         }
         a3c_tower3_bwd<FACT_RELU>(a.P, lds, Gp, a.o.p1w, a.o.p1b, a.o.p2w, a.o.p2b, a.o.p3w, a.o.p3b, GRID_O * K, PR, false);
@@ -301,5 +354,10 @@ __device__ __forceinline__ void grid_backward(GridArgs a, float *lds) {
         atomicAdd(&a.stats64[0], lp);
         atomicAdd(&a.stats64[2], ent);
         if (wave == 0) { atomicAdd(&a.stats64[1], lv); atomicAdd(&a.stats64[3], wsum); }
+    }
+    if constexpr (TEACH) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) agree += __shfl_xor(agree, d);
+        if (lane == 0 && wave < GRID_O) atomicAdd(tl.agree, agree);
     }
 }

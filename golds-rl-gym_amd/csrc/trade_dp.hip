@@ -27,6 +27,7 @@
 #include "rng.h"
 #include "flat_env_dev.h"
 #include "episode_host.h"
+#include "trade_dp_lookup.h"      // the table's look-up, shared with the grid trader's teacher
 
 namespace grl {
 
@@ -41,23 +42,6 @@ struct TdpArgs {
     double dx;                                   // (x_max + x_max) / (nx - 1)
     int n, NU, NX, NA, NK;                       // nu^n, nx^n, na^n, nq^n
 };
-
-// position on a uniform axis of n points, `pos` in units of the step from point 0, clamped to the axis: the lower neighbour and
-// the share of the upper one.  A NaN lands on point 0, so the index is always inside the table.
-struct TdpCoord { int i; double f; };
-__device__ __forceinline__ TdpCoord tdp_coord(double pos, int n) {
-    pos = fmin(fmax(pos, 0.0), (double)(n - 1));
-    int i = (int)pos;
-    if (i > n - 2) i = n - 2;
-    return TdpCoord{i, pos - (double)i};
-}
-
-__device__ __forceinline__ double tdp_lerp(double f, double lo, double hi) {
-    const double w = 1.0 - f;
-    const double a = w * lo;
-    const double b = f * hi;
-    return a + b;
-}
 
 // component i of the action grid: exactly -1, 0 and 1 at the ends and the middle
 __device__ __forceinline__ double tdp_action(int i, int na, double am1) { return (double)(2 * i - (na - 1)) / am1; }
@@ -206,41 +190,6 @@ __global__ __launch_bounds__(TDP_THREADS) void trade_dp_stage_kernel(TdpArgs A, 
     }
 }
 
-// the price half of the 2n-linear blend of component `comp` of one table row at share node s: axes x_0 (, x_1), the last innermost
-template <int N>
-__device__ __forceinline__ double tdp_blend_x(const float *__restrict__ row, size_t s, int NX, int nx, TdpCoord x0, TdpCoord x1, int comp) {
-    const float *b = row + s * NX * N + comp;
-    if constexpr (N == 1) {
-        return tdp_lerp(x0.f, (double)b[x0.i], (double)b[x0.i + 1]);
-    } else {
-        const float *b0 = b + ((size_t)x0.i * nx + x1.i) * 2;
-        const size_t d0 = (size_t)nx * 2;
-        const double lo = tdp_lerp(x1.f, (double)b0[0], (double)b0[2]);
-        const double hi = tdp_lerp(x1.f, (double)b0[d0], (double)b0[d0 + 2]);
-        return tdp_lerp(x0.f, lo, hi);
-    }
-}
-
-// the whole blend: the share axes u_0 (, u_1) around the price half
-template <int N>
-__device__ __forceinline__ double tdp_blend(const float *__restrict__ row, int NX, int nx, int nu, TdpCoord u0, TdpCoord u1, TdpCoord x0, TdpCoord x1, int comp) {
-    if constexpr (N == 1) {
-        return tdp_lerp(u0.f, tdp_blend_x<1>(row, u0.i, NX, nx, x0, x1, comp), tdp_blend_x<1>(row, u0.i + 1, NX, nx, x0, x1, comp));
-    } else {
-        const size_t s = (size_t)u0.i * nu + u1.i;
-        const double lo = tdp_lerp(u1.f, tdp_blend_x<2>(row, s, NX, nx, x0, x1, comp), tdp_blend_x<2>(row, s + 1, NX, nx, x0, x1, comp));
-        const double hi = tdp_lerp(u1.f, tdp_blend_x<2>(row, s + nu, NX, nx, x0, x1, comp), tdp_blend_x<2>(row, s + nu + 1, NX, nx, x0, x1, comp));
-        return tdp_lerp(u0.f, lo, hi);
-    }
-}
-
-// what the play needs of the grid: the axes of the table
-struct TdpAxes {
-    double um1, x_max, dx;
-    int nu, nx, NX;
-    size_t NS;                                   // nu^n * nx^n
-};
-
 struct TdpPlayOut {
     PairStats stats;
     double *final_assets, *trace_a;
@@ -267,26 +216,8 @@ __global__ __launch_bounds__(64) void trade_dp_play_kernel(TradeParams R_, TdpAx
     bool finished = false, depleted = false;
     for (int t = 0; t < max_steps; ++t) {
         const bool last = R.max_steps > 0 && el0 + t + 1 >= R.max_steps;
-        const int moves = R.max_steps > 0 ? R.max_steps - (el0 + t) - 1 : horizon;      // price moves left after this step
-        float act[2] = {0.f, 0.f};
-        if (moves > 0) {
-            const int rw = (moves < horizon ? moves : horizon) - 1;
-            const float *row = policy + (size_t)rw * A.NS * N;
-            double val[2] = {0.0, 0.0};
-            double W = cash;
-#pragma unroll
-            for (int a = 0; a < N; ++a) { val[a] = q[a] * p[a]; W = W + val[a]; }
-            TdpCoord cu[2] = {{0, 0.0}, {0, 0.0}}, cx[2] = {{0, 0.0}, {0, 0.0}};
-#pragma unroll
-            for (int a = 0; a < N; ++a) {
-                const double u = val[a] / W;
-                cu[a] = tdp_coord(u * A.um1, A.nu);
-                const double s = log(p[a]) + A.x_max;
-                cx[a] = tdp_coord(s / A.dx, A.nx);
-            }
-#pragma unroll
-            for (int a = 0; a < N; ++a) act[a] = (float)tdp_blend<N>(row, A.NX, A.nx, A.nu, cu[0], cu[1], cx[0], cx[1], a);
-        }
+        float act[2];
+        tdp_lookup<N>(A, policy, horizon, tdp_moves(R.max_steps, el0 + t, horizon), cash, q, p, act);      // trade_dp_lookup.h
         double cost = 0.0, value = 0.0;
         const double c0 = cash;
 #pragma unroll
@@ -365,17 +296,6 @@ static int tdp_grow_tables(grl_handle *h, size_t n_states, size_t table) {
     TradeDpState &d = h->tdp;
     const int rc = episode_reserve(h, d.cap_states, n_states, {buf(d.v[0]), buf(d.v[1]), buf(d.value)});
     return rc ? rc : episode_reserve(h, d.cap_table, table, {buf(d.policy)});
-}
-
-// TdpArgs of the table the handle keeps
-static TdpArgs tdp_kept(grl_handle *h) {
-    const grl_trade_dp_grid &g = h->tdp.grid;
-    TdpArgs A{};
-    A.g = g; A.n = h->cfg.n_assets;
-    A.NU = (int)tdp_pow(g.nu, A.n); A.NX = (int)tdp_pow(g.nx, A.n); A.NK = (int)tdp_pow(g.nq, A.n); A.NA = (int)tdp_pow(g.na, A.n);
-    A.um1 = (double)(g.nu - 1); A.am1 = (double)(g.na - 1);
-    A.dx = (g.x_max + g.x_max) / (double)(g.nx - 1);
-    return A;
 }
 
 template <int N>
@@ -466,8 +386,7 @@ int grl_trade_dp_play(grl_handle *h, const float *normals_host, int32_t max_step
         GRL_HIP(h, hipMemsetAsync(d.trace_a, 0, trace * 8, h->stream));
     }
     const TradeParams R = trade_params(h);
-    const TdpArgs K = tdp_kept(h);
-    const TdpAxes A{K.um1, K.g.x_max, K.dx, K.g.nu, K.g.nx, K.NX, (size_t)K.NU * K.NX};
+    const TdpAxes A = tdp_axes(d.grid, n);
     TdpPlayOut O{};
     O.stats = d.stats; O.final_assets = d.final_assets; O.depleted = d.depleted;
     O.trace_act = d.trace_act; O.trace_r = d.trace_r; O.trace_a = d.trace_a;
